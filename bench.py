@@ -107,8 +107,9 @@ def cpu_baseline(batch, budget_s=20.0):
     from pixelrec_amd import synth
 
     # all cores up to 32 threads: beyond that the 3.3 GB dense optimizer sweep and the intra-op thread pool stop
-    # scaling (measured on the 256-core GPU host: 256 threads ran 60x SLOWER than 8 threads on the dev container)
-    torch.set_num_threads(min(os.cpu_count() or 1, 32))
+    # scaling (measured on the 256-core GPU host: 256 threads ran 60x SLOWER than 8 threads on the dev container); a thread count
+    # the environment sets (OMP_NUM_THREADS: the CPUs this job was given) wins over the machine's core count
+    torch.set_num_threads(int(os.environ.get("OMP_NUM_THREADS") or 0) or min(os.cpu_count() or 1, 32))
     cores = torch.get_num_threads()
     params = O.synth_params(NS["n_items"], NS["D"], NS["L"], NS["n_layers"], NS["inner"], seed=1, perturb=False)
     cfg = {"n_layers": NS["n_layers"], "n_heads": NS["H"], "layer_norm_eps": 1e-12}
@@ -313,6 +314,42 @@ def emit(out):
     print(text, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: the whole dump stays under this
+DUMP_SAMPLE_SEED = 2020
+
+
+def dump_outputs(path, loss, model, write=True):
+    """--dump-outputs: what the timed path hands its caller after its LAST timed step -- the step's loss and the parameters as
+    `model.state_dict()` returns them (lazily updated table rows brought current) -- as `<path>/<name>.npy`, float32 (float64 stays
+    float64).  A tensor too large for the budget is cut to a fixed, seeded sample of its elements (sorted flat indices drawn from
+    DUMP_SAMPLE_SEED and the tensor's size alone), so two builds run with the same arguments compare output for output.  Every rank
+    calls this (the flush must happen on all replicas alike); only the one with `write` writes.  -> summary for the full record."""
+    sd = {k: v for k, v in model.state_dict().items() if v.is_floating_point()}
+    arrays = {"loss": loss.detach().reshape(1)}
+    width = 8 if any(v.dtype == torch.float64 for v in sd.values()) else 4
+    cap = (DUMP_LIMIT_BYTES - 256 * (len(sd) + 1)) // width // max(len(sd), 1)   # elements per tensor (256 B: room for a header)
+    for k, v in sd.items():
+        flat = v.detach().reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.numel(), cap, replace=False))
+            arrays[k] = flat[torch.from_numpy(idx).to(flat.device)]
+        else:
+            arrays[k] = v.detach()
+    if not write:
+        return None
+    os.makedirs(path, exist_ok=True)
+    total, sampled = 0, []
+    for k, t in arrays.items():
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        total += a.nbytes + 256
+        if t.numel() != sd.get(k, t).numel():
+            sampled.append(k)
+        np.save(os.path.join(path, f"{k}.npy"), a)
+    assert total <= DUMP_LIMIT_BYTES, total
+    return {"dir": path, "arrays": len(arrays), "bytes": total, "sampled": sampled, "sample_seed": DUMP_SAMPLE_SEED}
+
+
 def pixelnet_main(args):
     out = pixelnet_run(args, args.steps, max(args.warmup, 2))
     if out is not None:
@@ -359,12 +396,18 @@ def pixelnet_run(args, steps, warmup, init_dist=True, n_inst=3):
              torch.ones(B, L, dtype=torch.int64, device=dev)) for _ in range(2)]
     one = torch.ones((), dtype=torch.float32, device=dev)
 
+    def opt_step():
+        try:
+            opt.step()
+        except ops.H2StaleOverflow:        # (the optimizer's status poll, after the step has run: see step() below)
+            pass
+
     def eager_step(i):
         opt.zero_grad()
         loss = dp(pool[i % 2])
         loss.backward(one)
         dp.sync_gradients(defer_flat=True)
-        opt.step()
+        opt_step()
         return loss
 
     for i in range(warmup):
@@ -409,6 +452,8 @@ def pixelnet_run(args, steps, warmup, init_dist=True, n_inst=3):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dump_dir = getattr(args, "dump_outputs", None) if init_dist else None
+    dumped = dump_outputs(dump_dir, loss, m, write=rank == 0) if dump_dir else None
     # GEMM family of the step (ViT blocks + sequence block): HIP events around every launch of a few extra steps
     ev = []
     ops.GEMM_TIMING = ev
@@ -426,7 +471,7 @@ def pixelnet_run(args, steps, warmup, init_dist=True, n_inst=3):
         l_ = dp(pool[i % 2]); marks[1].record()
         l_.backward(one); marks[2].record()
         dp.sync_gradients(defer_flat=True); marks[3].record()
-        opt.step(); marks[4].record()
+        opt_step(); marks[4].record()
         torch.cuda.synchronize()
         for k, nm in enumerate(("forward (tower + sequence block + loss)", "backward (sequence block, trainable tower blocks, weight gradients)",
                                 "gradient exchange (enqueue; the flat all-reduces are joined in the optimizer)", "optimizer (both groups)")):
@@ -452,6 +497,7 @@ def pixelnet_run(args, steps, warmup, init_dist=True, n_inst=3):
                       "parallelism": f"dp{world}", "hip_graph": gstep is not None,
                       **({"hip_graph_error": graph_err} if graph_err else {})},
            "images_per_s": world * n_img * steps / dt, "final_loss": float(loss.detach()),
+           **({"dumped_outputs": dumped} if dumped else {}),
            "operands": (OPERANDS_H2 + " (every ViT block and the sequence block; rec_fc: " + OPERANDS_B3 + ")") if h2_fl else
                        (OPERANDS_B3 if ops.gemm_mode() == "bf16x3" else "f32_input_mfma"),
            "data_parallel_phases": {"ms": ph_acc, "rccl_ranks": world if (gsync is not None and getattr(gsync, "active", False)) else 1,
@@ -528,6 +574,10 @@ def main():
                     help="idnet = the headline (BASELINE configs[1]); pixelnet = SASRec PixelNet + ViT end to end "
                          "(BASELINE configs[2]: train_batch_size 16, MAX_ITEM_LIST_LENGTH 10, 352 images per step)")
     ap.add_argument("--encoder", default="clip-vit-base-patch16", help="--model pixelnet: image encoder")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (the loss and the parameters as "
+                         "state_dict() returns them; a fixed seeded sample of the large ones, <= 64 MB in all) as DIR/<name>.npy. "
+                         "The table is brought current there, so the untimed measurements after it start from a flushed table")
     args = ap.parse_args()
     launch_ranks(args)
     if args.model == "pixelnet":
@@ -650,6 +700,8 @@ def main():
     from types import SimpleNamespace
     state = SimpleNamespace(opt=opt)      # the optimizer eager_step steps (bench_extras swaps in the dense-sweep one for an A/B)
 
+    stale_overflows = [0]
+
     def eager_step(batch, nxt=None):
         state.opt.zero_grad()
         if nxt is not None and hasattr(model, "set_next_batch"):
@@ -657,10 +709,19 @@ def main():
         loss = dp(batch)
         loss.backward(one)       # preallocated d(loss)/d(loss): no ones_like fill per step
         dp.sync_gradients(defer_flat=True)
-        state.opt.step()
+        try:
+            state.opt.step()
+        except ops.H2StaleOverflow:      # the optimizer's status poll, after the step has run (see step())
+            stale_overflows[0] += 1
         return loss
 
-    stale_overflows = [0]
+    def replay(g, *b, **kw):
+        """A captured step outside step() (the six-product twin, bench_extras): an overflow report is counted like step()'s."""
+        try:
+            return g(*b, **kw)
+        except ops.H2StaleOverflow:
+            stale_overflows[0] += 1
+            return g.loss
 
     def step(i=None, record=False):
         b = next_batch()
@@ -726,6 +787,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = float(loss.detach())
+    dumped = dump_outputs(args.dump_outputs, loss, model, write=rank == 0) if args.dump_outputs else None
     # the same K steps four more times (continuing the batch stream), each block bracketed like the official one: what one run can
     # say about the spread of its own number (boxes of the pool differ by a few percent, clocks move).
     # `value` / `ms_per_step` stay the FIRST block -- the contract's timed region.
@@ -754,11 +816,11 @@ def main():
         with _env(PXR_SEQ_H2="0"):
             g6 = GraphedTrainStep(dp, opt, *pool[cursor[0] % len(pool)], lookahead=not (not args.lookahead))
             for i in range(args.warmup):
-                g6(*next_batch(), next_items=peek_items())
+                replay(g6, *next_batch(), next_items=peek_items())
             torch.cuda.synchronize()
             t6 = time.perf_counter()
             for i in range(args.steps):
-                g6(*next_batch(), next_items=peek_items())
+                replay(g6, *next_batch(), next_items=peek_items())
             torch.cuda.synchronize()
             t6 = time.perf_counter() - t6
         six = {"value": B * args.steps / t6, "unit": "sequences/s", "ms_per_step": t6 / args.steps * 1e3, "steps": args.steps,
@@ -972,6 +1034,7 @@ def main():
                    "parallelism": f"dp{world}" + ("+row-sharded-table" if args.table_sharding else ""),
                    "hip_graph": bool(use_graph), **({"hip_graph_error": graph_err} if graph_err else {})},
         "final_loss": final_loss, "host_enqueue_ms_per_step": t_enqueued / args.steps * 1e3, "h2_stale_overflows": stale_overflows[0],
+        **({"dumped_outputs": dumped} if dumped else {}),
         "spread": {"blocks": len(block_ms), "steps_per_block": args.steps, "ms_per_step": block_ms,
                    "median_ms_per_step": sorted(block_ms)[len(block_ms) // 2], "min_ms_per_step": min(block_ms),
                    "max_ms_per_step": max(block_ms),
@@ -1031,7 +1094,8 @@ def main():
 
         bench_extras.run(SimpleNamespace(args=args, world=world, custom=custom, dev=dev, B=B, L=L, D=D, N=N, model=model, dp=dp, state=state,
                                          rng=rng, zipf=zipf, use_graph=use_graph, b3=b3, dt=dt, t_eager=t_eager, eager_step=eager_step,
-                                         next_batch=next_batch), out)
+                                         next_batch=next_batch, replay=replay), out)
+        out["h2_stale_overflows"] = stale_overflows[0]      # (the extras' steps count too)
         gstep = None
 
     if args.emulate_world > 1 and world == 1 and not custom:

@@ -21,7 +21,7 @@ def run(ctx, out):
     B, L, D, N = ctx.B, ctx.L, ctx.D, ctx.N
     model, dp, opt, rng, zipf = ctx.model, ctx.dp, ctx.state.opt, ctx.rng, ctx.zipf
     use_graph, b3, dt, t_eager = ctx.use_graph, ctx.b3, ctx.dt, ctx.t_eager
-    eager_step, next_batch = ctx.eager_step, ctx.next_batch
+    eager_step, next_batch, replay = ctx.eager_step, ctx.next_batch, ctx.replay
     from pixelrec_amd import ops, synth
     from pixelrec_amd.optim import PxrAdamW
 
@@ -44,7 +44,7 @@ def run(ctx, out):
                   cur[0] += 1
                   nxt = None if (not args.lookahead) else bt[cur[0] % n_bt][0]
                   if g2 is not None and not eager:
-                      return g2(*b, next_items=nxt)
+                      return replay(g2, *b, next_items=nxt)
                   return eager_step(b, nxt)
 
               for i in range(3):

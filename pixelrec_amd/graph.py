@@ -52,9 +52,12 @@ class GraphedTrainStep:
         cur = torch.cuda.current_stream()
         s = torch.cuda.Stream()
         s.wait_stream(cur)
+        # an ops.H2StaleOverflow the status poll raises in an eager warm-up / dry-run step (a report on a step that has run) is held
+        # and raised by the FIRST replay, where the owner handles it anyway: it must not cost the capture, nor the dry run's restore
+        self._held = None
         with torch.cuda.stream(s):          # eager warm-up: sizes every persistent buffer / workspace
             for _ in range(warmup):
-                self._eager()
+                self._eager_holding()
             if warmup == 0:
                 # size the buffers WITHOUT consuming a training step: run one eager step on a snapshot of all state and
                 # restore it (a trainer that captures in the middle of an epoch must not train on a batch twice)
@@ -99,7 +102,7 @@ class GraphedTrainStep:
             table_state = [t.clone() for t in (m.item_embedding.weight.data, o._tm, o._tv, o._last)]
         counters = (o.step_count, m._step_counter, o._dirty, o._step_dev.clone(), m._drop_dev.clone())
         acc = self.loss_sum.clone() if self.loss_sum is not None else None
-        self._eager()
+        self._eager_holding()
         if acc is not None:
             self.loss_sum.copy_(acc)
         for dst, src in zip((flat, o._m, o._v), keep):
@@ -112,6 +115,14 @@ class GraphedTrainStep:
         m._drop_dev.copy_(counters[4])
         if hasattr(m, "refresh_weight_planes"):
             m.refresh_weight_planes()     # the weights were restored behind the optimizer's back: its planes are stale
+
+    def _eager_holding(self):
+        from .ops import H2StaleOverflow
+
+        try:
+            self._eager()
+        except H2StaleOverflow as e:
+            self._held = self._held or e
 
     def _eager(self):
         self.opt.zero_grad()
@@ -162,4 +173,7 @@ class GraphedTrainStep:
         if hasattr(self.model, "planes_housekeeping"):
             self.model.planes_housekeeping()     # every PXR_H2_REFRESH_STEPS replays: exponents / statistics of the weight planes
                                                  # re-derived from the values, status word polled (no stream stall)
+        if self._held is not None:
+            held, self._held = self._held, None
+            raise held
         return self.loss

@@ -370,11 +370,13 @@ class SeqRecCore(BaseModel):
         self._since_plane_refresh = 0
         if self._status_poll is None:
             self._status_poll = ops.StatusPoll(self._flat.device)
-        self._status_poll.check()
-        if self._planes_fmt_active == 1 and self._wplanes_h2 is not None and self._planes_on():
-            ops.split_h2_auto(self._weight_mats(), col_stats=False, outs=self._wplanes_h2, top=self._W_TOP)
-            self._wplanes_h2_fresh = True
-        self._status_poll.start()
+        try:
+            self._status_poll.check()
+        finally:     # a condition it raises on does not cost the refresh or the next poll
+            if self._planes_fmt_active == 1 and self._wplanes_h2 is not None and self._planes_on():
+                ops.split_h2_auto(self._weight_mats(), col_stats=False, outs=self._wplanes_h2, top=self._W_TOP)
+                self._wplanes_h2_fresh = True
+            self._status_poll.start()
 
     # opt-in like trust_optimizer_planes (GraphedTrainStep, Trainer, bench.py -- loops of similar consecutive steps): the h2 gradient
     # planes of the backward pass are written by their producers under the PREVIOUS step's maxima (ops.H2Sites; PXR_SEQ_H2_STALE=0/1

@@ -292,16 +292,15 @@ class PxrAdamW:
                            close=(self._cumlog, self._cur_hyper, g["lr"], g["weight_decay"]) if fold else None)
         if segs:
             self.model.mark_weight_planes_fresh()
+        if not fold:
+            # close the step: count it on the device and prepare the next step's scalars -- one 1-thread launch.  (Folding it into
+            # the flat update as "the last workgroup to arrive closes the step" was measured: 4096 arrivals on one atomic cost
+            # +29 us on the launch to save this 5 us one, and a fenced variant for folded reductions 0.6 ms -- DESIGN.md dead ends.)
+            ops.adamw_hyper_append(self._hyper, self._cumlog, self.step_count + 2, *cfg, step_dev=sd, advance=True)
+        self.step_count += 1
+        # last: the status poll may raise (ops.H2StaleOverflow), and what it reports on is a step that has been taken AND closed
         if hasattr(self.model, "planes_housekeeping") and flat.is_cuda and not torch.cuda.is_current_stream_capturing():
             self.model.planes_housekeeping()     # eager loops; a captured step is looked after by GraphedTrainStep.__call__
-        if fold:
-            self.step_count += 1
-            return
-        # close the step: count it on the device and prepare the next step's scalars -- one 1-thread launch.  (Folding it into
-        # the flat update as "the last workgroup to arrive closes the step" was measured: 4096 arrivals on one atomic cost
-        # +29 us on the launch to save this 5 us one, and a fenced variant for folded reductions 0.6 ms -- DESIGN.md dead ends.)
-        ops.adamw_hyper_append(self._hyper, self._cumlog, self.step_count + 2, *cfg, step_dev=sd, advance=True)
-        self.step_count += 1
 
     def state_dict(self, layout: str = "native"):
         """layout="native": {step, param_groups, m, v, table_m, table_v} (views of the live buffers);

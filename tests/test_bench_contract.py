@@ -245,3 +245,56 @@ def test_gpus_flag_spawns_one_rank_per_gpu(monkeypatch):
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     assert cmd[-4:] == ["--gpus", "8", "--steps", "7"] and cmd[-5].endswith("bench.py")
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_dump_outputs_writes_the_loss_and_a_seeded_sample_of_the_parameters(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: the loss and every floating parameter as DIR/<name>.npy in float32, the whole dump under the budget;
+    a tensor over its share is a fixed, seeded sample of its elements, so two runs (two builds) write identical files."""
+    import numpy as np
+    import torch
+
+    b = _bench_module()
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 64 << 10)
+
+    class M(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.table = torch.nn.Parameter(torch.randn(1000, 32))          # 128 KB: over its share, sampled
+            self.small = torch.nn.Parameter(torch.randn(4, 8, dtype=torch.float64))
+            self.register_buffer("ids", torch.arange(5))                     # integer: not a parameter output
+
+    torch.manual_seed(0)
+    m, loss = M(), torch.tensor(1.25)
+    info = b.dump_outputs(str(tmp_path / "a"), loss, m)
+    b.dump_outputs(str(tmp_path / "b"), loss, m)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["loss.npy", "small.npy", "table.npy"] and info["sampled"] == ["table"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= b.DUMP_LIMIT_BYTES
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [1.25]
+    small = np.load(tmp_path / "a" / "small.npy")
+    assert small.dtype == np.float64 and np.array_equal(small, m.small.detach().numpy())
+    table = np.load(tmp_path / "a" / "table.npy")
+    assert table.dtype == np.float32 and 0 < table.size < m.table.numel()
+    flat = m.table.detach().reshape(-1).numpy()
+    idx = np.sort(np.random.default_rng(b.DUMP_SAMPLE_SEED).choice(flat.size, table.size, replace=False))
+    assert np.array_equal(table, flat[idx])
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))
+
+
+def test_dump_outputs_flag_is_parsed(monkeypatch):
+    b = _bench_module()
+
+    class Parsed(Exception):
+        pass
+
+    def stop(args):
+        raise Parsed(args)
+
+    monkeypatch.setattr(b, "launch_ranks", stop)
+    monkeypatch.setattr(b.sys, "argv", ["bench.py", "--steps", "3", "--dump-outputs", "out_dir"])
+    try:
+        b.main()
+    except Parsed as e:
+        args = e.args[0]
+    assert args.dump_outputs == "out_dir" and args.steps == 3

@@ -270,3 +270,88 @@ def test_trainer_epoch_loss_survives_a_mid_epoch_recapture(tmp_path, monkeypatch
     assert n == n2 and n >= 6
     assert tr.model.module.h2_stale_scales is True and getattr(tr, "_stale_resume_at", None) is None      # fell back at step 2, resumed at step 4
     assert abs(got - base) <= 2e-4 * abs(base), (got, base)
+
+
+STATUS_H2_STALE = 128      # the status-word bit ops.raise_on_bad_indices reports as ops.H2StaleOverflow (csrc/pxr_common.h)
+_SMALL = {"n_layers": 2, "n_heads": 2, "embedding_size": 128, "inner_size": 2, "hidden_dropout_prob": 0.1, "attn_dropout_prob": 0.1,
+          "hidden_act": "gelu", "layer_norm_eps": 1e-12, "initializer_range": 0.02, "MAX_ITEM_LIST_LENGTH": 20, "seed": 2020}
+
+
+def _small_run(n_batches):
+    from pixelrec_amd import synth
+    from pixelrec_amd.model import SASRec
+    from pixelrec_amd.optim import PxrAdamW
+
+    N, B = 3000, 32
+
+    class DL:
+        item_num = N
+
+    rng = np.random.default_rng(4)
+    z = synth.ZipfItems(N, seed=2)
+    batches = [tuple(torch.from_numpy(a).cuda() for a in synth.train_batch(N, B, 20, rng, z)) for _ in range(n_batches)]
+    torch.manual_seed(3)
+    m = SASRec(_SMALL, DL()).cuda().train()
+    m.trust_optimizer_planes = True          # what bench.py / the Trainer set: the optimizer's step does the housekeeping poll
+    return m, PxrAdamW(m, lr=1e-3, weight_decay=0.1), batches
+
+
+def _eager(m, opt, b):
+    loss = m(b)
+    loss.backward()
+    torch.cuda.synchronize()                 # every earlier poll's copy has landed: a set bit is reported by the next poll
+    opt.step()
+
+
+def test_an_overflow_report_from_the_optimizer_comes_after_the_step_is_closed(monkeypatch):
+    """PxrAdamW.step polls the status word last: the step an ops.H2StaleOverflow comes out of has been taken AND closed (device step
+    advanced, next step's scalars prepared), so going on -- what the Trainer and bench.py do -- continues the very trajectory of a
+    run without the report."""
+    from pixelrec_amd import ops
+
+    monkeypatch.setenv("PXR_H2_REFRESH_STEPS", "1")        # poll at every step
+    out = {}
+    for flagged in (False, True):
+        m, opt, batches = _small_run(6)
+        raised = 0
+        for i, b in enumerate(batches):
+            if flagged and i == 2:
+                ops.device_status("cuda").bitwise_or_(STATUS_H2_STALE)
+            try:
+                _eager(m, opt, b)
+            except ops.H2StaleOverflow:
+                raised += 1
+        assert raised == int(flagged) and opt.step_count == len(batches)
+        ops.raise_on_bad_indices("cuda")
+        out[flagged] = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
+    for k, v in out[False].items():
+        assert (out[True][k] - v).abs().max().item() <= 1e-6, k     # a step left open shifts AdamW's bias corrections ~1e-4
+
+
+@pytest.mark.parametrize("warmup", [0, 1])
+def test_an_overflow_report_in_a_graph_warm_up_is_raised_by_its_first_replay(monkeypatch, warmup):
+    """An ops.H2StaleOverflow the poll raises inside GraphedTrainStep's eager warm-up (warmup >= 1) or dry run (warmup=0) costs
+    neither the capture nor the dry run's restore: the graph is built and its first replay raises the report (after running)."""
+    from pixelrec_amd import ops
+    from pixelrec_amd.graph import GraphedTrainStep
+    from pixelrec_amd.parallel import DataParallel
+
+    monkeypatch.setenv("PXR_H2_REFRESH_STEPS", "1")
+    m, opt, batches = _small_run(5)
+    _eager(m, opt, batches[0])
+    ops.device_status("cuda").bitwise_or_(STATUS_H2_STALE)
+    _eager(m, opt, batches[1])                            # its poll copies the bit: the next poll reports it
+    torch.cuda.synchronize()
+    before = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    n0 = opt.step_count
+    g = GraphedTrainStep(DataParallel(m), opt, *batches[2], warmup=warmup)
+    assert opt.step_count == n0 + warmup
+    if warmup == 0:
+        for k, v in m.state_dict().items():
+            assert torch.equal(v, before[k]), k          # the dry run's step was rolled back
+    with pytest.raises(ops.H2StaleOverflow):
+        g(*batches[3])
+    assert opt.step_count == n0 + warmup + 1
+    g(*batches[4])                                        # reported once
+    torch.cuda.synchronize()
+    ops.raise_on_bad_indices("cuda")
