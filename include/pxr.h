@@ -491,6 +491,59 @@ int pxr_bpr_ln_bwd_f32(const float* pos_score, const float* neg_score, const flo
                        float* dbeta, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws,
                        int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, float* stat, void* stream);
 
+/* ---- BERT4Rec (reference code/REC/model/IDNet/bert4rec.py) --------------------------------------------------------------- */
+/* The training head and table gradient of SASRec with the id layout as arguments: position t of sequence b scores against
+ * items[b*id_bstride + pos_off + t] (target) and items[b*id_bstride + neg_off + t] (negative); SASRec's shifted windows are
+ * (2(L+1), 1, L+2).  BERT4Rec's batch items [B, 3, L] = masked sequence | original sequence | negatives over its L = MAX_ITEM_
+ * LIST_LENGTH + 1 positions (REC/data/dataset/trainset.py:470-478) is (3L, L, 2L), with masked_index [B, L]: the loss
+ * -sum_masked log(1e-8 + sigmoid(pos - neg)) / B of bert4rec.py:98-111 is what pxr_bpr_loss_fwd_f32 computes on that layout. */
+int pxr_bpr_loss_fwd_lay_f32(const float* out, const float* table, int64_t n_table, const int64_t* items,
+                             const int64_t* masked_index, int B, int L, int D, float* pos_score, float* neg_score, float* lossrow,
+                             float* loss, int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream);
+int pxr_bpr_loss_bwd_lay_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
+                             const int64_t* items, const int64_t* masked_index, int B, int L, int D, float grad_scale,
+                             const float* grad_scale_dev, float* dout, float* coef, int64_t id_bstride, int64_t pos_off,
+                             int64_t neg_off, void* stream);
+/* pxr_ln_residual_bpr_fwd_f32 / pxr_bpr_ln_bwd_f32 / pxr_ln_bwd_h2s_f32 with the id layout (bert4rec.py:98-111 fused into the
+ * encoder's last LayerNorm, layers.py:670-671, and its backward) */
+int pxr_ln_residual_bpr_fwd_lay_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps, int B,
+                                    int L, int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
+                                    uint32_t stream_id, const int64_t* step_dev, const float* table, int64_t n_table,
+                                    const int64_t* items, const int64_t* masked_index, float* pos_score, float* neg_score,
+                                    float* lossrow, float* loss, int64_t id_bstride, int64_t pos_off, int64_t neg_off,
+                                    void* stream);
+int pxr_bpr_ln_bwd_lay_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
+                           const int64_t* items, const int64_t* masked_index, int B, int L, float grad_scale,
+                           const float* grad_scale_dev, float* coef, const float* xhat, const float* rstd, const float* gamma,
+                           int D, float* dz, float* dx, float* dgamma, float* dbeta, float p_drop, uint64_t seed,
+                           uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes, void* g_planes,
+                           int64_t g_plane_stride, int64_t g_panel_rows, float* stat, int64_t id_bstride, int64_t pos_off,
+                           int64_t neg_off, void* stream);
+int pxr_ln_bwd_h2s_lay_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
+                           const int64_t* items, const int64_t* masked_index, int B, int L, float grad_scale,
+                           const float* grad_scale_dev, float* coef, const float* dy, const float* xhat, const float* rstd,
+                           const float* gamma, int rows, int D, float* dz, float* dgamma, float* dbeta, float p_drop,
+                           uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes,
+                           void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, const int* g_exp_dev, float* stat,
+                           float* zero, int zero_n, int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream);
+/* Phase 1 of the table gradient (pxr_sasrec_occ_sort) for an id layout: the input ids at in_off, targets at pos_off, negatives at
+ * neg_off of each sequence's id_bstride ids (BERT4Rec: (3L, 0, L, 2L); the table's three uses in bert4rec.py:76-81 under
+ * autograd).  Phase 2 is pxr_sasrec_occ_segsum / pxr_sasrec_occ_segsum_split with the same B, L: deterministic, no float atomics,
+ * row 0 dropped, every other row (BERT4Rec's mask token item_num included) ordinary. */
+int pxr_seq_occ_sort_lay(const int64_t* items, int B, int L, int64_t id_bstride, int64_t in_off, int64_t pos_off,
+                         int64_t neg_off, int64_t n_table, int64_t* uniq_idx, int32_t* n_uniq_dev, void* ws, int64_t ws_bytes,
+                         void* stream);
+/* Bidirectional attention forward: pxr_attn_fwd_f32 / _planes_f32 / _h2_f32 with the key-padding mask only (bert4rec.py:150-155:
+ * -1e9 on keys whose keymask entry is 0, no causal term).  ctx_planes NULL: fp32 ctx only; else planes_fmt 0 = bf16x3, 1 = h2.
+ * The backward entries (pxr_attn_bwd_*) serve it unchanged: they work from the saved probabilities. */
+int pxr_attn_fwd_bidir_f32(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
+                           int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx, float* probs, float p_drop,
+                           uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ctx_planes,
+                           int64_t ctx_plane_stride, int64_t ctx_panel_rows, int planes_fmt, void* stream);
+/* pxr_attn_rows_fwd_f32 (L > 128) with the key-padding mask only; pxr_attn_rows_bwd_f32 serves it unchanged */
+int pxr_attn_rows_fwd_bidir_f32(float* S, float* PD, const int64_t* keymask, int64_t km_bstride, int B, int H, int L, int ld,
+                                float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, int d, void* stream);
+
 /* ---- PixelNet (MOSASRec) ------------------------------------------------------------------------------------- */
 /* Gradient w.r.t. the visual encoder's output viewed [B, L+1, 2, D] (pos_t | neg_t interleaved, PixelNet/
  * mosasrec.py:69-74,88-89): d_emb[b,t,0] = [t<L] dx0[b,t] + [t>=1] coef[b,t-1] out[b,t-1];  d_emb[b,t,1] = -[t>=1] ... */

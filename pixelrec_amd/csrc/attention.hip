@@ -8,6 +8,9 @@
 //   attn_{fwd,bwd}_mfma_kernel      L <= 64, any d % 8 == 0: d-chunked (emb 4096: d = 1024)
 //   attn_{fwd,bwd}_long_kernel      65 <= L <= 128, d % 8 == 0: 128-row tiles, two keys per lane
 //   attn_{fwd,bwd}_kernel<NW>       L <= 64, d % 4 == 0: VALU fallback (PXR_ATTN_MFMA=0 or d % 8 != 0)
+// Mask mode: every forward is a __device__ body templated on CAUSAL.  The __global__ kernels above instantiate CAUSAL = true
+// (SASRec: key j <= query i and key real); attn_fwd_*_bidir_kernel instantiate false (BERT4Rec, bert4rec.py:150-155: key real only),
+// behind pxr_attn_fwd_bidir_f32.  The backward kernels serve both: they read the saved probabilities.
 // Common design:
 //   * q/k/v are read in place from the fused QKV projection output [B, L, 3D] (row stride `ld`), the context
 //     is written head-merged into [B, L, D]: no permute/contiguous copies (layers.py:590-592,610-612);
@@ -125,8 +128,8 @@ __device__ __forceinline__ void rowmix_store(const float* sW, const float* sX, i
   }
 }
 
-template <int NW>
-__global__ void __launch_bounds__(NW * 64) attn_fwd_kernel(AttnArgs a) {
+template <int NW, bool CAUSAL>
+__device__ __forceinline__ void attn_fwd_body(AttnArgs a) {
   if (a.step_dev) a.seed += (uint64_t)a.step_dev[0];
   __shared__ __attribute__((aligned(16))) float sA[ATT_MAXL * ATT_DC];    // Q chunk, later V chunk
   __shared__ __attribute__((aligned(16))) float sB[ATT_MAXL * ATT_KLD];   // K chunk
@@ -162,7 +165,7 @@ __global__ void __launch_bounds__(NW * 64) attn_fwd_kernel(AttnArgs a) {
     const int i = wave + NW * g;  // acc[gg*4+r] holds row wave + NW*(4*gg + r)
     if (i < L) {
       // reference arithmetic: scores / sqrt(d) + (-1e9 | 0)   (layers.py:597,601; sasrec.py:125)
-      float s = acc[g] / a.sqrt_d + ((key_real && lane <= i) ? 0.0f : -1e9f);
+      float s = acc[g] / a.sqrt_d + ((key_real && (!CAUSAL || lane <= i)) ? 0.0f : -1e9f);
       if (lane >= L) s = -INFINITY;
       const float m = wave_max(s);
       const float e = (lane < L) ? expf(s - m) : 0.f;
@@ -188,6 +191,10 @@ __global__ void __launch_bounds__(NW * 64) attn_fwd_kernel(AttnArgs a) {
     __syncthreads();
   }
 }
+template <int NW>
+__global__ void __launch_bounds__(NW * 64) attn_fwd_kernel(AttnArgs a) { attn_fwd_body<NW, true>(a); }
+template <int NW>
+__global__ void __launch_bounds__(NW * 64) attn_fwd_bidir_kernel(AttnArgs a) { attn_fwd_body<NW, false>(a); }
 
 template <int NW>
 __global__ void __launch_bounds__(NW * 64) attn_bwd_kernel(AttnArgs a) {
@@ -384,7 +391,8 @@ __device__ __forceinline__ void stage_tile_z(float* tile, int tstride, const flo
   }
 }
 
-__global__ void __launch_bounds__(256) attn_fwd_mfma_kernel(AttnArgs a) {
+template <bool CAUSAL>
+__device__ __forceinline__ void attn_fwd_mfma_body(AttnArgs a) {
   if (a.step_dev) a.seed += (uint64_t)a.step_dev[0];
   __shared__ __attribute__((aligned(16))) float sQ[ATT_MAXL * ATT_KLD];   // Q chunk (KC); later V chunk (XC, stride 128)
   __shared__ __attribute__((aligned(16))) float sK[ATT_MAXL * ATT_KLD];   // K chunk (KC)
@@ -418,7 +426,7 @@ __global__ void __launch_bounds__(256) attn_fwd_mfma_kernel(AttnArgs a) {
   const float inv_keep = 1.0f / (1.0f - a.p_drop);
   for (int i = wave; i < L; i += 4) {
     // reference arithmetic: scores / sqrt(d) + (-1e9 | 0)   (layers.py:597,601; sasrec.py:125)
-    float s = sS[i * ATT_SLD + lane] / a.sqrt_d + ((key_real && lane <= i) ? 0.0f : -1e9f);
+    float s = sS[i * ATT_SLD + lane] / a.sqrt_d + ((key_real && (!CAUSAL || lane <= i)) ? 0.0f : -1e9f);
     if (lane >= L) s = -INFINITY;
     const float m = wave_max(s);
     const float e = (lane < L) ? expf(s - m) : 0.f;
@@ -447,6 +455,8 @@ __global__ void __launch_bounds__(256) attn_fwd_mfma_kernel(AttnArgs a) {
     __syncthreads();
   }
 }
+__global__ void __launch_bounds__(256) attn_fwd_mfma_kernel(AttnArgs a) { attn_fwd_mfma_body<true>(a); }
+__global__ void __launch_bounds__(256) attn_fwd_mfma_bidir_kernel(AttnArgs a) { attn_fwd_mfma_body<false>(a); }
 
 __global__ void __launch_bounds__(256) attn_bwd_mfma_kernel(AttnArgs a) {
   if (a.step_dev) a.seed += (uint64_t)a.step_dev[0];
@@ -538,8 +548,8 @@ __global__ void __launch_bounds__(256) attn_bwd_mfma_kernel(AttnArgs a) {
 // NW = 4 or 8 waves.  The 64x64 score tile is always computed by waves 0-3 (one 32x32 block each); with 8 waves the
 // row softmax handles 7 instead of 13 rows per wave, the staging issues half as many loads per thread and the
 // 64x128 output is 8 blocks of 32x32 (one per wave) instead of 4 slabs of 32x64.
-template <int NW>
-__global__ void __launch_bounds__(64 * NW) attn_fwd_mfma1_kernel(AttnArgs a) {
+template <int NW, bool CAUSAL>
+__device__ __forceinline__ void attn_fwd_mfma1_body(AttnArgs a) {
   if (a.step_dev) a.seed += (uint64_t)a.step_dev[0];
   constexpr int NT = 64 * NW;
   __shared__ __attribute__((aligned(16))) float sQ[ATT_MAXL * ATT_KLD];
@@ -570,7 +580,7 @@ __global__ void __launch_bounds__(64 * NW) attn_fwd_mfma1_kernel(AttnArgs a) {
   const bool drop = a.drop_thr != 0u;
   const float inv_keep = 1.0f / (1.0f - a.p_drop);
   for (int i = wave; i < L; i += NW) {
-    float s = sS[i * ATT_SLD + lane] / a.sqrt_d + ((key_real && lane <= i) ? 0.0f : -1e9f);
+    float s = sS[i * ATT_SLD + lane] / a.sqrt_d + ((key_real && (!CAUSAL || lane <= i)) ? 0.0f : -1e9f);
     if (lane >= L) s = -INFINITY;
     const float m = wave_max(s);
     const float e = (lane < L) ? expf(s - m) : 0.f;
@@ -603,6 +613,10 @@ __global__ void __launch_bounds__(64 * NW) attn_fwd_mfma1_kernel(AttnArgs a) {
     if (a.op.p) store_acc_planes<1, NT>(accO, wn * 32 < d, sQ, wm * 32, wn * 32, L, d, lane, a.op, (int64_t)b * L, h * d, a.op_fmt, a.status);
   }
 }
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) attn_fwd_mfma1_kernel(AttnArgs a) { attn_fwd_mfma1_body<NW, true>(a); }
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) attn_fwd_mfma1_bidir_kernel(AttnArgs a) { attn_fwd_mfma1_body<NW, false>(a); }
 
 template <int NW>
 __global__ void __launch_bounds__(64 * NW) attn_bwd_mfma1_kernel(AttnArgs a) {
@@ -825,7 +839,8 @@ __device__ __forceinline__ void tile2_to_planes(const float* tile, int L, int w,
   }
 }
 
-__global__ void __launch_bounds__(ATT2_NT, 4) attn_fwd_mfma2_kernel(AttnArgs a) {
+template <bool CAUSAL>
+__device__ __forceinline__ void attn_fwd_mfma2_body(AttnArgs a) {
   if (a.step_dev) a.seed += (uint64_t)a.step_dev[0];
   constexpr int NW = 8;
   __shared__ __attribute__((aligned(16))) float T0[ATT2_TR * ATT_KLD];   // Q, then V
@@ -858,7 +873,7 @@ __global__ void __launch_bounds__(ATT2_NT, 4) attn_fwd_mfma2_kernel(AttnArgs a) 
   const bool drop = a.drop_thr != 0u;
   const float inv_keep = 1.0f / (1.0f - a.p_drop);
   for (int i = wave; i < L; i += NW) {
-    float s = sS[i * ATT_SLD + lane] / a.sqrt_d + ((key_real && lane <= i) ? 0.0f : -1e9f);
+    float s = sS[i * ATT_SLD + lane] / a.sqrt_d + ((key_real && (!CAUSAL || lane <= i)) ? 0.0f : -1e9f);
     if (lane >= L) s = -INFINITY;
     const float m = wave_max(s);
     const float e = (lane < L) ? expf(s - m) : 0.f;
@@ -887,6 +902,8 @@ __global__ void __launch_bounds__(ATT2_NT, 4) attn_fwd_mfma2_kernel(AttnArgs a) 
     tile2_to_planes(T1, L, d, a.op, (int64_t)b * L, h * d, a.op_fmt, a.status);
   }
 }
+__global__ void __launch_bounds__(ATT2_NT, 4) attn_fwd_mfma2_kernel(AttnArgs a) { attn_fwd_mfma2_body<true>(a); }
+__global__ void __launch_bounds__(ATT2_NT, 4) attn_fwd_mfma2_bidir_kernel(AttnArgs a) { attn_fwd_mfma2_body<false>(a); }
 
 __global__ void __launch_bounds__(ATT2_NT, 4) attn_bwd_mfma2_kernel(AttnArgs a) {
   if (a.step_dev) a.seed += (uint64_t)a.step_dev[0];
@@ -1056,7 +1073,8 @@ __device__ __forceinline__ void acc2_to_tile(const f32x16 (&acc)[2], float* sS, 
       sS[(wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh) * ATTL_SLD + wn * 64 + j * 32 + r] = acc[j][e];
 }
 
-__global__ void __launch_bounds__(ATTL_NT) attn_fwd_long_kernel(AttnArgs a) {
+template <bool CAUSAL>
+__device__ __forceinline__ void attn_fwd_long_body(AttnArgs a) {
   if (a.step_dev) a.seed += (uint64_t)a.step_dev[0];
   __shared__ __attribute__((aligned(16))) float sA[ATTL_MAXL * ATTL_KLD];   // Q chunk (KC); later V chunk (XC, stride 64)
   __shared__ __attribute__((aligned(16))) float sB[ATTL_MAXL * ATTL_KLD];   // K chunk (KC)
@@ -1086,8 +1104,8 @@ __global__ void __launch_bounds__(ATTL_NT) attn_fwd_long_kernel(AttnArgs a) {
   const bool drop = a.drop_thr != 0u;
   const float inv_keep = 1.0f / (1.0f - a.p_drop);
   for (int i = wave; i < L; i += ATTL_NT / 64) {
-    float s0 = sS[i * ATTL_SLD + k0] / a.sqrt_d + ((real0 && k0 <= i) ? 0.0f : -1e9f);
-    float s1 = sS[i * ATTL_SLD + k1] / a.sqrt_d + ((real1 && k1 <= i) ? 0.0f : -1e9f);
+    float s0 = sS[i * ATTL_SLD + k0] / a.sqrt_d + ((real0 && (!CAUSAL || k0 <= i)) ? 0.0f : -1e9f);
+    float s1 = sS[i * ATTL_SLD + k1] / a.sqrt_d + ((real1 && (!CAUSAL || k1 <= i)) ? 0.0f : -1e9f);
     if (k0 >= L) s0 = -INFINITY;
     if (k1 >= L) s1 = -INFINITY;
     const float m = wave_max(fmaxf(s0, s1));
@@ -1122,6 +1140,8 @@ __global__ void __launch_bounds__(ATTL_NT) attn_fwd_long_kernel(AttnArgs a) {
     __syncthreads();
   }
 }
+__global__ void __launch_bounds__(ATTL_NT) attn_fwd_long_kernel(AttnArgs a) { attn_fwd_long_body<true>(a); }
+__global__ void __launch_bounds__(ATTL_NT) attn_fwd_long_bidir_kernel(AttnArgs a) { attn_fwd_long_body<false>(a); }
 
 __global__ void __launch_bounds__(ATTL_NT) attn_bwd_long_kernel(AttnArgs a) {
   if (a.step_dev) a.seed += (uint64_t)a.step_dev[0];
@@ -1287,7 +1307,7 @@ extern "C" int pxr_attn_fwd_f32(const float* q, const float* k, const float* v, 
 static int attn_fwd_planes_impl(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
                                 int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx, float* probs, float p_drop,
                                 uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ctx_planes,
-                                int64_t ctx_plane_stride, int64_t ctx_panel_rows, int c_fmt, void* stream);
+                                int64_t ctx_plane_stride, int64_t ctx_panel_rows, int c_fmt, void* stream, bool causal = true);
 extern "C" int pxr_attn_fwd_planes_f32(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
                                        int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx,
                                        float* probs, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
@@ -1304,10 +1324,24 @@ extern "C" int pxr_attn_fwd_h2_f32(const float* q, const float* k, const float* 
   return attn_fwd_planes_impl(q, k, v, ld, keymask, km_bstride, B, H, L, d, ctx, ld_ctx, probs, p_drop, seed, stream_id, step_dev,
                               ctx_planes, ctx_plane_stride, ctx_panel_rows, PXR_PLANES_H2, stream);
 }
+// Bidirectional (key-padding-only) attention: the same kernels instantiated with CAUSAL = false, i.e. the additive -1e9 lands
+// only on keys whose keymask entry is 0 -- BERT4Rec's get_attention_mask (reference IDNet/bert4rec.py:150-155).  One entry for
+// the three output forms: ctx_planes NULL = fp32 ctx only (pxr_attn_fwd_f32); else planes_fmt PXR_PLANES_BF16X3 (0) or
+// PXR_PLANES_H2 (1) as pxr_attn_fwd_planes_f32 / pxr_attn_fwd_h2_f32.  The backward entries need no mask form: they work from the
+// saved probabilities, which carry the mask.
+extern "C" int pxr_attn_fwd_bidir_f32(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
+                                      int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx, float* probs,
+                                      float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ctx_planes,
+                                      int64_t ctx_plane_stride, int64_t ctx_panel_rows, int planes_fmt, void* stream) {
+  PXR_REQUIRE(planes_fmt == 0 || planes_fmt == 1, "pxr_attn_fwd_bidir_f32: planes_fmt must be 0 (bf16x3) or 1 (h2)");
+  return attn_fwd_planes_impl(q, k, v, ld, keymask, km_bstride, B, H, L, d, ctx, ld_ctx, probs, p_drop, seed, stream_id, step_dev,
+                              ctx_planes, ctx_plane_stride, ctx_panel_rows, planes_fmt == 1 ? PXR_PLANES_H2 : PXR_PLANES_BF16X3,
+                              stream, false);
+}
 static int attn_fwd_planes_impl(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
                                 int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx, float* probs, float p_drop,
                                 uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ctx_planes,
-                                int64_t ctx_plane_stride, int64_t ctx_panel_rows, int c_fmt, void* stream) {
+                                int64_t ctx_plane_stride, int64_t ctx_panel_rows, int c_fmt, void* stream, bool causal) {
   PXR_REQUIRE(q && k && v && keymask && (ctx || ctx_planes), "pxr_attn_fwd_f32: null pointer");
   PXR_REQUIRE(!ctx_planes || (pxr_attn_planes_supported(L, d) && p3_mat_ok(ctx_planes, ctx_plane_stride, ctx_panel_rows, (int64_t)B * L, (int64_t)H * d)),
               "pxr_attn_fwd_planes_f32: planes are not available for this shape (L=%d, d=%d)", L, d);
@@ -1325,22 +1359,22 @@ static int attn_fwd_planes_impl(const float* q, const float* k, const float* v, 
   a.p_drop = p_drop; a.drop_thr = pxr_drop_threshold(p_drop); a.stream = stream_id; a.seed = seed;
   a.step_dev = step_dev;
   if (L > ATT_MAXL) {   // 65..128 positions: two keys per lane, 128-row tiles
-    hipLaunchKernelGGL(attn_fwd_long_kernel, dim3(B * H), dim3(ATTL_NT), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(causal ? attn_fwd_long_kernel : attn_fwd_long_bidir_kernel, dim3(B * H), dim3(ATTL_NT), 0, (hipStream_t)stream, a);
     return pxr_check_launch("pxr_attn_fwd_f32(long)");
   }
   if (attn_use_mfma(d)) {
     if (d <= ATT_DC) {
-      if (attn_use_two(L, d)) hipLaunchKernelGGL(attn_fwd_mfma2_kernel, dim3(B * H), dim3(ATT2_NT), 0, (hipStream_t)stream, a);
-      else if (attn_mfma_waves() == 8) hipLaunchKernelGGL(attn_fwd_mfma1_kernel<8>, dim3(B * H), dim3(512), 0, (hipStream_t)stream, a);
-      else hipLaunchKernelGGL(attn_fwd_mfma1_kernel<4>, dim3(B * H), dim3(256), 0, (hipStream_t)stream, a);
+      if (attn_use_two(L, d)) hipLaunchKernelGGL(causal ? attn_fwd_mfma2_kernel : attn_fwd_mfma2_bidir_kernel, dim3(B * H), dim3(ATT2_NT), 0, (hipStream_t)stream, a);
+      else if (attn_mfma_waves() == 8) hipLaunchKernelGGL(causal ? attn_fwd_mfma1_kernel<8> : attn_fwd_mfma1_bidir_kernel<8>, dim3(B * H), dim3(512), 0, (hipStream_t)stream, a);
+      else hipLaunchKernelGGL(causal ? attn_fwd_mfma1_kernel<4> : attn_fwd_mfma1_bidir_kernel<4>, dim3(B * H), dim3(256), 0, (hipStream_t)stream, a);
     }
-    else hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3(B * H), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(causal ? attn_fwd_mfma_kernel : attn_fwd_mfma_bidir_kernel, dim3(B * H), dim3(256), 0, (hipStream_t)stream, a);
     return pxr_check_launch("pxr_attn_fwd_f32(mfma)");
   }
   switch (attn_waves()) {
-    case 4: hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3(B * H), dim3(256), 0, (hipStream_t)stream, a); break;
-    case 16: hipLaunchKernelGGL(attn_fwd_kernel<16>, dim3(B * H), dim3(1024), 0, (hipStream_t)stream, a); break;
-    default: hipLaunchKernelGGL(attn_fwd_kernel<8>, dim3(B * H), dim3(512), 0, (hipStream_t)stream, a); break;
+    case 4: hipLaunchKernelGGL(causal ? attn_fwd_kernel<4> : attn_fwd_bidir_kernel<4>, dim3(B * H), dim3(256), 0, (hipStream_t)stream, a); break;
+    case 16: hipLaunchKernelGGL(causal ? attn_fwd_kernel<16> : attn_fwd_bidir_kernel<16>, dim3(B * H), dim3(1024), 0, (hipStream_t)stream, a); break;
+    default: hipLaunchKernelGGL(causal ? attn_fwd_kernel<8> : attn_fwd_bidir_kernel<8>, dim3(B * H), dim3(512), 0, (hipStream_t)stream, a); break;
   }
   return pxr_check_launch("pxr_attn_fwd_f32");
 }

@@ -30,6 +30,9 @@ struct BprArgs {
   int B, L, D;
   float grad_scale;
   const float* grad_scale_dev;  // optional device scalar multiplied in (autograd's upstream gradient)
+  // id layout: position t of sequence b scores against items[b*id_bstride + pos_off + t] / [... + neg_off + t] -- SASRec's
+  // shifted [B, 2, L+1] windows (2(L+1), 1, L+2), BERT4Rec's aligned [B, 3, L] planes (3L, L, 2L)
+  int64_t id_bstride, pos_off, neg_off;
 };
 
 __device__ __forceinline__ int64_t clamp_id(int64_t r, int64_t n) { return r < 0 ? 0 : (r >= n ? n - 1 : r); }
@@ -39,9 +42,9 @@ __global__ void __launch_bounds__(256) bpr_fwd_kernel(BprArgs a) {
   const int r = blockIdx.x * 4 + wave;
   if (r >= a.B * a.L) return;
   const int b = r / a.L, t = r - b * a.L;
-  const int64_t* it = a.items + (int64_t)b * 2 * (a.L + 1);
-  const float* ep = a.table + clamp_id(it[t + 1], a.n_table) * a.D;
-  const float* en = a.table + clamp_id(it[(a.L + 1) + t + 1], a.n_table) * a.D;
+  const int64_t* it = a.items + (int64_t)b * a.id_bstride;
+  const float* ep = a.table + clamp_id(it[a.pos_off + t], a.n_table) * a.D;
+  const float* en = a.table + clamp_id(it[a.neg_off + t], a.n_table) * a.D;
   const float* o = a.out + (int64_t)r * a.D;
   float sp = 0.f, sn = 0.f;
   for (int c = lane * 4; c < a.D; c += 256) {
@@ -100,9 +103,9 @@ __global__ void __launch_bounds__(256) bpr_bwd_kernel(BprArgs a) {
   float cf = -((float)a.mask[r] / (float)a.B) * (s * (1.0f - s)) / (s + 1e-8f) * a.grad_scale;
   if (a.grad_scale_dev) cf *= a.grad_scale_dev[0];
   if (lane == 0) a.coef[r] = cf;
-  const int64_t* it = a.items + (int64_t)b * 2 * (a.L + 1);
-  const float* ep = a.table + clamp_id(it[t + 1], a.n_table) * a.D;
-  const float* en = a.table + clamp_id(it[(a.L + 1) + t + 1], a.n_table) * a.D;
+  const int64_t* it = a.items + (int64_t)b * a.id_bstride;
+  const float* ep = a.table + clamp_id(it[a.pos_off + t], a.n_table) * a.D;
+  const float* en = a.table + clamp_id(it[a.neg_off + t], a.n_table) * a.D;
   float* d = a.dout + (int64_t)r * a.D;
   for (int c = lane * 4; c < a.D; c += 256) {
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -120,19 +123,39 @@ __global__ void __launch_bounds__(256) bpr_bwd_kernel(BprArgs a) {
 using namespace pxr;
 
 // loss (device scalar), pos_score / neg_score [B*L].  lossrow is [B*L] scratch.
-extern "C" int pxr_bpr_loss_fwd_f32(const float* out, const float* table, int64_t n_table, const int64_t* items,
-                                    const int64_t* masked_index, int B, int L, int D, float* pos_score,
-                                    float* neg_score, float* lossrow, float* loss, void* stream) {
+static int bpr_loss_fwd_impl(const float* out, const float* table, int64_t n_table, const int64_t* items,
+                             const int64_t* masked_index, int B, int L, int D, float* pos_score, float* neg_score, float* lossrow,
+                             float* loss, int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream) {
   PXR_REQUIRE(out && table && items && masked_index && pos_score && neg_score && lossrow && loss,
               "pxr_bpr_loss_fwd_f32: null pointer");
   PXR_REQUIRE(B > 0 && L > 0 && D > 0 && D % 4 == 0, "pxr_bpr_loss_fwd_f32: bad shape");
   BprArgs a{};
   a.out = out; a.table = table; a.items = items; a.mask = masked_index; a.pos_score = pos_score;
   a.neg_score = neg_score; a.lossrow = lossrow; a.loss = loss; a.n_table = n_table; a.B = B; a.L = L; a.D = D;
+  a.id_bstride = id_bstride; a.pos_off = pos_off; a.neg_off = neg_off;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(bpr_fwd_kernel, dim3((B * L + 3) / 4), dim3(256), 0, st, a);
   hipLaunchKernelGGL(bpr_reduce_kernel, dim3(1), dim3(256), 0, st, (const float*)lossrow, B, L, loss);
   return pxr_check_launch("pxr_bpr_loss_fwd_f32");
+}
+extern "C" int pxr_bpr_loss_fwd_f32(const float* out, const float* table, int64_t n_table, const int64_t* items,
+                                    const int64_t* masked_index, int B, int L, int D, float* pos_score,
+                                    float* neg_score, float* lossrow, float* loss, void* stream) {
+  return bpr_loss_fwd_impl(out, table, n_table, items, masked_index, B, L, D, pos_score, neg_score, lossrow, loss,
+                           2 * (int64_t)(L + 1), 1, L + 2, stream);
+}
+static bool bpr_layout_ok(int L, int64_t id_bstride, int64_t pos_off, int64_t neg_off) {
+  return id_bstride > 0 && pos_off >= 0 && neg_off >= 0 && pos_off + L <= id_bstride && neg_off + L <= id_bstride;
+}
+// ... with the id layout as arguments (BprArgs::id_bstride): BERT4Rec's aligned masked head, reference IDNet/bert4rec.py:98-111
+// (items [B, 3, L] = masked sequence | original sequence | negatives: layout (3L, L, 2L); masked_index [B, L])
+extern "C" int pxr_bpr_loss_fwd_lay_f32(const float* out, const float* table, int64_t n_table, const int64_t* items,
+                                        const int64_t* masked_index, int B, int L, int D, float* pos_score, float* neg_score,
+                                        float* lossrow, float* loss, int64_t id_bstride, int64_t pos_off, int64_t neg_off,
+                                        void* stream) {
+  PXR_REQUIRE(bpr_layout_ok(L, id_bstride, pos_off, neg_off), "pxr_bpr_loss_fwd_lay_f32: bad id layout");
+  return bpr_loss_fwd_impl(out, table, n_table, items, masked_index, B, L, D, pos_score, neg_score, lossrow, loss, id_bstride,
+                           pos_off, neg_off, stream);
 }
 
 // The second stage alone: loss = (1/B) sum_b sum_t lossrow[b,t] in bpr_reduce_kernel's fixed order (for producers of lossrow
@@ -144,10 +167,10 @@ extern "C" int pxr_bpr_loss_reduce_f32(const float* lossrow, int B, int L, float
 }
 
 // dout [B*L, D] and coef [B*L] from the saved scores; upstream d(loss) = grad_scale * (*grad_scale_dev if given).
-extern "C" int pxr_bpr_loss_bwd_f32(const float* pos_score, const float* neg_score, const float* table,
-                                    int64_t n_table, const int64_t* items, const int64_t* masked_index, int B, int L,
-                                    int D, float grad_scale, const float* grad_scale_dev, float* dout, float* coef,
-                                    void* stream) {
+static int bpr_loss_bwd_impl(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
+                             const int64_t* items, const int64_t* masked_index, int B, int L, int D, float grad_scale,
+                             const float* grad_scale_dev, float* dout, float* coef, int64_t id_bstride, int64_t pos_off,
+                             int64_t neg_off, void* stream) {
   PXR_REQUIRE(pos_score && neg_score && table && items && masked_index && dout && coef,
               "pxr_bpr_loss_bwd_f32: null pointer");
   PXR_REQUIRE(B > 0 && L > 0 && D > 0 && D % 4 == 0, "pxr_bpr_loss_bwd_f32: bad shape");
@@ -155,6 +178,23 @@ extern "C" int pxr_bpr_loss_bwd_f32(const float* pos_score, const float* neg_sco
   a.table = table; a.items = items; a.mask = masked_index; a.pos_score = const_cast<float*>(pos_score);
   a.neg_score = const_cast<float*>(neg_score); a.dout = dout; a.coef = coef; a.n_table = n_table;
   a.B = B; a.L = L; a.D = D; a.grad_scale = grad_scale; a.grad_scale_dev = grad_scale_dev;
+  a.id_bstride = id_bstride; a.pos_off = pos_off; a.neg_off = neg_off;
   hipLaunchKernelGGL(bpr_bwd_kernel, dim3((B * L + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
   return pxr_check_launch("pxr_bpr_loss_bwd_f32");
+}
+extern "C" int pxr_bpr_loss_bwd_f32(const float* pos_score, const float* neg_score, const float* table,
+                                    int64_t n_table, const int64_t* items, const int64_t* masked_index, int B, int L,
+                                    int D, float grad_scale, const float* grad_scale_dev, float* dout, float* coef,
+                                    void* stream) {
+  return bpr_loss_bwd_impl(pos_score, neg_score, table, n_table, items, masked_index, B, L, D, grad_scale, grad_scale_dev, dout,
+                           coef, 2 * (int64_t)(L + 1), 1, L + 2, stream);
+}
+// ... with the id layout of pxr_bpr_loss_fwd_lay_f32 (BERT4Rec: reference IDNet/bert4rec.py:98-113 under autograd)
+extern "C" int pxr_bpr_loss_bwd_lay_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
+                                        const int64_t* items, const int64_t* masked_index, int B, int L, int D, float grad_scale,
+                                        const float* grad_scale_dev, float* dout, float* coef, int64_t id_bstride,
+                                        int64_t pos_off, int64_t neg_off, void* stream) {
+  PXR_REQUIRE(bpr_layout_ok(L, id_bstride, pos_off, neg_off), "pxr_bpr_loss_bwd_lay_f32: bad id layout");
+  return bpr_loss_bwd_impl(pos_score, neg_score, table, n_table, items, masked_index, B, L, D, grad_scale, grad_scale_dev, dout,
+                           coef, id_bstride, pos_off, neg_off, stream);
 }

@@ -38,16 +38,21 @@ __global__ void __launch_bounds__(256) occ_keys_rows_kernel(const int64_t* __res
   keys[o] = (int)r;
   vals[o] = o;
 }
+// id layout of the three occurrence kinds: position t of sequence b reads items[b*bstride + off[kind] + t].  SASRec's shifted
+// [B, 2, L+1] windows: bstride 2(L+1), off (0, 1, L+2); BERT4Rec's aligned [B, 3, L] planes: bstride 3L, off (0, L, 2L)
+struct OccLayout { int64_t bstride, off_in, off_pos, off_neg; };
+__host__ __device__ inline OccLayout sasrec_occ_layout(int L) { return OccLayout{2 * (int64_t)(L + 1), 0, 1, (int64_t)L + 2}; }
+
 __global__ void __launch_bounds__(256) occ_keys_sasrec_kernel(const int64_t* __restrict__ items, int B, int L,
                                                               int* __restrict__ keys, int* __restrict__ vals,
-                                                              int64_t n_table) {
+                                                              int64_t n_table, OccLayout lay) {
   const int T = B * L;
   const int o = blockIdx.x * 256 + threadIdx.x;
   if (o >= 3 * T) return;
   const int type = o / T, r = o - type * T;
   const int b = r / L, t = r - b * L;
-  const int64_t* row = items + (int64_t)b * 2 * (L + 1);
-  int64_t id = (type == 0) ? row[t] : (type == 1 ? row[t + 1] : row[(L + 1) + t + 1]);
+  const int64_t* row = items + (int64_t)b * lay.bstride;
+  int64_t id = row[(type == 0 ? lay.off_in : (type == 1 ? lay.off_pos : lay.off_neg)) + t];
   if (id < 0 || id >= n_table) id = 0;
   keys[o] = (int)id;
   vals[o] = o;
@@ -240,6 +245,7 @@ struct FusedPassArgs {
   int* keys_out; int* vals_out;
   int n, B, L, shift, bits, first;
   int64_t n_table;
+  OccLayout lay;               // MODE_SASREC: where the three occurrence kinds sit in `src`
 };
 
 template <int MODE>
@@ -251,8 +257,8 @@ __device__ __forceinline__ int occ_key(const FusedPassArgs& a, int o) {
     const int T = a.B * a.L;
     const int type = o / T, r = o - type * T;
     const int b = r / a.L, t = r - b * a.L;
-    const int64_t* row = a.src + (int64_t)b * 2 * (a.L + 1);
-    id = (type == 0) ? row[t] : (type == 1 ? row[t + 1] : row[(a.L + 1) + t + 1]);
+    const int64_t* row = a.src + (int64_t)b * a.lay.bstride;
+    id = row[(type == 0 ? a.lay.off_in : (type == 1 ? a.lay.off_pos : a.lay.off_neg)) + t];
   }
   return (id < 0 || id >= a.n_table) ? 0 : (int)id;
 }
@@ -875,7 +881,7 @@ static int fused_passes(int64_t n_table) {
 }
 template <int MODE>
 static int fused_sort(const int64_t* src, int n, int B, int L, int64_t n_table, const SortWs& w, int64_t* uniq_idx,
-                      int* n_uniq, hipStream_t st, const int** sorted_vals) {
+                      int* n_uniq, hipStream_t st, const int** sorted_vals, OccLayout lay = OccLayout{}) {
   int bits = 1;
   while (((int64_t)1 << bits) < n_table) ++bits;
   const int npass = fused_passes(n_table);
@@ -884,7 +890,7 @@ static int fused_sort(const int64_t* src, int n, int B, int L, int64_t n_table, 
   for (int p = 0; p < npass; ++p) {
     FusedPassArgs a{};
     a.src = src; a.keys_in = kin; a.vals_in = vin; a.keys_out = kout; a.vals_out = vout;
-    a.n = n; a.B = B; a.L = L; a.shift = p * width; a.bits = width; a.first = (p == 0); a.n_table = n_table;
+    a.n = n; a.B = B; a.L = L; a.shift = p * width; a.bits = width; a.first = (p == 0); a.n_table = n_table; a.lay = lay;
     hipLaunchKernelGGL(fused_pass_kernel<MODE>, dim3(w.nblk), dim3(FP_THREADS), 0, st, a);
     int* t = kin; kin = kout; kout = t;
     t = vin; vin = vout; vout = t;
@@ -938,8 +944,8 @@ extern "C" int pxr_embed_grad_rows_f32(const int64_t* idx, int64_t n, const floa
 // `items` only, so it can run BEFORE the forward pass (the lazy table optimizer needs the unique rows of the batch
 // to bring them up to date before they are read).  The sorted state stays in `ws` for phase 2: the caller must keep
 // `ws` untouched in between.
-extern "C" int pxr_sasrec_occ_sort(const int64_t* items, int B, int L, int64_t n_table, int64_t* uniq_idx,
-                                   int32_t* n_uniq_dev, void* ws, int64_t ws_bytes, void* stream) {
+static int occ_sort_impl(const int64_t* items, int B, int L, int64_t n_table, int64_t* uniq_idx, int32_t* n_uniq_dev, void* ws,
+                         int64_t ws_bytes, OccLayout lay, void* stream) {
   PXR_REQUIRE(items && uniq_idx && n_uniq_dev && ws, "pxr_sasrec_occ_sort: null pointer");
   const int64_t n64 = (int64_t)3 * B * L;
   PXR_REQUIRE(B > 0 && L > 0 && n64 < (1ll << 30) && n_table > 0 && n_table < (1ll << 31), "pxr_sasrec_occ_sort: bad shape");
@@ -949,17 +955,33 @@ extern "C" int pxr_sasrec_occ_sort(const int64_t* items, int B, int L, int64_t n
   hipStream_t st = (hipStream_t)stream;
   const int* sorted_vals = nullptr;
   if (use_fused_sort(n)) {
-    int rc = fused_sort<MODE_SASREC>(items, n, B, L, n_table, w, uniq_idx, n_uniq_dev, st, &sorted_vals);
+    int rc = fused_sort<MODE_SASREC>(items, n, B, L, n_table, w, uniq_idx, n_uniq_dev, st, &sorted_vals, lay);
     if (rc) return rc;
     if (sorted_vals != sasrec_sorted_vals(w, n, n_table)) { pxr_set_error("pxr_sasrec_occ_sort: internal buffer parity"); return PXR_ERR_LAUNCH; }
     return PXR_OK;
   }
   hipLaunchKernelGGL(occ_keys_sasrec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, items, B, L, w.keysA, w.valsA,
-                     n_table);
+                     n_table, lay);
   int rc = sort_and_segment(w, n, n_table, uniq_idx, n_uniq_dev, st, &sorted_vals);
   if (rc) return rc;
   if (sorted_vals != sasrec_sorted_vals(w, n, n_table)) { pxr_set_error("pxr_sasrec_occ_sort: internal buffer parity"); return PXR_ERR_LAUNCH; }
   return PXR_OK;
+}
+extern "C" int pxr_sasrec_occ_sort(const int64_t* items, int B, int L, int64_t n_table, int64_t* uniq_idx,
+                                   int32_t* n_uniq_dev, void* ws, int64_t ws_bytes, void* stream) {
+  return occ_sort_impl(items, B, L, n_table, uniq_idx, n_uniq_dev, ws, ws_bytes, sasrec_occ_layout(L), stream);
+}
+// Phase 1 for another id layout of the same three occurrence kinds (input | target | negative of position t of sequence b at
+// items[b*id_bstride + {in_off, pos_off, neg_off} + t]).  BERT4Rec: items [B, 3, L] = masked sequence | original sequence |
+// negatives, layout (3L, 0, L, 2L) -- the table's three uses in reference IDNet/bert4rec.py:76-81,98-111 under autograd; its
+// mask-token row is an ordinary row, row 0 (padding_idx) is dropped.  Phase 2 is pxr_sasrec_occ_segsum[_split] unchanged: the
+// occurrence o of kind k at row r = b*L + t adds dx0[r], +coef[r] out[r] or -coef[r] out[r] whatever the layout.
+extern "C" int pxr_seq_occ_sort_lay(const int64_t* items, int B, int L, int64_t id_bstride, int64_t in_off, int64_t pos_off,
+                                    int64_t neg_off, int64_t n_table, int64_t* uniq_idx, int32_t* n_uniq_dev, void* ws,
+                                    int64_t ws_bytes, void* stream) {
+  PXR_REQUIRE(id_bstride > 0 && in_off >= 0 && pos_off >= 0 && neg_off >= 0 && in_off + L <= id_bstride && pos_off + L <= id_bstride &&
+              neg_off + L <= id_bstride, "pxr_seq_occ_sort_lay: bad id layout");
+  return occ_sort_impl(items, B, L, n_table, uniq_idx, n_uniq_dev, ws, ws_bytes, OccLayout{id_bstride, in_off, pos_off, neg_off}, stream);
 }
 
 // Phase 2: uniq_rows[u,:] = scale * sum over the occurrences of unique id u (see the header comment for the terms).

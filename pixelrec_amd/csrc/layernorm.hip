@@ -33,6 +33,9 @@ struct BprHead {
   int B, L;
   float grad_scale;
   const float* grad_scale_dev;
+  // id layout: position t of sequence b scores against items[b*id_bstride + pos_off + t] / [... + neg_off + t].  SASRec's shifted
+  // [B, 2, L+1] windows: (2(L+1), 1, L+2); BERT4Rec's aligned [B, 3, L] planes: (3L, L, 2L)
+  int64_t id_bstride, pos_off, neg_off;
 };
 __device__ __forceinline__ int64_t ln_clamp_id(int64_t r, int64_t n) { return r < 0 ? 0 : (r >= n ? n - 1 : r); }
 
@@ -160,9 +163,9 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs a) {
     if constexpr (!GATHER) {
       if (a.head.items) {   // wave-uniform
         const int b = row / a.head.L, t = row - b * a.head.L;
-        const int64_t* it = a.head.items + (int64_t)b * 2 * (a.head.L + 1);
-        ep = a.head.table + ln_clamp_id(it[t + 1], a.head.n_table) * D;
-        en = a.head.table + ln_clamp_id(it[(a.head.L + 1) + t + 1], a.head.n_table) * D;
+        const int64_t* it = a.head.items + (int64_t)b * a.head.id_bstride;
+        ep = a.head.table + ln_clamp_id(it[a.head.pos_off + t], a.head.n_table) * D;
+        en = a.head.table + ln_clamp_id(it[a.head.neg_off + t], a.head.n_table) * D;
       }
     }
 #pragma unroll
@@ -325,9 +328,9 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(LnBwdArgs a) {
         cf = -((float)a.head.mask[row] / (float)a.head.B) * (sg * (1.0f - sg)) / (sg + 1e-8f) * a.head.grad_scale;
         if (a.head.grad_scale_dev) cf *= a.head.grad_scale_dev[0];
         if (lane == 0) a.head.coef[row] = cf;
-        const int64_t* it = a.head.items + (int64_t)b * 2 * (a.head.L + 1);
-        ep = a.head.table + ln_clamp_id(it[t + 1], a.head.n_table) * D;
-        en = a.head.table + ln_clamp_id(it[(a.head.L + 1) + t + 1], a.head.n_table) * D;
+        const int64_t* it = a.head.items + (int64_t)b * a.head.id_bstride;
+        ep = a.head.table + ln_clamp_id(it[a.head.pos_off + t], a.head.n_table) * D;
+        en = a.head.table + ln_clamp_id(it[a.head.neg_off + t], a.head.n_table) * D;
       }
     }
 #pragma unroll
@@ -623,11 +626,11 @@ extern "C" int pxr_ln_residual_fwd_planes_f32(const float* x, const float* res, 
 // Replaces pxr_ln_residual_fwd_f32 + pxr_bpr_loss_fwd_f32 (reference layers.py:670-671 + sasrec.py:86-92): one launch and one
 // pass over `y` less; bit-identical outputs.
 extern "C" int pxr_bpr_loss_reduce_f32(const float* lossrow, int B, int L, float* loss, void* stream);
-extern "C" int pxr_ln_residual_bpr_fwd_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps, int B,
-                                           int L, int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
-                                           uint32_t stream_id, const int64_t* step_dev, const float* table, int64_t n_table,
-                                           const int64_t* items, const int64_t* masked_index, float* pos_score, float* neg_score,
-                                           float* lossrow, float* loss, void* stream) {
+static int ln_residual_bpr_fwd_impl(const float* x, const float* res, const float* gamma, const float* beta, float eps, int B, int L,
+                                    int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed, uint32_t stream_id,
+                                    const int64_t* step_dev, const float* table, int64_t n_table, const int64_t* items,
+                                    const int64_t* masked_index, float* pos_score, float* neg_score, float* lossrow, float* loss,
+                                    int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream) {
   PXR_REQUIRE(x && gamma && beta && y && table && items && masked_index && pos_score && neg_score && lossrow && loss,
               "pxr_ln_residual_bpr_fwd_f32: null pointer");
   PXR_REQUIRE(D > 0 && D % 4 == 0 && B > 0 && L > 0 && n_table > 0, "pxr_ln_residual_bpr_fwd_f32: bad shape");
@@ -639,9 +642,31 @@ extern "C" int pxr_ln_residual_bpr_fwd_f32(const float* x, const float* res, con
   a.step_dev = step_dev;
   a.head.table = table; a.head.items = items; a.head.mask = masked_index; a.head.pos = pos_score; a.head.neg = neg_score;
   a.head.lossrow = lossrow; a.head.n_table = n_table; a.head.B = B; a.head.L = L;
+  a.head.id_bstride = id_bstride; a.head.pos_off = pos_off; a.head.neg_off = neg_off;
   const int rc = launch_ln_fwd<false>(a, (hipStream_t)stream);
   if (rc) return rc;
   return pxr_bpr_loss_reduce_f32(lossrow, B, L, loss, stream);
+}
+extern "C" int pxr_ln_residual_bpr_fwd_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps, int B,
+                                           int L, int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
+                                           uint32_t stream_id, const int64_t* step_dev, const float* table, int64_t n_table,
+                                           const int64_t* items, const int64_t* masked_index, float* pos_score, float* neg_score,
+                                           float* lossrow, float* loss, void* stream) {
+  return ln_residual_bpr_fwd_impl(x, res, gamma, beta, eps, B, L, D, y, xhat, rstd, p_drop, seed, stream_id, step_dev, table, n_table,
+                                  items, masked_index, pos_score, neg_score, lossrow, loss, 2 * (int64_t)(L + 1), 1, L + 2, stream);
+}
+// ... with the id layout as arguments (BprHead::id_bstride): BERT4Rec's aligned masked head (reference IDNet/bert4rec.py:98-111 on
+// the output of layers.py:670-671) passes (3L, L, 2L) for items [B, 3, L] = (masked sequence | original sequence | negatives).
+extern "C" int pxr_ln_residual_bpr_fwd_lay_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps,
+                                               int B, int L, int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
+                                               uint32_t stream_id, const int64_t* step_dev, const float* table, int64_t n_table,
+                                               const int64_t* items, const int64_t* masked_index, float* pos_score,
+                                               float* neg_score, float* lossrow, float* loss, int64_t id_bstride, int64_t pos_off,
+                                               int64_t neg_off, void* stream) {
+  PXR_REQUIRE(id_bstride > 0 && pos_off >= 0 && neg_off >= 0 && pos_off + L <= id_bstride && neg_off + L <= id_bstride,
+              "pxr_ln_residual_bpr_fwd_lay_f32: bad id layout");
+  return ln_residual_bpr_fwd_impl(x, res, gamma, beta, eps, B, L, D, y, xhat, rstd, p_drop, seed, stream_id, step_dev, table, n_table,
+                                  items, masked_index, pos_score, neg_score, lossrow, loss, id_bstride, pos_off, neg_off, stream);
 }
 // the same with y as TWO fp16 planes (planes.cuh "h2", unit scale): the operand of pxr_gemm_h2_f32 -- the image tower, the sequence
 // block of large batches.  A LayerNorm output beyond the fp16 range sets PXR_STATUS_H2_RANGE in the registered status word.
@@ -748,31 +773,58 @@ extern "C" int pxr_ln_bwd_res_f32(const float* dy, const float* xhat, const floa
 // The backward of the block's LAST LayerNorm with the loss head's backward fused in: dy is not read but formed per row from the
 // saved scores (bpr_loss.hip: coef * (E[pos] - E[neg])); coef [B*L] is written for the table-gradient segment sums.  Replaces
 // pxr_bpr_loss_bwd_f32 + pxr_ln_bwd_planes_f32 / pxr_ln_bwd_stat_f32 (gather_mode 0); g_planes and stat are both optional.
+static int bpr_ln_bwd_impl(const float* pos_score, const float* neg_score, const float* table, int64_t n_table, const int64_t* items,
+                           const int64_t* masked_index, int B, int L, float grad_scale, const float* grad_scale_dev, float* coef,
+                           const float* xhat, const float* rstd, const float* gamma, int D, float* dz, float* dx, float* dgamma,
+                           float* dbeta, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws,
+                           int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, float* stat,
+                           const int64_t* layout, void* stream) {
+  PXR_REQUIRE(pos_score && neg_score && table && items && masked_index && coef && B > 0 && L > 0 && n_table > 0,
+              "pxr_bpr_ln_bwd_f32: null pointer / bad shape");
+  BprHead h{};
+  h.table = table; h.items = items; h.mask = masked_index; h.pos = const_cast<float*>(pos_score); h.neg = const_cast<float*>(neg_score);
+  h.coef = coef; h.n_table = n_table; h.B = B; h.L = L; h.grad_scale = grad_scale; h.grad_scale_dev = grad_scale_dev;
+  h.id_bstride = 2 * (int64_t)(L + 1); h.pos_off = 1; h.neg_off = L + 2;
+  if (layout) { h.id_bstride = layout[0]; h.pos_off = layout[1]; h.neg_off = layout[2]; }
+  return ln_bwd_impl(0, nullptr, xhat, rstd, gamma, B * L, D, dz, dx, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes,
+                     g_planes, g_plane_stride, g_panel_rows, stat, stream, &h);
+}
 extern "C" int pxr_bpr_ln_bwd_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
                                   const int64_t* items, const int64_t* masked_index, int B, int L, float grad_scale,
                                   const float* grad_scale_dev, float* coef, const float* xhat, const float* rstd,
                                   const float* gamma, int D, float* dz, float* dx, float* dgamma, float* dbeta, float p_drop,
                                   uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes,
                                   void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, float* stat, void* stream) {
-  PXR_REQUIRE(pos_score && neg_score && table && items && masked_index && coef && B > 0 && L > 0 && n_table > 0,
-              "pxr_bpr_ln_bwd_f32: null pointer / bad shape");
-  BprHead h{};
-  h.table = table; h.items = items; h.mask = masked_index; h.pos = const_cast<float*>(pos_score); h.neg = const_cast<float*>(neg_score);
-  h.coef = coef; h.n_table = n_table; h.B = B; h.L = L; h.grad_scale = grad_scale; h.grad_scale_dev = grad_scale_dev;
-  return ln_bwd_impl(0, nullptr, xhat, rstd, gamma, B * L, D, dz, dx, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes,
-                     g_planes, g_plane_stride, g_panel_rows, stat, stream, &h);
+  return bpr_ln_bwd_impl(pos_score, neg_score, table, n_table, items, masked_index, B, L, grad_scale, grad_scale_dev, coef, xhat, rstd,
+                         gamma, D, dz, dx, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes, g_planes, g_plane_stride,
+                         g_panel_rows, stat, nullptr, stream);
+}
+// ... with the id layout of pxr_ln_residual_bpr_fwd_lay_f32 (BERT4Rec: reference IDNet/bert4rec.py:98-113 under autograd)
+extern "C" int pxr_bpr_ln_bwd_lay_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
+                                      const int64_t* items, const int64_t* masked_index, int B, int L, float grad_scale,
+                                      const float* grad_scale_dev, float* coef, const float* xhat, const float* rstd,
+                                      const float* gamma, int D, float* dz, float* dx, float* dgamma, float* dbeta, float p_drop,
+                                      uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes,
+                                      void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, float* stat, int64_t id_bstride,
+                                      int64_t pos_off, int64_t neg_off, void* stream) {
+  PXR_REQUIRE(id_bstride > 0 && pos_off >= 0 && neg_off >= 0 && pos_off + L <= id_bstride && neg_off + L <= id_bstride,
+              "pxr_bpr_ln_bwd_lay_f32: bad id layout");
+  const int64_t lay[3] = {id_bstride, pos_off, neg_off};
+  return bpr_ln_bwd_impl(pos_score, neg_score, table, n_table, items, masked_index, B, L, grad_scale, grad_scale_dev, coef, xhat, rstd,
+                         gamma, D, dz, dx, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes, g_planes, g_plane_stride,
+                         g_panel_rows, stat, lay, stream);
 }
 // A residual site's backward whose GEMM-facing gradient (dropout applied when p_drop > 0; no fp32 copy of it is written) leaves ONLY as
 // two fp16 planes of gradient * 2^g_exp_dev[0] -- an exponent that exists BEFORE the launch (the previous step's maximum of the same
 // gradient less PXR headroom binades: pxr_h2_sites_update) -- range-checked and saturated (PXR_STATUS_H2_STALE), together with this
 // step's partial maxima in stat[pxr_ln_bwd_partial_rows(rows)] for the next update.  pos_score != NULL: the loss head's backward is
 // fused in as in pxr_bpr_ln_bwd_f32 (dy unused).  Replaces pxr_ln_bwd_stat_f32 / pxr_bpr_ln_bwd_f32 + pxr_h2_split_parts_f32.
-extern "C" int pxr_ln_bwd_h2s_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table, const int64_t* items,
-                                  const int64_t* masked_index, int B, int L, float grad_scale, const float* grad_scale_dev, float* coef,
-                                  const float* dy, const float* xhat, const float* rstd, const float* gamma, int rows, int D, float* dz,
-                                  float* dgamma, float* dbeta, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
-                                  void* ws, int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows,
-                                  const int* g_exp_dev, float* stat, float* zero, int zero_n, void* stream) {
+static int ln_bwd_h2s_impl(const float* pos_score, const float* neg_score, const float* table, int64_t n_table, const int64_t* items,
+                           const int64_t* masked_index, int B, int L, float grad_scale, const float* grad_scale_dev, float* coef,
+                           const float* dy, const float* xhat, const float* rstd, const float* gamma, int rows, int D, float* dz,
+                           float* dgamma, float* dbeta, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
+                           void* ws, int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows,
+                           const int* g_exp_dev, float* stat, float* zero, int zero_n, const int64_t* layout, void* stream) {
   PXR_REQUIRE(g_planes && g_exp_dev && stat, "pxr_ln_bwd_h2s_f32: planes, their device exponent and the statistics buffer are required");
   BprHead h{};
   if (pos_score) {
@@ -780,10 +832,37 @@ extern "C" int pxr_ln_bwd_h2s_f32(const float* pos_score, const float* neg_score
                 "pxr_ln_bwd_h2s_f32: null pointer / bad shape of the fused loss head");
     h.table = table; h.items = items; h.mask = masked_index; h.pos = const_cast<float*>(pos_score); h.neg = const_cast<float*>(neg_score);
     h.coef = coef; h.n_table = n_table; h.B = B; h.L = L; h.grad_scale = grad_scale; h.grad_scale_dev = grad_scale_dev;
+    h.id_bstride = 2 * (int64_t)(L + 1); h.pos_off = 1; h.neg_off = L + 2;
+    if (layout) { h.id_bstride = layout[0]; h.pos_off = layout[1]; h.neg_off = layout[2]; }
   }
   return ln_bwd_impl(0, pos_score ? nullptr : dy, xhat, rstd, gamma, rows, D, dz, nullptr, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws,
                      ws_bytes, g_planes, g_plane_stride, g_panel_rows, stat, stream, pos_score ? &h : nullptr, zero, zero_n, g_exp_dev,
                      p_drop > 0.f ? 1 : 0);
+}
+extern "C" int pxr_ln_bwd_h2s_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table, const int64_t* items,
+                                  const int64_t* masked_index, int B, int L, float grad_scale, const float* grad_scale_dev, float* coef,
+                                  const float* dy, const float* xhat, const float* rstd, const float* gamma, int rows, int D, float* dz,
+                                  float* dgamma, float* dbeta, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
+                                  void* ws, int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows,
+                                  const int* g_exp_dev, float* stat, float* zero, int zero_n, void* stream) {
+  return ln_bwd_h2s_impl(pos_score, neg_score, table, n_table, items, masked_index, B, L, grad_scale, grad_scale_dev, coef, dy, xhat, rstd,
+                         gamma, rows, D, dz, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes, g_planes, g_plane_stride,
+                         g_panel_rows, g_exp_dev, stat, zero, zero_n, nullptr, stream);
+}
+// ... with the fused head's id layout as in pxr_bpr_ln_bwd_lay_f32 (BERT4Rec: reference IDNet/bert4rec.py:98-113 under autograd)
+extern "C" int pxr_ln_bwd_h2s_lay_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
+                                      const int64_t* items, const int64_t* masked_index, int B, int L, float grad_scale,
+                                      const float* grad_scale_dev, float* coef, const float* dy, const float* xhat, const float* rstd,
+                                      const float* gamma, int rows, int D, float* dz, float* dgamma, float* dbeta, float p_drop,
+                                      uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes,
+                                      void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, const int* g_exp_dev, float* stat,
+                                      float* zero, int zero_n, int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream) {
+  PXR_REQUIRE(id_bstride > 0 && pos_off >= 0 && neg_off >= 0 && pos_off + L <= id_bstride && neg_off + L <= id_bstride,
+              "pxr_ln_bwd_h2s_lay_f32: bad id layout");
+  const int64_t lay[3] = {id_bstride, pos_off, neg_off};
+  return ln_bwd_h2s_impl(pos_score, neg_score, table, n_table, items, masked_index, B, L, grad_scale, grad_scale_dev, coef, dy, xhat, rstd,
+                         gamma, rows, D, dz, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes, g_planes, g_plane_stride,
+                         g_panel_rows, g_exp_dev, stat, zero, zero_n, lay, stream);
 }
 static int ln_bwd_impl(int gather_mode, const float* dy, const float* xhat, const float* rstd, const float* gamma, int rows, int D,
                        float* dz, float* dx, float* dgamma, float* dbeta, float p_drop, uint64_t seed, uint32_t stream_id,

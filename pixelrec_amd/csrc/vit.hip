@@ -143,7 +143,8 @@ struct AttnRowsArgs {
   const int64_t* step_dev;
 };
 
-__global__ void __launch_bounds__(256) attn_rows_fwd_kernel(AttnRowsArgs a) {
+template <bool CAUSAL>
+__device__ __forceinline__ void attn_rows_fwd_body(AttnRowsArgs a) {
   if (a.step_dev) a.seed += (uint64_t)a.step_dev[0];
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);       // (b*H + h)*L + i
@@ -154,7 +155,7 @@ __global__ void __launch_bounds__(256) attn_rows_fwd_kernel(AttnRowsArgs a) {
   const int64_t* km = a.keymask + (int64_t)b * a.km_bstride;
   float m = -3.0e38f;
   for (int j = lane; j < a.L; j += 64) {
-    const float v = s[j] / a.sqrt_d + ((km[j] != 0 && j <= i) ? 0.0f : -1e9f);
+    const float v = s[j] / a.sqrt_d + ((km[j] != 0 && (!CAUSAL || j <= i)) ? 0.0f : -1e9f);
     s[j] = v;
     m = fmaxf(m, v);
   }
@@ -173,6 +174,8 @@ __global__ void __launch_bounds__(256) attn_rows_fwd_kernel(AttnRowsArgs a) {
     }
   }
 }
+__global__ void __launch_bounds__(256) attn_rows_fwd_kernel(AttnRowsArgs a) { attn_rows_fwd_body<true>(a); }
+__global__ void __launch_bounds__(256) attn_rows_fwd_bidir_kernel(AttnRowsArgs a) { attn_rows_fwd_body<false>(a); }
 
 // dS = P o (dP - rowsum(dP o P)) / sqrt(d)  with  dP = dPD * keep / (1 - p_drop); in place on dPD
 __global__ void __launch_bounds__(256) attn_rows_bwd_kernel(AttnRowsArgs a, float* dPD) {
@@ -292,9 +295,9 @@ extern "C" int pxr_add_f32(const float* a, const float* b, float* out, int64_t n
 // S [B*H, L, ld] (= Q K^T, unscaled) -> in place the softmax probabilities of the SASRec attention (additive -1e9
 // causal + key mask, reference layers.py:595-604, sasrec.py:119-126); PD (may be NULL when p_drop == 0) receives the
 // dropped probabilities (layers.py:608).  For sequences beyond the fused kernels of attention.hip (L > 128).
-extern "C" int pxr_attn_rows_fwd_f32(float* S, float* PD, const int64_t* keymask, int64_t km_bstride, int B, int H, int L,
-                                     int ld, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
-                                     int d, void* stream) {
+static int attn_rows_fwd_impl(float* S, float* PD, const int64_t* keymask, int64_t km_bstride, int B, int H, int L, int ld,
+                              float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, int d, void* stream,
+                              bool causal) {
   PXR_REQUIRE(S && keymask && B >= 0 && H > 0 && L > 0 && ld >= L && d > 0, "pxr_attn_rows_fwd_f32: bad args");
   PXR_REQUIRE(p_drop >= 0.f && p_drop < 1.f && (p_drop == 0.f || PD), "pxr_attn_rows_fwd_f32: dropout needs PD");
   if (B == 0) return PXR_OK;
@@ -303,8 +306,21 @@ extern "C" int pxr_attn_rows_fwd_f32(float* S, float* PD, const int64_t* keymask
   a.sqrt_d = sqrtf((float)d); a.p_drop = p_drop; a.drop_thr = pxr_drop_threshold(p_drop); a.stream = stream_id;
   a.seed = seed; a.step_dev = step_dev;
   const int64_t rows = (int64_t)B * H * L;
-  hipLaunchKernelGGL(attn_rows_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(causal ? attn_rows_fwd_kernel : attn_rows_fwd_bidir_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
+                     (hipStream_t)stream, a);
   return pxr_check_launch("pxr_attn_rows_fwd_f32");
+}
+extern "C" int pxr_attn_rows_fwd_f32(float* S, float* PD, const int64_t* keymask, int64_t km_bstride, int B, int H, int L,
+                                     int ld, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
+                                     int d, void* stream) {
+  return attn_rows_fwd_impl(S, PD, keymask, km_bstride, B, H, L, ld, p_drop, seed, stream_id, step_dev, d, stream, true);
+}
+// The same rows with the key-padding mask only (no causal term): BERT4Rec's attention beyond 128 positions
+// (reference IDNet/bert4rec.py:150-155).  pxr_attn_rows_bwd_f32 serves both: it reads the saved probabilities.
+extern "C" int pxr_attn_rows_fwd_bidir_f32(float* S, float* PD, const int64_t* keymask, int64_t km_bstride, int B, int H, int L,
+                                           int ld, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
+                                           int d, void* stream) {
+  return attn_rows_fwd_impl(S, PD, keymask, km_bstride, B, H, L, ld, p_drop, seed, stream_id, step_dev, d, stream, false);
 }
 
 // dPD [B*H, L, ld] (gradient w.r.t. the dropped probabilities) -> in place the gradient w.r.t. the unscaled scores S

@@ -147,6 +147,75 @@ class SeqTrainBatcher:
             yield torch.from_numpy(items), torch.from_numpy(mask)
 
 
+
+class BERT4RecTrainDataset(Dataset):
+    """Reference BERT4RecTrainDataset (REC/data/dataset/trainset.py:418-479), per sample: each real position of the window is
+    masked with probability mask_ratio -- the mask token item_num in the masked sequence, a negative outside the sequence, 1 in
+    masked_index -- and the planes are left-padded AFTER masking, so padding is never masked.
+    item = (items [3, L+1] = masked sequence | original sequence | negatives, masked_index [L+1])."""
+
+    def __init__(self, config, dataload):
+        self.dataload = dataload
+        self.item_num = dataload.item_num
+        self.train_seq = dataload.train_feat["item_seq"]
+        self.length = len(self.train_seq)
+        self.max_seq_length = config["MAX_ITEM_LIST_LENGTH"] + 1
+        self.mask_ratio = config["mask_ratio"]
+        self.mask_token = self.item_num
+
+    def __len__(self):
+        return self.length
+
+    def _neg_sample(self, item_set):
+        item = random.randint(1, self.item_num - 1)
+        while item in item_set:
+            item = random.randint(1, self.item_num - 1)
+        return item
+
+    def __getitem__(self, index):
+        item_seq = list(self.train_seq[index])
+        neg, masked, mask = [], [], []
+        for item in item_seq:
+            if random.random() < self.mask_ratio:
+                neg.append(self._neg_sample(item_seq))
+                masked.append(self.mask_token)
+                mask.append(1)
+            else:
+                neg.append(0)
+                masked.append(item)
+                mask.append(0)
+        pad = lambda x: SEQTrainDataset._pad(x, self.max_seq_length)
+        return torch.stack((pad(masked), pad(item_seq), pad(neg))), pad(mask)
+
+
+class BERT4RecTrainBatcher(SeqTrainBatcher):
+    """Vectorised BERT4RecTrainDataset over SeqTrainBatcher's windows and sample order: yields whole (items [B,3,L+1],
+    masked_index [B,L+1]) int64 batches.  Same distribution as the reference (Bernoulli(mask_ratio) per real position, negatives
+    uniform over [1, item_num-1] rejecting the sequence's own items), not the same random stream."""
+
+    def __init__(self, config, dataload, rank=0, world=1, seed=0, drop_last=False):
+        super().__init__(config, dataload, rank=rank, world=world, seed=seed, drop_last=drop_last)
+        self.mask_ratio = float(config["mask_ratio"])
+        self.mask_token = self.item_num
+        self.device_sampler = False      # the device-side sampler draws SASRec's batches only
+
+    def make_batch(self, rows, rng):
+        pos = self.windows[rows]                                   # [B, W], left-padded
+        lens = self.lens[rows]
+        B, W = pos.shape
+        real = np.arange(W)[None, :] >= (W - lens[:, None])        # the sequence's own positions (never the padding)
+        masked = real & (rng.random((B, W)) < self.mask_ratio)
+        neg = rng.integers(1, self.item_num, size=(B, W))
+        for _ in range(64):                                        # rejection of the sequence's own items
+            clash = (neg[:, :, None] == pos[:, None, :]).any(-1) & masked
+            if not clash.any():
+                break
+            neg[clash] = rng.integers(1, self.item_num, size=int(clash.sum()))
+        neg = np.where(masked, neg, 0)
+        inp = np.where(masked, self.mask_token, pos)
+        items = np.stack((inp, pos, neg), axis=1)
+        return items, masked.astype(np.int64)
+
 class SeqEvalDataset(Dataset):
     def __init__(self, config, dataload, phase="valid"):
         self.dataload = dataload

@@ -71,6 +71,19 @@ _SIGNATURES = {
     "pxr_bpr_loss_fwd_f32": (_I, [_P, _P, _I64, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "pxr_bpr_loss_bwd_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
     "pxr_bpr_loss_reduce_f32": (_I, [_P, _I, _I, _P, _P]),
+    # BERT4Rec (aligned, masked id layout; bidirectional attention)
+    "pxr_bpr_loss_fwd_lay_f32": (_I, [_P, _P, _I64, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I64, _I64, _I64, _P]),
+    "pxr_bpr_loss_bwd_lay_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I, _I, _I, _F, _P, _P, _P, _I64, _I64, _I64, _P]),
+    "pxr_ln_residual_bpr_fwd_lay_f32": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _P, _P, _P, _P,
+                                             _P, _P, _I64, _I64, _I64, _P]),
+    "pxr_bpr_ln_bwd_lay_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _F, _U64, _U32, _P,
+                                    _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _P]),
+    "pxr_ln_bwd_h2s_lay_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _F, _U64, _U32,
+                                    _P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _I, _I64, _I64, _I64, _P]),
+    "pxr_seq_occ_sort_lay": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _I64, _P]),
+    "pxr_attn_fwd_bidir_f32": (_I, [_P, _P, _P, _I64, _P, _I64, _I, _I, _I, _I, _P, _I64, _P, _F, _U64, _U32, _P, _P, _I64, _I64, _I,
+                                    _P]),
+    "pxr_attn_rows_fwd_bidir_f32": (_I, [_P, _P, _P, _I64, _I, _I, _I, _I, _F, _U64, _U32, _P, _I, _P]),
     "pxr_ln_residual_bpr_fwd_f32": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _P, _P, _P, _P, _P,
                                          _P, _P]),
     "pxr_bpr_ln_bwd_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _F, _U64, _U32, _P, _P,

@@ -1,5 +1,6 @@
 from .basemodel import BaseModel  # noqa: F401
 from .sasrec import SASRec  # noqa: F401
+from .bert4rec import BERT4Rec  # noqa: F401
 from .mosasrec import MOSASRec  # noqa: F401
 from .fsasrec import FSASRec  # noqa: F401
 from .gru4rec import GRU4Rec  # noqa: F401

@@ -88,11 +88,27 @@ class SASRec(SeqRecCore):
         stream do not change it) -- see DESIGN.md "dead ends"."""
         self._next_items = items_next
 
+    # ---- the id layout of a training batch, as the table-gradient sort sees it (BERT4Rec overrides these three)
+    # the split catch-up claims the input rows from the raw window items[:, 0, :L] of SASRec's [B, 2, L+1] layout
+    _split_catch_up_ok = True
+
+    def _occ_positions(self, items):
+        """Positions per sequence of a batch `items` [B, 2, L+1]: L."""
+        return items.shape[2] - 1
+
+    def _table_rows(self):
+        """Rows of the item table the batch's ids index (the n_table of the occurrence sort and its segment sums)."""
+        return self.item_num
+
+    def _occ_sort(self, items, sp, ws):
+        """Phase 1 of the table gradient: the batch's unique ids into `sp`, the sorted occurrences into `ws`."""
+        ops.sasrec_occ_sort(items, self._table_rows(), sp, ws)
+
     def _start_prefetch(self, items_next):
         """Sort the next batch's ids and replay their rows' missed steps on a side stream (must be issued AFTER this
         batch's own catch-up: a row in both batches is then already current and is skipped, not raced for)."""
-        B, _, W = items_next.shape
-        L = W - 1
+        B = items_next.shape[0]
+        L = self._occ_positions(items_next)
         cap = B * (2 * L + 1)
         sp = self._next_sparse
         if sp is None or sp.cap != cap or sp.idx.device != items_next.device:
@@ -112,7 +128,7 @@ class SASRec(SeqRecCore):
             self._prefetch_stream = side
         side.wait_stream(main)
         with torch.cuda.stream(side):
-            ops.sasrec_occ_sort(items_next, self.item_num, sp, self._next_ws)
+            self._occ_sort(items_next, sp, self._next_ws)
             # a THIN launch (PXR_PREFETCH_BLOCKS workgroups, default one per CU): the replay is pure VALU work with a
             # whole forward + backward pass of time to finish in; it must not take the CUs' wave slots from the GEMMs
             self._table_hooks.catch_up_rows(sp.idx, sp.n, sp.cap, max_blocks=int(os.environ.get("PXR_PREFETCH_BLOCKS", "256")))
@@ -165,7 +181,7 @@ class SASRec(SeqRecCore):
                 self._occ_ws2 = torch.zeros(need2, dtype=torch.uint8, device=items.device)
             hooks = self._table_hooks
             if (hooks is not None and getattr(hooks, "table_update", None) == "lazy" and hasattr(hooks, "catch_up_input_ids")
-                    and self.split_catch_up and self._next_items is None):
+                    and self.split_catch_up and self._split_catch_up_ok and self._next_items is None):
                 # SPLIT catch-up (round 5; graph.GraphedTrainStep turns it on): only the INPUT rows stand between the batch and
                 # the first LayerNorm -- they are claimed from the raw id window items[:, 0, :L] (no sort needed).  Everything
                 # else the step does with the ids before the loss head -- the catch-up of the target / negative rows (the long
@@ -196,12 +212,12 @@ class SASRec(SeqRecCore):
                     side = self._sort_stream = torch.cuda.Stream(device=main.device)
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    ops.sasrec_occ_sort(items, self.item_num, sp, self._occ_ws)
+                    self._occ_sort(items, sp, self._occ_ws)
                 self._sort_pending = True
                 if not hooks.catch_up_ids(items):
                     self._join_sort()
             else:
-                ops.sasrec_occ_sort(items, self.item_num, sp, self._occ_ws)
+                self._occ_sort(items, sp, self._occ_ws)
             if hooks is not None:
                 if not self._sort_pending and self._fork is None:
                     hooks.catch_up_rows(sp.idx, sp.n, sp.cap)
@@ -249,7 +265,7 @@ class SASRec(SeqRecCore):
         side.wait_event(ev)
         with torch.cuda.stream(side):
             hooks.catch_up_ids(items)
-            ops.sasrec_occ_sort(items, self.item_num, sp, self._occ_ws)
+            self._occ_sort(items, sp, self._occ_ws)
         self._sort_pending = True
 
     def _before_head(self):
@@ -259,7 +275,7 @@ class SASRec(SeqRecCore):
     def _after_input_grads(self, dx0, coef, s):
         sp = self._local_sparse
         self._join_sort()
-        ops.sasrec_occ_segsum(self._occ_ws, dx0, s["out"], coef, self.item_num, sp, 1.0, ws2=self._occ_ws2)
+        ops.sasrec_occ_segsum(self._occ_ws, dx0, s["out"], coef, self._table_rows(), sp, 1.0, ws2=self._occ_ws2)
         self.sparse_table_grad = sp
         hook = getattr(self, "_sparse_ready_hook", None)
         if hook is not None:

@@ -437,7 +437,7 @@ class SeqRecCore(BaseModel):
         for i in range(self.n_layers):
             qkv, _, _ = ops.linear_fwd_planes(hp, wp[f"{i}.qkv"], self._p(f"{i}.q.b", span=3), lead_shape=(B, L))
             ctxp, probs = ops.attn_fwd(qkv, keymask, km_bstride, B, H, L, d, pa, seed, 1 + 3 * i, save=train, step_dev=sdv,
-                                       planes=pf)
+                                       planes=pf, causal=self._causal)
             a, _, _ = ops.linear_fwd_planes(ctxp, wp[f"{i}.o"], self._p(f"{i}.o.b"), lead_shape=(B, L))
             h1, xhat1, rstd1, h1p = ops.ln_residual_fwd(a, h, self._p(f"{i}.ln1.w"), self._p(f"{i}.ln1.b"), eps, ph, seed,
                                                         2 + 3 * i, save=train, step_dev=sdv, planes=pf)
@@ -450,7 +450,7 @@ class SeqRecCore(BaseModel):
                 self._before_head()
                 h2, xhat2, rstd2, *self._head_out = ops.ln_residual_bpr_fwd(
                     f2, h1, self._p(f"{i}.ln2.w"), self._p(f"{i}.ln2.b"), eps, *head, p_drop=ph, seed=seed, stream_id=3 + 3 * i,
-                    save=train, step_dev=sdv)
+                    save=train, step_dev=sdv, layout=self._head_layout)
                 r = (h2, xhat2, rstd2, None)
             else:
                 r = ops.ln_residual_fwd(f2, h1, self._p(f"{i}.ln2.w"), self._p(f"{i}.ln2.b"), eps, ph, seed, 3 + 3 * i,
@@ -467,6 +467,15 @@ class SeqRecCore(BaseModel):
     # the transformer block fuses the loss head into its last LayerNorm launch (forward) and into that LayerNorm's backward;
     # blocks that bring their own _encode / _backward_core (gru4rec.py, nextitnet.py) set this to False
     _fused_head = True
+    # attention mask: causal + key padding (SASRec) or key padding only (BERT4Rec: causal = False)
+    _causal = True
+    # (id_bstride, pos_off, neg_off) of the loss head's target / negative ids in `items`; None = SASRec's shifted [B, 2, L+1] windows
+    _head_layout = None
+
+    def _train_inputs(self, items, masked_index):
+        """(idx_bstride, keymask, km_bstride) of a training batch: where the input ids and the attention's key mask sit.  SASRec: the
+        input window items[:, 0, :L] and masked_index (sasrec.py:68,119)."""
+        return 2 * (self.max_seq_length + 1), masked_index, self.max_seq_length
 
     def _encode(self, table, idx, idx_bstride, B, keymask, km_bstride, train: bool, head=None):
         """row ids into `table` -> last-layer states [B, L, D] (sasrec.py:68-86 / :97-109); saves activations when
@@ -490,7 +499,8 @@ class SeqRecCore(BaseModel):
             saved["xhat0"], saved["rstd0"] = xhat0, rstd0
         for i in range(self.n_layers):
             qkv = ops.linear_fwd(h, self._p(f"{i}.q.w", span=3), self._p(f"{i}.q.b", span=3))
-            ctx, probs = ops.attn_fwd(qkv, keymask, km_bstride, B, H, L, d, pa, seed, 1 + 3 * i, save=train, step_dev=sdv)
+            ctx, probs = ops.attn_fwd(qkv, keymask, km_bstride, B, H, L, d, pa, seed, 1 + 3 * i, save=train, step_dev=sdv,
+                                      causal=self._causal)
             a = ops.linear_fwd(ctx, self._p(f"{i}.o.w"), self._p(f"{i}.o.b"))
             h1, xhat1, rstd1 = ops.ln_residual_fwd(a, h, self._p(f"{i}.ln1.w"), self._p(f"{i}.ln1.b"), eps, ph, seed,
                                                    2 + 3 * i, save=train, step_dev=sdv)
@@ -501,7 +511,7 @@ class SeqRecCore(BaseModel):
                 self._before_head()
                 h2, xhat2, rstd2, *self._head_out = ops.ln_residual_bpr_fwd(
                     f2, h1, self._p(f"{i}.ln2.w"), self._p(f"{i}.ln2.b"), eps, *head, p_drop=ph, seed=seed, stream_id=3 + 3 * i,
-                    save=train, step_dev=sdv)
+                    save=train, step_dev=sdv, layout=self._head_layout)
             else:
                 h2, xhat2, rstd2 = ops.ln_residual_fwd(f2, h1, self._p(f"{i}.ln2.w"), self._p(f"{i}.ln2.b"), eps, ph, seed,
                                                        3 + 3 * i, save=train, step_dev=sdv)
@@ -517,14 +527,15 @@ class SeqRecCore(BaseModel):
         B = items.shape[0]
         L = self.max_seq_length
         fused = self._fused_head and os.environ.get("PXR_FUSED_HEAD", "1") != "0"
+        idx_bstride, keymask, km_bstride = self._train_inputs(items, masked_index)
         if fused:
-            out, saved = self._encode(table, items, 2 * (L + 1), B, masked_index, L, train=train, head=(table, items, masked_index))
+            out, saved = self._encode(table, items, idx_bstride, B, keymask, km_bstride, train=train, head=(table, items, masked_index))
             loss, pos, neg = self._head_out
             self._head_out = None
         else:
-            out, saved = self._encode(table, items, 2 * (L + 1), B, masked_index, L, train=train)
+            out, saved = self._encode(table, items, idx_bstride, B, keymask, km_bstride, train=train)
             self._before_head()
-            loss, pos, neg = ops.bpr_loss_fwd(out, table, items, masked_index)
+            loss, pos, neg = ops.bpr_loss_fwd(out, table, items, masked_index, layout=self._head_layout)
         if saved is None:  # eval-mode forward (dropout off): activations are not kept, backward is unavailable
             self._saved = None
         else:
@@ -596,7 +607,7 @@ class SeqRecCore(BaseModel):
         if fused:
             dh = coef = None       # formed inside the last LayerNorm's backward launch (ops.bpr_ln_bwd)
         else:
-            dh, coef = ops.bpr_loss_bwd(s["pos"], s["neg"], table, s["items"], s["mask"], D, self.grad_scale, gsd)
+            dh, coef = ops.bpr_loss_bwd(s["pos"], s["neg"], table, s["items"], s["mask"], D, self.grad_scale, gsd, layout=self._head_layout)
         if s.get("planes"):
             # every GEMM operand as planes: the gradients that only GEMMs read (du, dqkv) exist as planes only
             wp = s["wp"]
@@ -637,7 +648,7 @@ class SeqRecCore(BaseModel):
 
             def head_ln_bwd_planes(xhat, rstd, gamma, dgamma, dbeta, stream_id, bound_with=None):
                 """ln_bwd_planes of the block's last LayerNorm with the loss head's backward fused in: (dz, planes, coef)."""
-                kw = dict(p_drop=ph, seed=seed, stream_id=stream_id, need_dx=ph > 0, step_dev=sdv, defer=defer)
+                kw = dict(p_drop=ph, seed=seed, stream_id=stream_id, need_dx=ph > 0, step_dev=sdv, defer=defer, layout=self._head_layout)
                 if not h2m:
                     dz, _, gp, cf = ops.bpr_ln_bwd(*head_args, xhat, rstd, gamma, dgamma, dbeta, planes=True, **kw)
                     return dz, gp, cf
@@ -646,7 +657,7 @@ class SeqRecCore(BaseModel):
                 site_w[si] = bound_with[0] if bound_with is not None else None
                 if stale:
                     return ops.ln_bwd_h2s(None, xhat, rstd, gamma, dgamma, dbeta, sites, si, st, ph, seed, stream_id, step_dev=sdv,
-                                          defer=defer, bound_with=bound_with, head=head_args)
+                                          defer=defer, bound_with=bound_with, head=head_args, layout=self._head_layout)
                 dz, dx, _, cf = ops.bpr_ln_bwd(*head_args, xhat, rstd, gamma, dgamma, dbeta, stat=st, **kw)
                 return dz, ops.split_h2_parts((dx if dx is not None else dz).view(T, D), st, n_parts, bound_with=bound_with), cf
 
@@ -711,7 +722,7 @@ class SeqRecCore(BaseModel):
             if fused and i == self.n_layers - 1:
                 dz2, dxf2, _, coef = ops.bpr_ln_bwd(*head_args, a["xhat2"], a["rstd2"], self._p(f"{i}.ln2.w"), g(f"{i}.ln2.w"),
                                                     g(f"{i}.ln2.b"), p_drop=ph, seed=seed, stream_id=3 + 3 * i, need_dx=ph > 0,
-                                                    step_dev=sdv, defer=defer)
+                                                    step_dev=sdv, defer=defer, layout=self._head_layout)
             else:
                 dz2, dxf2 = ops.ln_bwd(0, dh, a["xhat2"], a["rstd2"], self._p(f"{i}.ln2.w"), g(f"{i}.ln2.w"),
                                        g(f"{i}.ln2.b"), ph, seed, 3 + 3 * i, need_dx=ph > 0, step_dev=sdv, defer=defer)

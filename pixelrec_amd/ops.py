@@ -740,10 +740,11 @@ class H2Sites:
 
 
 def ln_bwd_h2s(dy, xhat, rstd, gamma, dgamma, dbeta, sites: H2Sites, site: int, stat: torch.Tensor, p_drop=0.0, seed=0, stream_id=0,
-               step_dev=None, defer=None, zero: torch.Tensor | None = None, bound_with=None, head=None):
+               step_dev=None, defer=None, zero: torch.Tensor | None = None, bound_with=None, head=None, layout=None):
     """A residual LayerNorm site's backward whose GEMM-facing gradient leaves ONLY as h2 planes under the site's stale scale
     (pxr_ln_bwd_h2s_f32), + this step's partial maxima in `stat`.  head = (pos, neg, table, items, masked_index, grad_scale,
-    grad_scale_dev): the loss head's backward fused in (dy unused).  -> (dz, Planes, coef | None)."""
+    grad_scale_dev): the loss head's backward fused in (dy unused).  layout = (id_bstride, pos_off, neg_off) of the head's ids (None:
+    SASRec's shifted windows; pxr_ln_bwd_h2s_lay_f32).  -> (dz, Planes, coef | None)."""
     Lb = _l.load()
     D = xhat.shape[-1]
     rows = xhat.numel() // D
@@ -767,10 +768,13 @@ def ln_bwd_h2s(dy, xhat, rstd, gamma, dgamma, dbeta, sites: H2Sites, site: int, 
                  _l.ptr(grad_scale_dev), _l.ptr(coef))
     else:
         hargs = (None, None, None, 0, None, None, 0, 0, 1.0, None, None)
-    _l.check(Lb.pxr_ln_bwd_h2s_f32(*hargs, _l.ptr(dy), _l.ptr(xhat), _l.ptr(rstd), _l.ptr(gamma), rows, D, _l.ptr(dz), _l.ptr(dgamma),
-                                   _l.ptr(dbeta), p_drop, seed, stream_id, _l.ptr(step_dev), _l.ptr(ws), ws_bytes, *_pl(gp),
-                                   _l.ptr(gp.exp_dev), _l.ptr(stat), _l.ptr(zero), zero.numel() if zero is not None else 0,
-                                   _l.stream_ptr()), "pxr_ln_bwd_h2s_f32")
+    args = (*hargs, _l.ptr(dy), _l.ptr(xhat), _l.ptr(rstd), _l.ptr(gamma), rows, D, _l.ptr(dz), _l.ptr(dgamma), _l.ptr(dbeta), p_drop, seed,
+            stream_id, _l.ptr(step_dev), _l.ptr(ws), ws_bytes, *_pl(gp), _l.ptr(gp.exp_dev), _l.ptr(stat), _l.ptr(zero),
+            zero.numel() if zero is not None else 0)
+    if layout is None:
+        _l.check(Lb.pxr_ln_bwd_h2s_f32(*args, _l.stream_ptr()), "pxr_ln_bwd_h2s_f32")
+    else:
+        _l.check(Lb.pxr_ln_bwd_h2s_lay_f32(*args, *layout, _l.stream_ptr()), "pxr_ln_bwd_h2s_lay_f32")
     return dz, gp, coef
 
 
@@ -1020,9 +1024,11 @@ def ln_residual_fwd(x, res, gamma, beta, eps, p_drop=0.0, seed=0, stream_id=0, s
 
 
 def ln_residual_bpr_fwd(x, res, gamma, beta, eps, table, items, masked_index, p_drop=0.0, seed=0, stream_id=0, save=True,
-                        step_dev=None):
+                        step_dev=None, layout=None):
     """The block's last LayerNorm with the loss head's forward fused in (pxr_ln_residual_bpr_fwd_f32):
-    -> (y [B,L,D], xhat, rstd, loss [1], pos [B,L], neg [B,L]) -- what ln_residual_fwd + bpr_loss_fwd return, bit for bit."""
+    -> (y [B,L,D], xhat, rstd, loss [1], pos [B,L], neg [B,L]) -- what ln_residual_fwd + bpr_loss_fwd return, bit for bit.
+    layout = (id_bstride, pos_off, neg_off) of the target / negative ids in `items` (None: SASRec's shifted [B, 2, L+1] windows;
+    BERT4Rec's aligned [B, 3, L]: (3L, L, 2L), pxr_ln_residual_bpr_fwd_lay_f32)."""
     Lb = _l.load()
     _req(x, torch.float32, "x"); _req(table, torch.float32, "table")
     _req(items, torch.int64, "items"); _req(masked_index, torch.int64, "masked_index")
@@ -1036,17 +1042,22 @@ def ln_residual_bpr_fwd(x, res, gamma, beta, eps, table, items, masked_index, p_
     lossrow = torch.empty(B * L, dtype=torch.float32, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     with _gemm_timer(0.0, "ln_fwd_kernel<RESIDUAL + loss head>"):
-        _l.check(Lb.pxr_ln_residual_bpr_fwd_f32(_l.ptr(x), _l.ptr(res), _l.ptr(gamma), _l.ptr(beta), eps, B, L, D, _l.ptr(y),
-                                                _l.ptr(xhat), _l.ptr(rstd), p_drop, seed, stream_id, _l.ptr(step_dev), _l.ptr(table),
-                                                table.shape[0], _l.ptr(items), _l.ptr(masked_index), _l.ptr(pos), _l.ptr(neg),
-                                                _l.ptr(lossrow), _l.ptr(loss), _l.stream_ptr()), "pxr_ln_residual_bpr_fwd_f32")
+        args = (_l.ptr(x), _l.ptr(res), _l.ptr(gamma), _l.ptr(beta), eps, B, L, D, _l.ptr(y), _l.ptr(xhat), _l.ptr(rstd), p_drop, seed,
+                stream_id, _l.ptr(step_dev), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), _l.ptr(pos), _l.ptr(neg),
+                _l.ptr(lossrow), _l.ptr(loss))
+        if layout is None:
+            _l.check(Lb.pxr_ln_residual_bpr_fwd_f32(*args, _l.stream_ptr()), "pxr_ln_residual_bpr_fwd_f32")
+        else:
+            _l.check(Lb.pxr_ln_residual_bpr_fwd_lay_f32(*args, *layout, _l.stream_ptr()), "pxr_ln_residual_bpr_fwd_lay_f32")
     return y, xhat, rstd, loss, pos, neg
 
 
 def bpr_ln_bwd(pos, neg, table, items, masked_index, grad_scale, grad_scale_dev, xhat, rstd, gamma, dgamma, dbeta, p_drop=0.0,
-               seed=0, stream_id=0, need_dx=False, step_dev=None, defer=None, planes: bool = False, stat: torch.Tensor | None = None):
+               seed=0, stream_id=0, need_dx=False, step_dev=None, defer=None, planes: bool = False, stat: torch.Tensor | None = None,
+               layout=None):
     """bpr_loss_bwd + ln_bwd(0, ...) of the block's last LayerNorm in one launch (pxr_bpr_ln_bwd_f32): the gradient w.r.t. the
-    block's output never reaches HBM.  -> (dz, dx | None, planes of the gradient the next GEMMs read | None, coef [B,L])."""
+    block's output never reaches HBM.  -> (dz, dx | None, planes of the gradient the next GEMMs read | None, coef [B,L]).
+    layout: as ln_residual_bpr_fwd (pxr_bpr_ln_bwd_lay_f32)."""
     Lb = _l.load()
     B, L = pos.shape
     D = xhat.shape[-1]
@@ -1063,11 +1074,13 @@ def bpr_ln_bwd(pos, neg, table, items, masked_index, grad_scale, grad_scale_dev,
         ws = _ws.get(ws_bytes, xhat.device)
     assert not (planes and stat is not None)
     gp = Planes.alloc(rows, D, xhat.device) if planes else None
-    _l.check(Lb.pxr_bpr_ln_bwd_f32(_l.ptr(pos), _l.ptr(neg), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), B, L,
-                                   float(grad_scale), _l.ptr(grad_scale_dev), _l.ptr(coef), _l.ptr(xhat), _l.ptr(rstd), _l.ptr(gamma),
-                                   D, _l.ptr(dz), _l.ptr(dx), _l.ptr(dgamma), _l.ptr(dbeta), p_drop, seed, stream_id,
-                                   _l.ptr(step_dev), _l.ptr(ws), ws_bytes, *_pl(gp), _l.ptr(stat), _l.stream_ptr()),
-             "pxr_bpr_ln_bwd_f32")
+    args = (_l.ptr(pos), _l.ptr(neg), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), B, L, float(grad_scale),
+            _l.ptr(grad_scale_dev), _l.ptr(coef), _l.ptr(xhat), _l.ptr(rstd), _l.ptr(gamma), D, _l.ptr(dz), _l.ptr(dx), _l.ptr(dgamma),
+            _l.ptr(dbeta), p_drop, seed, stream_id, _l.ptr(step_dev), _l.ptr(ws), ws_bytes, *_pl(gp), _l.ptr(stat))
+    if layout is None:
+        _l.check(Lb.pxr_bpr_ln_bwd_f32(*args, _l.stream_ptr()), "pxr_bpr_ln_bwd_f32")
+    else:
+        _l.check(Lb.pxr_bpr_ln_bwd_lay_f32(*args, *layout, _l.stream_ptr()), "pxr_bpr_ln_bwd_lay_f32")
     return dz, dx, gp, coef
 
 
@@ -1156,7 +1169,7 @@ def _attn_takes_gemm_path(L, d):
     return L > ATTN_FUSED_MAX_L or (L > 64 and d % 8 != 0)
 
 
-def _attn_long_fwd(qkv, keymask, km_bstride, B, H, L, d, p_drop, seed, stream_id, step_dev):
+def _attn_long_fwd(qkv, keymask, km_bstride, B, H, L, d, p_drop, seed, stream_id, step_dev, causal=True):
     """MAX_ITEM_LIST_LENGTH > 128: S = Q K^T and O = PD V as batched fp32-MFMA GEMMs (grid.z = batch x head) around the
     row kernel pxr_attn_rows_fwd_f32 (mask + softmax + dropout).  Same arithmetic as the fused kernels."""
     Lb = _l.load()
@@ -1165,8 +1178,9 @@ def _attn_long_fwd(qkv, keymask, km_bstride, B, H, L, d, p_drop, seed, stream_id
     sP, sQ, sC = (H * L * Lp, L * Lp), (L * ld, d), (L * D, d)
     gemm_batched(True, True, L, L, d, qkv, 0, ld, qkv, D, ld, P, 0, Lp, bh, H, sQ, sQ, sP)            # q at 0, k at D
     PD = torch.empty_like(P) if p_drop > 0 else None
-    _l.check(Lb.pxr_attn_rows_fwd_f32(_l.ptr(P), _l.ptr(PD), _l.ptr(keymask), km_bstride, B, H, L, Lp, p_drop, seed,
-                                      stream_id, _l.ptr(step_dev), d, _l.stream_ptr()), "pxr_attn_rows_fwd_f32")
+    rows_fwd = Lb.pxr_attn_rows_fwd_f32 if causal else Lb.pxr_attn_rows_fwd_bidir_f32
+    _l.check(rows_fwd(_l.ptr(P), _l.ptr(PD), _l.ptr(keymask), km_bstride, B, H, L, Lp, p_drop, seed, stream_id, _l.ptr(step_dev), d,
+                      _l.stream_ptr()), "pxr_attn_rows_fwd_f32")
     ctx = torch.empty(B, L, D, dtype=torch.float32, device=qkv.device)
     gemm_batched(True, False, L, d, L, PD if PD is not None else P, 0, Lp, qkv, 2 * D, ld, ctx, 0, D, bh, H, sP, sQ, sC)
     return ctx, (P, PD)
@@ -1193,15 +1207,16 @@ def attn_planes_supported(L: int, d: int) -> bool:
 
 
 def attn_fwd(qkv, keymask, km_bstride, B, H, L, d, p_drop=0.0, seed=0, stream_id=0, save=True, step_dev=None,
-             planes: bool = False):
+             planes: bool = False, causal: bool = True):
     """qkv [B,L,3*H*d] fused projection output -> (ctx [B,L,H*d], probs [B,H,L,L] | None).  planes=True: ctx is returned
     as Planes [B*L, H*d] INSTEAD of the fp32 tensor (written by the fused kernel where it serves the shape, by a split
-    launch otherwise)."""
+    launch otherwise).  causal=False: the key-padding mask only (BERT4Rec; pxr_attn_fwd_bidir_f32 / pxr_attn_rows_fwd_bidir_f32);
+    attn_bwd serves both masks (it works from the saved probabilities)."""
     Lb = _l.load()
     _req(qkv, torch.float32, "qkv"); _req(keymask, torch.int64, "keymask", contiguous=False)
     D = H * d
     if _attn_takes_gemm_path(L, d):
-        ctx, saved = _attn_long_fwd(qkv, keymask, km_bstride, B, H, L, d, p_drop, seed, stream_id, step_dev)
+        ctx, saved = _attn_long_fwd(qkv, keymask, km_bstride, B, H, L, d, p_drop, seed, stream_id, step_dev, causal=causal)
         return (split_planes(ctx.view(B * L, D)) if planes else ctx), (saved if save else None)
     fused_p = planes and attn_planes_supported(L, d)
     h2 = planes == "h2"
@@ -1211,9 +1226,12 @@ def attn_fwd(qkv, keymask, km_bstride, B, H, L, d, p_drop=0.0, seed=0, stream_id
     probs = torch.empty(B, H, L, L, dtype=torch.float32, device=qkv.device) if save else None
     base = qkv.data_ptr()
     q, k, v = _l.c_void_p(base), _l.c_void_p(base + 4 * D), _l.c_void_p(base + 8 * D)
-    _l.check((Lb.pxr_attn_fwd_h2_f32 if h2 else Lb.pxr_attn_fwd_planes_f32)(q, k, v, 3 * D, _l.ptr(keymask), km_bstride, B, H, L, d, _l.ptr(ctx), D,
-                                        _l.ptr(probs), p_drop, seed, stream_id, _l.ptr(step_dev), *_pl(cp_), _l.stream_ptr()),
-             "pxr_attn_fwd_f32")
+    args = (q, k, v, 3 * D, _l.ptr(keymask), km_bstride, B, H, L, d, _l.ptr(ctx), D, _l.ptr(probs), p_drop, seed, stream_id,
+            _l.ptr(step_dev), *_pl(cp_))
+    if causal:
+        _l.check((Lb.pxr_attn_fwd_h2_f32 if h2 else Lb.pxr_attn_fwd_planes_f32)(*args, _l.stream_ptr()), "pxr_attn_fwd_f32")
+    else:
+        _l.check(Lb.pxr_attn_fwd_bidir_f32(*args, int(h2), _l.stream_ptr()), "pxr_attn_fwd_bidir_f32")
     if planes and not fused_p:
         cp_ = split_planes(ctx.view(B * L, D))
     return (cp_ if planes else ctx), probs
@@ -1255,8 +1273,9 @@ def attn_bwd(dctx, qkv, probs, B, H, L, d, p_drop=0.0, seed=0, stream_id=0, step
 
 
 # ------------------------------------------------------------------------------------------------ loss head
-def bpr_loss_fwd(out, table, items, masked_index):
-    """-> (loss [1] on device, pos_score [B,L], neg_score [B,L])   (sasrec.py:88-92)."""
+def bpr_loss_fwd(out, table, items, masked_index, layout=None):
+    """-> (loss [1] on device, pos_score [B,L], neg_score [B,L])   (sasrec.py:88-92).  layout = (id_bstride, pos_off, neg_off) of the
+    target / negative ids (None: SASRec's shifted windows; BERT4Rec: (3L, L, 2L), bert4rec.py:98-111)."""
     Lb = _l.load()
     _req(out, torch.float32, "out"); _req(table, torch.float32, "table")
     _req(items, torch.int64, "items"); _req(masked_index, torch.int64, "masked_index")
@@ -1266,22 +1285,27 @@ def bpr_loss_fwd(out, table, items, masked_index):
     neg = torch.empty(B, L, dtype=torch.float32, device=dev)
     lossrow = torch.empty(B * L, dtype=torch.float32, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
-    _l.check(Lb.pxr_bpr_loss_fwd_f32(_l.ptr(out), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index),
-                                     B, L, D, _l.ptr(pos), _l.ptr(neg), _l.ptr(lossrow), _l.ptr(loss),
-                                     _l.stream_ptr()), "pxr_bpr_loss_fwd_f32")
+    args = (_l.ptr(out), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), B, L, D, _l.ptr(pos), _l.ptr(neg),
+            _l.ptr(lossrow), _l.ptr(loss))
+    if layout is None:
+        _l.check(Lb.pxr_bpr_loss_fwd_f32(*args, _l.stream_ptr()), "pxr_bpr_loss_fwd_f32")
+    else:
+        _l.check(Lb.pxr_bpr_loss_fwd_lay_f32(*args, *layout, _l.stream_ptr()), "pxr_bpr_loss_fwd_lay_f32")
     return loss, pos, neg
 
 
-def bpr_loss_bwd(pos, neg, table, items, masked_index, D, grad_scale=1.0, grad_scale_dev=None):
+def bpr_loss_bwd(pos, neg, table, items, masked_index, D, grad_scale=1.0, grad_scale_dev=None, layout=None):
     """-> (dout [B,L,D], coef [B,L])."""
     Lb = _l.load()
     B, L = pos.shape
     dout = torch.empty(B, L, D, dtype=torch.float32, device=pos.device)
     coef = torch.empty(B, L, dtype=torch.float32, device=pos.device)
-    _l.check(Lb.pxr_bpr_loss_bwd_f32(_l.ptr(pos), _l.ptr(neg), _l.ptr(table), table.shape[0], _l.ptr(items),
-                                     _l.ptr(masked_index), B, L, D, float(grad_scale), _l.ptr(grad_scale_dev), _l.ptr(dout),
-                                     _l.ptr(coef),
-                                     _l.stream_ptr()), "pxr_bpr_loss_bwd_f32")
+    args = (_l.ptr(pos), _l.ptr(neg), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), B, L, D, float(grad_scale),
+            _l.ptr(grad_scale_dev), _l.ptr(dout), _l.ptr(coef))
+    if layout is None:
+        _l.check(Lb.pxr_bpr_loss_bwd_f32(*args, _l.stream_ptr()), "pxr_bpr_loss_bwd_f32")
+    else:
+        _l.check(Lb.pxr_bpr_loss_bwd_lay_f32(*args, *layout, _l.stream_ptr()), "pxr_bpr_loss_bwd_lay_f32")
     return dout, coef
 
 
@@ -1472,6 +1496,16 @@ def sasrec_occ_sort(items, n_table, sp: SparseRows, ws: torch.Tensor):
     B, _, W = items.shape
     _l.check(Lb.pxr_sasrec_occ_sort(_l.ptr(items), B, W - 1, n_table, _l.ptr(sp.idx), _l.ptr(sp.n), _l.ptr(ws),
                                     ws.numel(), _l.stream_ptr()), "pxr_sasrec_occ_sort")
+
+
+def seq_occ_sort(items, L: int, layout, n_table, sp: SparseRows, ws: torch.Tensor):
+    """sasrec_occ_sort for another id layout: layout = (id_bstride, in_off, pos_off, neg_off) of the L positions of each sequence
+    (BERT4Rec's [B, 3, L]: (3L, 0, L, 2L); pxr_seq_occ_sort_lay).  Phase 2 is sasrec_occ_segsum, unchanged.  `ws`: occ_ws_bytes(B, L)."""
+    Lb = _l.load()
+    _req(items, torch.int64, "items")
+    B = items.shape[0]
+    _l.check(Lb.pxr_seq_occ_sort_lay(_l.ptr(items), B, L, *layout, n_table, _l.ptr(sp.idx), _l.ptr(sp.n), _l.ptr(ws), ws.numel(),
+                                     _l.stream_ptr()), "pxr_seq_occ_sort_lay")
 
 
 def occ_split_ws_bytes(B: int, L: int, D: int) -> int:

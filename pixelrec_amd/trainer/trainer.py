@@ -525,7 +525,7 @@ class Trainer:
         out, last = (m.encode_last(user_d, self.item_feature) if (self.use_modality or not has_item_table(m))
                      else m.encode_last(user_d))
         B, L, D = out.shape
-        idx, _ = ops.score_topk(last, L * D, B, self.item_feature.data, max(self.config["topk"]), ptr, items,
+        idx, _ = ops.score_topk(last, last.stride(0), B, self.item_feature.data, max(self.config["topk"]), ptr, items,
                                 table_planes=getattr(self, "_item_planes", None), table_norm_max=getattr(self, "_item_norm_max", None))
         return idx, positive_i
 
