@@ -35,8 +35,10 @@ extern "C" {
 /* The ABI revision this header describes.  pxr_version() of the loaded library must EQUAL it: entries may change meaning between
  * revisions while keeping their names (0.2.0 -> 0.3.0: the `stat` buffers of pxr_ln_bwd_stat_f32 / pxr_attn_bwd_stat_f32 became
  * pxr_ln_bwd_partial_rows(rows) / 64 words instead of one caller-zeroed word, and pxr_ln_bwd_stat_f32 gained `zero`, `zero_n`),
- * so a caller built against another revision must refuse to run instead of writing out of bounds (pixelrec_amd/lib.py does). */
-#define PXR_ABI_VERSION 300
+ * so a caller built against another revision must refuse to run instead of writing out of bounds (pixelrec_amd/lib.py does).
+ * 0.3.0 -> 0.3.1: one entry per kernel family -- the plane-writing, h2, bidirectional and id-layout variants were folded into the
+ * plain names, which now take the most general argument list (planes triple + planes_fmt, causal, id layout); the shims died. */
+#define PXR_ABI_VERSION 301
 int pxr_version(void);                 /* major*10000 + minor*100 + patch; == PXR_ABI_VERSION of the header it was built from */
 const char* pxr_last_error(void);      /* message of the last failing call on this thread */
 const char* pxr_target_arch(void);     /* "gfx950" */
@@ -118,18 +120,16 @@ int pxr_ids_to_compact_i64(const int64_t* ids, int64_t n, const int64_t* uniq_id
  * AdamW catch-up. */
 int pxr_shard_first_rows_i64(const int64_t* ids_all, int W, int64_t cap, int rank, int64_t n_table,
                              int64_t* local_rows, void* stream);
-/* The same for the three uses of the table inside SASRec.forward (sasrec.py:68-74,88-89) without materialising the
- * [B,2,L+1,D] gather: items[B,2,L+1]; dx0 = grad of (table row + pos) [B*L,D]; out = last-layer states [B*L,D];
- * coef[B*L] from pxr_bpr_loss_bwd_f32.  n_occ = 3*B*L for the workspace size. */
-int pxr_sasrec_embed_grad_f32(const int64_t* items, int B, int L, const float* dx0, const float* out,
-                              const float* coef, int D, int64_t n_table, float scale, int64_t* uniq_idx,
-                              float* uniq_rows, int32_t* n_uniq_dev, void* ws, int64_t ws_bytes, void* stream);
-
-/* The two phases separately: phase 1 depends on `items` only and may run before the forward pass (the lazy table
- * optimizer brings exactly these unique rows up to date before they are read); `ws` carries the sorted occurrences to
- * phase 2 and must not be touched in between. */
-int pxr_sasrec_occ_sort(const int64_t* items, int B, int L, int64_t n_table, int64_t* uniq_idx, int32_t* n_uniq_dev,
-                        void* ws, int64_t ws_bytes, void* stream);
+/* The table gradient of the three uses of the table inside SASRec.forward (sasrec.py:68-74,88-89) without materialising the
+ * [B,2,L+1,D] gather, in two phases: phase 1 depends on `items` only and may run before the forward pass (the lazy table
+ * optimizer brings exactly these unique rows up to date before they are read); `ws` (pxr_embed_grad_ws_bytes(3*B*L) bytes)
+ * carries the sorted occurrences to phase 2 and must not be touched in between.  Phase 1: the input ids at in_off, targets at
+ * pos_off, negatives at neg_off of each sequence's id_bstride ids -- SASRec's items [B,2,L+1]: (2(L+1), 0, 1, L+2); BERT4Rec's
+ * [B,3,L]: (3L, 0, L, 2L), the table's three uses in bert4rec.py:76-81 under autograd.  Phase 2: dx0 = grad of (table row + pos)
+ * [B*L,D]; out = last-layer states [B*L,D]; coef[B*L] from pxr_bpr_loss_bwd_f32, whatever the layout.  Deterministic, no float
+ * atomics, row 0 dropped, every other row (BERT4Rec's mask token item_num included) ordinary. */
+int pxr_seq_occ_sort(const int64_t* items, int B, int L, int64_t id_bstride, int64_t in_off, int64_t pos_off, int64_t neg_off,
+                     int64_t n_table, int64_t* uniq_idx, int32_t* n_uniq_dev, void* ws, int64_t ws_bytes, void* stream);
 int pxr_sasrec_occ_segsum(const void* ws, int64_t ws_bytes, int B, int L, const float* dx0, const float* out,
                           const float* coef, int D, int64_t n_table, float scale, const int32_t* n_uniq_dev,
                           float* uniq_rows, void* stream);
@@ -147,23 +147,29 @@ int pxr_sasrec_occ_segsum_split(const void* ws, int64_t ws_bytes, int B, int L, 
 
 /* ---- LayerNorm sites ---------------------------------------------------------------------------------------- */
 /* y = dropout(LN(table[idx[b*idx_bstride+t]] + pos[t]))       sasrec.py:68,77-82 (train) / :99-104 (predict).
- * xhat [B*L,D] / rstd [B*L] are saved for the backward and may be NULL for inference. */
+ * xhat [B*L,D] / rstd [B*L] are saved for the backward and may be NULL for inference.  y is ALSO written as planes (see
+ * "pre-split operands" below; y_planes NULL: none) in the format planes_fmt: 0 = bf16x3, 1 = h2 (y_planes then required). */
 int pxr_input_ln_fwd_f32(const float* table, int64_t n_table, const int64_t* idx, int64_t idx_bstride,
                          const float* pos, const float* gamma, const float* beta, float eps, int B, int L, int D,
                          float* y, float* xhat, float* rstd, float p_drop, uint64_t seed, uint32_t stream_id,
-                         const int64_t* step_dev, void* stream);
-/* y = LN(dropout(x) + res)                                      layers.py:614-615 and :670-671 */
+                         const int64_t* step_dev, void* y_planes, int64_t y_plane_stride, int64_t y_panel_rows, int planes_fmt,
+                         void* stream);
+/* y = LN(dropout(x) + res)                                      layers.py:614-615 and :670-671
+ * y as planes as above; y may then be NULL (h2: y_planes required). */
 int pxr_ln_residual_fwd_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps,
                             int rows, int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
-                            uint32_t stream_id, const int64_t* step_dev, void* stream);
+                            uint32_t stream_id, const int64_t* step_dev, void* y_planes, int64_t y_plane_stride,
+                            int64_t y_panel_rows, int planes_fmt, void* stream);
 /* autograd of either site.  gather_mode=1: dy is w.r.t. the dropped output, dz = grad of (table row + pos).
  * gather_mode=0: dz = grad w.r.t. res, dx (optional) = grad w.r.t. x.  dgamma/dbeta are overwritten; pass both NULL to
- * defer the final reduction (partials stay in ws, reduce them with pxr_reduce_partials_multi_f32). */
+ * defer the final reduction (partials stay in ws, reduce them with pxr_reduce_partials_multi_f32).  g_planes (residual sites
+ * only; NULL: none): the gradient the next GEMMs read (dx when given, else dz) also as bf16x3 planes. */
 int64_t pxr_ln_bwd_ws_bytes(int rows, int D);
 int pxr_ln_bwd_partial_rows(int rows);   /* rows of the [P, 2*D] partial buffer left in ws when dgamma/dbeta are NULL */
 int pxr_ln_bwd_f32(int gather_mode, const float* dy, const float* xhat, const float* rstd, const float* gamma,
                    int rows, int D, float* dz, float* dx, float* dgamma, float* dbeta, float p_drop, uint64_t seed,
-                   uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes, void* stream);
+                   uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes, void* g_planes,
+                   int64_t g_plane_stride, int64_t g_panel_rows, void* stream);
 
 /* ---- fp32 MFMA GEMMs (v_mfma_f32_32x32x2_f32) --------------------------------------------------------------- */
 /* General: C[M,N] = A_op x B_op; a_kc/b_kc select k-contiguous ([M][K] / [N][K]) or x-contiguous ([K][M] / [K][N])
@@ -224,8 +230,8 @@ int pxr_split_planes_multi_f32(int n, const float* const* x, const int64_t* rows
  *                            BIAS_GELU_GRAD | BIAS_ACT_GRAD | BIAS_ADD | BIAS_QGELU | BIAS_QGELU_GRAD | BIAS_RELU) or [K][N] (input gradient; NONE | ADD | MUL);
  *                            exponents immediate or read from *_exp_dev; c_fmt 0: output planes as three bf16 planes, 1: as two
  *                            fp16 planes holding C 2^(*c_exp_dev) (unit scale when null)
- *   pxr_ln_residual_fwd_h2_f32 / pxr_input_ln_fwd_h2_f32 / pxr_attn_fwd_h2_f32 / pxr_tower_attn_fwd_h2_f32: the plane-writing
- *                            producers (same arguments as their *_planes_f32 versions) with h2 planes, unit scale */
+ *   pxr_ln_residual_fwd_f32 / pxr_input_ln_fwd_f32 / pxr_attn_fwd_f32 / pxr_tower_attn_fwd_f32 with planes_fmt 1: the
+ *                            plane-writing producers with h2 planes, unit scale */
 int pxr_split_h2_multi_f32(int n, const float* const* x, const int64_t* rows, const int64_t* cols, const int64_t* ldx,
                            void* const* planes, const int64_t* plane_stride, const int64_t* panel_rows, const int* scale_exp,
                            void* stream);
@@ -281,8 +287,9 @@ int pxr_attn_bwd_stat_f32(const float* dctx, int64_t ld_ctx, const float* q, con
  * pxr_ln_bwd_h2s_f32: a residual LayerNorm site's backward (reference layers.py:614-615 / :670-671 under autograd); dz as fp32, the
  *   gradient the next GEMMs read (dropout applied when p_drop > 0; no fp32 copy) ONLY as two fp16 planes of gradient * 2^g_exp_dev[0];
  *   stat[pxr_ln_bwd_partial_rows(rows)] partial maxima; zero / zero_n as pxr_ln_bwd_stat_f32.  pos_score != NULL: the loss head's
- *   backward fused in as in pxr_bpr_ln_bwd_f32 (dy unused, rows == B * L); NULL: the eleven head arguments are ignored.
- * pxr_attn_bwd_h2s_f32: dq | dk | dv ONLY as such planes (column ranges as in pxr_attn_bwd_planes_f32) + the 64 spread maxima.
+ *   backward fused in as in pxr_bpr_ln_bwd_f32, with its id layout (dy unused, rows == B * L); NULL: the eleven head arguments
+ *   are ignored (the id layout is still checked).
+ * pxr_attn_bwd_h2s_f32: dq | dk | dv ONLY as such planes (column ranges as in pxr_attn_bwd_f32) + the 64 spread maxima.
  * pxr_h2_sites_update: n <= 16 sites; per site m = max(maximum of its n_parts[s] partial maxima, run_max[s] * decay) (the maxima are
  *   heavy-tailed: the scale follows a decaying maximum of the recent steps; run_max persistent, zero-initialised) -> exps[s] (m 2^e in
  *   [2^(13-headroom), 2^(14-headroom))), stats[2 s ..] = (max 2^headroom, rows[s] max 2^headroom) and, where bound_b[s] (the largest
@@ -295,57 +302,21 @@ int pxr_ln_bwd_h2s_f32(const float* pos_score, const float* neg_score, const flo
                        const float* dy, const float* xhat, const float* rstd, const float* gamma, int rows, int D, float* dz,
                        float* dgamma, float* dbeta, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
                        void* ws, int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows,
-                       const int* g_exp_dev, float* stat, float* zero, int zero_n, void* stream);
+                       const int* g_exp_dev, float* stat, float* zero, int zero_n, int64_t id_bstride, int64_t pos_off,
+                       int64_t neg_off, void* stream);
 int pxr_attn_bwd_h2s_f32(const float* dctx, int64_t ld_ctx, const float* q, const float* k, const float* v, int64_t ld,
                          const float* probs, int B, int H, int L, int d, float p_drop, uint64_t seed, uint32_t stream_id,
                          const int64_t* step_dev, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, int g_cols,
                          int col_q, int col_k, int col_v, const int* g_exp_dev, float* stat, void* stream);
 int pxr_h2_sites_update(int n, const float* const* parts, const int* n_parts, const int* rows, const float* const* bound_b,
                         float bound_factor, int headroom, float decay, float* run_max, int* exps, float* stats, int* bexp, void* stream);
-int pxr_ln_residual_fwd_h2_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps, int rows,
-                               int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed, uint32_t stream_id,
-                               const int64_t* step_dev, void* y_planes, int64_t y_plane_stride, int64_t y_panel_rows,
-                               void* stream);
-int pxr_input_ln_fwd_h2_f32(const float* table, int64_t n_table, const int64_t* idx, int64_t idx_bstride, const float* pos,
-                            const float* gamma, const float* beta, float eps, int B, int L, int D, float* y, float* xhat,
-                            float* rstd, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
-                            void* y_planes, int64_t y_plane_stride, int64_t y_panel_rows, void* stream);
-int pxr_attn_fwd_h2_f32(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask, int64_t km_bstride,
-                        int B, int H, int L, int d, float* ctx, int64_t ld_ctx, float* probs, float p_drop, uint64_t seed,
-                        uint32_t stream_id, const int64_t* step_dev, void* ctx_planes, int64_t ctx_plane_stride,
-                        int64_t ctx_panel_rows, void* stream);
-int pxr_tower_attn_fwd_h2_f32(const float* q, const float* k, const float* v, int64_t ld, int64_t images, int heads, int T, int d,
-                              float scale, float* ctx, int64_t ld_ctx, void* ctx_planes, int64_t ctx_plane_stride,
-                              int64_t ctx_panel_rows, float* lse, void* stream);
 
-/* Producers that write their output straight as planes (same arguments as the functions they extend + the planes matrix;
- * planes == NULL: exactly the plain function).  LayerNorm sites: y as planes; LayerNorm backward (residual sites): the
- * gradient the next GEMMs read (dx when given, else dz); attention: ctx as the [B*L, H*d] matrix (ctx may then be NULL),
- * dq | dk | dv as column ranges starting at col_q / col_k / col_v of one [B*L, g_cols] matrix (dq, dk, dv may then all be
- * NULL).  pxr_attn_planes_supported(L, d): whether the fused attention kernels that can do so serve the shape. */
-int pxr_input_ln_fwd_planes_f32(const float* table, int64_t n_table, const int64_t* idx, int64_t idx_bstride,
-                                const float* pos, const float* gamma, const float* beta, float eps, int B, int L, int D,
-                                float* y, float* xhat, float* rstd, float p_drop, uint64_t seed, uint32_t stream_id,
-                                const int64_t* step_dev, void* y_planes, int64_t y_plane_stride, int64_t y_panel_rows,
-                                void* stream);
-int pxr_ln_residual_fwd_planes_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps,
-                                   int rows, int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
-                                   uint32_t stream_id, const int64_t* step_dev, void* y_planes, int64_t y_plane_stride,
-                                   int64_t y_panel_rows, void* stream);
-int pxr_ln_bwd_planes_f32(int gather_mode, const float* dy, const float* xhat, const float* rstd, const float* gamma,
-                          int rows, int D, float* dz, float* dx, float* dgamma, float* dbeta, float p_drop, uint64_t seed,
-                          uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes, void* g_planes,
-                          int64_t g_plane_stride, int64_t g_panel_rows, void* stream);
+/* Producers that write their output straight as planes: pxr_input_ln_fwd_f32 / pxr_ln_residual_fwd_f32 (y), pxr_ln_bwd_f32
+ * (residual sites: the gradient the next GEMMs read, dx when given, else dz), pxr_attn_fwd_f32 (ctx as the [B*L, H*d] matrix;
+ * ctx may then be NULL), pxr_attn_bwd_f32 (dq | dk | dv as column ranges starting at col_q / col_k / col_v of one [B*L, g_cols]
+ * matrix; dq, dk, dv may then all be NULL), pxr_adamw_flat_tab_f32 and pxr_score_topk_f32 (pre-split operands); planes NULL:
+ * fp32 outputs only.  pxr_attn_planes_supported(L, d): whether the fused attention kernels that can do so serve the shape. */
 int pxr_attn_planes_supported(int L, int d);
-int pxr_attn_fwd_planes_f32(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
-                            int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx, float* probs,
-                            float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ctx_planes,
-                            int64_t ctx_plane_stride, int64_t ctx_panel_rows, void* stream);
-int pxr_attn_bwd_planes_f32(const float* dctx, int64_t ld_ctx, const float* q, const float* k, const float* v, int64_t ld,
-                            const float* probs, int B, int H, int L, int d, float* dq, float* dk, float* dv, int64_t ld_d,
-                            float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* g_planes,
-                            int64_t g_plane_stride, int64_t g_panel_rows, int g_cols, int col_q, int col_k, int col_v,
-                            void* stream);
 /* Measurement hook of bench.py (no reference analogue): registers two uint64 in DEVICE memory (NULL unregisters).  Every later
  * main-pass launch of the fused scoring's DEFAULT (reduced-product) threshold kernel adds the shader-clock cycles (s_memtime) and the constant 100 MHz reference ticks
  * (s_memrealtime) that its workgroup 0 lived through: clk2[0] / clk2[1] * 0.1 = the clock in GHz the part sustained INSIDE those
@@ -369,12 +340,12 @@ int pxr_grouped_dw_planes_f32(int n, const void* const* dy, const int64_t* dy_pl
 /* Fused self-attention of a tower block, forward (csrc/tower_attn.hip): per (image, head)
  * ctx[b*T + t, 64 h ..] = softmax_t'(scale * q_t . k_t') v_t'; no mask, no dropout (HF CLIPAttention.forward as the item tower of
  * REC/model/modules.py runs it).  q/k/v fp32, element (b, t, h, c) at p[(b*T + t)*ld + 64 h + c]; head size 64, T <= 288
- * (pxr_tower_attn_supported).  Outputs: ctx fp32 [images*T, ld_ctx] and/or ctx as planes (at least one); lse (optional)
- * [images*heads, T] = log sum_t' exp(scale * q.k).  The score matrix never exists in memory. */
+ * (pxr_tower_attn_supported).  Outputs: ctx fp32 [images*T, ld_ctx] and/or ctx as planes (at least one; planes_fmt 0 = bf16x3,
+ * 1 = h2); lse (optional) [images*heads, T] = log sum_t' exp(scale * q.k).  The score matrix never exists in memory. */
 int pxr_tower_attn_supported(int T, int d);
 int pxr_tower_attn_fwd_f32(const float* q, const float* k, const float* v, int64_t ld, int64_t images, int heads, int T, int d,
                            float scale, float* ctx, int64_t ld_ctx, void* ctx_planes, int64_t ctx_plane_stride,
-                           int64_t ctx_panel_rows, float* lse, void* stream);
+                           int64_t ctx_panel_rows, int planes_fmt, float* lse, void* stream);
 /* Backward of pxr_tower_attn_fwd_f32 (the trainable blocks of the tower): dq | dk | dv from dctx, recomputing the
  * probabilities from the forward's lse -- no [images*heads, T, T] matrix is saved or written.  ctx = the forward's fp32
  * output (for delta = rowsum(dctx o ctx)); delta_ws = [images*heads, T] floats of scratch; dq / dk / dv are addressed like
@@ -396,10 +367,12 @@ int pxr_token_mean_relu_bwd_f32(const float* dout, const float* act, float* dact
 /* SASRec attention for MAX_ITEM_LIST_LENGTH > 128 (beyond the fused kernels behind pxr_attn_fwd_f32): the scores come
  * from a batched GEMM (S = Q K^T, unscaled, [B*H, L, ld]); this turns them in place into softmax(S / sqrt(d) + mask) with
  * the reference's additive -1e9 causal + key mask (model/layers.py:595-604, model/IDNet/sasrec.py:119-126) and writes
- * the dropped probabilities (layers.py:608; same counter hash and element numbering as pxr_attn_fwd_f32) to PD. */
+ * the dropped probabilities (layers.py:608; same counter hash and element numbering as pxr_attn_fwd_f32) to PD.  causal = 0:
+ * the key-padding mask only (BERT4Rec, bert4rec.py:150-155). */
 int pxr_attn_rows_fwd_f32(float* S, float* PD, const int64_t* keymask, int64_t km_bstride, int B, int H, int L, int ld,
-                          float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, int d, void* stream);
-/* in place on dPD (gradient w.r.t. the dropped probabilities): gradient w.r.t. the unscaled scores */
+                          float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, int d, int causal,
+                          void* stream);
+/* in place on dPD (gradient w.r.t. the dropped probabilities): gradient w.r.t. the unscaled scores (either mask) */
 int pxr_attn_rows_bwd_f32(const float* P, float* dPD, int B, int H, int L, int ld, float p_drop, uint64_t seed,
                           uint32_t stream_id, const int64_t* step_dev, int d, void* stream);
 /* out = a + b (n floats, n % 4 == 0): the two branches of a residual-stream gradient */
@@ -440,13 +413,18 @@ int pxr_colsum_f32(const float* x, int64_t ldx, int M, int N, float* out, void* 
 /* ctx = softmax(q k^T / sqrt(d) + mask) v with the reference's additive -1e9 causal+padding mask
  * (layers.py:590-612, sasrec.py:119-126).  q/k/v element (b,t,h,c) at p[(b*L+t)*ld + h*d + c] (fused QKV output);
  * key j of batch b is real iff keymask[b*km_bstride + j] != 0 (masked_index in training, item_seq in predict).
- * ctx is written head-merged [B*L, ld_ctx]; probs [B,H,L,L] (pre-dropout) is saved for backward, may be NULL. */
+ * ctx is written head-merged [B*L, ld_ctx]; probs [B,H,L,L] (pre-dropout) is saved for backward, may be NULL.  ctx planes:
+ * "Producers that write their output straight as planes" (planes_fmt 0 = bf16x3, 1 = h2).  causal = 0: the key-padding mask
+ * only, -1e9 on keys whose keymask entry is 0, no causal term (BERT4Rec, bert4rec.py:150-155).  The backward serves both masks:
+ * it works from the saved probabilities. */
 int pxr_attn_fwd_f32(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
                      int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx, float* probs,
-                     float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* stream);
+                     float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ctx_planes,
+                     int64_t ctx_plane_stride, int64_t ctx_panel_rows, int planes_fmt, int causal, void* stream);
 int pxr_attn_bwd_f32(const float* dctx, int64_t ld_ctx, const float* q, const float* k, const float* v, int64_t ld,
                      const float* probs, int B, int H, int L, int d, float* dq, float* dk, float* dv, int64_t ld_d,
-                     float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* stream);
+                     float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* g_planes,
+                     int64_t g_plane_stride, int64_t g_panel_rows, int g_cols, int col_q, int col_k, int col_v, void* stream);
 
 /* ---- GRU4Rec (code/REC/model/IDNet/gru4rec.py; torch.nn.GRU, bias=False): the gate arithmetic of one time step --------- */
 /* r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z + gh_z), n = tanh(gi_n + r gh_n), h = (1 - z) n + z h_prev; gi, gh [B, 3H] in
@@ -465,84 +443,36 @@ int pxr_causal_im2col_f32(const float* x, float* xcol, int64_t B, int L, int C, 
 int pxr_causal_col2im_f32(const float* dxcol, float* dx, int64_t B, int L, int C, int k, int dilation, void* stream);
 
 /* ---- training head ------------------------------------------------------------------------------------------ */
-/* loss = mean_b(-sum_t log(sigmoid(pos-neg)+1e-8) * mask)            sasrec.py:88-92; loss stays on the device */
+/* loss = mean_b(-sum_t log(sigmoid(pos-neg)+1e-8) * mask)            sasrec.py:88-92; loss stays on the device
+ * The id layout: position t of sequence b scores against items[b*id_bstride + pos_off + t] (target) and
+ * items[b*id_bstride + neg_off + t] (negative).  SASRec's shifted windows items [B, 2, L+1] are (2(L+1), 1, L+2).  BERT4Rec's
+ * batch items [B, 3, L] = masked sequence | original sequence | negatives over its L = MAX_ITEM_LIST_LENGTH + 1 positions
+ * (REC/data/dataset/trainset.py:470-478) is (3L, L, 2L), with masked_index [B, L]: the loss -sum_masked log(1e-8 +
+ * sigmoid(pos - neg)) / B of bert4rec.py:98-111 is this function on that layout. */
 int pxr_bpr_loss_fwd_f32(const float* out, const float* table, int64_t n_table, const int64_t* items,
                          const int64_t* masked_index, int B, int L, int D, float* pos_score, float* neg_score,
-                         float* lossrow, float* loss, void* stream);
+                         float* lossrow, float* loss, int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream);
 int pxr_bpr_loss_bwd_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
                          const int64_t* items, const int64_t* masked_index, int B, int L, int D, float grad_scale,
-                         const float* grad_scale_dev, float* dout, float* coef, void* stream);
-/* The second stage of pxr_bpr_loss_fwd_f32 alone (loss = 1/B sum_b sum_t lossrow[b,t], fixed order). */
-int pxr_bpr_loss_reduce_f32(const float* lossrow, int B, int L, float* loss, void* stream);
+                         const float* grad_scale_dev, float* dout, float* coef, int64_t id_bstride, int64_t pos_off,
+                         int64_t neg_off, void* stream);
 /* The block's LAST LayerNorm (reference layers.py:670-671, the output sasrec.py:86 names) with the loss head's forward
  * (sasrec.py:88-92) fused in: y = LN(dropout(x) + res) over B*L rows, pos / neg scores and the loss as pxr_bpr_loss_fwd_f32
- * would compute them from y -- bit-identical, one launch and one pass over y less. */
+ * would compute them from y -- bit-identical, one launch and one pass over y less.  Same id layout. */
 int pxr_ln_residual_bpr_fwd_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps, int B, int L,
                                 int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed, uint32_t stream_id,
                                 const int64_t* step_dev, const float* table, int64_t n_table, const int64_t* items,
                                 const int64_t* masked_index, float* pos_score, float* neg_score, float* lossrow, float* loss,
-                                void* stream);
-/* Its backward: pxr_bpr_loss_bwd_f32 + pxr_ln_bwd_planes_f32 (gather_mode 0) in one launch -- the gradient w.r.t. the block's
+                                int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream);
+/* Its backward: pxr_bpr_loss_bwd_f32 + pxr_ln_bwd_f32 (gather_mode 0) in one launch -- the gradient w.r.t. the block's
  * output is formed per row in registers from the saved scores instead of being written and read back; coef [B*L] is written
- * for pxr_sasrec_occ_segsum.  g_planes / stat optional (the two forms of pxr_ln_bwd_planes_f32 / pxr_ln_bwd_stat_f32). */
+ * for pxr_sasrec_occ_segsum.  g_planes / stat optional (the two forms of pxr_ln_bwd_f32 / pxr_ln_bwd_stat_f32). */
 int pxr_bpr_ln_bwd_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table, const int64_t* items,
                        const int64_t* masked_index, int B, int L, float grad_scale, const float* grad_scale_dev, float* coef,
                        const float* xhat, const float* rstd, const float* gamma, int D, float* dz, float* dx, float* dgamma,
                        float* dbeta, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws,
-                       int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, float* stat, void* stream);
-
-/* ---- BERT4Rec (reference code/REC/model/IDNet/bert4rec.py) --------------------------------------------------------------- */
-/* The training head and table gradient of SASRec with the id layout as arguments: position t of sequence b scores against
- * items[b*id_bstride + pos_off + t] (target) and items[b*id_bstride + neg_off + t] (negative); SASRec's shifted windows are
- * (2(L+1), 1, L+2).  BERT4Rec's batch items [B, 3, L] = masked sequence | original sequence | negatives over its L = MAX_ITEM_
- * LIST_LENGTH + 1 positions (REC/data/dataset/trainset.py:470-478) is (3L, L, 2L), with masked_index [B, L]: the loss
- * -sum_masked log(1e-8 + sigmoid(pos - neg)) / B of bert4rec.py:98-111 is what pxr_bpr_loss_fwd_f32 computes on that layout. */
-int pxr_bpr_loss_fwd_lay_f32(const float* out, const float* table, int64_t n_table, const int64_t* items,
-                             const int64_t* masked_index, int B, int L, int D, float* pos_score, float* neg_score, float* lossrow,
-                             float* loss, int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream);
-int pxr_bpr_loss_bwd_lay_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
-                             const int64_t* items, const int64_t* masked_index, int B, int L, int D, float grad_scale,
-                             const float* grad_scale_dev, float* dout, float* coef, int64_t id_bstride, int64_t pos_off,
-                             int64_t neg_off, void* stream);
-/* pxr_ln_residual_bpr_fwd_f32 / pxr_bpr_ln_bwd_f32 / pxr_ln_bwd_h2s_f32 with the id layout (bert4rec.py:98-111 fused into the
- * encoder's last LayerNorm, layers.py:670-671, and its backward) */
-int pxr_ln_residual_bpr_fwd_lay_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps, int B,
-                                    int L, int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
-                                    uint32_t stream_id, const int64_t* step_dev, const float* table, int64_t n_table,
-                                    const int64_t* items, const int64_t* masked_index, float* pos_score, float* neg_score,
-                                    float* lossrow, float* loss, int64_t id_bstride, int64_t pos_off, int64_t neg_off,
-                                    void* stream);
-int pxr_bpr_ln_bwd_lay_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
-                           const int64_t* items, const int64_t* masked_index, int B, int L, float grad_scale,
-                           const float* grad_scale_dev, float* coef, const float* xhat, const float* rstd, const float* gamma,
-                           int D, float* dz, float* dx, float* dgamma, float* dbeta, float p_drop, uint64_t seed,
-                           uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes, void* g_planes,
-                           int64_t g_plane_stride, int64_t g_panel_rows, float* stat, int64_t id_bstride, int64_t pos_off,
-                           int64_t neg_off, void* stream);
-int pxr_ln_bwd_h2s_lay_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
-                           const int64_t* items, const int64_t* masked_index, int B, int L, float grad_scale,
-                           const float* grad_scale_dev, float* coef, const float* dy, const float* xhat, const float* rstd,
-                           const float* gamma, int rows, int D, float* dz, float* dgamma, float* dbeta, float p_drop,
-                           uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes,
-                           void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, const int* g_exp_dev, float* stat,
-                           float* zero, int zero_n, int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream);
-/* Phase 1 of the table gradient (pxr_sasrec_occ_sort) for an id layout: the input ids at in_off, targets at pos_off, negatives at
- * neg_off of each sequence's id_bstride ids (BERT4Rec: (3L, 0, L, 2L); the table's three uses in bert4rec.py:76-81 under
- * autograd).  Phase 2 is pxr_sasrec_occ_segsum / pxr_sasrec_occ_segsum_split with the same B, L: deterministic, no float atomics,
- * row 0 dropped, every other row (BERT4Rec's mask token item_num included) ordinary. */
-int pxr_seq_occ_sort_lay(const int64_t* items, int B, int L, int64_t id_bstride, int64_t in_off, int64_t pos_off,
-                         int64_t neg_off, int64_t n_table, int64_t* uniq_idx, int32_t* n_uniq_dev, void* ws, int64_t ws_bytes,
-                         void* stream);
-/* Bidirectional attention forward: pxr_attn_fwd_f32 / _planes_f32 / _h2_f32 with the key-padding mask only (bert4rec.py:150-155:
- * -1e9 on keys whose keymask entry is 0, no causal term).  ctx_planes NULL: fp32 ctx only; else planes_fmt 0 = bf16x3, 1 = h2.
- * The backward entries (pxr_attn_bwd_*) serve it unchanged: they work from the saved probabilities. */
-int pxr_attn_fwd_bidir_f32(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
-                           int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx, float* probs, float p_drop,
-                           uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ctx_planes,
-                           int64_t ctx_plane_stride, int64_t ctx_panel_rows, int planes_fmt, void* stream);
-/* pxr_attn_rows_fwd_f32 (L > 128) with the key-padding mask only; pxr_attn_rows_bwd_f32 serves it unchanged */
-int pxr_attn_rows_fwd_bidir_f32(float* S, float* PD, const int64_t* keymask, int64_t km_bstride, int B, int H, int L, int ld,
-                                float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, int d, void* stream);
+                       int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, float* stat,
+                       int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream);
 
 /* ---- PixelNet (MOSASRec) ------------------------------------------------------------------------------------- */
 /* Gradient w.r.t. the visual encoder's output viewed [B, L+1, 2, D] (pos_t | neg_t interleaved, PixelNet/
@@ -560,31 +490,21 @@ int pxr_image_u8_to_f32(const uint8_t* store, int64_t n_store, int H, int W, con
  * hist_ptr int32 [B+1] + hist_items int64 = CSR of seq_eval_collate's (history_u, history_i) pairs (NULL = none);
  * K <= 32.  Outputs topk_idx int64 [B,K] / topk_val [B,K], descending. */
 int64_t pxr_score_topk_ws_bytes(int B, int N, int K);
-int pxr_score_topk_f32(const float* users, int64_t ld_users, int B, const float* table, int N, int D,
-                       const int32_t* hist_ptr, const int64_t* hist_items, int K, int64_t* topk_idx, float* topk_val,
-                       void* ws, int64_t ws_bytes, void* stream);
-
-/* The same with both operands ALSO given as planes ("pre-split operands" above; both NULL: the plain function): on catalogues
- * that take the two-pass threshold schedule the pass over every item tile runs on the planes as one LDS-DMA stream; the
- * table's planes are made once per evaluation with pxr_split_planes_f32 (model/IDNet/sasrec.py:112,115-117). */
-int pxr_score_topk_planes_f32(const float* users, int64_t ld_users, int B, const float* table, int N, int D,
-                              const void* users_planes, int64_t users_plane_stride, int64_t users_panel_rows,
-                              const void* table_planes, int64_t table_plane_stride, int64_t table_panel_rows,
-                              const int32_t* hist_ptr, const int64_t* hist_items, int K, int64_t* topk_idx, float* topk_val,
-                              void* ws, int64_t ws_bytes, void* stream);
-
-/* ... and with the pass over the catalogue on `products` = 3 (hi*hi + mid*hi + hi*mid) or 1 (hi*hi) of the six bf16 products
- * (6: exactly the function above).  That pass only decides "score >= threshold": the threshold is lowered by a rigorous per-user
- * bound on what the dropped products and the different rounding can change (c ||user||_2 max_i ||table[i]||_2), and the few
- * survivors that can still reach the top K are re-scored with all six products in the full pass's own MFMA order -- ids and
- * values are those of pxr_score_topk_planes_f32, bit for bit, at about half (3) of its MFMA work.  Needs both operands as planes
- * and table_row_norm_max: DEVICE pointer to max_i ||table[i]||_2 (pxr_row_norm_max_f32, once per evaluation like the planes).
+/* users_planes / table_planes: both operands ALSO given as planes ("pre-split operands" above; both NULL: fp32 only): on
+ * catalogues that take the two-pass threshold schedule the pass over every item tile runs on the planes as one LDS-DMA stream;
+ * the table's planes are made once per evaluation with pxr_split_planes_f32 (model/IDNet/sasrec.py:112,115-117).  That pass
+ * runs on `products` = 6, 3 (hi*hi + mid*hi + hi*mid) or 1 (hi*hi) of the six bf16 products; it only decides "score >=
+ * threshold": with 3 or 1 the threshold is lowered by a rigorous per-user bound on what the dropped products and the different
+ * rounding can change (c ||user||_2 max_i ||table[i]||_2), and the few survivors that can still reach the top K are re-scored
+ * with all six products in the full pass's own MFMA order -- ids and values are the six-product pass's, bit for bit, at about
+ * half (3) of its MFMA work.  products 3 / 1 need both operands as planes and table_row_norm_max: DEVICE pointer to
+ * max_i ||table[i]||_2 (pxr_row_norm_max_f32, once per evaluation like the planes; NULL with 6).
  * Same reference path: model/IDNet/sasrec.py:112 + trainer/trainer.py:327-337 + evaluator/collector.py:131-139. */
-int pxr_score_topk_fast_f32(const float* users, int64_t ld_users, int B, const float* table, int N, int D,
-                            const void* users_planes, int64_t users_plane_stride, int64_t users_panel_rows,
-                            const void* table_planes, int64_t table_plane_stride, int64_t table_panel_rows,
-                            const float* table_row_norm_max, int products, const int32_t* hist_ptr, const int64_t* hist_items,
-                            int K, int64_t* topk_idx, float* topk_val, void* ws, int64_t ws_bytes, void* stream);
+int pxr_score_topk_f32(const float* users, int64_t ld_users, int B, const float* table, int N, int D,
+                       const void* users_planes, int64_t users_plane_stride, int64_t users_panel_rows,
+                       const void* table_planes, int64_t table_plane_stride, int64_t table_panel_rows,
+                       const float* table_row_norm_max, int products, const int32_t* hist_ptr, const int64_t* hist_items,
+                       int K, int64_t* topk_idx, float* topk_val, void* ws, int64_t ws_bytes, void* stream);
 /* out[0] (device float) = max_i ||x[i, :]||_2 of x [rows, cols] fp32 (row stride ldx, cols % 4 == 0): the item-table statistic of
  * the function above (computed over what compute_item_all returns, model/IDNet/sasrec.py:115-117). */
 int pxr_row_norm_max_f32(const float* x, int64_t rows, int64_t cols, int64_t ldx, float* out, void* stream);
@@ -634,7 +554,7 @@ int pxr_adamw_rows_ids2d_f32(float* table, float* m, float* v, int32_t* last, in
                              int64_t t_prev, const int64_t* step_dev, double beta1, double beta2, double eps,
                              void* cur_hyper_out, void* stream);
 /* cur_hyper_out (optional, 16 bytes): the launch also copies the scalars of the optimizer step about to run (hyper entry
- * t_prev + 1) there.  pxr_adamw_flat_tab_ex_f32 = pxr_adamw_flat_tab_planes_f32 with two options: (a) seg_fmt = 1: the weight
+ * t_prev + 1) there.  pxr_adamw_flat_tab_ex_f32 = pxr_adamw_flat_tab_f32 with two options: (a) seg_fmt = 1: the weight
  * segments leave the launch as fp16 two-plane operands (planes "h2"), segment i scaled by 2^seg_exps[i] (device ints: the
  * exponents the planes were last split with; the next forward needs no statistics + split launches); (b) cur_hyper != NULL: this
  * step's scalars are read from that slot and the launch CLOSES the step itself (counts it in *step_dev, appends the next entry:
@@ -645,17 +565,15 @@ int pxr_adamw_flat_tab_ex_f32(float* p, const float* g, float* m, float* v, int6
                               double eps, double weight_decay, int n_seg, const int64_t* seg_off, const int64_t* seg_rows,
                               const int64_t* seg_cols, void* const* seg_planes, const int64_t* seg_plane_stride,
                               const int64_t* seg_panel_rows, int seg_fmt, const int* seg_exps, void* stream);
-/* pxr_adamw_flat_f32 with the step's scalars read from hyper[step] (or hyper[*step_dev + 1]). */
+/* pxr_adamw_flat_f32 with the step's scalars read from hyper[step] (or hyper[*step_dev + 1]); it also writes the UPDATED values
+ * of n_seg (<= 16; 0: none) weight matrices inside the flat buffer ([seg_rows, seg_cols] row-major at element seg_off) as bf16x3
+ * planes (see "pre-split operands"): the operands of the next step's GEMMs come out of the optimizer (trainer.py:125) with no
+ * split launch. */
 int pxr_adamw_flat_tab_f32(float* p, const float* g, float* m, float* v, int64_t n, const void* hyper, int64_t step,
-                           const int64_t* step_dev, double beta1, double beta2, double eps, void* stream);
-/* pxr_adamw_flat_tab_f32 that also writes the UPDATED values of n_seg (<= 16) weight matrices inside the flat buffer
- * ([seg_rows, seg_cols] row-major at element seg_off) as bf16x3 planes (see "pre-split operands"): the operands of the next
- * step's GEMMs come out of the optimizer (trainer.py:125) with no split launch. */
-int pxr_adamw_flat_tab_planes_f32(float* p, const float* g, float* m, float* v, int64_t n, const void* hyper, int64_t step,
-                                  const int64_t* step_dev, double beta1, double beta2, double eps, int n_seg,
-                                  const int64_t* seg_off, const int64_t* seg_rows, const int64_t* seg_cols,
-                                  void* const* seg_planes, const int64_t* seg_plane_stride, const int64_t* seg_panel_rows,
-                                  void* stream);
+                           const int64_t* step_dev, double beta1, double beta2, double eps, int n_seg,
+                           const int64_t* seg_off, const int64_t* seg_rows, const int64_t* seg_cols,
+                           void* const* seg_planes, const int64_t* seg_plane_stride, const int64_t* seg_panel_rows,
+                           void* stream);
 /* *counter += delta on the device. */
 int pxr_counter_add_i64(int64_t* counter, int64_t delta, void* stream);
 

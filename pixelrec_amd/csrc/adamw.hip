@@ -608,33 +608,22 @@ extern "C" int pxr_adamw_hyper_append(void* hyper, void* cumlog, int64_t capacit
   return pxr_check_launch("pxr_adamw_hyper_append");
 }
 
-// Flat AdamW with the step's scalars taken from the hyper table entry `step` (or *step_dev + 1).
-extern "C" int pxr_adamw_flat_tab_planes_f32(float* p, const float* g, float* m, float* v, int64_t n, const void* hyper,
-                                             int64_t step, const int64_t* step_dev, double beta1, double beta2, double eps,
-                                             int n_seg, const int64_t* seg_off, const int64_t* seg_rows, const int64_t* seg_cols,
-                                             void* const* seg_planes, const int64_t* seg_plane_stride,
-                                             const int64_t* seg_panel_rows, void* stream);
-extern "C" int pxr_adamw_flat_tab_f32(float* p, const float* g, float* m, float* v, int64_t n, const void* hyper,
-                                      int64_t step, const int64_t* step_dev, double beta1, double beta2, double eps,
-                                      void* stream) {
-  return pxr_adamw_flat_tab_planes_f32(p, g, m, v, n, hyper, step, step_dev, beta1, beta2, eps, 0, nullptr, nullptr, nullptr,
-                                       nullptr, nullptr, nullptr, stream);
-}
-// the same; the updated values of n_seg (<= 16) weight matrices inside the flat buffer ([seg_rows, seg_cols] row-major at
-// element seg_off) are additionally written as bf16x3 planes (pxr.h: planes) -- the operands of the next step's GEMMs
+// Flat AdamW with the step's scalars taken from the hyper table entry `step` (or *step_dev + 1); the updated values of n_seg (<= 16)
+// weight matrices inside the flat buffer ([seg_rows, seg_cols] row-major at element seg_off) are additionally written as bf16x3
+// planes (pxr.h: planes) -- the operands of the next step's GEMMs (n_seg = 0: none)
 static int flat_tab_impl(float* p, const float* g, float* m, float* v, int64_t n, const void* hyper, int64_t step,
                          const int64_t* step_dev, double beta1, double beta2, double eps, int n_seg, const int64_t* seg_off,
                          const int64_t* seg_rows, const int64_t* seg_cols, void* const* seg_planes, const int64_t* seg_plane_stride,
                          const int64_t* seg_panel_rows, const FlatClose& cl, void* stream, int seg_fmt = 0, const int* seg_exps = nullptr);
-extern "C" int pxr_adamw_flat_tab_planes_f32(float* p, const float* g, float* m, float* v, int64_t n, const void* hyper,
-                                             int64_t step, const int64_t* step_dev, double beta1, double beta2, double eps,
-                                             int n_seg, const int64_t* seg_off, const int64_t* seg_rows, const int64_t* seg_cols,
-                                             void* const* seg_planes, const int64_t* seg_plane_stride,
-                                             const int64_t* seg_panel_rows, void* stream) {
+extern "C" int pxr_adamw_flat_tab_f32(float* p, const float* g, float* m, float* v, int64_t n, const void* hyper,
+                                      int64_t step, const int64_t* step_dev, double beta1, double beta2, double eps,
+                                      int n_seg, const int64_t* seg_off, const int64_t* seg_rows, const int64_t* seg_cols,
+                                      void* const* seg_planes, const int64_t* seg_plane_stride,
+                                      const int64_t* seg_panel_rows, void* stream) {
   return flat_tab_impl(p, g, m, v, n, hyper, step, step_dev, beta1, beta2, eps, n_seg, seg_off, seg_rows, seg_cols, seg_planes,
                        seg_plane_stride, seg_panel_rows, FlatClose{}, stream);
 }
-// pxr_adamw_flat_tab_planes_f32 with two options.  (a) seg_fmt = PXR_PLANES_H2: the weight segments are written as fp16 two-plane
+// pxr_adamw_flat_tab_f32 with two options.  (a) seg_fmt = PXR_PLANES_H2: the weight segments are written as fp16 two-plane
 // operands, segment i scaled by 2^seg_exps[i] (device ints, see FlatPlanes).  (b) cur_hyper != NULL: the launch also CLOSES the
 // optimizer step (what pxr_adamw_hyper_append(advance = 1) does in a launch of its own): this step's scalars are read from
 // `cur_hyper` (float4, filled at the head of the step by pxr_adamw_rows_ids2d_f32's cur_hyper_out), one thread counts the step in
@@ -664,7 +653,7 @@ static int flat_tab_impl(float* p, const float* g, float* m, float* v, int64_t n
               "pxr_adamw_flat_tab_f32: h2 segments need their device exponents");
   PXR_REQUIRE(n >= 0 && n % 4 == 0 && (step_dev || step >= 1), "pxr_adamw_flat_tab_f32: bad n / step");
   PXR_REQUIRE(n_seg >= 0 && n_seg <= 16 && (n_seg == 0 || (seg_off && seg_rows && seg_cols && seg_planes && seg_plane_stride && seg_panel_rows)),
-              "pxr_adamw_flat_tab_planes_f32: bad segment table");
+              "pxr_adamw_flat_tab_f32: bad segment table");
   if (n == 0) return PXR_OK;
   FlatPlanes fp{};
   fp.n = n_seg; fp.fmt = seg_fmt; fp.exps = seg_exps; fp.status = pxr_status_word();
@@ -672,7 +661,7 @@ static int flat_tab_impl(float* p, const float* g, float* m, float* v, int64_t n
     PXR_REQUIRE(seg_off[i] >= 0 && seg_off[i] % 4 == 0 && seg_rows[i] > 0 && seg_rows[i] < (1ll << 31) && seg_cols[i] > 0 &&
                     seg_off[i] + seg_rows[i] * seg_cols[i] <= n && seg_planes[i] &&
                     p3_mat_ok(seg_planes[i], seg_plane_stride[i], seg_panel_rows[i], seg_rows[i], seg_cols[i]),
-                "pxr_adamw_flat_tab_planes_f32: segment %d is bad", i);
+                "pxr_adamw_flat_tab_f32: segment %d is bad", i);
     fp.off[i] = seg_off[i]; fp.rows[i] = (int)seg_rows[i]; fp.cols[i] = (int)seg_cols[i];
     fp.out[i] = P3Mat{reinterpret_cast<__bf16*>(seg_planes[i]), seg_plane_stride[i], seg_panel_rows[i]};
   }

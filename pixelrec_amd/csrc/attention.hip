@@ -10,7 +10,7 @@
 //   attn_{fwd,bwd}_kernel<NW>       L <= 64, d % 4 == 0: VALU fallback (PXR_ATTN_MFMA=0 or d % 8 != 0)
 // Mask mode: every forward is a __device__ body templated on CAUSAL.  The __global__ kernels above instantiate CAUSAL = true
 // (SASRec: key j <= query i and key real); attn_fwd_*_bidir_kernel instantiate false (BERT4Rec, bert4rec.py:150-155: key real only),
-// behind pxr_attn_fwd_bidir_f32.  The backward kernels serve both: they read the saved probabilities.
+// behind pxr_attn_fwd_f32(causal = 0).  The backward kernels serve both: they read the saved probabilities.
 // Common design:
 //   * q/k/v are read in place from the fused QKV projection output [B, L, 3D] (row stride `ld`), the context
 //     is written head-merged into [B, L, D]: no permute/contiguous copies (layers.py:590-592,610-612);
@@ -1287,64 +1287,24 @@ static int attn_check(int B, int H, int L, int d, int64_t ld, const char* who) {
 }
 
 // ctx[b,t,h*d:(h+1)*d] = softmax(q k^T / sqrt(d) + mask) v       (eval: p_drop = 0)
-// 1 when the fused kernels that can write their outputs as planes serve this shape (pxr_attn_*_planes_f32)
+// 1 when the fused kernels that can write their outputs as planes serve this shape (ctx_planes / g_planes of the entries below)
 extern "C" int pxr_attn_planes_supported(int L, int d) { return (L <= ATT_MAXL && attn_use_mfma(d) && d <= ATT_DC && d % 8 == 0) ? 1 : 0; }
 
-extern "C" int pxr_attn_fwd_planes_f32(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
-                                       int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx,
-                                       float* probs, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
-                                       void* ctx_planes, int64_t ctx_plane_stride, int64_t ctx_panel_rows, void* stream);
+// ctx (the [B*L, H*d] matrix) additionally -- or, ctx == NULL, only -- written as planes: planes_fmt 0 = bf16x3, the operand format
+// of the output projection that follows (layers.py:613); 1 = two fp16 planes (planes.cuh "h2", unit scale; the operand of
+// pxr_gemm_h2_f32, ctx_planes required).  Shapes: pxr_attn_planes_supported.  causal = 0: the key-padding mask only, the additive
+// -1e9 lands only on keys whose keymask entry is 0 -- BERT4Rec's get_attention_mask (reference IDNet/bert4rec.py:150-155).  The
+// backward needs no mask form: it works from the saved probabilities, which carry the mask.
 extern "C" int pxr_attn_fwd_f32(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
-                                int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx,
-                                float* probs, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
-                                void* stream) {
-  PXR_REQUIRE(ctx, "pxr_attn_fwd_f32: null pointer");
-  return pxr_attn_fwd_planes_f32(q, k, v, ld, keymask, km_bstride, B, H, L, d, ctx, ld_ctx, probs, p_drop, seed, stream_id,
-                                 step_dev, nullptr, 0, 0, stream);
-}
-// the same with ctx (the [B*L, H*d] matrix) additionally -- or, ctx == NULL, only -- written as bf16x3 planes: the operand
-// format of the output projection that follows (layers.py:613).  Shapes: pxr_attn_planes_supported.
-static int attn_fwd_planes_impl(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
-                                int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx, float* probs, float p_drop,
-                                uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ctx_planes,
-                                int64_t ctx_plane_stride, int64_t ctx_panel_rows, int c_fmt, void* stream, bool causal = true);
-extern "C" int pxr_attn_fwd_planes_f32(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
-                                       int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx,
-                                       float* probs, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
-                                       void* ctx_planes, int64_t ctx_plane_stride, int64_t ctx_panel_rows, void* stream) {
-  return attn_fwd_planes_impl(q, k, v, ld, keymask, km_bstride, B, H, L, d, ctx, ld_ctx, probs, p_drop, seed, stream_id, step_dev,
-                              ctx_planes, ctx_plane_stride, ctx_panel_rows, PXR_PLANES_BF16X3, stream);
-}
-// ... with the ctx planes in the two-plane fp16 format (planes.cuh "h2", unit scale): the operand of pxr_gemm_h2_f32
-extern "C" int pxr_attn_fwd_h2_f32(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
-                                   int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx, float* probs,
-                                   float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ctx_planes,
-                                   int64_t ctx_plane_stride, int64_t ctx_panel_rows, void* stream) {
-  PXR_REQUIRE(ctx_planes, "pxr_attn_fwd_h2_f32: no planes");
-  return attn_fwd_planes_impl(q, k, v, ld, keymask, km_bstride, B, H, L, d, ctx, ld_ctx, probs, p_drop, seed, stream_id, step_dev,
-                              ctx_planes, ctx_plane_stride, ctx_panel_rows, PXR_PLANES_H2, stream);
-}
-// Bidirectional (key-padding-only) attention: the same kernels instantiated with CAUSAL = false, i.e. the additive -1e9 lands
-// only on keys whose keymask entry is 0 -- BERT4Rec's get_attention_mask (reference IDNet/bert4rec.py:150-155).  One entry for
-// the three output forms: ctx_planes NULL = fp32 ctx only (pxr_attn_fwd_f32); else planes_fmt PXR_PLANES_BF16X3 (0) or
-// PXR_PLANES_H2 (1) as pxr_attn_fwd_planes_f32 / pxr_attn_fwd_h2_f32.  The backward entries need no mask form: they work from the
-// saved probabilities, which carry the mask.
-extern "C" int pxr_attn_fwd_bidir_f32(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
-                                      int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx, float* probs,
-                                      float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ctx_planes,
-                                      int64_t ctx_plane_stride, int64_t ctx_panel_rows, int planes_fmt, void* stream) {
-  PXR_REQUIRE(planes_fmt == 0 || planes_fmt == 1, "pxr_attn_fwd_bidir_f32: planes_fmt must be 0 (bf16x3) or 1 (h2)");
-  return attn_fwd_planes_impl(q, k, v, ld, keymask, km_bstride, B, H, L, d, ctx, ld_ctx, probs, p_drop, seed, stream_id, step_dev,
-                              ctx_planes, ctx_plane_stride, ctx_panel_rows, planes_fmt == 1 ? PXR_PLANES_H2 : PXR_PLANES_BF16X3,
-                              stream, false);
-}
-static int attn_fwd_planes_impl(const float* q, const float* k, const float* v, int64_t ld, const int64_t* keymask,
-                                int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx, float* probs, float p_drop,
-                                uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ctx_planes,
-                                int64_t ctx_plane_stride, int64_t ctx_panel_rows, int c_fmt, void* stream, bool causal) {
+                                int64_t km_bstride, int B, int H, int L, int d, float* ctx, int64_t ld_ctx, float* probs,
+                                float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ctx_planes,
+                                int64_t ctx_plane_stride, int64_t ctx_panel_rows, int planes_fmt, int causal, void* stream) {
+  PXR_REQUIRE(planes_fmt == 0 || planes_fmt == 1, "pxr_attn_fwd_f32: planes_fmt must be 0 (bf16x3) or 1 (h2)");
+  PXR_REQUIRE(causal == 0 || causal == 1, "pxr_attn_fwd_f32: causal must be 0 or 1");
+  PXR_REQUIRE(planes_fmt == 0 || ctx_planes, "pxr_attn_fwd_f32: h2 output needs planes");
   PXR_REQUIRE(q && k && v && keymask && (ctx || ctx_planes), "pxr_attn_fwd_f32: null pointer");
   PXR_REQUIRE(!ctx_planes || (pxr_attn_planes_supported(L, d) && p3_mat_ok(ctx_planes, ctx_plane_stride, ctx_panel_rows, (int64_t)B * L, (int64_t)H * d)),
-              "pxr_attn_fwd_planes_f32: planes are not available for this shape (L=%d, d=%d)", L, d);
+              "pxr_attn_fwd_f32: planes are not available for this shape (L=%d, d=%d)", L, d);
   int rc = attn_check(B, H, L, d, ld, "pxr_attn_fwd_f32");
   if (rc) return rc;
   PXR_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "pxr_attn_fwd_f32: bad dropout p");
@@ -1353,7 +1313,7 @@ static int attn_fwd_planes_impl(const float* q, const float* k, const float* v, 
   a.q = q; a.k = k; a.v = v; a.ld = ld; a.keymask = keymask; a.km_bstride = km_bstride;
   a.ctx = ctx; a.ld_ctx = ld_ctx; a.probs = probs; a.B = B; a.H = H; a.L = L; a.d = d;
   a.op = P3Mat{reinterpret_cast<__bf16*>(ctx_planes), ctx_plane_stride, ctx_panel_rows};
-  a.op_fmt = c_fmt;
+  a.op_fmt = planes_fmt == 1 ? PXR_PLANES_H2 : PXR_PLANES_BF16X3;
   a.status = pxr_status_word();
   a.sqrt_d = sqrtf((float)d);
   a.p_drop = p_drop; a.drop_thr = pxr_drop_threshold(p_drop); a.stream = stream_id; a.seed = seed;
@@ -1379,32 +1339,19 @@ static int attn_fwd_planes_impl(const float* q, const float* k, const float* v, 
   return pxr_check_launch("pxr_attn_fwd_f32");
 }
 
-// Gradients w.r.t. q, k, v (written with row stride ld_d, head h at column h*d) from dctx and the saved probs.
-extern "C" int pxr_attn_bwd_planes_f32(const float* dctx, int64_t ld_ctx, const float* q, const float* k, const float* v,
-                                       int64_t ld, const float* probs, int B, int H, int L, int d, float* dq, float* dk,
-                                       float* dv, int64_t ld_d, float p_drop, uint64_t seed, uint32_t stream_id,
-                                       const int64_t* step_dev, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows,
-                                       int g_cols, int col_q, int col_k, int col_v, void* stream);
-extern "C" int pxr_attn_bwd_f32(const float* dctx, int64_t ld_ctx, const float* q, const float* k, const float* v,
-                                int64_t ld, const float* probs, int B, int H, int L, int d, float* dq, float* dk,
-                                float* dv, int64_t ld_d, float p_drop, uint64_t seed, uint32_t stream_id,
-                                const int64_t* step_dev, void* stream) {
-  PXR_REQUIRE(dq && dk && dv, "pxr_attn_bwd_f32: null pointer");
-  return pxr_attn_bwd_planes_f32(dctx, ld_ctx, q, k, v, ld, probs, B, H, L, d, dq, dk, dv, ld_d, p_drop, seed, stream_id,
-                                 step_dev, nullptr, 0, 0, 0, 0, 0, 0, stream);
-}
-// the same with dq | dk | dv additionally -- or, all three NULL, only -- written as bf16x3 planes: column ranges starting at
-// col_q / col_k / col_v of one [B*L, g_cols] planes matrix (the gradient of the fused QKV projection's output).
+// Gradients w.r.t. q, k, v (written with row stride ld_d, head h at column h*d) from dctx and the saved probs; dq | dk | dv
+// additionally -- or, all three NULL, only -- written as bf16x3 planes: column ranges starting at col_q / col_k / col_v of one
+// [B*L, g_cols] planes matrix (the gradient of the fused QKV projection's output; g_planes NULL: none).
 static int attn_bwd_impl(const float* dctx, int64_t ld_ctx, const float* q, const float* k, const float* v, int64_t ld,
                          const float* probs, int B, int H, int L, int d, float* dq, float* dk, float* dv, int64_t ld_d, float p_drop,
                          uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* g_planes, int64_t g_plane_stride,
                          int64_t g_panel_rows, int g_cols, int col_q, int col_k, int col_v, float* stat, void* stream,
                          const int* g_exp = nullptr);
-extern "C" int pxr_attn_bwd_planes_f32(const float* dctx, int64_t ld_ctx, const float* q, const float* k, const float* v,
-                                       int64_t ld, const float* probs, int B, int H, int L, int d, float* dq, float* dk,
-                                       float* dv, int64_t ld_d, float p_drop, uint64_t seed, uint32_t stream_id,
-                                       const int64_t* step_dev, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows,
-                                       int g_cols, int col_q, int col_k, int col_v, void* stream) {
+extern "C" int pxr_attn_bwd_f32(const float* dctx, int64_t ld_ctx, const float* q, const float* k, const float* v,
+                                int64_t ld, const float* probs, int B, int H, int L, int d, float* dq, float* dk,
+                                float* dv, int64_t ld_d, float p_drop, uint64_t seed, uint32_t stream_id,
+                                const int64_t* step_dev, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows,
+                                int g_cols, int col_q, int col_k, int col_v, void* stream) {
   return attn_bwd_impl(dctx, ld_ctx, q, k, v, ld, probs, B, H, L, d, dq, dk, dv, ld_d, p_drop, seed, stream_id, step_dev, g_planes,
                        g_plane_stride, g_panel_rows, g_cols, col_q, col_k, col_v, nullptr, stream);
 }
@@ -1419,7 +1366,7 @@ extern "C" int pxr_attn_bwd_stat_f32(const float* dctx, int64_t ld_ctx, const fl
                        0, 0, 0, stat, stream);
 }
 // dq | dk | dv ONLY as two fp16 planes of gradient * 2^g_exp_dev[0] (column ranges of one [B*L, g_cols] matrix as in
-// pxr_attn_bwd_planes_f32) under an exponent that exists before the launch (pxr_h2_sites_update: the previous step's maximum less the
+// pxr_attn_bwd_f32) under an exponent that exists before the launch (pxr_h2_sites_update: the previous step's maximum less the
 // headroom), range-checked and saturated (PXR_STATUS_H2_STALE), + this step's partial maxima in the PXR_ATTN_STAT_SLOTS words of
 // `stat` (zeroed by the caller / the LayerNorm launch in front).  Replaces pxr_attn_bwd_stat_f32 + pxr_h2_split_parts_f32.
 extern "C" int pxr_attn_bwd_h2s_f32(const float* dctx, int64_t ld_ctx, const float* q, const float* k, const float* v, int64_t ld,
@@ -1440,7 +1387,7 @@ static int attn_bwd_impl(const float* dctx, int64_t ld_ctx, const float* q, cons
   PXR_REQUIRE(!g_planes || (pxr_attn_planes_supported(L, d) && p3_mat_ok(g_planes, g_plane_stride, g_panel_rows, (int64_t)B * L, g_cols) &&
                             col_q % 8 == 0 && col_k % 8 == 0 && col_v % 8 == 0 && col_q >= 0 && col_k >= 0 && col_v >= 0 &&
                             (int64_t)H * d + (col_q > col_k ? (col_q > col_v ? col_q : col_v) : (col_k > col_v ? col_k : col_v)) <= g_cols),
-              "pxr_attn_bwd_planes_f32: planes are not available for this shape (L=%d, d=%d) or bad column ranges", L, d);
+              "pxr_attn_bwd_f32: planes are not available for this shape (L=%d, d=%d) or bad column ranges", L, d);
   int rc = attn_check(B, H, L, d, ld, "pxr_attn_bwd_f32");
   if (rc) return rc;
   PXR_REQUIRE(ld_d % 4 == 0 && ld_ctx % 4 == 0, "pxr_attn_bwd_f32: strides must be multiples of 4");

@@ -122,10 +122,14 @@ __global__ void __launch_bounds__(256) bpr_bwd_kernel(BprArgs a) {
 
 using namespace pxr;
 
-// loss (device scalar), pos_score / neg_score [B*L].  lossrow is [B*L] scratch.
-static int bpr_loss_fwd_impl(const float* out, const float* table, int64_t n_table, const int64_t* items,
-                             const int64_t* masked_index, int B, int L, int D, float* pos_score, float* neg_score, float* lossrow,
-                             float* loss, int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream) {
+// loss (device scalar), pos_score / neg_score [B*L].  lossrow is [B*L] scratch.  The id layout (BprArgs::id_bstride): SASRec's
+// shifted windows pass (2(L+1), 1, L+2); BERT4Rec's aligned masked head, reference IDNet/bert4rec.py:98-111, passes (3L, L, 2L)
+// (items [B, 3, L] = masked sequence | original sequence | negatives; masked_index [B, L]).
+extern "C" int pxr_bpr_loss_fwd_f32(const float* out, const float* table, int64_t n_table, const int64_t* items,
+                                    const int64_t* masked_index, int B, int L, int D, float* pos_score, float* neg_score,
+                                    float* lossrow, float* loss, int64_t id_bstride, int64_t pos_off, int64_t neg_off,
+                                    void* stream) {
+  PXR_REQUIRE(pxr_bpr_layout_ok(L, id_bstride, pos_off, neg_off), "pxr_bpr_loss_fwd_f32: bad id layout");
   PXR_REQUIRE(out && table && items && masked_index && pos_score && neg_score && lossrow && loss,
               "pxr_bpr_loss_fwd_f32: null pointer");
   PXR_REQUIRE(B > 0 && L > 0 && D > 0 && D % 4 == 0, "pxr_bpr_loss_fwd_f32: bad shape");
@@ -138,39 +142,21 @@ static int bpr_loss_fwd_impl(const float* out, const float* table, int64_t n_tab
   hipLaunchKernelGGL(bpr_reduce_kernel, dim3(1), dim3(256), 0, st, (const float*)lossrow, B, L, loss);
   return pxr_check_launch("pxr_bpr_loss_fwd_f32");
 }
-extern "C" int pxr_bpr_loss_fwd_f32(const float* out, const float* table, int64_t n_table, const int64_t* items,
-                                    const int64_t* masked_index, int B, int L, int D, float* pos_score,
-                                    float* neg_score, float* lossrow, float* loss, void* stream) {
-  return bpr_loss_fwd_impl(out, table, n_table, items, masked_index, B, L, D, pos_score, neg_score, lossrow, loss,
-                           2 * (int64_t)(L + 1), 1, L + 2, stream);
-}
-static bool bpr_layout_ok(int L, int64_t id_bstride, int64_t pos_off, int64_t neg_off) {
-  return id_bstride > 0 && pos_off >= 0 && neg_off >= 0 && pos_off + L <= id_bstride && neg_off + L <= id_bstride;
-}
-// ... with the id layout as arguments (BprArgs::id_bstride): BERT4Rec's aligned masked head, reference IDNet/bert4rec.py:98-111
-// (items [B, 3, L] = masked sequence | original sequence | negatives: layout (3L, L, 2L); masked_index [B, L])
-extern "C" int pxr_bpr_loss_fwd_lay_f32(const float* out, const float* table, int64_t n_table, const int64_t* items,
-                                        const int64_t* masked_index, int B, int L, int D, float* pos_score, float* neg_score,
-                                        float* lossrow, float* loss, int64_t id_bstride, int64_t pos_off, int64_t neg_off,
-                                        void* stream) {
-  PXR_REQUIRE(bpr_layout_ok(L, id_bstride, pos_off, neg_off), "pxr_bpr_loss_fwd_lay_f32: bad id layout");
-  return bpr_loss_fwd_impl(out, table, n_table, items, masked_index, B, L, D, pos_score, neg_score, lossrow, loss, id_bstride,
-                           pos_off, neg_off, stream);
-}
 
-// The second stage alone: loss = (1/B) sum_b sum_t lossrow[b,t] in bpr_reduce_kernel's fixed order (for producers of lossrow
-// other than bpr_fwd_kernel: the LayerNorm launch with the fused head, layernorm.hip).
-extern "C" int pxr_bpr_loss_reduce_f32(const float* lossrow, int B, int L, float* loss, void* stream) {
-  PXR_REQUIRE(lossrow && loss && B > 0 && L > 0, "pxr_bpr_loss_reduce_f32: bad args");
+// The second stage alone (pxr_common.h).
+int pxr_bpr_loss_reduce(const float* lossrow, int B, int L, float* loss, void* stream) {
+  PXR_REQUIRE(lossrow && loss && B > 0 && L > 0, "pxr_bpr_loss_reduce: bad args");
   hipLaunchKernelGGL(bpr_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, lossrow, B, L, loss);
-  return pxr_check_launch("pxr_bpr_loss_reduce_f32");
+  return pxr_check_launch("pxr_bpr_loss_reduce");
 }
 
-// dout [B*L, D] and coef [B*L] from the saved scores; upstream d(loss) = grad_scale * (*grad_scale_dev if given).
-static int bpr_loss_bwd_impl(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
-                             const int64_t* items, const int64_t* masked_index, int B, int L, int D, float grad_scale,
-                             const float* grad_scale_dev, float* dout, float* coef, int64_t id_bstride, int64_t pos_off,
-                             int64_t neg_off, void* stream) {
+// dout [B*L, D] and coef [B*L] from the saved scores; upstream d(loss) = grad_scale * (*grad_scale_dev if given).  The id layout
+// is pxr_bpr_loss_fwd_f32's (BERT4Rec: reference IDNet/bert4rec.py:98-113 under autograd).
+extern "C" int pxr_bpr_loss_bwd_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
+                                    const int64_t* items, const int64_t* masked_index, int B, int L, int D, float grad_scale,
+                                    const float* grad_scale_dev, float* dout, float* coef, int64_t id_bstride,
+                                    int64_t pos_off, int64_t neg_off, void* stream) {
+  PXR_REQUIRE(pxr_bpr_layout_ok(L, id_bstride, pos_off, neg_off), "pxr_bpr_loss_bwd_f32: bad id layout");
   PXR_REQUIRE(pos_score && neg_score && table && items && masked_index && dout && coef,
               "pxr_bpr_loss_bwd_f32: null pointer");
   PXR_REQUIRE(B > 0 && L > 0 && D > 0 && D % 4 == 0, "pxr_bpr_loss_bwd_f32: bad shape");
@@ -181,20 +167,4 @@ static int bpr_loss_bwd_impl(const float* pos_score, const float* neg_score, con
   a.id_bstride = id_bstride; a.pos_off = pos_off; a.neg_off = neg_off;
   hipLaunchKernelGGL(bpr_bwd_kernel, dim3((B * L + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
   return pxr_check_launch("pxr_bpr_loss_bwd_f32");
-}
-extern "C" int pxr_bpr_loss_bwd_f32(const float* pos_score, const float* neg_score, const float* table,
-                                    int64_t n_table, const int64_t* items, const int64_t* masked_index, int B, int L,
-                                    int D, float grad_scale, const float* grad_scale_dev, float* dout, float* coef,
-                                    void* stream) {
-  return bpr_loss_bwd_impl(pos_score, neg_score, table, n_table, items, masked_index, B, L, D, grad_scale, grad_scale_dev, dout,
-                           coef, 2 * (int64_t)(L + 1), 1, L + 2, stream);
-}
-// ... with the id layout of pxr_bpr_loss_fwd_lay_f32 (BERT4Rec: reference IDNet/bert4rec.py:98-113 under autograd)
-extern "C" int pxr_bpr_loss_bwd_lay_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
-                                        const int64_t* items, const int64_t* masked_index, int B, int L, int D, float grad_scale,
-                                        const float* grad_scale_dev, float* dout, float* coef, int64_t id_bstride,
-                                        int64_t pos_off, int64_t neg_off, void* stream) {
-  PXR_REQUIRE(bpr_layout_ok(L, id_bstride, pos_off, neg_off), "pxr_bpr_loss_bwd_lay_f32: bad id layout");
-  return bpr_loss_bwd_impl(pos_score, neg_score, table, n_table, items, masked_index, B, L, D, grad_scale, grad_scale_dev, dout,
-                           coef, id_bstride, pos_off, neg_off, stream);
 }

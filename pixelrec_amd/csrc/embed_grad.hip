@@ -41,7 +41,6 @@ __global__ void __launch_bounds__(256) occ_keys_rows_kernel(const int64_t* __res
 // id layout of the three occurrence kinds: position t of sequence b reads items[b*bstride + off[kind] + t].  SASRec's shifted
 // [B, 2, L+1] windows: bstride 2(L+1), off (0, 1, L+2); BERT4Rec's aligned [B, 3, L] planes: bstride 3L, off (0, L, 2L)
 struct OccLayout { int64_t bstride, off_in, off_pos, off_neg; };
-__host__ __device__ inline OccLayout sasrec_occ_layout(int L) { return OccLayout{2 * (int64_t)(L + 1), 0, 1, (int64_t)L + 2}; }
 
 __global__ void __launch_bounds__(256) occ_keys_sasrec_kernel(const int64_t* __restrict__ items, int B, int L,
                                                               int* __restrict__ keys, int* __restrict__ vals,
@@ -900,7 +899,7 @@ static int fused_sort(const int64_t* src, int n, int B, int L, int64_t n_table, 
   *sorted_vals = vin;
   return pxr_check_launch("embed grad (fused sort/segment)");
 }
-// where pxr_sasrec_occ_sort leaves the sorted occurrence ids for pxr_sasrec_occ_segsum
+// where pxr_seq_occ_sort leaves the sorted occurrence ids for pxr_sasrec_occ_segsum
 static const int* sasrec_sorted_vals(const SortWs& w, int n, int64_t n_table) {
   const int npass = use_fused_sort(n) ? fused_passes(n_table) : radix_passes(n_table);
   return (npass & 1) ? w.valsB : w.valsA;   // the ping-pong buffers swap once per pass
@@ -940,48 +939,40 @@ extern "C" int pxr_embed_grad_rows_f32(const int64_t* idx, int64_t n, const floa
 }
 
 
-// Phase 1 of the SASRec table gradient: occurrence keys -> stable sort -> unique ids + segments.  Depends on
-// `items` only, so it can run BEFORE the forward pass (the lazy table optimizer needs the unique rows of the batch
-// to bring them up to date before they are read).  The sorted state stays in `ws` for phase 2: the caller must keep
-// `ws` untouched in between.
-static int occ_sort_impl(const int64_t* items, int B, int L, int64_t n_table, int64_t* uniq_idx, int32_t* n_uniq_dev, void* ws,
-                         int64_t ws_bytes, OccLayout lay, void* stream) {
-  PXR_REQUIRE(items && uniq_idx && n_uniq_dev && ws, "pxr_sasrec_occ_sort: null pointer");
+// Phase 1 of the table gradient: occurrence keys -> stable sort -> unique ids + segments.  Depends on `items` only, so it can
+// run BEFORE the forward pass (the lazy table optimizer needs the unique rows of the batch to bring them up to date before they
+// are read).  The sorted state stays in `ws` for phase 2: the caller must keep `ws` untouched in between.  The three occurrence
+// kinds -- input | target | negative of position t of sequence b -- are at items[b*id_bstride + {in_off, pos_off, neg_off} + t]:
+// SASRec's shifted [B, 2, L+1] windows are (2(L+1), 0, 1, L+2); BERT4Rec's items [B, 3, L] = masked sequence | original sequence |
+// negatives are (3L, 0, L, 2L) -- the table's three uses in reference IDNet/bert4rec.py:76-81,98-111 under autograd; its
+// mask-token row is an ordinary row, row 0 (padding_idx) is dropped.  Phase 2 is pxr_sasrec_occ_segsum[_split] whatever the
+// layout: the occurrence o of kind k at row r = b*L + t adds dx0[r], +coef[r] out[r] or -coef[r] out[r].
+extern "C" int pxr_seq_occ_sort(const int64_t* items, int B, int L, int64_t id_bstride, int64_t in_off, int64_t pos_off,
+                                int64_t neg_off, int64_t n_table, int64_t* uniq_idx, int32_t* n_uniq_dev, void* ws,
+                                int64_t ws_bytes, void* stream) {
+  PXR_REQUIRE(id_bstride > 0 && in_off >= 0 && pos_off >= 0 && neg_off >= 0 && in_off + L <= id_bstride && pos_off + L <= id_bstride &&
+              neg_off + L <= id_bstride, "pxr_seq_occ_sort: bad id layout");
+  PXR_REQUIRE(items && uniq_idx && n_uniq_dev && ws, "pxr_seq_occ_sort: null pointer");
   const int64_t n64 = (int64_t)3 * B * L;
-  PXR_REQUIRE(B > 0 && L > 0 && n64 < (1ll << 30) && n_table > 0 && n_table < (1ll << 31), "pxr_sasrec_occ_sort: bad shape");
+  PXR_REQUIRE(B > 0 && L > 0 && n64 < (1ll << 30) && n_table > 0 && n_table < (1ll << 31), "pxr_seq_occ_sort: bad shape");
   const int n = (int)n64;
+  const OccLayout lay{id_bstride, in_off, pos_off, neg_off};
   SortWs w;
-  if (carve(ws, n, &w) > ws_bytes) { pxr_set_error("pxr_sasrec_occ_sort: workspace too small"); return PXR_ERR_WORKSPACE; }
+  if (carve(ws, n, &w) > ws_bytes) { pxr_set_error("pxr_seq_occ_sort: workspace too small"); return PXR_ERR_WORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
   const int* sorted_vals = nullptr;
   if (use_fused_sort(n)) {
     int rc = fused_sort<MODE_SASREC>(items, n, B, L, n_table, w, uniq_idx, n_uniq_dev, st, &sorted_vals, lay);
     if (rc) return rc;
-    if (sorted_vals != sasrec_sorted_vals(w, n, n_table)) { pxr_set_error("pxr_sasrec_occ_sort: internal buffer parity"); return PXR_ERR_LAUNCH; }
+    if (sorted_vals != sasrec_sorted_vals(w, n, n_table)) { pxr_set_error("pxr_seq_occ_sort: internal buffer parity"); return PXR_ERR_LAUNCH; }
     return PXR_OK;
   }
   hipLaunchKernelGGL(occ_keys_sasrec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, items, B, L, w.keysA, w.valsA,
                      n_table, lay);
   int rc = sort_and_segment(w, n, n_table, uniq_idx, n_uniq_dev, st, &sorted_vals);
   if (rc) return rc;
-  if (sorted_vals != sasrec_sorted_vals(w, n, n_table)) { pxr_set_error("pxr_sasrec_occ_sort: internal buffer parity"); return PXR_ERR_LAUNCH; }
+  if (sorted_vals != sasrec_sorted_vals(w, n, n_table)) { pxr_set_error("pxr_seq_occ_sort: internal buffer parity"); return PXR_ERR_LAUNCH; }
   return PXR_OK;
-}
-extern "C" int pxr_sasrec_occ_sort(const int64_t* items, int B, int L, int64_t n_table, int64_t* uniq_idx,
-                                   int32_t* n_uniq_dev, void* ws, int64_t ws_bytes, void* stream) {
-  return occ_sort_impl(items, B, L, n_table, uniq_idx, n_uniq_dev, ws, ws_bytes, sasrec_occ_layout(L), stream);
-}
-// Phase 1 for another id layout of the same three occurrence kinds (input | target | negative of position t of sequence b at
-// items[b*id_bstride + {in_off, pos_off, neg_off} + t]).  BERT4Rec: items [B, 3, L] = masked sequence | original sequence |
-// negatives, layout (3L, 0, L, 2L) -- the table's three uses in reference IDNet/bert4rec.py:76-81,98-111 under autograd; its
-// mask-token row is an ordinary row, row 0 (padding_idx) is dropped.  Phase 2 is pxr_sasrec_occ_segsum[_split] unchanged: the
-// occurrence o of kind k at row r = b*L + t adds dx0[r], +coef[r] out[r] or -coef[r] out[r] whatever the layout.
-extern "C" int pxr_seq_occ_sort_lay(const int64_t* items, int B, int L, int64_t id_bstride, int64_t in_off, int64_t pos_off,
-                                    int64_t neg_off, int64_t n_table, int64_t* uniq_idx, int32_t* n_uniq_dev, void* ws,
-                                    int64_t ws_bytes, void* stream) {
-  PXR_REQUIRE(id_bstride > 0 && in_off >= 0 && pos_off >= 0 && neg_off >= 0 && in_off + L <= id_bstride && pos_off + L <= id_bstride &&
-              neg_off + L <= id_bstride, "pxr_seq_occ_sort_lay: bad id layout");
-  return occ_sort_impl(items, B, L, n_table, uniq_idx, n_uniq_dev, ws, ws_bytes, OccLayout{id_bstride, in_off, pos_off, neg_off}, stream);
 }
 
 // Phase 2: uniq_rows[u,:] = scale * sum over the occurrences of unique id u (see the header comment for the terms).
@@ -1044,16 +1035,6 @@ extern "C" int pxr_sasrec_occ_segsum_split(const void* ws, int64_t ws_bytes, int
   hipLaunchKernelGGL(segsum_parts_kernel<MODE_SASREC>, dim3(a.max_parts < 1024 ? a.max_parts : 1024), dim3(SEG_THREADS), SEG_THREADS * 16, st, a);
   hipLaunchKernelGGL(segsum_big_kernel, dim3(a.big_cap < 64 ? a.big_cap : 64), dim3(SEG_THREADS), 0, st, a);
   return pxr_check_launch("pxr_sasrec_occ_segsum_split");
-}
-
-// Both phases back to back (gradient-only use).
-extern "C" int pxr_sasrec_embed_grad_f32(const int64_t* items, int B, int L, const float* dx0, const float* out,
-                                         const float* coef, int D, int64_t n_table, float scale, int64_t* uniq_idx,
-                                         float* uniq_rows, int32_t* n_uniq_dev, void* ws, int64_t ws_bytes,
-                                         void* stream) {
-  int rc = pxr_sasrec_occ_sort(items, B, L, n_table, uniq_idx, n_uniq_dev, ws, ws_bytes, stream);
-  if (rc) return rc;
-  return pxr_sasrec_occ_segsum(ws, ws_bytes, B, L, dx0, out, coef, D, n_table, scale, n_uniq_dev, uniq_rows, stream);
 }
 
 extern "C" int64_t pxr_merge_rows_ws_bytes(int W, int64_t cap) {

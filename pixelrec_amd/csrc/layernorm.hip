@@ -560,26 +560,16 @@ using namespace pxr;
 
 // y = dropout(LN(table[idx] + pos))   rows = B*L; idx element (b,t) at idx[b*idx_bstride + t].
 // xhat / rstd may be null (inference).  (sasrec.py:68,77-82 train; :99-104 predict)
-extern "C" int pxr_input_ln_fwd_planes_f32(const float* table, int64_t n_table, const int64_t* idx, int64_t idx_bstride,
-                                           const float* pos, const float* gamma, const float* beta, float eps, int B, int L,
-                                           int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
-                                           uint32_t stream_id, const int64_t* step_dev, void* y_planes,
-                                           int64_t y_plane_stride, int64_t y_panel_rows, void* stream);
+// y is additionally written as planes, the QKV GEMM's operand: planes_fmt 0 = bf16x3 (y_planes may be NULL); 1 = two fp16 planes
+// (planes.cuh "h2", unit scale; the operand of pxr_gemm_h2_f32; y_planes required).
 extern "C" int pxr_input_ln_fwd_f32(const float* table, int64_t n_table, const int64_t* idx, int64_t idx_bstride,
                                     const float* pos, const float* gamma, const float* beta, float eps, int B, int L,
                                     int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
-                                    uint32_t stream_id, const int64_t* step_dev, void* stream) {
-  return pxr_input_ln_fwd_planes_f32(table, n_table, idx, idx_bstride, pos, gamma, beta, eps, B, L, D, y, xhat, rstd, p_drop,
-                                     seed, stream_id, step_dev, nullptr, 0, 0, stream);
-}
-// the same, y additionally written as bf16x3 planes (y_planes may be NULL): the QKV GEMM's operand
-extern "C" int pxr_input_ln_fwd_planes_f32(const float* table, int64_t n_table, const int64_t* idx, int64_t idx_bstride,
-                                           const float* pos, const float* gamma, const float* beta, float eps, int B, int L,
-                                           int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
-                                           uint32_t stream_id, const int64_t* step_dev, void* y_planes,
-                                           int64_t y_plane_stride, int64_t y_panel_rows, void* stream) {
-  PXR_REQUIRE(table && idx && pos && gamma && beta && y, "pxr_input_ln_fwd_f32: null pointer");
-  PXR_REQUIRE(p3_mat_ok(y_planes, y_plane_stride, y_panel_rows, (int64_t)B * L, D), "pxr_input_ln_fwd_planes_f32: bad planes");
+                                    uint32_t stream_id, const int64_t* step_dev, void* y_planes,
+                                    int64_t y_plane_stride, int64_t y_panel_rows, int planes_fmt, void* stream) {
+  PXR_REQUIRE(planes_fmt == 0 || planes_fmt == 1, "pxr_input_ln_fwd_f32: planes_fmt must be 0 (bf16x3) or 1 (h2)");
+  PXR_REQUIRE(table && idx && pos && gamma && beta && y && (planes_fmt == 0 || y_planes), "pxr_input_ln_fwd_f32: null pointer");
+  PXR_REQUIRE(p3_mat_ok(y_planes, y_plane_stride, y_panel_rows, (int64_t)B * L, D), "pxr_input_ln_fwd_f32: bad planes");
   PXR_REQUIRE(D > 0 && D % 4 == 0 && B >= 0 && L > 0, "pxr_input_ln_fwd_f32: bad shape");
   PXR_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "pxr_input_ln_fwd_f32: bad dropout p");
   if (B == 0) return PXR_OK;
@@ -590,26 +580,21 @@ extern "C" int pxr_input_ln_fwd_planes_f32(const float* table, int64_t n_table, 
   a.p_drop = p_drop; a.drop_thr = pxr_drop_threshold(p_drop); a.stream = stream_id; a.seed = seed;
   a.step_dev = step_dev;
   a.yp = P3Mat{reinterpret_cast<__bf16*>(y_planes), y_plane_stride, y_panel_rows};
+  a.yp_fmt = planes_fmt == 1 ? PXR_PLANES_H2 : PXR_PLANES_BF16X3;
   return launch_ln_fwd<true>(a, (hipStream_t)stream);
 }
 
-// y = LN(dropout(x) + res)   (layers.py:614-615, :670-671).  res may be null.
-extern "C" int pxr_ln_residual_fwd_planes_f32(const float* x, const float* res, const float* gamma, const float* beta,
-                                              float eps, int rows, int D, float* y, float* xhat, float* rstd, float p_drop,
-                                              uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* y_planes,
-                                              int64_t y_plane_stride, int64_t y_panel_rows, void* stream);
+// y = LN(dropout(x) + res)   (layers.py:614-615, :670-671).  res may be null.  y is additionally -- or, y == NULL, only --
+// written as planes: planes_fmt 0 = bf16x3 (y_planes may be NULL); 1 = two fp16 planes (planes.cuh "h2", unit scale; the operand
+// of pxr_gemm_h2_f32 -- the image tower, the sequence block of large batches; y_planes required): a LayerNorm output beyond the
+// fp16 range then sets PXR_STATUS_H2_RANGE in the registered status word.
 extern "C" int pxr_ln_residual_fwd_f32(const float* x, const float* res, const float* gamma, const float* beta,
                                        float eps, int rows, int D, float* y, float* xhat, float* rstd, float p_drop,
-                                       uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* stream) {
-  return pxr_ln_residual_fwd_planes_f32(x, res, gamma, beta, eps, rows, D, y, xhat, rstd, p_drop, seed, stream_id, step_dev,
-                                        nullptr, 0, 0, stream);
-}
-extern "C" int pxr_ln_residual_fwd_planes_f32(const float* x, const float* res, const float* gamma, const float* beta,
-                                              float eps, int rows, int D, float* y, float* xhat, float* rstd, float p_drop,
-                                              uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* y_planes,
-                                              int64_t y_plane_stride, int64_t y_panel_rows, void* stream) {
-  PXR_REQUIRE(x && gamma && beta && (y || y_planes), "pxr_ln_residual_fwd_f32: null pointer");   // y optional next to planes
-  PXR_REQUIRE(p3_mat_ok(y_planes, y_plane_stride, y_panel_rows, rows, D), "pxr_ln_residual_fwd_planes_f32: bad planes");
+                                       uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* y_planes,
+                                       int64_t y_plane_stride, int64_t y_panel_rows, int planes_fmt, void* stream) {
+  PXR_REQUIRE(planes_fmt == 0 || planes_fmt == 1, "pxr_ln_residual_fwd_f32: planes_fmt must be 0 (bf16x3) or 1 (h2)");
+  PXR_REQUIRE(x && gamma && beta && (y_planes || (planes_fmt == 0 && y)), "pxr_ln_residual_fwd_f32: null pointer");
+  PXR_REQUIRE(p3_mat_ok(y_planes, y_plane_stride, y_panel_rows, rows, D), "pxr_ln_residual_fwd_f32: bad planes");
   PXR_REQUIRE(D > 0 && D % 4 == 0 && rows >= 0, "pxr_ln_residual_fwd_f32: bad shape");
   PXR_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "pxr_ln_residual_fwd_f32: bad dropout p");
   if (rows == 0) return PXR_OK;
@@ -618,19 +603,24 @@ extern "C" int pxr_ln_residual_fwd_planes_f32(const float* x, const float* res, 
   a.rows = rows; a.D = D; a.L = 1; a.eps = eps;
   a.p_drop = p_drop; a.drop_thr = pxr_drop_threshold(p_drop); a.stream = stream_id; a.seed = seed;
   a.step_dev = step_dev;
+  if (planes_fmt == 1) a.status = pxr_status_word();   // the range check of the h2 planes (the bf16x3 form has none)
   a.yp = P3Mat{reinterpret_cast<__bf16*>(y_planes), y_plane_stride, y_panel_rows};
+  a.yp_fmt = planes_fmt == 1 ? PXR_PLANES_H2 : PXR_PLANES_BF16X3;
   return launch_ln_fwd<false>(a, (hipStream_t)stream);
 }
 // The block's LAST LayerNorm with the loss head's forward fused in (BprHead): y = LN(dropout(x) + res) over rows = B*L, and
 // for every row the two target-row scores + the per-position loss term; then the fixed-order loss reduction (bpr_loss.hip).
 // Replaces pxr_ln_residual_fwd_f32 + pxr_bpr_loss_fwd_f32 (reference layers.py:670-671 + sasrec.py:86-92): one launch and one
-// pass over `y` less; bit-identical outputs.
-extern "C" int pxr_bpr_loss_reduce_f32(const float* lossrow, int B, int L, float* loss, void* stream);
-static int ln_residual_bpr_fwd_impl(const float* x, const float* res, const float* gamma, const float* beta, float eps, int B, int L,
-                                    int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed, uint32_t stream_id,
-                                    const int64_t* step_dev, const float* table, int64_t n_table, const int64_t* items,
-                                    const int64_t* masked_index, float* pos_score, float* neg_score, float* lossrow, float* loss,
-                                    int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream) {
+// pass over `y` less; bit-identical outputs.  The id layout (BprHead::id_bstride): SASRec's shifted windows pass
+// (2(L+1), 1, L+2); BERT4Rec's aligned masked head (reference IDNet/bert4rec.py:98-111 on the output of layers.py:670-671) passes
+// (3L, L, 2L) for items [B, 3, L] = (masked sequence | original sequence | negatives).
+extern "C" int pxr_ln_residual_bpr_fwd_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps,
+                                           int B, int L, int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
+                                           uint32_t stream_id, const int64_t* step_dev, const float* table, int64_t n_table,
+                                           const int64_t* items, const int64_t* masked_index, float* pos_score,
+                                           float* neg_score, float* lossrow, float* loss, int64_t id_bstride, int64_t pos_off,
+                                           int64_t neg_off, void* stream) {
+  PXR_REQUIRE(pxr_bpr_layout_ok(L, id_bstride, pos_off, neg_off), "pxr_ln_residual_bpr_fwd_f32: bad id layout");
   PXR_REQUIRE(x && gamma && beta && y && table && items && masked_index && pos_score && neg_score && lossrow && loss,
               "pxr_ln_residual_bpr_fwd_f32: null pointer");
   PXR_REQUIRE(D > 0 && D % 4 == 0 && B > 0 && L > 0 && n_table > 0, "pxr_ln_residual_bpr_fwd_f32: bad shape");
@@ -645,69 +635,7 @@ static int ln_residual_bpr_fwd_impl(const float* x, const float* res, const floa
   a.head.id_bstride = id_bstride; a.head.pos_off = pos_off; a.head.neg_off = neg_off;
   const int rc = launch_ln_fwd<false>(a, (hipStream_t)stream);
   if (rc) return rc;
-  return pxr_bpr_loss_reduce_f32(lossrow, B, L, loss, stream);
-}
-extern "C" int pxr_ln_residual_bpr_fwd_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps, int B,
-                                           int L, int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
-                                           uint32_t stream_id, const int64_t* step_dev, const float* table, int64_t n_table,
-                                           const int64_t* items, const int64_t* masked_index, float* pos_score, float* neg_score,
-                                           float* lossrow, float* loss, void* stream) {
-  return ln_residual_bpr_fwd_impl(x, res, gamma, beta, eps, B, L, D, y, xhat, rstd, p_drop, seed, stream_id, step_dev, table, n_table,
-                                  items, masked_index, pos_score, neg_score, lossrow, loss, 2 * (int64_t)(L + 1), 1, L + 2, stream);
-}
-// ... with the id layout as arguments (BprHead::id_bstride): BERT4Rec's aligned masked head (reference IDNet/bert4rec.py:98-111 on
-// the output of layers.py:670-671) passes (3L, L, 2L) for items [B, 3, L] = (masked sequence | original sequence | negatives).
-extern "C" int pxr_ln_residual_bpr_fwd_lay_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps,
-                                               int B, int L, int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
-                                               uint32_t stream_id, const int64_t* step_dev, const float* table, int64_t n_table,
-                                               const int64_t* items, const int64_t* masked_index, float* pos_score,
-                                               float* neg_score, float* lossrow, float* loss, int64_t id_bstride, int64_t pos_off,
-                                               int64_t neg_off, void* stream) {
-  PXR_REQUIRE(id_bstride > 0 && pos_off >= 0 && neg_off >= 0 && pos_off + L <= id_bstride && neg_off + L <= id_bstride,
-              "pxr_ln_residual_bpr_fwd_lay_f32: bad id layout");
-  return ln_residual_bpr_fwd_impl(x, res, gamma, beta, eps, B, L, D, y, xhat, rstd, p_drop, seed, stream_id, step_dev, table, n_table,
-                                  items, masked_index, pos_score, neg_score, lossrow, loss, id_bstride, pos_off, neg_off, stream);
-}
-// the same with y as TWO fp16 planes (planes.cuh "h2", unit scale): the operand of pxr_gemm_h2_f32 -- the image tower, the sequence
-// block of large batches.  A LayerNorm output beyond the fp16 range sets PXR_STATUS_H2_RANGE in the registered status word.
-extern "C" int pxr_ln_residual_fwd_h2_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps,
-                                          int rows, int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
-                                          uint32_t stream_id, const int64_t* step_dev, void* y_planes, int64_t y_plane_stride,
-                                          int64_t y_panel_rows, void* stream) {
-  PXR_REQUIRE(x && gamma && beta && y_planes, "pxr_ln_residual_fwd_h2_f32: null pointer");
-  PXR_REQUIRE(p3_mat_ok(y_planes, y_plane_stride, y_panel_rows, rows, D), "pxr_ln_residual_fwd_h2_f32: bad planes");
-  PXR_REQUIRE(D > 0 && D % 4 == 0 && rows >= 0, "pxr_ln_residual_fwd_h2_f32: bad shape");
-  PXR_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "pxr_ln_residual_fwd_h2_f32: bad dropout p");
-  if (rows == 0) return PXR_OK;
-  LnFwdArgs a{};
-  a.x = x; a.res = res; a.gamma = gamma; a.beta = beta; a.y = y; a.xhat = xhat; a.rstd = rstd;
-  a.rows = rows; a.D = D; a.L = 1; a.eps = eps;
-  a.p_drop = p_drop; a.drop_thr = pxr_drop_threshold(p_drop); a.stream = stream_id; a.seed = seed;
-  a.step_dev = step_dev;
-  a.status = pxr_status_word();
-  a.yp = P3Mat{reinterpret_cast<__bf16*>(y_planes), y_plane_stride, y_panel_rows};
-  a.yp_fmt = PXR_PLANES_H2;
-  return launch_ln_fwd<false>(a, (hipStream_t)stream);
-}
-extern "C" int pxr_input_ln_fwd_h2_f32(const float* table, int64_t n_table, const int64_t* idx, int64_t idx_bstride,
-                                       const float* pos, const float* gamma, const float* beta, float eps, int B, int L, int D,
-                                       float* y, float* xhat, float* rstd, float p_drop, uint64_t seed, uint32_t stream_id,
-                                       const int64_t* step_dev, void* y_planes, int64_t y_plane_stride, int64_t y_panel_rows,
-                                       void* stream) {
-  PXR_REQUIRE(table && idx && pos && gamma && beta && y && y_planes, "pxr_input_ln_fwd_h2_f32: null pointer");
-  PXR_REQUIRE(p3_mat_ok(y_planes, y_plane_stride, y_panel_rows, (int64_t)B * L, D), "pxr_input_ln_fwd_h2_f32: bad planes");
-  PXR_REQUIRE(D > 0 && D % 4 == 0 && B >= 0 && L > 0, "pxr_input_ln_fwd_h2_f32: bad shape");
-  PXR_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "pxr_input_ln_fwd_h2_f32: bad dropout p");
-  if (B == 0) return PXR_OK;
-  LnFwdArgs a{};
-  a.table = table; a.idx = idx; a.pos = pos; a.gamma = gamma; a.beta = beta; a.y = y; a.xhat = xhat; a.rstd = rstd;
-  a.idx_bstride = idx_bstride; a.n_table = n_table; a.rows = B * L; a.D = D; a.L = L; a.eps = eps;
-  a.status = pxr_status_word();
-  a.p_drop = p_drop; a.drop_thr = pxr_drop_threshold(p_drop); a.stream = stream_id; a.seed = seed;
-  a.step_dev = step_dev;
-  a.yp = P3Mat{reinterpret_cast<__bf16*>(y_planes), y_plane_stride, y_panel_rows};
-  a.yp_fmt = PXR_PLANES_H2;
-  return launch_ln_fwd<true>(a, (hipStream_t)stream);
+  return pxr_bpr_loss_reduce(lossrow, B, L, loss, stream);
 }
 
 extern "C" int pxr_ln_bwd_partial_rows(int rows) {
@@ -723,30 +651,18 @@ extern "C" int64_t pxr_ln_bwd_ws_bytes(int rows, int D) {
 
 // Backward of either LN site.  gather_mode=1: dy is w.r.t. dropout(LN(z)) and the mask is re-applied to dy;
 // gather_mode=0: dx (optional) = dropout-mask(dz)/(1-p) is the gradient w.r.t. the sub-layer output x and dz
-// the gradient w.r.t. the residual.  dgamma/dbeta are OVERWRITTEN (not accumulated).
-extern "C" int pxr_ln_bwd_planes_f32(int gather_mode, const float* dy, const float* xhat, const float* rstd,
-                                     const float* gamma, int rows, int D, float* dz, float* dx, float* dgamma, float* dbeta,
-                                     float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws,
-                                     int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows,
-                                     void* stream);
-extern "C" int pxr_ln_bwd_f32(int gather_mode, const float* dy, const float* xhat, const float* rstd,
-                              const float* gamma, int rows, int D, float* dz, float* dx, float* dgamma, float* dbeta,
-                              float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws,
-                              int64_t ws_bytes, void* stream) {
-  return pxr_ln_bwd_planes_f32(gather_mode, dy, xhat, rstd, gamma, rows, D, dz, dx, dgamma, dbeta, p_drop, seed, stream_id,
-                               step_dev, ws, ws_bytes, nullptr, 0, 0, stream);
-}
-// the same (gather_mode = 0), the gradient the next GEMMs read (dx when given, else dz) additionally written as planes
+// the gradient w.r.t. the residual.  dgamma/dbeta are OVERWRITTEN (not accumulated).  g_planes (gather_mode 0 only, may be NULL):
+// the gradient the next GEMMs read (dx when given, else dz) additionally written as bf16x3 planes.
 static int ln_bwd_impl(int gather_mode, const float* dy, const float* xhat, const float* rstd, const float* gamma, int rows, int D,
                        float* dz, float* dx, float* dgamma, float* dbeta, float p_drop, uint64_t seed, uint32_t stream_id,
                        const int64_t* step_dev, void* ws, int64_t ws_bytes, void* g_planes, int64_t g_plane_stride,
                        int64_t g_panel_rows, float* stat, void* stream, const BprHead* head = nullptr, float* zero = nullptr,
                        int zero_n = 0, const int* g_exp = nullptr, int dx_virtual = 0, const float* res = nullptr);
-extern "C" int pxr_ln_bwd_planes_f32(int gather_mode, const float* dy, const float* xhat, const float* rstd,
-                                     const float* gamma, int rows, int D, float* dz, float* dx, float* dgamma, float* dbeta,
-                                     float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws,
-                                     int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows,
-                                     void* stream) {
+extern "C" int pxr_ln_bwd_f32(int gather_mode, const float* dy, const float* xhat, const float* rstd,
+                              const float* gamma, int rows, int D, float* dz, float* dx, float* dgamma, float* dbeta,
+                              float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws,
+                              int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows,
+                              void* stream) {
   return ln_bwd_impl(gather_mode, dy, xhat, rstd, gamma, rows, D, dz, dx, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes,
                      g_planes, g_plane_stride, g_panel_rows, nullptr, stream);
 }
@@ -772,59 +688,39 @@ extern "C" int pxr_ln_bwd_res_f32(const float* dy, const float* xhat, const floa
 }
 // The backward of the block's LAST LayerNorm with the loss head's backward fused in: dy is not read but formed per row from the
 // saved scores (bpr_loss.hip: coef * (E[pos] - E[neg])); coef [B*L] is written for the table-gradient segment sums.  Replaces
-// pxr_bpr_loss_bwd_f32 + pxr_ln_bwd_planes_f32 / pxr_ln_bwd_stat_f32 (gather_mode 0); g_planes and stat are both optional.
-static int bpr_ln_bwd_impl(const float* pos_score, const float* neg_score, const float* table, int64_t n_table, const int64_t* items,
-                           const int64_t* masked_index, int B, int L, float grad_scale, const float* grad_scale_dev, float* coef,
-                           const float* xhat, const float* rstd, const float* gamma, int D, float* dz, float* dx, float* dgamma,
-                           float* dbeta, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws,
-                           int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, float* stat,
-                           const int64_t* layout, void* stream) {
-  PXR_REQUIRE(pos_score && neg_score && table && items && masked_index && coef && B > 0 && L > 0 && n_table > 0,
-              "pxr_bpr_ln_bwd_f32: null pointer / bad shape");
-  BprHead h{};
-  h.table = table; h.items = items; h.mask = masked_index; h.pos = const_cast<float*>(pos_score); h.neg = const_cast<float*>(neg_score);
-  h.coef = coef; h.n_table = n_table; h.B = B; h.L = L; h.grad_scale = grad_scale; h.grad_scale_dev = grad_scale_dev;
-  h.id_bstride = 2 * (int64_t)(L + 1); h.pos_off = 1; h.neg_off = L + 2;
-  if (layout) { h.id_bstride = layout[0]; h.pos_off = layout[1]; h.neg_off = layout[2]; }
-  return ln_bwd_impl(0, nullptr, xhat, rstd, gamma, B * L, D, dz, dx, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes,
-                     g_planes, g_plane_stride, g_panel_rows, stat, stream, &h);
-}
+// pxr_bpr_loss_bwd_f32 + pxr_ln_bwd_f32 / pxr_ln_bwd_stat_f32 (gather_mode 0); g_planes and stat are both optional.  The id
+// layout is pxr_ln_residual_bpr_fwd_f32's (BERT4Rec: reference IDNet/bert4rec.py:98-113 under autograd).
 extern "C" int pxr_bpr_ln_bwd_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
                                   const int64_t* items, const int64_t* masked_index, int B, int L, float grad_scale,
                                   const float* grad_scale_dev, float* coef, const float* xhat, const float* rstd,
                                   const float* gamma, int D, float* dz, float* dx, float* dgamma, float* dbeta, float p_drop,
                                   uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes,
-                                  void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, float* stat, void* stream) {
-  return bpr_ln_bwd_impl(pos_score, neg_score, table, n_table, items, masked_index, B, L, grad_scale, grad_scale_dev, coef, xhat, rstd,
-                         gamma, D, dz, dx, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes, g_planes, g_plane_stride,
-                         g_panel_rows, stat, nullptr, stream);
-}
-// ... with the id layout of pxr_ln_residual_bpr_fwd_lay_f32 (BERT4Rec: reference IDNet/bert4rec.py:98-113 under autograd)
-extern "C" int pxr_bpr_ln_bwd_lay_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
-                                      const int64_t* items, const int64_t* masked_index, int B, int L, float grad_scale,
-                                      const float* grad_scale_dev, float* coef, const float* xhat, const float* rstd,
-                                      const float* gamma, int D, float* dz, float* dx, float* dgamma, float* dbeta, float p_drop,
-                                      uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes,
-                                      void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, float* stat, int64_t id_bstride,
-                                      int64_t pos_off, int64_t neg_off, void* stream) {
-  PXR_REQUIRE(id_bstride > 0 && pos_off >= 0 && neg_off >= 0 && pos_off + L <= id_bstride && neg_off + L <= id_bstride,
-              "pxr_bpr_ln_bwd_lay_f32: bad id layout");
-  const int64_t lay[3] = {id_bstride, pos_off, neg_off};
-  return bpr_ln_bwd_impl(pos_score, neg_score, table, n_table, items, masked_index, B, L, grad_scale, grad_scale_dev, coef, xhat, rstd,
-                         gamma, D, dz, dx, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes, g_planes, g_plane_stride,
-                         g_panel_rows, stat, lay, stream);
+                                  void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, float* stat, int64_t id_bstride,
+                                  int64_t pos_off, int64_t neg_off, void* stream) {
+  PXR_REQUIRE(pxr_bpr_layout_ok(L, id_bstride, pos_off, neg_off), "pxr_bpr_ln_bwd_f32: bad id layout");
+  PXR_REQUIRE(pos_score && neg_score && table && items && masked_index && coef && B > 0 && L > 0 && n_table > 0,
+              "pxr_bpr_ln_bwd_f32: null pointer / bad shape");
+  BprHead h{};
+  h.table = table; h.items = items; h.mask = masked_index; h.pos = const_cast<float*>(pos_score); h.neg = const_cast<float*>(neg_score);
+  h.coef = coef; h.n_table = n_table; h.B = B; h.L = L; h.grad_scale = grad_scale; h.grad_scale_dev = grad_scale_dev;
+  h.id_bstride = id_bstride; h.pos_off = pos_off; h.neg_off = neg_off;
+  return ln_bwd_impl(0, nullptr, xhat, rstd, gamma, B * L, D, dz, dx, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes,
+                     g_planes, g_plane_stride, g_panel_rows, stat, stream, &h);
 }
 // A residual site's backward whose GEMM-facing gradient (dropout applied when p_drop > 0; no fp32 copy of it is written) leaves ONLY as
 // two fp16 planes of gradient * 2^g_exp_dev[0] -- an exponent that exists BEFORE the launch (the previous step's maximum of the same
 // gradient less PXR headroom binades: pxr_h2_sites_update) -- range-checked and saturated (PXR_STATUS_H2_STALE), together with this
 // step's partial maxima in stat[pxr_ln_bwd_partial_rows(rows)] for the next update.  pos_score != NULL: the loss head's backward is
-// fused in as in pxr_bpr_ln_bwd_f32 (dy unused).  Replaces pxr_ln_bwd_stat_f32 / pxr_bpr_ln_bwd_f32 + pxr_h2_split_parts_f32.
-static int ln_bwd_h2s_impl(const float* pos_score, const float* neg_score, const float* table, int64_t n_table, const int64_t* items,
-                           const int64_t* masked_index, int B, int L, float grad_scale, const float* grad_scale_dev, float* coef,
-                           const float* dy, const float* xhat, const float* rstd, const float* gamma, int rows, int D, float* dz,
-                           float* dgamma, float* dbeta, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
-                           void* ws, int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows,
-                           const int* g_exp_dev, float* stat, float* zero, int zero_n, const int64_t* layout, void* stream) {
+// fused in as in pxr_bpr_ln_bwd_f32 (dy unused), with its id layout.  Replaces pxr_ln_bwd_stat_f32 / pxr_bpr_ln_bwd_f32 +
+// pxr_h2_split_parts_f32.
+extern "C" int pxr_ln_bwd_h2s_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
+                                  const int64_t* items, const int64_t* masked_index, int B, int L, float grad_scale,
+                                  const float* grad_scale_dev, float* coef, const float* dy, const float* xhat, const float* rstd,
+                                  const float* gamma, int rows, int D, float* dz, float* dgamma, float* dbeta, float p_drop,
+                                  uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes,
+                                  void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, const int* g_exp_dev, float* stat,
+                                  float* zero, int zero_n, int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream) {
+  PXR_REQUIRE(pxr_bpr_layout_ok(L, id_bstride, pos_off, neg_off), "pxr_ln_bwd_h2s_f32: bad id layout");
   PXR_REQUIRE(g_planes && g_exp_dev && stat, "pxr_ln_bwd_h2s_f32: planes, their device exponent and the statistics buffer are required");
   BprHead h{};
   if (pos_score) {
@@ -832,37 +728,11 @@ static int ln_bwd_h2s_impl(const float* pos_score, const float* neg_score, const
                 "pxr_ln_bwd_h2s_f32: null pointer / bad shape of the fused loss head");
     h.table = table; h.items = items; h.mask = masked_index; h.pos = const_cast<float*>(pos_score); h.neg = const_cast<float*>(neg_score);
     h.coef = coef; h.n_table = n_table; h.B = B; h.L = L; h.grad_scale = grad_scale; h.grad_scale_dev = grad_scale_dev;
-    h.id_bstride = 2 * (int64_t)(L + 1); h.pos_off = 1; h.neg_off = L + 2;
-    if (layout) { h.id_bstride = layout[0]; h.pos_off = layout[1]; h.neg_off = layout[2]; }
+    h.id_bstride = id_bstride; h.pos_off = pos_off; h.neg_off = neg_off;
   }
   return ln_bwd_impl(0, pos_score ? nullptr : dy, xhat, rstd, gamma, rows, D, dz, nullptr, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws,
                      ws_bytes, g_planes, g_plane_stride, g_panel_rows, stat, stream, pos_score ? &h : nullptr, zero, zero_n, g_exp_dev,
                      p_drop > 0.f ? 1 : 0);
-}
-extern "C" int pxr_ln_bwd_h2s_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table, const int64_t* items,
-                                  const int64_t* masked_index, int B, int L, float grad_scale, const float* grad_scale_dev, float* coef,
-                                  const float* dy, const float* xhat, const float* rstd, const float* gamma, int rows, int D, float* dz,
-                                  float* dgamma, float* dbeta, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
-                                  void* ws, int64_t ws_bytes, void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows,
-                                  const int* g_exp_dev, float* stat, float* zero, int zero_n, void* stream) {
-  return ln_bwd_h2s_impl(pos_score, neg_score, table, n_table, items, masked_index, B, L, grad_scale, grad_scale_dev, coef, dy, xhat, rstd,
-                         gamma, rows, D, dz, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes, g_planes, g_plane_stride,
-                         g_panel_rows, g_exp_dev, stat, zero, zero_n, nullptr, stream);
-}
-// ... with the fused head's id layout as in pxr_bpr_ln_bwd_lay_f32 (BERT4Rec: reference IDNet/bert4rec.py:98-113 under autograd)
-extern "C" int pxr_ln_bwd_h2s_lay_f32(const float* pos_score, const float* neg_score, const float* table, int64_t n_table,
-                                      const int64_t* items, const int64_t* masked_index, int B, int L, float grad_scale,
-                                      const float* grad_scale_dev, float* coef, const float* dy, const float* xhat, const float* rstd,
-                                      const float* gamma, int rows, int D, float* dz, float* dgamma, float* dbeta, float p_drop,
-                                      uint64_t seed, uint32_t stream_id, const int64_t* step_dev, void* ws, int64_t ws_bytes,
-                                      void* g_planes, int64_t g_plane_stride, int64_t g_panel_rows, const int* g_exp_dev, float* stat,
-                                      float* zero, int zero_n, int64_t id_bstride, int64_t pos_off, int64_t neg_off, void* stream) {
-  PXR_REQUIRE(id_bstride > 0 && pos_off >= 0 && neg_off >= 0 && pos_off + L <= id_bstride && neg_off + L <= id_bstride,
-              "pxr_ln_bwd_h2s_lay_f32: bad id layout");
-  const int64_t lay[3] = {id_bstride, pos_off, neg_off};
-  return ln_bwd_h2s_impl(pos_score, neg_score, table, n_table, items, masked_index, B, L, grad_scale, grad_scale_dev, coef, dy, xhat, rstd,
-                         gamma, rows, D, dz, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes, g_planes, g_plane_stride,
-                         g_panel_rows, g_exp_dev, stat, zero, zero_n, lay, stream);
 }
 static int ln_bwd_impl(int gather_mode, const float* dy, const float* xhat, const float* rstd, const float* gamma, int rows, int D,
                        float* dz, float* dx, float* dgamma, float* dbeta, float p_drop, uint64_t seed, uint32_t stream_id,
@@ -875,7 +745,7 @@ static int ln_bwd_impl(int gather_mode, const float* dy, const float* xhat, cons
   PXR_REQUIRE(!dx_virtual || (g_planes && !dx && !gather_mode), "pxr_ln_bwd_h2s_f32: a planes-only dx needs planes (residual sites)");
   PXR_REQUIRE(zero_n >= 0 && zero_n <= 256 && (zero || zero_n == 0), "pxr_ln_bwd_f32: at most 256 floats to clear");
   PXR_REQUIRE(p3_mat_ok(g_planes, g_plane_stride, g_panel_rows, rows, D) && !(g_planes && gather_mode),
-              "pxr_ln_bwd_planes_f32: bad planes (residual sites only)");
+              "pxr_ln_bwd_f32: bad planes (residual sites only)");
   PXR_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), "pxr_ln_bwd_f32: dgamma and dbeta must both be given or both NULL");
   PXR_REQUIRE(D > 0 && D % 4 == 0 && rows > 0, "pxr_ln_bwd_f32: bad shape");
   LnBwdArgs a{};

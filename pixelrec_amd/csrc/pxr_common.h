@@ -53,6 +53,15 @@ static inline int pxr_check_launch(const char* what) {
     }                                \
   } while (0)
 
+// The loss head's id layout (bpr_loss.hip BprArgs / layernorm.hip BprHead): the target and negative ids of position t of sequence b
+// at items[b*id_bstride + pos_off + t] and items[b*id_bstride + neg_off + t], both windows inside the row.
+static inline bool pxr_bpr_layout_ok(int L, int64_t id_bstride, int64_t pos_off, int64_t neg_off) {
+  return id_bstride > 0 && pos_off >= 0 && neg_off >= 0 && pos_off + L <= id_bstride && neg_off + L <= id_bstride;
+}
+// bpr_loss.hip: loss = (1/B) sum_b sum_t lossrow[b,t] in the fixed order of the loss head's reduction (for producers of lossrow
+// other than the loss head's own forward: the LayerNorm launch with the fused head, layernorm.hip).  Internal, not in the ABI.
+int pxr_bpr_loss_reduce(const float* lossrow, int B, int L, float* loss, void* stream);
+
 #ifdef __HIPCC__
 // ---------------------------------------------------------------- streaming (non-temporal) 16-byte accesses
 // For data that is touched once per launch (table sweeps, big gathers, score matrices): keeps the stream out of

@@ -1143,7 +1143,7 @@ static int score_topk_thresh(ScoreTopkArgs a, int K, int kt, int64_t* topk_idx, 
     if (!attr) {                                                                                                              \
       if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) { \
         (void)hipGetLastError();                                                                                              \
-        pxr_set_error("pxr_score_topk_fast_f32: cannot reserve %d bytes of LDS", lds);                                        \
+        pxr_set_error("pxr_score_topk_f32: cannot reserve %d bytes of LDS", lds);                                        \
         return PXR_ERR_LAUNCH;                                                                                                \
       }                                                                                                                       \
       attr = true;                                                                                                            \
@@ -1161,11 +1161,11 @@ static int score_topk_thresh(ScoreTopkArgs a, int K, int kt, int64_t* topk_idx, 
       else PXR_FAST(1, 8);
     }
 #undef PXR_FAST
-    int rc = pxr_check_launch("pxr_score_topk_fast_f32(threshold pass)");
+    int rc = pxr_check_launch("pxr_score_topk_f32(threshold pass)");
     if (rc) return rc;
     hipLaunchKernelGGL(topk_rescore_kernel, dim3((a.B + 3) / 4), dim3(256), 0, st, cval, (const int*)cidx, (const int*)cnt, ST4_CAP, a.B, K,
                        (const float*)delta, *table_p, *users_p, a.D, topk_idx, topk_val, pxr_status_word(), a.hist_ptr, a.hist_items);
-    return pxr_check_launch("pxr_score_topk_fast_f32(re-scoring)");
+    return pxr_check_launch("pxr_score_topk_f32(re-scoring)");
   }
   if (table_p != nullptr) {
     // planes: 256-item tiles, one workgroup per CU, every CU the same number of tiles.  Default: round 3's lockstep stream with
@@ -1179,7 +1179,7 @@ static int score_topk_thresh(ScoreTopkArgs a, int K, int kt, int64_t* topk_idx, 
     if (!attr_set[env_p4 ? 1 : 0]) {
       if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
         (void)hipGetLastError();
-        pxr_set_error("pxr_score_topk_planes_f32: cannot reserve %d bytes of LDS", lds);
+        pxr_set_error("pxr_score_topk_f32: cannot reserve %d bytes of LDS", lds);
         return PXR_ERR_LAUNCH;
       }
       attr_set[env_p4 ? 1 : 0] = true;
@@ -1209,57 +1209,28 @@ static int score_topk_thresh(ScoreTopkArgs a, int K, int kt, int64_t* topk_idx, 
   return pxr_check_launch("pxr_score_topk_f32(candidate merge)");
 }
 
-extern "C" int pxr_score_topk_planes_f32(const float* users, int64_t ld_users, int B, const float* table, int N, int D,
-                                         const void* users_planes, int64_t users_plane_stride, int64_t users_panel_rows,
-                                         const void* table_planes, int64_t table_plane_stride, int64_t table_panel_rows,
-                                         const int32_t* hist_ptr, const int64_t* hist_items, int K, int64_t* topk_idx,
-                                         float* topk_val, void* ws, int64_t ws_bytes, void* stream);
-
 // Top-K item ids / scores per user of  users[B,D] x table[N,D]^T  with item 0 and each user's history masked.
 // hist_ptr int32 [B+1] / hist_items int64: CSR of the (history_u, history_i) pairs of seq_eval_collate (may be NULL).
+// The operands may ALSO be given as planes (include/pxr.h "pre-split operands"; both NULL: fp32 only): on catalogues that take
+// the threshold schedule the main pass -- every item tile -- runs on the planes (gemm_p3_stream); the sample pass keeps the fp32
+// operands.  The table's planes are made once per evaluation (pxr_split_planes_f32).  `products` = 6: that pass on all six bf16
+// products; 3 or 1: needs the planes and table_row_norm_max (device pointer to max_i ||table[i]||_2, pxr_row_norm_max_f32, once
+// per evaluation).  Results are the six-product schedule's, bit for bit (the survivors are re-scored with all six products).
 extern "C" int pxr_score_topk_f32(const float* users, int64_t ld_users, int B, const float* table, int N, int D,
-                                  const int32_t* hist_ptr, const int64_t* hist_items, int K, int64_t* topk_idx,
-                                  float* topk_val, void* ws, int64_t ws_bytes, void* stream) {
-  return pxr_score_topk_planes_f32(users, ld_users, B, table, N, D, nullptr, 0, 0, nullptr, 0, 0, hist_ptr, hist_items, K, topk_idx,
-                                   topk_val, ws, ws_bytes, stream);
-}
-extern "C" int pxr_score_topk_fast_f32(const float* users, int64_t ld_users, int B, const float* table, int N, int D,
-                                       const void* users_planes, int64_t users_plane_stride, int64_t users_panel_rows,
-                                       const void* table_planes, int64_t table_plane_stride, int64_t table_panel_rows,
-                                       const float* table_row_norm_max, int products, const int32_t* hist_ptr,
-                                       const int64_t* hist_items, int K, int64_t* topk_idx, float* topk_val, void* ws, int64_t ws_bytes,
-                                       void* stream);
-
-// The same with the operands ALSO given as planes (include/pxr.h "pre-split operands"; both NULL: the plain function): on
-// catalogues that take the threshold schedule the main pass -- every item tile -- runs on the planes (gemm_p3_stream); the
-// sample pass keeps the fp32 operands.  The table's planes are made once per evaluation (pxr_split_planes_f32).
-extern "C" int pxr_score_topk_planes_f32(const float* users, int64_t ld_users, int B, const float* table, int N, int D,
-                                         const void* users_planes, int64_t users_plane_stride, int64_t users_panel_rows,
-                                         const void* table_planes, int64_t table_plane_stride, int64_t table_panel_rows,
-                                         const int32_t* hist_ptr, const int64_t* hist_items, int K, int64_t* topk_idx,
-                                         float* topk_val, void* ws, int64_t ws_bytes, void* stream) {
-  return pxr_score_topk_fast_f32(users, ld_users, B, table, N, D, users_planes, users_plane_stride, users_panel_rows, table_planes,
-                                 table_plane_stride, table_panel_rows, nullptr, 6, hist_ptr, hist_items, K, topk_idx, topk_val, ws,
-                                 ws_bytes, stream);
-}
-// ... and with the threshold pass on `products` = 3 or 1 of the six bf16 products (6: the function above): needs the planes and
-// table_row_norm_max (device pointer to max_i ||table[i]||_2, pxr_row_norm_max_f32, once per evaluation).  Results are the
-// six-product schedule's, bit for bit (the survivors are re-scored with all six products).
-extern "C" int pxr_score_topk_fast_f32(const float* users, int64_t ld_users, int B, const float* table, int N, int D,
-                                       const void* users_planes, int64_t users_plane_stride, int64_t users_panel_rows,
-                                       const void* table_planes, int64_t table_plane_stride, int64_t table_panel_rows,
-                                       const float* table_row_norm_max, int products, const int32_t* hist_ptr,
-                                       const int64_t* hist_items, int K, int64_t* topk_idx, float* topk_val, void* ws, int64_t ws_bytes,
-                                       void* stream) {
-  PXR_REQUIRE(products == 6 || products == 3 || products == 1, "pxr_score_topk_fast_f32: products must be 6, 3 or 1");
+                                  const void* users_planes, int64_t users_plane_stride, int64_t users_panel_rows,
+                                  const void* table_planes, int64_t table_plane_stride, int64_t table_panel_rows,
+                                  const float* table_row_norm_max, int products, const int32_t* hist_ptr,
+                                  const int64_t* hist_items, int K, int64_t* topk_idx, float* topk_val, void* ws, int64_t ws_bytes,
+                                  void* stream) {
+  PXR_REQUIRE(products == 6 || products == 3 || products == 1, "pxr_score_topk_f32: products must be 6, 3 or 1");
   PXR_REQUIRE(products == 6 || (table_row_norm_max && users_planes && table_planes),
-              "pxr_score_topk_fast_f32: the reduced-product pass needs both planes and the table's largest row norm");
+              "pxr_score_topk_f32: the reduced-product pass needs both planes and the table's largest row norm");
   PXR_REQUIRE(users && table && topk_idx && topk_val && ws, "pxr_score_topk_f32: null pointer");
-  PXR_REQUIRE((users_planes == nullptr) == (table_planes == nullptr), "pxr_score_topk_planes_f32: give both planes or neither");
+  PXR_REQUIRE((users_planes == nullptr) == (table_planes == nullptr), "pxr_score_topk_f32: give both planes or neither");
   PXR_REQUIRE(!users_planes || (D % 32 == 0 && p3_mat_ok(users_planes, users_plane_stride, users_panel_rows, B, D) &&
                                 p3_mat_ok(table_planes, table_plane_stride, table_panel_rows, N, D) &&
                                 table_plane_stride * 6 < 0x7FFFFFF0ll),
-              "pxr_score_topk_planes_f32: bad planes (D %% 32 == 0, three planes < 2 GiB)");
+              "pxr_score_topk_f32: bad planes (D %% 32 == 0, three planes < 2 GiB)");
   PXR_REQUIRE(B > 0 && N > 0 && D > 0 && D % 4 == 0 && ld_users % 4 == 0, "pxr_score_topk_f32: bad shape");
   PXR_REQUIRE(!hist_ptr || hist_items, "pxr_score_topk_f32: hist_ptr without hist_items");
   const int kt = pick_kt(K);

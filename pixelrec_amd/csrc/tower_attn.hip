@@ -643,25 +643,14 @@ extern "C" int pxr_tower_attn_supported(int T, int d) { return (d == TA_D && T >
 
 // ctx[b*T + t, 64 h .. 64 h + 63] = softmax_t'(scale * q_t . k_t') v_t'   per (image b, head h); no mask, no dropout.
 // q/k/v: fp32, element (b, t, h, c) at p[(b*T + t)*ld + 64 h + c] (the fused projection output is passed with three base
-// pointers).  Outputs: ctx fp32 and/or ctx planes (planes.cuh) -- at least one; lse optional ([images*heads, T]).
-static int tower_attn_fwd_impl(const float* q, const float* k, const float* v, int64_t ld, int64_t images, int heads, int T, int d,
-                               float scale, float* ctx, int64_t ld_ctx, void* ctx_planes, int64_t c_ps, int64_t c_pr, int c_fmt,
-                               float* lse, void* stream);
+// pointers).  Outputs: ctx fp32 and/or ctx planes (planes.cuh) -- at least one; lse optional ([images*heads, T]).  planes_fmt 0:
+// bf16x3 planes; 1: two fp16 planes ("h2", unit scale; the operand of pxr_gemm_h2_f32, ctx_planes required).
 extern "C" int pxr_tower_attn_fwd_f32(const float* q, const float* k, const float* v, int64_t ld, int64_t images, int heads,
                                       int T, int d, float scale, float* ctx, int64_t ld_ctx, void* ctx_planes, int64_t c_ps,
-                                      int64_t c_pr, float* lse, void* stream) {
-  return tower_attn_fwd_impl(q, k, v, ld, images, heads, T, d, scale, ctx, ld_ctx, ctx_planes, c_ps, c_pr, PXR_PLANES_BF16X3, lse, stream);
-}
-// the same with the context planes in the two-plane fp16 format (planes.cuh "h2", unit scale; the operand of pxr_gemm_h2_f32)
-extern "C" int pxr_tower_attn_fwd_h2_f32(const float* q, const float* k, const float* v, int64_t ld, int64_t images, int heads,
-                                         int T, int d, float scale, float* ctx, int64_t ld_ctx, void* ctx_planes, int64_t c_ps,
-                                         int64_t c_pr, float* lse, void* stream) {
-  PXR_REQUIRE(ctx_planes, "pxr_tower_attn_fwd_h2_f32: no planes");
-  return tower_attn_fwd_impl(q, k, v, ld, images, heads, T, d, scale, ctx, ld_ctx, ctx_planes, c_ps, c_pr, PXR_PLANES_H2, lse, stream);
-}
-static int tower_attn_fwd_impl(const float* q, const float* k, const float* v, int64_t ld, int64_t images, int heads, int T, int d,
-                               float scale, float* ctx, int64_t ld_ctx, void* ctx_planes, int64_t c_ps, int64_t c_pr, int c_fmt,
-                               float* lse, void* stream) {
+                                      int64_t c_pr, int planes_fmt, float* lse, void* stream) {
+  PXR_REQUIRE(planes_fmt == 0 || planes_fmt == 1, "pxr_tower_attn_fwd_f32: planes_fmt must be 0 (bf16x3) or 1 (h2)");
+  PXR_REQUIRE(planes_fmt == 0 || ctx_planes, "pxr_tower_attn_fwd_f32: h2 output needs planes");
+  const int c_fmt = planes_fmt == 1 ? PXR_PLANES_H2 : PXR_PLANES_BF16X3;
   PXR_REQUIRE(q && k && v && images >= 0 && heads > 0, "pxr_tower_attn_fwd_f32: bad args");
   PXR_REQUIRE(pxr_tower_attn_supported(T, d), "pxr_tower_attn_fwd_f32: head size %d / %d tokens not supported (64, <= %d)", d,
               T, 32 * TA_MAXW);

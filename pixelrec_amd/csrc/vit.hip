@@ -294,10 +294,13 @@ extern "C" int pxr_add_f32(const float* a, const float* b, float* out, int64_t n
 
 // S [B*H, L, ld] (= Q K^T, unscaled) -> in place the softmax probabilities of the SASRec attention (additive -1e9
 // causal + key mask, reference layers.py:595-604, sasrec.py:119-126); PD (may be NULL when p_drop == 0) receives the
-// dropped probabilities (layers.py:608).  For sequences beyond the fused kernels of attention.hip (L > 128).
-static int attn_rows_fwd_impl(float* S, float* PD, const int64_t* keymask, int64_t km_bstride, int B, int H, int L, int ld,
-                              float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev, int d, void* stream,
-                              bool causal) {
+// dropped probabilities (layers.py:608).  For sequences beyond the fused kernels of attention.hip (L > 128).  causal = 0: the
+// key-padding mask only (BERT4Rec, reference IDNet/bert4rec.py:150-155); pxr_attn_rows_bwd_f32 serves both masks: it reads the
+// saved probabilities.
+extern "C" int pxr_attn_rows_fwd_f32(float* S, float* PD, const int64_t* keymask, int64_t km_bstride, int B, int H, int L,
+                                     int ld, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
+                                     int d, int causal, void* stream) {
+  PXR_REQUIRE(causal == 0 || causal == 1, "pxr_attn_rows_fwd_f32: causal must be 0 or 1");
   PXR_REQUIRE(S && keymask && B >= 0 && H > 0 && L > 0 && ld >= L && d > 0, "pxr_attn_rows_fwd_f32: bad args");
   PXR_REQUIRE(p_drop >= 0.f && p_drop < 1.f && (p_drop == 0.f || PD), "pxr_attn_rows_fwd_f32: dropout needs PD");
   if (B == 0) return PXR_OK;
@@ -309,18 +312,6 @@ static int attn_rows_fwd_impl(float* S, float* PD, const int64_t* keymask, int64
   hipLaunchKernelGGL(causal ? attn_rows_fwd_kernel : attn_rows_fwd_bidir_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
                      (hipStream_t)stream, a);
   return pxr_check_launch("pxr_attn_rows_fwd_f32");
-}
-extern "C" int pxr_attn_rows_fwd_f32(float* S, float* PD, const int64_t* keymask, int64_t km_bstride, int B, int H, int L,
-                                     int ld, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
-                                     int d, void* stream) {
-  return attn_rows_fwd_impl(S, PD, keymask, km_bstride, B, H, L, ld, p_drop, seed, stream_id, step_dev, d, stream, true);
-}
-// The same rows with the key-padding mask only (no causal term): BERT4Rec's attention beyond 128 positions
-// (reference IDNet/bert4rec.py:150-155).  pxr_attn_rows_bwd_f32 serves both: it reads the saved probabilities.
-extern "C" int pxr_attn_rows_fwd_bidir_f32(float* S, float* PD, const int64_t* keymask, int64_t km_bstride, int B, int H, int L,
-                                           int ld, float p_drop, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
-                                           int d, void* stream) {
-  return attn_rows_fwd_impl(S, PD, keymask, km_bstride, B, H, L, ld, p_drop, seed, stream_id, step_dev, d, stream, false);
 }
 
 // dPD [B*H, L, ld] (gradient w.r.t. the dropped probabilities) -> in place the gradient w.r.t. the unscaled scores S

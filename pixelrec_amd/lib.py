@@ -46,18 +46,18 @@ _SIGNATURES = {
     "pxr_packed_rows_offset": (_I64, [_I64]),
     "pxr_packed_rows_bytes": (_I64, [_I64, _I]),
     "pxr_merge_packed_rows_f32": (_I, [_P, _I, _I64, _I, _I64, _F, _P, _P, _P, _P, _I64, _P]),
-    "pxr_sasrec_embed_grad_f32": (_I, [_P, _I, _I, _P, _P, _P, _I, _I64, _F, _P, _P, _P, _P, _I64, _P]),
-    "pxr_sasrec_occ_sort": (_I, [_P, _I, _I, _I64, _P, _P, _P, _I64, _P]),
+    "pxr_seq_occ_sort": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _I64, _P]),
     "pxr_sasrec_occ_segsum": (_I, [_P, _I64, _I, _I, _P, _P, _P, _I, _I64, _F, _P, _P, _P]),
     "pxr_sasrec_occ_split_ws_bytes": (_I64, [_I, _I, _I]),
     "pxr_sasrec_occ_segsum_split": (_I, [_P, _I64, _I, _I, _P, _P, _P, _I, _I64, _F, _P, _P, _P, _I64, _P]),
-    "pxr_input_ln_fwd_f32": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P]),
-    "pxr_ln_residual_fwd_f32": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P]),
+    "pxr_input_ln_fwd_f32": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _I64, _I,
+                                  _P]),
+    "pxr_ln_residual_fwd_f32": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _I64, _I, _P]),
     "pxr_ln_bwd_ws_bytes": (_I64, [_I, _I]),
     "pxr_ln_bwd_partial_rows": (_I, [_I]),
     "pxr_colsum_partial_rows": (_I, [_I]),
     "pxr_reduce_partials_multi_f32": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "pxr_ln_bwd_f32": (_I, [_I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _P]),
+    "pxr_ln_bwd_f32": (_I, [_I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _P, _I64, _I64, _P]),
     "pxr_gemm_ws_bytes": (_I64, [_I, _I, _I, _I, _I]),
     "pxr_gemm_f32": (_I, [_I, _I, _I, _I, _I, _P, _I64, _P, _I64, _P, _I64, _I, _P, _P, _I64, _P, _I64, _I, _I, _P]),
     "pxr_linear_fwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
@@ -66,34 +66,20 @@ _SIGNATURES = {
     "pxr_grouped_linear_bwd_weight_f32": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pxr_colsum_ws_bytes": (_I64, [_I, _I]),
     "pxr_colsum_f32": (_I, [_P, _I64, _I, _I, _P, _P, _I64, _P]),
-    "pxr_attn_fwd_f32": (_I, [_P, _P, _P, _I64, _P, _I64, _I, _I, _I, _I, _P, _I64, _P, _F, _U64, _U32, _P, _P]),
-    "pxr_attn_bwd_f32": (_I, [_P, _I64, _P, _P, _P, _I64, _P, _I, _I, _I, _I, _P, _P, _P, _I64, _F, _U64, _U32, _P, _P]),
-    "pxr_bpr_loss_fwd_f32": (_I, [_P, _P, _I64, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
-    "pxr_bpr_loss_bwd_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
-    "pxr_bpr_loss_reduce_f32": (_I, [_P, _I, _I, _P, _P]),
-    # BERT4Rec (aligned, masked id layout; bidirectional attention)
-    "pxr_bpr_loss_fwd_lay_f32": (_I, [_P, _P, _I64, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I64, _I64, _I64, _P]),
-    "pxr_bpr_loss_bwd_lay_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I, _I, _I, _F, _P, _P, _P, _I64, _I64, _I64, _P]),
-    "pxr_ln_residual_bpr_fwd_lay_f32": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _P, _P, _P, _P,
-                                             _P, _P, _I64, _I64, _I64, _P]),
-    "pxr_bpr_ln_bwd_lay_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _F, _U64, _U32, _P,
-                                    _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _P]),
-    "pxr_ln_bwd_h2s_lay_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _F, _U64, _U32,
-                                    _P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _I, _I64, _I64, _I64, _P]),
-    "pxr_seq_occ_sort_lay": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _I64, _P]),
-    "pxr_attn_fwd_bidir_f32": (_I, [_P, _P, _P, _I64, _P, _I64, _I, _I, _I, _I, _P, _I64, _P, _F, _U64, _U32, _P, _P, _I64, _I64, _I,
-                                    _P]),
-    "pxr_attn_rows_fwd_bidir_f32": (_I, [_P, _P, _P, _I64, _I, _I, _I, _I, _F, _U64, _U32, _P, _I, _P]),
+    "pxr_attn_fwd_f32": (_I, [_P, _P, _P, _I64, _P, _I64, _I, _I, _I, _I, _P, _I64, _P, _F, _U64, _U32, _P, _P, _I64, _I64, _I, _I,
+                              _P]),
+    "pxr_attn_bwd_f32": (_I, [_P, _I64, _P, _P, _P, _I64, _P, _I, _I, _I, _I, _P, _P, _P, _I64, _F, _U64, _U32, _P, _P, _I64, _I64, _I,
+                              _I, _I, _I, _P]),
+    "pxr_bpr_loss_fwd_f32": (_I, [_P, _P, _I64, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I64, _I64, _I64, _P]),
+    "pxr_bpr_loss_bwd_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I, _I, _I, _F, _P, _P, _P, _I64, _I64, _I64, _P]),
     "pxr_ln_residual_bpr_fwd_f32": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _P, _P, _P, _P, _P,
-                                         _P, _P]),
+                                         _P, _I64, _I64, _I64, _P]),
     "pxr_bpr_ln_bwd_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _F, _U64, _U32, _P, _P,
-                                _I64, _P, _I64, _I64, _P, _P]),
+                                _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _P]),
     "pxr_mosasrec_emb_grad_f32": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "pxr_image_u8_to_f32": (_I, [_P, _I64, _I, _I, _P, _I, _P, _P]),
     "pxr_score_topk_ws_bytes": (_I64, [_I, _I, _I]),
-    "pxr_score_topk_f32": (_I, [_P, _I64, _I, _P, _I, _I, _P, _P, _I, _P, _P, _P, _I64, _P]),
-    "pxr_score_topk_planes_f32": (_I, [_P, _I64, _I, _P, _I, _I, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _I, _P, _P, _P, _I64, _P]),
-    "pxr_score_topk_fast_f32": (_I, [_P, _I64, _I, _P, _I, _I, _P, _I64, _I64, _P, _I64, _I64, _P, _I, _P, _P, _I, _P, _P, _P, _I64, _P]),
+    "pxr_score_topk_f32": (_I, [_P, _I64, _I, _P, _I, _I, _P, _I64, _I64, _P, _I64, _I64, _P, _I, _P, _P, _I, _P, _P, _P, _I64, _P]),
     "pxr_row_norm_max_f32": (_I, [_P, _I64, _I64, _I64, _P, _P]),
     "pxr_adamw_flat_f32": (_I, [_P, _P, _P, _P, _I64, _D, _D, _D, _D, _D, _I64, _P]),
     "pxr_slot_fill_i32": (_I, [_P, _I64, ctypes.c_int32, _P]),
@@ -106,8 +92,7 @@ _SIGNATURES = {
     "pxr_adamw_rows_ids2d_f32": (_I, [_P, _P, _P, _P, _I64, _I, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _D, _D, _D, _P, _P]),
     "pxr_adamw_flat_tab_ex_f32": (_I, [_P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _P, _P, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P,
                                        _I, _P, _P]),
-    "pxr_adamw_flat_tab_f32": (_I, [_P, _P, _P, _P, _I64, _P, _I64, _P, _D, _D, _D, _P]),
-    "pxr_adamw_flat_tab_planes_f32": (_I, [_P, _P, _P, _P, _I64, _P, _I64, _P, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "pxr_adamw_flat_tab_f32": (_I, [_P, _P, _P, _P, _I64, _P, _I64, _P, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P]),
     "pxr_counter_add_i64": (_I, [_P, _I64, _P]),
     "pxr_set_status_word": (_I, [_P]),
     "pxr_gemm_batched_f32": (_I, [_I, _I, _I, _I, _I, _P, _I64, _P, _I64, _P, _I64, _I, _I, _I64, _I64, _I64, _I64, _I64,
@@ -115,7 +100,7 @@ _SIGNATURES = {
     "pxr_set_gemm_mode": (_I, [_I]),
     "pxr_get_gemm_mode": (_I, []),
     "pxr_tower_attn_supported": (_I, [_I, _I]),
-    "pxr_tower_attn_fwd_f32": (_I, [_P, _P, _P, _I64, _I64, _I, _I, _I, _F, _P, _I64, _P, _I64, _I64, _P, _P]),
+    "pxr_tower_attn_fwd_f32": (_I, [_P, _P, _P, _I64, _I64, _I, _I, _I, _F, _P, _I64, _P, _I64, _I64, _I, _P, _P]),
     "pxr_tower_attn_bwd_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I, _I, _I, _F, _P, _P, _P, _I64, _P, _P]),
     "pxr_causal_im2col_f32": (_I, [_P, _P, _I64, _I, _I, _I, _I, _P]),
     "pxr_causal_col2im_f32": (_I, [_P, _P, _I64, _I, _I, _I, _I, _P]),
@@ -128,7 +113,7 @@ _SIGNATURES = {
     "pxr_token_mean_relu_bwd_f32": (_I, [_P, _P, _P, _I64, _I, _I, _P]),
     "pxr_add_f32": (_I, [_P, _P, _P, _I64, _P]),
     "pxr_dropout_f32": (_I, [_P, _P, _I64, _F, _U64, _U32, _P, _P]),
-    "pxr_attn_rows_fwd_f32": (_I, [_P, _P, _P, _I64, _I, _I, _I, _I, _F, _U64, _U32, _P, _I, _P]),
+    "pxr_attn_rows_fwd_f32": (_I, [_P, _P, _P, _I64, _I, _I, _I, _I, _F, _U64, _U32, _P, _I, _I, _P]),
     "pxr_attn_rows_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _F, _U64, _U32, _P, _I, _P]),
     "pxr_split_planes_f32": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _P]),
     "pxr_gemm_planes_f32": (_I, [_I, _I, _I, _I, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I, _P, _P, _I64, _P, _I64, _I64,
@@ -144,30 +129,18 @@ _SIGNATURES = {
     "pxr_ln_bwd_res_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I64, _P, _P]),
     "pxr_h2_split_parts_f32": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _P, _I, _P, _P, _P, _F, _P, _P]),
     "pxr_ln_bwd_h2s_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P,
-                                _I64, _P, _I64, _I64, _P, _P, _P, _I, _P]),
+                                _I64, _P, _I64, _I64, _P, _P, _P, _I, _I64, _I64, _I64, _P]),
     "pxr_attn_bwd_h2s_f32": (_I, [_P, _I64, _P, _P, _P, _I64, _P, _I, _I, _I, _I, _F, _U64, _U32, _P, _P, _I64, _I64, _I, _I, _I, _I, _P,
                                   _P, _P]),
     "pxr_h2_sites_update": (_I, [_I, _P, _P, _P, _P, _F, _I, _F, _P, _P, _P, _P, _P]),
     "pxr_attn_bwd_stat_f32": (_I, [_P, _I64, _P, _P, _P, _I64, _P, _I, _I, _I, _I, _P, _P, _P, _I64, _F, _U64, _U32, _P, _P, _P]),
-    "pxr_ln_residual_fwd_h2_f32": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _I64, _P]),
-    "pxr_input_ln_fwd_h2_f32": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _I64, _P]),
-    "pxr_attn_fwd_h2_f32": (_I, [_P, _P, _P, _I64, _P, _I64, _I, _I, _I, _I, _P, _I64, _P, _F, _U64, _U32, _P, _P, _I64, _I64, _P]),
-    "pxr_tower_attn_fwd_h2_f32": (_I, [_P, _P, _P, _I64, _I64, _I, _I, _I, _F, _P, _I64, _P, _I64, _I64, _P, _P]),
-    "pxr_input_ln_fwd_planes_f32": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64,
-                                         _I64, _P]),
-    "pxr_ln_residual_fwd_planes_f32": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _I64, _P]),
-    "pxr_ln_bwd_planes_f32": (_I, [_I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _P, _I64, _I64, _P]),
     "pxr_attn_planes_supported": (_I, [_I, _I]),
-    "pxr_attn_fwd_planes_f32": (_I, [_P, _P, _P, _I64, _P, _I64, _I, _I, _I, _I, _P, _I64, _P, _F, _U64, _U32, _P, _P, _I64, _I64,
-                                     _P]),
-    "pxr_attn_bwd_planes_f32": (_I, [_P, _I64, _P, _P, _P, _I64, _P, _I, _I, _I, _I, _P, _P, _P, _I64, _F, _U64, _U32, _P, _P, _I64,
-                                     _I64, _I, _I, _I, _I, _P]),
     "pxr_grouped_dw_planes_f32": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "pxr_merge_split_rows_f32": (_I, [_P, _P, _I, _I64, _I64, _I, _I64, _F, _P, _P, _P, _P, _I64, _P]),
 }
 
 
-ABI_VERSION = 300      # include/pxr.h PXR_ABI_VERSION (tests/test_abi.py pins header == binding == library)
+ABI_VERSION = 301      # include/pxr.h PXR_ABI_VERSION (tests/test_abi.py pins header == binding == library)
 
 
 def load():

@@ -7,11 +7,11 @@ table gradient and the lazy / series-replay AdamW, hipGraph capture).  What diff
   * positions: the encoder runs on P = MAX_ITEM_LIST_LENGTH + 1 positions (bert4rec.py:34; trainset.py:427), and the table
     has item_num + 1 rows -- row item_num is the mask token (bert4rec.py:29-33), an ordinary row for the optimizer;
   * attention: key padding only, no causal term (get_attention_mask, bert4rec.py:150-155): the CAUSAL = false instantiations
-    of every attention family (pxr_attn_fwd_bidir_f32 / pxr_attn_rows_fwd_bidir_f32); the mask is built from the masked
+    of every attention family (pxr_attn_fwd_f32 / pxr_attn_rows_fwd_f32 with causal = 0); the mask is built from the masked
     sequence items[:, 0], whose mask tokens are real keys;
   * loss head: the batch is items [B, 3, P] = (masked sequence | original sequence | negatives) with masked_index [B, P]
     (trainset.py:470-478); targets are aligned with the output position (no shift): the head kernels and the occurrence
-    sort of the table gradient take that id layout as arguments (the *_lay entries of include/pxr.h).  The loss
+    sort of the table gradient take that id layout as arguments (id_bstride and offsets in include/pxr.h).  The loss
     sum_masked -log(1e-8 + sigmoid(pos - neg)) / B (bert4rec.py:98-111) is the SASRec head's arithmetic on this layout;
   * predict: a mask-token column is appended to item_seq [B, L] and the last of the P positions is scored
     (reconstruct_test_data, bert4rec.py:61-66,116-135); compute_item_all() is weight[:item_num] (bert4rec.py:138-140).
@@ -61,9 +61,6 @@ class BERT4Rec(SASRec):
 
     def _table_rows(self):
         return self.item_num + 1
-
-    def _occ_sort(self, items, sp, ws):
-        ops.seq_occ_sort(items, items.shape[2], self._occ_layout, self._table_rows(), sp, ws)
 
     def _train_inputs(self, items, masked_index):
         # input ids = the masked sequence items[:, 0]; its nonzero entries are the attention's real keys (bert4rec.py:75,86)

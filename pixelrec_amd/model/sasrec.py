@@ -88,9 +88,11 @@ class SASRec(SeqRecCore):
         stream do not change it) -- see DESIGN.md "dead ends"."""
         self._next_items = items_next
 
-    # ---- the id layout of a training batch, as the table-gradient sort sees it (BERT4Rec overrides these three)
+    # ---- the id layout of a training batch, as the table-gradient sort sees it (BERT4Rec overrides these four)
     # the split catch-up claims the input rows from the raw window items[:, 0, :L] of SASRec's [B, 2, L+1] layout
     _split_catch_up_ok = True
+    # (id_bstride, in_off, pos_off, neg_off) of the input / target / negative ids in `items`; None = SASRec's shifted windows
+    _occ_layout = None
 
     def _occ_positions(self, items):
         """Positions per sequence of a batch `items` [B, 2, L+1]: L."""
@@ -102,7 +104,7 @@ class SASRec(SeqRecCore):
 
     def _occ_sort(self, items, sp, ws):
         """Phase 1 of the table gradient: the batch's unique ids into `sp`, the sorted occurrences into `ws`."""
-        ops.sasrec_occ_sort(items, self._table_rows(), sp, ws)
+        ops.occ_sort(items, self._occ_positions(items), self._occ_layout, self._table_rows(), sp, ws)
 
     def _start_prefetch(self, items_next):
         """Sort the next batch's ids and replay their rows' missed steps on a side stream (must be issued AFTER this

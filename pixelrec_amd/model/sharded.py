@@ -148,7 +148,7 @@ class ShardedSASRec(SASRec):
         need = ops.occ_ws_bytes(B, L)
         if self._occ_ws is None or self._occ_ws.numel() < need or self._occ_ws.device != items.device:
             self._occ_ws = torch.empty(need, dtype=torch.uint8, device=items.device)
-        ops.sasrec_occ_sort(items, self.item_num, sp, self._occ_ws)                       # 1. U_r
+        ops.occ_sort(items, L, None, self.item_num, sp, self._occ_ws)                     # 1. U_r
         if self.row_exchange == "alltoall":
             block = self._fetch_rows_alltoall(sp, cap, D)
         else:

@@ -393,12 +393,11 @@ def tower_attn_fwd(qkv: torch.Tensor, n: int, T: int, heads: int, d: int, q_off:
     ls = torch.empty(n * heads, T, dtype=torch.float32, device=qkv.device) if lse else None
     cp = _l.c_void_p
     base = qkv.data_ptr()
-    fn = _l.load().pxr_tower_attn_fwd_h2_f32 if h2 else _l.load().pxr_tower_attn_fwd_f32
     if h2:
         device_status(qkv.device)
     with _gemm_timer(4.0 * T * T * d * n * heads, "tower_attn_fwd_kernel (fused QK^T / softmax / PV of a tower block)"):
-        _l.check(fn(cp(base + 4 * q_off), cp(base + 4 * k_off), cp(base + 4 * v_off), ld, n, heads, T,
-                                                  d, float(scale), _l.ptr(out) if ctx else None, H, *_pl(op),
+        _l.check(_l.load().pxr_tower_attn_fwd_f32(cp(base + 4 * q_off), cp(base + 4 * k_off), cp(base + 4 * v_off), ld, n, heads, T,
+                                                  d, float(scale), _l.ptr(out) if ctx else None, H, *_pl(op), int(h2),
                                                   _l.ptr(ls) if lse else None, _l.stream_ptr()), "pxr_tower_attn_fwd_f32")
     return out, op, ls
 
@@ -605,7 +604,7 @@ def _dw_token_parts(M: int, N: int, K: int) -> int:
     return max(1, min(MULTI_MAX, -(-192 // t128), M // 2048))
 
 
-MULTI_MAX = 16      # matrices per pxr_split_planes_multi_f32 launch / plane segments per pxr_adamw_flat_tab_planes_f32 launch
+MULTI_MAX = 16      # matrices per pxr_split_planes_multi_f32 launch / plane segments per pxr_adamw_flat_tab_f32 launch
 
 
 def h2_exponent(max_abs: float) -> int:
@@ -744,7 +743,7 @@ def ln_bwd_h2s(dy, xhat, rstd, gamma, dgamma, dbeta, sites: H2Sites, site: int, 
     """A residual LayerNorm site's backward whose GEMM-facing gradient leaves ONLY as h2 planes under the site's stale scale
     (pxr_ln_bwd_h2s_f32), + this step's partial maxima in `stat`.  head = (pos, neg, table, items, masked_index, grad_scale,
     grad_scale_dev): the loss head's backward fused in (dy unused).  layout = (id_bstride, pos_off, neg_off) of the head's ids (None:
-    SASRec's shifted windows; pxr_ln_bwd_h2s_lay_f32).  -> (dz, Planes, coef | None)."""
+    SASRec's shifted windows).  -> (dz, Planes, coef | None)."""
     Lb = _l.load()
     D = xhat.shape[-1]
     rows = xhat.numel() // D
@@ -767,14 +766,12 @@ def ln_bwd_h2s(dy, xhat, rstd, gamma, dgamma, dbeta, sites: H2Sites, site: int, 
         hargs = (_l.ptr(pos), _l.ptr(neg), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), B, L, float(grad_scale),
                  _l.ptr(grad_scale_dev), _l.ptr(coef))
     else:
-        hargs = (None, None, None, 0, None, None, 0, 0, 1.0, None, None)
-    args = (*hargs, _l.ptr(dy), _l.ptr(xhat), _l.ptr(rstd), _l.ptr(gamma), rows, D, _l.ptr(dz), _l.ptr(dgamma), _l.ptr(dbeta), p_drop, seed,
-            stream_id, _l.ptr(step_dev), _l.ptr(ws), ws_bytes, *_pl(gp), _l.ptr(gp.exp_dev), _l.ptr(stat), _l.ptr(zero),
-            zero.numel() if zero is not None else 0)
-    if layout is None:
-        _l.check(Lb.pxr_ln_bwd_h2s_f32(*args, _l.stream_ptr()), "pxr_ln_bwd_h2s_f32")
-    else:
-        _l.check(Lb.pxr_ln_bwd_h2s_lay_f32(*args, *layout, _l.stream_ptr()), "pxr_ln_bwd_h2s_lay_f32")
+        B = L = 0
+        hargs = (None, None, None, 0, None, None, B, L, 1.0, None, None)
+    _l.check(Lb.pxr_ln_bwd_h2s_f32(*hargs, _l.ptr(dy), _l.ptr(xhat), _l.ptr(rstd), _l.ptr(gamma), rows, D, _l.ptr(dz), _l.ptr(dgamma),
+                                   _l.ptr(dbeta), p_drop, seed, stream_id, _l.ptr(step_dev), _l.ptr(ws), ws_bytes, *_pl(gp),
+                                   _l.ptr(gp.exp_dev), _l.ptr(stat), _l.ptr(zero), zero.numel() if zero is not None else 0,
+                                   *_head_layout(L, layout), _l.stream_ptr()), "pxr_ln_bwd_h2s_f32")
     return dz, gp, coef
 
 
@@ -987,12 +984,11 @@ def input_ln_fwd(table, idx, idx_bstride, B, L, pos, gamma, beta, eps, p_drop=0.
     # reference never exists (SURVEY.md §8d "fused" rule)
     h2 = planes == "h2"
     yp = Planes.alloc(B * L, D, table.device, fmt=int(h2)) if planes else None
-    fn = Lb.pxr_input_ln_fwd_h2_f32 if h2 else Lb.pxr_input_ln_fwd_planes_f32
     # (+ the planes of y -- three bf16 ones, 6 B per element, or two fp16 ones -- when the kernel also writes them for the QKV GEMM)
     with _gemm_timer(B * L * D * (4.0 * (3 if save else 2) + ((4.0 if h2 else 6.0) if planes else 0.0)), "ln_fwd_kernel<GATHER> (gather + pos + LN + dropout)"):
-        _l.check(fn(_l.ptr(table), N, _l.ptr(idx), idx_bstride, _l.ptr(pos), _l.ptr(gamma),
-                                                _l.ptr(beta), eps, B, L, D, _l.ptr(y), _l.ptr(xhat), _l.ptr(rstd), p_drop,
-                                                seed, stream_id, _l.ptr(step_dev), *_pl(yp), _l.stream_ptr()),
+        _l.check(Lb.pxr_input_ln_fwd_f32(_l.ptr(table), N, _l.ptr(idx), idx_bstride, _l.ptr(pos), _l.ptr(gamma),
+                                         _l.ptr(beta), eps, B, L, D, _l.ptr(y), _l.ptr(xhat), _l.ptr(rstd), p_drop,
+                                         seed, stream_id, _l.ptr(step_dev), *_pl(yp), int(h2), _l.stream_ptr()),
                  "pxr_input_ln_fwd_f32")
     return (y, xhat, rstd, yp) if planes else (y, xhat, rstd)
 
@@ -1009,17 +1005,13 @@ def ln_residual_fwd(x, res, gamma, beta, eps, p_drop=0.0, seed=0, stream_id=0, s
     y = torch.empty_like(x) if want_y else None
     xhat = torch.empty_like(x) if save else None
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if save else None
-    if planes == "h2":                # y as two fp16 planes (the image tower, the sequence block of large batches)
-        yp = Planes.alloc(rows, D, x.device, fmt=1)
+    h2 = planes == "h2"               # y as two fp16 planes (the image tower, the sequence block of large batches)
+    yp = Planes.alloc(rows, D, x.device, fmt=int(h2)) if planes else None
+    if h2:
         device_status(x.device)
-        _l.check(Lb.pxr_ln_residual_fwd_h2_f32(_l.ptr(x), _l.ptr(res), _l.ptr(gamma), _l.ptr(beta), eps, rows, D, _l.ptr(y),
-                                               _l.ptr(xhat), _l.ptr(rstd), p_drop, seed, stream_id, _l.ptr(step_dev), *_pl(yp),
-                                               _l.stream_ptr()), "pxr_ln_residual_fwd_h2_f32")
-        return (y, xhat, rstd, yp)
-    yp = Planes.alloc(rows, D, x.device) if planes else None
-    _l.check(Lb.pxr_ln_residual_fwd_planes_f32(_l.ptr(x), _l.ptr(res), _l.ptr(gamma), _l.ptr(beta), eps, rows, D, _l.ptr(y),
-                                               _l.ptr(xhat), _l.ptr(rstd), p_drop, seed, stream_id, _l.ptr(step_dev),
-                                               *_pl(yp), _l.stream_ptr()), "pxr_ln_residual_fwd_f32")
+    _l.check(Lb.pxr_ln_residual_fwd_f32(_l.ptr(x), _l.ptr(res), _l.ptr(gamma), _l.ptr(beta), eps, rows, D, _l.ptr(y), _l.ptr(xhat),
+                                        _l.ptr(rstd), p_drop, seed, stream_id, _l.ptr(step_dev), *_pl(yp), int(h2), _l.stream_ptr()),
+             "pxr_ln_residual_fwd_f32")
     return (y, xhat, rstd, yp) if planes else (y, xhat, rstd)
 
 
@@ -1028,7 +1020,7 @@ def ln_residual_bpr_fwd(x, res, gamma, beta, eps, table, items, masked_index, p_
     """The block's last LayerNorm with the loss head's forward fused in (pxr_ln_residual_bpr_fwd_f32):
     -> (y [B,L,D], xhat, rstd, loss [1], pos [B,L], neg [B,L]) -- what ln_residual_fwd + bpr_loss_fwd return, bit for bit.
     layout = (id_bstride, pos_off, neg_off) of the target / negative ids in `items` (None: SASRec's shifted [B, 2, L+1] windows;
-    BERT4Rec's aligned [B, 3, L]: (3L, L, 2L), pxr_ln_residual_bpr_fwd_lay_f32)."""
+    BERT4Rec's aligned [B, 3, L]: (3L, L, 2L))."""
     Lb = _l.load()
     _req(x, torch.float32, "x"); _req(table, torch.float32, "table")
     _req(items, torch.int64, "items"); _req(masked_index, torch.int64, "masked_index")
@@ -1042,13 +1034,11 @@ def ln_residual_bpr_fwd(x, res, gamma, beta, eps, table, items, masked_index, p_
     lossrow = torch.empty(B * L, dtype=torch.float32, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     with _gemm_timer(0.0, "ln_fwd_kernel<RESIDUAL + loss head>"):
-        args = (_l.ptr(x), _l.ptr(res), _l.ptr(gamma), _l.ptr(beta), eps, B, L, D, _l.ptr(y), _l.ptr(xhat), _l.ptr(rstd), p_drop, seed,
-                stream_id, _l.ptr(step_dev), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), _l.ptr(pos), _l.ptr(neg),
-                _l.ptr(lossrow), _l.ptr(loss))
-        if layout is None:
-            _l.check(Lb.pxr_ln_residual_bpr_fwd_f32(*args, _l.stream_ptr()), "pxr_ln_residual_bpr_fwd_f32")
-        else:
-            _l.check(Lb.pxr_ln_residual_bpr_fwd_lay_f32(*args, *layout, _l.stream_ptr()), "pxr_ln_residual_bpr_fwd_lay_f32")
+        _l.check(Lb.pxr_ln_residual_bpr_fwd_f32(_l.ptr(x), _l.ptr(res), _l.ptr(gamma), _l.ptr(beta), eps, B, L, D, _l.ptr(y),
+                                                _l.ptr(xhat), _l.ptr(rstd), p_drop, seed, stream_id, _l.ptr(step_dev), _l.ptr(table),
+                                                table.shape[0], _l.ptr(items), _l.ptr(masked_index), _l.ptr(pos), _l.ptr(neg),
+                                                _l.ptr(lossrow), _l.ptr(loss), *_head_layout(L, layout), _l.stream_ptr()),
+                 "pxr_ln_residual_bpr_fwd_f32")
     return y, xhat, rstd, loss, pos, neg
 
 
@@ -1057,7 +1047,7 @@ def bpr_ln_bwd(pos, neg, table, items, masked_index, grad_scale, grad_scale_dev,
                layout=None):
     """bpr_loss_bwd + ln_bwd(0, ...) of the block's last LayerNorm in one launch (pxr_bpr_ln_bwd_f32): the gradient w.r.t. the
     block's output never reaches HBM.  -> (dz, dx | None, planes of the gradient the next GEMMs read | None, coef [B,L]).
-    layout: as ln_residual_bpr_fwd (pxr_bpr_ln_bwd_lay_f32)."""
+    layout: as ln_residual_bpr_fwd."""
     Lb = _l.load()
     B, L = pos.shape
     D = xhat.shape[-1]
@@ -1074,13 +1064,11 @@ def bpr_ln_bwd(pos, neg, table, items, masked_index, grad_scale, grad_scale_dev,
         ws = _ws.get(ws_bytes, xhat.device)
     assert not (planes and stat is not None)
     gp = Planes.alloc(rows, D, xhat.device) if planes else None
-    args = (_l.ptr(pos), _l.ptr(neg), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), B, L, float(grad_scale),
-            _l.ptr(grad_scale_dev), _l.ptr(coef), _l.ptr(xhat), _l.ptr(rstd), _l.ptr(gamma), D, _l.ptr(dz), _l.ptr(dx), _l.ptr(dgamma),
-            _l.ptr(dbeta), p_drop, seed, stream_id, _l.ptr(step_dev), _l.ptr(ws), ws_bytes, *_pl(gp), _l.ptr(stat))
-    if layout is None:
-        _l.check(Lb.pxr_bpr_ln_bwd_f32(*args, _l.stream_ptr()), "pxr_bpr_ln_bwd_f32")
-    else:
-        _l.check(Lb.pxr_bpr_ln_bwd_lay_f32(*args, *layout, _l.stream_ptr()), "pxr_bpr_ln_bwd_lay_f32")
+    _l.check(Lb.pxr_bpr_ln_bwd_f32(_l.ptr(pos), _l.ptr(neg), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), B, L,
+                                   float(grad_scale), _l.ptr(grad_scale_dev), _l.ptr(coef), _l.ptr(xhat), _l.ptr(rstd), _l.ptr(gamma), D,
+                                   _l.ptr(dz), _l.ptr(dx), _l.ptr(dgamma), _l.ptr(dbeta), p_drop, seed, stream_id, _l.ptr(step_dev),
+                                   _l.ptr(ws), ws_bytes, *_pl(gp), _l.ptr(stat), *_head_layout(L, layout), _l.stream_ptr()),
+             "pxr_bpr_ln_bwd_f32")
     return dz, dx, gp, coef
 
 
@@ -1153,9 +1141,9 @@ def ln_bwd(gather_mode, dy, xhat, rstd, gamma, dgamma, dbeta, p_drop=0.0, seed=0
                  "pxr_ln_bwd_stat_f32")
         return dz, dx
     gp = Planes.alloc(rows, D, dy.device) if planes else None
-    _l.check(Lb.pxr_ln_bwd_planes_f32(int(gather_mode), _l.ptr(dy), _l.ptr(xhat), _l.ptr(rstd), _l.ptr(gamma), rows, D,
-                                      _l.ptr(dz), _l.ptr(dx), _l.ptr(dgamma), _l.ptr(dbeta), p_drop, seed, stream_id,
-                                      _l.ptr(step_dev), _l.ptr(ws), ws_bytes, *_pl(gp), _l.stream_ptr()), "pxr_ln_bwd_f32")
+    _l.check(Lb.pxr_ln_bwd_f32(int(gather_mode), _l.ptr(dy), _l.ptr(xhat), _l.ptr(rstd), _l.ptr(gamma), rows, D,
+                               _l.ptr(dz), _l.ptr(dx), _l.ptr(dgamma), _l.ptr(dbeta), p_drop, seed, stream_id,
+                               _l.ptr(step_dev), _l.ptr(ws), ws_bytes, *_pl(gp), _l.stream_ptr()), "pxr_ln_bwd_f32")
     return (dz, dx, gp) if planes else (dz, dx)
 
 
@@ -1178,9 +1166,8 @@ def _attn_long_fwd(qkv, keymask, km_bstride, B, H, L, d, p_drop, seed, stream_id
     sP, sQ, sC = (H * L * Lp, L * Lp), (L * ld, d), (L * D, d)
     gemm_batched(True, True, L, L, d, qkv, 0, ld, qkv, D, ld, P, 0, Lp, bh, H, sQ, sQ, sP)            # q at 0, k at D
     PD = torch.empty_like(P) if p_drop > 0 else None
-    rows_fwd = Lb.pxr_attn_rows_fwd_f32 if causal else Lb.pxr_attn_rows_fwd_bidir_f32
-    _l.check(rows_fwd(_l.ptr(P), _l.ptr(PD), _l.ptr(keymask), km_bstride, B, H, L, Lp, p_drop, seed, stream_id, _l.ptr(step_dev), d,
-                      _l.stream_ptr()), "pxr_attn_rows_fwd_f32")
+    _l.check(Lb.pxr_attn_rows_fwd_f32(_l.ptr(P), _l.ptr(PD), _l.ptr(keymask), km_bstride, B, H, L, Lp, p_drop, seed, stream_id,
+                                      _l.ptr(step_dev), d, int(causal), _l.stream_ptr()), "pxr_attn_rows_fwd_f32")
     ctx = torch.empty(B, L, D, dtype=torch.float32, device=qkv.device)
     gemm_batched(True, False, L, d, L, PD if PD is not None else P, 0, Lp, qkv, 2 * D, ld, ctx, 0, D, bh, H, sP, sQ, sC)
     return ctx, (P, PD)
@@ -1210,8 +1197,8 @@ def attn_fwd(qkv, keymask, km_bstride, B, H, L, d, p_drop=0.0, seed=0, stream_id
              planes: bool = False, causal: bool = True):
     """qkv [B,L,3*H*d] fused projection output -> (ctx [B,L,H*d], probs [B,H,L,L] | None).  planes=True: ctx is returned
     as Planes [B*L, H*d] INSTEAD of the fp32 tensor (written by the fused kernel where it serves the shape, by a split
-    launch otherwise).  causal=False: the key-padding mask only (BERT4Rec; pxr_attn_fwd_bidir_f32 / pxr_attn_rows_fwd_bidir_f32);
-    attn_bwd serves both masks (it works from the saved probabilities)."""
+    launch otherwise).  causal=False: the key-padding mask only (BERT4Rec); attn_bwd serves both masks (it works from the saved
+    probabilities)."""
     Lb = _l.load()
     _req(qkv, torch.float32, "qkv"); _req(keymask, torch.int64, "keymask", contiguous=False)
     D = H * d
@@ -1226,12 +1213,8 @@ def attn_fwd(qkv, keymask, km_bstride, B, H, L, d, p_drop=0.0, seed=0, stream_id
     probs = torch.empty(B, H, L, L, dtype=torch.float32, device=qkv.device) if save else None
     base = qkv.data_ptr()
     q, k, v = _l.c_void_p(base), _l.c_void_p(base + 4 * D), _l.c_void_p(base + 8 * D)
-    args = (q, k, v, 3 * D, _l.ptr(keymask), km_bstride, B, H, L, d, _l.ptr(ctx), D, _l.ptr(probs), p_drop, seed, stream_id,
-            _l.ptr(step_dev), *_pl(cp_))
-    if causal:
-        _l.check((Lb.pxr_attn_fwd_h2_f32 if h2 else Lb.pxr_attn_fwd_planes_f32)(*args, _l.stream_ptr()), "pxr_attn_fwd_f32")
-    else:
-        _l.check(Lb.pxr_attn_fwd_bidir_f32(*args, int(h2), _l.stream_ptr()), "pxr_attn_fwd_bidir_f32")
+    _l.check(Lb.pxr_attn_fwd_f32(q, k, v, 3 * D, _l.ptr(keymask), km_bstride, B, H, L, d, _l.ptr(ctx), D, _l.ptr(probs), p_drop, seed,
+                                 stream_id, _l.ptr(step_dev), *_pl(cp_), int(h2), int(causal), _l.stream_ptr()), "pxr_attn_fwd_f32")
     if planes and not fused_p:
         cp_ = split_planes(ctx.view(B * L, D))
     return (cp_ if planes else ctx), probs
@@ -1263,9 +1246,9 @@ def attn_bwd(dctx, qkv, probs, B, H, L, d, p_drop=0.0, seed=0, stream_id=0, step
     base = qkv.data_ptr()
     cp = _l.c_void_p
     dptr = (lambda o: None) if fused_p else (lambda o: cp(dqkv.data_ptr() + o))
-    _l.check(Lb.pxr_attn_bwd_planes_f32(_l.ptr(dctx), D, cp(base), cp(base + 4 * D), cp(base + 8 * D), 3 * D, _l.ptr(probs),
-                                        B, H, L, d, dptr(0), dptr(4 * D), dptr(8 * D), 3 * D, p_drop, seed,
-                                        stream_id, _l.ptr(step_dev), *_pl(gp), 3 * D, 0, D, 2 * D, _l.stream_ptr()),
+    _l.check(Lb.pxr_attn_bwd_f32(_l.ptr(dctx), D, cp(base), cp(base + 4 * D), cp(base + 8 * D), 3 * D, _l.ptr(probs),
+                                 B, H, L, d, dptr(0), dptr(4 * D), dptr(8 * D), 3 * D, p_drop, seed,
+                                 stream_id, _l.ptr(step_dev), *_pl(gp), 3 * D, 0, D, 2 * D, _l.stream_ptr()),
              "pxr_attn_bwd_f32")
     if planes and not fused_p:
         gp = split_planes(dqkv.view(B * L, 3 * D))
@@ -1273,6 +1256,20 @@ def attn_bwd(dctx, qkv, probs, B, H, L, d, p_drop=0.0, seed=0, stream_id=0, step
 
 
 # ------------------------------------------------------------------------------------------------ loss head
+def _sasrec_layout(L: int):
+    """SASRec's shifted [B, 2, L+1] id windows: (id_bstride, in_off, pos_off, neg_off) -- the inputs items[:, 0, t], the targets
+    items[:, 0, t+1], the negatives items[:, 1, t+1] of the L positions.  What layout=None means throughout this module."""
+    return 2 * (L + 1), 0, 1, L + 2
+
+
+def _head_layout(L: int, layout):
+    """(id_bstride, pos_off, neg_off) of the loss head's target / negative ids: `layout`, or SASRec's windows when None."""
+    if layout is not None:
+        return tuple(layout)
+    bstride, _, pos_off, neg_off = _sasrec_layout(L)
+    return bstride, pos_off, neg_off
+
+
 def bpr_loss_fwd(out, table, items, masked_index, layout=None):
     """-> (loss [1] on device, pos_score [B,L], neg_score [B,L])   (sasrec.py:88-92).  layout = (id_bstride, pos_off, neg_off) of the
     target / negative ids (None: SASRec's shifted windows; BERT4Rec: (3L, L, 2L), bert4rec.py:98-111)."""
@@ -1285,12 +1282,9 @@ def bpr_loss_fwd(out, table, items, masked_index, layout=None):
     neg = torch.empty(B, L, dtype=torch.float32, device=dev)
     lossrow = torch.empty(B * L, dtype=torch.float32, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
-    args = (_l.ptr(out), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), B, L, D, _l.ptr(pos), _l.ptr(neg),
-            _l.ptr(lossrow), _l.ptr(loss))
-    if layout is None:
-        _l.check(Lb.pxr_bpr_loss_fwd_f32(*args, _l.stream_ptr()), "pxr_bpr_loss_fwd_f32")
-    else:
-        _l.check(Lb.pxr_bpr_loss_fwd_lay_f32(*args, *layout, _l.stream_ptr()), "pxr_bpr_loss_fwd_lay_f32")
+    _l.check(Lb.pxr_bpr_loss_fwd_f32(_l.ptr(out), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), B, L, D,
+                                     _l.ptr(pos), _l.ptr(neg), _l.ptr(lossrow), _l.ptr(loss), *_head_layout(L, layout), _l.stream_ptr()),
+             "pxr_bpr_loss_fwd_f32")
     return loss, pos, neg
 
 
@@ -1300,12 +1294,9 @@ def bpr_loss_bwd(pos, neg, table, items, masked_index, D, grad_scale=1.0, grad_s
     B, L = pos.shape
     dout = torch.empty(B, L, D, dtype=torch.float32, device=pos.device)
     coef = torch.empty(B, L, dtype=torch.float32, device=pos.device)
-    args = (_l.ptr(pos), _l.ptr(neg), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), B, L, D, float(grad_scale),
-            _l.ptr(grad_scale_dev), _l.ptr(dout), _l.ptr(coef))
-    if layout is None:
-        _l.check(Lb.pxr_bpr_loss_bwd_f32(*args, _l.stream_ptr()), "pxr_bpr_loss_bwd_f32")
-    else:
-        _l.check(Lb.pxr_bpr_loss_bwd_lay_f32(*args, *layout, _l.stream_ptr()), "pxr_bpr_loss_bwd_lay_f32")
+    _l.check(Lb.pxr_bpr_loss_bwd_f32(_l.ptr(pos), _l.ptr(neg), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), B, L,
+                                     D, float(grad_scale), _l.ptr(grad_scale_dev), _l.ptr(dout), _l.ptr(coef), *_head_layout(L, layout),
+                                     _l.stream_ptr()), "pxr_bpr_loss_bwd_f32")
     return dout, coef
 
 
@@ -1470,42 +1461,19 @@ def ids_to_compact(ids: torch.Tensor, uniq_idx: torch.Tensor, n_uniq: torch.Tens
     return out
 
 
-def sasrec_embed_grad(items, dx0, out, coef, n_table, scale=1.0, sp: SparseRows | None = None) -> SparseRows:
-    Lb = _l.load()
-    _req(items, torch.int64, "items"); _req(dx0, torch.float32, "dx0"); _req(out, torch.float32, "out")
-    _req(coef, torch.float32, "coef")
-    B, L, D = out.shape
-    n = 3 * B * L
-    sp = sp if sp is not None else SparseRows(n, D, out.device)
-    ws_bytes = int(Lb.pxr_embed_grad_ws_bytes(n))
-    ws = _ws.get(ws_bytes, out.device)
-    _l.check(Lb.pxr_sasrec_embed_grad_f32(_l.ptr(items), B, L, _l.ptr(dx0), _l.ptr(out), _l.ptr(coef), D, n_table,
-                                          float(scale), _l.ptr(sp.idx), _l.ptr(sp.rows), _l.ptr(sp.n), _l.ptr(ws),
-                                          ws_bytes, _l.stream_ptr()), "pxr_sasrec_embed_grad_f32")
-    return sp
-
-
 def occ_ws_bytes(B: int, L: int) -> int:
     return int(_l.load().pxr_embed_grad_ws_bytes(3 * B * L))
 
 
-def sasrec_occ_sort(items, n_table, sp: SparseRows, ws: torch.Tensor):
-    """Phase 1 (ids only): fills sp.idx / sp.n, leaves the sorted occurrences in `ws` (caller-owned, persistent)."""
-    Lb = _l.load()
-    _req(items, torch.int64, "items")
-    B, _, W = items.shape
-    _l.check(Lb.pxr_sasrec_occ_sort(_l.ptr(items), B, W - 1, n_table, _l.ptr(sp.idx), _l.ptr(sp.n), _l.ptr(ws),
-                                    ws.numel(), _l.stream_ptr()), "pxr_sasrec_occ_sort")
-
-
-def seq_occ_sort(items, L: int, layout, n_table, sp: SparseRows, ws: torch.Tensor):
-    """sasrec_occ_sort for another id layout: layout = (id_bstride, in_off, pos_off, neg_off) of the L positions of each sequence
-    (BERT4Rec's [B, 3, L]: (3L, 0, L, 2L); pxr_seq_occ_sort_lay).  Phase 2 is sasrec_occ_segsum, unchanged.  `ws`: occ_ws_bytes(B, L)."""
+def occ_sort(items, L: int, layout, n_table, sp: SparseRows, ws: torch.Tensor):
+    """Phase 1 of the table gradient (ids only): fills sp.idx / sp.n, leaves the sorted occurrences in `ws` (occ_ws_bytes(B, L),
+    caller-owned, persistent).  layout = (id_bstride, in_off, pos_off, neg_off) of the L positions of each sequence (None: SASRec's
+    [B, 2, L+1] windows, _sasrec_layout; BERT4Rec's [B, 3, L]: (3L, 0, L, 2L)).  Phase 2 is sasrec_occ_segsum whatever the layout."""
     Lb = _l.load()
     _req(items, torch.int64, "items")
     B = items.shape[0]
-    _l.check(Lb.pxr_seq_occ_sort_lay(_l.ptr(items), B, L, *layout, n_table, _l.ptr(sp.idx), _l.ptr(sp.n), _l.ptr(ws), ws.numel(),
-                                     _l.stream_ptr()), "pxr_seq_occ_sort_lay")
+    _l.check(Lb.pxr_seq_occ_sort(_l.ptr(items), B, L, *(_sasrec_layout(L) if layout is None else layout), n_table, _l.ptr(sp.idx),
+                                 _l.ptr(sp.n), _l.ptr(ws), ws.numel(), _l.stream_ptr()), "pxr_seq_occ_sort")
 
 
 def occ_split_ws_bytes(B: int, L: int, D: int) -> int:
@@ -1589,9 +1557,9 @@ def score_topk(users: torch.Tensor, ld_users: int, B: int, table: torch.Tensor, 
                hist_items=None, table_planes: Planes | None = None, table_norm_max: torch.Tensor | None = None):
     """Fused full-catalog scoring + masking + top-K (see pxr.h).  `users` may be a strided view (row stride
     ld_users floats).  Returns (topk_idx int64 [B,K], topk_val fp32 [B,K]).  table_planes: split_planes(table), made once
-    per evaluation -- the main pass over the catalogue then runs on pre-split operands (pxr_score_topk_planes_f32);
-    table_norm_max: row_norm_max(table), made with them -- that pass then runs on topk_products() of the six bf16 products and the
-    survivors are re-scored exactly (pxr_score_topk_fast_f32): same ids, same bits."""
+    per evaluation -- the main pass over the catalogue then runs on pre-split operands; table_norm_max: row_norm_max(table), made
+    with them -- that pass then runs on topk_products() of the six bf16 products and the survivors are re-scored exactly: same
+    ids, same bits (pxr_score_topk_f32)."""
     Lb = _l.load()
     _req(users, torch.float32, "users", contiguous=False); _req(table, torch.float32, "table")
     N, D = table.shape
@@ -1607,10 +1575,10 @@ def score_topk(users: torch.Tensor, ld_users: int, B: int, table: torch.Tensor, 
         u2 = torch.as_strided(users, (B, D), (ld_users, 1))
         up = split_planes(u2)
     products = topk_products() if (table_planes is not None and table_norm_max is not None) else 6
-    _l.check(Lb.pxr_score_topk_fast_f32(_l.ptr(users), ld_users, B, _l.ptr(table), N, D, *_pl(up), *_pl(table_planes),
-                                        _l.ptr(table_norm_max) if products != 6 else None, products,
-                                        _l.ptr(hist_ptr), _l.ptr(hist_items), K, _l.ptr(idx), _l.ptr(val), _l.ptr(ws),
-                                        ws_bytes, _l.stream_ptr()), "pxr_score_topk_f32")
+    _l.check(Lb.pxr_score_topk_f32(_l.ptr(users), ld_users, B, _l.ptr(table), N, D, *_pl(up), *_pl(table_planes),
+                                   _l.ptr(table_norm_max) if products != 6 else None, products,
+                                   _l.ptr(hist_ptr), _l.ptr(hist_items), K, _l.ptr(idx), _l.ptr(val), _l.ptr(ws),
+                                   ws_bytes, _l.stream_ptr()), "pxr_score_topk_f32")
     return idx, val
 
 
@@ -1721,8 +1689,8 @@ def adamw_flat_tab(p, g, m, v, hyper, step, beta1, beta2, eps, step_dev=None, pl
                                                   beta1, beta2, eps, wd, *sa, 1 if h2 else 0, _l.ptr(planes_exps) if h2 else None,
                                                   _l.stream_ptr()), "pxr_adamw_flat_tab_ex_f32")
     else:
-        _l.check(Lb.pxr_adamw_flat_tab_planes_f32(_l.ptr(p), _l.ptr(g), _l.ptr(m), _l.ptr(v), p.numel(), _l.ptr(hyper), step,
-                                                  _l.ptr(step_dev), beta1, beta2, eps, *sa, _l.stream_ptr()),
+        _l.check(Lb.pxr_adamw_flat_tab_f32(_l.ptr(p), _l.ptr(g), _l.ptr(m), _l.ptr(v), p.numel(), _l.ptr(hyper), step,
+                                           _l.ptr(step_dev), beta1, beta2, eps, *sa, _l.stream_ptr()),
                  "pxr_adamw_flat_tab_f32")
     if late:
         split_planes_multi([p[o:o + r * c].view(r, c) for o, r, c, _ in late], [pl for _, _, _, pl in late])

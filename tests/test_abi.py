@@ -16,10 +16,12 @@ def _header_symbols():
 
 def test_library_loads_and_reports_target():
     L = lib.load()
-    # one ABI revision in three places: the header, the ctypes binding, the built library.  0.3.0 = the revision in which the
-    # `stat` buffers of pxr_ln_bwd_stat_f32 / pxr_attn_bwd_stat_f32 changed size under unchanged names
+    # one ABI revision in three places: the header, the ctypes binding, the built library.  0.3.1 = the revision in which every
+    # kernel family kept one entry: the plain names (pxr_attn_fwd_f32, pxr_input_ln_fwd_f32, pxr_bpr_loss_fwd_f32, ...) took the
+    # general argument lists of their planes / h2 / bidirectional / id-layout twins, which are gone (0.3.0: the `stat` buffers of
+    # pxr_ln_bwd_stat_f32 / pxr_attn_bwd_stat_f32 changed size under unchanged names)
     hdr = int(re.search(r"#define\s+PXR_ABI_VERSION\s+(\d+)", open(os.path.join(ROOT, "include", "pxr.h")).read()).group(1))
-    assert hdr == lib.ABI_VERSION == L.pxr_version() == 300
+    assert hdr == lib.ABI_VERSION == L.pxr_version() == 301
     assert L.pxr_target_arch() == b"gfx950"
 
 

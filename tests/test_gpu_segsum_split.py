@@ -50,7 +50,7 @@ def test_split_segment_sums_equal_the_one_launch_sums(B, L, D, heavy):
     one, two, again = (ops.SparseRows(cap, D, "cuda") for _ in range(3))
     for sp, w2 in ((one, None), (two, ws2), (again, ws2)):
         sp.rows.fill_(float("nan"))
-        ops.sasrec_occ_sort(items, n_items, sp, ws)
+        ops.occ_sort(items, L, None, n_items, sp, ws)
         ops.sasrec_occ_segsum(ws, dx0, out, coef, n_items, sp, 1.0, ws2=w2)
         assert int(ws2[:8].view(torch.int32)[0]) == 0          # the cursor is back at zero after every call
     n = one.count()

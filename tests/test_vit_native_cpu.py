@@ -89,7 +89,7 @@ def test_visual_adamw_matches_torch_adamw(monkeypatch):
     enc = _build("mean", 5 + 16 * 2, monkeypatch)
 
     # torch stand-ins for the two optimizer entry points VisualAdamW uses (the step number and its scalars live in a table on the
-    # device: pxr_adamw_hyper_append / pxr_adamw_flat_tab_planes_f32) -- same formulas as csrc/adamw.hip::adam_elem / make_hyper
+    # device: pxr_adamw_hyper_append / pxr_adamw_flat_tab_f32) -- same formulas as csrc/adamw.hip::adam_elem / make_hyper
     def hyper_append(hyper, cumlog, step, lr, b1, b2, eps, wd, step_dev=None, advance=False):
         if step_dev is not None and advance:
             step_dev += 1
