@@ -49,9 +49,10 @@ int pxr_dropout_keep_host(uint64_t seed, uint32_t stream_id, uint64_t first_inde
                           uint8_t* keep_out);
 
 /* Registers a caller-owned int32 in DEVICE memory as this process' status word (NULL unregisters).  Kernels that
- * gather table rows by id (pxr_embed_gather_f32, pxr_input_ln_fwd_f32) OR bit 0 into it when an id lies outside
- * [0, N) -- where the reference's nn.Embedding raises IndexError / a device-side assert (model/IDNet/sasrec.py:68) --
- * and clamp the id; pxr_merge_split_rows_f32 ORs bit 1 when a rank's row count exceeded the exchanged capacity.  The
+ * gather table rows by id (pxr_embed_gather_f32, pxr_input_ln_fwd_f32, the loss head's target / negative ids in
+ * pxr_bpr_loss_fwd_f32 and pxr_ln_residual_bpr_fwd_f32, the occurrence ids of pxr_seq_occ_sort) OR bit 0 into it when an id lies
+ * outside [0, N) -- where the reference's nn.Embedding raises IndexError / a device-side assert (model/IDNet/sasrec.py:68) --
+ * and clamp (the sort: drop) the id; pxr_merge_split_rows_f32 ORs bit 1 when a rank's row count exceeded the exchanged capacity.  The
  * host reads the word at its next synchronisation point and raises.  One process per GPU. */
 int pxr_set_status_word(int32_t* dev_word);
 

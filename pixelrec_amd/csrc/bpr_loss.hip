@@ -30,12 +30,14 @@ struct BprArgs {
   int B, L, D;
   float grad_scale;
   const float* grad_scale_dev;  // optional device scalar multiplied in (autograd's upstream gradient)
+  int32_t* status;              // fwd: device status word (bad-index flag) or null
   // id layout: position t of sequence b scores against items[b*id_bstride + pos_off + t] / [... + neg_off + t] -- SASRec's
   // shifted [B, 2, L+1] windows (2(L+1), 1, L+2), BERT4Rec's aligned [B, 3, L] planes (3L, L, 2L)
   int64_t id_bstride, pos_off, neg_off;
 };
 
 __device__ __forceinline__ int64_t clamp_id(int64_t r, int64_t n) { return r < 0 ? 0 : (r >= n ? n - 1 : r); }
+__device__ __forceinline__ bool bad_id(int64_t r, int64_t n) { return r < 0 || r >= n; }
 
 __global__ void __launch_bounds__(256) bpr_fwd_kernel(BprArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -43,8 +45,12 @@ __global__ void __launch_bounds__(256) bpr_fwd_kernel(BprArgs a) {
   if (r >= a.B * a.L) return;
   const int b = r / a.L, t = r - b * a.L;
   const int64_t* it = a.items + (int64_t)b * a.id_bstride;
-  const float* ep = a.table + clamp_id(it[a.pos_off + t], a.n_table) * a.D;
-  const float* en = a.table + clamp_id(it[a.neg_off + t], a.n_table) * a.D;
+  const int64_t ip = it[a.pos_off + t], in = it[a.neg_off + t];
+  // an id outside the table is an error in the reference (nn.Embedding raises on items, sasrec.py:68): flag it, then clamp.
+  // (The backward reads the same ids after this launch and does not flag again.)
+  if ((bad_id(ip, a.n_table) || bad_id(in, a.n_table)) && a.status && lane == 0) atomicOr(a.status, PXR_STATUS_BAD_INDEX);
+  const float* ep = a.table + clamp_id(ip, a.n_table) * a.D;
+  const float* en = a.table + clamp_id(in, a.n_table) * a.D;
   const float* o = a.out + (int64_t)r * a.D;
   float sp = 0.f, sn = 0.f;
   for (int c = lane * 4; c < a.D; c += 256) {
@@ -137,6 +143,7 @@ extern "C" int pxr_bpr_loss_fwd_f32(const float* out, const float* table, int64_
   a.out = out; a.table = table; a.items = items; a.mask = masked_index; a.pos_score = pos_score;
   a.neg_score = neg_score; a.lossrow = lossrow; a.loss = loss; a.n_table = n_table; a.B = B; a.L = L; a.D = D;
   a.id_bstride = id_bstride; a.pos_off = pos_off; a.neg_off = neg_off;
+  a.status = pxr_status_word();
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(bpr_fwd_kernel, dim3((B * L + 3) / 4), dim3(256), 0, st, a);
   hipLaunchKernelGGL(bpr_reduce_kernel, dim3(1), dim3(256), 0, st, (const float*)lossrow, B, L, loss);

@@ -42,9 +42,11 @@ __global__ void __launch_bounds__(256) occ_keys_rows_kernel(const int64_t* __res
 // [B, 2, L+1] windows: bstride 2(L+1), off (0, 1, L+2); BERT4Rec's aligned [B, 3, L] planes: bstride 3L, off (0, L, 2L)
 struct OccLayout { int64_t bstride, off_in, off_pos, off_neg; };
 
+// An id outside [0, n_table) is an error in the reference (nn.Embedding raises on the whole items tensor): it sets the bad-index
+// bit of `status` (when given) and is then dropped like padding.  The plain (MODE_ROWS) keys only drop.
 __global__ void __launch_bounds__(256) occ_keys_sasrec_kernel(const int64_t* __restrict__ items, int B, int L,
                                                               int* __restrict__ keys, int* __restrict__ vals,
-                                                              int64_t n_table, OccLayout lay) {
+                                                              int64_t n_table, OccLayout lay, int32_t* status) {
   const int T = B * L;
   const int o = blockIdx.x * 256 + threadIdx.x;
   if (o >= 3 * T) return;
@@ -52,7 +54,10 @@ __global__ void __launch_bounds__(256) occ_keys_sasrec_kernel(const int64_t* __r
   const int b = r / L, t = r - b * L;
   const int64_t* row = items + (int64_t)b * lay.bstride;
   int64_t id = row[(type == 0 ? lay.off_in : (type == 1 ? lay.off_pos : lay.off_neg)) + t];
-  if (id < 0 || id >= n_table) id = 0;
+  if (id < 0 || id >= n_table) {
+    if (status) atomicOr(status, PXR_STATUS_BAD_INDEX);
+    id = 0;
+  }
   keys[o] = (int)id;
   vals[o] = o;
 }
@@ -245,10 +250,13 @@ struct FusedPassArgs {
   int n, B, L, shift, bits, first;
   int64_t n_table;
   OccLayout lay;               // MODE_SASREC: where the three occurrence kinds sit in `src`
+  int32_t* status;             // MODE_SASREC: bad-index flag (occ_keys_sasrec_kernel) or null
 };
 
+// flag: this call is the one read of occurrence o that reports an id outside the table (pass 0 reads every key once per block
+// for the histogram, and once more, in its own block only, to rank it)
 template <int MODE>
-__device__ __forceinline__ int occ_key(const FusedPassArgs& a, int o) {
+__device__ __forceinline__ int occ_key(const FusedPassArgs& a, int o, bool flag = false) {
   int64_t id;
   if constexpr (MODE == 0) {
     id = a.src[o];
@@ -259,7 +267,11 @@ __device__ __forceinline__ int occ_key(const FusedPassArgs& a, int o) {
     const int64_t* row = a.src + (int64_t)b * a.lay.bstride;
     id = row[(type == 0 ? a.lay.off_in : (type == 1 ? a.lay.off_pos : a.lay.off_neg)) + t];
   }
-  return (id < 0 || id >= a.n_table) ? 0 : (int)id;
+  if (id < 0 || id >= a.n_table) {
+    if (MODE != 0 && flag && a.status) atomicOr(a.status, PXR_STATUS_BAD_INDEX);
+    return 0;
+  }
+  return (int)id;
 }
 
 template <int MODE>
@@ -321,7 +333,7 @@ __global__ void __launch_bounds__(FP_THREADS) fused_pass_kernel(FusedPassArgs a)
   for (int e = 0; e < FP_ITEMS; ++e) {
     const int i = base + e * 64 + lane;
     const bool valid = i < a.n;
-    key[e] = valid ? (a.first ? occ_key<MODE>(a, i) : a.keys_in[i]) : 0;
+    key[e] = valid ? (a.first ? occ_key<MODE>(a, i, true) : a.keys_in[i]) : 0;
     val[e] = valid ? (a.first ? i : a.vals_in[i]) : 0;
     const int dg = (key[e] >> a.shift) & mask;
     unsigned long long m = __ballot(valid);
@@ -890,6 +902,7 @@ static int fused_sort(const int64_t* src, int n, int B, int L, int64_t n_table, 
     FusedPassArgs a{};
     a.src = src; a.keys_in = kin; a.vals_in = vin; a.keys_out = kout; a.vals_out = vout;
     a.n = n; a.B = B; a.L = L; a.shift = p * width; a.bits = width; a.first = (p == 0); a.n_table = n_table; a.lay = lay;
+    a.status = MODE == MODE_SASREC ? pxr_status_word() : nullptr;
     hipLaunchKernelGGL(fused_pass_kernel<MODE>, dim3(w.nblk), dim3(FP_THREADS), 0, st, a);
     int* t = kin; kin = kout; kout = t;
     t = vin; vin = vout; vout = t;
@@ -945,7 +958,8 @@ extern "C" int pxr_embed_grad_rows_f32(const int64_t* idx, int64_t n, const floa
 // kinds -- input | target | negative of position t of sequence b -- are at items[b*id_bstride + {in_off, pos_off, neg_off} + t]:
 // SASRec's shifted [B, 2, L+1] windows are (2(L+1), 0, 1, L+2); BERT4Rec's items [B, 3, L] = masked sequence | original sequence |
 // negatives are (3L, 0, L, 2L) -- the table's three uses in reference IDNet/bert4rec.py:76-81,98-111 under autograd; its
-// mask-token row is an ordinary row, row 0 (padding_idx) is dropped.  Phase 2 is pxr_sasrec_occ_segsum[_split] whatever the
+// mask-token row is an ordinary row, row 0 (padding_idx) is dropped.  An id outside [0, n_table) is dropped too and sets the
+// bad-index bit of the status word (the reference's nn.Embedding raises).  Phase 2 is pxr_sasrec_occ_segsum[_split] whatever the
 // layout: the occurrence o of kind k at row r = b*L + t adds dx0[r], +coef[r] out[r] or -coef[r] out[r].
 extern "C" int pxr_seq_occ_sort(const int64_t* items, int B, int L, int64_t id_bstride, int64_t in_off, int64_t pos_off,
                                 int64_t neg_off, int64_t n_table, int64_t* uniq_idx, int32_t* n_uniq_dev, void* ws,
@@ -968,7 +982,7 @@ extern "C" int pxr_seq_occ_sort(const int64_t* items, int B, int L, int64_t id_b
     return PXR_OK;
   }
   hipLaunchKernelGGL(occ_keys_sasrec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, items, B, L, w.keysA, w.valsA,
-                     n_table, lay);
+                     n_table, lay, pxr_status_word());
   int rc = sort_and_segment(w, n, n_table, uniq_idx, n_uniq_dev, st, &sorted_vals);
   if (rc) return rc;
   if (sorted_vals != sasrec_sorted_vals(w, n, n_table)) { pxr_set_error("pxr_seq_occ_sort: internal buffer parity"); return PXR_ERR_LAUNCH; }

@@ -21,7 +21,10 @@ namespace pxr {
 // The loss head fused into the LAST LayerNorm of the block (sasrec.py:86-92: the head reads exactly the rows this LayerNorm
 // writes): forward = the two target-row dot products + the per-position loss term of bpr_loss.hip's bpr_fwd_kernel in the wave
 // that holds the row; backward = bpr_bwd_kernel's d out row formed in registers instead of being written and read back.  Same
-// formulas, same order of operations as bpr_loss.hip (bit-identical scores / coefficients).  items == null: no head.
+// formulas, same order of operations as bpr_loss.hip.  The backward is bit-identical to bpr_bwd_kernel + ln_bwd_kernel at every D;
+// the forward's scores and loss are bit-identical to bpr_fwd_kernel's for D <= 1024 (VEC <= 4), while at VEC = 8 / 16 the two
+// separately compiled dot products do not round alike and the scores differ by a few ulp of the D-term sum (measured:
+// tests/test_gpu_bpr_ref.py).  items == null: no head.
 struct BprHead {
   const float* table;      // [n_table, D]
   const int64_t* items;    // [B, 2, L+1]
@@ -59,7 +62,7 @@ struct LnFwdArgs {
   uint32_t stream;
   uint64_t seed;
   const int64_t* step_dev;  // optional device counter added to the seed (hipGraph replays advance it on the device)
-  int32_t* status;          // GATHER: device status word (bad-index flag) or null
+  int32_t* status;          // device status word or null: GATHER's and the loss head's bad-index flag, the h2 planes' range flag
   P3Mat yp;                 // optional: y also as planes (the next GEMM's operand format, planes.cuh); p == null: none
   int yp_fmt;               // PXR_PLANES_BF16X3 | PXR_PLANES_H2 (two fp16 planes; a value beyond the fp16 range flags `status`)
   BprHead head;             // RESIDUAL only: the loss head's forward on the rows this launch writes (items == null: none)
@@ -164,8 +167,12 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs a) {
       if (a.head.items) {   // wave-uniform
         const int b = row / a.head.L, t = row - b * a.head.L;
         const int64_t* it = a.head.items + (int64_t)b * a.head.id_bstride;
-        ep = a.head.table + ln_clamp_id(it[a.head.pos_off + t], a.head.n_table) * D;
-        en = a.head.table + ln_clamp_id(it[a.head.neg_off + t], a.head.n_table) * D;
+        const int64_t ip = it[a.head.pos_off + t], in = it[a.head.neg_off + t];
+        // (as bpr_fwd_kernel: an id outside the table is flagged, then clamped; the fused backward does not flag again)
+        if ((ip < 0 || ip >= a.head.n_table || in < 0 || in >= a.head.n_table) && a.status && lane == 0)
+          atomicOr(a.status, PXR_STATUS_BAD_INDEX);
+        ep = a.head.table + ln_clamp_id(ip, a.head.n_table) * D;
+        en = a.head.table + ln_clamp_id(in, a.head.n_table) * D;
       }
     }
 #pragma unroll
@@ -611,7 +618,7 @@ extern "C" int pxr_ln_residual_fwd_f32(const float* x, const float* res, const f
 // The block's LAST LayerNorm with the loss head's forward fused in (BprHead): y = LN(dropout(x) + res) over rows = B*L, and
 // for every row the two target-row scores + the per-position loss term; then the fixed-order loss reduction (bpr_loss.hip).
 // Replaces pxr_ln_residual_fwd_f32 + pxr_bpr_loss_fwd_f32 (reference layers.py:670-671 + sasrec.py:86-92): one launch and one
-// pass over `y` less; bit-identical outputs.  The id layout (BprHead::id_bstride): SASRec's shifted windows pass
+// pass over `y` less; bit-identical outputs for D <= 1024 (beyond, the scores and the loss within fp32 rounding: BprHead above).  The id layout (BprHead::id_bstride): SASRec's shifted windows pass
 // (2(L+1), 1, L+2); BERT4Rec's aligned masked head (reference IDNet/bert4rec.py:98-111 on the output of layers.py:670-671) passes
 // (3L, L, 2L) for items [B, 3, L] = (masked sequence | original sequence | negatives).
 extern "C" int pxr_ln_residual_bpr_fwd_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps,
@@ -633,6 +640,7 @@ extern "C" int pxr_ln_residual_bpr_fwd_f32(const float* x, const float* res, con
   a.head.table = table; a.head.items = items; a.head.mask = masked_index; a.head.pos = pos_score; a.head.neg = neg_score;
   a.head.lossrow = lossrow; a.head.n_table = n_table; a.head.B = B; a.head.L = L;
   a.head.id_bstride = id_bstride; a.head.pos_off = pos_off; a.head.neg_off = neg_off;
+  a.status = pxr_status_word();   // the head's bad-index flag (no planes here, so nothing else of this launch writes it)
   const int rc = launch_ln_fwd<false>(a, (hipStream_t)stream);
   if (rc) return rc;
   return pxr_bpr_loss_reduce(lossrow, B, L, loss, stream);

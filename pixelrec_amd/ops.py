@@ -1018,7 +1018,8 @@ def ln_residual_fwd(x, res, gamma, beta, eps, p_drop=0.0, seed=0, stream_id=0, s
 def ln_residual_bpr_fwd(x, res, gamma, beta, eps, table, items, masked_index, p_drop=0.0, seed=0, stream_id=0, save=True,
                         step_dev=None, layout=None):
     """The block's last LayerNorm with the loss head's forward fused in (pxr_ln_residual_bpr_fwd_f32):
-    -> (y [B,L,D], xhat, rstd, loss [1], pos [B,L], neg [B,L]) -- what ln_residual_fwd + bpr_loss_fwd return, bit for bit.
+    -> (y [B,L,D], xhat, rstd, loss [1], pos [B,L], neg [B,L]) -- what ln_residual_fwd + bpr_loss_fwd return, bit for bit for
+    D <= 1024; beyond, y / xhat / rstd bit for bit and the scores / loss within the fp32 rounding of the dot product.
     layout = (id_bstride, pos_off, neg_off) of the target / negative ids in `items` (None: SASRec's shifted [B, 2, L+1] windows;
     BERT4Rec's aligned [B, 3, L]: (3L, L, 2L))."""
     Lb = _l.load()
@@ -1033,6 +1034,7 @@ def ln_residual_bpr_fwd(x, res, gamma, beta, eps, table, items, masked_index, p_
     neg = torch.empty(B, L, dtype=torch.float32, device=dev)
     lossrow = torch.empty(B * L, dtype=torch.float32, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
+    device_status(dev)                # an id outside the table flags the status word (raise_on_bad_indices)
     with _gemm_timer(0.0, "ln_fwd_kernel<RESIDUAL + loss head>"):
         _l.check(Lb.pxr_ln_residual_bpr_fwd_f32(_l.ptr(x), _l.ptr(res), _l.ptr(gamma), _l.ptr(beta), eps, B, L, D, _l.ptr(y),
                                                 _l.ptr(xhat), _l.ptr(rstd), p_drop, seed, stream_id, _l.ptr(step_dev), _l.ptr(table),
@@ -1258,7 +1260,9 @@ def attn_bwd(dctx, qkv, probs, B, H, L, d, p_drop=0.0, seed=0, stream_id=0, step
 # ------------------------------------------------------------------------------------------------ loss head
 def _sasrec_layout(L: int):
     """SASRec's shifted [B, 2, L+1] id windows: (id_bstride, in_off, pos_off, neg_off) -- the inputs items[:, 0, t], the targets
-    items[:, 0, t+1], the negatives items[:, 1, t+1] of the L positions.  What layout=None means throughout this module."""
+    items[:, 0, t+1], the negatives items[:, 1, t+1] of the L positions.  What layout=None means throughout this module.
+    items[:, 1, 0] is read by no kernel, so an id outside the table there is not flagged in the status word -- the reference embeds
+    the whole items tensor (sasrec.py:68) and would raise on it."""
     return 2 * (L + 1), 0, 1, L + 2
 
 
@@ -1282,6 +1286,7 @@ def bpr_loss_fwd(out, table, items, masked_index, layout=None):
     neg = torch.empty(B, L, dtype=torch.float32, device=dev)
     lossrow = torch.empty(B * L, dtype=torch.float32, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
+    device_status(dev)                # an id outside the table flags the status word (raise_on_bad_indices)
     _l.check(Lb.pxr_bpr_loss_fwd_f32(_l.ptr(out), _l.ptr(table), table.shape[0], _l.ptr(items), _l.ptr(masked_index), B, L, D,
                                      _l.ptr(pos), _l.ptr(neg), _l.ptr(lossrow), _l.ptr(loss), *_head_layout(L, layout), _l.stream_ptr()),
              "pxr_bpr_loss_fwd_f32")
@@ -1472,6 +1477,7 @@ def occ_sort(items, L: int, layout, n_table, sp: SparseRows, ws: torch.Tensor):
     Lb = _l.load()
     _req(items, torch.int64, "items")
     B = items.shape[0]
+    device_status(items.device)       # an id outside the table flags the status word (raise_on_bad_indices)
     _l.check(Lb.pxr_seq_occ_sort(_l.ptr(items), B, L, *(_sasrec_layout(L) if layout is None else layout), n_table, _l.ptr(sp.idx),
                                  _l.ptr(sp.n), _l.ptr(ws), ws.numel(), _l.stream_ptr()), "pxr_seq_occ_sort")
 
