@@ -578,6 +578,30 @@ int pxr_adamw_flat_tab_f32(float* p, const float* g, float* m, float* v, int64_t
 /* *counter += delta on the device. */
 int pxr_counter_add_i64(int64_t* counter, int64_t delta, void* stream);
 
+/* ---- LightGCN (model/IDNet/lightgcn.py, layers.py:13-22; csrc/lightgcn.hip) ----------------------------------------------- */
+/* CSR SpMM over the symmetric normalised user-item graph with a fused layer-mean epilogue: s = A x (row_ptr int64 [n_rows+1],
+ * col int32 / w fp32 [nnz], x [n_rows, D]); y = s when y is given; acc_out = (acc_in + s) * scale when acc_out is given (acc_in
+ * may be NULL: 0, and may equal acc_out).  x must not alias y or acc_out.  Rows of more than part_len edges are the n_split rows
+ * split_row[j], cut into parts of part_len edges (parts split_part0[j] .. split_part0[j+1]-1, n_parts in all, part_owner[q] = j)
+ * that are summed in part order: deterministic, no atomics.  A neighbour id outside [0, n_rows) ORs bit 0 into the status word
+ * (clamped).  D % 4 == 0, D <= 2048.  ws: pxr_lgcn_spmm_ws_bytes(n_parts, D). */
+int64_t pxr_lgcn_spmm_ws_bytes(int64_t n_parts, int D);
+int pxr_lgcn_spmm_f32(const int64_t* row_ptr, const int32_t* col, const float* w, int64_t n_rows, int D,
+                      const int32_t* split_row, const int32_t* split_part0, int n_split, const int32_t* part_owner,
+                      int n_parts, int part_len, const float* x, float* y, const float* acc_in, float* acc_out,
+                      float scale, void* ws, int64_t ws_bytes, void* stream);
+/* Pair loss head (lightgcn.py:70-78) on E_final [n_users + n_items, D] (users first): x_b = <u_b, i+_b> - <u_b, i-_b> with
+ * user[b] and item[b, 0..1] = (positive, negative); lossrow[b] = -(1e-8 + log sigmoid(x_b)), loss = mean, coef[b] =
+ * d loss / d x_b = -(1 - sigmoid(x_b)) / B, nodes[3b..3b+2] = the three row ids (int32).  Ids outside [0, n_users) /
+ * [0, n_items) OR bit 0 into the status word (clamped). */
+int pxr_lgcn_pair_fwd_f32(const float* emb, int64_t n_users, int64_t n_items, int D, const int64_t* user,
+                          const int64_t* item, int B, float* diff, float* coef, float* lossrow, int32_t* nodes,
+                          float* loss, void* stream);
+/* Its backward: grad [n_nodes, D] is zeroed, then every row the batch touched gets the sum of its contributions in occurrence
+ * order (deterministic when users and items repeat); upstream d(loss) = grad_scale * (*grad_scale_dev if given). */
+int pxr_lgcn_pair_bwd_f32(const float* emb, int64_t n_nodes, int D, const int32_t* nodes, const float* coef, int B,
+                          float grad_scale, const float* grad_scale_dev, float* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,9 +67,25 @@ class Data:
         self.user_seq = {int(uids[g]): sorted_items[starts[g]:starts[g] + counts[g]] for g in range(len(uniq))}
         self._uids, self._starts, self._counts, self._sorted_items = uids, starts, counts, sorted_items
 
+        if self.config["MODEL_INPUT_TYPE"] == InputType.PAIR:
+            self.train_feat = self._build_pair()
+            return
         if self.config["MODEL_INPUT_TYPE"] not in (InputType.SEQ, None):
-            raise NotImplementedError("only InputType.SEQ (SASRec family) is built on this path")
+            raise NotImplementedError("only InputType.SEQ (SASRec family) and InputType.PAIR (LightGCN) are built on this path")
         self.train_feat = self._build_seq()
+
+    def _build_pair(self):
+        """dataload.py:80-83 without the window step: every user's interactions but the last two, users in first-appearance
+        order, time order inside a user -- one (user, item) training pair each."""
+        keep = np.maximum(self._counts - 2, 0)
+        first = np.repeat(self._starts, keep)
+        within = np.arange(int(keep.sum()), dtype=np.int64) - np.repeat(np.cumsum(keep) - keep, keep)
+        return {"user_id": np.repeat(self._uids, keep).astype(np.int64),
+                "item_id": self._sorted_items[first + within].astype(np.int64)}
+
+    def get_norm_adj_csr(self):
+        """The normalised graph of dataload.py:318-339 as CSR (row_ptr int64, col int32, w fp32): see norm_adj_csr."""
+        return norm_adj_csr(self.train_feat[self.uid_field], self.train_feat[self.iid_field], self.user_num, self.item_num)
 
     def _build_seq(self):
         W = self.config["MAX_ITEM_LIST_LENGTH"] + 1
@@ -101,3 +117,24 @@ class Data:
                           f"The sparsity of the dataset: {self.sparsity * 100}%"])
 
     __repr__ = __str__
+
+
+def norm_adj_csr(users, items, user_num: int, item_num: int):
+    """get_norm_adj_mat (dataload.py:318-339) as CSR over nodes users 0..U-1, items U..U+I-1: every training pair in both
+    directions (duplicates stay separate edges), rows = source nodes, edges of a row in edge_index order;
+    w = d_src^-1/2 d_dst^-1/2 with d = edges by source (a degree of 0 counts as 1), in fp32 like the reference's tensors.
+    -> (row_ptr int64 [U+I+1], col int32 [2n], w fp32 [2n])."""
+    u = np.asarray(users, dtype=np.int64)
+    i = np.asarray(items, dtype=np.int64) + user_num
+    n = user_num + item_num
+    if n >= (1 << 31):
+        raise ValueError("norm_adj_csr: more than 2^31 nodes")
+    src = np.concatenate([u, i])
+    dst = np.concatenate([i, u])
+    deg = np.bincount(src, minlength=n).astype(np.float32)
+    norm = np.float32(1.0) / np.sqrt(np.where(deg == 0, np.float32(1.0), deg))
+    w = norm[src] * norm[dst]
+    order = np.argsort(src, kind="stable")
+    row_ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(src, minlength=n), out=row_ptr[1:])
+    return row_ptr, dst[order].astype(np.int32), w[order].astype(np.float32)

@@ -293,3 +293,68 @@ class SeqEvalBatcher:
             item_seq = np.where(ok, self.flat[np.where(ok, start[:, None] + src, 0)], 0)
             yield (torch.from_numpy(item_seq), (torch.from_numpy(hist_u), torch.from_numpy(hist_i)),
                    torch.arange(len(u)), torch.from_numpy(target))
+
+
+class PairTrainBatcher:
+    """Vectorised PairTrainDataset (reference REC/data/dataset/trainset.py:171-198) under torch's DistributedSampler order: one
+    sample per training interaction, yielded as whole (user int64 [B], item int64 [B, 2] = (positive, negative)) batches.  The
+    negative is uniform over [1, item_num - 1] and redrawn while it lies in the user's training history user_seq[user][:-2] --
+    the reference's distribution, not its random stream.  The sample order and the split by rank are SeqTrainBatcher's."""
+
+    def __init__(self, config, dataload, rank=0, world=1, seed=0, drop_last=False):
+        self.dataload = dataload
+        self.item_num = dataload.item_num
+        self.batch_size = config["train_batch_size"]
+        self.users = np.asarray(dataload.train_feat["user_id"], dtype=np.int64)
+        self.items = np.asarray(dataload.train_feat["item_id"], dtype=np.int64)
+        self.n = len(self.users)
+        # membership keys user * item_num + item of every training interaction (= every user's user_seq[:-2]), sorted
+        self._keys = np.unique(self.users * self.item_num + self.items)
+        # a user whose history covers every candidate would loop forever in the reference: refuse up front
+        hist = np.bincount(self._keys // self.item_num)
+        if self.item_num <= 1 or (hist >= self.item_num - 1).any():
+            raise ValueError("PairTrainBatcher: a user has interacted with every item: no negative can be drawn")
+        self.rank, self.world, self.seed, self.epoch = rank, world, seed, 0
+        self.num_samples = -(-self.n // world)
+        self.drop_last = drop_last
+        self.neg_seed = int(config["seed"] or 0)
+
+    set_epoch = SeqTrainBatcher.set_epoch
+    __len__ = SeqTrainBatcher.__len__
+    _indices = SeqTrainBatcher._indices
+
+    def in_history(self, user, item):
+        """bool array: item[k] is in user[k]'s training history."""
+        keys = user * self.item_num + item
+        pos = np.minimum(np.searchsorted(self._keys, keys), len(self._keys) - 1)
+        return self._keys[pos] == keys
+
+    def make_batch(self, rows, rng):
+        user = self.users[rows]
+        neg = rng.integers(1, self.item_num, size=len(rows))
+        clash = self.in_history(user, neg)
+        while clash.any():
+            neg[clash] = rng.integers(1, self.item_num, size=int(clash.sum()))
+            clash = self.in_history(user, neg)
+        return user, np.stack((self.items[rows], neg), axis=1)
+
+    def __iter__(self):
+        idx = self._indices()
+        rng = np.random.default_rng([self.neg_seed, self.epoch, self.rank])
+        for b in range(len(self)):
+            user, item = self.make_batch(idx[b * self.batch_size:(b + 1) * self.batch_size], rng)
+            yield torch.from_numpy(user), torch.from_numpy(item)
+
+
+class PairEvalBatcher(SeqEvalBatcher):
+    """PairEvalDataset (reference evalset.py:41-66) through SeqEvalBatcher: the same users, histories and targets (valid:
+    [:-2] / [-2], test: [:-1] / [-1]), with the user ids in place of the item windows:
+    `(user [b], (history_u, history_i), positive_u [b], item_target [b])`."""
+
+    def __init__(self, config, dataload, phase="valid", rank=0, world=1):
+        super().__init__(config, dataload, phase=phase, rank=rank, world=world)
+        self.uids = np.fromiter(dataload.user_seq.keys(), dtype=np.int64, count=len(dataload.user_seq))
+
+    def __iter__(self):
+        for b0, (_, hist, pos_u, target) in zip(range(0, len(self.users), self.batch_size), super().__iter__()):
+            yield torch.from_numpy(self.uids[self.users[b0:b0 + self.batch_size]]), hist, pos_u, target

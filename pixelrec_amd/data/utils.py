@@ -14,10 +14,11 @@ from torch.utils.data import DataLoader
 
 from ..parallel import world_info
 from .dataload import Data
-from .dataset import BERT4RecTrainBatcher, SeqEvalBatcher, SeqEvalDataset, SeqTrainBatcher, seq_eval_collate
+from .dataset import (BERT4RecTrainBatcher, PairEvalBatcher, PairTrainBatcher, SeqEvalBatcher, SeqEvalDataset, SeqTrainBatcher,
+                      seq_eval_collate)
 
 SUPPORTED = {"SASRec": "SEQ", "MOSASRec": "SEQ", "FSASRec": "SEQ", "GRU4Rec": "SEQ", "NextItNet": "SEQ",
-             "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ"}      # REC/data/utils.py:24-31
+             "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR"}      # REC/data/utils.py:24-31
 
 
 def load_data(config):
@@ -66,6 +67,11 @@ def bulid_dataloader(config, dataload):
     logger = getLogger()
     logger.info(f"[Training]: train_batch_size = [{config['train_batch_size']}]")
     logger.info(f"[Evaluation]: eval_batch_size = [{config['eval_batch_size']}]")
+    if SUPPORTED[model_name] == "PAIR":
+        # PairTrainDataset / PairEvalDataset (REC/data/utils.py:24-31): one sample per training interaction, users scored
+        train_loader = _TrainLoader(PairTrainBatcher(config, dataload, rank=rank, world=world))
+        return (train_loader, PairEvalBatcher(config, dataload, phase="valid", rank=rank, world=world),
+                PairEvalBatcher(config, dataload, phase="test", rank=rank, world=world))
     # BERT4Rec masks its windows (REC/data/utils.py:25: BERT4RecTrainDataset); evaluation is SeqEvalDataset's for both
     batcher = BERT4RecTrainBatcher if model_name == "BERT4Rec" else SeqTrainBatcher
     train_loader = _TrainLoader(batcher(config, dataload, rank=rank, world=world))

@@ -137,6 +137,10 @@ _SIGNATURES = {
     "pxr_attn_planes_supported": (_I, [_I, _I]),
     "pxr_grouped_dw_planes_f32": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "pxr_merge_split_rows_f32": (_I, [_P, _P, _I, _I64, _I64, _I, _I64, _F, _P, _P, _P, _P, _I64, _P]),
+    "pxr_lgcn_spmm_ws_bytes": (_I64, [_I64, _I]),
+    "pxr_lgcn_spmm_f32": (_I, [_P, _P, _P, _I64, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _F, _P, _I64, _P]),
+    "pxr_lgcn_pair_fwd_f32": (_I, [_P, _I64, _I64, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "pxr_lgcn_pair_bwd_f32": (_I, [_P, _I64, _I, _P, _P, _I, _F, _P, _P, _P]),
 }
 
 

@@ -7,4 +7,5 @@ from .gru4rec import GRU4Rec  # noqa: F401
 from .nextitnet import NextItNet  # noqa: F401
 from .mogru4rec import MOGRU4Rec  # noqa: F401
 from .monextitnet import MONextItNet  # noqa: F401
+from .lightgcn import LightGCN  # noqa: F401
 from .sharded import ShardedDataParallel, ShardedSASRec  # noqa: F401

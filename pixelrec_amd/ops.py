@@ -1728,3 +1728,97 @@ def counter_add(counter, delta=1):
     Lb = _l.load()
     _req(counter, torch.int64, "counter")
     _l.check(Lb.pxr_counter_add_i64(_l.ptr(counter), delta, _l.stream_ptr()), "pxr_counter_add_i64")
+
+
+# ------------------------------------------------------------------------------------------------ LightGCN (csrc/lightgcn.hip)
+class LgcnGraph:
+    """The normalised user-item graph on the device as CSR (row_ptr int64 [n+1], col int32, w fp32), plus the split plan of its
+    long rows: rows of more than `part_len` edges are cut into parts of part_len edges that pxr_lgcn_spmm_f32 sums in part order.
+    The plan is host arithmetic on row_ptr, made once per graph."""
+
+    PART_LEN = 512
+
+    def __init__(self, row_ptr, col, w, device, part_len: int | None = None):
+        import numpy as np
+
+        row_ptr = np.asarray(row_ptr, dtype=np.int64)
+        col = np.asarray(col, dtype=np.int32)
+        w = np.asarray(w, dtype=np.float32)
+        n = len(row_ptr) - 1
+        if n <= 0 or row_ptr[0] != 0 or row_ptr[-1] != len(col) or len(w) != len(col) or (np.diff(row_ptr) < 0).any():
+            raise ValueError("LgcnGraph: not a CSR (row_ptr must start at 0, be non-decreasing and end at nnz = len(col) = len(w))")
+        self.n_rows, self.nnz = n, len(col)
+        self.part_len = int(part_len or self.PART_LEN)
+        deg = np.diff(row_ptr)
+        split = np.nonzero(deg > self.part_len)[0]
+        n_parts = -(-deg[split] // self.part_len)
+        part0 = np.zeros(len(split) + 1, dtype=np.int64)
+        np.cumsum(n_parts, out=part0[1:])
+        if part0[-1] >= (1 << 31):
+            raise ValueError("LgcnGraph: too many parts")
+        self.n_split, self.n_parts = len(split), int(part0[-1])
+        dev = torch.device(device)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        self.row_ptr, self.col, self.w = t(row_ptr), t(col), t(w)
+        self.split_row = t(split.astype(np.int32))
+        self.split_part0 = t(part0.astype(np.int32))
+        self.part_owner = t(np.repeat(np.arange(len(split), dtype=np.int32), n_parts))
+        self.device = dev
+
+    def spmm(self, x, y=None, acc_in=None, acc_out=None, scale=1.0):
+        """s = A x; y = s (if given); acc_out = (acc_in + s) * scale (if given; acc_in None = 0, may be acc_out).  One launch (two
+        when the graph has split rows)."""
+        Lb = _l.load()
+        _req(x, torch.float32, "x")
+        for t, nm in ((y, "y"), (acc_in, "acc_in"), (acc_out, "acc_out")):
+            if t is not None:
+                _req(t, torch.float32, nm)
+                if t.shape != x.shape:
+                    raise _l.PxrError(f"lgcn spmm: {nm} has shape {tuple(t.shape)}, x {tuple(x.shape)}")
+        N, D = x.shape
+        if N != self.n_rows:
+            raise _l.PxrError(f"lgcn spmm: x has {N} rows, the graph {self.n_rows}")
+        device_status(x.device)
+        ws_bytes = int(Lb.pxr_lgcn_spmm_ws_bytes(self.n_parts, D))
+        if ws_bytes < 0:
+            raise _l.PxrError(f"lgcn spmm: D={D} must be a positive multiple of 4")
+        ws = _ws.get(ws_bytes, x.device) if self.n_parts else None
+        _l.check(Lb.pxr_lgcn_spmm_f32(_l.ptr(self.row_ptr), _l.ptr(self.col), _l.ptr(self.w), N, D, _l.ptr(self.split_row),
+                                      _l.ptr(self.split_part0), self.n_split, _l.ptr(self.part_owner), self.n_parts, self.part_len,
+                                      _l.ptr(x), _l.ptr(y), _l.ptr(acc_in), _l.ptr(acc_out), float(scale), _l.ptr(ws), ws_bytes,
+                                      _l.stream_ptr()), "pxr_lgcn_spmm_f32")
+        return y if acc_out is None else acc_out
+
+
+def lgcn_pair_fwd(emb, n_users: int, n_items: int, user, item):
+    """LightGCN's pair loss head (lightgcn.py:70-78) on E_final [n_users + n_items, D]: user int64 [B], item int64 [B, 2] ->
+    (loss [1], diff [B] = x_b, coef [B] = d loss / d x_b, nodes int32 [3B])."""
+    Lb = _l.load()
+    _req(emb, torch.float32, "emb"); _req(user, torch.int64, "user"); _req(item, torch.int64, "item")
+    B = user.numel()
+    if item.numel() != 2 * B:
+        raise _l.PxrError(f"lgcn pair head: item must be [B, 2] for B={B}, got {tuple(item.shape)}")
+    N, D = emb.shape
+    if N != n_users + n_items:
+        raise _l.PxrError(f"lgcn pair head: emb has {N} rows, n_users + n_items = {n_users + n_items}")
+    dev = emb.device
+    f = torch.empty(3 * B + 1, dtype=torch.float32, device=dev)
+    diff, coef, lossrow, loss = f[:B], f[B:2 * B], f[2 * B:3 * B], f[3 * B:]
+    nodes = torch.empty(3 * B, dtype=torch.int32, device=dev)
+    device_status(dev)
+    _l.check(Lb.pxr_lgcn_pair_fwd_f32(_l.ptr(emb), n_users, n_items, D, _l.ptr(user), _l.ptr(item), B, _l.ptr(diff), _l.ptr(coef),
+                                      _l.ptr(lossrow), _l.ptr(nodes), _l.ptr(loss), _l.stream_ptr()), "pxr_lgcn_pair_fwd_f32")
+    return loss, diff, coef, nodes
+
+
+def lgcn_pair_bwd(emb, nodes, coef, grad, grad_scale=1.0, grad_scale_dev=None):
+    """grad [n, D] (overwritten) = d loss / d E_final of lgcn_pair_fwd, scaled by grad_scale * (*grad_scale_dev)."""
+    Lb = _l.load()
+    _req(emb, torch.float32, "emb"); _req(grad, torch.float32, "grad"); _req(nodes, torch.int32, "nodes")
+    _req(coef, torch.float32, "coef")
+    if grad.shape != emb.shape:
+        raise _l.PxrError("lgcn pair head backward: grad must have emb's shape")
+    N, D = emb.shape
+    _l.check(Lb.pxr_lgcn_pair_bwd_f32(_l.ptr(emb), N, D, _l.ptr(nodes), _l.ptr(coef), coef.numel(), float(grad_scale),
+                                      _l.ptr(grad_scale_dev), _l.ptr(grad), _l.stream_ptr()), "pxr_lgcn_pair_bwd_f32")
+    return grad

@@ -73,7 +73,7 @@ def native_to_torch_state(sd, model, first_index=0):
     state = {}
     if step > 0:     # torch creates a parameter's state at its first step
         for j, name in enumerate(names):
-            if name == "item_embedding.weight":
+            if name == "item_embedding.weight" and has_item_table(model):
                 m, v = sd["table_m"], sd["table_v"]
             else:
                 off, n, shape = model._views[_short_name(name, model)]
@@ -101,7 +101,7 @@ def torch_to_native_state(sd, model, group_index=-1):
         if st is None:
             continue
         steps.add(int(float(st["step"])))
-        if name == "item_embedding.weight":
+        if name == "item_embedding.weight" and has_item_table(model):
             out["table_m"], out["table_v"] = st["exp_avg"], st["exp_avg_sq"]
             continue
         off, n, shape = model._views[_short_name(name, model)]
