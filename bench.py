@@ -9,12 +9,14 @@ train_batch_size, overall/ID.yaml:19).  Synthetic ids: Zipf(1.0) positives throu
 negatives, ~30 % left-padded sequences.
 
   python bench.py [--gpus N --steps K --warmup W]          # N>1 is launched by torch.distributed.run
+  python bench.py --full [...]                             # ... and everything measured beside the headline
 
-Prints ONE JSON line on rank 0 (see the task contract): value = whole-job sequences/s; `roofline` = the dominant
-kernel of the step -- the fp32-MFMA GEMM kernel behind every nn.Linear forward/backward (22 launches, ~60 % of the
-step's GPU time; MFMA-bound) -- `cpu_baseline` = the CPU oracle (plain PyTorch fp32 restatement of the reference step)
-timed on this host, plus extra roofline objects for the north-star targets (embedding gather GB/s, full-catalog
-scoring GEMM MFMA utilisation) and for the dense AdamW table sweep that the default lazy optimizer avoids.
+Prints ONE JSON line on rank 0: value = whole-job sequences/s.  A plain run sets up, ages the optimizer, warms up, times
+the K steps, writes --dump-outputs and prints the line -- nothing else.  --full goes on after the timed steps: `roofline`
+= the dominant kernel of the step -- the fp32-MFMA GEMM kernel behind every nn.Linear forward/backward (22 launches,
+~60 % of the step's GPU time; MFMA-bound) -- `cpu_baseline` = the CPU oracle (plain PyTorch fp32 restatement of the
+reference step) timed on this host, plus extra roofline objects for the north-star targets (embedding gather GB/s,
+full-catalog scoring GEMM MFMA utilisation) and for the dense AdamW table sweep that the default lazy optimizer avoids.
 """
 import argparse
 import json
@@ -213,6 +215,26 @@ OPERANDS_B3 = "bf16x3_six_products"
 OPERANDS_H2 = "fp16_two_plane_three_products"
 
 
+def operand_fields(b3, h2):
+    """`operands` / `arithmetic` of the IDNet line: b3 = GEMM mode bf16x3, h2 = the step's GEMMs ran on fp16 two-plane operands."""
+    return {
+        "operands": ((OPERANDS_H2 if h2 else OPERANDS_B3) if b3 else "f32_input_mfma"),
+        "arithmetic": ("fp32 storage and accumulation everywhere; GEMM operands as TWO fp16 planes with a power-of-two scale (22 "
+                       "significant bits; three MFMA products per multiply: hi*hi + lo*hi + hi*lo).  Per GEMM of this step no further "
+                       "from fp64 than the f32-input MFMA (PXR_GEMM_MODE=f32, the reference's arithmetic class): 0.62-1.02 x its error; a "
+                       "40-step AdamW trajectory as close to the f32 mode's as the six-product path's (tests/test_gpu_h2.py::"
+                       "test_every_gemm_of_the_step_on_h2_is_no_further_from_fp64_than_the_f32_input_mfma, "
+                       "::test_forty_adamw_steps_on_h2_stay_as_close_to_the_f32_mode_as_the_six_product_path; against an fp64 trajectory of "
+                       "the same 40 steps the Linear weights end 1.8e-8 rms away on these operands, 2.8e-8 on the f32-input MFMA "
+                       "(::test_forty_adamw_steps_against_an_fp64_trajectory_h2_is_no_further_than_the_f32_input_mfma, table in DESIGN.md 2; "
+                       "profiles/r05/h2_evidence.log).  The six-product figure of the same run: `six_products` (--full).  Attention, "
+                       "LayerNorm, loss, optimizer in fp32" if (b3 and h2) else
+                       "fp32 storage and accumulation everywhere; GEMM products on the bf16 matrix pipe after an exact split of "
+                       "each fp32 operand into 3 bf16 terms (6 of 9 cross products: error ~2^-25 |a||b| per product, fp32-class; "
+                       "tests/test_gpu_gemm_b3.py); attention, LayerNorm, loss, optimizer in fp32" if b3 else
+                       "fp32 end to end (f32-input MFMA)")}
+
+
 def world_fields(world):
     """Top-level fields of the JSON line that say how many ranks really ran and over what."""
     return {"rccl_ranks": world, "dist_backend": (dist.get_backend() if dist.is_initialized() else None)}
@@ -296,8 +318,7 @@ def compact_line(out):
 
 def emit(out):
     """Full record -> the side file (PXR_BENCH_EXTRAS, default gpurun_out/bench_extras.json under the repo); compact record -> the
-    last stdout line.  RCCL prints its version banner through C stdio (NCCL_DEBUG=VERSION is exported on the GPU boxes) and that
-    buffer is only flushed at exit: flush it first so the JSON line is the LAST line on stdout."""
+    last stdout line (print_line)."""
     path = os.environ.get("PXR_BENCH_EXTRAS") or os.path.join(ROOT, "gpurun_out", "bench_extras.json")
     try:
         os.makedirs(os.path.dirname(path), exist_ok=True)
@@ -307,6 +328,13 @@ def emit(out):
         out["extras"] = os.path.relpath(path, ROOT)
     except OSError as e:
         out["extras"] = f"not written ({type(e).__name__})"
+    print_line(out)
+
+
+def print_line(out):
+    """Compact record -> the last stdout line (a plain run prints only this).  RCCL prints its version banner through C stdio
+    (NCCL_DEBUG=VERSION may be exported) and that buffer is only flushed at exit: flush it first so the JSON line is the LAST
+    line on stdout."""
     import ctypes
     ctypes.CDLL(None).fflush(None)
     text = json.dumps(compact_line(out))
@@ -351,17 +379,18 @@ def dump_outputs(path, loss, model, write=True):
 
 
 def pixelnet_main(args):
-    out = pixelnet_run(args, args.steps, max(args.warmup, 2))
+    out = pixelnet_run(args, args.steps, max(args.warmup, 2), full=args.full)
     if out is not None:
-        emit(out)
+        (emit if args.full else print_line)(out)
     if dist.is_initialized():
         dist.destroy_process_group()
 
 
-def pixelnet_run(args, steps, warmup, init_dist=True, n_inst=3):
+def pixelnet_run(args, steps, warmup, init_dist=True, n_inst=3, full=True):
     """BASELINE configs[2] / [4]: one training step of MOSASRec (reference mosasrec.py:66-93) with the image encoder
     trained end to end (blocks >= tune_scale; reference load.py:90-120), both optimizer groups (trainer.py:74-96).
-    Synthetic images already resident in HBM as fp32 pixel tensors; random-init weights of the named architecture."""
+    Synthetic images already resident in HBM as fp32 pixel tensors; random-init weights of the named architecture.
+    `full`: after the timed steps, instrumented eager steps for the GEMM roofline, the phases and `operands`."""
     from pixelrec_amd import ops
     from pixelrec_amd.model import MOSASRec
     from pixelrec_amd.model.visual import ENCODER_SHAPES
@@ -455,15 +484,16 @@ def pixelnet_run(args, steps, warmup, init_dist=True, n_inst=3):
     dump_dir = getattr(args, "dump_outputs", None) if init_dist else None
     dumped = dump_outputs(dump_dir, loss, m, write=rank == 0) if dump_dir else None
     # GEMM family of the step (ViT blocks + sequence block): HIP events around every launch of a few extra steps
+    # (--full only, like the phases below: a plain run ends with its timed steps)
     ev = []
     ops.GEMM_TIMING = ev
-    n_inst = min(steps, n_inst)
+    n_inst = min(steps, n_inst) if full else 0
     for i in range(n_inst):
         eager_step(i)
     ops.GEMM_TIMING = None
     torch.cuda.synchronize()
     # where a step's device time goes (events on the compute stream around the four host-level phases of `step`)
-    ph_acc, n_ph = {}, min(steps, 3)
+    ph_acc, n_ph = {}, min(steps, 3) if full else 0
     for i in range(n_ph):
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
         marks[0].record()
@@ -523,6 +553,9 @@ def pixelnet_run(args, steps, warmup, init_dist=True, n_inst=3):
                                           "`bench.py --model pixelnet` on this round's ping-pong tiles; NOT measured in this run)",
                         "note": "HIP events around every GEMM launch of extra eager steps (sum of durations; one stream)"},
            "cpu_baseline": None}
+    if not full:        # nothing was instrumented
+        for k in ("operands", "data_parallel_phases", "roofline"):
+            del out[k]
     del m, dp, opt, pool, gstep
     torch.cuda.empty_cache()
     return out
@@ -534,12 +567,17 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=64, help="sequences per GPU per step (reference: 64)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the gather / scoring roofline micro-runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure everything else: spread blocks, the six-product twin, the GEMM roofline "
+                         "(instrumented eager steps), lazy-schedule figures, the extras of bench_extras.py and the CPU baseline; "
+                         "writes the full record to a side file.  A plain run (the default) only sets up, warms up, times the "
+                         "steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the spread blocks and the extra measurement runs")
     ap.add_argument("--no-overlap", action="store_true", help="weight gradients on the main stream (A/B knob)")
     ap.add_argument("--no-group", action="store_true", help="per-layer weight-gradient GEMMs instead of one grouped launch")
     ap.add_argument("--no-graph", action="store_true", help="issue the step eagerly instead of replaying a hipGraph")
-    ap.add_argument("--no-gemm-events", action="store_true", help="do not bracket GEMM launches with HIP events")
+    ap.add_argument("--no-gemm-events", action="store_true", help="--full: do not bracket GEMM launches with HIP events")
     ap.add_argument("--clock-ramp-s", type=float, default=0.0, help="seconds of extra untimed steps before the warm-up")
     ap.add_argument("--age-steps", type=int, default=600,
                     help="untimed steps on DISTINCT batches before the warm-up: they bring the lazily updated table rows "
@@ -567,7 +605,7 @@ def main():
     ap.add_argument("--no-graph-collectives", action="store_true",
                     help="data parallel: issue the step eagerly instead of replaying a hipGraph that contains the RCCL collectives")
     ap.add_argument("--emulate-world", type=int, default=0,
-                    help="after the run, project the step of a W-rank data-parallel job on this ONE GPU: merge of W ranks' "
+                    help="--full: after the run, project the step of a W-rank data-parallel job on this ONE GPU: merge of W ranks' "
                          "sparse-gradient blocks + the merged row update are measured on a run fed W batches per step, the "
                          "collectives are modelled from bytes and a stated xGMI link rate (tools/world_projection.py)")
     ap.add_argument("--model", choices=("idnet", "pixelnet"), default="idnet",
@@ -579,6 +617,8 @@ def main():
                          "state_dict() returns them; a fixed seeded sample of the large ones, <= 64 MB in all) as DIR/<name>.npy. "
                          "The table is brought current there, so the untimed measurements after it start from a flushed table")
     args = ap.parse_args()
+    if args.emulate_world > 1 and not args.full:
+        ap.error("--emulate-world is a measurement beside the headline: add --full")
     launch_ranks(args)
     if args.model == "pixelnet":
         return pixelnet_main(args)
@@ -622,25 +662,31 @@ def main():
     n_inst_plan = 0 if args.no_gemm_events else min(args.steps, 20)
     n_spread = 0 if args.no_extras else 4          # extra blocks of --steps steps timed like the official one (box / clock spread)
     n_stream = min(args.age_steps + 2 * args.warmup + (2 + n_spread) * args.steps + n_inst_plan + 40, 4096)
+    # two collectives with fewer rows pay off when the volume dominates the exchange (W x rows per rank received); at 1-2
+    # ranks the extra collective costs more than the bytes it saves (1-rank RCCL group: 1.273 vs 1.249 ms/step)
+    want_split = args.split_exchange or (world >= 4 and not args.full_exchange)
+    split = (world > 1 or args.force_collectives) and want_split and not args.table_sharding
+    # a plain run draws only the batches its own steps consume (+ the look-ahead's): the stream is drawn in order, so these are
+    # the same batches, and it still wraps at n_stream.  The split exchange's row bound is taken over the whole stream
+    n_draw = n_stream
+    if not (args.full or split or args.clock_ramp_s > 0):
+        n_draw = min(n_stream, args.age_steps + args.warmup + args.steps + 1)
     t_gen = time.perf_counter()
-    its, mks = zip(*(synth.train_batch(N, B, L, rng, zipf) for _ in range(n_stream)))
+    its, mks = zip(*(synth.train_batch(N, B, L, rng, zipf) for _ in range(n_draw)))
     # a rigorous bound on the unique table rows any batch of THIS stream touches: the row capacity of the data-parallel
     # exchange (GradSync(exchange_rows=...)); all ranks agree on the maximum once, before the first step
     max_unique = max(int(np.count_nonzero(np.unique(it))) for it in its)
     # every batch is ONE packed int64 row (ids | mask), the two tensors are views of it: the graphed step copies a batch
     # into its static buffer with one copy (pixelrec_amd/graph.py)
     n_it = its[0].size
-    packed_all = torch.from_numpy(np.concatenate([np.stack(its).reshape(n_stream, -1),
-                                                  np.stack(mks).reshape(n_stream, -1).astype(np.int64)], axis=1)).to(dev)
+    packed_all = torch.from_numpy(np.concatenate([np.stack(its).reshape(n_draw, -1),
+                                                  np.stack(mks).reshape(n_draw, -1).astype(np.int64)], axis=1)).to(dev)
     items_shape, mask_shape = its[0].shape, mks[0].shape
     t_gen = time.perf_counter() - t_gen
     del its, mks
 
     exchange_rows = None
-    # two collectives with fewer rows pay off when the volume dominates the exchange (W x rows per rank received); at 1-2
-    # ranks the extra collective costs more than the bytes it saves (1-rank RCCL group: 1.273 vs 1.249 ms/step)
-    want_split = args.split_exchange or (world >= 4 and not args.full_exchange)
-    if (world > 1 or args.force_collectives) and want_split and not args.table_sharding:
+    if split:
         t_mx = torch.tensor([max_unique], dtype=torch.int64, device=dev)
         dist.all_reduce(t_mx, op=dist.ReduceOp.MAX)
         exchange_rows = min(B * (2 * L + 1), (int(t_mx.item()) + 255) // 256 * 256)
@@ -788,6 +834,33 @@ def main():
         dt = float(t.item())
     final_loss = float(loss.detach())
     dumped = dump_outputs(args.dump_outputs, loss, model, write=rank == 0) if args.dump_outputs else None
+    b3 = ops.gemm_mode() == "bf16x3"
+    out = {
+        "metric": (f"user-sequences/sec at emb={D} seq_len={L} (SASRec IDNet training step: fwd+bwd+AdamW)" if custom else
+                   "user-sequences/sec at emb=512 seq_len=50 (SASRec IDNet training step: fwd+bwd+AdamW)"),
+        "value": world * B * args.steps / dt, "unit": "sequences/s", "n_gpus": world, **world_fields(world), "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        # (the model's own switch; --full replaces it with what the instrumented launches ran)
+        **operand_fields(b3, b3 and bool(getattr(model, "_h2_on", lambda b_: False)(B))),
+        "config": {"workload": (f"custom shape (NOT the headline config): SASRec IDNet emb={D} seq_len={L}, {N} items, "
+                                f"{NS['H']} heads, inner 2x, 2 layers" if custom else
+                                "BASELINE.json configs[1]: SASRec IDNet emb=512 seq_len=50, 400001 items, 4 heads, "
+                                "inner 2x, 2 layers, BPR loss vs 1 sampled negative, dropout 0.1, AdamW lr 1e-4 wd 0.1"),
+                   "batch_per_gpu": B, "global_batch": world * B, "seq_len": L, "n_items": N, "embedding_size": D,
+                   "parallelism": f"dp{world}" + ("+row-sharded-table" if args.table_sharding else ""),
+                   "hip_graph": bool(use_graph), **({"hip_graph_error": graph_err} if graph_err else {})},
+        "final_loss": final_loss, "host_enqueue_ms_per_step": t_enqueued / args.steps * 1e3, "h2_stale_overflows": stale_overflows[0],
+        **({"dumped_outputs": dumped} if dumped else {}),
+    }
+    if not args.full:
+        # a plain run ends with its timed steps: the line carries the headline and nothing measured beside it
+        if rank == 0:
+            print_line(out)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
+    # ---- --full: everything below is measured after (and beside) the headline ----------------------------------------------
     # the same K steps four more times (continuing the batch stream), each block bracketed like the official one: what one run can
     # say about the spread of its own number (boxes of the pool differ by a few percent, clocks move).
     # `value` / `ms_per_step` stay the FIRST block -- the contract's timed region.
@@ -951,7 +1024,6 @@ def main():
             traffic = json.load(open(tr_file)).get("hbm_bytes_per_launch")
         except Exception:
             traffic = None
-    b3 = ops.gemm_mode() == "bf16x3"
     planes_on = bool(b3 and getattr(model, "_planes_on", lambda: False)())
     # the same family in the committed rocprofv3 --kernel-trace --stats summary of this command (tools/r05_session.sh prof): kernel
     # durations without the event pair's launch gap -- what `avg_kernel_us` has to agree with (read from the file, not measured here)
@@ -1005,36 +1077,9 @@ def main():
                     "TFLOP/s in f32 mode); `algorithmic_tflops` is the fp32-equivalent rate; `traffic`: see `traffic_source`"}
     hbm_kernels = per_tag(other_events, 1e9, "gbs")
 
-    out = {
-        "metric": (f"user-sequences/sec at emb={D} seq_len={L} (SASRec IDNet training step: fwd+bwd+AdamW)" if custom else
-                   "user-sequences/sec at emb=512 seq_len=50 (SASRec IDNet training step: fwd+bwd+AdamW)"),
-        "value": world * B * args.steps / dt, "unit": "sequences/s", "n_gpus": world, **world_fields(world), "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "operands": ((OPERANDS_H2 if g_h2 else OPERANDS_B3) if b3 else "f32_input_mfma"),
-        "arithmetic": ("fp32 storage and accumulation everywhere; GEMM operands as TWO fp16 planes with a power-of-two scale (22 "
-                       "significant bits; three MFMA products per multiply: hi*hi + lo*hi + hi*lo).  Per GEMM of this step no further "
-                       "from fp64 than the f32-input MFMA (PXR_GEMM_MODE=f32, the reference's arithmetic class): 0.62-1.02 x its error; a "
-                       "40-step AdamW trajectory as close to the f32 mode's as the six-product path's (tests/test_gpu_h2.py::"
-                       "test_every_gemm_of_the_step_on_h2_is_no_further_from_fp64_than_the_f32_input_mfma, "
-                       "::test_forty_adamw_steps_on_h2_stay_as_close_to_the_f32_mode_as_the_six_product_path; against an fp64 trajectory of "
-                       "the same 40 steps the Linear weights end 1.8e-8 rms away on these operands, 2.8e-8 on the f32-input MFMA "
-                       "(::test_forty_adamw_steps_against_an_fp64_trajectory_h2_is_no_further_than_the_f32_input_mfma, table in DESIGN.md 2; "
-                       "profiles/r05/h2_evidence.log).  The six-product figure of the same run: `six_products`.  Attention, "
-                       "LayerNorm, loss, optimizer in fp32" if (b3 and g_h2) else
-                       "fp32 storage and accumulation everywhere; GEMM products on the bf16 matrix pipe after an exact split of "
-                       "each fp32 operand into 3 bf16 terms (6 of 9 cross products: error ~2^-25 |a||b| per product, fp32-class; "
-                       "tests/test_gpu_gemm_b3.py); attention, LayerNorm, loss, optimizer in fp32" if b3 else
-                       "fp32 end to end (f32-input MFMA)"),
-        "config": {"workload": (f"custom shape (NOT the headline config): SASRec IDNet emb={D} seq_len={L}, {N} items, "
-                                f"{NS['H']} heads, inner 2x, 2 layers" if custom else
-                                "BASELINE.json configs[1]: SASRec IDNet emb=512 seq_len=50, 400001 items, 4 heads, "
-                                "inner 2x, 2 layers, BPR loss vs 1 sampled negative, dropout 0.1, AdamW lr 1e-4 wd 0.1"),
-                   "batch_per_gpu": B, "global_batch": world * B, "seq_len": L, "n_items": N, "embedding_size": D,
-                   "parallelism": f"dp{world}" + ("+row-sharded-table" if args.table_sharding else ""),
-                   "hip_graph": bool(use_graph), **({"hip_graph_error": graph_err} if graph_err else {})},
-        "final_loss": final_loss, "host_enqueue_ms_per_step": t_enqueued / args.steps * 1e3, "h2_stale_overflows": stale_overflows[0],
-        **({"dumped_outputs": dumped} if dumped else {}),
+    out.update({
+        **operand_fields(b3, g_h2),
+        "h2_stale_overflows": stale_overflows[0],
         "spread": {"blocks": len(block_ms), "steps_per_block": args.steps, "ms_per_step": block_ms,
                    "median_ms_per_step": sorted(block_ms)[len(block_ms) // 2], "min_ms_per_step": min(block_ms),
                    "max_ms_per_step": max(block_ms),
@@ -1043,7 +1088,7 @@ def main():
         "stream": {"distinct_batches": n_stream, "age_steps": args.age_steps, "age_s": t_age, "host_gen_s": t_gen,
                    "repeats_inside_run": bool(stream_repeats), "optimizer_steps_before_timed_region": args.age_steps + args.warmup,
                    "table_update": args.table_update},
-    }
+    })
     if six is not None:
         out["six_products"] = six
     if phases is not None:

@@ -1,5 +1,5 @@
-"""bench_extras.py -- everything `python bench.py` measures BESIDE the contract's timed region (run after it, on rank 0 of a 1-GPU run,
-skipped with --no-extras): the same step at throughput-oriented batch sizes on both arithmetics, the HBM copy rate of the box, the
+"""bench_extras.py -- everything `python bench.py --full` measures BESIDE the contract's timed region (run after it, on rank 0 of a
+1-GPU run, skipped with --no-extras): the same step at throughput-oriented batch sizes on both arithmetics, the HBM copy rate of the box, the
 north-star kernel rooflines (embedding gather standalone and as run, full-catalogue scoring literal / fused / default), the dense AdamW
 sweep, what the lazy table schedule costs against it, the PixelNet step (BASELINE configs[2]) and the review targets.  All of it lands in
 the full record (the side file bench.py names in `extras`); the one-line stdout record only carries a digest (bench.compact_line).

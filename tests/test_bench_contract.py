@@ -298,3 +298,33 @@ def test_dump_outputs_flag_is_parsed(monkeypatch):
     except Parsed as e:
         args = e.args[0]
     assert args.dump_outputs == "out_dir" and args.steps == 3
+
+
+def _parsed(monkeypatch, argv):
+    b = _bench_module()
+
+    class Parsed(Exception):
+        pass
+
+    def stop(args):
+        raise Parsed(args)
+
+    monkeypatch.setattr(b, "launch_ranks", stop)
+    monkeypatch.setattr(b.sys, "argv", ["bench.py", *argv])
+    try:
+        b.main()
+    except Parsed as e:
+        return e.args[0]
+    raise AssertionError("bench.main() did not reach launch_ranks")
+
+
+def test_a_plain_run_is_the_default_and_full_is_opt_in(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` is the plain run (headline only); whatever else it measures is behind --full."""
+    import pytest
+    assert _parsed(monkeypatch, ["--gpus", "1", "--steps", "5", "--warmup", "2"]).full is False
+    args = _parsed(monkeypatch, ["--full", "--emulate-world", "8"])
+    assert args.full is True and args.emulate_world == 8
+    with pytest.raises(SystemExit) as e:                 # a projection beside the headline is a --full measurement
+        _parsed(monkeypatch, ["--emulate-world", "8"])
+    assert e.value.code == 2
+
