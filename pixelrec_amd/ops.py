@@ -1155,8 +1155,9 @@ ATTN_FUSED_MAX_L = 128     # sequences beyond this take the batched-GEMM path be
 
 def _attn_takes_gemm_path(L, d):
     """Beyond 128 positions -- or 65..128 with a head size that is not a multiple of 8, which the two-keys-per-lane fused
-    kernels need -- the attention runs as batched GEMMs + the row kernel (any length, head size % 4 == 0)."""
-    return L > ATTN_FUSED_MAX_L or (L > 64 and d % 8 != 0)
+    kernels need, or with the MFMA kernels turned off (PXR_ATTN_MFMA=0: attn_planes_supported(1, 8) is false exactly then) --
+    the attention runs as batched GEMMs + the row kernel (any length, head size % 4 == 0)."""
+    return L > ATTN_FUSED_MAX_L or (L > 64 and (d % 8 != 0 or not attn_planes_supported(1, 8)))
 
 
 def _attn_long_fwd(qkv, keymask, km_bstride, B, H, L, d, p_drop, seed, stream_id, step_dev, causal=True):
