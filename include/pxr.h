@@ -602,6 +602,43 @@ int pxr_lgcn_pair_fwd_f32(const float* emb, int64_t n_users, int64_t n_items, in
 int pxr_lgcn_pair_bwd_f32(const float* emb, int64_t n_nodes, int D, const int32_t* nodes, const float* coef, int B,
                           float grad_scale, const float* grad_scale_dev, float* grad, void* stream);
 
+/* ---- SRGNN (model/IDNet/srgnn.py, collate_fn.py graph_train_collate; csrc/srgnn.hip) ----------------------------------------- */
+/* Session graphs built on the device at a FIXED size of L nodes (the collate pads to the batch's largest node count): one wave per
+ * sequence seq [B, L] (right-padded with 0).  nodes [B, L] = the distinct ids ascending (0 included when padded), then 0;
+ * alias [B, L] = node index of seq[b, t]; A [B, L, 2L] = [A_in | A_out] with A_in[v][u] = e(u,v) / indeg(v), A_out[u][v] =
+ * e(u,v) / outdeg(u) (a degree of 0 counts as 1), edges seq[i] -> seq[i+1] until the next id is 0, a repeat counted once.
+ * Optional: occ [B, 3L] = nodes | target[b,0], 0.. | target[b,1], 0.. (the id rows of pxr_seq_occ_sort with layout (3L, 0, L,
+ * 2L); needs target [B, 2]); mask [B, L] = seq != 0.  An id outside [0, n_items) ORs bit 0 into the status word (clamped).
+ * 1 <= L <= 64. */
+int pxr_srgnn_graph_i64(const int64_t* seq, int64_t B, int L, int64_t n_items, const int64_t* target, int64_t* nodes,
+                        int32_t* alias, float* A, int64_t* occ, int64_t* mask, void* stream);
+/* One workgroup per session, A in LDS; x, y [B*L, 2D].  transpose 0: y[v] = [sum_u A_in[v][u] x[u, :D] | sum_u A_out[v][u]
+ * x[u, D:]] + bias (bias [2D] or NULL); transpose 1 (the backward, no bias): y[u] = [sum_v A_in[v][u] x[v, :D] | sum_v
+ * A_out[v][u] x[v, D:]].  Sums in ascending node order.  D % 4 == 0, D <= 2048, L <= 64. */
+int pxr_srgnn_prop_f32(const float* A, int B, int L, int D, const float* x, float* y, const float* bias, int transpose,
+                       void* stream);
+/* Readout (srgnn.py seq_modeling after the GNN), one workgroup per session.  Hn [B*L, D] node states, P [B*L, 2D] = [Hn W1^T
+ * + b1 | Hn W2^T + b2]; position t reads node alias[b, t]; last = sum(mask[b]) - 1 (an empty history wraps to L-1 like torch
+ * indexing).  s_t = sigmoid(P1[last node] + P2[alias t]), alpha_t = <w3, s_t>, cat [B, 2D] = [sum_t alpha_t sh_t mask_t | ht].
+ * sig [B, L, D] / alpha [B, L] are saved for the backward (may be NULL for inference). */
+int pxr_srgnn_readout_fwd_f32(const float* Hn, const float* P, const int32_t* alias, const int64_t* mask, const float* w3,
+                              int B, int L, int D, float* cat, float* sig, float* alpha, void* stream);
+/* Its backward from dcat [B, 2D]: dP [B*L, 2D], dH [B*L, D] (the direct paths into the node states) and dw3p [B, D] (per-session
+ * parts of d w3, reduced by pxr_colsum_f32).  A node's sums run over its positions in ascending order: no atomics. */
+int pxr_srgnn_readout_bwd_f32(const float* dcat, const float* Hn, const int32_t* alias, const int64_t* mask, const float* w3,
+                              const float* sig, const float* alpha, int B, int L, int D, float* dP, float* dH, float* dw3p,
+                              void* stream);
+/* Pair loss head (srgnn.py:60-66): x_b = <out_b, e[target b,0]> - <out_b, e[target b,1]> with out rows ld_out floats apart;
+ * lossrow[b] = -(1e-8 + log sigmoid(x_b)), loss = mean, coef[b] = -(1 - sigmoid(x_b)) / B.  Ids outside [0, n_table) OR bit 0
+ * into the status word (clamped). */
+int pxr_srgnn_pair_fwd_f32(const float* out, int64_t ld_out, const float* table, int64_t n_table, int D, const int64_t* target,
+                           int B, float* lossrow, float* coef, float* loss, void* stream);
+/* Its backward: c_b = coef[b] * grad_scale * (*grad_scale_dev if given); dout[b] = c_b (e[pos] - e[neg]) (rows ld_dout apart);
+ * coef_out[b * coef_stride] = c_b (optional) for the target rows' gradient in pxr_sasrec_occ_segsum. */
+int pxr_srgnn_pair_bwd_f32(const float* table, int64_t n_table, int D, const int64_t* target, const float* coef, int B,
+                           float grad_scale, const float* grad_scale_dev, float* dout, int64_t ld_dout, float* coef_out,
+                           int64_t coef_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,8 +70,12 @@ class Data:
         if self.config["MODEL_INPUT_TYPE"] == InputType.PAIR:
             self.train_feat = self._build_pair()
             return
+        if self.config["MODEL_INPUT_TYPE"] == InputType.AUGSEQ:
+            self.train_feat = self._build_aug_seq()
+            return
         if self.config["MODEL_INPUT_TYPE"] not in (InputType.SEQ, None):
-            raise NotImplementedError("only InputType.SEQ (SASRec family) and InputType.PAIR (LightGCN) are built on this path")
+            raise NotImplementedError("only InputType.SEQ (SASRec family), InputType.PAIR (LightGCN) and InputType.AUGSEQ (SRGNN) "
+                                      "are built on this path")
         self.train_feat = self._build_seq()
 
     def _build_pair(self):
@@ -105,6 +109,33 @@ class Data:
                 uid_list.append(self._uids[g])
                 seqs.append(hist)
         return {"user_id": np.array(uid_list), "item_seq": seqs}
+
+    def _build_aug_seq(self):
+        """dataload.py:152-200: the chunks of _build_seq (at most L+1 items; a longer history drops its oldest len % (L+1)), and
+        every prefix of a chunk of length >= 2 is one sample -- chunk order, shorter prefixes first.  Held as index arithmetic
+        into the time-ordered item array instead of one list per sample: seq_start (first item of the chunk in
+        `self._sorted_items`) and seq_len (prefix length: the history plus its target)."""
+        W = self.config["MAX_ITEM_LIST_LENGTH"] + 1
+        n = self._counts - 2                                           # leave-last-two-out
+        keep = n > 0
+        n, s, uid = n[keep], self._starts[keep], self._uids[keep]
+        long = n > W
+        n_chunks = np.where(long, n // W, 1)
+        off = np.where(long, n % W, 0)
+        g = np.repeat(np.arange(len(n)), n_chunks)                     # user of each chunk
+        c = np.arange(int(n_chunks.sum()), dtype=np.int64) - np.repeat(np.cumsum(n_chunks) - n_chunks, n_chunks)
+        c_start = s[g] + off[g] + c * W
+        c_len = np.where(long[g], W, n[g])
+        per = c_len - 1                                                # prefixes of length 2..len
+        k = np.repeat(np.arange(len(c_len)), per)
+        within = np.arange(int(per.sum()), dtype=np.int64) - np.repeat(np.cumsum(per) - per, per)
+        return {"user_id": uid[g][k].astype(np.int64), "seq_start": c_start[k].astype(np.int64),
+                "seq_len": (within + 2).astype(np.int64)}
+
+    def aug_item_seqs(self):
+        """The AUGSEQ samples as the reference's list of arrays (train_feat['item_seq'] of dataload.py:198): tests / tools."""
+        tf = self.train_feat
+        return [self._sorted_items[a:a + n] for a, n in zip(tf["seq_start"], tf["seq_len"])]
 
     # ---- statistics used in the log line -----------------------------------------------------------------
     @property

@@ -358,3 +358,77 @@ class PairEvalBatcher(SeqEvalBatcher):
     def __iter__(self):
         for b0, (_, hist, pos_u, target) in zip(range(0, len(self.users), self.batch_size), super().__iter__()):
             yield torch.from_numpy(self.uids[self.users[b0:b0 + self.batch_size]]), hist, pos_u, target
+
+
+class GraphTrainBatcher:
+    """Vectorised GraphTrainDataset (reference REC/data/dataset/trainset.py:939-981) under torch's DistributedSampler order: one
+    sample per AUGSEQ prefix (Data._build_aug_seq), yielded as whole (item_seq int64 [B, L], mask int64 [B, L], target int64
+    [B, 2]) batches.  item_seq = prefix[:-1] RIGHT-padded with 0, mask = 1 on its real positions, target = (prefix[-1], negative);
+    the negative is uniform over [1, item_num - 1] and redrawn while it lies in the prefix -- the reference's distribution, not
+    its random stream.  The sample order and the split by rank are SeqTrainBatcher's."""
+
+    MAX_REDRAWS = 1000
+
+    def __init__(self, config, dataload, rank=0, world=1, seed=0, drop_last=False):
+        self.dataload = dataload
+        self.item_num = dataload.item_num
+        self.L = config["MAX_ITEM_LIST_LENGTH"]
+        self.batch_size = config["train_batch_size"]
+        self.flat = np.asarray(dataload._sorted_items, dtype=np.int64)
+        self.start = np.asarray(dataload.train_feat["seq_start"], dtype=np.int64)
+        self.length = np.asarray(dataload.train_feat["seq_len"], dtype=np.int64)
+        self.n = len(self.start)
+        if self.item_num <= 2:
+            raise ValueError("GraphTrainBatcher: no negative can be drawn from [1, item_num) outside a prefix")
+        self.rank, self.world, self.seed, self.epoch = rank, world, seed, 0
+        self.num_samples = -(-self.n // world)
+        self.drop_last = drop_last
+        self.neg_seed = int(config["seed"] or 0)
+
+    set_epoch = SeqTrainBatcher.set_epoch
+    __len__ = SeqTrainBatcher.__len__
+    _indices = SeqTrainBatcher._indices
+
+    def make_batch(self, rows, rng):
+        st, ln = self.start[rows], self.length[rows]
+        B, L = len(rows), self.L
+        col = np.arange(L + 1, dtype=np.int64)[None, :]
+        in_prefix = col < ln[:, None]                                  # [B, L+1]: the prefix, target included
+        win = np.where(in_prefix, self.flat[np.where(in_prefix, st[:, None] + col, 0)], 0)
+        real = col[:, :L] < (ln - 1)[:, None]
+        item_seq = np.where(real, win[:, :L], 0)
+        pos = win[np.arange(B), ln - 1]
+        neg = rng.integers(1, self.item_num, size=B)
+        for _ in range(self.MAX_REDRAWS):
+            clash = ((neg[:, None] == win) & in_prefix).any(1)
+            if not clash.any():
+                break
+            neg[clash] = rng.integers(1, self.item_num, size=int(clash.sum()))
+        else:
+            raise ValueError("GraphTrainBatcher: a prefix covers (nearly) every item: no negative could be drawn")
+        return item_seq, real.astype(np.int64), np.stack((pos, neg), axis=1)
+
+    def __iter__(self):
+        idx = self._indices()
+        rng = np.random.default_rng([self.neg_seed, self.epoch, self.rank])
+        for b in range(len(self)):
+            item_seq, mask, target = self.make_batch(idx[b * self.batch_size:(b + 1) * self.batch_size], rng)
+            yield torch.from_numpy(item_seq), torch.from_numpy(mask), torch.from_numpy(target)
+
+
+class GraphEvalBatcher(SeqEvalBatcher):
+    """GraphEvalDataset (reference evalset.py:187-224) through SeqEvalBatcher: the same users, histories and targets, with the
+    last L history items RIGHT-padded with 0 (the sequence models' batcher left-pads).  The mask of a right-padded window is
+    item_seq != 0; the model derives it on the device.  `(item_seq [b, L], (history_u, history_i), positive_u [b], target [b])`."""
+
+    def __iter__(self):
+        L = self.L
+        col = np.arange(L, dtype=np.int64)[None, :]
+        for b0, (_, hist, pos_u, target) in zip(range(0, len(self.users), self.batch_size), super().__iter__()):
+            u = self.users[b0:b0 + self.batch_size]
+            start, cut = self.offsets[u], self.cut[u]
+            n = np.minimum(cut, L)
+            ok = col < n[:, None]
+            src = start[:, None] + (cut - n)[:, None] + col
+            item_seq = np.where(ok, self.flat[np.where(ok, src, 0)], 0)
+            yield torch.from_numpy(item_seq), hist, pos_u, target

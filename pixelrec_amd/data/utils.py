@@ -14,11 +14,12 @@ from torch.utils.data import DataLoader
 
 from ..parallel import world_info
 from .dataload import Data
-from .dataset import (BERT4RecTrainBatcher, PairEvalBatcher, PairTrainBatcher, SeqEvalBatcher, SeqEvalDataset, SeqTrainBatcher,
-                      seq_eval_collate)
+from .dataset import (BERT4RecTrainBatcher, GraphEvalBatcher, GraphTrainBatcher, PairEvalBatcher, PairTrainBatcher, SeqEvalBatcher,
+                      SeqEvalDataset, SeqTrainBatcher, seq_eval_collate)
 
 SUPPORTED = {"SASRec": "SEQ", "MOSASRec": "SEQ", "FSASRec": "SEQ", "GRU4Rec": "SEQ", "NextItNet": "SEQ",
-             "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR"}      # REC/data/utils.py:24-31
+             "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR",
+             "SRGNN": "AUGSEQ"}      # REC/data/utils.py:24-31
 
 
 def load_data(config):
@@ -57,6 +58,15 @@ class _TrainLoader:
         return iter(self.batcher)
 
 
+class _GraphTrainLoader(_TrainLoader):
+    """GraphTrainBatcher's (item_seq, mask, target) as the two int64 tensors the training loop stages and replays:
+    (item_seq [B, L], mask | target [B, L + 2]) -- SRGNN.forward takes either form."""
+
+    def __iter__(self):
+        for item_seq, mask, target in self.batcher:
+            yield item_seq, torch.cat((mask, target), dim=1)
+
+
 def bulid_dataloader(config, dataload):
     """-> (train_loader, valid_loader, test_loader).  (The misspelt name is the reference's, utils.py:20.)"""
     model_name = config["model"]
@@ -72,6 +82,11 @@ def bulid_dataloader(config, dataload):
         train_loader = _TrainLoader(PairTrainBatcher(config, dataload, rank=rank, world=world))
         return (train_loader, PairEvalBatcher(config, dataload, phase="valid", rank=rank, world=world),
                 PairEvalBatcher(config, dataload, phase="test", rank=rank, world=world))
+    if SUPPORTED[model_name] == "AUGSEQ":
+        # GraphTrainDataset / GraphEvalDataset (REC/data/utils.py:24-31): every prefix a sample, right-padded windows
+        train_loader = _GraphTrainLoader(GraphTrainBatcher(config, dataload, rank=rank, world=world))
+        return (train_loader, GraphEvalBatcher(config, dataload, phase="valid", rank=rank, world=world),
+                GraphEvalBatcher(config, dataload, phase="test", rank=rank, world=world))
     # BERT4Rec masks its windows (REC/data/utils.py:25: BERT4RecTrainDataset); evaluation is SeqEvalDataset's for both
     batcher = BERT4RecTrainBatcher if model_name == "BERT4Rec" else SeqTrainBatcher
     train_loader = _TrainLoader(batcher(config, dataload, rank=rank, world=world))

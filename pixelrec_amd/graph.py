@@ -90,6 +90,8 @@ class GraphedTrainStep:
         self.model._step_counter = st[1]
 
     def _dry_run(self):
+        from .optim import item_table
+
         m, o = self.model, self.opt
         if hasattr(o, "opts"):
             raise NotImplementedError("GraphedTrainStep(warmup=0) snapshots ONE PxrAdamW; capture an optimizer group with warmup >= 1")
@@ -99,7 +101,7 @@ class GraphedTrainStep:
         table_state = None
         if getattr(o, "has_table", False):
             o.flush()
-            table_state = [t.clone() for t in (m.item_embedding.weight.data, o._tm, o._tv, o._last)]
+            table_state = [t.clone() for t in (item_table(m).data, o._tm, o._tv, o._last)]
         counters = (o.step_count, m._step_counter, o._dirty, o._step_dev.clone(), m._drop_dev.clone())
         acc = self.loss_sum.clone() if self.loss_sum is not None else None
         self._eager_holding()
@@ -108,7 +110,7 @@ class GraphedTrainStep:
         for dst, src in zip((flat, o._m, o._v), keep):
             dst.copy_(src)
         if table_state is not None:
-            for dst, src in zip((m.item_embedding.weight.data, o._tm, o._tv, o._last), table_state):
+            for dst, src in zip((item_table(m).data, o._tm, o._tv, o._last), table_state):
                 dst.copy_(src)
         o.step_count, m._step_counter, o._dirty = counters[:3]
         o._step_dev.copy_(counters[3])

@@ -141,6 +141,12 @@ _SIGNATURES = {
     "pxr_lgcn_spmm_f32": (_I, [_P, _P, _P, _I64, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _F, _P, _I64, _P]),
     "pxr_lgcn_pair_fwd_f32": (_I, [_P, _I64, _I64, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "pxr_lgcn_pair_bwd_f32": (_I, [_P, _I64, _I, _P, _P, _I, _F, _P, _P, _P]),
+    "pxr_srgnn_graph_i64": (_I, [_P, _I64, _I, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    "pxr_srgnn_prop_f32": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P]),
+    "pxr_srgnn_readout_fwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "pxr_srgnn_readout_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "pxr_srgnn_pair_fwd_f32": (_I, [_P, _I64, _P, _I64, _I, _P, _I, _P, _P, _P, _P]),
+    "pxr_srgnn_pair_bwd_f32": (_I, [_P, _I64, _I, _P, _P, _I, _F, _P, _P, _I64, _P, _I64, _P]),
 }
 
 

@@ -1,0 +1,385 @@
+"""SRGNN (IDNet) -- drop-in for `REC.model.IDNet.srgnn.SRGNN` (code/REC/model/IDNet/srgnn.py) on the hand-written gfx950 kernels
+of csrc/srgnn.hip and the library's fp32-operand GEMMs.
+
+    session graph (nodes, alias, A = [A_in | A_out])  of item_seq [B, L], right-padded, built on the device at L nodes
+    H_0 = embedding[nodes];  step times:  E = H [W_ei; W_eo]^T + [b_ei; b_eo]            (one GEMM)
+                                          X = [A_in E_in + b_iah | A_out E_out + b_oah]   (pxr_srgnn_prop_f32)
+                                          H = GRU gates(X W_ih^T + b_ih, H W_hh^T + b_hh, H)   (gru.hip)
+    P = H [W1; W2]^T + [b1; b2] (one GEMM);  readout: s_t = sigmoid(P1[ht] + P2[alias t]), alpha_t = <w3, s_t>,
+    a = sum_t alpha_t sh_t mask_t;  out = W_t [a | ht] + b_t;  loss = -mean(1e-8 + log sigmoid(<out, e+> - <out, e->))
+
+The graph is padded to L nodes, not to the batch's largest node count as the reference's collate does: a padding node has id 0
+and no edges, so every output stays the same and the step has one shape -- it is captured once and replayed (graph.py).
+
+The item table is SASRec's: the batch's node and target ids go through the occurrence sort (id rows [B, 3L] = nodes |
+target | negative, written by the graph build) before anything reads the table, a lazy PxrAdamW brings exactly those rows up
+to date, and the backward leaves the table gradient as sparse rows (`sparse_table_grad`, the segment sums of embed_grad.hip).
+The order inside a step is graph build -> occurrence sort -> catch-up -> gather.  Every other parameter lives in one flat
+buffer (PxrAdamW's one launch); the step's weight gradients are one grouped launch -- the `step` iterations stack their rows,
+so dW_ih, dW_hh and the edge weights are one product each.
+
+Contract kept: `input_type = AUGSEQ`; `__init__(config, dataload)` with `embedding_size`, `step`; forward((item_seq [B, L],
+mask [B, L], target [B, 2])) -> loss (or (item_seq, mask | target [B, L + 2]), the form the training loop stages);
+`predict(item_seq, item_feature) -> [B, N]`; `compute_item_all` = embedding.weight; `state_dict` names and order of the
+reference (`embedding.weight` without padding_idx, `gnn.*`, `linear_{one,two,three,transform}`), every parameter initialised
+uniform(-1/sqrt(D), 1/sqrt(D)).  `gnn.linear_edge_f` is read by nothing: it gets no gradient, stays out of the flat buffer and
+is never updated (torch.optim.AdamW skips a parameter without a gradient, weight decay included).
+An empty history (sum(mask) = 0) reads its `ht` from the last slot, as torch's index -1 does in the reference.
+One process: the data-parallel exchange is not built for this model.
+"""
+from __future__ import annotations
+
+import math
+import os
+
+import torch
+import torch.nn as nn
+
+from .. import ops
+from ..lib import PxrError
+from ..parallel import world_info
+from ..utils.enum_type import InputType
+from .basemodel import BaseModel
+
+
+class _GNN(nn.Module):
+    """Parameter container with the reference GNN's names (srgnn.py GNN); its forward is never called."""
+
+    def __init__(self, hidden_size, step):
+        super().__init__()
+        self.step = step
+        self.hidden_size = hidden_size
+        self.w_ih = nn.Parameter(torch.empty(3 * hidden_size, 2 * hidden_size))
+        self.w_hh = nn.Parameter(torch.empty(3 * hidden_size, hidden_size))
+        self.b_ih = nn.Parameter(torch.empty(3 * hidden_size))
+        self.b_hh = nn.Parameter(torch.empty(3 * hidden_size))
+        self.b_iah = nn.Parameter(torch.empty(hidden_size))
+        self.b_oah = nn.Parameter(torch.empty(hidden_size))
+        self.linear_edge_in = nn.Linear(hidden_size, hidden_size, bias=True)
+        self.linear_edge_out = nn.Linear(hidden_size, hidden_size, bias=True)
+        self.linear_edge_f = nn.Linear(hidden_size, hidden_size, bias=True)
+
+
+class _SrgnnStep(torch.autograd.Function):
+    """Bridges `loss.backward()` to the hand-written backward chain."""
+
+    @staticmethod
+    def forward(ctx, anchor, model, item_seq, mask, target):
+        ctx.model = model
+        return model._forward_train(item_seq, mask, target).view(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ctx.model._backward_train(grad_out)
+        return None, None, None, None, None
+
+
+class SRGNN(BaseModel):
+    input_type = InputType.AUGSEQ
+    item_table_attr = "embedding"          # the reference's table name (optim.item_table_name)
+
+    def __init__(self, config, dataload):
+        super().__init__()
+        if world_info()[1] > 1:
+            raise NotImplementedError("SRGNN runs on one process: data parallelism is not built for the graph models")
+        self.hidden_size = config["embedding_size"]
+        self.step = int(config["step"])
+        self.item_num = dataload.item_num
+        self.max_seq_length = config["MAX_ITEM_LIST_LENGTH"]
+        D = self.hidden_size
+        if D % 4:
+            raise ValueError("embedding_size must be a multiple of 4 (16-byte vector accesses)")
+        if self.step < 1:
+            raise ValueError("step must be >= 1")
+        if not 1 <= self.max_seq_length <= ops.SRGNN_MAX_L:
+            raise ValueError(f"MAX_ITEM_LIST_LENGTH must be in 1..{ops.SRGNN_MAX_L} for SRGNN's session graphs")
+        self.embedding = nn.Embedding(self.item_num, D)
+        self.gnn = _GNN(D, self.step)
+        self.linear_one = nn.Linear(D, D, bias=True)
+        self.linear_two = nn.Linear(D, D, bias=True)
+        self.linear_three = nn.Linear(D, 1, bias=False)
+        self.linear_transform = nn.Linear(2 * D, D, bias=True)
+        stdv = 1.0 / math.sqrt(D)
+        for w in self.parameters():                       # srgnn.py _reset_parameters, in parameter order
+            w.data.uniform_(-stdv, stdv)
+        self._flat = self._gflat = None
+        self._views = {}
+        self._bufs = {}
+        self._gbufs = {}
+        self._saved = None
+        self._step_counter = 0
+        self._drop_dev = None                              # (no dropout: the step counter graph.py keeps)
+        self.grad_scale = 1.0
+        # the sparse table (SASRec's bookkeeping)
+        self.sparse_table_grad = None
+        self._local_sparse = None
+        self._table_hooks = None
+        self._occ_ws = self._occ_ws2 = None
+
+    # ------------------------------------------------------------------------------------------ flat packing
+    def _flat_specs(self):
+        """Flat layout: the two edge Linears side by side (E is one GEMM), b_iah | b_oah (one bias of the propagation),
+        linear_one | linear_two (P is one GEMM).  linear_edge_f and the table stay outside."""
+        g = self.gnn
+        return [("ein.w", g.linear_edge_in.weight), ("eout.w", g.linear_edge_out.weight),
+                ("ein.b", g.linear_edge_in.bias), ("eout.b", g.linear_edge_out.bias),
+                ("iah", g.b_iah), ("oah", g.b_oah),
+                ("w_ih", g.w_ih), ("b_ih", g.b_ih), ("w_hh", g.w_hh), ("b_hh", g.b_hh),
+                ("one.w", self.linear_one.weight), ("two.w", self.linear_two.weight),
+                ("one.b", self.linear_one.bias), ("two.b", self.linear_two.bias),
+                ("three.w", self.linear_three.weight), ("t.w", self.linear_transform.weight), ("t.b", self.linear_transform.bias)]
+
+    def rec_parameter_names(self):
+        """{reference parameter name: flat-buffer key} in the reference's registration order (optim.native_to_torch_state):
+        the table and linear_edge_f (no gradient, no optimizer state) map to None."""
+        return {"embedding.weight": None, "gnn.w_ih": "w_ih", "gnn.w_hh": "w_hh", "gnn.b_ih": "b_ih", "gnn.b_hh": "b_hh",
+                "gnn.b_iah": "iah", "gnn.b_oah": "oah", "gnn.linear_edge_in.weight": "ein.w", "gnn.linear_edge_in.bias": "ein.b",
+                "gnn.linear_edge_out.weight": "eout.w", "gnn.linear_edge_out.bias": "eout.b", "gnn.linear_edge_f.weight": None,
+                "gnn.linear_edge_f.bias": None, "linear_one.weight": "one.w", "linear_one.bias": "one.b",
+                "linear_two.weight": "two.w", "linear_two.bias": "two.b", "linear_three.weight": "three.w",
+                "linear_transform.weight": "t.w", "linear_transform.bias": "t.b"}
+
+    def _ensure_packed(self):
+        w0 = self.gnn.linear_edge_in.weight
+        if self._flat is not None and self._flat.device == w0.device and w0.data_ptr() == self._flat.data_ptr():
+            return
+        dev = w0.device
+        if dev.type != "cuda":
+            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with .to('cuda') first")
+        specs = self._flat_specs()
+        total = sum(p.numel() for _, p in specs)
+        flat = torch.empty(total, dtype=torch.float32, device=dev)
+        gflat = torch.zeros(total, dtype=torch.float32, device=dev)
+        off, views = 0, {}
+        for name, p in specs:
+            n = p.numel()
+            flat[off:off + n].copy_(p.data.reshape(-1))
+            p.data = flat[off:off + n].view(p.shape)
+            p.grad = gflat[off:off + n].view(p.shape)
+            views[name] = (off, n, tuple(p.shape))
+            off += n
+        self._flat, self._gflat, self._views = flat, gflat, views
+        self._anchor = torch.zeros((), dtype=torch.float32, device=dev, requires_grad=True)
+        self._drop_dev = torch.full((1,), self._step_counter, dtype=torch.int64, device=dev)
+        self._bufs, self._gbufs = {}, {}
+
+    def flat_parameters(self):
+        self._ensure_packed()
+        return self._flat, self._gflat
+
+    def _p(self, name, grad=False, span=1):
+        """View of parameter `name` (or of `span` adjacent ones fused along dim 0) in the flat (grad) buffer."""
+        off, n, shape = self._views[name]
+        buf = self._gflat if grad else self._flat
+        if span == 1:
+            return buf[off:off + n].view(shape)
+        return buf[off:off + span * n].view((span * shape[0],) + tuple(shape[1:]))
+
+    def _buf(self, name, shape, zero=False):
+        """Persistent work buffers (stable addresses: a captured step replays on them)."""
+        b = self._bufs.get(name)
+        if b is None or tuple(b.shape) != tuple(shape):
+            b = self._bufs[name] = (torch.zeros if zero else torch.empty)(*shape, dtype=torch.float32, device=self._flat.device)
+        return b
+
+    # ------------------------------------------------------------------------------------------ the table (SASRec's machinery)
+    def register_table_hooks(self, opt):
+        """Attach a lazy table optimizer: it is asked to bring rows up to date before they are read."""
+        self._table_hooks = opt
+
+    def join_prefetch(self):
+        return None
+
+    def sync_table(self):
+        """Make every table row current (no-op without a lazy optimizer)."""
+        if self._table_hooks is not None:
+            self._table_hooks.flush()
+
+    def state_dict(self, *args, **kwargs):
+        self.sync_table()
+        return super().state_dict(*args, **kwargs)
+
+    def load_state_dict(self, state_dict, strict=True, **kwargs):
+        self.sync_table()
+        return super().load_state_dict(state_dict, strict=strict, **kwargs)
+
+    def _table_prepare(self, g, B, L, D, device):
+        """Occurrence sort of the batch's node and target ids, then the lazy catch-up of exactly those rows."""
+        cap = B * (L + 2)
+        sp = self._local_sparse
+        if sp is None or sp.cap != cap or sp.rows.shape[1] != D or sp.rows.device != device:
+            sp = self._local_sparse = ops.SparseRows(cap, D, device, packed=True)
+        need = ops.occ_ws_bytes(B, L)
+        if self._occ_ws is None or self._occ_ws.numel() < need or self._occ_ws.device != device:
+            self._occ_ws = torch.empty(need, dtype=torch.uint8, device=device)
+        env = os.environ.get("PXR_SEGSUM_SPLIT", "auto")
+        need2 = ops.occ_split_ws_bytes(B, L, D) if (env == "1" or (env != "0" and 3 * B * L >= 30000)) else 0
+        if need2 == 0:
+            self._occ_ws2 = None
+        elif self._occ_ws2 is None or self._occ_ws2.numel() != need2 or self._occ_ws2.device != device:
+            self._occ_ws2 = torch.zeros(need2, dtype=torch.uint8, device=device)
+        ops.occ_sort(g["occ"], L, (3 * L, 0, L, 2 * L), self.item_num, sp, self._occ_ws)
+        if self._table_hooks is not None:
+            self._table_hooks.catch_up_rows(sp.idx, sp.n, sp.cap)
+        return sp
+
+    # ------------------------------------------------------------------------------------------ the network
+    def _gnn_forward(self, table, nodes, A, B, train):
+        """H_0 = table[nodes], then `step` gated-GNN cells.  -> (Hs [step + 1, B L, D], saved tensors | None)."""
+        L, D, S = self.max_seq_length, self.hidden_size, self.step
+        dev = table.device
+        BL = B * L
+        Hs = torch.empty(S + 1, BL, D, dtype=torch.float32, device=dev)
+        ops.embed_gather(table, nodes.reshape(-1), out=Hs[0])
+        Xs = torch.empty(S, BL, 2 * D, dtype=torch.float32, device=dev)
+        saves = torch.empty(S, BL, 4 * D, dtype=torch.float32, device=dev) if train else None
+        We, be, bah = self._p("ein.w", span=2), self._p("ein.b", span=2), self._p("iah", span=2)
+        Wih, bih, Whh, bhh = self._p("w_ih"), self._p("b_ih"), self._p("w_hh"), self._p("b_hh")
+        for k in range(S):
+            E = ops.linear_fwd(Hs[k], We, be)                                        # [BL, 2D] = [E_in | E_out]
+            ops.srgnn_prop(A, E, y=Xs[k], bias=bah)                                  # [BL, 2D] = [in | out]
+            gi = ops.linear_fwd(Xs[k], Wih, bih)
+            gh = ops.linear_fwd(Hs[k], Whh, bhh)
+            ops.gru_gates_fwd(gi, gh, Hs[k], Hs[k + 1], saves[k] if train else None)
+        return Hs, Xs, saves
+
+    def _readout(self, Hn, alias, mask, B, train):
+        """-> cat [B, 2D] = [a | ht] (+ saved sig / alpha when training)."""
+        L, D = self.max_seq_length, self.hidden_size
+        P = ops.linear_fwd(Hn, self._p("one.w", span=2), self._p("one.b", span=2))      # [BL, 2D] = [q1 | q2] per node
+        sig = torch.empty(B, L, D, dtype=torch.float32, device=Hn.device) if train else None
+        alpha = torch.empty(B, L, dtype=torch.float32, device=Hn.device) if train else None
+        cat = ops.srgnn_readout_fwd(Hn, P, alias, mask, self._p("three.w").view(-1), sig=sig, alpha=alpha)
+        return cat, sig, alpha
+
+    # ------------------------------------------------------------------------------------------ training
+    def forward(self, interaction):
+        """interaction = (item_seq [B, L], mask [B, L], target [B, 2]) or (item_seq, mask | target [B, L + 2]) -> 0-dim loss."""
+        if len(interaction) == 3:
+            item_seq, mask, target = interaction
+        else:
+            item_seq, tail = interaction
+            L = self.max_seq_length
+            mask, target = tail[:, :L], tail[:, L:L + 2]
+        L = self.max_seq_length
+        if item_seq.dim() != 2 or item_seq.shape[1] != L:
+            raise ValueError(f"item_seq must be [B, {L}], got {tuple(item_seq.shape)}")
+        self._ensure_packed()
+        item_seq, mask, target = item_seq.contiguous(), mask.contiguous(), target.contiguous()
+        if torch.is_grad_enabled() and self.training:
+            return _SrgnnStep.apply(self._anchor, self, item_seq, mask, target)
+        was = self.training
+        try:
+            self.training = False
+            return self._forward_train(item_seq, mask, target).view(())
+        finally:
+            self.training = was
+
+    def _forward_train(self, item_seq, mask, target):
+        B, L, D = item_seq.shape[0], self.max_seq_length, self.hidden_size
+        dev = item_seq.device
+        table = self.embedding.weight.data
+        g = ops.srgnn_graph(item_seq, self.item_num, target, want_occ=self.training, out=self._gbufs)
+        if self.training:
+            sp = self._table_prepare(g, B, L, D, dev)
+        elif self._table_hooks is not None:
+            self.sync_table()
+        Hs, Xs, saves = self._gnn_forward(table, g["nodes"], g["A"], B, self.training)
+        Hn = Hs[self.step]
+        cat, sig, alpha = self._readout(Hn, g["alias"], mask, B, self.training)
+        # out rows L*D apart: row 0 of each session's [L, D] block, the layout the occurrence segment sums read (coef 0 elsewhere)
+        out_pad = self._buf("out_pad", (B, L, D), zero=True)
+        ops.gemm(True, True, B, D, 2 * D, cat, 2 * D, self._p("t.w"), 2 * D, out_pad, L * D, ops.EPI_BIAS, bias=self._p("t.b"),
+                 use_ws=False)
+        loss, coef = ops.srgnn_pair_fwd(out_pad, L * D, table, target, B)
+        if self.training:
+            self._saved = dict(B=B, g=g, sp=sp, Hs=Hs, Xs=Xs, saves=saves, cat=cat, sig=sig, alpha=alpha, mask=mask, target=target,
+                               out_pad=out_pad, coef=coef)
+        return loss
+
+    def _backward_train(self, grad_out):
+        s = self._saved
+        if s is None:
+            raise PxrError("backward() without a training-mode forward()")
+        B, L, D, S = s["B"], self.max_seq_length, self.hidden_size, self.step
+        BL = B * L
+        dev = s["cat"].device
+        table = self.embedding.weight.data
+        g = lambda name, span=1: self._p(name, grad=True, span=span)
+        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
+        dout = self._buf("dout", (B, D))
+        coef_pad = self._buf("coef_pad", (B, L), zero=True)
+        ops.srgnn_pair_bwd(table, s["target"], s["coef"], dout, D, self.grad_scale, gsd, coef_out=coef_pad, coef_stride=L)
+        dcat = ops.linear_bwd_input(dout, self._p("t.w"))                                  # [B, 2D]
+        Hs, Xs, saves = s["Hs"], s["Xs"], s["saves"]
+        Hn = Hs[S]
+        gr = s["g"]
+        dP, dHr, dw3p = ops.srgnn_readout_bwd(dcat, Hn, gr["alias"], s["mask"], self._p("three.w").view(-1), s["sig"], s["alpha"])
+        ops.colsum(dw3p, out=g("three.w").view(-1))
+        dH = ops.linear_bwd_input(dP, self._p("one.w", span=2), add=dHr)                  # d loss / d H_step  [BL, D]
+        dgi = torch.empty(S, BL, 3 * D, dtype=torch.float32, device=dev)
+        dgh = torch.empty(S, BL, 3 * D, dtype=torch.float32, device=dev)
+        dX = torch.empty(S, BL, 2 * D, dtype=torch.float32, device=dev)
+        dE = torch.empty(S, BL, 2 * D, dtype=torch.float32, device=dev)
+        direct = torch.empty(BL, D, dtype=torch.float32, device=dev)
+        We, Wih, Whh = self._p("ein.w", span=2), self._p("w_ih"), self._p("w_hh")
+        for k in reversed(range(S)):
+            ops.gru_gates_bwd(dH, saves[k], Hs[k], dgi[k], dgh[k], direct)
+            ops.linear_bwd_input(dgi[k], Wih, out=dX[k])
+            ops.srgnn_prop(gr["A"], dX[k], y=dE[k], transpose=True)
+            t1 = ops.linear_bwd_input(dgh[k], Whh, add=direct)
+            dH = ops.linear_bwd_input(dE[k], We, add=t1)                                  # d loss / d H_k
+        ops.colsum(dX.view(S * BL, 2 * D), out=g("iah", span=2))                          # b_iah | b_oah
+        Hprev = Hs[:S].reshape(S * BL, D)
+        ops.grouped_linear_bwd_weight([
+            (dout, s["cat"], g("t.w"), g("t.b")),
+            (dP, Hn, g("one.w", span=2), g("one.b", span=2)),
+            (dgi.view(S * BL, 3 * D), Xs.view(S * BL, 2 * D), g("w_ih"), g("b_ih")),
+            (dgh.view(S * BL, 3 * D), Hprev, g("w_hh"), g("b_hh")),
+            (dE.view(S * BL, 2 * D), Hprev, g("ein.w", span=2), g("ein.b", span=2)),
+        ])
+        sp = s["sp"]
+        ops.sasrec_occ_segsum(self._occ_ws, dH.view(B, L, D), s["out_pad"], coef_pad, self.item_num, sp, 1.0, ws2=self._occ_ws2)
+        self.sparse_table_grad = sp
+        self._saved = None
+        ops.counter_add(self._drop_dev, 1)
+        self._step_counter += 1
+
+    # ------------------------------------------------------------------------------------------ evaluation
+    @torch.no_grad()
+    def _encode(self, item_seq, table):
+        B = item_seq.shape[0]
+        g = ops.srgnn_graph(item_seq, table.shape[0], want_mask=True)
+        Hs, _, _ = self._gnn_forward(table, g["nodes"], g["A"], B, train=False)
+        cat, _, _ = self._readout(Hs[self.step], g["alias"], g["mask"], B, train=False)
+        return ops.linear_fwd(cat, self._p("t.w"), self._p("t.b"))                         # [B, D]
+
+    @torch.no_grad()
+    def encode_last(self, item_seq, item_feature=None):
+        """item_seq int64 [B, L] (right-padded; mask = item_seq != 0) -> (out [B, 1, D], out [B, D]): the query vectors of the
+        fused scoring (`last` with row stride D)."""
+        self._ensure_packed()
+        self.sync_table()
+        item_seq = item_seq.contiguous()
+        if item_seq.dim() != 2 or item_seq.shape[1] != self.max_seq_length:
+            raise ValueError(f"item_seq must be [B, {self.max_seq_length}], got {tuple(item_seq.shape)}")
+        table = self.embedding.weight.data if item_feature is None else item_feature.contiguous()
+        out = self._encode(item_seq, table)
+        return out.view(out.shape[0], 1, -1), out
+
+    @torch.no_grad()
+    def predict(self, item_seq, item_feature):
+        """scores [B, N] = seq_output item_feature^T (srgnn.py predict: the node rows are read from item_feature)."""
+        feat = item_feature if item_feature.is_contiguous() else item_feature.contiguous()
+        _, out = self.encode_last(item_seq, feat)
+        B, D = out.shape
+        N = feat.shape[0]
+        scores = torch.empty(B, N, dtype=torch.float32, device=out.device)
+        ops.gemm(True, True, B, N, D, out, D, feat, D, scores, N, ops.EPI_NONE, use_ws=False)
+        ops.raise_on_bad_indices(out.device)     # an id outside the catalogue raises, like the reference's indexing
+        return scores
+
+    @torch.no_grad()
+    def compute_item_all(self):
+        self.sync_table()
+        return self.embedding.weight

@@ -165,14 +165,18 @@ def raise_on_bad_indices(device=None):
 
 
 # ------------------------------------------------------------------------------------------------ K1 gather
-def embed_gather(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
-    """out[..., :] = table[idx[...], :]  (reference: nn.Embedding forward, sasrec.py:68,101)."""
+def embed_gather(table: torch.Tensor, idx: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[..., :] = table[idx[...], :]  (reference: nn.Embedding forward, sasrec.py:68,101).  out: a contiguous buffer of
+    idx.numel() * D floats to write into (default: a new tensor)."""
     L = _l.load()
     _req(table, torch.float32, "table")
     _req(idx, torch.int64, "idx")
     N, D = table.shape
     device_status(table.device)       # out-of-range ids are flagged on the device (and clamped), raised at the next check
-    out = torch.empty(*idx.shape, D, dtype=torch.float32, device=table.device)
+    if out is None:
+        out = torch.empty(*idx.shape, D, dtype=torch.float32, device=table.device)
+    elif out.numel() != idx.numel() * D or not out.is_contiguous() or out.dtype != torch.float32:
+        raise _l.PxrError("embed_gather: out must be a contiguous fp32 buffer of idx.numel() * D elements")
     _l.check(L.pxr_embed_gather_f32(_l.ptr(table), N, D, _l.ptr(idx), idx.numel(), _l.ptr(out), _l.stream_ptr()),
              "pxr_embed_gather_f32")
     if _CHECK_IDX:
@@ -507,14 +511,20 @@ def dropout(x: torch.Tensor, p: float, seed: int, stream_id: int, step_dev=None)
 
 
 def linear_bwd_input(dy: torch.Tensor, W: torch.Tensor, dgelu_pre: torch.Tensor | None = None,
-                     add: torch.Tensor | None = None, mul: torch.Tensor | None = None):
+                     add: torch.Tensor | None = None, mul: torch.Tensor | None = None, out: torch.Tensor | None = None):
     """dx = dy W, optionally times gelu'(pre) (from the saved pre-activation), times `mul` (gelu' saved by the forward),
-    or plus `add` (residual gradient)."""
+    or plus `add` (residual gradient).  out: a contiguous buffer to write dx into (default: a new tensor)."""
     L = _l.load()
     _req(dy, torch.float32, "dy"); _req(W, torch.float32, "W")
     N, K = W.shape
     M = dy.numel() // N
-    dx = torch.empty(*dy.shape[:-1], K, dtype=torch.float32, device=dy.device)
+    if out is None:
+        dx = torch.empty(*dy.shape[:-1], K, dtype=torch.float32, device=dy.device)
+    else:
+        _req(out, torch.float32, "out")
+        if out.numel() != M * K:
+            raise _l.PxrError(f"linear_bwd_input: out has {out.numel()} elements, expected {M * K}")
+        dx = out
     tag = ("gemm_kernel<KC,XC,EPI_MUL_DGELU> (dX through GELU)" if dgelu_pre is not None else
            "gemm_kernel<KC,XC,EPI_MUL> (dX x saved gelu')" if mul is not None else
            "gemm_kernel<KC,XC,EPI_ADD> (dX + residual grad)" if add is not None else "gemm_kernel<KC,XC,EPI_NONE> (dX)")
@@ -1823,3 +1833,105 @@ def lgcn_pair_bwd(emb, nodes, coef, grad, grad_scale=1.0, grad_scale_dev=None):
     _l.check(Lb.pxr_lgcn_pair_bwd_f32(_l.ptr(emb), N, D, _l.ptr(nodes), _l.ptr(coef), coef.numel(), float(grad_scale),
                                       _l.ptr(grad_scale_dev), _l.ptr(grad), _l.stream_ptr()), "pxr_lgcn_pair_bwd_f32")
     return grad
+
+
+# ------------------------------------------------------------------------------------------------ SRGNN (csrc/srgnn.hip)
+SRGNN_MAX_L = 64
+
+
+def srgnn_graph(seq, n_items: int, target=None, want_occ: bool = False, want_mask: bool = False, out=None):
+    """Session graphs of seq int64 [B, L] (right-padded) at a fixed L nodes -> dict(nodes int64 [B, L], alias int32 [B, L],
+    A fp32 [B, L, 2L], occ int64 [B, 3L] | None, mask int64 [B, L] | None).  `out`: a dict of persistent buffers to fill."""
+    Lb = _l.load()
+    _req(seq, torch.int64, "seq")
+    B, L = seq.shape
+    if L < 1 or L > SRGNN_MAX_L:
+        raise _l.PxrError(f"srgnn graph: L={L} outside 1..{SRGNN_MAX_L} (the node bitmasks of one wave)")
+    if want_occ:
+        _req(target, torch.int64, "target")
+        if target.numel() != 2 * B:
+            raise _l.PxrError(f"srgnn graph: target must be [B, 2] for B={B}, got {tuple(target.shape)}")
+    dev = seq.device
+    o = out if out is not None else {}
+    if o.get("nodes") is None or o["nodes"].shape != (B, L) or o["nodes"].device != dev:
+        o.update(nodes=torch.empty(B, L, dtype=torch.int64, device=dev), alias=torch.empty(B, L, dtype=torch.int32, device=dev),
+                 A=torch.empty(B, L, 2 * L, dtype=torch.float32, device=dev), occ=None, mask=None)
+    if want_occ and o.get("occ") is None:
+        o["occ"] = torch.empty(B, 3 * L, dtype=torch.int64, device=dev)
+    if want_mask and o.get("mask") is None:
+        o["mask"] = torch.empty(B, L, dtype=torch.int64, device=dev)
+    device_status(dev)                # an id outside the table flags the status word (raise_on_bad_indices)
+    _l.check(Lb.pxr_srgnn_graph_i64(_l.ptr(seq), B, L, n_items, _l.ptr(target) if want_occ else None, _l.ptr(o["nodes"]),
+                                    _l.ptr(o["alias"]), _l.ptr(o["A"]), _l.ptr(o["occ"]) if want_occ else None,
+                                    _l.ptr(o["mask"]) if want_mask else None, _l.stream_ptr()), "pxr_srgnn_graph_i64")
+    return o
+
+
+def srgnn_prop(A, x, y=None, bias=None, transpose: bool = False):
+    """[A_in x_in | A_out x_out] (+ bias) per session, or its transpose (the backward): x, y [B*L, 2D]."""
+    Lb = _l.load()
+    _req(A, torch.float32, "A"); _req(x, torch.float32, "x")
+    B, L, _ = A.shape
+    D = x.shape[-1] // 2
+    if x.numel() != B * L * 2 * D:
+        raise _l.PxrError(f"srgnn prop: x has {x.numel()} elements, expected B*L*2D = {B * L * 2 * D}")
+    y = y if y is not None else torch.empty_like(x)
+    _l.check(Lb.pxr_srgnn_prop_f32(_l.ptr(A), B, L, D, _l.ptr(x), _l.ptr(y), _l.ptr(bias), int(transpose), _l.stream_ptr()),
+             "pxr_srgnn_prop_f32")
+    return y
+
+
+def srgnn_readout_fwd(Hn, P, alias, mask, w3, cat=None, sig=None, alpha=None):
+    """Attention readout: Hn [B*L, D], P [B*L, 2D] -> cat [B, 2D] = [a | ht] (sig [B, L, D] / alpha [B, L] saved when given)."""
+    Lb = _l.load()
+    _req(Hn, torch.float32, "Hn"); _req(P, torch.float32, "P"); _req(alias, torch.int32, "alias"); _req(mask, torch.int64, "mask")
+    _req(w3, torch.float32, "w3")
+    B, L = alias.shape
+    D = Hn.shape[-1]
+    cat = cat if cat is not None else torch.empty(B, 2 * D, dtype=torch.float32, device=Hn.device)
+    _l.check(Lb.pxr_srgnn_readout_fwd_f32(_l.ptr(Hn), _l.ptr(P), _l.ptr(alias), _l.ptr(mask), _l.ptr(w3), B, L, D, _l.ptr(cat),
+                                          _l.ptr(sig), _l.ptr(alpha), _l.stream_ptr()), "pxr_srgnn_readout_fwd_f32")
+    return cat
+
+
+def srgnn_readout_bwd(dcat, Hn, alias, mask, w3, sig, alpha, dP=None, dH=None, dw3p=None):
+    """-> (dP [B*L, 2D], dH [B*L, D], dw3p [B, D]) from dcat [B, 2D]."""
+    Lb = _l.load()
+    _req(dcat, torch.float32, "dcat"); _req(sig, torch.float32, "sig"); _req(alpha, torch.float32, "alpha")
+    B, L = alias.shape
+    D = Hn.shape[-1]
+    dev = Hn.device
+    dP = dP if dP is not None else torch.empty(B * L, 2 * D, dtype=torch.float32, device=dev)
+    dH = dH if dH is not None else torch.empty(B * L, D, dtype=torch.float32, device=dev)
+    dw3p = dw3p if dw3p is not None else torch.empty(B, D, dtype=torch.float32, device=dev)
+    _l.check(Lb.pxr_srgnn_readout_bwd_f32(_l.ptr(dcat), _l.ptr(Hn), _l.ptr(alias), _l.ptr(mask), _l.ptr(w3), _l.ptr(sig),
+                                          _l.ptr(alpha), B, L, D, _l.ptr(dP), _l.ptr(dH), _l.ptr(dw3p), _l.stream_ptr()),
+             "pxr_srgnn_readout_bwd_f32")
+    return dP, dH, dw3p
+
+
+def srgnn_pair_fwd(out, ld_out: int, table, target, B: int):
+    """SRGNN's pair loss (srgnn.py:60-66): query rows out[b * ld_out : + D], target [B, 2] rows of the table ->
+    (loss [1], coef [B] = d loss / d x_b)."""
+    Lb = _l.load()
+    _req(out, torch.float32, "out", contiguous=False); _req(table, torch.float32, "table"); _req(target, torch.int64, "target")
+    N, D = table.shape
+    if target.numel() != 2 * B:
+        raise _l.PxrError(f"srgnn pair head: target must be [B, 2] for B={B}, got {tuple(target.shape)}")
+    f = torch.empty(2 * B + 1, dtype=torch.float32, device=out.device)
+    lossrow, coef, loss = f[:B], f[B:2 * B], f[2 * B:]
+    device_status(out.device)
+    _l.check(Lb.pxr_srgnn_pair_fwd_f32(_l.ptr(out), ld_out, _l.ptr(table), N, D, _l.ptr(target), B, _l.ptr(lossrow), _l.ptr(coef),
+                                       _l.ptr(loss), _l.stream_ptr()), "pxr_srgnn_pair_fwd_f32")
+    return loss, coef
+
+
+def srgnn_pair_bwd(table, target, coef, dout, ld_dout: int, grad_scale=1.0, grad_scale_dev=None, coef_out=None, coef_stride: int = 1):
+    """dout rows (ld_dout apart) = c_b (e[pos] - e[neg]); coef_out[b * coef_stride] = c_b when given."""
+    Lb = _l.load()
+    _req(table, torch.float32, "table"); _req(target, torch.int64, "target"); _req(coef, torch.float32, "coef")
+    N, D = table.shape
+    _l.check(Lb.pxr_srgnn_pair_bwd_f32(_l.ptr(table), N, D, _l.ptr(target), _l.ptr(coef), coef.numel(), float(grad_scale),
+                                       _l.ptr(grad_scale_dev), _l.ptr(dout), ld_dout, _l.ptr(coef_out), coef_stride,
+                                       _l.stream_ptr()), "pxr_srgnn_pair_bwd_f32")
+    return dout

@@ -49,10 +49,26 @@ def reference_rec_parameter_names(model):
     return ["position_embedding.weight", "LayerNorm.weight", "LayerNorm.bias"] + layers
 
 
+def item_table_name(model) -> str:
+    """Attribute name of the item table: `item_embedding`, or the model's own `item_table_attr` (SRGNN keeps the reference's
+    `embedding`)."""
+    return getattr(model, "item_table_attr", "item_embedding")
+
+
 def has_item_table(model) -> bool:
-    """True for the ID model: `item_embedding` is the nn.Embedding that is updated sparsely / lazily and exchanged as rows.
-    (FSASRec also has an `item_embedding`, but it is an encoder module whose parameters live in the flat buffer.)"""
-    return isinstance(getattr(model, "item_embedding", None), torch.nn.Embedding)
+    """True for the ID model: the item table (`item_embedding`, see item_table_name) is the nn.Embedding that is updated
+    sparsely / lazily and exchanged as rows.  (FSASRec also has an `item_embedding`, but it is an encoder module whose
+    parameters live in the flat buffer.)"""
+    return isinstance(getattr(model, item_table_name(model), None), torch.nn.Embedding)
+
+
+def item_table(model) -> torch.nn.Parameter:
+    """The item table's weight (has_item_table(model) must hold)."""
+    return getattr(model, item_table_name(model)).weight
+
+
+def _is_table(name, model) -> bool:
+    return name == item_table_name(model) + ".weight" and has_item_table(model)
 
 
 def is_torch_adamw_state(sd) -> bool:
@@ -73,8 +89,10 @@ def native_to_torch_state(sd, model, first_index=0):
     state = {}
     if step > 0:     # torch creates a parameter's state at its first step
         for j, name in enumerate(names):
-            if name == "item_embedding.weight" and has_item_table(model):
+            if _is_table(name, model):
                 m, v = sd["table_m"], sd["table_v"]
+            elif _short_name(name, model) is None:
+                continue             # a parameter nothing reads (SRGNN's gnn.linear_edge_f): torch's AdamW keeps no state for it
             else:
                 off, n, shape = model._views[_short_name(name, model)]
                 m, v = sd["m"][off:off + n].view(shape), sd["v"][off:off + n].view(shape)
@@ -101,7 +119,7 @@ def torch_to_native_state(sd, model, group_index=-1):
         if st is None:
             continue
         steps.add(int(float(st["step"])))
-        if name == "item_embedding.weight" and has_item_table(model):
+        if _is_table(name, model):
             out["table_m"], out["table_v"] = st["exp_avg"], st["exp_avg_sq"]
             continue
         off, n, shape = model._views[_short_name(name, model)]
@@ -114,7 +132,7 @@ def torch_to_native_state(sd, model, group_index=-1):
     out["step"] = steps.pop() if steps else 0
     out["m"], out["v"] = m, v
     if has_item_table(model) and "table_m" not in out:
-        t = model.item_embedding.weight
+        t = item_table(model)
         out["table_m"], out["table_v"] = torch.zeros_like(t), torch.zeros_like(t)
     return out
 
@@ -172,7 +190,7 @@ class PxrAdamW:
                 self._step_dev = torch.full((1,), self.step_count, dtype=torch.int64, device=dev)
                 self._seeded_cfg = None
             return flat, None
-        table = self.model.item_embedding.weight.data
+        table = item_table(self.model).data
         if self._tm is None or self._tm.device != dev or self._tm.shape != table.shape:
             self._tm, self._tv = torch.zeros_like(table), torch.zeros_like(table)
             self._slot = torch.empty(table.shape[0], dtype=torch.int32, device=dev)
@@ -195,7 +213,7 @@ class PxrAdamW:
         if self.table_update != "lazy" or self._last is None or not self.has_table:
             return
         b1, b2 = self.param_groups[0]["betas"]
-        ops.adamw_rows(self.model.item_embedding.weight.data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
+        ops.adamw_rows(item_table(self.model).data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
                        self.step_count, 0, b1, b2, self.param_groups[0]["eps"], rows=idx, n_rows=n_dev, max_rows=cap,
                        step_dev=self._step_dev, max_blocks=max_blocks)
 
@@ -205,7 +223,7 @@ class PxrAdamW:
         if self.table_update != "lazy" or self._last is None or not self.has_table:
             return False
         b1, b2 = self.param_groups[0]["betas"]
-        ops.adamw_rows_ids(self.model.item_embedding.weight.data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
+        ops.adamw_rows_ids(item_table(self.model).data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
                            self.step_count, b1, b2, self.param_groups[0]["eps"], ids, step_dev=self._step_dev)
         return True
 
@@ -218,7 +236,7 @@ class PxrAdamW:
         B, _, W = items.shape
         if self._cur_hyper is None or self._cur_hyper.device != items.device:
             self._cur_hyper = torch.zeros(4, dtype=torch.float32, device=items.device)
-        ops.adamw_rows_ids2d(self.model.item_embedding.weight.data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
+        ops.adamw_rows_ids2d(item_table(self.model).data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
                              self.step_count, b1, b2, self.param_groups[0]["eps"], items, B, W - 1, 2 * W, step_dev=self._step_dev,
                              cur_hyper_out=self._cur_hyper)
         # the launch left the scalars of step step_count + 1 in _cur_hyper: step() may read them there and close the step in
@@ -231,7 +249,7 @@ class PxrAdamW:
         if self.table_update != "lazy" or not self._dirty or self._last is None:
             return
         b1, b2 = self.param_groups[0]["betas"]
-        ops.adamw_rows(self.model.item_embedding.weight.data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
+        ops.adamw_rows(item_table(self.model).data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
                        self.step_count, 0, b1, b2, self.param_groups[0]["eps"], step_dev=self._step_dev)
         self._dirty = False
 
@@ -598,7 +616,7 @@ class FragmentAdamW:
             st = self._state.get(name)
             if st is None:
                 st = self._state[name] = (torch.zeros_like(p.data), torch.zeros_like(p.data))
-            if self.has_table and p is self.model.item_embedding.weight:
+            if self.has_table and p is item_table(self.model):
                 if self._slot is None or self._slot.numel() != p.shape[0] or self._slot.device != p.device:
                     self._slot = torch.empty(p.shape[0], dtype=torch.int32, device=p.device)
                     ops.slot_fill(self._slot, -1)
