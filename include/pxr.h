@@ -639,6 +639,31 @@ int pxr_srgnn_pair_bwd_f32(const float* table, int64_t n_table, int D, const int
                            float grad_scale, const float* grad_scale_dev, float* dout, int64_t ld_dout, float* coef_out,
                            int64_t coef_stride, void* stream);
 
+/* ---- LightSANs (model/IDNet/lightsans.py; model/layers.py:762-932 ItemToInterestAggregation / LightMultiHeadAttention; ------ */
+/* ---- csrc/lightsans.hip).  One workgroup per sequence; fp32 throughout, no float atomics, sums in a fixed order.  Limits:   */
+/* ---- 1 <= L <= 64, D <= 1024 with D % (4H) == 0, 1 <= K <= 16 (anything else fails with a message).                        */
+/* Forward core (layers.py:784-790, 839-878 up to the merged context), no mask anywhere.  qkv [B*L, 3D] = q | k | v rows;
+ * theta [2, D, K] = attpooling_key.theta | attpooling_value.theta; A [H, L, L] = the position probabilities.
+ * pi_K = softmax over l of (k thK), Kp = pi_K^T k (Vp from v and thV); per head S = q_h Kp_h^T / sqrt(dh), P = softmax over the
+ * QUERIES (dim -2), P~ = dropout(P) with keep(seed + *step_dev, stream_id, ((b H + h) L + i) K + k) (the counter hash of
+ * pxr_dropout_f32, scaled 1/(1-p)); ctx [B*L, D] (head-merged) = P~ Vp_h + A_h v_h.  KVp [B, 2K, D] = Kp rows then Vp rows
+ * (always written); pi [B, 2, L, K] (pi_K | pi_V) and probs [B, H, L, K] (P before dropout) are saved for the backward, both or
+ * neither (NULL for inference). */
+int pxr_lightsans_fwd_f32(const float* qkv, const float* theta, const float* A, int B, int L, int D, int H, int K, float p_drop,
+                          uint64_t seed, uint32_t stream_id, const int64_t* step_dev, float* ctx, float* pi, float* probs, float* KVp,
+                          void* stream);
+/* Its backward from dctx [B*L, D]: dqkv [B*L, 3D] (every path into k and v summed: pooled, through the interest logits and, for v,
+ * the positional one); dKVp [B, 2K, D] = d Kp | d Vp; per-sequence parts dtheta_part [B, 2 D K] of d thK | d thV and dA_part
+ * [B, H L L] of d A, each reduced over B by pxr_colsum_f32.  Same dropout arguments as the forward. */
+int pxr_lightsans_bwd_f32(const float* dctx, const float* qkv, const float* theta, const float* A, const float* pi, const float* probs,
+                          const float* KVp, int B, int L, int D, int H, int K, float p_drop, uint64_t seed, uint32_t stream_id,
+                          const int64_t* step_dev, float* dqkv, float* dKVp, float* dtheta_part, float* dA_part, void* stream);
+/* Position probabilities (layers.py:862-868), one workgroup per head: pqk [L, 2D] = pos_ln(P) Wpq^T + bpq | pos_ln(P) Wpk^T + bpk;
+ * A[h, i, j] = softmax over the queries i of (pq_h[i] . pk_h[j]) (2 dh)^-1/2 / sqrt(dh).  The backward takes dA [H, L, L] (the
+ * reduced dA_part) to dpqk [L, 2D] = d pq | d pk. */
+int pxr_lightsans_pos_fwd_f32(const float* pqk, int L, int D, int H, float* A, void* stream);
+int pxr_lightsans_pos_bwd_f32(const float* pqk, const float* A, const float* dA, int L, int D, int H, float* dpqk, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

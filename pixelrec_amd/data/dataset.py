@@ -216,6 +216,66 @@ class BERT4RecTrainBatcher(SeqTrainBatcher):
         items = np.stack((inp, pos, neg), axis=1)
         return items, masked.astype(np.int64)
 
+class TwoTowerTrainBatcher:
+    """Vectorised TwoTowerTrainDataset (reference REC/data/dataset/trainset.py:256-290) under torch's DistributedSampler order.  The
+    reference tags LightSANs AUGSEQ, so its train_feat['item_seq'] holds every prefix of length >= 2 of every training chunk
+    (Data._build_aug_seq, as for SRGNN) and each prefix is one row: the prefix followed by one negative, left-padded with 0 to
+    L+2.  The negative is uniform over [1, item_num - 1] and redrawn while it lies in the prefix, target included -- the
+    reference's distribution, not its random stream.  Yields whole (history int64 [B, L] = row[:, :L], target int64 [B, 2] =
+    (row[:, L], row[:, L+1])) batches: the two tensors the training loop stages (LightSANs.forward joins them).  The sample order
+    and the split by rank are SeqTrainBatcher's."""
+
+    MAX_REDRAWS = 1000
+
+    def __init__(self, config, dataload, rank=0, world=1, seed=0, drop_last=False):
+        self.dataload = dataload
+        self.item_num = dataload.item_num
+        self.L = config["MAX_ITEM_LIST_LENGTH"]
+        self.batch_size = config["train_batch_size"]
+        if "seq_start" not in dataload.train_feat:
+            raise ValueError("TwoTowerTrainBatcher reads the AUGSEQ prefixes: build the data with MODEL_INPUT_TYPE = AUGSEQ")
+        self.flat = np.asarray(dataload._sorted_items, dtype=np.int64)
+        self.start = np.asarray(dataload.train_feat["seq_start"], dtype=np.int64)
+        self.length = np.asarray(dataload.train_feat["seq_len"], dtype=np.int64)
+        self.n = len(self.start)
+        if self.item_num <= 2:
+            raise ValueError("TwoTowerTrainBatcher: no negative can be drawn from [1, item_num) outside a prefix")
+        self.rank, self.world, self.seed, self.epoch = rank, world, seed, 0
+        self.num_samples = -(-self.n // world)
+        self.drop_last = drop_last
+        self.neg_seed = int(config["seed"] or 0)
+
+    set_epoch = SeqTrainBatcher.set_epoch
+    __len__ = SeqTrainBatcher.__len__
+    _indices = SeqTrainBatcher._indices
+
+    def make_batch(self, rows, rng):
+        st, ln = self.start[rows], self.length[rows]                   # prefix length: 2 .. L+1
+        W = self.L + 1
+        col = np.arange(W, dtype=np.int64)[None, :]
+        pad = (W - ln)[:, None]
+        real = col >= pad                                              # the prefix, left-padded to L+1
+        win = np.where(real, self.flat[np.where(real, st[:, None] + col - pad, 0)], 0)
+        neg = self._draw_negatives(win, real, rng)
+        return win[:, :W - 1].copy(), np.stack((win[:, W - 1], neg), axis=1)
+
+    def _draw_negatives(self, win, real, rng):
+        neg = rng.integers(1, self.item_num, size=len(win))
+        for _ in range(self.MAX_REDRAWS):
+            clash = ((neg[:, None] == win) & real).any(1)
+            if not clash.any():
+                return neg
+            neg[clash] = rng.integers(1, self.item_num, size=int(clash.sum()))
+        raise ValueError("TwoTowerTrainBatcher: a prefix covers (nearly) every item: no negative could be drawn")
+
+    def __iter__(self):
+        idx = self._indices()
+        rng = np.random.default_rng([self.neg_seed, self.epoch, self.rank])
+        for b in range(len(self)):
+            hist, target = self.make_batch(idx[b * self.batch_size:(b + 1) * self.batch_size], rng)
+            yield torch.from_numpy(hist), torch.from_numpy(target)
+
+
 class SeqEvalDataset(Dataset):
     def __init__(self, config, dataload, phase="valid"):
         self.dataload = dataload

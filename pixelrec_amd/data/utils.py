@@ -15,11 +15,11 @@ from torch.utils.data import DataLoader
 from ..parallel import world_info
 from .dataload import Data
 from .dataset import (BERT4RecTrainBatcher, GraphEvalBatcher, GraphTrainBatcher, PairEvalBatcher, PairTrainBatcher, SeqEvalBatcher,
-                      SeqEvalDataset, SeqTrainBatcher, seq_eval_collate)
+                      SeqEvalDataset, SeqTrainBatcher, TwoTowerTrainBatcher, seq_eval_collate)
 
 SUPPORTED = {"SASRec": "SEQ", "MOSASRec": "SEQ", "FSASRec": "SEQ", "GRU4Rec": "SEQ", "NextItNet": "SEQ",
              "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR",
-             "SRGNN": "AUGSEQ"}      # REC/data/utils.py:24-31
+             "SRGNN": "AUGSEQ", "LightSANs": "TWOTOWER"}      # REC/data/utils.py:24-31
 
 
 def load_data(config):
@@ -87,8 +87,9 @@ def bulid_dataloader(config, dataload):
         train_loader = _GraphTrainLoader(GraphTrainBatcher(config, dataload, rank=rank, world=world))
         return (train_loader, GraphEvalBatcher(config, dataload, phase="valid", rank=rank, world=world),
                 GraphEvalBatcher(config, dataload, phase="test", rank=rank, world=world))
-    # BERT4Rec masks its windows (REC/data/utils.py:25: BERT4RecTrainDataset); evaluation is SeqEvalDataset's for both
-    batcher = BERT4RecTrainBatcher if model_name == "BERT4Rec" else SeqTrainBatcher
+    # BERT4Rec masks its windows (REC/data/utils.py:25: BERT4RecTrainDataset); LightSANs (AUGSEQ, so Data built every prefix)
+    # reads TwoTowerTrainDataset's rows of those prefixes (:35); evaluation is SeqEvalDataset's for all of them
+    batcher = {"BERT4Rec": BERT4RecTrainBatcher, "LightSANs": TwoTowerTrainBatcher}.get(model_name, SeqTrainBatcher)
     train_loader = _TrainLoader(batcher(config, dataload, rank=rank, world=world))
     loaders = []
     workers = int(config["eval_num_workers"] or 0)

@@ -147,6 +147,10 @@ _SIGNATURES = {
     "pxr_srgnn_readout_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "pxr_srgnn_pair_fwd_f32": (_I, [_P, _I64, _P, _I64, _I, _P, _I, _P, _P, _P, _P]),
     "pxr_srgnn_pair_bwd_f32": (_I, [_P, _I64, _I, _P, _P, _I, _F, _P, _P, _I64, _P, _I64, _P]),
+    "pxr_lightsans_fwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _U64, _U32, _P, _P, _P, _P, _P, _P]),
+    "pxr_lightsans_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _U64, _U32, _P, _P, _P, _P, _P, _P]),
+    "pxr_lightsans_pos_fwd_f32": (_I, [_P, _I, _I, _I, _P, _P]),
+    "pxr_lightsans_pos_bwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
 }
 
 

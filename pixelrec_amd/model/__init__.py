@@ -9,4 +9,5 @@ from .mogru4rec import MOGRU4Rec  # noqa: F401
 from .monextitnet import MONextItNet  # noqa: F401
 from .lightgcn import LightGCN  # noqa: F401
 from .srgnn import SRGNN  # noqa: F401
+from .lightsans import LightSANs  # noqa: F401
 from .sharded import ShardedDataParallel, ShardedSASRec  # noqa: F401

@@ -1935,3 +1935,84 @@ def srgnn_pair_bwd(table, target, coef, dout, ld_dout: int, grad_scale=1.0, grad
                                        _l.ptr(grad_scale_dev), _l.ptr(dout), ld_dout, _l.ptr(coef_out), coef_stride,
                                        _l.stream_ptr()), "pxr_srgnn_pair_bwd_f32")
     return dout
+
+
+# ------------------------------------------------------------------------------------------------ LightSANs (csrc/lightsans.hip)
+LIGHTSANS_MAX_L, LIGHTSANS_MAX_D, LIGHTSANS_MAX_K = 64, 1024, 16
+
+
+def lightsans_shape_error(L: int, D: int, H: int, K: int):
+    """The message the kernels would fail with for this shape, or None when they serve it (checked before any launch)."""
+    if not 1 <= L <= LIGHTSANS_MAX_L:
+        return f"MAX_ITEM_LIST_LENGTH={L} outside 1..{LIGHTSANS_MAX_L}"
+    if H < 1 or D < 4 or D > LIGHTSANS_MAX_D or D % (4 * H):
+        return f"embedding_size={D} with n_heads={H}: need D <= {LIGHTSANS_MAX_D} and D % (4 * n_heads) == 0"
+    if not 1 <= K <= LIGHTSANS_MAX_K:
+        return f"k_interests={K} outside 1..{LIGHTSANS_MAX_K}"
+    return None
+
+
+def lightsans_fwd(qkv, theta, A, B: int, L: int, H: int, K: int, p_drop=0.0, seed=0, stream_id=0, step_dev=None, save=True):
+    """Low-rank interest attention (layers.py:784-790, 839-878): qkv [B*L, 3D], theta [2, D, K] (thK | thV), A [H, L, L] ->
+    (ctx [B*L, D], saved dict(pi [B, 2, L, K], probs [B, H, L, K], KVp [B, 2K, D]) | None without save)."""
+    Lb = _l.load()
+    _req(qkv, torch.float32, "qkv"); _req(theta, torch.float32, "theta"); _req(A, torch.float32, "A")
+    D = qkv.shape[-1] // 3
+    if qkv.numel() != B * L * 3 * D or theta.numel() != 2 * D * K or A.numel() != H * L * L:
+        raise _l.PxrError(f"lightsans fwd: qkv {tuple(qkv.shape)} / theta {tuple(theta.shape)} / A {tuple(A.shape)} do not match "
+                          f"B={B}, L={L}, H={H}, K={K}")
+    dev = qkv.device
+    ctx = torch.empty(B * L, D, dtype=torch.float32, device=dev)
+    KVp = torch.empty(B, 2 * K, D, dtype=torch.float32, device=dev)
+    pi = torch.empty(B, 2, L, K, dtype=torch.float32, device=dev) if save else None
+    probs = torch.empty(B, H, L, K, dtype=torch.float32, device=dev) if save else None
+    _l.check(Lb.pxr_lightsans_fwd_f32(_l.ptr(qkv), _l.ptr(theta), _l.ptr(A), B, L, D, H, K, float(p_drop), seed & 0xFFFFFFFFFFFFFFFF,
+                                      stream_id, _l.ptr(step_dev), _l.ptr(ctx), _l.ptr(pi), _l.ptr(probs), _l.ptr(KVp), _l.stream_ptr()),
+             "pxr_lightsans_fwd_f32")
+    return ctx, (dict(pi=pi, probs=probs, KVp=KVp) if save else None)
+
+
+def lightsans_bwd(dctx, qkv, theta, A, saved, B: int, L: int, H: int, K: int, p_drop=0.0, seed=0, stream_id=0, step_dev=None):
+    """-> (dqkv [B*L, 3D], dKVp [B, 2K, D], dtheta_part [B, 2DK], dA_part [B, HLL]); the parts are reduced with colsum."""
+    Lb = _l.load()
+    D = qkv.shape[-1] // 3
+    want = {"dctx": (dctx, B * L * D), "qkv": (qkv, B * L * 3 * D), "theta": (theta, 2 * D * K), "A": (A, H * L * L),
+            "pi": (saved["pi"], B * 2 * L * K), "probs": (saved["probs"], B * H * L * K), "KVp": (saved["KVp"], B * 2 * K * D)}
+    for name, (t, n) in want.items():
+        _req(t, torch.float32, name)
+        if t.numel() != n:
+            raise _l.PxrError(f"lightsans bwd: {name} has {t.numel()} elements, B={B}, L={L}, D={D}, H={H}, K={K} need {n}")
+    dev = qkv.device
+    dqkv = torch.empty(B * L, 3 * D, dtype=torch.float32, device=dev)
+    dKVp = torch.empty(B, 2 * K, D, dtype=torch.float32, device=dev)
+    dth = torch.empty(B, 2 * D * K, dtype=torch.float32, device=dev)
+    dA = torch.empty(B, H * L * L, dtype=torch.float32, device=dev)
+    _l.check(Lb.pxr_lightsans_bwd_f32(_l.ptr(dctx), _l.ptr(qkv), _l.ptr(theta), _l.ptr(A), _l.ptr(saved["pi"]), _l.ptr(saved["probs"]),
+                                      _l.ptr(saved["KVp"]), B, L, D, H, K, float(p_drop), seed & 0xFFFFFFFFFFFFFFFF, stream_id,
+                                      _l.ptr(step_dev), _l.ptr(dqkv), _l.ptr(dKVp), _l.ptr(dth), _l.ptr(dA), _l.stream_ptr()),
+             "pxr_lightsans_bwd_f32")
+    return dqkv, dKVp, dth, dA
+
+
+def lightsans_pos_fwd(pqk, H: int):
+    """pqk [L, 2D] = pq | pk (before pos_scaling) -> A [H, L, L], softmax over the queries (layers.py:862-868)."""
+    Lb = _l.load()
+    _req(pqk, torch.float32, "pqk")
+    L, D2 = pqk.shape
+    A = torch.empty(H, L, L, dtype=torch.float32, device=pqk.device)
+    _l.check(Lb.pxr_lightsans_pos_fwd_f32(_l.ptr(pqk), L, D2 // 2, H, _l.ptr(A), _l.stream_ptr()), "pxr_lightsans_pos_fwd_f32")
+    return A
+
+
+def lightsans_pos_bwd(pqk, A, dA):
+    """dA [H, L, L] -> dpqk [L, 2D] = d pq | d pk."""
+    Lb = _l.load()
+    _req(pqk, torch.float32, "pqk"); _req(A, torch.float32, "A"); _req(dA, torch.float32, "dA")
+    L, D2 = pqk.shape
+    H = A.shape[0]
+    if A.numel() != H * L * L or dA.numel() != H * L * L:
+        raise _l.PxrError(f"lightsans pos bwd: A {tuple(A.shape)} / dA {tuple(dA.shape)} do not match L={L}, H={H}")
+    dpqk = torch.empty_like(pqk)
+    _l.check(Lb.pxr_lightsans_pos_bwd_f32(_l.ptr(pqk), _l.ptr(A), _l.ptr(dA), L, D2 // 2, H, _l.ptr(dpqk), _l.stream_ptr()),
+             "pxr_lightsans_pos_bwd_f32")
+    return dpqk
