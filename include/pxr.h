@@ -664,6 +664,44 @@ int pxr_lightsans_bwd_f32(const float* dctx, const float* qkv, const float* thet
 int pxr_lightsans_pos_fwd_f32(const float* pqk, int L, int D, int H, float* A, void* stream);
 int pxr_lightsans_pos_bwd_f32(const float* pqk, const float* A, const float* dA, int L, int D, int H, float* dpqk, void* stream);
 
+/* ---- MF (model/IDNet/mf.py, layers.py:239-294 MLPLayers; csrc/mf.hip) ------------------------------------------------------- */
+/* The table is ONE [1 + n_users + n_items, D] buffer: user u at row 1 + u, item i at row 1 + n_users + i, row 0 a spare (the
+ * sparse-row kernels treat id 0 as padding / an empty slot).  rows[3B] = [1 + user[b] for b < B | the rows of item.view(-1)]
+ * (item [B, 2] = (positive, negative)); item == NULL: the B user rows only.  An id outside [0, n_users) / [0, n_items) ORs bit 0
+ * into the status word (clamped). */
+int pxr_mf_pair_rows_i64(const int64_t* user, const int64_t* item, int B, int64_t n_users, int64_t n_items, int64_t* rows,
+                         void* stream);
+/* Pair loss head (mf.py forward): x_b = <u_b, i+_b> - <u_b, i-_b>, lossrow[b] = -(1e-8 + log sigmoid(x_b)), loss = mean,
+ * coef[b] = d loss / d x_b = -(1 - sigmoid(x_b)) / B.  rows != NULL: u_b = ufeat[rows[b]], i+-_b = ifeat[rows[B + 2b (+1)]]
+ * (the table, ufeat == ifeat); rows == NULL: the tower outputs, u_b = ufeat[b] ([B, H]), i+-_b = ifeat[2b (+1)] ([2B, H]).
+ * H % 4 == 0, H <= 4096. */
+int pxr_mf_pair_fwd_f32(const float* ufeat, const float* ifeat, const int64_t* rows, int H, int B, float* coef, float* lossrow,
+                        float* loss, void* stream);
+/* Its backward onto the tower outputs: du[b] = c_b (i+_b - i-_b), di[2b] = c_b u_b, di[2b + 1] = -c_b u_b with c_b = coef[b] *
+ * grad_scale * (*grad_scale_dev if given). */
+int pxr_mf_pair_bwd_f32(const float* ufeat, const float* ifeat, const float* coef, int H, int B, float grad_scale,
+                        const float* grad_scale_dev, float* du, float* di, void* stream);
+/* The step's table gradient as sparse rows (SparseRows: sp_idx int64 [cap], sp_rows [cap, D], *sp_n = 3B): slot o of occurrence
+ * o = (rows[o], the sum of every occurrence of that row in ascending order) for the first occurrence of a row, (0, zeros) for the
+ * others.  occ != NULL: occurrence k contributes occ[k, :] ([3B, D], the towers' input gradients in the rows[] layout); occ ==
+ * NULL: the head's formula on table [n_table, D] with coef (scaled as above).  O(B D) work, deterministic, no atomics.  D % 4 ==
+ * 0, D <= 4096, cap >= 3B. */
+int pxr_mf_table_grad_f32(const float* table, int64_t n_table, int D, const int64_t* rows, int B, const float* coef,
+                          const float* occ, float grad_scale, const float* grad_scale_dev, int64_t* sp_idx, float* sp_rows,
+                          int32_t* sp_n, int64_t cap, void* stream);
+/* BatchNorm1d (training) + tanh over x [R, H]: batch mean and biased variance (eps), y = tanh(gamma xhat + beta); mean / rstd
+ * [H] saved for the backward; running_mean / running_var updated with momentum and the unbiased variance, *num_batches_tracked
+ * += 1 (may be NULL).  Column sums in a fixed order.  R >= 2, H % 4 == 0, H <= 4096; y must not alias x. */
+int pxr_mf_bn_tanh_fwd_f32(const float* x, int R, int H, const float* gamma, const float* beta, float eps, float momentum,
+                           float* running_mean, float* running_var, int64_t* num_batches_tracked, float* y, float* mean,
+                           float* rstd, void* stream);
+/* Its backward from dy [R, H] through the tanh (y) and the batch statistics: dx [R, H], dgamma / dbeta [H] (overwritten). */
+int pxr_mf_bn_tanh_bwd_f32(const float* dy, const float* x, const float* y, const float* mean, const float* rstd,
+                           const float* gamma, int R, int H, float* dx, float* dgamma, float* dbeta, void* stream);
+/* Eval form: y = tanh(gamma (x - running_mean) / sqrt(running_var + eps) + beta), elementwise over [R, H]. */
+int pxr_mf_bn_tanh_eval_f32(const float* x, int64_t R, int H, const float* gamma, const float* beta, const float* running_mean,
+                            const float* running_var, float eps, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

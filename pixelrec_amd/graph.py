@@ -90,7 +90,7 @@ class GraphedTrainStep:
         self.model._step_counter = st[1]
 
     def _dry_run(self):
-        from .optim import item_table
+        from .optim import lazy_table
 
         m, o = self.model, self.opt
         if hasattr(o, "opts"):
@@ -101,7 +101,10 @@ class GraphedTrainStep:
         table_state = None
         if getattr(o, "has_table", False):
             o.flush()
-            table_state = [t.clone() for t in (item_table(m).data, o._tm, o._tv, o._last)]
+            table_state = [t.clone() for t in (lazy_table(m).data, o._tm, o._tv, o._last)]
+        # state the step advances on the device besides the optimizer's (MF's BatchNorm running statistics)
+        running = list(m.running_state_buffers()) if hasattr(m, "running_state_buffers") else []
+        running_keep = [t.clone() for t in running]
         counters = (o.step_count, m._step_counter, o._dirty, o._step_dev.clone(), m._drop_dev.clone())
         acc = self.loss_sum.clone() if self.loss_sum is not None else None
         self._eager_holding()
@@ -110,8 +113,10 @@ class GraphedTrainStep:
         for dst, src in zip((flat, o._m, o._v), keep):
             dst.copy_(src)
         if table_state is not None:
-            for dst, src in zip((item_table(m).data, o._tm, o._tv, o._last), table_state):
+            for dst, src in zip((lazy_table(m).data, o._tm, o._tv, o._last), table_state):
                 dst.copy_(src)
+        for dst, src in zip(running, running_keep):
+            dst.copy_(src)
         o.step_count, m._step_counter, o._dirty = counters[:3]
         o._step_dev.copy_(counters[3])
         m._drop_dev.copy_(counters[4])

@@ -10,4 +10,5 @@ from .monextitnet import MONextItNet  # noqa: F401
 from .lightgcn import LightGCN  # noqa: F401
 from .srgnn import SRGNN  # noqa: F401
 from .lightsans import LightSANs  # noqa: F401
+from .mf import MF  # noqa: F401
 from .sharded import ShardedDataParallel, ShardedSASRec  # noqa: F401

@@ -2016,3 +2016,122 @@ def lightsans_pos_bwd(pqk, A, dA):
     _l.check(Lb.pxr_lightsans_pos_bwd_f32(_l.ptr(pqk), _l.ptr(A), _l.ptr(dA), L, D2 // 2, H, _l.ptr(dpqk), _l.stream_ptr()),
              "pxr_lightsans_pos_bwd_f32")
     return dpqk
+
+
+# ------------------------------------------------------------------------------------------------ MF (csrc/mf.hip)
+def mf_pair_rows(user, item, n_users: int, n_items: int, out=None):
+    """user int64 [B], item int64 [B, 2] | None -> rows int64 [3B] (or [B]) of the [1 + U + I, D] table: [1 + user | 1 + U +
+    item.view(-1)].  Bad ids flag the status word (ops.raise_on_bad_indices) and are clamped."""
+    Lb = _l.load()
+    _req(user, torch.int64, "user")
+    B = user.numel()
+    if item is not None:
+        _req(item, torch.int64, "item")
+        if item.numel() != 2 * B:
+            raise _l.PxrError(f"mf pair rows: item must be [B, 2] for B={B}, got {tuple(item.shape)}")
+    n = 3 * B if item is not None else B
+    rows = out if out is not None else torch.empty(n, dtype=torch.int64, device=user.device)
+    if rows.numel() != n or rows.dtype != torch.int64:
+        raise _l.PxrError(f"mf pair rows: out must be int64 [{n}]")
+    device_status(user.device)
+    _l.check(Lb.pxr_mf_pair_rows_i64(_l.ptr(user), _l.ptr(item), B, int(n_users), int(n_items), _l.ptr(rows), _l.stream_ptr()),
+             "pxr_mf_pair_rows_i64")
+    return rows
+
+
+def mf_pair_fwd(ufeat, ifeat, B: int, rows=None, out=None):
+    """MF's pair loss head (mf.py forward).  rows given: u / i+- read from the table ufeat (= ifeat) at rows [3B]; else ufeat [B, H],
+    ifeat [2B, H] (tower outputs).  -> (loss [1], coef [B] = d loss / d x_b).  out: a float32 [2B + 1] buffer to reuse."""
+    Lb = _l.load()
+    _req(ufeat, torch.float32, "ufeat"); _req(ifeat, torch.float32, "ifeat")
+    H = ufeat.shape[-1]
+    if ifeat.shape[-1] != H:
+        raise _l.PxrError("mf pair head: ufeat and ifeat widths differ")
+    if rows is None and (ufeat.shape[0] != B or ifeat.shape[0] != 2 * B):
+        raise _l.PxrError(f"mf pair head: tower outputs must be [B, H] and [2B, H] for B={B}")
+    if rows is not None:
+        _req(rows, torch.int64, "rows")
+        if rows.numel() != 3 * B:
+            raise _l.PxrError(f"mf pair head: rows must be [3B] for B={B}")
+    f = out if out is not None else torch.empty(2 * B + 1, dtype=torch.float32, device=ufeat.device)
+    coef, lossrow, loss = f[:B], f[B:2 * B], f[2 * B:]
+    _l.check(Lb.pxr_mf_pair_fwd_f32(_l.ptr(ufeat), _l.ptr(ifeat), _l.ptr(rows), H, B, _l.ptr(coef), _l.ptr(lossrow), _l.ptr(loss),
+                                    _l.stream_ptr()), "pxr_mf_pair_fwd_f32")
+    return loss, coef
+
+
+def mf_pair_bwd(ufeat, ifeat, coef, du, di, grad_scale=1.0, grad_scale_dev=None):
+    """du [B, H] / di [2B, H] (overwritten) = the head's gradient onto the tower outputs."""
+    Lb = _l.load()
+    for t, nm in ((ufeat, "ufeat"), (ifeat, "ifeat"), (coef, "coef"), (du, "du"), (di, "di")):
+        _req(t, torch.float32, nm)
+    B, H = ufeat.shape
+    if ifeat.shape != (2 * B, H) or du.shape != (B, H) or di.shape != (2 * B, H) or coef.numel() != B:
+        raise _l.PxrError("mf pair head backward: shapes must be [B, H], [2B, H], coef [B], du [B, H], di [2B, H]")
+    _l.check(Lb.pxr_mf_pair_bwd_f32(_l.ptr(ufeat), _l.ptr(ifeat), _l.ptr(coef), H, B, float(grad_scale), _l.ptr(grad_scale_dev),
+                                    _l.ptr(du), _l.ptr(di), _l.stream_ptr()), "pxr_mf_pair_bwd_f32")
+
+
+def mf_table_grad(rows, B: int, sp: SparseRows, table=None, coef=None, occ=None, grad_scale=1.0, grad_scale_dev=None):
+    """The step's table gradient in sparse form (pxr_mf_table_grad_f32): from the head's formula on `table` with `coef`, or from the
+    per-occurrence rows occ [3B, D] (the towers' input gradients).  Writes sp (cap >= 3B) and returns it."""
+    Lb = _l.load()
+    _req(rows, torch.int64, "rows")
+    if rows.numel() != 3 * B:
+        raise _l.PxrError(f"mf table grad: rows must be [3B] for B={B}")
+    D = sp.rows.shape[1]
+    if occ is not None:
+        _req(occ, torch.float32, "occ")
+        if occ.shape != (3 * B, D):
+            raise _l.PxrError(f"mf table grad: occ must be [3B, D] = [{3 * B}, {D}], got {tuple(occ.shape)}")
+        n_table = 0
+    else:
+        _req(table, torch.float32, "table"); _req(coef, torch.float32, "coef")
+        if table.shape[1] != D or coef.numel() != B:
+            raise _l.PxrError("mf table grad: table width / coef length do not match")
+        n_table = table.shape[0]
+    _l.check(Lb.pxr_mf_table_grad_f32(_l.ptr(table), n_table, D, _l.ptr(rows), B, _l.ptr(coef), _l.ptr(occ), float(grad_scale),
+                                      _l.ptr(grad_scale_dev), _l.ptr(sp.idx), _l.ptr(sp.rows), _l.ptr(sp.n), sp.cap,
+                                      _l.stream_ptr()), "pxr_mf_table_grad_f32")
+    return sp
+
+
+def mf_bn_tanh_fwd(x, gamma, beta, running_mean, running_var, num_batches_tracked, eps=1e-5, momentum=0.1, y=None, stats=None):
+    """Training BatchNorm1d + tanh over x [R, H] (running statistics updated on the device) -> (y, mean [H], rstd [H])."""
+    Lb = _l.load()
+    for t, nm in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _req(t, torch.float32, nm)
+    R, H = x.shape
+    y = y if y is not None else torch.empty_like(x)
+    st = stats if stats is not None else torch.empty(2, H, dtype=torch.float32, device=x.device)
+    _l.check(Lb.pxr_mf_bn_tanh_fwd_f32(_l.ptr(x), R, H, _l.ptr(gamma), _l.ptr(beta), float(eps), float(momentum),
+                                       _l.ptr(running_mean), _l.ptr(running_var), _l.ptr(num_batches_tracked), _l.ptr(y),
+                                       _l.ptr(st[0]), _l.ptr(st[1]), _l.stream_ptr()), "pxr_mf_bn_tanh_fwd_f32")
+    return y, st[0], st[1]
+
+
+def mf_bn_tanh_bwd(dy, x, y, mean, rstd, gamma, dgamma, dbeta, dx=None):
+    """Backward of mf_bn_tanh_fwd: -> dx [R, H]; dgamma / dbeta [H] overwritten."""
+    Lb = _l.load()
+    for t, nm in ((dy, "dy"), (x, "x"), (y, "y"), (mean, "mean"), (rstd, "rstd"), (gamma, "gamma"), (dgamma, "dgamma"),
+                  (dbeta, "dbeta")):
+        _req(t, torch.float32, nm)
+    R, H = x.shape
+    if dy.shape != x.shape or y.shape != x.shape:
+        raise _l.PxrError("mf bn backward: dy, x and y must have one shape")
+    dx = dx if dx is not None else torch.empty_like(x)
+    _l.check(Lb.pxr_mf_bn_tanh_bwd_f32(_l.ptr(dy), _l.ptr(x), _l.ptr(y), _l.ptr(mean), _l.ptr(rstd), _l.ptr(gamma), R, H, _l.ptr(dx),
+                                       _l.ptr(dgamma), _l.ptr(dbeta), _l.stream_ptr()), "pxr_mf_bn_tanh_bwd_f32")
+    return dx
+
+
+def mf_bn_tanh_eval(x, gamma, beta, running_mean, running_var, eps=1e-5, y=None):
+    """Eval-mode BatchNorm1d + tanh over x [R, H] (running statistics)."""
+    Lb = _l.load()
+    for t, nm in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _req(t, torch.float32, nm)
+    R, H = x.shape
+    y = y if y is not None else torch.empty_like(x)
+    _l.check(Lb.pxr_mf_bn_tanh_eval_f32(_l.ptr(x), R, H, _l.ptr(gamma), _l.ptr(beta), _l.ptr(running_mean), _l.ptr(running_var),
+                                        float(eps), _l.ptr(y), _l.stream_ptr()), "pxr_mf_bn_tanh_eval_f32")
+    return y

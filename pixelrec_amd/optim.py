@@ -67,8 +67,25 @@ def item_table(model) -> torch.nn.Parameter:
     return getattr(model, item_table_name(model)).weight
 
 
+def table_spans(model) -> dict:
+    """{reference parameter name: (first row, end row)} of the parameters that share ONE lazily updated table buffer, for a model
+    that hands the optimizer such a buffer through `table_parameter_spans()` (MF: user rows, then item rows); {} otherwise (the
+    item table is then the table, whole)."""
+    return dict(model.table_parameter_spans()) if hasattr(model, "table_parameter_spans") else {}
+
+
+def has_lazy_table(model) -> bool:
+    """True when the model has a table that PxrAdamW updates sparsely / lazily (the item table, or a model's `lazy_table()`)."""
+    return hasattr(model, "table_parameter_spans") or has_item_table(model)
+
+
+def lazy_table(model) -> torch.Tensor:
+    """The whole table buffer the lazy schedule updates (has_lazy_table(model) must hold)."""
+    return model.lazy_table() if hasattr(model, "table_parameter_spans") else item_table(model)
+
+
 def _is_table(name, model) -> bool:
-    return name == item_table_name(model) + ".weight" and has_item_table(model)
+    return (name == item_table_name(model) + ".weight" and has_item_table(model)) or name in table_spans(model)
 
 
 def is_torch_adamw_state(sd) -> bool:
@@ -91,6 +108,9 @@ def native_to_torch_state(sd, model, first_index=0):
         for j, name in enumerate(names):
             if _is_table(name, model):
                 m, v = sd["table_m"], sd["table_v"]
+                span = table_spans(model).get(name)
+                if span is not None:             # one parameter's rows of a shared table buffer
+                    m, v = m[span[0]:span[1]], v[span[0]:span[1]]
             elif _short_name(name, model) is None:
                 continue             # a parameter nothing reads (SRGNN's gnn.linear_edge_f): torch's AdamW keeps no state for it
             else:
@@ -119,6 +139,15 @@ def torch_to_native_state(sd, model, group_index=-1):
         if st is None:
             continue
         steps.add(int(float(st["step"])))
+        span = table_spans(model).get(name)
+        if span is not None:                     # one parameter's rows of a shared table buffer
+            tm, tv = _table_state_buffers(out, model)
+            lo, hi = span
+            if tuple(st["exp_avg"].shape) != tuple(tm[lo:hi].shape):
+                raise ValueError(f"optimizer state of {name}: shape {tuple(st['exp_avg'].shape)} != {tuple(tm[lo:hi].shape)}")
+            tm[lo:hi].copy_(st["exp_avg"])
+            tv[lo:hi].copy_(st["exp_avg_sq"])
+            continue
         if _is_table(name, model):
             out["table_m"], out["table_v"] = st["exp_avg"], st["exp_avg_sq"]
             continue
@@ -134,7 +163,17 @@ def torch_to_native_state(sd, model, group_index=-1):
     if has_item_table(model) and "table_m" not in out:
         t = item_table(model)
         out["table_m"], out["table_v"] = torch.zeros_like(t), torch.zeros_like(t)
+    elif table_spans(model):
+        _table_state_buffers(out, model)
     return out
+
+
+def _table_state_buffers(out, model):
+    """(table_m, table_v) of a native state under construction: zeros of the table's shape, made on first use."""
+    if "table_m" not in out:
+        t = lazy_table(model)
+        out["table_m"], out["table_v"] = torch.zeros_like(t), torch.zeros_like(t)
+    return out["table_m"], out["table_v"]
 
 
 def _short_name(name, model=None):
@@ -174,7 +213,7 @@ class PxrAdamW:
         self._dirty = False          # lazy mode: some rows lag behind step_count (set by step, cleared by flush)
         self._seeded_cfg = None      # hyper-parameters the table entry of step_count+1 was written with (None: not yet)
         self.param_groups = [{"lr": self.lr, "weight_decay": self.weight_decay, "betas": self.betas, "eps": self.eps}]
-        self.has_table = has_item_table(model)
+        self.has_table = has_lazy_table(model)
         if table_update == "lazy" and self.has_table:
             model.register_table_hooks(self)
 
@@ -190,7 +229,7 @@ class PxrAdamW:
                 self._step_dev = torch.full((1,), self.step_count, dtype=torch.int64, device=dev)
                 self._seeded_cfg = None
             return flat, None
-        table = item_table(self.model).data
+        table = lazy_table(self.model).data
         if self._tm is None or self._tm.device != dev or self._tm.shape != table.shape:
             self._tm, self._tv = torch.zeros_like(table), torch.zeros_like(table)
             self._slot = torch.empty(table.shape[0], dtype=torch.int32, device=dev)
@@ -213,7 +252,7 @@ class PxrAdamW:
         if self.table_update != "lazy" or self._last is None or not self.has_table:
             return
         b1, b2 = self.param_groups[0]["betas"]
-        ops.adamw_rows(item_table(self.model).data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
+        ops.adamw_rows(lazy_table(self.model).data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
                        self.step_count, 0, b1, b2, self.param_groups[0]["eps"], rows=idx, n_rows=n_dev, max_rows=cap,
                        step_dev=self._step_dev, max_blocks=max_blocks)
 
@@ -223,7 +262,7 @@ class PxrAdamW:
         if self.table_update != "lazy" or self._last is None or not self.has_table:
             return False
         b1, b2 = self.param_groups[0]["betas"]
-        ops.adamw_rows_ids(item_table(self.model).data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
+        ops.adamw_rows_ids(lazy_table(self.model).data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
                            self.step_count, b1, b2, self.param_groups[0]["eps"], ids, step_dev=self._step_dev)
         return True
 
@@ -236,7 +275,7 @@ class PxrAdamW:
         B, _, W = items.shape
         if self._cur_hyper is None or self._cur_hyper.device != items.device:
             self._cur_hyper = torch.zeros(4, dtype=torch.float32, device=items.device)
-        ops.adamw_rows_ids2d(item_table(self.model).data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
+        ops.adamw_rows_ids2d(lazy_table(self.model).data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
                              self.step_count, b1, b2, self.param_groups[0]["eps"], items, B, W - 1, 2 * W, step_dev=self._step_dev,
                              cur_hyper_out=self._cur_hyper)
         # the launch left the scalars of step step_count + 1 in _cur_hyper: step() may read them there and close the step in
@@ -249,7 +288,7 @@ class PxrAdamW:
         if self.table_update != "lazy" or not self._dirty or self._last is None:
             return
         b1, b2 = self.param_groups[0]["betas"]
-        ops.adamw_rows(item_table(self.model).data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
+        ops.adamw_rows(lazy_table(self.model).data, self._tm, self._tv, self._last, self._hyper, self._cumlog,
                        self.step_count, 0, b1, b2, self.param_groups[0]["eps"], step_dev=self._step_dev)
         self._dirty = False
 
@@ -378,7 +417,7 @@ def clip_grad_norm_(model, max_norm, norm_type=2.0, **_ignored):
         model.wait_flat_grads()
     _, gflat = model.flat_parameters()
     sq = gflat.pow(2).sum()
-    sp = getattr(model, "sparse_table_grad", None) if has_item_table(model) else None
+    sp = getattr(model, "sparse_table_grad", None) if has_lazy_table(model) else None
     live = None
     if sp is not None:
         ar = torch.arange(sp.rows.shape[0], device=sp.rows.device, dtype=torch.int32)
@@ -588,6 +627,9 @@ class FragmentAdamW:
         if hasattr(self.model, "trust_optimizer_planes"):
             self.model.trust_optimizer_planes = False
         self.has_table = has_item_table(self.model)
+        if hasattr(self.model, "table_parameter_spans"):
+            raise NotImplementedError("FragmentAdamW (decay_check_name) is not built for a model whose table buffer spans several "
+                                      "parameters (MF)")
 
     def _named(self):
         """[(name as the reference's DDP-wrapped model yields it, parameter)] of the trainable parameters, named_parameters() order."""
