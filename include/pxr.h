@@ -702,6 +702,41 @@ int pxr_mf_bn_tanh_bwd_f32(const float* dy, const float* x, const float* y, cons
 int pxr_mf_bn_tanh_eval_f32(const float* x, int64_t R, int H, const float* gamma, const float* beta, const float* running_mean,
                             const float* running_var, float eps, float* y, void* stream);
 
+/* ---- VBPR (model/ViNet/vbpr.py; csrc/vbpr.hip) ----------------------------------------------------------------------------- */
+/* The tables are ONE [1 + 2 n_users + n_items, Dh] buffer in the reference's parameter order: user_id_embedding row u at 1 + u,
+ * item_id_embedding row i at 1 + n_users + i, user_modal_embedding row u at 1 + n_users + n_items + u, row 0 a spare (the
+ * sparse-row kernels treat id 0 as padding / an empty slot).  rows[4B] = [id row of user[b] | modal row of user[b] | id rows of
+ * item.view(-1)] (item [B, 2] = (positive, negative)); item == NULL: the 2B user rows only (vbpr.py:57-60 forward's three
+ * embedding lookups, :79-82 predict's).  An id outside [0, n_users) / [0, n_items) ORs bit 0 into the status word (clamped). */
+int pxr_vbpr_rows_i64(const int64_t* user, const int64_t* item, int B, int64_t n_users, int64_t n_items, int64_t* rows,
+                      void* stream);
+/* Feature gather with the visual bias fused (vbpr.py:61,65 self.v_feat[item] read twice, :94 compute_item_all's bias): out[r, :]
+ * = feat[item[r], :] ([n, F], the projection GEMM's operand) and beta[r] = <feat[item[r], :], wb> from one read of the row.
+ * item == NULL: row r itself (n <= n_items); out == NULL: beta only.  Item ids outside [0, n_items) flag and clamp.  F % 4 == 0. */
+int pxr_vbpr_gather_f32(const float* feat, int64_t n_items, int F, const int64_t* item, int64_t n, const float* wb, float* out,
+                        float* beta, void* stream);
+/* Pair head (vbpr.py:64-70): s_{b,t} = <uid_b, iid_{b,t}> + <um_b, e[2b + t]> + beta[2b + t] with the id rows read from table at
+ * rows[4B]; x_b = s_{b,0} - s_{b,1}; lossrow[b] = -log(1e-8 + sigmoid(x_b)), loss = mean; coef[b] = d loss / d x_b.
+ * Dh % 4 == 0, Dh <= 4096. */
+int pxr_vbpr_pair_fwd_f32(const float* table, const int64_t* rows, const float* e, const float* beta, int Dh, int B, float* coef,
+                          float* lossrow, float* loss, void* stream);
+/* Its backward (autograd of vbpr.py:57-70), c_b = coef[b] * grad_scale * (*grad_scale_dev if given): de[2b + t] = +-c_b um_b
+ * ([2B, Dh], the weight-gradient GEMM's operand), csign[2b + t] = +-c_b, and the three tables' gradient as sparse rows
+ * (SparseRows: sp_idx int64 [cap], sp_rows [cap, Dh], *sp_n = 4B): slot o of occurrence o = (rows[o], the sum of every occurrence
+ * of that row in ascending order) for the first occurrence of a row, (0, zeros) for the others; occurrences contribute c_b (iid+ -
+ * iid-) (id row of the user), c_b (e+ - e-) (modal row), +-c_b uid_b (item rows).  Deterministic, no atomics.  cap >= 4B. */
+int pxr_vbpr_pair_bwd_f32(const float* table, const int64_t* rows, const float* e, const float* coef, int Dh, int B,
+                          float grad_scale, const float* grad_scale_dev, float* de, float* csign, int64_t* sp_idx, float* sp_rows,
+                          int32_t* sp_n, int64_t cap, void* stream);
+/* Gradient of bias_projection.weight (autograd of vbpr.py:65): dwb[F] = sum_r csign[r] x[r, :] over the gathered rows x [R, F],
+ * column sums in a fixed order.  F % 4 == 0. */
+int pxr_vbpr_bias_grad_f32(const float* x, const float* csign, int R, int F, float* dwb, void* stream);
+/* One side of the evaluation score as an inner product (vbpr.py:79-88 predict): out[r, :] = [a[ra, :] | b[rb, :] | s_r | 0 ...]
+ * ([R, Dp]; ra = a_rows ? a_rows[r] : r, rb likewise, both operands Dh wide; s_r = s ? s[r] : 1).  Items: (item id rows,
+ * projected features, visual bias); queries: (user id rows, user modal rows, 1).  Dh % 4 == 0, Dp % 4 == 0, Dp > 2 Dh. */
+int pxr_vbpr_pack_f32(const float* a, const int64_t* a_rows, const float* b, const int64_t* b_rows, const float* s, int64_t R,
+                      int Dh, int Dp, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ from .dataset import (BERT4RecTrainBatcher, GraphEvalBatcher, GraphTrainBatcher,
                       SeqEvalDataset, SeqTrainBatcher, TwoTowerTrainBatcher, seq_eval_collate)
 
 SUPPORTED = {"SASRec": "SEQ", "MOSASRec": "SEQ", "FSASRec": "SEQ", "GRU4Rec": "SEQ", "NextItNet": "SEQ",
-             "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR", "MF": "PAIR",
+             "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR", "MF": "PAIR", "VBPR": "PAIR",
              "SRGNN": "AUGSEQ", "LightSANs": "TWOTOWER"}      # REC/data/utils.py:24-31
 
 

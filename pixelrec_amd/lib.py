@@ -158,6 +158,12 @@ _SIGNATURES = {
     "pxr_mf_bn_tanh_fwd_f32": (_I, [_P, _I, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
     "pxr_mf_bn_tanh_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "pxr_mf_bn_tanh_eval_f32": (_I, [_P, _I64, _I, _P, _P, _P, _P, _F, _P, _P]),
+    "pxr_vbpr_rows_i64": (_I, [_P, _P, _I, _I64, _I64, _P, _P]),
+    "pxr_vbpr_gather_f32": (_I, [_P, _I64, _I, _P, _I64, _P, _P, _P, _P]),
+    "pxr_vbpr_pair_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "pxr_vbpr_pair_bwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "pxr_vbpr_bias_grad_f32": (_I, [_P, _P, _I, _I, _P, _P]),
+    "pxr_vbpr_pack_f32": (_I, [_P, _P, _P, _P, _P, _I64, _I, _I, _P, _P]),
 }
 
 

@@ -11,4 +11,5 @@ from .lightgcn import LightGCN  # noqa: F401
 from .srgnn import SRGNN  # noqa: F401
 from .lightsans import LightSANs  # noqa: F401
 from .mf import MF  # noqa: F401
+from .vbpr import VBPR  # noqa: F401
 from .sharded import ShardedDataParallel, ShardedSASRec  # noqa: F401

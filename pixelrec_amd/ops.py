@@ -2135,3 +2135,131 @@ def mf_bn_tanh_eval(x, gamma, beta, running_mean, running_var, eps=1e-5, y=None)
     _l.check(Lb.pxr_mf_bn_tanh_eval_f32(_l.ptr(x), R, H, _l.ptr(gamma), _l.ptr(beta), _l.ptr(running_mean), _l.ptr(running_var),
                                         float(eps), _l.ptr(y), _l.stream_ptr()), "pxr_mf_bn_tanh_eval_f32")
     return y
+
+
+# ------------------------------------------------------------------------------------------------ VBPR (csrc/vbpr.hip)
+def vbpr_rows(user, item, n_users: int, n_items: int, out=None):
+    """user int64 [B], item int64 [B, 2] | None -> rows int64 [4B] (or [2B]) of the [1 + U + I + U, Dh] table: [1 + user | 1 + U + I
+    + user | 1 + U + item.view(-1)].  Bad ids flag the status word (ops.raise_on_bad_indices) and are clamped."""
+    Lb = _l.load()
+    _req(user, torch.int64, "user")
+    B = user.numel()
+    if item is not None:
+        _req(item, torch.int64, "item")
+        if item.numel() != 2 * B:
+            raise _l.PxrError(f"vbpr rows: item must be [B, 2] for B={B}, got {tuple(item.shape)}")
+    n = 4 * B if item is not None else 2 * B
+    rows = out if out is not None else torch.empty(n, dtype=torch.int64, device=user.device)
+    if rows.numel() != n or rows.dtype != torch.int64:
+        raise _l.PxrError(f"vbpr rows: out must be int64 [{n}]")
+    device_status(user.device)
+    _l.check(Lb.pxr_vbpr_rows_i64(_l.ptr(user), _l.ptr(item), B, int(n_users), int(n_items), _l.ptr(rows), _l.stream_ptr()),
+             "pxr_vbpr_rows_i64")
+    return rows
+
+
+def vbpr_gather(feat, item, wb, out=None, beta=None, copy=True):
+    """feat [I, F] (frozen features), item int64 [n] | None (every row), wb [F] -> (out [n, F] | None, beta [n] = rows . wb), the row
+    read once.  copy=False: beta only.  Bad item ids flag the status word and are clamped."""
+    Lb = _l.load()
+    _req(feat, torch.float32, "feat"); _req(wb, torch.float32, "wb")
+    I, F = feat.shape
+    if wb.numel() != F:
+        raise _l.PxrError(f"vbpr gather: wb must have F={F} elements, got {wb.numel()}")
+    if item is not None:
+        _req(item, torch.int64, "item")
+    n = item.numel() if item is not None else I
+    if copy:
+        out = out if out is not None else torch.empty(n, F, dtype=torch.float32, device=feat.device)
+        _req(out, torch.float32, "out")
+        if out.numel() != n * F:
+            raise _l.PxrError(f"vbpr gather: out must be [{n}, {F}]")
+    else:
+        out = None
+    beta = beta if beta is not None else torch.empty(n, dtype=torch.float32, device=feat.device)
+    _req(beta, torch.float32, "beta")
+    if beta.numel() != n:
+        raise _l.PxrError(f"vbpr gather: beta must be [{n}]")
+    device_status(feat.device)
+    _l.check(Lb.pxr_vbpr_gather_f32(_l.ptr(feat), I, F, _l.ptr(item), n, _l.ptr(wb), _l.ptr(out), _l.ptr(beta), _l.stream_ptr()),
+             "pxr_vbpr_gather_f32")
+    return out, beta
+
+
+def vbpr_pair_fwd(table, rows, e, beta, B: int, out=None):
+    """VBPR's pair loss head (vbpr.py forward) on the table rows at rows [4B], the projected features e [2B, Dh] and beta [2B]
+    -> (loss [1], coef [B] = d loss / d x_b).  out: a float32 [2B + 1] buffer to reuse."""
+    Lb = _l.load()
+    _req(table, torch.float32, "table"); _req(rows, torch.int64, "rows"); _req(e, torch.float32, "e"); _req(beta, torch.float32, "beta")
+    Dh = table.shape[1]
+    if rows.numel() != 4 * B or tuple(e.shape) != (2 * B, Dh) or beta.numel() != 2 * B:
+        raise _l.PxrError(f"vbpr pair head: need rows [4B], e [2B, Dh], beta [2B] for B={B}, Dh={Dh}")
+    f = out if out is not None else torch.empty(2 * B + 1, dtype=torch.float32, device=table.device)
+    coef, lossrow, loss = f[:B], f[B:2 * B], f[2 * B:]
+    _l.check(Lb.pxr_vbpr_pair_fwd_f32(_l.ptr(table), _l.ptr(rows), _l.ptr(e), _l.ptr(beta), Dh, B, _l.ptr(coef), _l.ptr(lossrow),
+                                      _l.ptr(loss), _l.stream_ptr()), "pxr_vbpr_pair_fwd_f32")
+    return loss, coef
+
+
+def vbpr_pair_bwd(table, rows, e, coef, B: int, de, csign, sp: SparseRows, grad_scale=1.0, grad_scale_dev=None):
+    """The head's backward: de [2B, Dh] and csign [2B] overwritten, the tables' gradient written to sp (cap >= 4B) and returned."""
+    Lb = _l.load()
+    for t, nm in ((table, "table"), (e, "e"), (coef, "coef"), (de, "de"), (csign, "csign")):
+        _req(t, torch.float32, nm)
+    _req(rows, torch.int64, "rows")
+    Dh = table.shape[1]
+    if (rows.numel() != 4 * B or tuple(e.shape) != (2 * B, Dh) or tuple(de.shape) != (2 * B, Dh) or coef.numel() != B
+            or csign.numel() != 2 * B or sp.rows.shape[1] != Dh):
+        raise _l.PxrError(f"vbpr pair head backward: need rows [4B], e / de [2B, Dh], coef [B], csign [2B], sparse rows Dh wide "
+                          f"(B={B}, Dh={Dh})")
+    _l.check(Lb.pxr_vbpr_pair_bwd_f32(_l.ptr(table), _l.ptr(rows), _l.ptr(e), _l.ptr(coef), Dh, B, float(grad_scale),
+                                      _l.ptr(grad_scale_dev), _l.ptr(de), _l.ptr(csign), _l.ptr(sp.idx), _l.ptr(sp.rows),
+                                      _l.ptr(sp.n), sp.cap, _l.stream_ptr()), "pxr_vbpr_pair_bwd_f32")
+    return sp
+
+
+def vbpr_bias_grad(x, csign, out):
+    """out [F] = sum_r csign[r] x[r, :] (the gradient of bias_projection.weight), fixed summation order."""
+    Lb = _l.load()
+    _req(x, torch.float32, "x"); _req(csign, torch.float32, "csign"); _req(out, torch.float32, "out")
+    R, F = x.shape
+    if csign.numel() != R or out.numel() != F:
+        raise _l.PxrError(f"vbpr bias gradient: need csign [{R}] and out [{F}]")
+    _l.check(Lb.pxr_vbpr_bias_grad_f32(_l.ptr(x), _l.ptr(csign), R, F, _l.ptr(out), _l.stream_ptr()), "pxr_vbpr_bias_grad_f32")
+    return out
+
+
+def vbpr_packed_width(Dh: int) -> int:
+    """Width of the packed scoring vectors: 2 Dh + 1, zero-padded to a multiple of 32 (the fused top-k's plane path)."""
+    return (2 * Dh + 1 + 31) // 32 * 32
+
+
+def vbpr_pack(a, b, s=None, a_rows=None, b_rows=None, out=None):
+    """out [R, vbpr_packed_width(Dh)] = [a[a_rows] | b[b_rows] | s | 0 ...] (rows None: row r itself; s None: 1)."""
+    Lb = _l.load()
+    _req(a, torch.float32, "a"); _req(b, torch.float32, "b")
+    Dh = a.shape[1]
+    if b.shape[1] != Dh:
+        raise _l.PxrError("vbpr pack: both operands must be Dh wide")
+    if (a_rows is None) != (b_rows is None):
+        raise _l.PxrError("vbpr pack: give both row lists or neither")
+    if a_rows is not None:
+        _req(a_rows, torch.int64, "a_rows"); _req(b_rows, torch.int64, "b_rows")
+        R = a_rows.numel()
+        if b_rows.numel() != R:
+            raise _l.PxrError("vbpr pack: row lists differ in length")
+    else:
+        R = a.shape[0]
+        if b.shape[0] != R:
+            raise _l.PxrError("vbpr pack: operands differ in row count")
+    if s is not None:
+        _req(s, torch.float32, "s")
+        if s.numel() != R:
+            raise _l.PxrError(f"vbpr pack: s must be [{R}]")
+    Dp = vbpr_packed_width(Dh)
+    out = out if out is not None else torch.empty(R, Dp, dtype=torch.float32, device=a.device)
+    if tuple(out.shape) != (R, Dp) or not out.is_contiguous():
+        raise _l.PxrError(f"vbpr pack: out must be a contiguous [{R}, {Dp}]")
+    _l.check(Lb.pxr_vbpr_pack_f32(_l.ptr(a), _l.ptr(a_rows), _l.ptr(b), _l.ptr(b_rows), _l.ptr(s), R, Dh, Dp, _l.ptr(out),
+                                  _l.stream_ptr()), "pxr_vbpr_pack_f32")
+    return out

@@ -196,13 +196,59 @@ def _short_name(name, model=None):
     return f"{i}.{key}.{kind}"
 
 
+def _leading_flat_count(model) -> int:
+    """Number of flat-buffer parameters in front of the table parameters in the reference's order (a two-group PxrAdamW needs the
+    flat parameters first: torch numbers parameters through the groups in order)."""
+    names = reference_rec_parameter_names(model)
+    flags = [_is_table(n, model) for n in names]
+    n_flat = flags.index(True) if True in flags else len(flags)
+    if not all(flags[n_flat:]):
+        raise NotImplementedError("a separate flat parameter group needs every flat parameter in front of the table parameters")
+    return n_flat
+
+
+def flat_table_adamw(model, optim_args, fragment=None, table_update="lazy"):
+    """The reference's optimizer construction (trainer.py:66-103) for a model whose flat buffer and table buffer may be separate
+    parameter groups (`split_flat_table_groups`: VBPR).  2-key optim_args: one group.  4-key: group 0 = the parameters whose name
+    contains `fragment` (modal_lr, modal_decay; 'visual_encoder' when no decay_check_name is set), group 1 = the rest (rec_lr,
+    rec_decay).  Built: group 0 = exactly the flat parameters (lazy table rows under the rec scalars, one flat launch under the
+    modal scalars, every scalar on the device), or group 0 empty."""
+    a = optim_args
+    if len(a) != 4:
+        return PxrAdamW(model, lr=a["learning_rate"], weight_decay=a["weight_decay"], table_update=table_update)
+    frag = fragment or "visual_encoder"
+    names = reference_rec_parameter_names(model)
+    inside = [n for n in names if frag in n]
+    flat = [n for n in names if not _is_table(n, model)]
+    if not inside:
+        # the reference still builds TWO param groups (an empty modal group + the rec group, trainer.py:93-96)
+        opt = PxrAdamW(model, lr=a["rec_lr"], weight_decay=a["rec_decay"], table_update=table_update)
+        opt.empty_leading_group = {"lr": a["modal_lr"], "weight_decay": a["modal_decay"]}
+        return opt
+    if inside != flat:
+        outside = [n for n in names if frag not in n]
+        raise NotImplementedError(
+            f"decay_check_name fragment '{frag}' puts {inside} into the first parameter group and {outside} into the second: "
+            f"{type(model).__name__} updates {flat} in one flat launch and its tables as rows of one buffer, so the only split "
+            "built is the flat parameters against the tables (e.g. 'projection')")
+    _leading_flat_count(model)
+    return PxrAdamW(model, lr=a["rec_lr"], weight_decay=a["rec_decay"], table_update=table_update,
+                    flat_group={"lr": a["modal_lr"], "weight_decay": a["modal_decay"]})
+
+
 HYPER_CAPACITY = 1 << 22   # steps; 96 MB of per-step scalars, sized once so graph replays never see a reallocation
 
 
 class PxrAdamW:
-    def __init__(self, model, lr=1e-4, weight_decay=0.1, betas=(0.9, 0.999), eps=1e-8, table_update="lazy"):
+    def __init__(self, model, lr=1e-4, weight_decay=0.1, betas=(0.9, 0.999), eps=1e-8, table_update="lazy", flat_group=None):
         if table_update not in ("lazy", "dense"):
             raise ValueError("table_update must be 'lazy' or 'dense'")
+        # flat_group = {"lr", "weight_decay"}: the flat buffer is a parameter group of its own, IN FRONT of the table's (VBPR under
+        # decay_check_name 'projection': reference trainer.py:73-91) -- its launch reads per-step scalars from a second table
+        # (_fhyper), the table rows keep lr / weight_decay; None: one group, as ever
+        self.flat_group = None if flat_group is None else {"lr": float(flat_group["lr"]),
+                                                           "weight_decay": float(flat_group["weight_decay"])}
+        self._fhyper = self._fcumlog = None
         self.table_update = table_update
         self.model = model
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
@@ -239,6 +285,9 @@ class PxrAdamW:
             self._cumlog = torch.zeros(HYPER_CAPACITY, dtype=torch.float64, device=dev)
             self._step_dev = torch.full((1,), self.step_count, dtype=torch.int64, device=dev)
             self._seeded_cfg = None
+        if self.flat_group is not None and (self._fhyper is None or self._fhyper.device != dev):
+            self._fhyper = torch.zeros(HYPER_CAPACITY, 4, dtype=torch.float32, device=dev)
+            self._fcumlog = torch.zeros(HYPER_CAPACITY, dtype=torch.float64, device=dev)
         return flat, table
 
     def zero_grad(self, set_to_none: bool = False):
@@ -344,7 +393,14 @@ class PxrAdamW:
         fold = (self._cur_for == self.step_count + 1 and not reseeded and os.environ.get("PXR_FOLD_CLOSE", "1") != "0")
         self._cur_for = None
         exps = self.model.weight_plane_exps() if (segs and hasattr(self.model, "weight_plane_exps")) else None
-        ops.adamw_flat_tab(flat, gflat, self._m, self._v, self._hyper, self.step_count + 1, b1, b2, g["eps"], step_dev=sd,
+        fhyper = self._hyper
+        if self.flat_group is not None:
+            # the flat group's scalars of this step, written from the device counter into their own table (one 1-thread launch)
+            fg = self.flat_group
+            ops.adamw_hyper_append(self._fhyper, self._fcumlog, self.step_count + 1, fg["lr"], b1, b2, g["eps"], fg["weight_decay"],
+                                   step_dev=sd)
+            fhyper, fold = self._fhyper, False
+        ops.adamw_flat_tab(flat, gflat, self._m, self._v, fhyper, self.step_count + 1, b1, b2, g["eps"], step_dev=sd,
                            plane_segments=segs, planes_exps=exps,
                            close=(self._cumlog, self._cur_hyper, g["lr"], g["weight_decay"]) if fold else None)
         if segs:
@@ -369,8 +425,16 @@ class PxrAdamW:
         sd = {"step": self.step_count, "param_groups": self.param_groups, "m": self._m, "v": self._v}
         if self.has_table:
             sd.update(table_m=self._tm, table_v=self._tv)
+        if self.flat_group is not None:
+            sd["flat_group"] = self.flat_group
         if layout == "torch":
             out = native_to_torch_state(sd, self.model)
+            if self.flat_group is not None:
+                # two groups, parameter indices through the groups in order: the flat parameters, then the tables
+                tg = out["param_groups"][0]
+                n_flat = _leading_flat_count(self.model)
+                out["param_groups"] = [{**tg, "lr": self.flat_group["lr"], "weight_decay": self.flat_group["weight_decay"],
+                                        "params": tg["params"][:n_flat]}, {**tg, "params": tg["params"][n_flat:]}]
             lead = getattr(self, "empty_leading_group", None)
             if lead is not None:     # 4-key optim_args without trainable visual parameters: an empty modal group comes first
                 g0 = {"lr": lead["lr"], "betas": tuple(self.param_groups[0]["betas"]), "eps": self.param_groups[0]["eps"],
@@ -385,7 +449,24 @@ class PxrAdamW:
         self._ensure_state()
         self.flush()                     # updates still owed under the OLD state are applied with the old state
         if is_torch_adamw_state(sd):     # a reference checkpoint (or layout="torch"): per-parameter state -> flat buffers
+            fg = None
+            if self.flat_group is not None:
+                if len(sd["param_groups"]) != 2:
+                    raise ValueError(f"optimizer state has {len(sd['param_groups'])} parameter groups, this optimizer has 2 "
+                                     "(the flat parameters, then the tables)")
+                g0, g1 = sd["param_groups"]
+                if len(g0["params"]) != _leading_flat_count(self.model):
+                    raise ValueError(f"optimizer state has {len(g0['params'])} parameters in its first group, this model has "
+                                     f"{_leading_flat_count(self.model)} flat parameters")
+                fg = {"lr": g0["lr"], "weight_decay": g0["weight_decay"]}
+                sd = {"state": sd["state"], "param_groups": [{**g1, "params": list(g0["params"]) + list(g1["params"])}]}
             sd = torch_to_native_state(sd, self.model)
+            if fg is not None:
+                sd["flat_group"] = fg
+        if self.flat_group is not None:
+            if "flat_group" not in sd:
+                raise ValueError("optimizer state without the flat parameter group's scalars (flat_group)")
+            self.flat_group = {"lr": float(sd["flat_group"]["lr"]), "weight_decay": float(sd["flat_group"]["weight_decay"])}
         self.step_count = int(sd["step"])
         self.param_groups = sd["param_groups"]
         pairs = [(self._m, "m"), (self._v, "v")] + ([(self._tm, "table_m"), (self._tv, "table_v")] if self.has_table else [])

@@ -160,6 +160,12 @@ class Trainer:
         parameter is a 'rec' parameter, so both spellings resolve to one AdamW."""
         a = self.optim_args
         m = self.model.module
+        if getattr(m, "split_flat_table_groups", False):
+            # a model whose flat buffer and table buffer may be separate parameter groups (VBPR, decay_check_name 'projection'):
+            # the split runs on the native path with every scalar on the device, so the step stays capturable
+            from ..optim import flat_table_adamw
+
+            return flat_table_adamw(m, a, self.config["decay_check_name"])
         if len(a) == 4 and self.config["decay_check_name"]:
             # trainer.py:73-91: the two groups split by a name fragment instead of by 'visual_encoder' (no shipped YAML sets it):
             # per-tensor launches with host scalars -- eager steps, planes re-split every forward
@@ -213,6 +219,7 @@ class Trainer:
                                                    clip_grad_norm=self.clip_grad_norm, loss_sum=self._graph_loss,
                                                    lookahead=lookahead,
                                                    h2_stale_scales=getattr(self.model.module, "h2_stale_scales", None))
+                    self.logger.info("training step captured as a hipGraph (batch size %d)", int(data[0].shape[0]))
                 if self._gstep is not None and self._gstep.matches(data[0], data[1]):
                     # the replay adds its loss to self._graph_loss on the device
                     try:
@@ -432,16 +439,20 @@ class Trainer:
             self.item_feature = torch.cat(feats)
         else:
             self.item_feature = self.model.module.compute_item_all()
+        # what the fused scoring multiplies the queries of encode_last with: the item feature itself, or the packed matrix of a
+        # model whose score is more than one product (VBPR.scoring_item_matrix); the literal path keeps predict(item_feature)
+        hook = getattr(self.model.module, "scoring_item_matrix", None)
+        self._score_matrix = hook() if (hook is not None and self.fused_topk) else self.item_feature
         # the fused scoring's main pass reads the item vectors as pre-split planes: made once per evaluation (0.4 ms for
         # 400 K x 512), reused by every batch of users
         self._item_planes = self._item_norm_max = None
         use_p = self.config["eval_planes"]
-        if self.fused_topk and (use_p is None or bool(use_p)) and ops.score_planes_supported(self.item_feature.data):
+        if self.fused_topk and (use_p is None or bool(use_p)) and ops.score_planes_supported(self._score_matrix.data):
             buf = getattr(self, "_item_planes_buf", None)
-            N_, D_ = self.item_feature.shape
-            if buf is None or (buf.rows, buf.cols) != (N_, D_) or buf.buf.device != self.item_feature.device:
-                buf = self._item_planes_buf = ops.Planes.alloc(N_, D_, self.item_feature.device)
-            feat = self.item_feature.data.contiguous()
+            N_, D_ = self._score_matrix.shape
+            if buf is None or (buf.rows, buf.cols) != (N_, D_) or buf.buf.device != self._score_matrix.device:
+                buf = self._item_planes_buf = ops.Planes.alloc(N_, D_, self._score_matrix.device)
+            feat = self._score_matrix.data.contiguous()
             self._item_planes = ops.split_planes(feat, buf)
             # ... and the largest row norm: the margin of the threshold pass on 3 of the 6 bf16 products (ops.score_topk)
             self._item_norm_max = ops.row_norm_max(feat)
@@ -525,7 +536,9 @@ class Trainer:
         out, last = (m.encode_last(user_d, self.item_feature) if (self.use_modality or not has_item_table(m))
                      else m.encode_last(user_d))
         B, L, D = out.shape
-        idx, _ = ops.score_topk(last, last.stride(0), B, self.item_feature.data, max(self.config["topk"]), ptr, items,
+        sm = getattr(self, "_score_matrix", None)
+        sm = sm if sm is not None else self.item_feature
+        idx, _ = ops.score_topk(last, last.stride(0), B, sm.data, max(self.config["topk"]), ptr, items,
                                 table_planes=getattr(self, "_item_planes", None), table_norm_max=getattr(self, "_item_norm_max", None))
         return idx, positive_i
 
