@@ -737,6 +737,42 @@ int pxr_vbpr_bias_grad_f32(const float* x, const float* csign, int R, int F, flo
 int pxr_vbpr_pack_f32(const float* a, const int64_t* a_rows, const float* b, const int64_t* b_rows, const float* s, int64_t R,
                       int Dh, int Dp, float* out, void* stream);
 
+/* ---- ACF (model/ViNet/acf.py; csrc/acf.hip) ------------------------------------------------------------------------------- */
+/* The tables are ONE [1 + n_items + n_users, E] buffer in the reference's parameter order: item_model row i at 1 + i (item 0 is
+ * the reference's padding row: read, decayed, never given a gradient), user_embedding row u at 1 + n_items + u, row 0 a spare (the
+ * sparse-row kernels treat id 0 as padding / an empty slot).  Occurrences in the order [profile ids (n_profile) | item ids
+ * (n_item_occ: positive, negative per sample) | user ids (n_user_occ)]; a list with count 0 may be NULL.  rows[o] = the table row
+ * occurrence o reads; gidx[o] (may be NULL) = the row its gradient is summed into, 0 for item id 0 (dropped by
+ * pxr_embed_grad_rows_f32).  An id outside [0, n_items) / [0, n_users) ORs bit 0 into the status word (clamped). */
+int pxr_acf_rows_i64(const int64_t* profile, int64_t n_profile, const int64_t* items, int64_t n_item_occ, const int64_t* user,
+                     int64_t n_user_occ, int64_t n_items, int64_t n_users, int64_t* rows, int64_t* gidx, void* stream);
+/* Region attention (acf.py ACFFeatureNet.forward after the two Linears), r = b P + p: s_h = <w, relu(xt[r, h, :] + ut[b, :])>,
+ * beta[r, :] = softmax_H(s), pooled[r, :] = sum_h beta[r, h] x[r, h, :]; a masked r (profile[r] == 0) gets beta = 0 and pooled =
+ * 0.  x, xt [B P, H, E]; ut [B, E]; w [E] (feats.w.weight; its scalar bias cancels in the softmax).  One pass over x and xt,
+ * fixed summation order.  H <= 1024, E % 4 == 0, E <= 4096. */
+int pxr_acf_region_fwd_f32(const float* x, const float* xt, const float* ut, const float* w, const int64_t* profile, int B, int P,
+                           int H, int E, float* beta, float* pooled, void* stream);
+/* Its backward from dpooled [B P, E]: dxt [B P, H, E] (gradient of xt = of relu's argument), dut [B, E] = sum over the user's P H
+ * positions of dxt in ascending (p, h), dw_part [B P, E] whose column sum is d w (pxr_colsum_f32).  ws: B P E floats.  The
+ * gradient of x is NOT written here: see pxr_acf_region_dx_f32.  dxt must not alias x or xt. */
+int pxr_acf_region_bwd_f32(const float* dpooled, const float* x, const float* xt, const float* ut, const float* w,
+                           const int64_t* profile, const float* beta, int B, int P, int H, int E, float* dxt, float* dut,
+                           float* dw_part, float* ws, void* stream);
+/* Gradient of dim_reductor's pre-activation, in place: dx [R, H, E] holds the feats.w_x input gradient (dxt W) on entry and
+ * (dx + beta[r, h] dpooled[r, :]) (x > 0) on exit -- the pooled path added and the ReLU applied in one pass. */
+int pxr_acf_region_dx_f32(float* dx, const float* x, const float* beta, const float* dpooled, int64_t R, int H, int E,
+                          void* stream);
+/* Item attention and the user vector (acf.py ACFUserNet.forward after its three Linears): t_p = <w, relu(uw[b, :] + pq[r, :] +
+ * cx[r, :])>, alpha[b, :] = softmax_P(t) over the p with profile[r] != 0 (0 elsewhere; all zero for an empty profile),
+ * user[b, :] = uw[b, :] + sum_p alpha[b, p] prof[r, :].  uw [B, E]; pq, cx, prof [B P, E]; w [E].  P <= 1024. */
+int pxr_acf_item_fwd_f32(const float* uw, const float* pq, const float* cx, const float* prof, const float* w,
+                         const int64_t* profile, int B, int P, int E, float* alpha, float* user, void* stream);
+/* Its backward from duser [B, E]: da [B P, E] (the gradient of pq and of cx alike), dprof [B P, E] = alpha duser (the direct path
+ * onto the profile rows), duw [B, E] = duser + sum_p da, dw_part [B, E] whose column sum is d w.  Outputs must not alias inputs. */
+int pxr_acf_item_bwd_f32(const float* duser, const float* uw, const float* pq, const float* cx, const float* prof, const float* w,
+                         const float* alpha, int B, int P, int E, float* da, float* dprof, float* duw, float* dw_part,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

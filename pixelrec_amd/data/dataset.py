@@ -276,6 +276,71 @@ class TwoTowerTrainBatcher:
             yield torch.from_numpy(hist), torch.from_numpy(target)
 
 
+class SampleAcfTrainBatcher:
+    """Vectorised SampleACFTrainDataset (reference REC/data/dataset/trainset.py:603-652) under torch's DistributedSampler order.
+    Data builds the SEQ chunks of at most L+1 items with their user id; every position j of every chunk is one sample: profile =
+    the chunk without item j (order kept, left-padded with 0 to L), positive = item j, one negative uniform over [1, item_num - 1]
+    and redrawn while it lies in the chunk -- the reference's distribution, not its random stream.  A chunk of one item gives one
+    sample with an empty profile.  The number of samples is the sum of the chunk lengths.  Yields whole (profile int64 [B, L],
+    tail int64 [B, 3] = (positive, negative, user id)) batches: the two tensors the training loop stages (ACF.forward joins them
+    into the reference's [B, L + 3] row).  The sample order and the split by rank are SeqTrainBatcher's."""
+
+    MAX_REDRAWS = 1000
+
+    def __init__(self, config, dataload, rank=0, world=1, seed=0, drop_last=False):
+        self.dataload = dataload
+        self.item_num = dataload.item_num
+        self.L = config["MAX_ITEM_LIST_LENGTH"]
+        self.batch_size = config["train_batch_size"]
+        seqs = dataload.train_feat["item_seq"]
+        W = self.L + 1
+        self.windows = np.zeros((len(seqs), W), dtype=np.int64)       # the chunks, left-padded
+        lens = np.zeros(len(seqs), dtype=np.int64)
+        for i, s in enumerate(seqs):
+            k = len(s)
+            self.windows[i, W - k:] = s
+            lens[i] = k
+        self.chunk_user = np.asarray(dataload.train_feat["user_id"], dtype=np.int64)
+        self.chunk = np.repeat(np.arange(len(seqs), dtype=np.int64), lens)                 # chunk of each sample
+        within = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens)
+        self.col = (W - lens)[self.chunk] + within                                        # column of the sample's positive
+        self.n = len(self.chunk)
+        if self.item_num <= 2:
+            raise ValueError("SampleAcfTrainBatcher: no negative can be drawn from [1, item_num) outside a chunk")
+        self.rank, self.world, self.seed, self.epoch = rank, world, seed, 0
+        self.num_samples = -(-self.n // world)
+        self.drop_last = drop_last
+        self.neg_seed = int(config["seed"] or 0)
+
+    set_epoch = SeqTrainBatcher.set_epoch
+    __len__ = SeqTrainBatcher.__len__
+    _indices = SeqTrainBatcher._indices
+
+    def make_batch(self, rows, rng):
+        win, col = self.windows[self.chunk[rows]], self.col[rows]          # [B, L+1], [B]
+        B, W = win.shape
+        k = np.arange(W - 1, dtype=np.int64)[None, :]
+        profile = np.take_along_axis(win, k + (k >= col[:, None]), axis=1)  # the window without column col
+        pos = win[np.arange(B), col]
+        real = win != 0
+        neg = rng.integers(1, self.item_num, size=B)
+        for _ in range(self.MAX_REDRAWS):
+            clash = ((neg[:, None] == win) & real).any(1)
+            if not clash.any():
+                break
+            neg[clash] = rng.integers(1, self.item_num, size=int(clash.sum()))
+        else:
+            raise ValueError("SampleAcfTrainBatcher: a chunk covers (nearly) every item: no negative could be drawn")
+        return profile, np.stack((pos, neg, self.chunk_user[self.chunk[rows]]), axis=1)
+
+    def __iter__(self):
+        idx = self._indices()
+        rng = np.random.default_rng([self.neg_seed, self.epoch, self.rank])
+        for b in range(len(self)):
+            profile, tail = self.make_batch(idx[b * self.batch_size:(b + 1) * self.batch_size], rng)
+            yield torch.from_numpy(profile), torch.from_numpy(tail)
+
+
 class SeqEvalDataset(Dataset):
     def __init__(self, config, dataload, phase="valid"):
         self.dataload = dataload
@@ -418,6 +483,21 @@ class PairEvalBatcher(SeqEvalBatcher):
     def __iter__(self):
         for b0, (_, hist, pos_u, target) in zip(range(0, len(self.users), self.batch_size), super().__iter__()):
             yield torch.from_numpy(self.uids[self.users[b0:b0 + self.batch_size]]), hist, pos_u, target
+
+
+class AcfEvalBatcher(SeqEvalBatcher):
+    """ACFEvalDataset (reference evalset.py) through SeqEvalBatcher: the same users, windows, histories and targets, with the
+    user id (the key of user_seq) appended to the window as column L:
+    `([item_seq | user id] [b, L + 1], (history_u, history_i), positive_u [b], item_target [b])`."""
+
+    def __init__(self, config, dataload, phase="valid", rank=0, world=1):
+        super().__init__(config, dataload, phase=phase, rank=rank, world=world)
+        self.uids = np.fromiter(dataload.user_seq.keys(), dtype=np.int64, count=len(dataload.user_seq))
+
+    def __iter__(self):
+        for b0, (item_seq, hist, pos_u, target) in zip(range(0, len(self.users), self.batch_size), super().__iter__()):
+            uid = torch.from_numpy(self.uids[self.users[b0:b0 + self.batch_size]])
+            yield torch.cat((item_seq, uid[:, None]), dim=1), hist, pos_u, target
 
 
 class GraphTrainBatcher:

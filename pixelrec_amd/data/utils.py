@@ -14,12 +14,12 @@ from torch.utils.data import DataLoader
 
 from ..parallel import world_info
 from .dataload import Data
-from .dataset import (BERT4RecTrainBatcher, GraphEvalBatcher, GraphTrainBatcher, PairEvalBatcher, PairTrainBatcher, SeqEvalBatcher,
-                      SeqEvalDataset, SeqTrainBatcher, TwoTowerTrainBatcher, seq_eval_collate)
+from .dataset import (AcfEvalBatcher, BERT4RecTrainBatcher, GraphEvalBatcher, GraphTrainBatcher, PairEvalBatcher, PairTrainBatcher, SeqEvalBatcher,
+                      SampleAcfTrainBatcher, SeqEvalDataset, SeqTrainBatcher, TwoTowerTrainBatcher, seq_eval_collate)
 
 SUPPORTED = {"SASRec": "SEQ", "MOSASRec": "SEQ", "FSASRec": "SEQ", "GRU4Rec": "SEQ", "NextItNet": "SEQ",
              "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR", "MF": "PAIR", "VBPR": "PAIR",
-             "SRGNN": "AUGSEQ", "LightSANs": "TWOTOWER"}      # REC/data/utils.py:24-31
+             "SRGNN": "AUGSEQ", "LightSANs": "TWOTOWER", "ACF": "SEQ"}      # REC/data/utils.py:24-31
 
 
 def load_data(config):
@@ -89,8 +89,13 @@ def bulid_dataloader(config, dataload):
                 GraphEvalBatcher(config, dataload, phase="test", rank=rank, world=world))
     # BERT4Rec masks its windows (REC/data/utils.py:25: BERT4RecTrainDataset); LightSANs (AUGSEQ, so Data built every prefix)
     # reads TwoTowerTrainDataset's rows of those prefixes (:35); evaluation is SeqEvalDataset's for all of them
-    batcher = {"BERT4Rec": BERT4RecTrainBatcher, "LightSANs": TwoTowerTrainBatcher}.get(model_name, SeqTrainBatcher)
+    batcher = {"BERT4Rec": BERT4RecTrainBatcher, "LightSANs": TwoTowerTrainBatcher,
+               "ACF": SampleAcfTrainBatcher}.get(model_name, SeqTrainBatcher)
     train_loader = _TrainLoader(batcher(config, dataload, rank=rank, world=world))
+    if model_name == "ACF":
+        # SampleACFTrainDataset / ACFEvalDataset (REC/data/utils.py:24-31): leave-one-out samples of the chunks; windows + user id
+        return (train_loader, AcfEvalBatcher(config, dataload, phase="valid", rank=rank, world=world),
+                AcfEvalBatcher(config, dataload, phase="test", rank=rank, world=world))
     loaders = []
     workers = int(config["eval_num_workers"] or 0)
     for phase in ("valid", "test"):

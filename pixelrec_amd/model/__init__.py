@@ -12,4 +12,5 @@ from .srgnn import SRGNN  # noqa: F401
 from .lightsans import LightSANs  # noqa: F401
 from .mf import MF  # noqa: F401
 from .vbpr import VBPR  # noqa: F401
+from .acf import ACF  # noqa: F401
 from .sharded import ShardedDataParallel, ShardedSASRec  # noqa: F401

@@ -2263,3 +2263,111 @@ def vbpr_pack(a, b, s=None, a_rows=None, b_rows=None, out=None):
     _l.check(Lb.pxr_vbpr_pack_f32(_l.ptr(a), _l.ptr(a_rows), _l.ptr(b), _l.ptr(b_rows), _l.ptr(s), R, Dh, Dp, _l.ptr(out),
                                   _l.stream_ptr()), "pxr_vbpr_pack_f32")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ ACF (csrc/acf.hip)
+def acf_rows(profile, items, user, n_items: int, n_users: int, out=None, want_gidx: bool = True):
+    """profile int64 [B, P], items int64 [B, 2] | None, user int64 [B] -> (rows, gidx) int64 [B P + 2B + B] (or [B P + B]) of
+    the [1 + I + U, E] table in the order profile | items | users: rows = the row an occurrence reads, gidx = the row its gradient
+    goes to (0 for item id 0, the padding row).  Bad ids flag the status word (ops.raise_on_bad_indices) and are clamped.
+    out: an int64 [2, n] buffer to reuse."""
+    Lb = _l.load()
+    _req(profile, torch.int64, "profile"); _req(user, torch.int64, "user")
+    n_p, n_u = profile.numel(), user.numel()
+    n_i = 0
+    if items is not None:
+        _req(items, torch.int64, "items")
+        n_i = items.numel()
+    n = n_p + n_i + n_u
+    buf = out if out is not None else torch.empty(2, n, dtype=torch.int64, device=user.device)
+    if tuple(buf.shape) != (2, n) or buf.dtype != torch.int64:
+        raise _l.PxrError(f"acf rows: out must be int64 [2, {n}]")
+    device_status(user.device)
+    _l.check(Lb.pxr_acf_rows_i64(_l.ptr(profile), n_p, _l.ptr(items), n_i, _l.ptr(user), n_u, int(n_items), int(n_users),
+                                 _l.ptr(buf[0]), _l.ptr(buf[1]) if want_gidx else None, _l.stream_ptr()), "pxr_acf_rows_i64")
+    return buf[0], buf[1]
+
+
+def acf_region_fwd(x, xt, ut, w, profile, H: int, beta=None, pooled=None):
+    """Region attention forward (pxr_acf_region_fwd_f32): x, xt [B P H, E] (or [B P, H E]), ut [B, E], w [E], profile int64 [B, P]
+    -> (beta [B P, H], pooled [B P, E]); a padded position gets zeros."""
+    Lb = _l.load()
+    for t, nm in ((x, "x"), (xt, "xt"), (ut, "ut"), (w, "w")):
+        _req(t, torch.float32, nm)
+    _req(profile, torch.int64, "profile")
+    B, E = ut.shape
+    P = profile.numel() // B
+    if profile.numel() != B * P or x.numel() != B * P * H * E or xt.numel() != x.numel() or w.numel() != E:
+        raise _l.PxrError("acf region attention: need x, xt [B P H, E], ut [B, E], w [E], profile [B, P]")
+    beta = beta if beta is not None else torch.empty(B * P, H, dtype=torch.float32, device=x.device)
+    pooled = pooled if pooled is not None else torch.empty(B * P, E, dtype=torch.float32, device=x.device)
+    _l.check(Lb.pxr_acf_region_fwd_f32(_l.ptr(x), _l.ptr(xt), _l.ptr(ut), _l.ptr(w), _l.ptr(profile), B, P, H, E, _l.ptr(beta),
+                                       _l.ptr(pooled), _l.stream_ptr()), "pxr_acf_region_fwd_f32")
+    return beta, pooled
+
+
+def acf_region_bwd(dpooled, x, xt, ut, w, profile, beta, dxt, dut, dw_part, ws):
+    """Region attention backward (pxr_acf_region_bwd_f32): writes dxt [B P H, E], dut [B, E], dw_part [B P, E] (column sum = dw);
+    ws [B P, E] scratch."""
+    Lb = _l.load()
+    for t, nm in ((dpooled, "dpooled"), (x, "x"), (xt, "xt"), (ut, "ut"), (w, "w"), (beta, "beta"), (dxt, "dxt"), (dut, "dut"),
+                  (dw_part, "dw_part"), (ws, "ws")):
+        _req(t, torch.float32, nm)
+    _req(profile, torch.int64, "profile")
+    B, E = ut.shape
+    R, H = beta.shape
+    P = R // B
+    if (profile.numel() != R or R != B * P or x.numel() != R * H * E or xt.numel() != x.numel() or dxt.numel() != x.numel()
+            or dpooled.numel() != R * E or dw_part.numel() != R * E or ws.numel() < R * E or dut.numel() != B * E or w.numel() != E):
+        raise _l.PxrError("acf region attention backward: operand shapes do not match")
+    _l.check(Lb.pxr_acf_region_bwd_f32(_l.ptr(dpooled), _l.ptr(x), _l.ptr(xt), _l.ptr(ut), _l.ptr(w), _l.ptr(profile), _l.ptr(beta),
+                                       B, P, H, E, _l.ptr(dxt), _l.ptr(dut), _l.ptr(dw_part), _l.ptr(ws), _l.stream_ptr()),
+             "pxr_acf_region_bwd_f32")
+
+
+def acf_region_dx(dx, x, beta, dpooled):
+    """dx [R H, E] <- (dx + beta dpooled) (x > 0), in place (pxr_acf_region_dx_f32)."""
+    Lb = _l.load()
+    for t, nm in ((dx, "dx"), (x, "x"), (beta, "beta"), (dpooled, "dpooled")):
+        _req(t, torch.float32, nm)
+    R, H = beta.shape
+    E = dpooled.shape[-1]
+    if dx.numel() != R * H * E or x.numel() != dx.numel() or dpooled.numel() != R * E:
+        raise _l.PxrError("acf region dx: operand shapes do not match")
+    _l.check(Lb.pxr_acf_region_dx_f32(_l.ptr(dx), _l.ptr(x), _l.ptr(beta), _l.ptr(dpooled), R, H, E, _l.stream_ptr()),
+             "pxr_acf_region_dx_f32")
+    return dx
+
+
+def acf_item_fwd(uw, pq, cx, prof, w, profile, alpha=None, user=None):
+    """Item attention + user vector (pxr_acf_item_fwd_f32): uw [B, E], pq / cx / prof [B P, E], w [E], profile int64 [B, P] ->
+    (alpha [B, P], user [B, E])."""
+    Lb = _l.load()
+    for t, nm in ((uw, "uw"), (pq, "pq"), (cx, "cx"), (prof, "prof"), (w, "w")):
+        _req(t, torch.float32, nm)
+    _req(profile, torch.int64, "profile")
+    B, E = uw.shape
+    P = profile.numel() // B
+    if profile.numel() != B * P or any(t.numel() != B * P * E for t in (pq, cx, prof)) or w.numel() != E:
+        raise _l.PxrError("acf item attention: need uw [B, E], pq / cx / prof [B P, E], w [E], profile [B, P]")
+    alpha = alpha if alpha is not None else torch.empty(B, P, dtype=torch.float32, device=uw.device)
+    user = user if user is not None else torch.empty(B, E, dtype=torch.float32, device=uw.device)
+    _l.check(Lb.pxr_acf_item_fwd_f32(_l.ptr(uw), _l.ptr(pq), _l.ptr(cx), _l.ptr(prof), _l.ptr(w), _l.ptr(profile), B, P, E,
+                                     _l.ptr(alpha), _l.ptr(user), _l.stream_ptr()), "pxr_acf_item_fwd_f32")
+    return alpha, user
+
+
+def acf_item_bwd(duser, uw, pq, cx, prof, w, alpha, da, dprof, duw, dw_part):
+    """Item attention backward (pxr_acf_item_bwd_f32): writes da / dprof [B P, E], duw [B, E], dw_part [B, E] (column sum = dw)."""
+    Lb = _l.load()
+    for t, nm in ((duser, "duser"), (uw, "uw"), (pq, "pq"), (cx, "cx"), (prof, "prof"), (w, "w"), (alpha, "alpha"), (da, "da"),
+                  (dprof, "dprof"), (duw, "duw"), (dw_part, "dw_part")):
+        _req(t, torch.float32, nm)
+    B, E = uw.shape
+    P = alpha.numel() // B
+    if (alpha.numel() != B * P or any(t.numel() != B * P * E for t in (pq, cx, prof, da, dprof))
+            or any(t.numel() != B * E for t in (duser, duw, dw_part)) or w.numel() != E):
+        raise _l.PxrError("acf item attention backward: operand shapes do not match")
+    _l.check(Lb.pxr_acf_item_bwd_f32(_l.ptr(duser), _l.ptr(uw), _l.ptr(pq), _l.ptr(cx), _l.ptr(prof), _l.ptr(w), _l.ptr(alpha), B, P,
+                                     E, _l.ptr(da), _l.ptr(dprof), _l.ptr(duw), _l.ptr(dw_part), _l.stream_ptr()),
+             "pxr_acf_item_bwd_f32")
