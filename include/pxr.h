@@ -773,6 +773,24 @@ int pxr_acf_item_bwd_f32(const float* duser, const float* uw, const float* pq, c
                          const float* alpha, int B, int P, int E, float* da, float* dprof, float* duw, float* dw_part,
                          void* stream);
 
+/* ---- VISRANK (model/ViNet/visrank.py; csrc/visrank.hip) -------------------------------------------------------------------- */
+/* unit[i, :] = feat[i, :] / max(||feat[i, :]||_2, eps) ([N, F], F % 4 == 0): the operand of the cosine scoring, made once per
+ * model (visrank.py:44 torch.cosine_similarity, eps 1e-8). */
+int pxr_visrank_unit_rows_f32(const float* feat, int64_t N, int F, float eps, float* unit, void* stream);
+/* Workspace of the call below in bytes; -1 outside its limits (B >= 1, 1 <= H <= 64, N >= 1, 1 <= K <= 32).  Grows with B, K and
+ * the number of item splits only. */
+int64_t pxr_visrank_topk_ws_bytes(int B, int H, int N, int K);
+/* Fused VISRANK scoring (visrank.py:37-56 predict + trainer.py:333-336 masks + collector's torch.topk): per user b with the window
+ * w = the nonzero tail of window[b, :] (int64 [B, H], left-padded with 0, h = len(w) >= 1), S[r, j] = <unit[w[r]], unit[j]>,
+ * score[j] = the mean of the min(top_k, h) largest of S[:, j] (top_k in 1..16; top_k == 0: the mean of all h), score[0] = -inf and
+ * score[i] = -inf for every i in hist_items[hist_ptr[b] .. hist_ptr[b + 1]) (the CSR of pxr_score_topk_f32; may be NULL);
+ * topk_idx int64 / topk_val [B, K] = the K best, descending (fewer than K unmasked items: id -1, value -inf).  S never reaches
+ * memory.  A window or history id outside [0, N), a 0 inside the window's tail or an empty window ORs bit 0 into the status word
+ * and leaves both outputs untouched.  F % 4 == 0, N * F * 4 < 2 GiB. */
+int pxr_visrank_topk_f32(const float* unit, int N, int F, const int64_t* window, int B, int H, int top_k, const int32_t* hist_ptr,
+                         const int64_t* hist_items, int K, int64_t* topk_idx, float* topk_val, void* ws, int64_t ws_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -500,6 +500,38 @@ class AcfEvalBatcher(SeqEvalBatcher):
             yield torch.cat((item_seq, uid[:, None]), dim=1), hist, pos_u, target
 
 
+class VisRankEvalBatcher(SeqEvalBatcher):
+    """VisRankEvalDataset (reference evalset.py:113-145; one unpadded history per batch of 1) through SeqEvalBatcher: the same users,
+    targets and FULL-history pairs, with the model's window -- the last `history_window` history items (visrank.py:39 user[-50:],
+    default 50), left-padded with 0 -- in place of the MAX_ITEM_LIST_LENGTH window:
+    `(window [b, history_window], (history_u, history_i), positive_u [b], item_target [b])`."""
+
+    def __init__(self, config, dataload, phase="valid", rank=0, world=1):
+        super().__init__(config, dataload, phase=phase, rank=rank, world=world)
+        w = config["history_window"] if "history_window" in config else None
+        self.L = 50 if w is None else int(w)
+        if (self.cut < 1).any():
+            raise ValueError("VisRankEvalBatcher: a user without history (the mean of nothing)")
+
+
+class _NoTraining:
+    """The train side of a model that is not trained (VISRANK): a `_TrainLoader`-shaped object without batches."""
+
+    def __init__(self, dataload):
+        self.dataload = dataload
+        self.item_num = dataload.item_num
+        self.batcher = self.sampler = self.dataset = self
+
+    def set_epoch(self, epoch):
+        return None
+
+    def __len__(self):
+        return 0
+
+    def __iter__(self):
+        return iter(())
+
+
 class GraphTrainBatcher:
     """Vectorised GraphTrainDataset (reference REC/data/dataset/trainset.py:939-981) under torch's DistributedSampler order: one
     sample per AUGSEQ prefix (Data._build_aug_seq), yielded as whole (item_seq int64 [B, L], mask int64 [B, L], target int64

@@ -15,11 +15,12 @@ from torch.utils.data import DataLoader
 from ..parallel import world_info
 from .dataload import Data
 from .dataset import (AcfEvalBatcher, BERT4RecTrainBatcher, GraphEvalBatcher, GraphTrainBatcher, PairEvalBatcher, PairTrainBatcher, SeqEvalBatcher,
-                      SampleAcfTrainBatcher, SeqEvalDataset, SeqTrainBatcher, TwoTowerTrainBatcher, seq_eval_collate)
+                      SampleAcfTrainBatcher, SeqEvalDataset, SeqTrainBatcher, TwoTowerTrainBatcher, VisRankEvalBatcher, _NoTraining,
+                      seq_eval_collate)
 
 SUPPORTED = {"SASRec": "SEQ", "MOSASRec": "SEQ", "FSASRec": "SEQ", "GRU4Rec": "SEQ", "NextItNet": "SEQ",
              "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR", "MF": "PAIR", "VBPR": "PAIR",
-             "SRGNN": "AUGSEQ", "LightSANs": "TWOTOWER", "ACF": "SEQ"}      # REC/data/utils.py:24-31
+             "SRGNN": "AUGSEQ", "LightSANs": "TWOTOWER", "ACF": "SEQ", "VISRANK": "EVALONLY"}      # REC/data/utils.py:24-31
 
 
 def load_data(config):
@@ -77,6 +78,12 @@ def bulid_dataloader(config, dataload):
     logger = getLogger()
     logger.info(f"[Training]: train_batch_size = [{config['train_batch_size']}]")
     logger.info(f"[Evaluation]: eval_batch_size = [{config['eval_batch_size']}]")
+    if SUPPORTED[model_name] == "EVALONLY":
+        # BaseDataset / VisRankEvalDataset (REC/data/utils.py:37): nothing to train, windows + full histories to score
+        if config["need_training"] is not False:
+            raise ValueError(f"{model_name} is not trained: set `need_training: False` (reference ViNet/visrank.yaml)")
+        return (_NoTraining(dataload), VisRankEvalBatcher(config, dataload, phase="valid", rank=rank, world=world),
+                VisRankEvalBatcher(config, dataload, phase="test", rank=rank, world=world))
     if SUPPORTED[model_name] == "PAIR":
         # PairTrainDataset / PairEvalDataset (REC/data/utils.py:24-31): one sample per training interaction, users scored
         train_loader = _TrainLoader(PairTrainBatcher(config, dataload, rank=rank, world=world))

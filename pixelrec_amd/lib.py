@@ -170,6 +170,9 @@ _SIGNATURES = {
     "pxr_acf_region_dx_f32": (_I, [_P, _P, _P, _P, _I64, _I, _I, _P]),
     "pxr_acf_item_fwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "pxr_acf_item_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "pxr_visrank_unit_rows_f32": (_I, [_P, _I64, _I, _F, _P, _P]),
+    "pxr_visrank_topk_ws_bytes": (_I64, [_I, _I, _I, _I]),
+    "pxr_visrank_topk_f32": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I64, _P]),
 }
 
 

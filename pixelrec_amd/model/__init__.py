@@ -13,4 +13,5 @@ from .lightsans import LightSANs  # noqa: F401
 from .mf import MF  # noqa: F401
 from .vbpr import VBPR  # noqa: F401
 from .acf import ACF  # noqa: F401
+from .visrank import VISRANK  # noqa: F401
 from .sharded import ShardedDataParallel, ShardedSASRec  # noqa: F401

@@ -2371,3 +2371,46 @@ def acf_item_bwd(duser, uw, pq, cx, prof, w, alpha, da, dprof, duw, dw_part):
     _l.check(Lb.pxr_acf_item_bwd_f32(_l.ptr(duser), _l.ptr(uw), _l.ptr(pq), _l.ptr(cx), _l.ptr(prof), _l.ptr(w), _l.ptr(alpha), B, P,
                                      E, _l.ptr(da), _l.ptr(dprof), _l.ptr(duw), _l.ptr(dw_part), _l.stream_ptr()),
              "pxr_acf_item_bwd_f32")
+
+
+# ------------------------------------------------------------------------------------------------ VISRANK (csrc/visrank.hip)
+def visrank_unit_rows(feat, eps: float = 1e-8, out=None):
+    """feat [N, F] -> unit [N, F] = feat / max(||feat||_2, eps) row by row (F % 4 == 0): the cosine scoring's operand, made once."""
+    Lb = _l.load()
+    _req(feat, torch.float32, "feat")
+    if feat.dim() != 2:
+        raise _l.PxrError(f"visrank unit rows: feat must be [N, F], got {tuple(feat.shape)}")
+    N, F = feat.shape
+    out = out if out is not None else torch.empty_like(feat)
+    _req(out, torch.float32, "out")
+    if tuple(out.shape) != (N, F):
+        raise _l.PxrError(f"visrank unit rows: out must be [{N}, {F}]")
+    _l.check(Lb.pxr_visrank_unit_rows_f32(_l.ptr(feat), N, F, float(eps), _l.ptr(out), _l.stream_ptr()), "pxr_visrank_unit_rows_f32")
+    return out
+
+
+def visrank_topk(unit, window, top_k: int, K: int, hist_ptr=None, hist_items=None):
+    """Fused VISRANK scoring + masks + top-K (pxr_visrank_topk_f32): unit [N, F] unit rows, window int64 [B, H <= 64] left-padded
+    with 0, top_k in 1..16 (the mean of the min(top_k, h) largest similarities) or 0 (the mean over the window), hist_ptr int32
+    [B + 1] / hist_items int64 the CSR of the full histories.  Returns (topk_idx int64 [B, K], topk_val fp32 [B, K]).  Bad ids
+    flag the status word (ops.raise_on_bad_indices) and leave both outputs untouched."""
+    Lb = _l.load()
+    _req(unit, torch.float32, "unit"); _req(window, torch.int64, "window")
+    if unit.dim() != 2 or window.dim() != 2:
+        raise _l.PxrError("visrank top-k: unit must be [N, F] and window [B, H]")
+    N, F = unit.shape
+    B, H = window.shape
+    if hist_ptr is not None:
+        _req(hist_ptr, torch.int32, "hist_ptr"); _req(hist_items, torch.int64, "hist_items")
+        if hist_ptr.numel() != B + 1:
+            raise _l.PxrError(f"visrank top-k: hist_ptr must have B + 1 = {B + 1} entries")
+    ws_bytes = int(Lb.pxr_visrank_topk_ws_bytes(B, H, N, K))
+    if ws_bytes < 0:
+        raise _l.PxrError(f"visrank top-k: need B >= 1, 1 <= H <= 64, 1 <= K <= 32 (B={B}, H={H}, K={K})")
+    device_status(unit.device)
+    idx = torch.empty(B, K, dtype=torch.int64, device=unit.device)
+    val = torch.empty(B, K, dtype=torch.float32, device=unit.device)
+    ws = _ws.get(ws_bytes, unit.device)
+    _l.check(Lb.pxr_visrank_topk_f32(_l.ptr(unit), N, F, _l.ptr(window), B, H, int(top_k), _l.ptr(hist_ptr), _l.ptr(hist_items), K,
+                                     _l.ptr(idx), _l.ptr(val), _l.ptr(ws), ws_bytes, _l.stream_ptr()), "pxr_visrank_topk_f32")
+    return idx, val

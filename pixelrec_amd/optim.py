@@ -486,6 +486,31 @@ class PxrAdamW:
         self._dirty = False
 
 
+class NoParamAdamW:
+    """The optimizer of a model without anything to train (VISRANK: one zero-size parameter): torch.optim.AdamW over its
+    parameters, as the reference builds it (trainer.py:99-103), behind the interface the Trainer drives -- so checkpoints keep
+    the reference's optimizer layout and load back."""
+
+    def __init__(self, model, lr=1e-4, weight_decay=0.1):
+        self.opt = torch.optim.AdamW(list(model.parameters()), lr=lr, weight_decay=weight_decay)
+        self.param_groups = self.opt.param_groups
+
+    def zero_grad(self, set_to_none: bool = True):
+        self.opt.zero_grad(set_to_none=set_to_none)
+
+    def step(self):
+        return None
+
+    def flush(self):
+        return None
+
+    def state_dict(self, layout: str = "torch"):
+        return self.opt.state_dict()
+
+    def load_state_dict(self, sd):
+        self.opt.load_state_dict(sd)
+
+
 def clip_grad_norm_(model, max_norm, norm_type=2.0, **_ignored):
     """torch.nn.utils.clip_grad_norm_ for this build's gradient layout (reference trainer.py:123-124, K18): the flat
     gradient buffer + the sparse table rows (absent rows are zeros of the dense gradient the reference clips) + the

@@ -119,6 +119,9 @@ class Trainer:
         self.item_feature = None
         self.tot_item_num = None
         self.fused_topk = config["eval_fused_topk"] is None or bool(config["eval_fused_topk"])
+        if self.fused_topk and getattr(model.module, "fused_topk_supported", True) is False:
+            self.logger.info("eval_fused_topk: this model's settings are outside its fused scoring; evaluating through predict()")
+            self.fused_topk = False
         # The host side of the loop is index arithmetic on small arrays (batcher, packing, pinned staging).  With the intra-op pool
         # torch sizes by default -- one thread per core, 256 on the GPU hosts -- every torch.cat / copy above ATen's grain size wakes
         # that whole team: measured on the Pixel200K-shaped run, B = 512 batches took 32 ms each to build instead of 3 (18 K instead
@@ -160,6 +163,11 @@ class Trainer:
         parameter is a 'rec' parameter, so both spellings resolve to one AdamW."""
         a = self.optim_args
         m = self.model.module
+        if sum(p.numel() for p in m.parameters()) == 0:
+            # nothing to train (VISRANK's zero-size placeholder): the reference's plain AdamW over it, for the checkpoint's sake
+            from ..optim import NoParamAdamW
+
+            return NoParamAdamW(m, lr=a["learning_rate"], weight_decay=a["weight_decay"])
         if getattr(m, "split_flat_table_groups", False):
             # a model whose flat buffer and table buffer may be separate parameter groups (VBPR, decay_check_name 'projection'):
             # the split runs on the native path with every scalar on the device, so the step stays capturable
@@ -446,6 +454,8 @@ class Trainer:
         # the fused scoring's main pass reads the item vectors as pre-split planes: made once per evaluation (0.4 ms for
         # 400 K x 512), reused by every batch of users
         self._item_planes = self._item_norm_max = None
+        if self._score_matrix is None:      # a model that scores without an item matrix (VISRANK: compute_item_all is None)
+            return
         use_p = self.config["eval_planes"]
         if self.fused_topk and (use_p is None or bool(use_p)) and ops.score_planes_supported(self._score_matrix.data):
             buf = getattr(self, "_item_planes_buf", None)
@@ -532,6 +542,8 @@ class Trainer:
             user_d = user.to(self.device)
             if history_index is not None:
                 ptr, items = ops.history_csr(history_index[0], history_index[1], user.shape[0], self.device)
+        if hasattr(m, "fused_topk_batch"):            # a model with a fused scoring of its own (VISRANK: csrc/visrank.hip)
+            return m.fused_topk_batch(user_d, ptr, items, max(self.config["topk"])), positive_i
         # models whose item vectors come from an encoder (MOSASRec, FSASRec) read the sequence's rows from item_feature
         out, last = (m.encode_last(user_d, self.item_feature) if (self.use_modality or not has_item_table(m))
                      else m.encode_last(user_d))
