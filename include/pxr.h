@@ -385,8 +385,9 @@ int pxr_add_f32(const float* a, const float* b, float* out, int64_t n, void* str
 int pxr_dropout_f32(const float* x, float* y, int64_t n, float p, uint64_t seed, uint32_t stream_id, const int64_t* step_dev,
                     void* stream);
 
-/* y = x W^T + b (act=1: erf-GELU, pre-activation saved; act=2: erf-GELU, gelu'(pre-activation) saved)
- *                                                          layers.py:586-588,613,666-667,669; sasrec.py:112 */
+/* y = x W^T + b (act=1: erf-GELU, pre-activation saved; act=2: erf-GELU, gelu'(pre-activation) saved; act=3..7: relu / swish /
+ * tanh / sigmoid / selu of it, act'(pre-activation) saved -- selu' at exactly 0 is scale * alpha, torch's backward)
+ *                                        layers.py:586-588,613,642-649,666-667,669; sasrec.py:112; ViNet/curatornet.py:67-82 */
 int pxr_linear_fwd_f32(const float* x, const float* W, const float* b, float* y, float* pre, int M, int N, int K,
                        int act, void* stream);
 /* dx = dy W, optionally * gelu'(dgelu_pre) OR + add (residual gradient) OR * mul (gelu' saved by act=2);
@@ -790,6 +791,30 @@ int64_t pxr_visrank_topk_ws_bytes(int B, int H, int N, int K);
 int pxr_visrank_topk_f32(const float* unit, int N, int F, const int64_t* window, int B, int H, int top_k, const int32_t* hist_ptr,
                          const int64_t* hist_items, int K, int64_t* topk_idx, float* topk_val, void* ws, int64_t ws_bytes,
                          void* stream);
+
+/* ---- CuratorNet (model/ViNet/curatornet.py; csrc/curator.hip) ------------------------------------------------------------- */
+/* Profile pooling (curatornet.py:77-79 forward, :96-99 predict: AdaptiveMaxPool2d / AdaptiveAvgPool2d((1, E)) on [B, L, E], then
+ * torch.cat): cat[b, :] = [max over l | mean over l] over ALL L positions, padding included (the mean divides by L); argmax uint8
+ * [B, E] (may be NULL) = the position of the max, the FIRST among equal values.  ids == NULL: h is [B, L, E] (n_items unused);
+ * ids int64 [B, L]: h is the item matrix [n_items, E] and position (b, l) reads row ids[b, l] (predict's item_feature[user]) --
+ * an id outside [0, n_items) ORs bit 0 into the status word and is clamped.  E % 4 == 0, E <= 4096, 1 <= L <= 255. */
+int pxr_curator_pool_f32(const float* h, const int64_t* ids, int64_t n_items, int B, int L, int E, float* cat, uint8_t* argmax,
+                         void* stream);
+/* Its backward joined with the head's item gradient and the SELU of selu_common2 (autograd of curatornet.py:67-79): dpre
+ * [B (L + 2), E], rows [B L profile | 2B positive, negative]: profile row (b, l) = (dcat[b, E + e] / L + [l == argmax[b, e]]
+ * dcat[b, e]) * dact[row, e]; row B L + j = di[j, e] * dact[row, e].  dcat [B, 2E], di [2B, E] (pxr_mf_pair_bwd_f32), dact
+ * [B (L + 2), E] = selu' saved by the forward.  Every element written once: no atomics. */
+int pxr_curator_pool_bwd_f32(const float* dcat, const uint8_t* argmax, const float* di, const float* dact, int B, int L, int E,
+                             float* dpre, void* stream);
+/* Pair head on the towers' outputs (curatornet.py:86-88): x_b = <u_b, i+_b> - <u_b, i-_b> with ufeat [B, H], ifeat [2B, H] =
+ * (positive, negative) per sample; lossrow[b] = -log(1e-8 + sigmoid(x_b)) -- the 1e-8 INSIDE the log, unlike mf.py's head --
+ * loss = mean, coef[b] = d loss / d x_b = -(1/B) sigmoid(x)(1 - sigmoid(x)) / (1e-8 + sigmoid(x)).  The backward is
+ * pxr_mf_pair_bwd_f32 on this coef.  H % 4 == 0, H <= 4096. */
+int pxr_curator_pair_fwd_f32(const float* ufeat, const float* ifeat, int H, int B, float* coef, float* lossrow, float* loss,
+                             void* stream);
+/* out = a * b elementwise (n % 4 == 0; out may alias a or b): the head's user gradient times selu' of selu_pu3 -- autograd of
+ * F.selu at curatornet.py:82, the one activation of the step with no GEMM in front of it whose epilogue could multiply. */
+int pxr_mul_f32(const float* a, const float* b, float* out, int64_t n, void* stream);
 
 #ifdef __cplusplus
 }

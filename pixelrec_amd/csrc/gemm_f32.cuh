@@ -375,7 +375,11 @@ enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_MUL_DGELU = 3, EPI_ADD
        EPI_LAST = 10,
        // planes GEMMs only (gemm_p3.hip): quick_gelu(acc + bias) without the derivative -- the frozen blocks of the image tower
        EPI_BIAS_QGELU = 11 };
-enum { ACT_RELU = 3, ACT_SWISH = 4, ACT_TANH = 5, ACT_SIGMOID = 6 };
+enum { ACT_RELU = 3, ACT_SWISH = 4, ACT_TANH = 5, ACT_SIGMOID = 6,
+       ACT_SELU = 7 };      // F.selu (model/ViNet/curatornet.py:67-82), not one of ACT2FN
+// selu(x) = s x for x > 0, else s a (exp(x) - 1); torch's backward takes the negative branch at x == 0 (derivative s a)
+#define PXR_SELU_SCALE 1.0507009873554804934193349852946f
+#define PXR_SELU_ALPHA 1.6732632423543772848170429916717f
 
 // Batched launch: grid.z = batch index z; operand offsets (in floats) = (z / nb2) * x1 + (z % nb2) * x2 -- two levels, so
 // that "image n, head h" of a packed [n, T, 3, heads, d] projection is addressed without copies.
@@ -522,6 +526,10 @@ __device__ __forceinline__ void epi_store(const typename Cfg::Acc& accs, const A
           } else if (act == ACT_TANH) {
             const float th = tanhf(v);
             dv = 1.0f - th * th; v = th;
+          } else if (act == ACT_SELU) {             // exp of min(x, 0) only: a large positive x never makes an inf
+            const float sa = PXR_SELU_SCALE * PXR_SELU_ALPHA, ex = __expf(fminf(v, 0.f));
+            dv = v > 0.f ? PXR_SELU_SCALE : sa * ex;
+            v = v > 0.f ? PXR_SELU_SCALE * v : sa * (ex - 1.0f);
           } else {                                  // sigmoid
             const float sg = 1.0f / (1.0f + __expf(-v));
             dv = sg * (1.0f - sg); v = sg;

@@ -601,8 +601,8 @@ extern "C" int pxr_gemm_batched_f32(int a_kc, int b_kc, int M, int N, int K, con
 // gelu'(pre-activation) saved to `pre` instead -- the form the training step uses: the backward is one multiply)
 extern "C" int pxr_linear_fwd_f32(const float* x, const float* W, const float* b, float* y, float* pre, int M,
                                   int N, int K, int act, void* stream) {
-  PXR_REQUIRE(act >= 0 && act <= ACT_SIGMOID, "pxr_linear_fwd_f32: bad act %d", act);
-  if (act >= ACT_RELU) {   // relu / swish / tanh / sigmoid: act'(pre-activation) saved to `pre`
+  PXR_REQUIRE(act >= 0 && act <= ACT_SELU, "pxr_linear_fwd_f32: bad act %d", act);
+  if (act >= ACT_RELU) {   // relu / swish / tanh / sigmoid / selu: act'(pre-activation) saved to `pre`
     g_bt = GemmBatch{};
     g_bt.act = act;
     const int rc = pxr_gemm_f32(1, 1, M, N, K, x, K, W, K, y, N, EPI_BIAS_ACT_GRAD, b, pre, N, nullptr, 0, 0, 0, stream);

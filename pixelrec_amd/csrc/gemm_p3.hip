@@ -53,6 +53,10 @@ __device__ __forceinline__ float p3_epi_elem(float v, float bv, float av, float&
     } else if (act == ACT_TANH) {
       const float th = tanhf(v);
       dv = 1.0f - th * th; v = th;
+    } else if (act == ACT_SELU) {
+      const float sa = PXR_SELU_SCALE * PXR_SELU_ALPHA, ex = __expf(fminf(v, 0.f));
+      dv = v > 0.f ? PXR_SELU_SCALE : sa * ex;
+      v = v > 0.f ? PXR_SELU_SCALE * v : sa * (ex - 1.0f);
     } else {
       const float sg = 1.0f / (1.0f + __expf(-v));
       dv = sg * (1.0f - sg); v = sg;

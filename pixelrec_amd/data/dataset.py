@@ -341,6 +341,62 @@ class SampleAcfTrainBatcher:
             yield torch.from_numpy(profile), torch.from_numpy(tail)
 
 
+class CuratorTrainBatcher:
+    """Vectorised TwoTowerTrainDataset (reference REC/data/dataset/trainset.py:256-290) over the SEQ chunks, under torch's
+    DistributedSampler order.  The reference maps CuratorNet to a `TwoTowerTrainDataset2` that does not exist
+    (REC/data/utils.py:39); CuratorNet.forward reads [profile | positive | negative] rows, which is TwoTowerTrainDataset's row
+    format, and the class is InputType.SEQ, so Data builds the chunks of at most L+1 items.  One sample per chunk: profile = the
+    chunk without its last item, left-padded with 0 to L; positive = the last item; one negative uniform over [1, item_num - 1]
+    and redrawn while it lies in the chunk -- the reference's distribution, not its random stream.  A chunk of one item gives an
+    all-padding profile.  Yields whole (profile int64 [B, L], target int64 [B, 2] = (positive, negative)) batches: the two
+    tensors the training loop stages (CuratorNet.forward joins them into the [B, L + 2] row).  The sample order and the split by
+    rank are SeqTrainBatcher's."""
+
+    MAX_REDRAWS = 1000
+
+    def __init__(self, config, dataload, rank=0, world=1, seed=0, drop_last=False):
+        self.dataload = dataload
+        self.item_num = dataload.item_num
+        self.L = config["MAX_ITEM_LIST_LENGTH"]
+        self.batch_size = config["train_batch_size"]
+        seqs = dataload.train_feat["item_seq"]
+        W = self.L + 1
+        self.n = len(seqs)
+        self.windows = np.zeros((self.n, W), dtype=np.int64)          # the chunks, left-padded
+        for i, s in enumerate(seqs):
+            self.windows[i, W - len(s):] = s
+        if self.item_num <= 2:
+            raise ValueError("CuratorTrainBatcher: no negative can be drawn from [1, item_num) outside a chunk")
+        self.rank, self.world, self.seed, self.epoch = rank, world, seed, 0
+        self.num_samples = -(-self.n // world)
+        self.drop_last = drop_last
+        self.neg_seed = int(config["seed"] or 0)
+
+    set_epoch = SeqTrainBatcher.set_epoch
+    __len__ = SeqTrainBatcher.__len__
+    _indices = SeqTrainBatcher._indices
+
+    def make_batch(self, rows, rng):
+        win = self.windows[rows]                                       # [B, L+1]
+        real = win != 0
+        neg = rng.integers(1, self.item_num, size=len(win))
+        for _ in range(self.MAX_REDRAWS):
+            clash = ((neg[:, None] == win) & real).any(1)
+            if not clash.any():
+                break
+            neg[clash] = rng.integers(1, self.item_num, size=int(clash.sum()))
+        else:
+            raise ValueError("CuratorTrainBatcher: a chunk covers (nearly) every item: no negative could be drawn")
+        return win[:, :-1].copy(), np.stack((win[:, -1], neg), axis=1)
+
+    def __iter__(self):
+        idx = self._indices()
+        rng = np.random.default_rng([self.neg_seed, self.epoch, self.rank])
+        for b in range(len(self)):
+            profile, target = self.make_batch(idx[b * self.batch_size:(b + 1) * self.batch_size], rng)
+            yield torch.from_numpy(profile), torch.from_numpy(target)
+
+
 class SeqEvalDataset(Dataset):
     def __init__(self, config, dataload, phase="valid"):
         self.dataload = dataload

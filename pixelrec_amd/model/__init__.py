@@ -14,4 +14,5 @@ from .mf import MF  # noqa: F401
 from .vbpr import VBPR  # noqa: F401
 from .acf import ACF  # noqa: F401
 from .visrank import VISRANK  # noqa: F401
+from .curatornet import CuratorNet  # noqa: F401
 from .sharded import ShardedDataParallel, ShardedSASRec  # noqa: F401

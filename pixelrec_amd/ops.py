@@ -321,7 +321,8 @@ def gemm_mode() -> str:
     return "bf16x3" if _l.load().pxr_get_gemm_mode() else "f32"
 
 
-ACT_CODES = {"relu": 3, "swish": 4, "tanh": 5, "sigmoid": 6}      # the reference's ACT2FN besides gelu (layers.py:642-649)
+# the reference's ACT2FN besides gelu (layers.py:642-649), and F.selu (ViNet/curatornet.py:67-82)
+ACT_CODES = {"relu": 3, "swish": 4, "tanh": 5, "sigmoid": 6, "selu": 7}
 
 
 def linear_fwd(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor | None, gelu: bool = False, save_grad: bool = False,
@@ -2371,6 +2372,87 @@ def acf_item_bwd(duser, uw, pq, cx, prof, w, alpha, da, dprof, duw, dw_part):
     _l.check(Lb.pxr_acf_item_bwd_f32(_l.ptr(duser), _l.ptr(uw), _l.ptr(pq), _l.ptr(cx), _l.ptr(prof), _l.ptr(w), _l.ptr(alpha), B, P,
                                      E, _l.ptr(da), _l.ptr(dprof), _l.ptr(duw), _l.ptr(dw_part), _l.stream_ptr()),
              "pxr_acf_item_bwd_f32")
+
+
+# ------------------------------------------------------------------------------------------------ CuratorNet (csrc/curator.hip)
+def curator_pool(h, B: int, L: int, ids=None, cat=None, argmax=None, want_argmax: bool = True):
+    """Profile pooling (pxr_curator_pool_f32) -> (cat [B, 2E] = [max over L | mean over L], argmax uint8 [B, E] | None).  ids None:
+    h holds the B L profile rows first ([>= B L, E], read in place); ids int64 [B, L]: h is the item matrix [I, E] and position
+    (b, l) reads row ids[b, l] (a bad id flags the status word).  Padded positions are pooled like any other; the mean divides by L."""
+    Lb = _l.load()
+    _req(h, torch.float32, "h")
+    if h.dim() != 2:
+        raise _l.PxrError("curator pool: h must be 2-D ([rows, E])")
+    E = h.shape[1]
+    if not 1 <= L <= 255:
+        raise _l.PxrError(f"curator pool: need 1 <= L <= 255 (the argmax is stored in a byte), got L={L}")
+    if ids is not None:
+        _req(ids, torch.int64, "ids")
+        if ids.numel() != B * L:
+            raise _l.PxrError(f"curator pool: ids must be [B, L] = [{B}, {L}], got {tuple(ids.shape)}")
+        device_status(h.device)
+    elif h.shape[0] < B * L:
+        raise _l.PxrError(f"curator pool: h has {h.shape[0]} rows, the profiles need B L = {B * L}")
+    cat = cat if cat is not None else torch.empty(B, 2 * E, dtype=torch.float32, device=h.device)
+    if want_argmax and argmax is None:
+        argmax = torch.empty(B, E, dtype=torch.uint8, device=h.device)
+    if cat.numel() != 2 * B * E or cat.dtype != torch.float32 or (argmax is not None and (argmax.numel() != B * E or
+                                                                                           argmax.dtype != torch.uint8)):
+        raise _l.PxrError("curator pool: cat must be float32 [B, 2E] and argmax uint8 [B, E]")
+    _l.check(Lb.pxr_curator_pool_f32(_l.ptr(h), _l.ptr(ids), h.shape[0] if ids is not None else 0, B, L, E, _l.ptr(cat),
+                                     _l.ptr(argmax), _l.stream_ptr()), "pxr_curator_pool_f32")
+    if ids is not None and _CHECK_IDX:
+        raise_on_bad_indices(h.device)
+    return cat, argmax
+
+
+def curator_pool_bwd(dcat, argmax, di, dact, B: int, L: int, out=None):
+    """Pooling backward joined with the head's item gradient and selu' of the second common Linear (pxr_curator_pool_bwd_f32):
+    dcat [B, 2E], argmax uint8 [B, E], di [2B, E], dact [B (L + 2), E] -> the pre-activation gradient [B (L + 2), E]."""
+    Lb = _l.load()
+    for t, nm in ((dcat, "dcat"), (di, "di"), (dact, "dact")):
+        _req(t, torch.float32, nm)
+    _req(argmax, torch.uint8, "argmax")
+    E = dact.shape[-1]
+    n = B * (L + 2)
+    if dcat.numel() != 2 * B * E or argmax.numel() != B * E or di.numel() != 2 * B * E or dact.numel() != n * E:
+        raise _l.PxrError("curator pool backward: need dcat [B, 2E], argmax [B, E], di [2B, E], dact [B (L + 2), E]")
+    out = out if out is not None else torch.empty(n, E, dtype=torch.float32, device=dact.device)
+    if out.numel() != n * E or out.dtype != torch.float32 or not out.is_contiguous():
+        raise _l.PxrError("curator pool backward: out must be a contiguous float32 [B (L + 2), E]")
+    _l.check(Lb.pxr_curator_pool_bwd_f32(_l.ptr(dcat), _l.ptr(argmax), _l.ptr(di), _l.ptr(dact), B, L, E, _l.ptr(out),
+                                         _l.stream_ptr()), "pxr_curator_pool_bwd_f32")
+    return out
+
+
+def curator_pair_fwd(ufeat, ifeat, B: int, out=None):
+    """CuratorNet's pair loss head (pxr_curator_pair_fwd_f32): ufeat [B, H], ifeat [2B, H] -> (loss [1] = -mean log(1e-8 +
+    sigmoid(x_b)), coef [B] = d loss / d x_b).  The 1e-8 is inside the log (mf_pair_fwd has it outside); mf_pair_bwd takes this
+    coef.  out: a float32 [2B + 1] buffer to reuse."""
+    _req(ufeat, torch.float32, "ufeat"); _req(ifeat, torch.float32, "ifeat")
+    H = ufeat.shape[-1]
+    if tuple(ufeat.shape) != (B, H) or tuple(ifeat.shape) != (2 * B, H):
+        raise _l.PxrError(f"curator pair head: tower outputs must be [B, H] and [2B, H] for B={B}")
+    f = out if out is not None else torch.empty(2 * B + 1, dtype=torch.float32, device=ufeat.device)
+    if f.numel() != 2 * B + 1 or f.dtype != torch.float32:
+        raise _l.PxrError("curator pair head: out must be float32 [2B + 1]")
+    coef, lossrow, loss = f[:B], f[B:2 * B], f[2 * B:]
+    _l.check(_l.load().pxr_curator_pair_fwd_f32(_l.ptr(ufeat), _l.ptr(ifeat), H, B, _l.ptr(coef), _l.ptr(lossrow), _l.ptr(loss),
+                                                _l.stream_ptr()), "pxr_curator_pair_fwd_f32")
+    return loss, coef
+
+
+def mul(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """out = a * b elementwise (pxr_mul_f32): a gradient times a saved activation derivative where no GEMM epilogue can do it."""
+    _req(a, torch.float32, "a"); _req(b, torch.float32, "b")
+    if a.shape != b.shape:
+        raise _l.PxrError(f"mul: shapes differ ({tuple(a.shape)} and {tuple(b.shape)})")
+    out = out if out is not None else torch.empty_like(a)
+    _req(out, torch.float32, "out")
+    if out.numel() != a.numel():
+        raise _l.PxrError("mul: out has the wrong size")
+    _l.check(_l.load().pxr_mul_f32(_l.ptr(a), _l.ptr(b), _l.ptr(out), a.numel(), _l.stream_ptr()), "pxr_mul_f32")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ VISRANK (csrc/visrank.hip)
