@@ -816,6 +816,55 @@ int pxr_curator_pair_fwd_f32(const float* ufeat, const float* ifeat, int H, int 
  * F.selu at curatornet.py:82, the one activation of the step with no GEMM in front of it whose epilogue could multiply. */
 int pxr_mul_f32(const float* a, const float* b, float* out, int64_t n, void* stream);
 
+/* ---- DIN (model/IDNet/din.py with SequenceAttLayer, model/layers.py:460-514; csrc/din.hip) --------------------------------- */
+/* Occurrences of a batch: o in [0, B L) = history position (b, l); o = B L + 2 b + c = candidate c of sample b (0 positive, 1
+ * negative).  Pair rows of the attention MLP: r = (c B + b) L + l.  rows int64 [B L + 2 B] = the table row every occurrence reads
+ * (already range-checked: pxr_acf_rows_i64 with no users).
+ * Attention input (din.py:59-62 item_embedding(items); layers.py:486-491 repeat / cat): emb[o, :] = table[rows[o], :] and
+ * x[r, :] = [q | k | q - k | q * k] with q = the candidate's row, k = the history row.  emb [B L + 2 B, D], x [2 B L, 4 D].
+ * D % 4 == 0, D <= 4096. */
+int pxr_din_att_input_f32(const float* table, const int64_t* rows, int B, int L, int D, float* emb, float* x, void* stream);
+/* Head forward (layers.py:493-512 dense / masked_fill / divide / matmul; din.py:53 the score; din.py:79-81 the loss): alast
+ * [2 B L, hl] = the last hidden layer's activations, wd [hl], bd [1] = attention.dense, profile int64 [B, L] (0 = padding).
+ * s[r] = 0 at padding, else (<alast[r], wd> + bd) / sqrt(D); kq[r] = <k_l, q_c>; score_c = sum_l s kq in ascending l;
+ * head [2 + 3 B] = loss | 0.01 / (B ||emb||_2) (0 when the norm is 0) | coef [B] = d loss / d (score_0 - score_1) | the score
+ * differences [B] | per-sample sums of squares [B].  loss = -mean log(sigmoid(x) + 1e-8) + 0.01 ||emb||_2 / B, the norm over all
+ * B (L + 2) gathered rows (padding positions included), reduced in one fixed order. */
+int pxr_din_head_fwd_f32(const float* alast, const float* wd, const float* bd, const float* emb, const int64_t* profile, int B,
+                         int L, int D, int hl, float* s, float* kq, float* head, void* stream);
+/* Head backward, first half (autograd of the above down to the last hidden layer): g = grad_scale * grad_scale_dev[0];
+ * dsraw[r] = the gradient of dense's output (0 at padding), dz [2 B L, hl] = dsraw wd act' (dact = the derivative the forward
+ * GEMM saved), dwd [hl] and dbd [1] = the gradients of attention.dense, summed over r in one fixed order. */
+int pxr_din_head_bwd_f32(const float* alast, const float* dact, const float* wd, const int64_t* profile, const float* kq,
+                         const float* head, int B, int L, int D, int hl, float grad_scale, const float* grad_scale_dev, float* dz,
+                         float* dsraw, float* dwd, float* dbd, void* stream);
+/* Head backward, second half: one gradient row per occurrence, occ [B L + 2 B, D].  With dx [2 B L, 4 D] = the MLP's input
+ * gradient (blocks dx0 | dx1 | dx2 | dx3): candidate rows get g coef sum_l s k_l + sum_l (dx0 + dx2 + dx3 * k_l), history rows
+ * sum_c (g coef s q_c + dx1 - dx2 + dx3 * q_c) -- autograd of din.py:53 and layers.py:491 -- and every row the regulariser's
+ * g head[1] emb[o] (din.py:79).  A padding position's row is written as zeros (nn.Embedding(padding_idx=0) drops it). */
+int pxr_din_fold_bwd_f32(const float* dx, const float* emb, const int64_t* profile, const float* s, const float* head, int B, int L,
+                         int D, float grad_scale, const float* grad_scale_dev, float* occ, void* stream);
+/* The first Linear of the attention MLP factorised over cat[q, k, q - k, q * k] (layers.py:491-492): W1 [h1, 4 D] ->
+ * A = W1[:, 0:D] + W1[:, 2D:3D], Bm = W1[:, D:2D] - W1[:, 2D:3D], C = W1[:, 3D:4D], each [h1, D].  With the library's Linear on
+ * the item table, A gives the once-per-evaluation term A q + b1 of pxr_din_topk_f32. */
+int pxr_din_fold_w1_f32(const float* w1, int h1, int D, float* A, float* Bm, float* C, void* stream);
+/* Workspace of the call below in bytes; -1 outside the fused limits (D % 4 == 0, 4 <= D <= 128, 1 <= h1 <= 128, 0 <= h2 <= 128,
+ * 1 <= L <= 64, 1 <= K <= 32, N D 4 < 2 GiB).  Grows with B L h1 D (the scaled copies of C). */
+int64_t pxr_din_topk_ws_bytes(int B, int L, int N, int D, int h1, int h2, int K);
+/* Fused DIN evaluation (din.py:87-103 predict over CandiEvalDataset's [item_num, L + 1] id matrix per user + trainer.py:333-336
+ * masks + the collector's torch.topk): per user b, window row l with window[b, l] != 0 and item n,
+ *   z1 = aq[n, :] + Bm k_l + C (q_n * k_l),  s = dense(sigmoid(W2 sigmoid(z1) + b2)) / sqrt(D)   (h2 == 0: dense(sigmoid(z1))),
+ *   score[b, n] = sum_l s <k_l, q_n>     (a padded row contributes exactly 0; an all-padding window scores 0 everywhere)
+ * with aq [N, h1] = A q_n + b1, bm / cm [h1, D] from pxr_din_fold_w1_f32, w2 [h2, h1], b2 [h2], wd [h_last], bd [1].
+ * score[b, 0] = -inf and score[b, i] = -inf for i in hist_items[hist_ptr[b] .. hist_ptr[b + 1]) (the CSR of pxr_score_topk_f32;
+ * may be NULL); topk_idx int64 / topk_val [B, K] = the K best, descending (fewer than K unmasked items: id -1, value -inf).  No
+ * [B, L, N, *] value reaches memory.  A window or history id outside [0, N) ORs bit 0 into the status word and leaves both outputs
+ * untouched; nothing is read out of range. */
+int pxr_din_topk_f32(const float* table, int N, int D, const int64_t* window, int B, int L, const float* aq, const float* bm,
+                     const float* cm, int h1, const float* w2, const float* b2, int h2, const float* wd, const float* bd,
+                     const int32_t* hist_ptr, const int64_t* hist_items, int K, int64_t* topk_idx, float* topk_val, void* ws,
+                     int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -341,6 +341,20 @@ class SampleAcfTrainBatcher:
             yield torch.from_numpy(profile), torch.from_numpy(tail)
 
 
+class DinTrainBatcher(SampleAcfTrainBatcher):
+    """Vectorised SampleTwoTowerTrainDataset (reference REC/data/dataset/trainset.py:294-332) under torch's DistributedSampler
+    order: SampleAcfTrainBatcher's leave-one-out samples without the user id.  Every position j of every SEQ chunk is one sample:
+    profile = the chunk without item j (order kept, left-padded with 0 to L), positive = item j, one negative uniform over
+    [1, item_num - 1] and redrawn while it lies in the chunk.  The reference stacks a chunk's samples into one dataset item, so its
+    batches hold `train_batch_size` chunks; here a batch holds `train_batch_size` samples (ACF's decision).  Yields whole
+    (profile int64 [B, L], target int64 [B, 2] = (positive, negative)) batches: the two tensors the training loop stages
+    (DIN.forward joins them into the reference's [B, L + 2] row)."""
+
+    def make_batch(self, rows, rng):
+        profile, tail = super().make_batch(rows, rng)
+        return profile, np.ascontiguousarray(tail[:, :2])
+
+
 class CuratorTrainBatcher:
     """Vectorised TwoTowerTrainDataset (reference REC/data/dataset/trainset.py:256-290) over the SEQ chunks, under torch's
     DistributedSampler order.  The reference maps CuratorNet to a `TwoTowerTrainDataset2` that does not exist

@@ -177,6 +177,13 @@ _SIGNATURES = {
     "pxr_visrank_unit_rows_f32": (_I, [_P, _I64, _I, _F, _P, _P]),
     "pxr_visrank_topk_ws_bytes": (_I64, [_I, _I, _I, _I]),
     "pxr_visrank_topk_f32": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I64, _P]),
+    "pxr_din_att_input_f32": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "pxr_din_head_fwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "pxr_din_head_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
+    "pxr_din_fold_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P]),
+    "pxr_din_fold_w1_f32": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "pxr_din_topk_ws_bytes": (_I64, [_I, _I, _I, _I, _I, _I, _I]),
+    "pxr_din_topk_f32": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I64, _P]),
 }
 
 

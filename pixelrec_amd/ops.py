@@ -2496,3 +2496,184 @@ def visrank_topk(unit, window, top_k: int, K: int, hist_ptr=None, hist_items=Non
     _l.check(Lb.pxr_visrank_topk_f32(_l.ptr(unit), N, F, _l.ptr(window), B, H, int(top_k), _l.ptr(hist_ptr), _l.ptr(hist_items), K,
                                      _l.ptr(idx), _l.ptr(val), _l.ptr(ws), ws_bytes, _l.stream_ptr()), "pxr_visrank_topk_f32")
     return idx, val
+
+
+# ------------------------------------------------------------------------------------------------ DIN (csrc/din.hip)
+def din_rows(profile, target, n_items: int, out=None):
+    """profile int64 [B, L], target int64 [B, 2] -> (rows, gidx) int64 [B L + 2 B] of the [1 + I, D] table (item i at row 1 + i)
+    in the occurrence order history | candidates: rows = the row an occurrence reads, gidx = the row its gradient goes to (0 for
+    item id 0, the padding row).  Bad ids flag the status word (ops.raise_on_bad_indices) and are clamped.  out: int64 [2, n]."""
+    Lb = _l.load()
+    _req(profile, torch.int64, "profile"); _req(target, torch.int64, "target")
+    n_p, n_i = profile.numel(), target.numel()
+    n = n_p + n_i
+    buf = out if out is not None else torch.empty(2, n, dtype=torch.int64, device=profile.device)
+    if tuple(buf.shape) != (2, n) or buf.dtype != torch.int64:
+        raise _l.PxrError(f"din rows: out must be int64 [2, {n}]")
+    device_status(profile.device)
+    _l.check(Lb.pxr_acf_rows_i64(_l.ptr(profile), n_p, _l.ptr(target), n_i, None, 0, int(n_items), 1, _l.ptr(buf[0]),
+                                 _l.ptr(buf[1]), _l.stream_ptr()), "pxr_acf_rows_i64")
+    return buf[0], buf[1]
+
+
+def _din_shapes(B, L, D, emb=None, profile=None):
+    if emb is not None and (tuple(emb.shape) != (B * (L + 2), D) or not emb.is_contiguous()):
+        raise _l.PxrError(f"din: emb must be a contiguous [B (L + 2), D] = [{B * (L + 2)}, {D}], got {tuple(emb.shape)}")
+    if profile is not None and tuple(profile.shape) != (B, L):
+        raise _l.PxrError(f"din: profile must be [B, L] = [{B}, {L}], got {tuple(profile.shape)}")
+
+
+def din_att_input(table, rows, B: int, L: int, emb=None, x=None):
+    """Attention input (pxr_din_att_input_f32): table [T, D], rows int64 [B L + 2 B] (din_rows) -> (emb [B (L + 2), D] the gathered
+    rows, x [2 B L, 4 D] = [q | k | q - k | q * k], pair row r = (c B + b) L + l)."""
+    _req(table, torch.float32, "table"); _req(rows, torch.int64, "rows")
+    D = table.shape[1]
+    if rows.numel() != B * (L + 2):
+        raise _l.PxrError(f"din attention input: rows must hold B (L + 2) = {B * (L + 2)} entries, got {rows.numel()}")
+    emb = emb if emb is not None else torch.empty(B * (L + 2), D, dtype=torch.float32, device=table.device)
+    x = x if x is not None else torch.empty(2 * B * L, 4 * D, dtype=torch.float32, device=table.device)
+    _req(emb, torch.float32, "emb"); _req(x, torch.float32, "x")
+    _din_shapes(B, L, D, emb)
+    if tuple(x.shape) != (2 * B * L, 4 * D):
+        raise _l.PxrError(f"din attention input: x must be [2 B L, 4 D] = [{2 * B * L}, {4 * D}]")
+    _l.check(_l.load().pxr_din_att_input_f32(_l.ptr(table), _l.ptr(rows), B, L, D, _l.ptr(emb), _l.ptr(x), _l.stream_ptr()),
+             "pxr_din_att_input_f32")
+    return emb, x
+
+
+def din_head_fwd(alast, wd, bd, emb, profile, s=None, kq=None, head=None):
+    """Head forward (pxr_din_head_fwd_f32): alast [2 B L, hl], wd [hl], bd [1], emb [B (L + 2), D], profile int64 [B, L] ->
+    (loss [1], s [2 B L], kq [2 B L], head [2 + 3 B] = loss | regulariser coefficient | coef | score differences | squares)."""
+    for t, n in ((alast, "alast"), (wd, "wd"), (bd, "bd"), (emb, "emb")):
+        _req(t, torch.float32, n)
+    _req(profile, torch.int64, "profile")
+    B, L = profile.shape
+    D, hl = emb.shape[1], alast.shape[-1]
+    _din_shapes(B, L, D, emb, profile)
+    if alast.numel() != 2 * B * L * hl or wd.numel() != hl or bd.numel() != 1:
+        raise _l.PxrError(f"din head: alast must be [2 B L, hl], wd [hl], bd [1] (B={B}, L={L}, hl={hl})")
+    dev = emb.device
+    s = s if s is not None else torch.empty(2 * B * L, dtype=torch.float32, device=dev)
+    kq = kq if kq is not None else torch.empty(2 * B * L, dtype=torch.float32, device=dev)
+    head = head if head is not None else torch.empty(2 + 3 * B, dtype=torch.float32, device=dev)
+    if s.numel() != 2 * B * L or kq.numel() != 2 * B * L or head.numel() != 2 + 3 * B:
+        raise _l.PxrError("din head: s / kq must hold 2 B L floats and head 2 + 3 B")
+    _l.check(_l.load().pxr_din_head_fwd_f32(_l.ptr(alast), _l.ptr(wd), _l.ptr(bd), _l.ptr(emb), _l.ptr(profile), B, L, D, hl,
+                                            _l.ptr(s), _l.ptr(kq), _l.ptr(head), _l.stream_ptr()), "pxr_din_head_fwd_f32")
+    return head[:1], s, kq, head
+
+
+def din_head_bwd(alast, dact, wd, profile, kq, head, D: int, dwd, dbd, grad_scale=1.0, grad_scale_dev=None, dz=None, dsraw=None):
+    """Head backward down to the last hidden layer (pxr_din_head_bwd_f32) -> (dz [2 B L, hl], dsraw [2 B L]); dwd [hl] / dbd [1]
+    are written in place (the gradients of attention.dense)."""
+    for t, n in ((alast, "alast"), (dact, "dact"), (wd, "wd"), (kq, "kq"), (head, "head"), (dwd, "dwd"), (dbd, "dbd")):
+        _req(t, torch.float32, n)
+    _req(profile, torch.int64, "profile")
+    B, L = profile.shape
+    hl = alast.shape[-1]
+    if alast.numel() != 2 * B * L * hl or dact.shape != alast.shape or dwd.numel() != hl or dbd.numel() != 1:
+        raise _l.PxrError("din head backward: alast / dact must be [2 B L, hl], dwd [hl], dbd [1]")
+    if kq.numel() != 2 * B * L or head.numel() != 2 + 3 * B:
+        raise _l.PxrError("din head backward: kq must hold 2 B L floats and head 2 + 3 B")
+    gsd = grad_scale_dev if grad_scale_dev is not None else torch.ones(1, dtype=torch.float32, device=alast.device)
+    dz = dz if dz is not None else torch.empty_like(alast)
+    dsraw = dsraw if dsraw is not None else torch.empty(2 * B * L, dtype=torch.float32, device=alast.device)
+    if dz.numel() != alast.numel() or dsraw.numel() != 2 * B * L:
+        raise _l.PxrError("din head backward: dz / dsraw have the wrong size")
+    _l.check(_l.load().pxr_din_head_bwd_f32(_l.ptr(alast), _l.ptr(dact), _l.ptr(wd), _l.ptr(profile), _l.ptr(kq), _l.ptr(head), B, L,
+                                            int(D), hl, float(grad_scale), _l.ptr(gsd), _l.ptr(dz), _l.ptr(dsraw), _l.ptr(dwd),
+                                            _l.ptr(dbd), _l.stream_ptr()), "pxr_din_head_bwd_f32")
+    return dz, dsraw
+
+
+def din_fold_bwd(dx, emb, profile, s, head, grad_scale=1.0, grad_scale_dev=None, occ=None):
+    """One gradient row per occurrence (pxr_din_fold_bwd_f32): dx [2 B L, 4 D] the MLP's input gradient -> occ [B (L + 2), D]."""
+    for t, n in ((dx, "dx"), (emb, "emb"), (s, "s"), (head, "head")):
+        _req(t, torch.float32, n)
+    _req(profile, torch.int64, "profile")
+    B, L = profile.shape
+    D = emb.shape[1]
+    _din_shapes(B, L, D, emb, profile)
+    if dx.numel() != 2 * B * L * 4 * D or s.numel() != 2 * B * L or head.numel() != 2 + 3 * B:
+        raise _l.PxrError("din fold backward: dx must be [2 B L, 4 D], s [2 B L], head [2 + 3 B]")
+    gsd = grad_scale_dev if grad_scale_dev is not None else torch.ones(1, dtype=torch.float32, device=emb.device)
+    occ = occ if occ is not None else torch.empty_like(emb)
+    _req(occ, torch.float32, "occ")
+    _din_shapes(B, L, D, occ)
+    _l.check(_l.load().pxr_din_fold_bwd_f32(_l.ptr(dx), _l.ptr(emb), _l.ptr(profile), _l.ptr(s), _l.ptr(head), B, L, D,
+                                            float(grad_scale), _l.ptr(gsd), _l.ptr(occ), _l.stream_ptr()), "pxr_din_fold_bwd_f32")
+    return occ
+
+
+def din_fold_w1(w1, D: int):
+    """W1 [h1, 4 D] -> (A, Bm, C) [h1, D] each: the first attention Linear factorised over cat[q, k, q - k, q * k]."""
+    _req(w1, torch.float32, "w1")
+    if w1.dim() != 2 or w1.shape[1] != 4 * D:
+        raise _l.PxrError(f"din fold: W1 must be [h1, 4 D] with D = {D}, got {tuple(w1.shape)}")
+    h1 = w1.shape[0]
+    out = torch.empty(3, h1, D, dtype=torch.float32, device=w1.device)
+    _l.check(_l.load().pxr_din_fold_w1_f32(_l.ptr(w1), h1, D, _l.ptr(out[0]), _l.ptr(out[1]), _l.ptr(out[2]), _l.stream_ptr()),
+             "pxr_din_fold_w1_f32")
+    return out[0], out[1], out[2]
+
+
+DIN_MAX_D, DIN_MAX_HIDDEN, DIN_MAX_L, DIN_WS_CAP = 128, 128, 64, 1 << 28
+
+
+def din_topk_supported(D: int, hidden, L: int, K: int = 10) -> bool:
+    """Whether pxr_din_topk_f32 takes this shape: D % 4 == 0 up to 128, one or two hidden layers of at most 128 units, L <= 64,
+    K <= 32."""
+    hidden = list(hidden)
+    if len(hidden) not in (1, 2):
+        return False
+    h1, h2 = hidden[0], (hidden[1] if len(hidden) == 2 else 0)
+    return int(_l.load().pxr_din_topk_ws_bytes(1, int(L), 1, int(D), int(h1), int(h2), int(K))) >= 0 and h1 >= 1 and (len(hidden) == 1 or h2 >= 1)
+
+
+def din_topk(table, window, aq, bm, cm, w2, b2, wd, bd, K: int, hist_ptr=None, hist_items=None):
+    """Fused DIN scoring + masks + top-K (pxr_din_topk_f32): table [N, D], window int64 [B, L] left-padded with 0, aq [N, h1] =
+    A q + b1, bm / cm [h1, D] (din_fold_w1), w2 [h2, h1] / b2 [h2] or None (one hidden layer), wd [h_last], bd [1], hist_ptr int32
+    [B + 1] / hist_items int64 the CSR of the full histories.  Returns (topk_idx int64 [B, K], topk_val fp32 [B, K]).  Users are
+    taken in chunks that keep the workspace (a scaled copy of C per window position) below DIN_WS_CAP bytes.  Bad ids flag the
+    status word (ops.raise_on_bad_indices) and leave both outputs untouched."""
+    Lb = _l.load()
+    for t, n in ((table, "table"), (aq, "aq"), (bm, "bm"), (cm, "cm"), (wd, "wd"), (bd, "bd")):
+        _req(t, torch.float32, n)
+    _req(window, torch.int64, "window")
+    if table.dim() != 2 or window.dim() != 2:
+        raise _l.PxrError("din top-k: table must be [N, D] and window [B, L]")
+    N, D = table.shape
+    B, L = window.shape
+    h1 = bm.shape[0]
+    h2 = 0
+    if w2 is not None:
+        _req(w2, torch.float32, "w2"); _req(b2, torch.float32, "b2")
+        h2 = w2.shape[0]
+        if tuple(w2.shape) != (h2, h1) or b2.numel() != h2:
+            raise _l.PxrError(f"din top-k: w2 must be [h2, h1] = [{h2}, {h1}] and b2 [h2]")
+    if tuple(aq.shape) != (N, h1) or tuple(bm.shape) != (h1, D) or tuple(cm.shape) != (h1, D):
+        raise _l.PxrError(f"din top-k: aq must be [N, h1] and bm / cm [h1, D] (N={N}, D={D}, h1={h1})")
+    if wd.numel() != (h2 or h1) or bd.numel() != 1:
+        raise _l.PxrError("din top-k: wd must hold h_last floats and bd one")
+    if hist_ptr is not None:
+        _req(hist_ptr, torch.int32, "hist_ptr"); _req(hist_items, torch.int64, "hist_items")
+        if hist_ptr.numel() != B + 1:
+            raise _l.PxrError(f"din top-k: hist_ptr must have B + 1 = {B + 1} entries")
+    if int(Lb.pxr_din_topk_ws_bytes(1, L, N, D, h1, h2, K)) < 0:
+        raise _l.PxrError(f"din top-k: outside the fused limits (D % 4 == 0 up to 128, hidden widths up to 128, L <= 64, K <= 32): "
+                          f"D={D}, hidden=({h1}, {h2}), L={L}, K={K}")
+    device_status(table.device)
+    idx = torch.empty(B, K, dtype=torch.int64, device=table.device)
+    val = torch.empty(B, K, dtype=torch.float32, device=table.device)
+    chunk = max(1, min(B, DIN_WS_CAP // max(1, L * (h1 * D + 128) * 4)))
+    for lo in range(0, B, chunk):
+        hi = min(B, lo + chunk)
+        ws_bytes = int(Lb.pxr_din_topk_ws_bytes(hi - lo, L, N, D, h1, h2, K))
+        ws = _ws.get(ws_bytes, table.device)
+        # (the CSR offsets are absolute: a chunk's slice of hist_ptr still indexes the whole hist_items)
+        hp = hist_ptr[lo:hi + 1] if hist_ptr is not None else None
+        _l.check(Lb.pxr_din_topk_f32(_l.ptr(table), N, D, _l.ptr(window[lo:hi]), hi - lo, L, _l.ptr(aq), _l.ptr(bm), _l.ptr(cm), h1,
+                                     _l.ptr(w2), _l.ptr(b2), h2, _l.ptr(wd), _l.ptr(bd), _l.ptr(hp), _l.ptr(hist_items), K,
+                                     _l.ptr(idx[lo:hi]), _l.ptr(val[lo:hi]), _l.ptr(ws), ws_bytes, _l.stream_ptr()),
+                 "pxr_din_topk_f32")
+    return idx, val
