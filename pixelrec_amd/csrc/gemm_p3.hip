@@ -280,14 +280,21 @@ struct P3DwProblem {
 struct P3DwGroup {
   P3DwProblem p[DW_MAX];
   int n, total_tiles;
-  unsigned* flags;         // KS == 2: one zero-initialised word per tile (left zeroed)
+  unsigned* flags;         // KS == 2: two zero-initialised words per tile, one per half (left zeroed)
   unsigned* status;
 };
 int pxr_stream_flags(hipStream_t st, unsigned** flags, int* n_flags);      // gemm_f32.hip
 // KS == 2 (split-K, ping-pong tiles only): two workgroups per tile, each reducing HALF of the tokens -- the launches whose tiles fill
-// half the chip or less (the sequence block's four matrices per layer: 128 tiles of 256x128) run on all of it.  The first half STORES
-// its tile and raises the tile's flag; the second half (the next logical index: dispatched later, normally on the same XCD) waits for
-// it, ADDS its own sum and lowers the flag -- a fixed order (deterministic bits), no zero-filled output, no atomics on the data.
+// half the chip or less (the sequence block's four matrices per layer: 128 tiles of 256x128) run on all of it.  The hand-over is
+// SYMMETRIC: workgroup `half` = h owns row block h of the tile (rows [m0 + h BM/2, m0 + (h + 1) BM/2)).  From the tile staged in
+// the LDS it (A) stores its partial of the PARTNER's block with coherent stores and raises flag word 2 t + h, waits for the
+// partner's word 2 t + (1 - h), then (B) loads the partner's partial of its OWN block, adds and stores the final values with
+// ordinary stores; it lowers the word it waited on once its loads are consumed.  Both halves move half a tile three times, side
+// by side (before: one workgroup stored the whole tile, the other one then loaded, added and stored all of it).  Every element is
+// `first-half partial + second-half partial`, whichever side adds: IEEE addition is commutative, so `own + loaded` gives the same
+// bits in either block -- a fixed order (deterministic, the bits of the earlier store-then-add hand-over), no zero-filled output,
+// no atomics on the data.  Each side publishes BEFORE it waits (no cycle); both must be resident at once (launch_dw_p3 checks).
+// The bias column sums (1 KB per tile) stay one-directional: the first half publishes them with its block, the second adds.
 template <class Cfg, bool EARLY, int KS = 1>
 __global__ void __launch_bounds__(Cfg::NT) grouped_dw_p3_kernel(const P3DwGroup g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -313,19 +320,6 @@ __global__ void __launch_bounds__(Cfg::NT) grouped_dw_p3_kernel(const P3DwGroup 
     const P3Mat dyh{P.dy.p + (int64_t)kb * 32, P.dy.ps, P.dy.pr}, xh{P.x.p + (int64_t)kb * 32, P.x.ps, P.x.pr};
     if (do_bias) gemm_p4_mainloop<Cfg, false, false, true>(accs, dyh, xh, kl, m0, n0, smem, ones_acc);
     else gemm_p4_mainloop<Cfg, false, false, false>(accs, dyh, xh, kl, m0, n0, smem);
-    if (half) {
-      if (threadIdx.x == 0) {
-        unsigned spins = 0;
-        while (__hip_atomic_load(&g.flags[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-          __builtin_amdgcn_s_sleep(4);
-          if (++spins > (1u << 22)) {        // ~seconds: never in a healthy launch; flag it instead of hanging the GPU
-            if (g.status) atomicOr(g.status, (unsigned)PXR_STATUS_GEMM_TIMEOUT);
-            break;
-          }
-        }
-      }
-      __syncthreads();                       // (the loads below bypass the caches: no acquire fence -- an agent-scope fence is a full
-    }                                        //  L2 write-back + invalidate per wave, ~100 us per launch at 256 workgroups: measured)
   } else if constexpr (Cfg::PINGPONG) {
     if (do_bias) gemm_p4_mainloop<Cfg, false, false, true>(accs, P.dy, P.x, kpad, m0, n0, smem, ones_acc);
     else gemm_p4_mainloop<Cfg, false, false, false>(accs, P.dy, P.x, kpad, m0, n0, smem);
@@ -351,22 +345,22 @@ __global__ void __launch_bounds__(Cfg::NT) grouped_dw_p3_kernel(const P3DwGroup 
   float* dW = P.dW;
   const int64_t ldw = P.K;
   const bool vec_ok = (P.K % 8 == 0);
-  // split-K hand-over: the first half's stores and the second half's loads of the partial tile go THROUGH the caches (sc1 | sc0:
-  // write-through / bypass, as the stream-K partials of gemm_f32.hip), so the pair needs no fence whichever XCDs it runs on
+  // split-K hand-over: the stores and the loads of the partial blocks go THROUGH the caches (sc1 | sc0: write-through / bypass, as
+  // the stream-K partials of gemm_f32.hip), so the pair needs no fence whichever XCDs it runs on
   constexpr int COH = (1 << 4) | 1;
-  const bool add = (KS == 2) && half;          // the second half of a split tile adds to what the first one stored
-  const bool publish = (KS == 2) && !half;
+  constexpr int PLAIN = 0, PUBLISH = 1, ADD = 2;       // store | coherent store of a partial | coherent load of the partner's + store
   const bufrsrc rsw = make_rsrc(dW, (int64_t)P.N * P.K * 4);
-  auto store = [&](int, int row, int col, int nv, float (&v)[8]) {
+  auto store = [&](auto mode, int row, int col, int nv, float (&v)[8]) {
+    constexpr int MODE = decltype(mode)::value;
     float* cp = dW + (int64_t)row * ldw + col;
     const unsigned off = (unsigned)(((int64_t)row * ldw + col) * 4);
     if (vec_ok && nv == 8) {
-      if (add) {
+      if constexpr (MODE == ADD) {
         const auto a = __builtin_amdgcn_raw_buffer_load_b128(rsw, off, 0, COH), b = __builtin_amdgcn_raw_buffer_load_b128(rsw, off + 16, 0, COH);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { v[e] += __uint_as_float(a[e]); v[4 + e] += __uint_as_float(b[e]); }
       }
-      if (publish) {
+      if constexpr (MODE == PUBLISH) {
         p3_u32x4 a, b;
 #pragma unroll
         for (int e = 0; e < 4; ++e) { a[e] = __float_as_uint(v[e]); b[e] = __float_as_uint(v[4 + e]); }
@@ -381,41 +375,70 @@ __global__ void __launch_bounds__(Cfg::NT) grouped_dw_p3_kernel(const P3DwGroup 
       for (int e = 0; e < 8; ++e)
         if (e < nv) {
           float o = v[e];
-          if (add) o += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsw, off + 4 * e, 0, COH));
-          if (publish) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), rsw, off + 4 * e, 0, COH);
+          if constexpr (MODE == ADD) o += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsw, off + 4 * e, 0, COH));
+          if constexpr (MODE == PUBLISH) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), rsw, off + 4 * e, 0, COH);
           else cp[e] = o;
         }
     }
   };
-  if constexpr (Cfg::PINGPONG) p4_row_epilogue<Cfg>(accs, smem, P.N, P.K, m0, n0, [](int, int, int, int) {}, store);
-  else p3_row_epilogue<Cfg>(accs, smem, P.N, P.K, m0, n0, store);
-  if (do_bias) {
+  // db[row] of the tile's rows (the wn == 0 waves hold the column sums): KS == 2 -- the first half publishes, the second adds
+  auto bias = [&](auto mode) {
+    constexpr int MODE = decltype(mode)::value;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave / Cfg::WGN, wn = wave % Cfg::WGN, h = lane >> 5, r = lane & 31;
-    if (wn == 0 && r == 0) {
+    if (wn != 0 || r != 0) return;
+    const bufrsrc rsb = make_rsrc(P.db, (int64_t)P.N * 4);
 #pragma unroll
-      for (int i = 0; i < Cfg::TM; ++i)
+    for (int i = 0; i < Cfg::TM; ++i)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int row = m0 + wm * Cfg::WM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-          if (row < P.N) {
-            float o = ones_acc[i][e];
-            if constexpr (KS == 2) {
-              const bufrsrc rsb = make_rsrc(P.db, (int64_t)P.N * 4);
-              if (add) o += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsb, (unsigned)row * 4u, 0, COH));
-              if (publish) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), rsb, (unsigned)row * 4u, 0, COH);
-              else P.db[row] = o;
-            } else {
-              P.db[row] = o;
-            }
-          }
+      for (int e = 0; e < 16; ++e) {
+        const int row = m0 + wm * Cfg::WM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        if (row < P.N) {
+          float o = ones_acc[i][e];
+          if constexpr (MODE == ADD) o += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsb, (unsigned)row * 4u, 0, COH));
+          if constexpr (MODE == PUBLISH) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), rsb, (unsigned)row * 4u, 0, COH);
+          else P.db[row] = o;
         }
-    }
-  }
+      }
+  };
+  using Plain = std::integral_constant<int, PLAIN>;
+  using Publish = std::integral_constant<int, PUBLISH>;
+  using Add = std::integral_constant<int, ADD>;
   if constexpr (KS == 2) {
-    __builtin_amdgcn_s_waitcnt(0);           // every lane's stores acknowledged at the coherence point (first half); loads consumed
+    constexpr int HIT = P4ChunkMap<Cfg>::CPT / 2;      // the row loop's iterations per row block
+    static_assert(P4ChunkMap<Cfg>::CPT % 2 == 0 && HIT * P4ChunkMap<Cfg>::RPI * 2 == Cfg::BM, "two row blocks of BM / 2 rows");
+    p4_stage_tile<Cfg>(accs, smem);                    // (the fp16 formats' scale is already in: staged ONCE, walked twice)
+    // A: my partial of the partner's row block
+    p4_walk_rows<Cfg, HIT>(smem, P.N, P.K, m0, n0, (1 - half) * HIT,
+                           [&](int row, int col, int nv, float (&v)[8]) { store(Publish{}, row, col, nv, v); });
+    if (do_bias && !half) bias(Publish{});
+    __builtin_amdgcn_s_waitcnt(0);           // every lane's stores acknowledged at the coherence point
     __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(&g.flags[t], half ? 0u : 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) {
+      __hip_atomic_store(&g.flags[2 * t + half], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      unsigned spins = 0;
+      while (__hip_atomic_load(&g.flags[2 * t + 1 - half], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
+        __builtin_amdgcn_s_sleep(4);
+        if (++spins > (1u << 22)) {          // ~seconds: never in a healthy launch; flag it instead of hanging the GPU
+          if (g.status) atomicOr(g.status, (unsigned)PXR_STATUS_GEMM_TIMEOUT);
+          break;
+        }
+      }
+    }
+    __syncthreads();                         // (the loads below bypass the caches: no acquire fence -- an agent-scope fence is a full
+                                             //  L2 write-back + invalidate per wave, ~100 us per launch at 256 workgroups: measured)
+    // B: my own row block = my partial + the partner's; nobody reads it again before the kernel boundary: ordinary stores
+    p4_walk_rows<Cfg, HIT>(smem, P.N, P.K, m0, n0, half * HIT,
+                           [&](int row, int col, int nv, float (&v)[8]) { store(Add{}, row, col, nv, v); });
+    if (do_bias && half) bias(Add{});
+    __builtin_amdgcn_s_waitcnt(0);           // the partner's partial is consumed: only now may its flag go down (the word I waited
+    __syncthreads();                         //  on; the next launch on this stream finds both words of the tile zero)
+    if (threadIdx.x == 0) __hip_atomic_store(&g.flags[2 * t + 1 - half], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    auto plain = [&](int, int row, int col, int nv, float (&v)[8]) { store(Plain{}, row, col, nv, v); };
+    if constexpr (Cfg::PINGPONG) p4_row_epilogue<Cfg>(accs, smem, P.N, P.K, m0, n0, [](int, int, int, int) {}, plain);
+    else p3_row_epilogue<Cfg>(accs, smem, P.N, P.K, m0, n0, plain);
+    if (do_bias) bias(Plain{});
   }
 }
 
@@ -437,8 +460,8 @@ static int launch_dw_p3(P3DwGroup& g, hipStream_t st) {
     int n_flags = 0;
     const int rc = pxr_stream_flags(st, &g.flags, &n_flags);
     if (rc != PXR_OK) return rc;
-    if (tiles > n_flags) {
-      pxr_set_error("pxr_grouped_dw_planes_f32: split-K launch with %d tiles (max %d)", tiles, n_flags);
+    if (2 * tiles > n_flags) {
+      pxr_set_error("pxr_grouped_dw_planes_f32: split-K launch with %d tiles (max %d)", tiles, n_flags / 2);
       return PXR_ERR_BAD_ARG;
     }
     g.status = (unsigned*)pxr_status_word();
@@ -827,7 +850,7 @@ extern "C" int pxr_grouped_dw_planes_f32(int n, const void* const* dy, const int
   int t_min = T[0];
   for (int i = 1; i < n; ++i) t_min = T[i] < t_min ? T[i] : t_min;
   if (tile_hint == 0) {
-    // (split-K: the second half of a tile SPINS on the first one's flag, so both halves of every tile must be resident at once:
+    // (split-K: the two halves of a tile SPIN on each other's flag, so both halves of every tile must be resident at once:
     // 2 x tiles workgroups of one per CU -- checked against the device's CU count, which CU masks / partition modes shrink)
     if (env_p4dw && env_splitk && t256 >= 96 && t256 <= 128 && t_min >= 2048 && 2 * t256 <= pxr_cu_count()) tile_hint = 425612822;
     else tile_hint = (env_p4dw && ((t256 >= 192 && t256 <= 256) || t256 >= 512)) ? 425612832 : (t128 >= 192 ? 412812831 : 406406431);

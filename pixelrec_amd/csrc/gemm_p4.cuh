@@ -581,4 +581,42 @@ __device__ __forceinline__ void p4_row_epilogue(const typename Cfg::Acc& accs, c
   }
 }
 
+// The same in two steps, for an epilogue that walks the staged tile more than once without staging it twice (the split-K
+// hand-over of grouped_dw_p3_kernel; tiles of ONE pass, BN == EPI_COLS): p4_stage_tile writes the accumulators to the LDS,
+// p4_walk_rows calls `fn(row, col, nv, v)` for the thread's chunks of NIT of the row loop's CPT iterations, from iteration it0 on
+// -- the tile's rows [it0 * RPI, (it0 + NIT) * RPI).  The tile stays intact in the LDS between the walks.
+template <class Cfg>
+__device__ __forceinline__ void p4_stage_tile(const typename Cfg::Acc& accs, char* smem) {
+  static_assert(Cfg::EPI_OK && P4ChunkMap<Cfg>::NP == 1, "one epilogue pass");
+  float* t = reinterpret_cast<float*>(smem);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wm = wave / Cfg::WGN, wn = wave % Cfg::WGN, h = lane >> 5, r = lane & 31;
+#pragma unroll
+  for (int j = 0; j < Cfg::TN; ++j)
+#pragma unroll
+    for (int i = 0; i < Cfg::TM; ++i)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = wm * Cfg::WM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        t[row * Cfg::EPI_LD + wn * Cfg::WN + j * 32 + r] = accs.v[i][j][e];
+      }
+  __syncthreads();
+}
+template <class Cfg, int NIT, class Fn>
+__device__ __forceinline__ void p4_walk_rows(const char* smem, int M, int N, int m0, int n0, int it0, Fn&& fn) {
+  using Map = P4ChunkMap<Cfg>;
+  static_assert(Map::NP == 1 && NIT <= Map::CPT, "one epilogue pass");
+  const float* t = reinterpret_cast<const float*>(smem);
+  const int c8 = (threadIdx.x % Map::CPR) * 8, col = n0 + c8;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int row = (it0 + it) * Map::RPI + threadIdx.x / Map::CPR;
+    if (m0 + row >= M || col >= N) continue;
+    const float4 a = *reinterpret_cast<const float4*>(t + row * Cfg::EPI_LD + c8);
+    const float4 b = *reinterpret_cast<const float4*>(t + row * Cfg::EPI_LD + c8 + 4);
+    float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    fn(m0 + row, col, min(8, N - col), v);
+  }
+}
+
 }  // namespace pxr
