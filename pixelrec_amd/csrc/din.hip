@@ -18,8 +18,10 @@
 // fp32-operand MFMA main loop of gemm_f32.cuh (items x h1), applies the sigmoid into an LDS tile, multiplies that tile with W2
 // (held in LDS) on the same MFMA, applies the second sigmoid, and 128 threads -- one per item -- finish with dense, 1 / sqrt(D)
 // and <k_l, q>, accumulating over l in a register.  Masks (item 0, the ragged edge, the user's full history as a bitmap) and a
-// per-thread top-K list follow; the lists are merged by wave shuffles and a small merge kernel.  No [B, L, N, *] value reaches memory.
+// per-thread top-K list follow; the lists are merged by wave shuffles and the shared merge kernel (topk_select.cuh: pxr_topk_merge).
+// No [B, L, N, *] value reaches memory.
 #include "gemm_f32.cuh"
+#include "topk_select.cuh"
 
 namespace pxr {
 
@@ -281,33 +283,6 @@ __global__ void __launch_bounds__(256) din_prep_kernel(DinTopkArgs a) {
   }
 }
 
-template <int KT>
-struct DnTopList {
-  float v[KT];
-  int i[KT];
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int k = 0; k < KT; ++k) { v[k] = -INFINITY; i[k] = -1; }
-  }
-  // sorted descending; v[KT-1] is the admission threshold
-  __device__ __forceinline__ void insert(float x, int id) {
-    if (!(x > v[KT - 1])) return;
-    v[KT - 1] = x; i[KT - 1] = id;
-#pragma unroll
-    for (int k = KT - 1; k > 0; --k) {
-      if (v[k] > v[k - 1]) {
-        const float tv = v[k]; v[k] = v[k - 1]; v[k - 1] = tv;
-        const int ti = i[k]; i[k] = i[k - 1]; i[k - 1] = ti;
-      }
-    }
-  }
-  __device__ __forceinline__ void pop() {
-#pragma unroll
-    for (int k = 0; k + 1 < KT; ++k) { v[k] = v[k + 1]; i[k] = i[k + 1]; }
-    v[KT - 1] = -INFINITY; i[KT - 1] = -1;
-  }
-};
-
 // KT = length of the top-K lists; TWO = two hidden layers (else one: dense reads the first layer's activations)
 template <int KT, bool TWO>
 __global__ void __launch_bounds__(GEMM_THREADS) din_topk_kernel(DinTopkArgs a) {
@@ -345,7 +320,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) din_topk_kernel(DinTopkArgs a) {
   if (a.hist_ptr) { hb = a.hist_ptr[b]; he = a.hist_ptr[b + 1]; }
   const int64_t* win = a.window + (int64_t)b * a.L;
 
-  DnTopList<KT> top;
+  TopList<KT> top;
   top.init();
 
   for (int tn = tn0; tn < tn1; ++tn) {
@@ -464,69 +439,17 @@ __global__ void __launch_bounds__(GEMM_THREADS) din_topk_kernel(DinTopkArgs a) {
     __syncthreads();
   }
   if (wave >= 2) return;                       // the lists live in the 128 item threads (wave-uniform)
-  // the wave's 64 lists -> one: KT rounds of (best head of the wave, lowest lane first), the winner pops
+  // the wave's 64 lists -> one list per (user, split, wave)
   const int64_t o = (((int64_t)b * a.n_split + sp) * 2 + wave) * KT;
-  for (int kk = 0; kk < KT; ++kk) {
-    float bv = top.v[0];
-    int blane = lane;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(bv, off, 64);
-      const int ol = __shfl_xor(blane, off, 64);
-      if (ov > bv || (ov == bv && ol < blane)) { bv = ov; blane = ol; }
-    }
-    if (lane == blane) {
-      a.part_val[o + kk] = top.v[0];
-      a.part_idx[o + kk] = top.i[0];
-      top.pop();
-    }
-  }
+  wave_collapse_lists(top, lane, a.part_val + o, a.part_idx + o);
 }
 
-// one wave per user: the K best of its n_cand partial candidates, descending, ties by candidate position
-__global__ void __launch_bounds__(256) din_merge_kernel(const int* __restrict__ bad, const float* __restrict__ part_val,
-                                                        const int* __restrict__ part_idx, int B, int n_cand, int K,
-                                                        int64_t* __restrict__ out_idx, float* __restrict__ out_val) {
-  if (*bad) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int u = blockIdx.x * 4 + wave;
-  if (u >= B) return;
-  const float* pv = part_val + (int64_t)u * n_cand;
-  const int* pi = part_idx + (int64_t)u * n_cand;
-  float last_v = INFINITY;
-  int last_pos = -1;
-  for (int k = 0; k < K; ++k) {
-    float bv = -INFINITY;
-    int bp = 0x7fffffff;
-    for (int c = lane; c < n_cand; c += 64) {
-      const float v = pv[c];
-      const bool remaining = (v < last_v) || (v == last_v && c > last_pos);
-      if (remaining && pi[c] >= 0 && (v > bv || (v == bv && c < bp))) { bv = v; bp = c; }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(bv, off, 64);
-      const int op = __shfl_xor(bp, off, 64);
-      if (ov > bv || (ov == bv && op < bp)) { bv = ov; bp = op; }
-    }
-    if (lane == 0) {
-      const bool ok = bp != 0x7fffffff;
-      out_val[(int64_t)u * K + k] = ok ? bv : -INFINITY;
-      out_idx[(int64_t)u * K + k] = ok ? (int64_t)pi[bp] : (int64_t)-1;
-    }
-    last_v = bv;
-    last_pos = bp;
-  }
-}
-
-static int dn_pick_kt(int K) { return K <= 10 ? 10 : (K <= 16 ? 16 : (K <= 32 ? 32 : 0)); }
 static int dn_pick_split(int B, int N) {
   const int tiles_n = (N + DN_BM - 1) / DN_BM;
   int s = (512 + B - 1) / B;                   // one resident workgroup per CU (its LDS): about two rounds of the chip
   if (s > tiles_n) s = tiles_n;
   return s < 1 ? 1 : s;
 }
-static int64_t dn_a256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 static bool dn_shape_ok(int B, int L, int N, int D, int h1, int h2, int K) {
   return B > 0 && B <= (1 << 20) && L >= 1 && L <= DN_MAX_L && N > 0 && D >= 4 && D % 4 == 0 && D <= DN_MAX_D && h1 >= 1 &&
          h1 <= DN_MAX_H && h2 >= 0 && h2 <= DN_MAX_H && K >= 1 && K <= 32 && (int64_t)N * D * 4 < 0x7FFFFFF0ll;
@@ -614,8 +537,8 @@ extern "C" int pxr_din_fold_w1_f32(const float* w1, int h1, int D, float* A, flo
 // input flag | Bm k | C * k | partial values | partial ids
 extern "C" int64_t pxr_din_topk_ws_bytes(int B, int L, int N, int D, int h1, int h2, int K) {
   if (!dn_shape_ok(B, L, N, D, h1, h2, K)) return -1;
-  const int64_t cand = (int64_t)dn_pick_split(B, N) * 2 * dn_pick_kt(K);
-  return 256 + dn_a256((int64_t)B * L * 128 * 4) + dn_a256((int64_t)B * L * h1 * D * 4) + 2 * dn_a256((int64_t)B * cand * 4);
+  const int64_t cand = (int64_t)dn_pick_split(B, N) * 2 * pick_kt(K);
+  return 256 + a256((int64_t)B * L * 128 * 4) + a256((int64_t)B * L * h1 * D * 4) + 2 * a256((int64_t)B * cand * 4);
 }
 
 extern "C" int pxr_din_topk_f32(const float* table, int N, int D, const int64_t* window, int B, int L, const float* aq,
@@ -629,7 +552,7 @@ extern "C" int pxr_din_topk_f32(const float* table, int N, int D, const int64_t*
   PXR_REQUIRE(dn_aligned(table) && dn_aligned(ws), "pxr_din_topk_f32: table and workspace must be 16-byte aligned");
   PXR_REQUIRE(!hist_ptr || hist_items, "pxr_din_topk_f32: hist_ptr without hist_items");
   if (pxr_din_topk_ws_bytes(B, L, N, D, h1, h2, K) > ws_bytes) { pxr_set_error("pxr_din_topk_f32: workspace too small"); return PXR_ERR_WORKSPACE; }
-  const int kt = dn_pick_kt(K);
+  const int kt = pick_kt(K);
   DinTopkArgs a{};
   a.table = table; a.window = window; a.hist_ptr = hist_ptr; a.hist_items = hist_items; a.aq = aq; a.bm = bm; a.cm = cm;
   a.w2 = w2; a.b2 = b2; a.wd = wd; a.bd = bd; a.B = B; a.L = L; a.N = N; a.D = D; a.h1 = h1; a.h2 = h2;
@@ -640,9 +563,9 @@ extern "C" int pxr_din_topk_f32(const float* table, int N, int D, const int64_t*
   const int64_t cand = (int64_t)a.n_split * 2 * kt;
   char* w = (char*)ws;
   a.bad = (int*)w;                     w += 256;
-  a.bk = (float*)w;                    w += dn_a256((int64_t)B * L * 128 * 4);
-  a.cs = (float*)w;                    w += dn_a256((int64_t)B * L * h1 * D * 4);
-  a.part_val = (float*)w;              w += dn_a256((int64_t)B * cand * 4);
+  a.bk = (float*)w;                    w += a256((int64_t)B * L * 128 * 4);
+  a.cs = (float*)w;                    w += a256((int64_t)B * L * h1 * D * 4);
+  a.part_val = (float*)w;              w += a256((int64_t)B * cand * 4);
   a.part_idx = (int*)w;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(a.bad, 0, 256, st) != hipSuccess) return pxr_check_launch("pxr_din_topk_f32(memset)");
@@ -661,7 +584,5 @@ extern "C" int pxr_din_topk_f32(const float* table, int N, int D, const int64_t*
 #undef PXR_DN
   rc = pxr_check_launch("pxr_din_topk_f32");
   if (rc) return rc;
-  hipLaunchKernelGGL(din_merge_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, (const int*)a.bad, (const float*)a.part_val,
-                     (const int*)a.part_idx, B, (int)cand, K, topk_idx, topk_val);
-  return pxr_check_launch("pxr_din_topk_f32(merge)");
+  return pxr_topk_merge(a.bad, a.part_val, a.part_idx, B, (int)cand, K, topk_idx, topk_val, "pxr_din_topk_f32(merge)", stream);
 }

@@ -14,6 +14,7 @@
 // list only when fewer than K unmasked items exist.
 #include "gemm_b3.cuh"
 #include "gemm_p4.cuh"
+#include "topk_select.cuh"
 
 #include <cstdlib>
 
@@ -25,28 +26,6 @@ constexpr int ST_BM = 128, ST_BN = 128;
 constexpr int ST_LD = ST_BN + 1;  // score-tile row stride in LDS: lane=row scans are conflict-free
 using StCfg = GemmCfg<ST_BM, ST_BN, true, true>;
 constexpr int ST_SMEM_FLOATS = (2 * StCfg::STAGE > ST_BM * ST_LD) ? 2 * StCfg::STAGE : ST_BM * ST_LD;
-
-template <int KT>
-struct TopList {
-  float v[KT];
-  int i[KT];
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int k = 0; k < KT; ++k) { v[k] = -INFINITY; i[k] = -1; }
-  }
-  // sorted descending; v[KT-1] is the admission threshold
-  __device__ __forceinline__ void insert(float x, int id) {
-    if (!(x > v[KT - 1])) return;
-    v[KT - 1] = x; i[KT - 1] = id;
-#pragma unroll
-    for (int k = KT - 1; k > 0; --k) {
-      if (v[k] > v[k - 1]) {
-        const float tv = v[k]; v[k] = v[k - 1]; v[k - 1] = tv;
-        const int ti = i[k]; i[k] = i[k - 1]; i[k - 1] = ti;
-      }
-    }
-  }
-};
 
 struct ScoreTopkArgs {
   const float* users; int64_t ld_users;   // [B, D] rows at stride ld_users
@@ -129,12 +108,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) score_topk_kernel(ScoreTopkArgs 
     for (int p = hb + tid; p < he; p += GEMM_THREADS) {
       const int64_t it = a.hist_items[p];
       if (it >= n0 && it < n0 + ST_BN) {
-        // owner row of pair p: the user u with hist_ptr[u] <= p < hist_ptr[u+1]; binary search inside the block
-        int lo = m0, hi = min(a.B, m0 + ST_BM) - 1;
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (a.hist_ptr[mid] <= p) lo = mid; else hi = mid - 1;
-        }
+        const int lo = hist_owner(a.hist_ptr, p, m0, min(a.B, m0 + ST_BM) - 1);
         smem[(lo - m0) * ST_LD + (int)(it - n0)] = -INFINITY;
       }
     }
@@ -201,18 +175,7 @@ __global__ void __launch_bounds__((FINE == 1 ? 1024 : 512), (FINE == 1 ? 4 : 4))
     gemm_mainloop<ST_BM, ST_BN, true, true, false, 1, (FINE == 1 ? 2 : 1), 2, FINE>(accs, a.table, (int64_t)a.D, a.users, a.ld_users, a.N, a.B,
                                                                0, a.D, i0, u0, smem);
     // (the main loop starts and ends with barriers: the zeroed bitmap is visible, the staging buffers are not touched here)
-    for (int p = hb + tid; p < he; p += ST2_THREADS) {
-      const int64_t it = a.hist_items[p];
-      if (it >= i0 && it < i0 + ST_BM) {
-        int lo = u0, hi = min(a.B, u0 + ST_BN) - 1;          // owner of pair p: hist_ptr[u] <= p < hist_ptr[u+1]
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (a.hist_ptr[mid] <= p) lo = mid; else hi = mid - 1;
-        }
-        const int il = (int)(it - i0);
-        atomicOr(&bitmap[(lo - u0) * (ST_BM / 32) + (il >> 5)], 1u << (il & 31));
-      }
-    }
+    hist_bitmap_from_pairs<ST_BM, ST_BN, ST2_THREADS>(bitmap, a.hist_ptr, a.hist_items, hb, he, u0, a.B, i0, tid);
     __syncthreads();
     const bool user_ok = (u0 + ul) < a.B;
 #pragma unroll
@@ -246,7 +209,6 @@ __global__ void __launch_bounds__((FINE == 1 ? 1024 : 512), (FINE == 1 ? 4 : 4))
 // few survivors (score >= tau, not masked: ~64 K per user) to a per-user candidate buffer with one atomic each;
 // (3) the merge kernel picks the K best candidates (ties: lower item id first, so the result does not depend on the
 // order of the appends).
-constexpr int ST4_HIST_CAP = 2048;   // history pairs of the workgroup's (128 users x its item range) kept in LDS
 
 // B3 = 1: the product runs on the bf16 matrix pipe through the exact 3 x bf16 split (gemm_b3.cuh; GEMM mode bf16x3): 96 KB
 // of staging LDS, one 16-wave workgroup per CU at 128 VGPRs instead of two at 64.
@@ -276,23 +238,10 @@ __global__ void __launch_bounds__(1024, (B3 ? 4 : 8)) score_thresh_kernel(ScoreT
   if (tid == 0) *hcount = 0;
   __syncthreads();
   const int64_t r_lo = (int64_t)tn0 * ST_BM, r_hi = (int64_t)tn1 * ST_BM;
-  for (int p = hb + tid; p < he; p += 1024) {
-    const int64_t it = a.hist_items[p];
-    if (it >= r_lo && it < r_hi) {
-      int lo = u0, hi = min(a.B, u0 + ST_BN) - 1;          // owner of pair p: hist_ptr[u] <= p < hist_ptr[u+1]
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.hist_ptr[mid] <= p) lo = mid; else hi = mid - 1;
-      }
-      const int pos = atomicAdd(hcount, 1);
-      if (pos < ST4_HIST_CAP) hlist[pos] = ((unsigned)(lo - u0) << 20) | (unsigned)(it - r_lo);
-    }
-  }
+  hist_list_collect<ST_BN, 1024>(hlist, hcount, a.hist_ptr, a.hist_items, hb, he, u0, a.B, r_lo, r_hi, tid);
   __syncthreads();
   const int n_hist = *hcount;
-  // (else: walk the global pairs per tile, as before.  The packed pair keeps 20 bits for the item offset inside the split's
-  // range: a wider range -- few splits over a huge catalogue -- would run into the user field)
-  const bool list_ok = n_hist <= ST4_HIST_CAP && (r_hi - r_lo) <= (1ll << 20);
+  const bool list_ok = hist_list_ok(n_hist, r_lo, r_hi);   // (else: walk the global pairs per tile)
   for (int tn = tn0; tn < tn1; ++tn) {
     const int i0 = tn * ST_BM;
     if (tid < ST2_BITMAP_WORDS) bitmap[tid] = 0u;
@@ -303,29 +252,7 @@ __global__ void __launch_bounds__(1024, (B3 ? 4 : 8)) score_thresh_kernel(ScoreT
     else
       gemm_mainloop<ST_BM, ST_BN, true, true, false, 1, 2, 2, 1>(accs, a.table, (int64_t)a.D, a.users, a.ld_users, a.N, a.B,
                                                                  0, a.D, i0, u0, smem);
-    if (list_ok) {
-      const unsigned off0 = (unsigned)(i0 - (int)r_lo);
-      for (int q = tid; q < n_hist; q += 1024) {
-        const unsigned e = hlist[q], off = e & 0xFFFFFu;
-        if (off >= off0 && off < off0 + ST_BM) {
-          const int il = (int)(off - off0);
-          atomicOr(&bitmap[(e >> 20) * (ST_BM / 32) + (il >> 5)], 1u << (il & 31));
-        }
-      }
-    } else {
-      for (int p = hb + tid; p < he; p += 1024) {
-        const int64_t it = a.hist_items[p];
-        if (it >= i0 && it < i0 + ST_BM) {
-          int lo = u0, hi = min(a.B, u0 + ST_BN) - 1;
-          while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (a.hist_ptr[mid] <= p) lo = mid; else hi = mid - 1;
-          }
-          const int il = (int)(it - i0);
-          atomicOr(&bitmap[(lo - u0) * (ST_BM / 32) + (il >> 5)], 1u << (il & 31));
-        }
-      }
-    }
+    hist_bitmap_fill<ST_BM, ST_BN, 1024>(bitmap, list_ok, hlist, n_hist, r_lo, a.hist_ptr, a.hist_items, hb, he, u0, a.B, i0, tid);
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6;
     const int wi = wave / Cfg::WGN, wu = wave % Cfg::WGN;
@@ -427,10 +354,14 @@ __global__ void __launch_bounds__(256) topk_cand_merge_kernel(float* __restrict_
   }
 }
 
-// one wave per user: pick the K best of its n_cand partial candidates, descending
-__global__ void __launch_bounds__(256) topk_merge_kernel(const float* __restrict__ part_val,
+// one wave per user: pick the K best of its n_cand partial candidates, descending, ties by ascending position.  The candidates
+// are register lists (TopList, or lists collapsed from them), so a candidate's value is -inf exactly when its id is -1
+// (topk_select.cuh): a user with fewer than K unmasked items ends in (-inf, -1) pairs, whichever of those slots is picked.
+// skip (may be null): a flag of the caller's input check -- set: return at once, the outputs untouched.
+__global__ void __launch_bounds__(256) topk_merge_kernel(const int* __restrict__ skip, const float* __restrict__ part_val,
                                                          const int* __restrict__ part_idx, int B, int n_cand, int K,
                                                          int64_t* __restrict__ out_idx, float* __restrict__ out_val) {
+  if (skip && *skip) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int u = blockIdx.x * 4 + wave;
   if (u >= B) return;
@@ -463,7 +394,6 @@ __global__ void __launch_bounds__(256) topk_merge_kernel(const float* __restrict
   }
 }
 
-static int pick_kt(int K) { return K <= 10 ? 10 : (K <= 16 ? 16 : (K <= 32 ? 32 : 0)); }
 // selection variant: 2 / 3 = in the accumulator registers (8 / 16 waves per workgroup), 1 = score tile through LDS
 // (0 / unset: variant 4 -- two passes around a per-user threshold -- on catalogues of >= 65 536 items, else variant 2)
 static int topk_variant() {
@@ -515,21 +445,10 @@ __global__ void __launch_bounds__(Sp3Cfg::NT) score_thresh_p3_kernel(ScoreTopkAr
   if (tid == 0) *hcount = 0;
   __syncthreads();
   const int64_t r_lo = (int64_t)tn0 * SP3_BM, r_hi = (int64_t)tn1 * SP3_BM;
-  for (int p = hb + tid; p < he; p += NT) {
-    const int64_t it = a.hist_items[p];
-    if (it >= r_lo && it < r_hi) {
-      int lo = u0, hi = min(a.B, u0 + SP3_BN) - 1;         // owner of pair p: hist_ptr[u] <= p < hist_ptr[u+1]
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.hist_ptr[mid] <= p) lo = mid; else hi = mid - 1;
-      }
-      const int pos = atomicAdd(hcount, 1);
-      if (pos < ST4_HIST_CAP) hlist[pos] = ((unsigned)(lo - u0) << 20) | (unsigned)(it - r_lo);
-    }
-  }
+  hist_list_collect<SP3_BN, NT>(hlist, hcount, a.hist_ptr, a.hist_items, hb, he, u0, a.B, r_lo, r_hi, tid);
   __syncthreads();
   const int n_hist = *hcount;
-  const bool list_ok = n_hist <= ST4_HIST_CAP && (r_hi - r_lo) <= (1ll << 20);
+  const bool list_ok = hist_list_ok(n_hist, r_lo, r_hi);
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave / Sp3Cfg::WGN, wn = wave % Sp3Cfg::WGN;
   const int h = lane >> 5, r = lane & 31;
@@ -545,29 +464,7 @@ __global__ void __launch_bounds__(Sp3Cfg::NT) score_thresh_p3_kernel(ScoreTopkAr
     const int i0 = (tn0 + tile) * SP3_BM;
     for (int w = tid; w < SP3_BITMAP_WORDS; w += NT) bitmap[w] = 0u;
     p3_lds_barrier();
-    if (list_ok) {
-      const unsigned off0 = (unsigned)(i0 - (int)r_lo);
-      for (int q = tid; q < n_hist; q += NT) {
-        const unsigned e = hlist[q], off = e & 0xFFFFFu;
-        if (off >= off0 && off < off0 + SP3_BM) {
-          const int il = (int)(off - off0);
-          atomicOr(&bitmap[(e >> 20) * (SP3_BM / 32) + (il >> 5)], 1u << (il & 31));
-        }
-      }
-    } else {
-      for (int p = hb + tid; p < he; p += NT) {
-        const int64_t it = a.hist_items[p];
-        if (it >= i0 && it < i0 + SP3_BM) {
-          int lo = u0, hi = min(a.B, u0 + SP3_BN) - 1;
-          while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (a.hist_ptr[mid] <= p) lo = mid; else hi = mid - 1;
-          }
-          const int il = (int)(it - i0);
-          atomicOr(&bitmap[(lo - u0) * (SP3_BM / 32) + (il >> 5)], 1u << (il & 31));
-        }
-      }
-    }
+    hist_bitmap_fill<SP3_BM, SP3_BN, NT>(bitmap, list_ok, hlist, n_hist, r_lo, a.hist_ptr, a.hist_items, hb, he, u0, a.B, i0, tid);
     p3_lds_barrier();
 #pragma unroll
     for (int j = 0; j < Sp3Cfg::TN; ++j) {
@@ -1065,7 +962,6 @@ static bool use_thresh(int N) {
   const int tiles_n = (N + ST_BN - 1) / ST_BN;
   return (env == 0 || env == 4) && tiles_n >= ST4_MIN_TILES;
 }
-static int64_t a256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 static int sample_splits(int N, int kt) { return (((N + ST_BN - 1) / ST_BN) + st4_stride(kt) - 1) / st4_stride(kt); }
 static int64_t lists_bytes(int B, int N, int kt, int lists) { return a256((int64_t)B * sample_splits(N, kt) * lists * kt * 4) * 2; }
 
@@ -1114,8 +1010,7 @@ static int score_topk_thresh(ScoreTopkArgs a, int K, int kt, int64_t* topk_idx, 
     default: hipLaunchKernelGGL(score_topk_kernel<32>, grid_s, dim3(GEMM_THREADS), 0, st, a); break;
   }
   const int64_t cand = (int64_t)a.n_split * 2 * kt;
-  hipLaunchKernelGGL(topk_merge_kernel, dim3((a.B + 3) / 4), dim3(256), 0, st, (const float*)a.part_val,
-                     (const int*)a.part_idx, a.B, (int)cand, K, s_idx, s_val);
+  if (int rc = pxr_topk_merge(nullptr, a.part_val, a.part_idx, a.B, (int)cand, K, s_idx, s_val, "pxr_score_topk_f32(sample merge)", st)) return rc;
   if (fast)      // tau lowered by the rigorous margin of the reduced-product pass (see score_thresh_fast_kernel)
     hipLaunchKernelGGL(topk_tau_fast_kernel, dim3((a.B + 3) / 4), dim3(256), 0, st, (const float*)s_val, a.B, K, a.users, a.ld_users, a.D,
                        table_norm_max, spf_margin(products, a.D), tau, delta, cnt);
@@ -1279,9 +1174,14 @@ extern "C" int pxr_score_topk_f32(const float* users, int64_t ld_users, int B, c
   }
   int rc = pxr_check_launch("pxr_score_topk_f32");
   if (rc) return rc;
-  hipLaunchKernelGGL(topk_merge_kernel, dim3((B + 3) / 4), dim3(256), 0, st, (const float*)a.part_val,
-                     (const int*)a.part_idx, B, (int)cand, K, topk_idx, topk_val);
-  return pxr_check_launch("pxr_score_topk_f32(merge)");
+  return pxr_topk_merge(nullptr, a.part_val, a.part_idx, B, (int)cand, K, topk_idx, topk_val, "pxr_score_topk_f32(merge)", stream);
+}
+
+int pxr_topk_merge(const int* skip, const float* part_val, const int* part_idx, int B, int n_cand, int K, int64_t* out_idx,
+                   float* out_val, const char* what, void* stream) {
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, skip, part_val, part_idx, B,
+                     n_cand, K, out_idx, out_val);
+  return pxr_check_launch(what);
 }
 
 // out[0] = max_i ||x[i, :]||_2 (x [rows, cols] fp32, row stride ldx, cols % 4 == 0): the table statistic behind the margin of the

@@ -10,12 +10,14 @@
 // through a row list, gemm_mainloop's A_GATHER), drops the tile into LDS and gives each of the 256 threads one (user, column) pair:
 // the thread scans the column's h valid rows, keeps the k largest in a register list (TK entries, fully unrolled), takes their mean,
 // applies the masks (column 0, the ragged edge, the user's full history as a bitmap in LDS) and inserts into its private top-K list.
-// The 64 lists of a wave are merged with wave shuffles into one list per (user, split, wave); a tiny kernel merges those.
+// The 64 lists of a wave are merged with wave shuffles into one list per (user, split, wave); the shared merge kernel
+// (topk_select.cuh: pxr_topk_merge) merges those.
 // S never reaches HBM; the workspace holds the row list, the window lengths and the partial lists.
 //
 // Bad input (a window or history id outside [0, N), a 0 inside the window's valid tail, an empty window) is found by the first
 // kernel, which sets PXR_STATUS_BAD_INDEX and a flag in the workspace: the later kernels return at once, the outputs are untouched.
 #include "gemm_f32.cuh"
+#include "topk_select.cuh"
 
 namespace pxr {
 
@@ -88,33 +90,6 @@ __global__ void __launch_bounds__(64) visrank_prep_kernel(VisrankArgs a) {
   }
 }
 
-template <int KT>
-struct VrTopList {
-  float v[KT];
-  int i[KT];
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int k = 0; k < KT; ++k) { v[k] = -INFINITY; i[k] = -1; }
-  }
-  // sorted descending; v[KT-1] is the admission threshold
-  __device__ __forceinline__ void insert(float x, int id) {
-    if (!(x > v[KT - 1])) return;
-    v[KT - 1] = x; i[KT - 1] = id;
-#pragma unroll
-    for (int k = KT - 1; k > 0; --k) {
-      if (v[k] > v[k - 1]) {
-        const float tv = v[k]; v[k] = v[k - 1]; v[k - 1] = tv;
-        const int ti = i[k]; i[k] = i[k - 1]; i[k - 1] = ti;
-      }
-    }
-  }
-  __device__ __forceinline__ void pop() {
-#pragma unroll
-    for (int k = 0; k + 1 < KT; ++k) { v[k] = v[k + 1]; i[k] = i[k + 1]; }
-    v[KT - 1] = -INFINITY; i[KT - 1] = -1;
-  }
-};
-
 // KT = length of the top-K lists; TK = length of the k-largest list of the history reduction (0: the mean over all h rows)
 // (K <= 16: two workgroups per CU, so that one's column scan runs under the other's MFMAs; the 64 list registers of KT = 32 do not fit)
 template <int KT, int TK>
@@ -133,7 +108,7 @@ __global__ void __launch_bounds__(GEMM_THREADS, (KT <= 16 ? 2 : 1)) visrank_topk
   const int user = u0 + my_u;
   const int h = user < a.B ? a.hlen[user] : 0;
   const int k = TK == 0 ? h : min(a.top_k, h);
-  VrTopList<KT> top;
+  TopList<KT> top;
   top.init();
 
   const int lane = tid & 63, wave = tid >> 6;
@@ -202,62 +177,11 @@ __global__ void __launch_bounds__(GEMM_THREADS, (KT <= 16 ? 2 : 1)) visrank_topk
     __syncthreads();
   }
   if (user >= a.B) return;                                  // wave-uniform
-  // the wave's 64 lists -> one: KT rounds of (best head of the wave, lowest lane first), the winner pops
+  // the wave's 64 lists -> one list per (user, split, wave)
   const int64_t o = ((int64_t)user * (a.n_split * 2) + (sp * 2 + (wave & 1))) * KT;
-  for (int kk = 0; kk < KT; ++kk) {
-    float bv = top.v[0];
-    int bl = lane;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(bv, off, 64);
-      const int ol = __shfl_xor(bl, off, 64);
-      if (ov > bv || (ov == bv && ol < bl)) { bv = ov; bl = ol; }
-    }
-    if (lane == bl) {
-      a.part_val[o + kk] = top.v[0];
-      a.part_idx[o + kk] = top.i[0];
-      top.pop();
-    }
-  }
+  wave_collapse_lists(top, lane, a.part_val + o, a.part_idx + o);
 }
 
-// one wave per user: the K best of its n_cand partial candidates, descending (score_topk.hip's merge, behind the input flag)
-__global__ void __launch_bounds__(256) visrank_merge_kernel(const int* __restrict__ bad, const float* __restrict__ part_val,
-                                                            const int* __restrict__ part_idx, int B, int n_cand, int K,
-                                                            int64_t* __restrict__ out_idx, float* __restrict__ out_val) {
-  if (*bad) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int u = blockIdx.x * 4 + wave;
-  if (u >= B) return;
-  const float* pv = part_val + (int64_t)u * n_cand;
-  const int* pi = part_idx + (int64_t)u * n_cand;
-  float last_v = INFINITY;
-  int last_pos = -1;
-  for (int k = 0; k < K; ++k) {
-    float bv = -INFINITY;
-    int bp = 0x7fffffff;
-    for (int c = lane; c < n_cand; c += 64) {
-      const float v = pv[c];
-      const bool remaining = (v < last_v) || (v == last_v && c > last_pos);
-      if (remaining && (v > bv || (v == bv && c < bp))) { bv = v; bp = c; }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(bv, off, 64);
-      const int op = __shfl_xor(bp, off, 64);
-      if (ov > bv || (ov == bv && op < bp)) { bv = ov; bp = op; }
-    }
-    if (lane == 0) {
-      const bool ok = bp != 0x7fffffff;
-      out_val[(int64_t)u * K + k] = ok ? bv : -INFINITY;
-      out_idx[(int64_t)u * K + k] = ok ? (int64_t)pi[bp] : (int64_t)-1;
-    }
-    last_v = bv;
-    last_pos = bp;
-  }
-}
-
-static int vr_pick_kt(int K) { return K <= 10 ? 10 : (K <= 16 ? 16 : (K <= 32 ? 32 : 0)); }
 static int vr_pick_split(int B, int N) {
   const int row_blocks = (B + VR_UPT - 1) / VR_UPT;
   const int tiles_n = (N + VR_BN - 1) / VR_BN;
@@ -265,7 +189,6 @@ static int vr_pick_split(int B, int N) {
   if (s > tiles_n) s = tiles_n;
   return s < 1 ? 1 : s;
 }
-static int64_t vr_a256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 static bool vr_shape_ok(int B, int H, int N, int K) {
   return B > 0 && B <= (1 << 22) && H >= 1 && H <= VR_ROWS && N > 0 && K >= 1 && K <= 32;
 }
@@ -287,8 +210,8 @@ extern "C" int pxr_visrank_unit_rows_f32(const float* feat, int64_t N, int F, fl
 extern "C" int64_t pxr_visrank_topk_ws_bytes(int B, int H, int N, int K) {
   if (!vr_shape_ok(B, H, N, K)) return -1;
   const int row_blocks = (B + VR_UPT - 1) / VR_UPT;
-  const int64_t cand = (int64_t)vr_pick_split(B, N) * 2 * vr_pick_kt(K);
-  return 256 + vr_a256((int64_t)B * 4) + vr_a256((int64_t)row_blocks * VR_BM * 4) + 2 * vr_a256((int64_t)B * cand * 4);
+  const int64_t cand = (int64_t)vr_pick_split(B, N) * 2 * pick_kt(K);
+  return 256 + a256((int64_t)B * 4) + a256((int64_t)row_blocks * VR_BM * 4) + 2 * a256((int64_t)B * cand * 4);
 }
 
 extern "C" int pxr_visrank_topk_f32(const float* unit, int N, int F, const int64_t* window, int B, int H, int top_k,
@@ -301,7 +224,7 @@ extern "C" int pxr_visrank_topk_f32(const float* unit, int N, int F, const int64
   PXR_REQUIRE(top_k >= 0 && top_k <= 16, "pxr_visrank_topk_f32: top_k must be in [0, 16] (0 = the mean over the window)");
   PXR_REQUIRE(!hist_ptr || hist_items, "pxr_visrank_topk_f32: hist_ptr without hist_items");
   if (pxr_visrank_topk_ws_bytes(B, H, N, K) > ws_bytes) { pxr_set_error("pxr_visrank_topk_f32: workspace too small"); return PXR_ERR_WORKSPACE; }
-  const int kt = vr_pick_kt(K);
+  const int kt = pick_kt(K);
   VisrankArgs a{};
   a.unit = unit; a.window = window; a.hist_ptr = hist_ptr; a.hist_items = hist_items;
   a.B = B; a.H = H; a.N = N; a.F = F; a.top_k = top_k;
@@ -312,9 +235,9 @@ extern "C" int pxr_visrank_topk_f32(const float* unit, int N, int F, const int64
   const int64_t cand = (int64_t)a.n_split * 2 * kt;
   char* w = (char*)ws;
   a.bad = (int*)w;                     w += 256;
-  a.hlen = (int*)w;                    w += vr_a256((int64_t)B * 4);
-  a.rows = (int*)w;                    w += vr_a256((int64_t)a.row_blocks * VR_BM * 4);
-  a.part_val = (float*)w;              w += vr_a256((int64_t)B * cand * 4);
+  a.hlen = (int*)w;                    w += a256((int64_t)B * 4);
+  a.rows = (int*)w;                    w += a256((int64_t)a.row_blocks * VR_BM * 4);
+  a.part_val = (float*)w;              w += a256((int64_t)B * cand * 4);
   a.part_idx = (int*)w;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(a.bad, 0, 256, st) != hipSuccess) return pxr_check_launch("pxr_visrank_topk_f32(memset)");
@@ -338,7 +261,5 @@ extern "C" int pxr_visrank_topk_f32(const float* unit, int N, int F, const int64
 #undef PXR_VR
   rc = pxr_check_launch("pxr_visrank_topk_f32");
   if (rc) return rc;
-  hipLaunchKernelGGL(visrank_merge_kernel, dim3((B + 3) / 4), dim3(256), 0, st, (const int*)a.bad, (const float*)a.part_val,
-                     (const int*)a.part_idx, B, (int)cand, K, topk_idx, topk_val);
-  return pxr_check_launch("pxr_visrank_topk_f32(merge)");
+  return pxr_topk_merge(a.bad, a.part_val, a.part_idx, B, (int)cand, K, topk_idx, topk_val, "pxr_visrank_topk_f32(merge)", stream);
 }
