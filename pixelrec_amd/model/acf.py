@@ -38,8 +38,7 @@ from .. import ops
 from ..lib import PxrError
 from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .basemodel import BaseModel
-from .mf import _Rows
+from .packed import LazyTableModel, TrainStep, _Rows
 
 
 class _FeatNet(nn.Module):
@@ -67,27 +66,14 @@ class _UserNet(nn.Module):
         self.w = nn.Linear(E, 1)
 
 
-class _Step(torch.autograd.Function):
-    """Bridges `loss.backward()` to the hand-written backward chain."""
-
-    @staticmethod
-    def forward(ctx, anchor, model, profile, tail):
-        ctx.model = model
-        return model._forward_train(profile, tail).view(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        ctx.model._backward_train(grad_out)
-        return None, None, None, None
-
-
 # flat-buffer key -> path of the Linear below the model, in the reference's parameter order
 _LINEARS = (("fd", "user_model.feats.dim_reductor"), ("fx", "user_model.feats.w_x"), ("fu", "user_model.feats.w_u"),
             ("fw", "user_model.feats.w"), ("wu", "user_model.w_u"), ("wp", "user_model.w_p"), ("wx", "user_model.w_x"),
             ("w", "user_model.w"))
 
 
-class ACF(BaseModel):
+class ACF(LazyTableModel):
+    flat_align = 4                     # the one-element biases of the two `w` Linears would shift what follows off 16 bytes
     input_type = InputType.SEQ
     EVAL_CHUNK_ROWS = 1 << 17          # rows (items x regions) per projection launch of compute_item_all
 
@@ -121,16 +107,6 @@ class ACF(BaseModel):
                 nn.init.kaiming_normal_(mod.weight.data, nonlinearity="relu")
                 if getattr(mod, "bias", None) is not None:
                     nn.init.zeros_(mod.bias.data)
-        self._table = self._flat = self._gflat = None
-        self._views = {}
-        self._bufs = {}
-        self._saved = None
-        self._step_counter = 0
-        self._drop_dev = None
-        self.grad_scale = 1.0
-        self.sparse_table_grad = None
-        self._sparse = None
-        self._table_hooks = None
         self.store_ifeatures = None
         self._x_cache = self._xt_cache = None
 
@@ -160,78 +136,11 @@ class ACF(BaseModel):
         I = self.item_num
         return {"item_model.weight": (1, 1 + I), "user_model.user_embedding.weight": (1 + I, 1 + I + self.user_num)}
 
-    def lazy_table(self):
-        self._ensure_packed()
-        return self._table
-
-    def _ensure_packed(self):
-        """(Re)build the [1 + I + U, E] table and the flat Linear buffer when the parameters moved (e.g. after .to(device))."""
-        it = self.item_model.weight
-        if self._table is not None and self._table.device == it.device and it.data_ptr() == self._table[1].data_ptr():
-            return
-        dev = it.device
-        if dev.type != "cuda":
-            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with .to('cuda') first")
-        I, U, E = self.item_num, self.user_num, self.embedding_size
-        table = torch.zeros(1 + I + U, E, dtype=torch.float32, device=dev)
-        ue = self.user_model.user_embedding.weight
-        table[1:1 + I].copy_(it.data)
-        table[1 + I:].copy_(ue.data)
-        it.data, ue.data = table[1:1 + I], table[1 + I:]
-        specs = self._flat_specs()
-        # every tensor starts on a 16-byte boundary (the one-element biases of the two `w` Linears would shift what follows)
-        total = sum((p.numel() + 3) // 4 * 4 for _, p in specs)
-        flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        gflat = torch.zeros(total, dtype=torch.float32, device=dev)
-        off, views = 0, {}
-        for name, p in specs:
-            n = p.numel()
-            flat[off:off + n].copy_(p.data.reshape(-1))
-            p.data = flat[off:off + n].view(p.shape)
-            p.grad = gflat[off:off + n].view(p.shape)
-            views[name] = (off, n, tuple(p.shape))
-            off += (n + 3) // 4 * 4
+    def _after_pack(self, dev):
         self.v_feat = self.v_feat.to(dev)
-        self._table, self._flat, self._gflat, self._views = table, flat, gflat, views
-        self._anchor = torch.zeros((), dtype=torch.float32, device=dev, requires_grad=True)
-        self._drop_dev = torch.full((1,), self._step_counter, dtype=torch.int64, device=dev)     # (no dropout: the step counter only)
-        self._bufs = {}
         self._x_cache = self._xt_cache = None
 
-    def flat_parameters(self):
-        self._ensure_packed()
-        return self._flat, self._gflat
-
-    def _p(self, name, grad=False):
-        off, n, shape = self._views[name]
-        return (self._gflat if grad else self._flat)[off:off + n].view(shape)
-
-    def _buf(self, name, shape, dtype=torch.float32):
-        """Persistent work buffers (stable addresses: a captured step replays on them)."""
-        b = self._bufs.get(name)
-        if b is None or tuple(b.shape) != tuple(shape) or b.dtype != dtype:
-            b = self._bufs[name] = torch.empty(*shape, dtype=dtype, device=self._table.device)
-        return b
-
-    # ------------------------------------------------------------------------------------------ the table (lazy optimizer hooks)
-    def register_table_hooks(self, opt):
-        """Attach a lazy table optimizer: it is asked to bring rows up to date before they are read."""
-        self._table_hooks = opt
-
-    def join_prefetch(self):
-        return None
-
-    def sync_table(self):
-        """Make every table row current (no-op without a lazy optimizer)."""
-        if self._table_hooks is not None:
-            self._table_hooks.flush()
-
-    def state_dict(self, *args, **kwargs):
-        self.sync_table()
-        return super().state_dict(*args, **kwargs)
-
     def load_state_dict(self, state_dict, strict=True, **kwargs):
-        self.sync_table()
         self._x_cache = self._xt_cache = None
         return super().load_state_dict(state_dict, strict=strict, **kwargs)
 
@@ -258,7 +167,7 @@ class ACF(BaseModel):
             raise PxrError("ACF.forward is the training loss (acf.py forward); use compute_item_all / predict to score")
         self._ensure_packed()
         profile, tail = self._split_input(input, 3)
-        return _Step.apply(self._anchor, self, profile, tail)
+        return TrainStep.apply(self._anchor, self, profile, tail)
 
     def _features(self, profile):
         """profile [B, P] -> (g [R H, F] gathered regions, x = relu(dim_reductor(g)), x~ = feats.w_x(x))."""
@@ -296,12 +205,6 @@ class ACF(BaseModel):
         s.update(B=B, P=P, profile=profile, gidx=gidx, g=g, x=x, xt=xt, ie=ie, coef=coef)
         self._saved = s
         return loss
-
-    def _sparse_rows(self, n):
-        sp = self._sparse
-        if sp is None or sp.cap != n or sp.rows.device != self._table.device:
-            sp = self._sparse = ops.SparseRows(n, self.embedding_size, self._table.device)
-        return sp
 
     def _backward_train(self, grad_out):
         s = self._saved

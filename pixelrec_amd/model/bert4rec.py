@@ -22,7 +22,8 @@ from __future__ import annotations
 import torch
 
 from .. import ops
-from .sasrec import SASRec, _TrainStep
+from .packed import TrainStep
+from .sasrec import SASRec
 
 
 class _WithPositions:
@@ -82,7 +83,7 @@ class BERT4Rec(SASRec):
         items = items.contiguous()
         masked_index = masked_index.contiguous()
         if torch.is_grad_enabled() and self.training:
-            return _TrainStep.apply(self._anchor, self, items, masked_index)
+            return TrainStep.apply(self._anchor, self, items, masked_index)
         was = self.training
         try:
             self.training = False

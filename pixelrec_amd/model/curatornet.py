@@ -45,28 +45,15 @@ from .. import ops
 from ..lib import PxrError
 from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .basemodel import BaseModel
-
-
-class _Step(torch.autograd.Function):
-    """Bridges `loss.backward()` to the hand-written backward chain."""
-
-    @staticmethod
-    def forward(ctx, anchor, model, profile, target):
-        ctx.model = model
-        return model._forward_train(profile, target).view(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        ctx.model._backward_train(grad_out)
-        return None, None, None, None
+from .packed import PackedModel, TrainStep
 
 
 # flat-buffer key -> the Linear's attribute, in the reference's parameter order (curatornet.py:29-37)
 _LINEARS = (("c1", "selu_common1"), ("c2", "selu_common2"), ("p1", "selu_pu1"), ("p2", "selu_pu2"), ("p3", "selu_pu3"))
 
 
-class CuratorNet(BaseModel):
+class CuratorNet(PackedModel):
+    flat_align = 4                     # every tensor starts on a 16-byte boundary
     input_type = InputType.SEQ
     EVAL_CHUNK_ROWS = 1 << 15          # catalogue rows per launch of compute_item_all (its derivative buffers are this wide)
 
@@ -105,13 +92,6 @@ class CuratorNet(BaseModel):
         self.selu_pu3 = nn.Linear(Hd, E)
         for _, attr in _LINEARS:                           # reset_parameters (curatornet.py:43-54): the biases keep nn.Linear's init
             nn.init.xavier_uniform_(getattr(self, attr).weight)
-        self._flat = self._gflat = None
-        self._views = {}
-        self._bufs = {}
-        self._saved = None
-        self._step_counter = 0
-        self._drop_dev = None
-        self.grad_scale = 1.0
         self.store_ifeatures = None
 
     # ------------------------------------------------------------------------------------------ packing
@@ -133,46 +113,8 @@ class CuratorNet(BaseModel):
             out[attr + ".bias"] = key + ".b"
         return out
 
-    def _ensure_packed(self):
-        """(Re)build the flat Linear buffer when the parameters moved (e.g. after .to(device))."""
-        w = self.selu_common1.weight
-        if self._flat is not None and self._flat.device == w.device and w.data_ptr() == self._flat.data_ptr():
-            return
-        dev = w.device
-        if dev.type != "cuda":
-            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with .to('cuda') first")
-        specs = self._flat_specs()
-        total = sum((p.numel() + 3) // 4 * 4 for _, p in specs)      # every tensor starts on a 16-byte boundary
-        flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        gflat = torch.zeros(total, dtype=torch.float32, device=dev)
-        off, views = 0, {}
-        for name, p in specs:
-            n = p.numel()
-            flat[off:off + n].copy_(p.data.reshape(-1))
-            p.data = flat[off:off + n].view(p.shape)
-            p.grad = gflat[off:off + n].view(p.shape)
-            views[name] = (off, n, tuple(p.shape))
-            off += (n + 3) // 4 * 4
-        self._flat, self._gflat, self._views = flat, gflat, views
-        self._anchor = torch.zeros((), dtype=torch.float32, device=dev, requires_grad=True)
-        self._drop_dev = torch.full((1,), self._step_counter, dtype=torch.int64, device=dev)     # (no dropout: the step counter only)
-        self._bufs = {}
+    def _after_pack(self, dev):
         self.store_ifeatures = None
-
-    def flat_parameters(self):
-        self._ensure_packed()
-        return self._flat, self._gflat
-
-    def _p(self, name, grad=False):
-        off, n, shape = self._views[name]
-        return (self._gflat if grad else self._flat)[off:off + n].view(shape)
-
-    def _buf(self, name, shape, dtype=torch.float32):
-        """Persistent work buffers (stable addresses: a captured step replays on them)."""
-        b = self._bufs.get(name)
-        if b is None or tuple(b.shape) != tuple(shape) or b.dtype != dtype:
-            b = self._bufs[name] = torch.empty(*shape, dtype=dtype, device=self._flat.device)
-        return b
 
     def load_state_dict(self, state_dict, strict=True, **kwargs):
         self.store_ifeatures = None
@@ -201,7 +143,7 @@ class CuratorNet(BaseModel):
             raise PxrError("CuratorNet.forward is the training loss (curatornet.py forward); use compute_item_all / predict to score")
         self._ensure_packed()
         profile, target = self._split_input(input)
-        return _Step.apply(self._anchor, self, profile, target)
+        return TrainStep.apply(self._anchor, self, profile, target)
 
     def _profile_tower(self, cat):
         """[B, 2E] pooled profile -> the three SELU Linears; returns the activations and their derivatives."""

@@ -40,8 +40,7 @@ from .. import ops
 from ..lib import PxrError
 from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .basemodel import BaseModel
-from .mf import _Rows
+from .packed import LazyTableModel, TrainStep, _Rows
 
 
 class _AttMLP(nn.Module):
@@ -65,21 +64,8 @@ class _Attention(nn.Module):
         self.dense = nn.Linear(sizes[-1], 1)
 
 
-class _Step(torch.autograd.Function):
-    """Bridges `loss.backward()` to the hand-written backward chain."""
-
-    @staticmethod
-    def forward(ctx, anchor, model, profile, target):
-        ctx.model = model
-        return model._forward_train(profile, target).view(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        ctx.model._backward_train(grad_out)
-        return None, None, None, None
-
-
-class DIN(BaseModel):
+class DIN(LazyTableModel):
+    flat_align = 4                     # the one-element bias of `dense` would shift what follows off 16 bytes
     input_type = InputType.SEQ
     PREDICT_CHUNK_ROWS = 1 << 16       # (candidate, window row) pairs per chunk of the GEMM-path predict
 
@@ -109,16 +95,6 @@ class DIN(BaseModel):
                 nn.init.xavier_normal_(mod.weight.data)
                 if getattr(mod, "bias", None) is not None:
                     nn.init.zeros_(mod.bias.data)
-        self._table = self._flat = self._gflat = None
-        self._views = {}
-        self._bufs = {}
-        self._saved = None
-        self._step_counter = 0
-        self._drop_dev = None
-        self.grad_scale = 1.0
-        self.sparse_table_grad = None
-        self._sparse = None
-        self._table_hooks = None
         self._eval_cache = None
 
     # ------------------------------------------------------------------------------------------ packing
@@ -151,75 +127,10 @@ class DIN(BaseModel):
         """Rows of the table buffer the table parameter occupies (optim.table_spans)."""
         return {"item_embedding.weight": (1, 1 + self.item_num)}
 
-    def lazy_table(self):
-        self._ensure_packed()
-        return self._table
-
-    def _ensure_packed(self):
-        """(Re)build the [1 + I, D] table and the flat Linear buffer when the parameters moved (e.g. after .to(device))."""
-        it = self.item_embedding.weight
-        if self._table is not None and self._table.device == it.device and it.data_ptr() == self._table[1].data_ptr():
-            return
-        dev = it.device
-        if dev.type != "cuda":
-            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with .to('cuda') first")
-        I, D = self.item_num, self.embedding_size
-        table = torch.zeros(1 + I, D, dtype=torch.float32, device=dev)
-        table[1:].copy_(it.data)
-        it.data = table[1:]
-        specs = self._flat_specs()
-        # every tensor starts on a 16-byte boundary (the one-element bias of `dense` would shift what follows)
-        total = sum((p.numel() + 3) // 4 * 4 for _, p in specs)
-        flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        gflat = torch.zeros(total, dtype=torch.float32, device=dev)
-        off, views = 0, {}
-        for name, p in specs:
-            n = p.numel()
-            flat[off:off + n].copy_(p.data.reshape(-1))
-            p.data = flat[off:off + n].view(p.shape)
-            p.grad = gflat[off:off + n].view(p.shape)
-            views[name] = (off, n, tuple(p.shape))
-            off += (n + 3) // 4 * 4
-        self._table, self._flat, self._gflat, self._views = table, flat, gflat, views
-        self._anchor = torch.zeros((), dtype=torch.float32, device=dev, requires_grad=True)
-        self._drop_dev = torch.full((1,), self._step_counter, dtype=torch.int64, device=dev)     # (no dropout: the step counter only)
-        self._bufs = {}
+    def _after_pack(self, dev):
         self._eval_cache = None
 
-    def flat_parameters(self):
-        self._ensure_packed()
-        return self._flat, self._gflat
-
-    def _p(self, name, grad=False):
-        off, n, shape = self._views[name]
-        return (self._gflat if grad else self._flat)[off:off + n].view(shape)
-
-    def _buf(self, name, shape, dtype=torch.float32):
-        """Persistent work buffers (stable addresses: a captured step replays on them)."""
-        b = self._bufs.get(name)
-        if b is None or tuple(b.shape) != tuple(shape) or b.dtype != dtype:
-            b = self._bufs[name] = torch.empty(*shape, dtype=dtype, device=self._table.device)
-        return b
-
-    # ------------------------------------------------------------------------------------------ the table (lazy optimizer hooks)
-    def register_table_hooks(self, opt):
-        """Attach a lazy table optimizer: it is asked to bring rows up to date before they are read."""
-        self._table_hooks = opt
-
-    def join_prefetch(self):
-        return None
-
-    def sync_table(self):
-        """Make every table row current (no-op without a lazy optimizer)."""
-        if self._table_hooks is not None:
-            self._table_hooks.flush()
-
-    def state_dict(self, *args, **kwargs):
-        self.sync_table()
-        return super().state_dict(*args, **kwargs)
-
     def load_state_dict(self, state_dict, strict=True, **kwargs):
-        self.sync_table()
         self._eval_cache = None
         return super().load_state_dict(state_dict, strict=strict, **kwargs)
 
@@ -246,7 +157,7 @@ class DIN(BaseModel):
             raise PxrError("DIN.forward is the training loss (din.py forward); use fused_topk_batch / predict to score")
         self._ensure_packed()
         profile, target = self._split_input(input)
-        return _Step.apply(self._anchor, self, profile, target)
+        return TrainStep.apply(self._anchor, self, profile, target)
 
     def _mlp(self, x):
         """x [M, 4 D] -> lists of the hidden layers' activations and derivatives (library GEMMs, sigmoid epilogue)."""
@@ -271,12 +182,6 @@ class DIN(BaseModel):
                                              head=self._buf("head", (2 + 3 * B,)))
         self._saved = dict(B=B, L=L, profile=profile, gidx=gidx, emb=emb, x=x, acts=acts, ders=ders, s=s, kq=kq, head=head)
         return loss
-
-    def _sparse_rows(self, n):
-        sp = self._sparse
-        if sp is None or sp.cap != n or sp.rows.device != self._table.device:
-            sp = self._sparse = ops.SparseRows(n, self.embedding_size, self._table.device)
-        return sp
 
     def _backward_train(self, grad_out):
         s = self._saved

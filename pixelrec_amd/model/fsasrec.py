@@ -28,6 +28,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..utils.enum_type import InputType
+from .packed import TrainStep
 from .seqcore import SeqRecCore
 
 
@@ -112,23 +113,6 @@ def load_weights(config):
         return FIXItemEncoder(weight_path=config["v_feat_path"], device=device, output_dim=output_dim, dnn_layers=dnn_layers)
     raise ValueError("FSASRec needs one of semantic_model / hybrid_model / freeze_model (load.py:167-188 returns nothing "
                      "otherwise and the reference then fails on its first forward)")
-
-
-class _FeatStep(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, anchor, model, ids, idx, masked_index):
-        table, saved = model._encode_items(ids, keep=True)
-        ctx.model, ctx.table, ctx.saved = model, table, saved
-        return model._forward_core(table, idx, masked_index, train=True).view(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        m = ctx.model
-        dx0, coef, s = m._backward_core(grad_out, ctx.table)
-        d_emb = ops.mosasrec_emb_grad(dx0, s["out"], coef)            # [B, L+1, 2, D] = the order the ids were encoded in
-        m._encode_items_bwd(d_emb.view(-1, d_emb.shape[-1]), ctx.saved)
-        ctx.saved = ctx.table = None
-        return None, None, None, None, None
 
 
 class FSASRec(SeqRecCore):
@@ -254,9 +238,20 @@ class FSASRec(SeqRecCore):
         idx = self._row_ids(B, items.device)
         masked_index = masked_index.contiguous()
         if torch.is_grad_enabled() and self.training:
-            return _FeatStep.apply(self._anchor, self, ids, idx, masked_index)
+            return TrainStep.apply(self._anchor, self, ids, idx, masked_index)
         table, _ = self._encode_items(ids, keep=False)
         return self._forward_core(table, idx, masked_index, train=False).view(())
+
+    def _forward_train(self, ids, idx, masked_index):
+        table, saved = self._encode_items(ids, keep=True)
+        self._enc_saved = (table, saved)
+        return self._forward_core(table, idx, masked_index, train=True)
+
+    def _backward_train(self, grad_out):
+        (table, saved), self._enc_saved = self._enc_saved, None
+        dx0, coef, s = self._backward_core(grad_out, table)
+        d_emb = ops.mosasrec_emb_grad(dx0, s["out"], coef)            # [B, L+1, 2, D] = the order the ids were encoded in
+        self._encode_items_bwd(d_emb.view(-1, d_emb.shape[-1]), saved)
 
     @torch.no_grad()
     def encode_last(self, item_seq, item_feature):

@@ -25,32 +25,10 @@ from .. import ops
 from ..lib import PxrError
 from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .basemodel import BaseModel
+from .packed import PackedModel, TrainStep, _Rows
 
 
-class _Rows(nn.Module):
-    """Parameter container with nn.Embedding's `weight` name (state_dict keys of the reference); never called."""
-
-    def __init__(self, n, d):
-        super().__init__()
-        self.weight = nn.Parameter(torch.empty(n, d))
-
-
-class _PairStep(torch.autograd.Function):
-    """Bridges `loss.backward()` to the hand-written backward chain."""
-
-    @staticmethod
-    def forward(ctx, anchor, model, user, item):
-        ctx.model = model
-        return model._forward_train(user, item).view(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        ctx.model._backward_train(grad_out)
-        return None, None, None, None
-
-
-class LightGCN(BaseModel):
+class LightGCN(PackedModel):
     input_type = InputType.PAIR
 
     def __init__(self, config, dataload):
@@ -70,13 +48,7 @@ class LightGCN(BaseModel):
         self.item_embedding = _Rows(self.item_num, self.latent_dim)
         nn.init.xavier_normal_(self.user_embedding.weight)
         nn.init.xavier_normal_(self.item_embedding.weight)
-        self._flat = self._gflat = self._graph = None
-        self._views = {}
-        self._bufs = {}
-        self._saved = None
-        self._step_counter = 0
-        self._drop_dev = None                              # (no dropout: kept for the step-graph bookkeeping of graph.py)
-        self.grad_scale = 1.0
+        self._graph = None
         self.store_ufeatures = self.store_ifeatures = None
 
     # ------------------------------------------------------------------------------------------ flat packing
@@ -84,43 +56,20 @@ class LightGCN(BaseModel):
         """{reference parameter name: flat-buffer key} in the reference's registration order (optim.native_to_torch_state)."""
         return {"user_embedding.weight": "user", "item_embedding.weight": "item"}
 
-    def _ensure_packed(self):
-        """(Re)build the [U + I, D] buffer (and its gradient twin) when the parameters moved (e.g. after .to(device))."""
-        u, i = self.user_embedding.weight, self.item_embedding.weight
-        if self._flat is not None and self._flat.device == u.device and u.data_ptr() == self._flat.data_ptr():
-            return
-        dev = u.device
-        if dev.type != "cuda":
-            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with .to('cuda') first")
-        nu, ni, D = self.user_num * self.latent_dim, self.item_num * self.latent_dim, self.latent_dim
-        flat = torch.empty(nu + ni, dtype=torch.float32, device=dev)
-        gflat = torch.zeros(nu + ni, dtype=torch.float32, device=dev)
-        flat[:nu].copy_(u.data.reshape(-1))
-        flat[nu:].copy_(i.data.reshape(-1))
-        u.data, i.data = flat[:nu].view(self.user_num, D), flat[nu:].view(self.item_num, D)
-        u.grad, i.grad = gflat[:nu].view(self.user_num, D), gflat[nu:].view(self.item_num, D)
-        self._flat, self._gflat = flat, gflat
-        self._views = {"user": (0, nu, (self.user_num, D)), "item": (nu, ni, (self.item_num, D))}
-        self._anchor = torch.zeros((), dtype=torch.float32, device=dev, requires_grad=True)
-        self._drop_dev = torch.full((1,), self._step_counter, dtype=torch.int64, device=dev)
+    def _flat_specs(self):
+        """Flat layout: users, then items -- the buffer IS the propagation's E_0 [U + I, D]."""
+        return [("user", self.user_embedding.weight), ("item", self.item_embedding.weight)]
+
+    def _after_pack(self, dev):
         if self._graph is None or self._graph.device != dev:
             self._graph = ops.LgcnGraph(*self._csr, device=dev)
-        self._bufs = {}
-
-    def flat_parameters(self):
-        self._ensure_packed()
-        return self._flat, self._gflat
 
     def _table(self, flat):
         return flat.view(self.user_num + self.item_num, self.latent_dim)
 
-    def _buf(self, name):
-        """Persistent [U + I, D] work buffers (stable addresses: a captured step replays on them)."""
-        b = self._bufs.get(name)
-        if b is None:
-            b = self._bufs[name] = torch.empty(self.user_num + self.item_num, self.latent_dim, dtype=torch.float32,
-                                               device=self._flat.device)
-        return b
+    def _work(self, name):
+        """Persistent [U + I, D] work buffers."""
+        return self._buf(name, (self.user_num + self.item_num, self.latent_dim))
 
     # ------------------------------------------------------------------------------------------ propagation
     def propagate(self, e0, out):
@@ -129,7 +78,7 @@ class LightGCN(BaseModel):
         x = e0
         for k in range(1, K + 1):
             last = k == K
-            y = None if last else self._buf("t%d" % (k % 2))
+            y = None if last else self._work("t%d" % (k % 2))
             g.spmm(x, y=y, acc_in=e0 if k == 1 else out, acc_out=out, scale=1.0 / (K + 1) if last else 1.0)
             x = y
         return out
@@ -140,7 +89,7 @@ class LightGCN(BaseModel):
         h = gfin
         for k in range(1, K + 1):
             last = k == K
-            dst = out if last else self._buf("h%d" % (k % 2))
+            dst = out if last else self._work("h%d" % (k % 2))
             g.spmm(h, acc_in=gfin, acc_out=dst, scale=1.0 / (K + 1) if last else 1.0)
             h = dst
         return out
@@ -158,10 +107,10 @@ class LightGCN(BaseModel):
         if not self.training:
             raise PxrError("LightGCN.forward is the training loss (lightgcn.py:70-78); use compute_item_all / predict to score")
         self._ensure_packed()
-        return _PairStep.apply(self._anchor, self, user.contiguous(), item.contiguous())
+        return TrainStep.apply(self._anchor, self, user.contiguous(), item.contiguous())
 
     def _forward_train(self, user, item):
-        ef = self._buf("ef")
+        ef = self._work("ef")
         self.propagate(self._table(self._flat), ef)
         loss, diff, coef, nodes = ops.lgcn_pair_fwd(ef, self.user_num, self.item_num, user, item)
         self._saved = (ef, coef, nodes)
@@ -172,7 +121,7 @@ class LightGCN(BaseModel):
             raise PxrError("backward() without a training-mode forward()")
         ef, coef, nodes = self._saved
         gsd = grad_out.reshape(1).to(torch.float32).contiguous()
-        gfin = ops.lgcn_pair_bwd(ef, nodes, coef, self._buf("gf"), self.grad_scale, gsd)
+        gfin = ops.lgcn_pair_bwd(ef, nodes, coef, self._work("gf"), self.grad_scale, gsd)
         self.propagate_grad(gfin, self._table(self._gflat))
         self._saved = None
         ops.counter_add(self._drop_dev, 1)

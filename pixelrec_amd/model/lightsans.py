@@ -31,6 +31,7 @@ from .. import ops
 from ..lib import PxrError
 from ..parallel import world_info
 from ..utils.enum_type import InputType
+from .packed import TrainStep
 from .sasrec import SASRec
 from .seqcore import SeqRecCore, _FeedForwardParams
 
@@ -339,10 +340,8 @@ class LightSANs(LightSANsBlock, SASRec):
         return self._forward_dispatch(items, self._last_position_mask(items.shape[0], items.device))
 
     def _forward_dispatch(self, items, masked_index):
-        from .sasrec import _TrainStep
-
         if torch.is_grad_enabled() and self.training:
-            return _TrainStep.apply(self._anchor, self, items, masked_index)
+            return TrainStep.apply(self._anchor, self, items, masked_index)
         was = self.training
         try:
             self.training = False

@@ -32,15 +32,7 @@ from .. import ops
 from ..lib import PxrError
 from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .basemodel import BaseModel
-
-
-class _Rows(nn.Module):
-    """Parameter container with nn.Embedding's `weight` name (state_dict keys of the reference); never called."""
-
-    def __init__(self, n, d):
-        super().__init__()
-        self.weight = nn.Parameter(torch.empty(n, d))
+from .packed import LazyTableModel, TrainStep, _Rows
 
 
 class _MLP(nn.Module):
@@ -60,21 +52,7 @@ class _MLP(nn.Module):
         return [(m[4 * k + 1], m[4 * k + 2]) for k in range(len(m) // 4)]
 
 
-class _PairStep(torch.autograd.Function):
-    """Bridges `loss.backward()` to the hand-written backward chain."""
-
-    @staticmethod
-    def forward(ctx, anchor, model, user, item):
-        ctx.model = model
-        return model._forward_train(user, item).view(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        ctx.model._backward_train(grad_out)
-        return None, None, None, None
-
-
-class MF(BaseModel):
+class MF(LazyTableModel):
     input_type = InputType.PAIR
 
     def __init__(self, config, dataload):
@@ -105,16 +83,6 @@ class MF(BaseModel):
         nn.init.xavier_normal_(self.item_embedding.weight)
         s = config["seed"] if "seed" in config else None
         self._drop_seed = int(s) if s is not None else 2020
-        self._table = self._flat = self._gflat = None
-        self._views = {}
-        self._bufs = {}
-        self._saved = None
-        self._step_counter = 0
-        self._drop_dev = None
-        self.grad_scale = 1.0
-        self.sparse_table_grad = None
-        self._sparse = None
-        self._table_hooks = None
         self.store_ifeatures = None
 
     # ------------------------------------------------------------------------------------------ packing
@@ -144,76 +112,6 @@ class MF(BaseModel):
         """Rows of the table buffer each table parameter occupies (optim.table_spans), in the reference's order."""
         U = self.user_num
         return {"user_embedding.weight": (1, 1 + U), "item_embedding.weight": (1 + U, 1 + U + self.item_num)}
-
-    def lazy_table(self):
-        self._ensure_packed()
-        return self._table
-
-    def _ensure_packed(self):
-        """(Re)build the [1 + U + I, D] table and the flat tower buffer when the parameters moved (e.g. after .to(device))."""
-        u = self.user_embedding.weight
-        if self._table is not None and self._table.device == u.device and u.data_ptr() == self._table[1].data_ptr():
-            return
-        dev = u.device
-        if dev.type != "cuda":
-            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with .to('cuda') first")
-        U, I, D = self.user_num, self.item_num, self.embedding_size
-        table = torch.zeros(1 + U + I, D, dtype=torch.float32, device=dev)
-        table[1:1 + U].copy_(u.data)
-        table[1 + U:].copy_(self.item_embedding.weight.data)
-        u.data, self.item_embedding.weight.data = table[1:1 + U], table[1 + U:]
-        specs = self._flat_specs()
-        total = max(4, sum(p.numel() for _, p in specs))    # (never empty: the flat launch takes real pointers)
-        flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        gflat = torch.zeros(total, dtype=torch.float32, device=dev)
-        off, views = 0, {}
-        for name, p in specs:
-            n = p.numel()
-            flat[off:off + n].copy_(p.data.reshape(-1))
-            p.data = flat[off:off + n].view(p.shape)
-            p.grad = gflat[off:off + n].view(p.shape)
-            views[name] = (off, n, tuple(p.shape))
-            off += n
-        self._table, self._flat, self._gflat, self._views = table, flat, gflat, views
-        self._anchor = torch.zeros((), dtype=torch.float32, device=dev, requires_grad=True)
-        self._drop_dev = torch.full((1,), self._step_counter, dtype=torch.int64, device=dev)
-        self._bufs = {}
-
-    def flat_parameters(self):
-        self._ensure_packed()
-        return self._flat, self._gflat
-
-    def _p(self, name, grad=False):
-        off, n, shape = self._views[name]
-        return (self._gflat if grad else self._flat)[off:off + n].view(shape)
-
-    def _buf(self, name, shape, dtype=torch.float32):
-        """Persistent work buffers (stable addresses: a captured step replays on them)."""
-        b = self._bufs.get(name)
-        if b is None or tuple(b.shape) != tuple(shape) or b.dtype != dtype:
-            b = self._bufs[name] = torch.empty(*shape, dtype=dtype, device=self._table.device)
-        return b
-
-    # ------------------------------------------------------------------------------------------ the table (lazy optimizer hooks)
-    def register_table_hooks(self, opt):
-        """Attach a lazy table optimizer: it is asked to bring rows up to date before they are read."""
-        self._table_hooks = opt
-
-    def join_prefetch(self):
-        return None
-
-    def sync_table(self):
-        """Make every table row current (no-op without a lazy optimizer)."""
-        if self._table_hooks is not None:
-            self._table_hooks.flush()
-
-    def state_dict(self, *args, **kwargs):
-        self.sync_table()
-        return super().state_dict(*args, **kwargs)
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        self.sync_table()
-        return super().load_state_dict(state_dict, strict=strict, **kwargs)
 
     def running_state_buffers(self):
         """The BatchNorm buffers a training step advances on the device (GraphedTrainStep's dry run restores them)."""
@@ -269,7 +167,7 @@ class MF(BaseModel):
         if self.mlp_hidden_size and user.numel() == 1:
             raise ValueError("Expected more than 1 value per channel when training, got input size torch.Size([1, %d])"
                              % self.mlp_hidden_size[0])
-        return _PairStep.apply(self._anchor, self, user, item)
+        return TrainStep.apply(self._anchor, self, user, item)
 
     def _forward_train(self, user, item):
         B, D = user.numel(), self.embedding_size
@@ -288,19 +186,13 @@ class MF(BaseModel):
         self._saved = dict(B=B, rows=rows, coef=coef, hu=hu, hi=hi, su=su, si=si)
         return loss
 
-    def _sparse_rows(self, B):
-        sp = self._sparse
-        if sp is None or sp.cap != 3 * B or sp.rows.device != self._table.device:
-            sp = self._sparse = ops.SparseRows(3 * B, self.embedding_size, self._table.device)
-        return sp
-
     def _backward_train(self, grad_out):
         s = self._saved
         if s is None:
             raise PxrError("backward() without a training-mode forward()")
         B = s["B"]
         gsd = grad_out.reshape(1).to(torch.float32).contiguous()
-        sp = self._sparse_rows(B)
+        sp = self._sparse_rows(3 * B)
         if not self.mlp_hidden_size:
             ops.mf_table_grad(s["rows"], B, sp, table=self._table, coef=s["coef"], grad_scale=self.grad_scale, grad_scale_dev=gsd)
         else:

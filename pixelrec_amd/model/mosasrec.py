@@ -17,24 +17,9 @@ import torch
 
 from .. import ops
 from ..utils.enum_type import InputType
+from .packed import TrainStep
 from .seqcore import SeqRecCore
 from .visual import load_model
-
-
-class _PixelStep(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, item_emb, model, idx, masked_index):
-        ctx.model = model
-        table = item_emb.detach().reshape(-1, item_emb.shape[-1]).contiguous()
-        ctx.table = table
-        return model._forward_core(table, idx, masked_index, train=True).view(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        m = ctx.model
-        dx0, coef, s = m._backward_core(grad_out, ctx.table)
-        d_emb = ops.mosasrec_emb_grad(dx0, s["out"], coef)         # [B, L+1, 2, D]
-        return d_emb, None, None, None
 
 
 class MOSASRec(SeqRecCore):
@@ -77,9 +62,19 @@ class MOSASRec(SeqRecCore):
         if torch.is_grad_enabled() and self.training:
             if not item_emb.requires_grad:   # fully frozen encoder: still drive the backward of the sequence block
                 item_emb = item_emb + self._anchor * 0
-            return _PixelStep.apply(item_emb, self, idx, masked_index)
+            self._train_table = item_emb.detach().reshape(-1, self.embedding_size).contiguous()
+            return TrainStep.apply(item_emb, self, idx, masked_index)
         table = item_emb.detach().reshape(-1, self.embedding_size).contiguous()
         return self._forward_core(table, idx, masked_index, train=False).view(())
+
+    def _forward_train(self, idx, masked_index):
+        return self._forward_core(self._train_table, idx, masked_index, train=True)
+
+    def _backward_train(self, grad_out):
+        """-> the gradient of the encoder's output [B, L+1, 2, D] (the bridge's anchor)."""
+        table, self._train_table = self._train_table, None
+        dx0, coef, s = self._backward_core(grad_out, table)
+        return ops.mosasrec_emb_grad(dx0, s["out"], coef)
 
     @torch.no_grad()
     def encode_last(self, item_seq, item_feature):

@@ -20,24 +20,11 @@ import torch.nn as nn
 
 from .. import ops
 from ..utils.enum_type import InputType
+from .packed import TableHooks, TrainStep
 from .seqcore import SeqRecCore
 
 
-class _TrainStep(torch.autograd.Function):
-    """Bridges `loss.backward()` to the hand-written backward chain."""
-
-    @staticmethod
-    def forward(ctx, anchor, model, items, masked_index):
-        ctx.model = model
-        return model._forward_train(items, masked_index).view(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        ctx.model._backward_train(grad_out)
-        return None, None, None, None
-
-
-class SASRec(SeqRecCore):
+class SASRec(TableHooks, SeqRecCore):
     input_type = InputType.SEQ
 
     def __init__(self, config, dataload):
@@ -50,9 +37,7 @@ class SASRec(SeqRecCore):
 
     def _init_table_state(self):
         """Bookkeeping of the sparsely updated item table (shared with the sibling ID backbones)."""
-        self.sparse_table_grad = None   # the table gradient the optimizer will apply (local, or merged across ranks)
-        self._local_sparse = None       # reusable output buffer of this rank's backward
-        self._table_hooks = None        # the lazy optimizer (catch_up_rows / flush) when one is attached
+        self._local_sparse = None       # reusable output buffer of this rank's backward (-> sparse_table_grad, local or merged)
         self._occ_ws = None             # persistent workspace carrying the sorted occurrences fwd -> bwd
         self._occ_ws2 = None            # second workspace of the split segment sums (big batches; zero-initialised cursor)
         # look-ahead for a lazy table optimizer: the ids of the NEXT batch (set_next_batch).  Their rows are brought up to
@@ -73,10 +58,6 @@ class SASRec(SeqRecCore):
 
     # state_dict key order of the reference: item_embedding first (sasrec.py:31-45); register order above differs only
     # in position, which load_state_dict does not care about.
-
-    def register_table_hooks(self, opt):
-        """Attach a lazy table optimizer: it is asked to bring rows up to date before they are read."""
-        self._table_hooks = opt
 
     def set_next_batch(self, items_next):
         """Optional look-ahead (lazy table optimizer only): `items_next` int64 [B,2,L+1] on the device = the batch the
@@ -140,22 +121,6 @@ class SASRec(SeqRecCore):
         """Order the current stream behind the look-ahead catch-up (the optimizer calls this before it touches rows)."""
         if self._prefetched is not None and self._prefetch_stream is not None:
             torch.cuda.current_stream().wait_stream(self._prefetch_stream)
-
-    def sync_table(self):
-        """Make every table row current (no-op without a lazy optimizer).  Called before the table is read as a
-        whole: predict / compute_item_all / state_dict."""
-        if self._table_hooks is not None:
-            self._table_hooks.flush()
-
-    def state_dict(self, *args, **kwargs):
-        self.sync_table()
-        return super().state_dict(*args, **kwargs)
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        # updates a lazy optimizer still owes belong to the rows being REPLACED: apply them first, so that none is left
-        # to land on the loaded weights (the reference's dense AdamW has applied them by the time it loads)
-        self.sync_table()
-        return super().load_state_dict(state_dict, strict=strict, **kwargs)
 
     def _forward_train(self, items, masked_index):
         B = items.shape[0]
@@ -239,7 +204,7 @@ class SASRec(SeqRecCore):
         items = items.contiguous()
         masked_index = masked_index.contiguous()
         if torch.is_grad_enabled() and self.training:
-            return _TrainStep.apply(self._anchor, self, items, masked_index)
+            return TrainStep.apply(self._anchor, self, items, masked_index)
         was = self.training
         try:
             self.training = False

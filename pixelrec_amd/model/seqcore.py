@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..lib import PxrError
-from .basemodel import BaseModel
+from .packed import PackedModel
 
 
 # ---- parameter containers with the reference's module tree (names only; their forward is never called) -----
@@ -60,7 +60,7 @@ class _TransformerEncoderParams(nn.Module):
 
 
 
-class SeqRecCore(BaseModel):
+class SeqRecCore(PackedModel):
     """Parameters + forward/backward of the sequence block; subclasses supply the row source."""
 
     def _build_core(self, config):
@@ -92,14 +92,7 @@ class SeqRecCore(BaseModel):
     def _init_runtime_state(self, config):
         """Everything a model on the flat-buffer / hand-written-backward machinery carries besides its architecture (also used
         by the sibling backbones that bring their own layers: gru4rec.py)."""
-        self._flat = None            # packed non-table parameters
-        self._gflat = None           # packed gradients (same layout)
-        self._views = {}
-        self._anchor = None
-        self._saved = None
-        self.grad_scale = 1.0           # 1/world_size under data parallelism (sum-all-reduce == DDP's mean)
         self._side_stream = None
-        self._drop_dev = None              # device counter of completed backward passes (dropout seed offset)
         self.group_weight_grads = True     # all weight/bias gradients of a backward pass in one grouped GEMM launch
         self.overlap_weight_grads = False  # alternative: per-layer launches on a side HIP stream
         # WHERE the grouped weight-gradient launches go (group_weight_grads only):
@@ -123,7 +116,6 @@ class SeqRecCore(BaseModel):
         # reads p.grad right after backward() must not race with the side stream.
         self.defer_weight_grad_join = False
         self._drop_seed = int(config["seed"]) if config["seed"] is not None else 2020
-        self._step_counter = 0
         # GEMM operands as pre-split bf16x3 planes (csrc/gemm_p3.cuh): every producer of a GEMM operand (LayerNorm, attention,
         # GEMM epilogues) writes the three bf16 terms once, in the panel layout the GEMM tiles copy linearly, instead of every
         # reading tile splitting fp32 values again.  Same arithmetic as GEMM mode bf16x3 (bit-identical products).  Needs
@@ -161,41 +153,9 @@ class SeqRecCore(BaseModel):
         """The parameter at offset 0 of the flat buffer (its address tells whether the buffer is still the packed one)."""
         return self.position_embedding.weight
 
-    def _ensure_packed(self):
-        """(Re)build the flat parameter / gradient buffers when the parameters moved (e.g. after .to(device))."""
-        w0 = self._first_flat_parameter()
-        if self._flat is not None and self._flat.device == w0.device and w0.data_ptr() == self._flat.data_ptr():
-            return
-        dev = w0.device
-        if dev.type != "cuda":
-            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with "
-                           ".to('cuda') first")
-        specs = self._flat_specs()
-        total = sum(p.numel() for _, p in specs)
-        flat = torch.empty(total, dtype=torch.float32, device=dev)
-        gflat = torch.zeros(total, dtype=torch.float32, device=dev)
-        off = 0
-        views = {}
-        for name, p in specs:
-            n = p.numel()
-            flat[off:off + n].copy_(p.data.reshape(-1))
-            p.data = flat[off:off + n].view(p.shape)
-            p.grad = gflat[off:off + n].view(p.shape)
-            views[name] = (off, n, tuple(p.shape))
-            off += n
-        self._flat, self._gflat, self._views = flat, gflat, views
+    def _after_pack(self, dev):
         self._wplanes, self._wplanes_fresh = None, False
         self._wplanes_h2, self._wplanes_h2_fresh = None, False
-        self._anchor = torch.zeros((), dtype=torch.float32, device=dev, requires_grad=True)
-        self._drop_dev = torch.full((1,), self._step_counter, dtype=torch.int64, device=dev)
-
-    def _p(self, name, grad=False, span=1):
-        """View of parameter `name` (or of `span` adjacent ones fused along dim 0) in the flat (grad) buffer."""
-        off, n, shape = self._views[name]
-        buf = self._gflat if grad else self._flat
-        if span == 1:
-            return buf[off:off + n].view(shape)
-        return buf[off:off + span * n].view((span * shape[0],) + tuple(shape[1:]))
 
     # ---- the dropout "RNG state": masks are a stateless hash of (seed, site, element, step), so the only state is
     # the number of completed backward passes (host mirror + device counter).  Saved / restored with checkpoints.
@@ -206,10 +166,6 @@ class SeqRecCore(BaseModel):
         self._step_counter = int(n)
         if getattr(self, "_drop_dev", None) is not None:
             self._drop_dev.fill_(self._step_counter)
-
-    def flat_parameters(self):
-        self._ensure_packed()
-        return self._flat, self._gflat
 
     _flat_grad_waits = ()   # handles of an in-flight all-reduce of the flat gradient (parallel.GradSync, defer_flat)
 

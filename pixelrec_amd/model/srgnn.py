@@ -39,7 +39,7 @@ from .. import ops
 from ..lib import PxrError
 from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .basemodel import BaseModel
+from .packed import PackedModel, TableHooks, TrainStep
 
 
 class _GNN(nn.Module):
@@ -60,21 +60,7 @@ class _GNN(nn.Module):
         self.linear_edge_f = nn.Linear(hidden_size, hidden_size, bias=True)
 
 
-class _SrgnnStep(torch.autograd.Function):
-    """Bridges `loss.backward()` to the hand-written backward chain."""
-
-    @staticmethod
-    def forward(ctx, anchor, model, item_seq, mask, target):
-        ctx.model = model
-        return model._forward_train(item_seq, mask, target).view(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        ctx.model._backward_train(grad_out)
-        return None, None, None, None, None
-
-
-class SRGNN(BaseModel):
+class SRGNN(TableHooks, PackedModel):
     input_type = InputType.AUGSEQ
     item_table_attr = "embedding"          # the reference's table name (optim.item_table_name)
 
@@ -102,18 +88,8 @@ class SRGNN(BaseModel):
         stdv = 1.0 / math.sqrt(D)
         for w in self.parameters():                       # srgnn.py _reset_parameters, in parameter order
             w.data.uniform_(-stdv, stdv)
-        self._flat = self._gflat = None
-        self._views = {}
-        self._bufs = {}
-        self._gbufs = {}
-        self._saved = None
-        self._step_counter = 0
-        self._drop_dev = None                              # (no dropout: the step counter graph.py keeps)
-        self.grad_scale = 1.0
-        # the sparse table (SASRec's bookkeeping)
-        self.sparse_table_grad = None
-        self._local_sparse = None
-        self._table_hooks = None
+        self._gbufs = {}                                   # the session graph's buffers (ops.srgnn_graph)
+        self._local_sparse = None                          # the sparse table (SASRec's bookkeeping)
         self._occ_ws = self._occ_ws2 = None
 
     # ------------------------------------------------------------------------------------------ flat packing
@@ -139,70 +115,10 @@ class SRGNN(BaseModel):
                 "linear_two.weight": "two.w", "linear_two.bias": "two.b", "linear_three.weight": "three.w",
                 "linear_transform.weight": "t.w", "linear_transform.bias": "t.b"}
 
-    def _ensure_packed(self):
-        w0 = self.gnn.linear_edge_in.weight
-        if self._flat is not None and self._flat.device == w0.device and w0.data_ptr() == self._flat.data_ptr():
-            return
-        dev = w0.device
-        if dev.type != "cuda":
-            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with .to('cuda') first")
-        specs = self._flat_specs()
-        total = sum(p.numel() for _, p in specs)
-        flat = torch.empty(total, dtype=torch.float32, device=dev)
-        gflat = torch.zeros(total, dtype=torch.float32, device=dev)
-        off, views = 0, {}
-        for name, p in specs:
-            n = p.numel()
-            flat[off:off + n].copy_(p.data.reshape(-1))
-            p.data = flat[off:off + n].view(p.shape)
-            p.grad = gflat[off:off + n].view(p.shape)
-            views[name] = (off, n, tuple(p.shape))
-            off += n
-        self._flat, self._gflat, self._views = flat, gflat, views
-        self._anchor = torch.zeros((), dtype=torch.float32, device=dev, requires_grad=True)
-        self._drop_dev = torch.full((1,), self._step_counter, dtype=torch.int64, device=dev)
-        self._bufs, self._gbufs = {}, {}
-
-    def flat_parameters(self):
-        self._ensure_packed()
-        return self._flat, self._gflat
-
-    def _p(self, name, grad=False, span=1):
-        """View of parameter `name` (or of `span` adjacent ones fused along dim 0) in the flat (grad) buffer."""
-        off, n, shape = self._views[name]
-        buf = self._gflat if grad else self._flat
-        if span == 1:
-            return buf[off:off + n].view(shape)
-        return buf[off:off + span * n].view((span * shape[0],) + tuple(shape[1:]))
-
-    def _buf(self, name, shape, zero=False):
-        """Persistent work buffers (stable addresses: a captured step replays on them)."""
-        b = self._bufs.get(name)
-        if b is None or tuple(b.shape) != tuple(shape):
-            b = self._bufs[name] = (torch.zeros if zero else torch.empty)(*shape, dtype=torch.float32, device=self._flat.device)
-        return b
+    def _after_pack(self, dev):
+        self._gbufs = {}
 
     # ------------------------------------------------------------------------------------------ the table (SASRec's machinery)
-    def register_table_hooks(self, opt):
-        """Attach a lazy table optimizer: it is asked to bring rows up to date before they are read."""
-        self._table_hooks = opt
-
-    def join_prefetch(self):
-        return None
-
-    def sync_table(self):
-        """Make every table row current (no-op without a lazy optimizer)."""
-        if self._table_hooks is not None:
-            self._table_hooks.flush()
-
-    def state_dict(self, *args, **kwargs):
-        self.sync_table()
-        return super().state_dict(*args, **kwargs)
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        self.sync_table()
-        return super().load_state_dict(state_dict, strict=strict, **kwargs)
-
     def _table_prepare(self, g, B, L, D, device):
         """Occurrence sort of the batch's node and target ids, then the lazy catch-up of exactly those rows."""
         cap = B * (L + 2)
@@ -267,7 +183,7 @@ class SRGNN(BaseModel):
         self._ensure_packed()
         item_seq, mask, target = item_seq.contiguous(), mask.contiguous(), target.contiguous()
         if torch.is_grad_enabled() and self.training:
-            return _SrgnnStep.apply(self._anchor, self, item_seq, mask, target)
+            return TrainStep.apply(self._anchor, self, item_seq, mask, target)
         was = self.training
         try:
             self.training = False

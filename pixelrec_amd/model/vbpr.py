@@ -41,25 +41,10 @@ from .. import ops
 from ..lib import PxrError
 from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .basemodel import BaseModel
-from .mf import _Rows
+from .packed import LazyTableModel, TrainStep, _Rows
 
 
-class _PairStep(torch.autograd.Function):
-    """Bridges `loss.backward()` to the hand-written backward chain."""
-
-    @staticmethod
-    def forward(ctx, anchor, model, user, item):
-        ctx.model = model
-        return model._forward_train(user, item).view(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        ctx.model._backward_train(grad_out)
-        return None, None, None, None
-
-
-class VBPR(BaseModel):
+class VBPR(LazyTableModel):
     input_type = InputType.PAIR
     # the optimizer may run the flat buffer (the projections) and the table buffer under separate scalars: optim.flat_table_adamw
     split_flat_table_groups = True
@@ -97,23 +82,10 @@ class VBPR(BaseModel):
         for mod in (self.feature_projection, self.bias_projection, self.user_id_embedding, self.item_id_embedding,
                     self.user_modal_embedding):            # vbpr.py _init_weights through self.apply, in module order
             nn.init.xavier_normal_(mod.weight.data)
-        self._table = self._flat = self._gflat = None
-        self._views = {}
-        self._bufs = {}
-        self._saved = None
-        self._step_counter = 0
-        self._drop_dev = None
-        self.grad_scale = 1.0
-        self.sparse_table_grad = None
-        self._sparse = None
-        self._table_hooks = None
         self.store_ifeatures = None
         self.total_visual_bias = None
 
     # ------------------------------------------------------------------------------------------ packing
-    def _tables(self):
-        return (self.user_id_embedding, self.item_id_embedding, self.user_modal_embedding)
-
     def _flat_specs(self):
         """Flat layout: the two projections in the reference's parameter order."""
         return [("W", self.feature_projection.weight), ("wb", self.bias_projection.weight)]
@@ -130,76 +102,8 @@ class VBPR(BaseModel):
         return {"user_id_embedding.weight": (1, 1 + U), "item_id_embedding.weight": (1 + U, 1 + U + I),
                 "user_modal_embedding.weight": (1 + U + I, 1 + U + I + U)}
 
-    def lazy_table(self):
-        self._ensure_packed()
-        return self._table
-
-    def _ensure_packed(self):
-        """(Re)build the [1 + U + I + U, Dh] table and the flat projection buffer when the parameters moved (e.g. after .to(device))."""
-        u = self.user_id_embedding.weight
-        if self._table is not None and self._table.device == u.device and u.data_ptr() == self._table[1].data_ptr():
-            return
-        dev = u.device
-        if dev.type != "cuda":
-            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with .to('cuda') first")
-        spans = self.table_parameter_spans()
-        table = torch.zeros(1 + 2 * self.user_num + self.item_num, self.embedding_size, dtype=torch.float32, device=dev)
-        for mod, (lo, hi) in zip(self._tables(), spans.values()):
-            table[lo:hi].copy_(mod.weight.data)
-            mod.weight.data = table[lo:hi]
-        specs = self._flat_specs()
-        total = sum(p.numel() for _, p in specs)
-        flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        gflat = torch.zeros(total, dtype=torch.float32, device=dev)
-        off, views = 0, {}
-        for name, p in specs:
-            n = p.numel()
-            flat[off:off + n].copy_(p.data.reshape(-1))
-            p.data = flat[off:off + n].view(p.shape)
-            p.grad = gflat[off:off + n].view(p.shape)
-            views[name] = (off, n, tuple(p.shape))
-            off += n
+    def _after_pack(self, dev):
         self.v_feat = self.v_feat.to(dev)
-        self._table, self._flat, self._gflat, self._views = table, flat, gflat, views
-        self._anchor = torch.zeros((), dtype=torch.float32, device=dev, requires_grad=True)
-        self._drop_dev = torch.full((1,), self._step_counter, dtype=torch.int64, device=dev)     # (no dropout: the step counter only)
-        self._bufs = {}
-
-    def flat_parameters(self):
-        self._ensure_packed()
-        return self._flat, self._gflat
-
-    def _p(self, name, grad=False):
-        off, n, shape = self._views[name]
-        return (self._gflat if grad else self._flat)[off:off + n].view(shape)
-
-    def _buf(self, name, shape, dtype=torch.float32):
-        """Persistent work buffers (stable addresses: a captured step replays on them)."""
-        b = self._bufs.get(name)
-        if b is None or tuple(b.shape) != tuple(shape) or b.dtype != dtype:
-            b = self._bufs[name] = torch.empty(*shape, dtype=dtype, device=self._table.device)
-        return b
-
-    # ------------------------------------------------------------------------------------------ the table (lazy optimizer hooks)
-    def register_table_hooks(self, opt):
-        """Attach a lazy table optimizer: it is asked to bring rows up to date before they are read."""
-        self._table_hooks = opt
-
-    def join_prefetch(self):
-        return None
-
-    def sync_table(self):
-        """Make every table row current (no-op without a lazy optimizer)."""
-        if self._table_hooks is not None:
-            self._table_hooks.flush()
-
-    def state_dict(self, *args, **kwargs):
-        self.sync_table()
-        return super().state_dict(*args, **kwargs)
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        self.sync_table()
-        return super().load_state_dict(state_dict, strict=strict, **kwargs)
 
     # ------------------------------------------------------------------------------------------ training
     def forward(self, input):
@@ -208,7 +112,7 @@ class VBPR(BaseModel):
             raise PxrError("VBPR.forward is the training loss (vbpr.py forward); use compute_item_all / predict to score")
         self._ensure_packed()
         user, item = user.reshape(-1).contiguous(), item.contiguous()
-        return _PairStep.apply(self._anchor, self, user, item)
+        return TrainStep.apply(self._anchor, self, user, item)
 
     def _forward_train(self, user, item):
         B, Dh, F = user.numel(), self.embedding_size, self.feature_dim
@@ -222,19 +126,13 @@ class VBPR(BaseModel):
         self._saved = dict(B=B, rows=rows, coef=coef, x=x, e=e)
         return loss
 
-    def _sparse_rows(self, B):
-        sp = self._sparse
-        if sp is None or sp.cap != 4 * B or sp.rows.device != self._table.device:
-            sp = self._sparse = ops.SparseRows(4 * B, self.embedding_size, self._table.device)
-        return sp
-
     def _backward_train(self, grad_out):
         s = self._saved
         if s is None:
             raise PxrError("backward() without a training-mode forward()")
         B, Dh = s["B"], self.embedding_size
         gsd = grad_out.reshape(1).to(torch.float32).contiguous()
-        sp = self._sparse_rows(B)
+        sp = self._sparse_rows(4 * B)
         de, csign = self._buf("de", (2 * B, Dh)), self._buf("csign", (2 * B,))
         ops.vbpr_pair_bwd(self._table, s["rows"], s["e"], s["coef"], B, de, csign, sp, self.grad_scale, gsd)
         ops.vbpr_bias_grad(s["x"], csign, self._p("wb", grad=True).view(-1))
