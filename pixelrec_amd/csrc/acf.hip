@@ -12,16 +12,15 @@
 //
 // One workgroup (4 waves) per r (region level) or per b (item level): a wave owns one h (or p) at a time for the inner products,
 // then every thread owns float4 columns for the weighted sums.  Every sum has one fixed order; no atomics on floats.
-#include "pxr_common.h"
+#include "pair_head.cuh"
 
 namespace pxr {
 
-typedef float af4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float acf_dot4(const af4& p, const af4& q) { return p.x * q.x + p.y * q.y + p.z * q.z + p.w * q.w; }
-__device__ __forceinline__ af4 acf_relu4(const af4& z) { return af4{fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f)}; }
-__device__ __forceinline__ af4 acf_step4(const af4& z) {
-  return af4{z.x > 0.f ? 1.f : 0.f, z.y > 0.f ? 1.f : 0.f, z.z > 0.f ? 1.f : 0.f, z.w > 0.f ? 1.f : 0.f};
+__device__ __forceinline__ f32x4 acf_relu4(const f32x4& z) {
+  return f32x4{fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f)};
+}
+__device__ __forceinline__ f32x4 acf_step4(const f32x4& z) {
+  return f32x4{z.x > 0.f ? 1.f : 0.f, z.y > 0.f ? 1.f : 0.f, z.z > 0.f ? 1.f : 0.f, z.w > 0.f ? 1.f : 0.f};
 }
 constexpr int ACF_MAX_N = 1024;      // regions per item / history items per user held in LDS
 
@@ -35,12 +34,8 @@ __global__ void __launch_bounds__(256) acf_rows_kernel(const int64_t* __restrict
   const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (o >= n_prof + n_it + n_u) return;
   const bool is_user = o >= n_prof + n_it;
-  int64_t id = o < n_prof ? profile[o] : (is_user ? user[o - n_prof - n_it] : items[o - n_prof]);
-  const int64_t n = is_user ? n_users : n_items;
-  if (id < 0 || id >= n) {
-    if (status) atomicOr(status, PXR_STATUS_BAD_INDEX);
-    id = id < 0 ? 0 : n - 1;
-  }
+  const int64_t id = checked_id(o < n_prof ? profile[o] : (is_user ? user[o - n_prof - n_it] : items[o - n_prof]),
+                                is_user ? n_users : n_items, status, true);
   const int64_t row = 1 + (is_user ? n_items : 0) + id;
   rows[o] = row;
   if (gidx) gidx[o] = (!is_user && id == 0) ? 0 : row;
@@ -57,17 +52,17 @@ __device__ __forceinline__ void acf_softmax_stats(const float* s, int n, float& 
 }
 
 struct AcfRegionArgs {
-  const af4* x;                // [R, H, ev]
-  const af4* xt;               // [R, H, ev]
-  const af4* ut;               // [B, ev]
-  const af4* w;                // [ev]
+  const f32x4* x;              // [R, H, ev]
+  const f32x4* xt;             // [R, H, ev]
+  const f32x4* ut;             // [B, ev]
+  const f32x4* w;              // [ev]
   const int64_t* profile;      // [R] item ids (0 = padding)
   float* beta;                 // [R, H]
-  af4* pooled;                 // [R, ev]
-  const af4* dpooled;          // [R, ev]    (backward)
-  af4* dxt;                    // [R, H, ev]
-  af4* dutp;                   // [R, ev]: sum_h dxt[r, h, :]
-  af4* dwp;                    // [R, ev]: sum_h ds_h relu(z_h)
+  f32x4* pooled;               // [R, ev]
+  const f32x4* dpooled;        // [R, ev]    (backward)
+  f32x4* dxt;                  // [R, H, ev]
+  f32x4* dutp;                 // [R, ev]: sum_h dxt[r, h, :]
+  f32x4* dwp;                  // [R, ev]: sum_h ds_h relu(z_h)
   int R, P, H, ev;
 };
 
@@ -81,15 +76,15 @@ __global__ void __launch_bounds__(256) acf_region_fwd_kernel(AcfRegionArgs a) {
 #pragma unroll
     for (int k = 0; k < CH; ++k) {
       const int c = threadIdx.x + k * 256;
-      if (c < a.ev) a.pooled[(int64_t)r * a.ev + c] = af4{0.f, 0.f, 0.f, 0.f};
+      if (c < a.ev) a.pooled[(int64_t)r * a.ev + c] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     return;
   }
-  const af4* ut = a.ut + (int64_t)b * a.ev;
+  const f32x4* ut = a.ut + (int64_t)b * a.ev;
   for (int h = wave; h < a.H; h += 4) {
-    const af4* xt = a.xt + ((int64_t)r * a.H + h) * a.ev;
+    const f32x4* xt = a.xt + ((int64_t)r * a.H + h) * a.ev;
     float acc = 0.f;
-    for (int c = lane; c < a.ev; c += 64) acc += acf_dot4(a.w[c], acf_relu4(xt[c] + ut[c]));
+    for (int c = lane; c < a.ev; c += 64) acc += dot4(a.w[c], acf_relu4(xt[c] + ut[c]));
     acc = wave_sum(acc);
     if (lane == 0) s[h] = acc;
   }
@@ -97,12 +92,12 @@ __global__ void __launch_bounds__(256) acf_region_fwd_kernel(AcfRegionArgs a) {
   float mx, inv;
   acf_softmax_stats(s, a.H, mx, inv);
   for (int h = threadIdx.x; h < a.H; h += 256) a.beta[(int64_t)r * a.H + h] = expf(s[h] - mx) * inv;
-  af4 acc[CH];
+  f32x4 acc[CH];
 #pragma unroll
-  for (int k = 0; k < CH; ++k) acc[k] = af4{0.f, 0.f, 0.f, 0.f};
+  for (int k = 0; k < CH; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int h = 0; h < a.H; ++h) {
     const float bh = expf(s[h] - mx) * inv;
-    const af4* x = a.x + ((int64_t)r * a.H + h) * a.ev;
+    const f32x4* x = a.x + ((int64_t)r * a.H + h) * a.ev;
 #pragma unroll
     for (int k = 0; k < CH; ++k) {
       const int c = threadIdx.x + k * 256;
@@ -125,11 +120,11 @@ __global__ void __launch_bounds__(256) acf_region_bwd_kernel(AcfRegionArgs a) {
   const bool masked = a.profile[r] == 0;
   const float* beta = a.beta + (int64_t)r * a.H;
   if (!masked) {
-    const af4* dp = a.dpooled + (int64_t)r * a.ev;
+    const f32x4* dp = a.dpooled + (int64_t)r * a.ev;
     for (int h = wave; h < a.H; h += 4) {
-      const af4* x = a.x + ((int64_t)r * a.H + h) * a.ev;
+      const f32x4* x = a.x + ((int64_t)r * a.H + h) * a.ev;
       float acc = 0.f;
-      for (int c = lane; c < a.ev; c += 64) acc += acf_dot4(dp[c], x[c]);
+      for (int c = lane; c < a.ev; c += 64) acc += dot4(dp[c], x[c]);
       acc = wave_sum(acc);
       if (lane == 0) ds[h] = acc;
     }
@@ -141,12 +136,12 @@ __global__ void __launch_bounds__(256) acf_region_bwd_kernel(AcfRegionArgs a) {
   __syncthreads();
   for (int h = threadIdx.x; h < a.H; h += 256) ds[h] = masked ? 0.f : beta[h] * (ds[h] - dot);
   __syncthreads();
-  const af4* ut = a.ut + (int64_t)b * a.ev;
-  af4 su[CH], sw[CH], uu[CH], ww[CH];
+  const f32x4* ut = a.ut + (int64_t)b * a.ev;
+  f32x4 su[CH], sw[CH], uu[CH], ww[CH];
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
     const int c = threadIdx.x + k * 256;
-    su[k] = sw[k] = af4{0.f, 0.f, 0.f, 0.f};
+    su[k] = sw[k] = f32x4{0.f, 0.f, 0.f, 0.f};
     uu[k] = c < a.ev ? ut[c] : su[k];
     ww[k] = c < a.ev ? a.w[c] : su[k];
   }
@@ -157,9 +152,9 @@ __global__ void __launch_bounds__(256) acf_region_bwd_kernel(AcfRegionArgs a) {
     for (int k = 0; k < CH; ++k) {
       const int c = threadIdx.x + k * 256;
       if (c < a.ev) {
-        af4 dz = af4{0.f, 0.f, 0.f, 0.f};
+        f32x4 dz = f32x4{0.f, 0.f, 0.f, 0.f};
         if (!masked) {
-          const af4 z = a.xt[o + c] + uu[k];
+          const f32x4 z = a.xt[o + c] + uu[k];
           dz = d * ww[k] * acf_step4(z);
           su[k] += dz;
           sw[k] += d * acf_relu4(z);
@@ -179,19 +174,19 @@ __global__ void __launch_bounds__(256) acf_region_bwd_kernel(AcfRegionArgs a) {
 }
 
 // out[b, :] = sum_p in[b, p, :] in ascending p (float4 columns)
-__global__ void __launch_bounds__(256) acf_group_sum_kernel(const af4* __restrict__ in, af4* __restrict__ out, int B, int P, int ev) {
+__global__ void __launch_bounds__(256) acf_group_sum_kernel(const f32x4* __restrict__ in, f32x4* __restrict__ out, int B, int P, int ev) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= (int64_t)B * ev) return;
   const int b = (int)(e / ev), c = (int)(e % ev);
-  af4 s = af4{0.f, 0.f, 0.f, 0.f};
+  f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int p = 0; p < P; ++p) s += in[((int64_t)b * P + p) * ev + c];
   out[e] = s;
 }
 
 // dx[r, h, :] = (dx[r, h, :] + beta[r, h] dpooled[r, :]) (x[r, h, :] > 0): the pooled path joins the feats.w_x input gradient
 // already in dx, and the ReLU of dim_reductor is applied (beta = 0 on a masked r)
-__global__ void __launch_bounds__(256) acf_region_dx_kernel(af4* __restrict__ dx, const af4* __restrict__ x,
-                                                             const float* __restrict__ beta, const af4* __restrict__ dpooled,
+__global__ void __launch_bounds__(256) acf_region_dx_kernel(f32x4* __restrict__ dx, const f32x4* __restrict__ x,
+                                                             const float* __restrict__ beta, const f32x4* __restrict__ dpooled,
                                                              int64_t n_rows, int H, int ev) {
   const int64_t total = n_rows * ev;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
@@ -203,19 +198,19 @@ __global__ void __launch_bounds__(256) acf_region_dx_kernel(af4* __restrict__ dx
 }
 
 struct AcfItemArgs {
-  const af4* uw;               // [B, ev]
-  const af4* pq;               // [R, ev]
-  const af4* cx;               // [R, ev]
-  const af4* prof;             // [R, ev]
-  const af4* w;                // [ev]
+  const f32x4* uw;             // [B, ev]
+  const f32x4* pq;             // [R, ev]
+  const f32x4* cx;             // [R, ev]
+  const f32x4* prof;           // [R, ev]
+  const f32x4* w;              // [ev]
   const int64_t* profile;      // [R]
   float* alpha;                // [B, P]
-  af4* user;                   // [B, ev]
-  const af4* duser;            // [B, ev]   (backward)
-  af4* da;                     // [R, ev]: gradient of the pre-activation (the same for pq and cx)
-  af4* dprof;                  // [R, ev]: alpha_p duser (the direct path onto the profile rows)
-  af4* duw;                    // [B, ev]: duser + sum_p da
-  af4* dwp;                    // [B, ev]: sum_p dt_p relu(a_p)
+  f32x4* user;                 // [B, ev]
+  const f32x4* duser;          // [B, ev]   (backward)
+  f32x4* da;                   // [R, ev]: gradient of the pre-activation (the same for pq and cx)
+  f32x4* dprof;                // [R, ev]: alpha_p duser (the direct path onto the profile rows)
+  f32x4* duw;                  // [B, ev]: duser + sum_p da
+  f32x4* dwp;                  // [B, ev]: sum_p dt_p relu(a_p)
   int B, P, ev;
 };
 
@@ -223,11 +218,11 @@ template <int CH>
 __global__ void __launch_bounds__(256) acf_item_fwd_kernel(AcfItemArgs a) {
   __shared__ float t[ACF_MAX_N];
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const af4* uw = a.uw + (int64_t)b * a.ev;
+  const f32x4* uw = a.uw + (int64_t)b * a.ev;
   for (int p = wave; p < a.P; p += 4) {
     const int64_t r = (int64_t)b * a.P + p;
     float acc = 0.f;
-    for (int c = lane; c < a.ev; c += 64) acc += acf_dot4(a.w[c], acf_relu4(uw[c] + a.pq[r * a.ev + c] + a.cx[r * a.ev + c]));
+    for (int c = lane; c < a.ev; c += 64) acc += dot4(a.w[c], acf_relu4(uw[c] + a.pq[r * a.ev + c] + a.cx[r * a.ev + c]));
     acc = wave_sum(acc);
     if (lane == 0) t[p] = a.profile[r] == 0 ? -INFINITY : acc;
   }
@@ -235,16 +230,16 @@ __global__ void __launch_bounds__(256) acf_item_fwd_kernel(AcfItemArgs a) {
   float mx, inv;
   acf_softmax_stats(t, a.P, mx, inv);
   for (int p = threadIdx.x; p < a.P; p += 256) a.alpha[(int64_t)b * a.P + p] = inv > 0.f ? expf(t[p] - mx) * inv : 0.f;
-  af4 acc[CH];
+  f32x4 acc[CH];
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
     const int c = threadIdx.x + k * 256;
-    acc[k] = c < a.ev ? uw[c] : af4{0.f, 0.f, 0.f, 0.f};
+    acc[k] = c < a.ev ? uw[c] : f32x4{0.f, 0.f, 0.f, 0.f};
   }
   for (int p = 0; p < a.P; ++p) {
     const float al = inv > 0.f ? expf(t[p] - mx) * inv : 0.f;
     if (al == 0.f) continue;                 // (uniform over the workgroup)
-    const af4* pr = a.prof + ((int64_t)b * a.P + p) * a.ev;
+    const f32x4* pr = a.prof + ((int64_t)b * a.P + p) * a.ev;
 #pragma unroll
     for (int k = 0; k < CH; ++k) {
       const int c = threadIdx.x + k * 256;
@@ -262,12 +257,12 @@ template <int CH>
 __global__ void __launch_bounds__(256) acf_item_bwd_kernel(AcfItemArgs a) {
   __shared__ float dt[ACF_MAX_N];
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const af4* du = a.duser + (int64_t)b * a.ev;
+  const f32x4* du = a.duser + (int64_t)b * a.ev;
   const float* alpha = a.alpha + (int64_t)b * a.P;
   for (int p = wave; p < a.P; p += 4) {
-    const af4* pr = a.prof + ((int64_t)b * a.P + p) * a.ev;
+    const f32x4* pr = a.prof + ((int64_t)b * a.P + p) * a.ev;
     float acc = 0.f;
-    for (int c = lane; c < a.ev; c += 64) acc += acf_dot4(du[c], pr[c]);
+    for (int c = lane; c < a.ev; c += 64) acc += dot4(du[c], pr[c]);
     acc = wave_sum(acc);
     if (lane == 0) dt[p] = acc;
   }
@@ -277,12 +272,12 @@ __global__ void __launch_bounds__(256) acf_item_bwd_kernel(AcfItemArgs a) {
   __syncthreads();
   for (int p = threadIdx.x; p < a.P; p += 256) dt[p] = alpha[p] * (dt[p] - dot);
   __syncthreads();
-  const af4* uw = a.uw + (int64_t)b * a.ev;
-  af4 su[CH], sw[CH], uu[CH], ww[CH], dd[CH];
+  const f32x4* uw = a.uw + (int64_t)b * a.ev;
+  f32x4 su[CH], sw[CH], uu[CH], ww[CH], dd[CH];
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
     const int c = threadIdx.x + k * 256;
-    su[k] = sw[k] = af4{0.f, 0.f, 0.f, 0.f};
+    su[k] = sw[k] = f32x4{0.f, 0.f, 0.f, 0.f};
     uu[k] = c < a.ev ? uw[c] : su[k];
     ww[k] = c < a.ev ? a.w[c] : su[k];
     dd[k] = c < a.ev ? du[c] : su[k];
@@ -294,8 +289,8 @@ __global__ void __launch_bounds__(256) acf_item_bwd_kernel(AcfItemArgs a) {
     for (int k = 0; k < CH; ++k) {
       const int c = threadIdx.x + k * 256;
       if (c < a.ev) {
-        const af4 z = uu[k] + a.pq[o + c] + a.cx[o + c];
-        const af4 dz = d * ww[k] * acf_step4(z);
+        const f32x4 z = uu[k] + a.pq[o + c] + a.cx[o + c];
+        const f32x4 dz = d * ww[k] * acf_step4(z);
         a.da[o + c] = dz;
         a.dprof[o + c] = al * dd[k];
         su[k] += dz;
@@ -356,8 +351,8 @@ extern "C" int pxr_acf_region_fwd_f32(const float* x, const float* xt, const flo
   PXR_REQUIRE(acf_aligned(x) && acf_aligned(xt) && acf_aligned(ut) && acf_aligned(w) && acf_aligned(pooled),
               "pxr_acf_region_fwd_f32: operands must be 16-byte aligned");
   AcfRegionArgs a{};
-  a.x = (const af4*)x; a.xt = (const af4*)xt; a.ut = (const af4*)ut; a.w = (const af4*)w; a.profile = profile;
-  a.beta = beta; a.pooled = (af4*)pooled; a.R = B * P; a.P = P; a.H = H; a.ev = E / 4;
+  a.x = (const f32x4*)x; a.xt = (const f32x4*)xt; a.ut = (const f32x4*)ut; a.w = (const f32x4*)w; a.profile = profile;
+  a.beta = beta; a.pooled = (f32x4*)pooled; a.R = B * P; a.P = P; a.H = H; a.ev = E / 4;
   hipStream_t st = (hipStream_t)stream;
   ACF_LAUNCH_CH(acf_region_fwd_kernel, dim3((unsigned)a.R), st, a);
   return pxr_check_launch("pxr_acf_region_fwd_f32");
@@ -374,15 +369,15 @@ extern "C" int pxr_acf_region_bwd_f32(const float* dpooled, const float* x, cons
               "pxr_acf_region_bwd_f32: operands must be 16-byte aligned");
   PXR_REQUIRE(dxt != xt && dxt != x, "pxr_acf_region_bwd_f32: dxt must not alias x or xt");
   AcfRegionArgs a{};
-  a.x = (const af4*)x; a.xt = (const af4*)xt; a.ut = (const af4*)ut; a.w = (const af4*)w; a.profile = profile;
-  a.beta = (float*)beta; a.dpooled = (const af4*)dpooled; a.dxt = (af4*)dxt; a.dutp = (af4*)ws; a.dwp = (af4*)dw_part;
+  a.x = (const f32x4*)x; a.xt = (const f32x4*)xt; a.ut = (const f32x4*)ut; a.w = (const f32x4*)w; a.profile = profile;
+  a.beta = (float*)beta; a.dpooled = (const f32x4*)dpooled; a.dxt = (f32x4*)dxt; a.dutp = (f32x4*)ws; a.dwp = (f32x4*)dw_part;
   a.R = B * P; a.P = P; a.H = H; a.ev = E / 4;
   hipStream_t st = (hipStream_t)stream;
   ACF_LAUNCH_CH(acf_region_bwd_kernel, dim3((unsigned)a.R), st, a);
   int rc = pxr_check_launch("pxr_acf_region_bwd_f32");
   if (rc) return rc;
   const int64_t n = (int64_t)B * a.ev;
-  hipLaunchKernelGGL(acf_group_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const af4*)ws, (af4*)dut, B, P,
+  hipLaunchKernelGGL(acf_group_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const f32x4*)ws, (f32x4*)dut, B, P,
                      a.ev);
   return pxr_check_launch("pxr_acf_region_bwd_f32 (group sum)");
 }
@@ -396,8 +391,8 @@ extern "C" int pxr_acf_region_dx_f32(float* dx, const float* x, const float* bet
   const int64_t total = R * H * (E / 4);
   int64_t blocks = (total + 255) / 256;
   if (blocks > 256 * 256) blocks = 256 * 256;
-  hipLaunchKernelGGL(acf_region_dx_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (af4*)dx, (const af4*)x, beta,
-                     (const af4*)dpooled, R * H, H, E / 4);
+  hipLaunchKernelGGL(acf_region_dx_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (f32x4*)dx, (const f32x4*)x, beta,
+                     (const f32x4*)dpooled, R * H, H, E / 4);
   return pxr_check_launch("pxr_acf_region_dx_f32");
 }
 
@@ -415,8 +410,8 @@ extern "C" int pxr_acf_item_fwd_f32(const float* uw, const float* pq, const floa
   PXR_REQUIRE(acf_aligned(uw) && acf_aligned(pq) && acf_aligned(cx) && acf_aligned(prof) && acf_aligned(w) && acf_aligned(user),
               "pxr_acf_item_fwd_f32: operands must be 16-byte aligned");
   AcfItemArgs a{};
-  a.uw = (const af4*)uw; a.pq = (const af4*)pq; a.cx = (const af4*)cx; a.prof = (const af4*)prof; a.w = (const af4*)w;
-  a.profile = profile; a.alpha = alpha; a.user = (af4*)user; a.B = B; a.P = P; a.ev = E / 4;
+  a.uw = (const f32x4*)uw; a.pq = (const f32x4*)pq; a.cx = (const f32x4*)cx; a.prof = (const f32x4*)prof; a.w = (const f32x4*)w;
+  a.profile = profile; a.alpha = alpha; a.user = (f32x4*)user; a.B = B; a.P = P; a.ev = E / 4;
   hipStream_t st = (hipStream_t)stream;
   ACF_LAUNCH_CH(acf_item_fwd_kernel, dim3((unsigned)B), st, a);
   return pxr_check_launch("pxr_acf_item_fwd_f32");
@@ -433,8 +428,8 @@ extern "C" int pxr_acf_item_bwd_f32(const float* duser, const float* uw, const f
   PXR_REQUIRE(da != pq && da != cx && dprof != prof && duw != duser && duw != uw,
               "pxr_acf_item_bwd_f32: outputs must not alias inputs");
   AcfItemArgs a{};
-  a.duser = (const af4*)duser; a.uw = (const af4*)uw; a.pq = (const af4*)pq; a.cx = (const af4*)cx; a.prof = (const af4*)prof;
-  a.w = (const af4*)w; a.alpha = (float*)alpha; a.da = (af4*)da; a.dprof = (af4*)dprof; a.duw = (af4*)duw; a.dwp = (af4*)dw_part;
+  a.duser = (const f32x4*)duser; a.uw = (const f32x4*)uw; a.pq = (const f32x4*)pq; a.cx = (const f32x4*)cx; a.prof = (const f32x4*)prof;
+  a.w = (const f32x4*)w; a.alpha = (float*)alpha; a.da = (f32x4*)da; a.dprof = (f32x4*)dprof; a.duw = (f32x4*)duw; a.dwp = (f32x4*)dw_part;
   a.B = B; a.P = P; a.ev = E / 4;
   hipStream_t st = (hipStream_t)stream;
   ACF_LAUNCH_CH(acf_item_bwd_kernel, dim3((unsigned)B), st, a);

@@ -14,18 +14,16 @@
 // saturates at -log(1e-8) and its gradient fades; the backward is MF's (pxr_mf_pair_bwd_f32 needs coef alone).
 //
 // The pooling kernels are bandwidth-bound: one thread per four columns, 16-byte accesses, a loop over L.
-#include "pxr_common.h"
+#include "pair_head.cuh"
 
 namespace pxr {
 
-typedef float cu4 __attribute__((ext_vector_type(4)));
-
 struct CuratorPoolArgs {
-  const cu4* h;                // [B L, ev] (ids == NULL) or [n_items, ev]
+  const f32x4* h;              // [B L, ev] (ids == NULL) or [n_items, ev]
   const int64_t* ids;          // [B, L] or NULL
   int64_t n_items;
   int B, L, ev;                // ev = E / 4
-  cu4* cat;                    // [B, 2 ev]
+  f32x4* cat;                  // [B, 2 ev]
   uint32_t* argmax;            // [B, ev] (four uint8 positions per word) or NULL
 };
 
@@ -33,18 +31,12 @@ __global__ void __launch_bounds__(256) curator_pool_kernel(CuratorPoolArgs a, in
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= (int64_t)a.B * a.ev) return;
   const int b = (int)(t / a.ev), c = (int)(t % a.ev);
-  cu4 mx = {0.f, 0.f, 0.f, 0.f}, sum = {0.f, 0.f, 0.f, 0.f};
+  f32x4 mx = {0.f, 0.f, 0.f, 0.f}, sum = {0.f, 0.f, 0.f, 0.f};
   uint32_t ax = 0, ay = 0, az = 0, aw = 0;
   for (int l = 0; l < a.L; ++l) {
     int64_t row = (int64_t)b * a.L + l;
-    if (a.ids) {
-      row = a.ids[row];
-      if (row < 0 || row >= a.n_items) {
-        if (status) atomicOr(status, PXR_STATUS_BAD_INDEX);
-        row = row < 0 ? 0 : a.n_items - 1;
-      }
-    }
-    const cu4 v = a.h[row * a.ev + c];
+    if (a.ids) row = checked_id(a.ids[row], a.n_items, status, true);
+    const f32x4 v = a.h[row * a.ev + c];
     sum += v;
     if (l == 0) {
       mx = v;
@@ -61,12 +53,12 @@ __global__ void __launch_bounds__(256) curator_pool_kernel(CuratorPoolArgs a, in
 }
 
 struct CuratorPoolBwdArgs {
-  const cu4* dcat;             // [B, 2 ev]: gradient of [max | mean]
+  const f32x4* dcat;           // [B, 2 ev]: gradient of [max | mean]
   const uint32_t* argmax;      // [B, ev]
-  const cu4* di;               // [2B, ev]: the pair head's gradient onto the positive / negative rows
-  const cu4* dact;             // [B (L + 2), ev]: selu' of the second common Linear, saved by its forward
+  const f32x4* di;             // [2B, ev]: the pair head's gradient onto the positive / negative rows
+  const f32x4* dact;           // [B (L + 2), ev]: selu' of the second common Linear, saved by its forward
   int B, L, ev;
-  cu4* dpre;                   // [B (L + 2), ev]
+  f32x4* dpre;                 // [B (L + 2), ev]
 };
 
 __global__ void __launch_bounds__(256) curator_pool_bwd_kernel(CuratorPoolBwdArgs a) {
@@ -75,11 +67,11 @@ __global__ void __launch_bounds__(256) curator_pool_bwd_kernel(CuratorPoolBwdArg
   if (t >= (n_prof + 2 * (int64_t)a.B) * a.ev) return;
   const int64_t row = t / a.ev;
   const int c = (int)(t % a.ev);
-  cu4 g;
+  f32x4 g;
   if (row < n_prof) {
     const int b = (int)(row / a.L);
     const uint32_t l = (uint32_t)(row % a.L);
-    const cu4 dmax = a.dcat[(int64_t)b * 2 * a.ev + c];
+    const f32x4 dmax = a.dcat[(int64_t)b * 2 * a.ev + c];
     const uint32_t am = a.argmax[(int64_t)b * a.ev + c];
     g = a.dcat[(int64_t)b * 2 * a.ev + a.ev + c] / (float)a.L;
     if ((am & 255u) == l) g.x += dmax.x;
@@ -93,35 +85,22 @@ __global__ void __launch_bounds__(256) curator_pool_bwd_kernel(CuratorPoolBwdArg
 }
 
 // out = a * b over n / 4 vectors (the head's user gradient through selu_pu3's saved derivative: no GEMM stands in front of it)
-__global__ void __launch_bounds__(256) curator_mul_kernel(const cu4* __restrict__ x, const cu4* __restrict__ y, cu4* __restrict__ out,
+__global__ void __launch_bounds__(256) curator_mul_kernel(const f32x4* __restrict__ x, const f32x4* __restrict__ y, f32x4* __restrict__ out,
                                                            int64_t nv) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (t < nv) out[t] = x[t] * y[t];
 }
 
-// x_b = <u_b, i+_b> - <u_b, i-_b> on the towers' outputs (u [B, hv], it [2B, hv] = positive, negative per sample);
-// lossrow[b] = -log(1e-8 + sigmoid(x_b)); coef[b] = d loss / d x_b = -(1/B) sigmoid(x)(1 - sigmoid(x)) / (1e-8 + sigmoid(x)),
-// both sigmoids in forms that stay finite for any |x| (vbpr.hip's head).  One wave per b.
-__global__ void __launch_bounds__(256) curator_pair_fwd_kernel(const cu4* __restrict__ u, const cu4* __restrict__ it, int hv, int B,
+// x_b = <u_b, i+_b> - <u_b, i-_b> on the towers' outputs (u [B, hv], it [2B, hv] = positive, negative per sample) into the tail
+// with the 1e-8 inside the log.  One wave per b.
+__global__ void __launch_bounds__(256) curator_pair_fwd_kernel(const f32x4* __restrict__ u, const f32x4* __restrict__ it, int hv, int B,
                                                                 float* __restrict__ coef, float* __restrict__ lossrow) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
-  float sp = 0.f, sn = 0.f;
-  for (int c = lane; c < hv; c += 64) {
-    const cu4 uv = u[(int64_t)b * hv + c], p = it[2 * (int64_t)b * hv + c], n = it[(2 * (int64_t)b + 1) * hv + c];
-    sp += uv.x * p.x + uv.y * p.y + uv.z * p.z + uv.w * p.w;
-    sn += uv.x * n.x + uv.y * n.y + uv.z * n.z + uv.w * n.w;
-  }
-  sp = wave_sum(sp);
-  sn = wave_sum(sn);
-  if (lane != 0) return;
-  const float x = sp - sn;
-  const float ex = expf(-fabsf(x));
-  const float sig = x >= 0.f ? 1.f / (1.f + ex) : ex / (1.f + ex);
-  const float sneg = x >= 0.f ? ex / (1.f + ex) : 1.f / (1.f + ex);         // 1 - sigmoid(x)
-  lossrow[b] = -logf(1e-8f + sig);
-  coef[b] = -(sig * sneg / (1e-8f + sig)) / (float)B;
+  float sp, sn;
+  pair_dots(u + (int64_t)b * hv, it + 2 * (int64_t)b * hv, it + (2 * (int64_t)b + 1) * hv, hv, lane, sp, sn);
+  if (lane == 0) bpr_tail_log_inside(sp - sn, B, lossrow[b], coef[b]);
 }
 
 }  // namespace pxr
@@ -134,8 +113,8 @@ extern "C" int pxr_curator_pair_fwd_f32(const float* ufeat, const float* ifeat, 
   PXR_REQUIRE(H > 0 && H % 4 == 0 && H <= 4096, "pxr_curator_pair_fwd_f32: need H %% 4 == 0 and 0 < H <= 4096 (H=%d)", H);
   PXR_REQUIRE(B > 0 && B <= (1 << 28), "pxr_curator_pair_fwd_f32: bad batch size %d", B);
   PXR_REQUIRE((((uintptr_t)ufeat | (uintptr_t)ifeat) & 15) == 0, "pxr_curator_pair_fwd_f32: features must be 16-byte aligned");
-  hipLaunchKernelGGL(curator_pair_fwd_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const cu4*)ufeat,
-                     (const cu4*)ifeat, H / 4, B, coef, lossrow);
+  hipLaunchKernelGGL(curator_pair_fwd_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)ufeat,
+                     (const f32x4*)ifeat, H / 4, B, coef, lossrow);
   const int rc = pxr_check_launch("pxr_curator_pair_fwd_f32");
   if (rc) return rc;
   return pxr_bpr_loss_reduce(lossrow, B, 1, loss, stream);        // loss = (1/B) sum_b lossrow[b], fixed order
@@ -144,8 +123,8 @@ extern "C" int pxr_curator_pair_fwd_f32(const float* ufeat, const float* ifeat, 
 extern "C" int pxr_mul_f32(const float* a, const float* b, float* out, int64_t n, void* stream) {
   PXR_REQUIRE(a && b && out && n > 0 && n % 4 == 0 && n <= (1ll << 38), "pxr_mul_f32: bad args (n must be a positive multiple of 4)");
   PXR_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0, "pxr_mul_f32: operands must be 16-byte aligned");
-  hipLaunchKernelGGL(curator_mul_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const cu4*)a,
-                     (const cu4*)b, (cu4*)out, n / 4);
+  hipLaunchKernelGGL(curator_mul_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)a,
+                     (const f32x4*)b, (f32x4*)out, n / 4);
   return pxr_check_launch("pxr_mul_f32");
 }
 
@@ -158,7 +137,7 @@ extern "C" int pxr_curator_pool_f32(const float* h, const int64_t* ids, int64_t 
   PXR_REQUIRE(!ids || (n_items > 0 && n_items < (1ll << 40)), "pxr_curator_pool_f32: bad item count %lld", (long long)n_items);
   PXR_REQUIRE((((uintptr_t)h | (uintptr_t)cat) & 15) == 0 && ((uintptr_t)argmax & 3) == 0,
               "pxr_curator_pool_f32: operands must be 16-byte aligned (argmax: 4-byte)");
-  CuratorPoolArgs a{(const cu4*)h, ids, n_items, B, L, E / 4, (cu4*)cat, (uint32_t*)argmax};
+  CuratorPoolArgs a{(const f32x4*)h, ids, n_items, B, L, E / 4, (f32x4*)cat, (uint32_t*)argmax};
   const int64_t n = (int64_t)B * a.ev;
   hipLaunchKernelGGL(curator_pool_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a,
                      ids ? pxr_status_word() : nullptr);
@@ -173,7 +152,7 @@ extern "C" int pxr_curator_pool_bwd_f32(const float* dcat, const uint8_t* argmax
   PXR_REQUIRE(B > 0 && (int64_t)B * (L + 2) <= (1ll << 28), "pxr_curator_pool_bwd_f32: bad batch size %d", B);
   PXR_REQUIRE((((uintptr_t)dcat | (uintptr_t)di | (uintptr_t)dact | (uintptr_t)dpre) & 15) == 0 && ((uintptr_t)argmax & 3) == 0,
               "pxr_curator_pool_bwd_f32: operands must be 16-byte aligned (argmax: 4-byte)");
-  CuratorPoolBwdArgs a{(const cu4*)dcat, (const uint32_t*)argmax, (const cu4*)di, (const cu4*)dact, B, L, E / 4, (cu4*)dpre};
+  CuratorPoolBwdArgs a{(const f32x4*)dcat, (const uint32_t*)argmax, (const f32x4*)di, (const f32x4*)dact, B, L, E / 4, (f32x4*)dpre};
   const int64_t n = (int64_t)B * (L + 2) * a.ev;
   hipLaunchKernelGGL(curator_pool_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   return pxr_check_launch("pxr_curator_pool_bwd_f32");

@@ -12,11 +12,9 @@
 // `part_len` edges (Zipf-popular items: tens of thousands) are cut into parts that go to waves of their own and are summed in
 // part order by a second launch -- the fixed-order idea of the split segment sums in embed_grad.hip.  No float atomics anywhere:
 // every output is bit-identical from run to run.
-#include "pxr_common.h"
+#include "pair_head.cuh"
 
 namespace pxr {
-
-typedef float lf4 __attribute__((ext_vector_type(4)));
 
 struct SpmmArgs {
   const int64_t* row_ptr;
@@ -28,17 +26,17 @@ struct SpmmArgs {
   const int32_t* split_part0; // [n_split + 1] first part of each split row
   const int32_t* part_owner;  // [n_parts] split-row index of each part
   int n_split, n_parts, part_len;
-  const lf4* x;
-  lf4* y;
-  const lf4* acc_in;
-  lf4* acc_out;
+  const f32x4* x;
+  f32x4* y;
+  const f32x4* acc_in;
+  f32x4* acc_out;
   float scale;
-  lf4* ws;                    // [n_parts, dv] part sums
+  f32x4* ws;                  // [n_parts, dv] part sums
   int32_t* status;
 };
 
 // out chunk c of row r: y = s; acc_out = (acc_in + s) * scale
-__device__ __forceinline__ void spmm_store(const SpmmArgs& a, int64_t r, int c, const lf4& s) {
+__device__ __forceinline__ void spmm_store(const SpmmArgs& a, int64_t r, int c, const f32x4& s) {
   const int64_t o = r * a.dv + c;
   if (a.y) a.y[o] = s;
   if (a.acc_out) a.acc_out[o] = (a.acc_in ? a.acc_in[o] + s : s) * a.scale;
@@ -69,9 +67,9 @@ __global__ void __launch_bounds__(256) lgcn_spmm_kernel(SpmmArgs a) {
     b = rb + k * a.part_len;
     e = b + a.part_len < re ? b + a.part_len : re;
   }
-  lf4 s[CH];
+  f32x4 s[CH];
 #pragma unroll
-  for (int h = 0; h < CH; ++h) s[h] = lf4{0.f, 0.f, 0.f, 0.f};
+  for (int h = 0; h < CH; ++h) s[h] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int64_t base = b; base < e; base += (int64_t)U * P) {
     int64_t cj[U];
     float wj[U];
@@ -81,22 +79,17 @@ __global__ void __launch_bounds__(256) lgcn_spmm_kernel(SpmmArgs a) {
       cj[u] = -1;
       wj[u] = 0.f;
       if (ed < e) {
-        int64_t c = a.col[ed];
-        if (c < 0 || c >= a.n_rows) {             // a neighbour outside the table: flag it, clamp the access
-          if (a.status && gl == 0) atomicOr(a.status, PXR_STATUS_BAD_INDEX);
-          c = c < 0 ? 0 : a.n_rows - 1;
-        }
-        cj[u] = c;
+        cj[u] = checked_id(a.col[ed], a.n_rows, a.status, gl == 0);     // a neighbour outside the table: flagged, clamped
         wj[u] = a.w[ed];
       }
     }
-    lf4 v[U][CH];
+    f32x4 v[U][CH];
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int h = 0; h < CH; ++h) {
         const int c = gl + h * 64;
-        v[u][h] = (cj[u] >= 0 && c < a.dv) ? a.x[cj[u] * a.dv + c] : lf4{0.f, 0.f, 0.f, 0.f};
+        v[u][h] = (cj[u] >= 0 && c < a.dv) ? a.x[cj[u] * a.dv + c] : f32x4{0.f, 0.f, 0.f, 0.f};
       }
 #pragma unroll
     for (int u = 0; u < U; ++u)
@@ -131,10 +124,10 @@ __global__ void __launch_bounds__(256) lgcn_spmm_combine_kernel(SpmmArgs a) {
   if (r < 0 || r >= a.n_rows) return;
   const int p0 = a.split_part0[j], p1 = a.split_part0[j + 1];
   for (int c = lane; c < a.dv; c += 64) {
-    lf4 s = lf4{0.f, 0.f, 0.f, 0.f};
+    f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
     int k = p0;
     for (; k + 4 <= p1; k += 4) {                 // four loads in flight, added in part order
-      lf4 t[4];
+      f32x4 t[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) t[u] = a.ws[(int64_t)(k + u) * a.dv + c];
 #pragma unroll
@@ -146,10 +139,9 @@ __global__ void __launch_bounds__(256) lgcn_spmm_combine_kernel(SpmmArgs a) {
 }
 
 // ---------------------------------------------------------------- pair head (lightgcn.py:70-78)
-// x_b = <u_b, i+_b> - <u_b, i-_b>; loss = -mean(1e-8 + log sigmoid(x_b)) -- the 1e-8 sits OUTSIDE the log -- so
-// d loss / d x_b = -(1 - sigmoid(x_b)) / B.  Both in forms that stay finite for any |x|.
+// x_b = <u_b, i+_b> - <u_b, i-_b> into the tail with the 1e-8 outside the log.  One wave per b.
 struct PairArgs {
-  const lf4* emb;             // E_final [n_users + n_items, dv]
+  const f32x4* emb;           // E_final [n_users + n_items, dv]
   int64_t n_users, n_items;
   int dv, B;
   const int64_t* user;        // [B]
@@ -161,51 +153,31 @@ struct PairArgs {
   int32_t* status;
 };
 
-__device__ __forceinline__ float dot4(const lf4& p, const lf4& q) { return p.x * q.x + p.y * q.y + p.z * q.z + p.w * q.w; }
-
-__device__ __forceinline__ int64_t lgcn_check_id(int64_t id, int64_t n, int32_t* status, bool flag_lane) {
-  if (id < 0 || id >= n) {
-    if (status && flag_lane) atomicOr(status, PXR_STATUS_BAD_INDEX);
-    return id < 0 ? 0 : n - 1;
-  }
-  return id;
-}
-
 __global__ void __launch_bounds__(256) lgcn_pair_fwd_kernel(PairArgs a) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= a.B) return;
-  const int64_t nu = lgcn_check_id(a.user[b], a.n_users, a.status, lane == 0);
-  const int64_t np = a.n_users + lgcn_check_id(a.item[2 * (int64_t)b], a.n_items, a.status, lane == 0);
-  const int64_t nn = a.n_users + lgcn_check_id(a.item[2 * (int64_t)b + 1], a.n_items, a.status, lane == 0);
-  float sp = 0.f, sn = 0.f;
-  for (int c = lane; c < a.dv; c += 64) {
-    const lf4 u = a.emb[nu * a.dv + c];
-    sp += dot4(u, a.emb[np * a.dv + c]);
-    sn += dot4(u, a.emb[nn * a.dv + c]);
-  }
-  sp = wave_sum(sp);
-  sn = wave_sum(sn);
+  const int64_t nu = checked_id(a.user[b], a.n_users, a.status, lane == 0);
+  const int64_t np = a.n_users + checked_id(a.item[2 * (int64_t)b], a.n_items, a.status, lane == 0);
+  const int64_t nn = a.n_users + checked_id(a.item[2 * (int64_t)b + 1], a.n_items, a.status, lane == 0);
+  float sp, sn;
+  pair_dots(a.emb + nu * a.dv, a.emb + np * a.dv, a.emb + nn * a.dv, a.dv, lane, sp, sn);
   if (lane != 0) return;
-  const float x = sp - sn;
-  const float ls = fminf(x, 0.f) - log1pf(expf(-fabsf(x)));                  // log sigmoid(x)
-  const float e = expf(-fabsf(x));
-  const float sneg = x >= 0.f ? e / (1.f + e) : 1.f / (1.f + e);            // 1 - sigmoid(x) = sigmoid(-x)
-  a.diff[b] = x;
-  a.lossrow[b] = -(1e-8f + ls);
-  a.coef[b] = -sneg / (float)a.B;
+  a.diff[b] = sp - sn;
+  bpr_tail_log_outside(sp - sn, a.B, a.lossrow[b], a.coef[b]);
   a.nodes[3 * b] = (int32_t)nu;
   a.nodes[3 * b + 1] = (int32_t)np;
   a.nodes[3 * b + 2] = (int32_t)nn;
 }
 
 // Gradient rows of E_final: occurrence o = 3b + t of node nodes[o] contributes c_b (i+ - i-) (t = 0, the user), c_b u (t = 1)
-// or -c_b u (t = 2).  One wave per occurrence; the FIRST occurrence of a node sums all of that node's occurrences in ascending
-// order and writes the row, the others exit -- a fixed order without a sort and without atomics.  3B ids stay in L1/L2.
+// or -c_b u (t = 2).  One wave per occurrence, pair_head.cuh's first-occurrence scheme; a later occurrence writes nothing.  The
+// scheme is spelled out here: through the shared walk and register row the compiler fuses the three forms' multiply-adds
+// differently per CH and the gradient moves by an ulp (profiles/pair_head/README.md).
 template <int CH>
-__global__ void __launch_bounds__(256) lgcn_pair_bwd_kernel(const lf4* __restrict__ emb, int dv, const int32_t* __restrict__ nodes,
+__global__ void __launch_bounds__(256) lgcn_pair_bwd_kernel(const f32x4* __restrict__ emb, int dv, const int32_t* __restrict__ nodes,
                                                             const float* __restrict__ coef, int n_occ, float gscale,
-                                                            const float* __restrict__ gscale_dev, lf4* __restrict__ grad) {
+                                                            const float* __restrict__ gscale_dev, f32x4* __restrict__ grad) {
   const int lane = threadIdx.x & 63;
   const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (o >= n_occ) return;
@@ -215,9 +187,9 @@ __global__ void __launch_bounds__(256) lgcn_pair_bwd_kernel(const lf4* __restric
     if (__ballot(k < o && nodes[k] == node)) return;
   }
   const float g = gscale * (gscale_dev ? gscale_dev[0] : 1.f);
-  lf4 s[CH];
+  f32x4 s[CH];
 #pragma unroll
-  for (int h = 0; h < CH; ++h) s[h] = lf4{0.f, 0.f, 0.f, 0.f};
+  for (int h = 0; h < CH; ++h) s[h] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int k0 = o; k0 < n_occ; k0 += 64) {
     const int k = k0 + lane;
     unsigned long long m = __ballot(k < n_occ && nodes[k] == node);
@@ -278,17 +250,13 @@ extern "C" int pxr_lgcn_spmm_f32(const int64_t* row_ptr, const int32_t* col, con
   a.row_ptr = row_ptr; a.col = col; a.w = w; a.n_rows = n_rows; a.dv = D / 4;
   a.split_row = split_row; a.split_part0 = split_part0; a.part_owner = part_owner;
   a.n_split = n_split; a.n_parts = n_parts; a.part_len = part_len;
-  a.x = (const lf4*)x; a.y = (lf4*)y; a.acc_in = (const lf4*)acc_in; a.acc_out = (lf4*)acc_out; a.scale = scale;
-  a.ws = (lf4*)ws; a.status = pxr_status_word();
-  const int CH = (a.dv + 63) / 64;
-  a.lg = CH > 1 ? 6 : lgcn_lanes_log2(a.dv);
+  a.x = (const f32x4*)x; a.y = (f32x4*)y; a.acc_in = (const f32x4*)acc_in; a.acc_out = (f32x4*)acc_out; a.scale = scale;
+  a.ws = (f32x4*)ws; a.status = pxr_status_word();
+  a.lg = lgcn_lanes_log2(a.dv);                                    // dv > 64: all 64 lanes, CH chunks each
   hipStream_t st = (hipStream_t)stream;
-  switch (CH) {
-    case 1: hipLaunchKernelGGL(lgcn_spmm_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-    case 2: hipLaunchKernelGGL(lgcn_spmm_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-    case 3: case 4: hipLaunchKernelGGL(lgcn_spmm_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL(lgcn_spmm_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-  }
+  dispatch_ch<8>(a.dv, [&](auto ch) {
+    hipLaunchKernelGGL(lgcn_spmm_kernel<decltype(ch)::value>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  });
   if (n_split > 0)
     hipLaunchKernelGGL(lgcn_spmm_combine_kernel, dim3((unsigned)((n_split + 3) / 4)), dim3(256), 0, st, a);
   return pxr_check_launch("pxr_lgcn_spmm_f32");
@@ -302,7 +270,7 @@ extern "C" int pxr_lgcn_pair_fwd_f32(const float* emb, int64_t n_users, int64_t 
   PXR_REQUIRE(D > 0 && D % 4 == 0, "pxr_lgcn_pair_fwd_f32: need D %% 4 == 0 (D=%d)", D);
   PXR_REQUIRE(B > 0 && B <= (1 << 28), "pxr_lgcn_pair_fwd_f32: bad batch size %d", B);
   PairArgs a{};
-  a.emb = (const lf4*)emb; a.n_users = n_users; a.n_items = n_items; a.dv = D / 4; a.B = B;
+  a.emb = (const f32x4*)emb; a.n_users = n_users; a.n_items = n_items; a.dv = D / 4; a.B = B;
   a.user = user; a.item = item; a.diff = diff; a.coef = coef; a.lossrow = lossrow; a.nodes = nodes;
   a.status = pxr_status_word();
   hipStream_t st = (hipStream_t)stream;
@@ -323,14 +291,10 @@ extern "C" int pxr_lgcn_pair_bwd_f32(const float* emb, int64_t n_nodes, int D, c
     pxr_set_error("pxr_lgcn_pair_bwd_f32: memset failed");
     return PXR_ERR_LAUNCH;
   }
-  const int dv = D / 4, n_occ = 3 * B, CH = (dv + 63) / 64;
-  const dim3 g((unsigned)((n_occ + 3) / 4));
-  const lf4* e = (const lf4*)emb;
-  switch (CH) {
-    case 1: hipLaunchKernelGGL(lgcn_pair_bwd_kernel<1>, g, dim3(256), 0, st, e, dv, nodes, coef, n_occ, grad_scale, grad_scale_dev, (lf4*)grad); break;
-    case 2: hipLaunchKernelGGL(lgcn_pair_bwd_kernel<2>, g, dim3(256), 0, st, e, dv, nodes, coef, n_occ, grad_scale, grad_scale_dev, (lf4*)grad); break;
-    case 3: case 4: hipLaunchKernelGGL(lgcn_pair_bwd_kernel<4>, g, dim3(256), 0, st, e, dv, nodes, coef, n_occ, grad_scale, grad_scale_dev, (lf4*)grad); break;
-    default: hipLaunchKernelGGL(lgcn_pair_bwd_kernel<8>, g, dim3(256), 0, st, e, dv, nodes, coef, n_occ, grad_scale, grad_scale_dev, (lf4*)grad); break;
-  }
+  const int dv = D / 4, n_occ = 3 * B;
+  dispatch_ch<8>(dv, [&](auto ch) {
+    hipLaunchKernelGGL(lgcn_pair_bwd_kernel<decltype(ch)::value>, dim3((unsigned)((n_occ + 3) / 4)), dim3(256), 0, st,
+                       (const f32x4*)emb, dv, nodes, coef, n_occ, grad_scale, grad_scale_dev, (f32x4*)grad);
+  });
   return pxr_check_launch("pxr_lgcn_pair_bwd_f32");
 }

@@ -6,16 +6,11 @@
 //
 // A step's occurrences are laid out as rows[3B] = [user row of b for b < B | item rows of item.view(-1): (i+_b, i-_b) for b < B],
 // so the user tower reads rows[0:B] and the item tower rows[B:3B] in item.view(-1) order.  The sparse table gradient has one slot
-// per occurrence: the FIRST occurrence of a row sums all of that row's occurrences in ascending order and writes (row, sum); the
-// slots of the other occurrences are written as (0, zeros), the empty slots of a non-compacted list.  No float atomics: every
-// output is bit-identical from run to run.
-#include "pxr_common.h"
+// per occurrence, summed by pair_head.cuh's first-occurrence scheme: (row, sum) in the slot of a row's first occurrence, (0, zeros)
+// -- the empty slot of a non-compacted list -- in the others.
+#include "pair_head.cuh"
 
 namespace pxr {
-
-typedef float mf4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float mf_dot4(const mf4& p, const mf4& q) { return p.x * q.x + p.y * q.y + p.z * q.z + p.w * q.w; }
 
 // rows[o] of occurrence o (layout above); an id outside its range flags the status word and is clamped
 __global__ void __launch_bounds__(256) mf_pair_rows_kernel(const int64_t* __restrict__ user, const int64_t* __restrict__ item, int B,
@@ -25,28 +20,23 @@ __global__ void __launch_bounds__(256) mf_pair_rows_kernel(const int64_t* __rest
   const int64_t n_occ = item ? 3 * (int64_t)B : (int64_t)B;
   if (o >= n_occ) return;
   const bool is_user = o < B;
-  int64_t id = is_user ? user[o] : item[o - B];
-  const int64_t n = is_user ? n_users : n_items;
-  if (id < 0 || id >= n) {
-    if (status) atomicOr(status, PXR_STATUS_BAD_INDEX);
-    id = id < 0 ? 0 : n - 1;
-  }
+  const int64_t id = checked_id(is_user ? user[o] : item[o - B], is_user ? n_users : n_items, status, true);
   rows[o] = 1 + (is_user ? 0 : n_users) + id;
 }
 
 // Feature rows of sample b: the user's, the positive's and the negative's.  rows != NULL: rows of the table (ufeat == ifeat);
 // rows == NULL: the towers' outputs, user b at ufeat row b, item j of item.view(-1) at ifeat row j.
 struct MfPairArgs {
-  const mf4* ufeat;
-  const mf4* ifeat;
+  const f32x4* ufeat;
+  const f32x4* ifeat;
   const int64_t* rows;
   int hv, B;                   // H / 4; batch
   float* coef;                 // [B] d loss / d x_b
   float* lossrow;              // [B]
   float gscale;
   const float* gscale_dev;
-  mf4* du;                     // [B, hv]   (tower backward)
-  mf4* di;                     // [2B, hv]
+  f32x4* du;                   // [B, hv]   (tower backward)
+  f32x4* di;                   // [2B, hv]
 };
 
 __device__ __forceinline__ void mf_pair_rows_of(const MfPairArgs& a, int b, int64_t& ru, int64_t& rp, int64_t& rn) {
@@ -61,29 +51,16 @@ __device__ __forceinline__ void mf_pair_rows_of(const MfPairArgs& a, int b, int6
   }
 }
 
-// x_b = <u_b, i+_b> - <u_b, i-_b>; loss = -mean(1e-8 + log sigmoid(x_b)) (the 1e-8 OUTSIDE the log, mf.py forward), so
-// d loss / d x_b = -(1 - sigmoid(x_b)) / B -- both in forms that stay finite for any |x| (lightgcn.hip's head).  One wave per b.
+// x_b = <u_b, i+_b> - <u_b, i-_b> into the tail with the 1e-8 outside the log (mf.py forward).  One wave per b.
 __global__ void __launch_bounds__(256) mf_pair_fwd_kernel(MfPairArgs a) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= a.B) return;
   int64_t ru, rp, rn;
   mf_pair_rows_of(a, b, ru, rp, rn);
-  float sp = 0.f, sn = 0.f;
-  for (int c = lane; c < a.hv; c += 64) {
-    const mf4 u = a.ufeat[ru * a.hv + c];
-    sp += mf_dot4(u, a.ifeat[rp * a.hv + c]);
-    sn += mf_dot4(u, a.ifeat[rn * a.hv + c]);
-  }
-  sp = wave_sum(sp);
-  sn = wave_sum(sn);
-  if (lane != 0) return;
-  const float x = sp - sn;
-  const float e = expf(-fabsf(x));
-  const float ls = fminf(x, 0.f) - log1pf(e);                               // log sigmoid(x)
-  const float sneg = x >= 0.f ? e / (1.f + e) : 1.f / (1.f + e);            // 1 - sigmoid(x) = sigmoid(-x)
-  a.lossrow[b] = -(1e-8f + ls);
-  a.coef[b] = -sneg / (float)a.B;
+  float sp, sn;
+  pair_dots(a.ufeat + ru * a.hv, a.ifeat + rp * a.hv, a.ifeat + rn * a.hv, a.hv, lane, sp, sn);
+  if (lane == 0) bpr_tail_log_outside(sp - sn, a.B, a.lossrow[b], a.coef[b]);
 }
 
 // Tower form of the head's backward: d u_b = c_b (i+_b - i-_b), d i+_b = c_b u_b, d i-_b = -c_b u_b (dense, one wave per b).
@@ -94,7 +71,7 @@ __global__ void __launch_bounds__(256) mf_pair_bwd_kernel(MfPairArgs a) {
   const float c = a.coef[b] * a.gscale * (a.gscale_dev ? a.gscale_dev[0] : 1.f);
   const int64_t ru = b, rp = 2 * (int64_t)b, rn = rp + 1;
   for (int ch = lane; ch < a.hv; ch += 64) {
-    const mf4 u = a.ufeat[ru * a.hv + ch], p = a.ifeat[rp * a.hv + ch], n = a.ifeat[rn * a.hv + ch];
+    const f32x4 u = a.ufeat[ru * a.hv + ch], p = a.ifeat[rp * a.hv + ch], n = a.ifeat[rn * a.hv + ch];
     a.du[ru * a.hv + ch] = c * (p - n);
     a.di[rp * a.hv + ch] = c * u;
     a.di[rn * a.hv + ch] = -c * u;
@@ -105,15 +82,15 @@ __global__ void __launch_bounds__(256) mf_pair_bwd_kernel(MfPairArgs a) {
 //   occ != NULL (towers): occ[k, :], the first layer's input gradient of that occurrence;
 //   occ == NULL: the head's formula on the table rows (t = user: c_b (i+ - i-); positive: c_b u; negative: -c_b u).
 struct MfTableGradArgs {
-  const mf4* table;
+  const f32x4* table;
   const int64_t* rows;
   const float* coef;
-  const mf4* occ;
+  const f32x4* occ;
   int dv, B;
   float gscale;
   const float* gscale_dev;
   int64_t* sp_idx;             // [3B]
-  mf4* sp_rows;                // [3B, dv]
+  f32x4* sp_rows;              // [3B, dv]
   int32_t* sp_n;
 };
 
@@ -125,68 +102,28 @@ __global__ void __launch_bounds__(256) mf_table_grad_kernel(MfTableGradArgs a) {
   if (o == 0 && lane == 0) a.sp_n[0] = n_occ;
   if (o >= n_occ) return;
   const int64_t node = a.rows[o];
-  bool first = true;
-  for (int k0 = 0; k0 < o && first; k0 += 64) {
-    const int k = k0 + lane;
-    if (__ballot(k < o && a.rows[k] == node)) first = false;
-  }
-  mf4* dst = a.sp_rows + (int64_t)o * a.dv;
-  if (!first) {
-#pragma unroll
-    for (int h = 0; h < CH; ++h) {
-      const int ch = lane + h * 64;
-      if (ch < a.dv) dst[ch] = mf4{0.f, 0.f, 0.f, 0.f};
-    }
-    if (lane == 0) a.sp_idx[o] = 0;
-    return;
-  }
-  const float g = a.gscale * (a.gscale_dev ? a.gscale_dev[0] : 1.f);
-  mf4 s[CH];
-#pragma unroll
-  for (int h = 0; h < CH; ++h) s[h] = mf4{0.f, 0.f, 0.f, 0.f};
-  for (int k0 = o; k0 < n_occ; k0 += 64) {
-    const int k = k0 + lane;
-    unsigned long long m = __ballot(k < n_occ && a.rows[k] == node);
-    while (m) {
-      const int kk = k0 + __builtin_ctzll(m);
-      m &= m - 1;
+  const bool first = is_first_occurrence(a.rows, 0, o, node, lane);
+  f32x4 s[CH];
+  row_zero(s);
+  if (first) {
+    const float g = grad_scale(a.gscale, a.gscale_dev);
+    for_each_occurrence(a.rows, o, n_occ, node, lane, [&](int kk) {
       if (a.occ) {
-        const mf4* src = a.occ + (int64_t)kk * a.dv;
-#pragma unroll
-        for (int h = 0; h < CH; ++h) {
-          const int ch = lane + h * 64;
-          if (ch < a.dv) s[h] += src[ch];
-        }
-        continue;
+        row_add_scaled(s, 1.f, a.occ + (int64_t)kk * a.dv, a.dv, lane);      // 1 x is x: the plain sum of the occurrences' rows
+        return;
       }
       const bool is_user = kk < a.B;
       const int b = is_user ? kk : (kk - a.B) >> 1;
       const float c = a.coef[b] * g;
-      if (is_user) {
-        const mf4* p = a.table + a.rows[a.B + 2 * (int64_t)b] * a.dv;
-        const mf4* n = a.table + a.rows[a.B + 2 * (int64_t)b + 1] * a.dv;
-#pragma unroll
-        for (int h = 0; h < CH; ++h) {
-          const int ch = lane + h * 64;
-          if (ch < a.dv) s[h] += c * (p[ch] - n[ch]);
-        }
-      } else {
-        const float cs = ((kk - a.B) & 1) ? -c : c;
-        const mf4* u = a.table + a.rows[b] * a.dv;
-#pragma unroll
-        for (int h = 0; h < CH; ++h) {
-          const int ch = lane + h * 64;
-          if (ch < a.dv) s[h] += cs * u[ch];
-        }
-      }
-    }
+      if (is_user)
+        row_add_scaled_diff(s, c, a.table + a.rows[a.B + 2 * (int64_t)b] * a.dv, a.table + a.rows[a.B + 2 * (int64_t)b + 1] * a.dv,
+                            a.dv, lane);
+      else
+        row_add_scaled(s, ((kk - a.B) & 1) ? -c : c, a.table + a.rows[b] * a.dv, a.dv, lane);
+    });
   }
-#pragma unroll
-  for (int h = 0; h < CH; ++h) {
-    const int ch = lane + h * 64;
-    if (ch < a.dv) dst[ch] = s[h];
-  }
-  if (lane == 0) a.sp_idx[o] = node;
+  row_store(s, a.sp_rows + (int64_t)o * a.dv, a.dv, lane);
+  if (lane == 0) a.sp_idx[o] = first ? node : 0;
 }
 
 // ---------------------------------------------------------------- BatchNorm1d + tanh over x [R, H] (MLPLayers: Linear -> BN -> Tanh)
@@ -195,10 +132,10 @@ __global__ void __launch_bounds__(256) mf_table_grad_kernel(MfTableGradArgs a) {
 constexpr int BN_CC = 8, BN_RL = 32;
 
 struct BnArgs {
-  const mf4* x;                // [R, hv] (the Linear output)
-  const mf4* y;                // [R, hv] (the tanh output: backward)
-  const mf4* dy;               // [R, hv]
-  mf4* out;                    // y (forward / eval) or dx (backward)
+  const f32x4* x;              // [R, hv] (the Linear output)
+  const f32x4* y;              // [R, hv] (the tanh output: backward)
+  const f32x4* dy;             // [R, hv]
+  f32x4* out;                  // y (forward / eval) or dx (backward)
   const float* gamma;
   const float* beta;
   float* mean;                 // [H] batch mean (saved by the forward, read by the backward)
@@ -212,55 +149,55 @@ struct BnArgs {
   float eps, momentum;
 };
 
-__device__ __forceinline__ mf4 bn_col_reduce(mf4 s, mf4 (*red)[BN_CC], int rl, int cc) {
+__device__ __forceinline__ f32x4 bn_col_reduce(f32x4 s, f32x4 (*red)[BN_CC], int rl, int cc) {
   __syncthreads();                                   // red may still be read by the previous reduction
   red[rl][cc] = s;
   __syncthreads();
-  mf4 t = red[0][cc];
+  f32x4 t = red[0][cc];
 #pragma unroll
   for (int k = 1; k < BN_RL; ++k) t += red[k][cc];
   return t;
 }
 
-__device__ __forceinline__ mf4 ld4(const float* p, int c4) { return reinterpret_cast<const mf4*>(p)[c4]; }
+__device__ __forceinline__ f32x4 ld4(const float* p, int c4) { return reinterpret_cast<const f32x4*>(p)[c4]; }
 
-__device__ __forceinline__ mf4 tanh4(const mf4& z) { return mf4{tanhf(z.x), tanhf(z.y), tanhf(z.z), tanhf(z.w)}; }
+__device__ __forceinline__ f32x4 tanh4(const f32x4& z) { return f32x4{tanhf(z.x), tanhf(z.y), tanhf(z.z), tanhf(z.w)}; }
 
 // training forward: batch statistics (mean, then the centred sum of squares), y = tanh(gamma xhat + beta), running statistics
 // updated with the unbiased variance, num_batches_tracked += 1
 __global__ void __launch_bounds__(256) mf_bn_tanh_fwd_kernel(BnArgs a) {
-  __shared__ mf4 red[BN_RL][BN_CC];
+  __shared__ f32x4 red[BN_RL][BN_CC];
   const int cc = threadIdx.x % BN_CC, rl = threadIdx.x / BN_CC;
   const int c4 = blockIdx.x * BN_CC + cc;
   const bool ok = c4 < a.hv;
   const float inv_r = 1.f / (float)a.R;
-  mf4 s = mf4{0.f, 0.f, 0.f, 0.f};
+  f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
   if (ok)
     for (int r = rl; r < a.R; r += BN_RL) s += a.x[(int64_t)r * a.hv + c4];
-  const mf4 mean = bn_col_reduce(s, red, rl, cc) * inv_r;
-  s = mf4{0.f, 0.f, 0.f, 0.f};
+  const f32x4 mean = bn_col_reduce(s, red, rl, cc) * inv_r;
+  s = f32x4{0.f, 0.f, 0.f, 0.f};
   if (ok)
     for (int r = rl; r < a.R; r += BN_RL) {
-      const mf4 d = a.x[(int64_t)r * a.hv + c4] - mean;
+      const f32x4 d = a.x[(int64_t)r * a.hv + c4] - mean;
       s += d * d;
     }
-  const mf4 ss = bn_col_reduce(s, red, rl, cc);
-  const mf4 var = ss * inv_r;
-  const mf4 rstd = mf4{1.f / sqrtf(var.x + a.eps), 1.f / sqrtf(var.y + a.eps), 1.f / sqrtf(var.z + a.eps),
+  const f32x4 ss = bn_col_reduce(s, red, rl, cc);
+  const f32x4 var = ss * inv_r;
+  const f32x4 rstd = f32x4{1.f / sqrtf(var.x + a.eps), 1.f / sqrtf(var.y + a.eps), 1.f / sqrtf(var.z + a.eps),
                        1.f / sqrtf(var.w + a.eps)};
   if (!ok) return;
   if (rl == 0) {
-    reinterpret_cast<mf4*>(a.mean)[c4] = mean;
-    reinterpret_cast<mf4*>(a.rstd)[c4] = rstd;
+    reinterpret_cast<f32x4*>(a.mean)[c4] = mean;
+    reinterpret_cast<f32x4*>(a.rstd)[c4] = rstd;
     const float mo = a.momentum;
-    const mf4 uvar = ss * (1.f / (float)(a.R - 1));
-    mf4* rm = reinterpret_cast<mf4*>(a.run_mean) + c4;
-    mf4* rv = reinterpret_cast<mf4*>(a.run_var) + c4;
+    const f32x4 uvar = ss * (1.f / (float)(a.R - 1));
+    f32x4* rm = reinterpret_cast<f32x4*>(a.run_mean) + c4;
+    f32x4* rv = reinterpret_cast<f32x4*>(a.run_var) + c4;
     *rm = (1.f - mo) * *rm + mo * mean;
     *rv = (1.f - mo) * *rv + mo * uvar;
     if (c4 == 0 && a.n_tracked) a.n_tracked[0] += 1;
   }
-  const mf4 g = ld4(a.gamma, c4) * rstd, bt = ld4(a.beta, c4);
+  const f32x4 g = ld4(a.gamma, c4) * rstd, bt = ld4(a.beta, c4);
   for (int r = rl; r < a.R; r += BN_RL) {
     const int64_t o = (int64_t)r * a.hv + c4;
     a.out[o] = tanh4((a.x[o] - mean) * g + bt);
@@ -270,35 +207,35 @@ __global__ void __launch_bounds__(256) mf_bn_tanh_fwd_kernel(BnArgs a) {
 // backward through tanh and the batch normalisation: dz = dy (1 - y^2), dbeta = sum dz, dgamma = sum dz xhat,
 // dx = gamma rstd / R (R dz - dbeta - xhat dgamma)
 __global__ void __launch_bounds__(256) mf_bn_tanh_bwd_kernel(BnArgs a) {
-  __shared__ mf4 red[BN_RL][BN_CC];
+  __shared__ f32x4 red[BN_RL][BN_CC];
   const int cc = threadIdx.x % BN_CC, rl = threadIdx.x / BN_CC;
   const int c4 = blockIdx.x * BN_CC + cc;
   const bool ok = c4 < a.hv;
-  const mf4 mean = ok ? ld4(a.mean, c4) : mf4{0.f, 0.f, 0.f, 0.f};
-  const mf4 rstd = ok ? ld4(a.rstd, c4) : mf4{0.f, 0.f, 0.f, 0.f};
-  mf4 s1 = mf4{0.f, 0.f, 0.f, 0.f}, s2 = s1;
+  const f32x4 mean = ok ? ld4(a.mean, c4) : f32x4{0.f, 0.f, 0.f, 0.f};
+  const f32x4 rstd = ok ? ld4(a.rstd, c4) : f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 s1 = f32x4{0.f, 0.f, 0.f, 0.f}, s2 = s1;
   if (ok)
     for (int r = rl; r < a.R; r += BN_RL) {
       const int64_t o = (int64_t)r * a.hv + c4;
-      const mf4 y = a.y[o];
-      const mf4 dz = a.dy[o] * (1.f - y * y);
+      const f32x4 y = a.y[o];
+      const f32x4 dz = a.dy[o] * (1.f - y * y);
       s1 += dz;
       s2 += dz * ((a.x[o] - mean) * rstd);
     }
-  const mf4 db = bn_col_reduce(s1, red, rl, cc);
-  const mf4 dg = bn_col_reduce(s2, red, rl, cc);
+  const f32x4 db = bn_col_reduce(s1, red, rl, cc);
+  const f32x4 dg = bn_col_reduce(s2, red, rl, cc);
   if (!ok) return;
   if (rl == 0) {
-    reinterpret_cast<mf4*>(a.dbeta)[c4] = db;
-    reinterpret_cast<mf4*>(a.dgamma)[c4] = dg;
+    reinterpret_cast<f32x4*>(a.dbeta)[c4] = db;
+    reinterpret_cast<f32x4*>(a.dgamma)[c4] = dg;
   }
   const float fr = (float)a.R;
-  const mf4 k = ld4(a.gamma, c4) * rstd * (1.f / fr);
+  const f32x4 k = ld4(a.gamma, c4) * rstd * (1.f / fr);
   for (int r = rl; r < a.R; r += BN_RL) {
     const int64_t o = (int64_t)r * a.hv + c4;
-    const mf4 y = a.y[o];
-    const mf4 dz = a.dy[o] * (1.f - y * y);
-    const mf4 xh = (a.x[o] - mean) * rstd;
+    const f32x4 y = a.y[o];
+    const f32x4 dz = a.dy[o] * (1.f - y * y);
+    const f32x4 xh = (a.x[o] - mean) * rstd;
     a.out[o] = k * (fr * dz - db - xh * dg);
   }
 }
@@ -308,8 +245,8 @@ __global__ void __launch_bounds__(256) mf_bn_tanh_eval_kernel(BnArgs a) {
   const int64_t n = (int64_t)a.R * a.hv;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
     const int c4 = (int)(e % a.hv);
-    const mf4 rv = ld4(a.run_var, c4);
-    const mf4 rs = mf4{1.f / sqrtf(rv.x + a.eps), 1.f / sqrtf(rv.y + a.eps), 1.f / sqrtf(rv.z + a.eps), 1.f / sqrtf(rv.w + a.eps)};
+    const f32x4 rv = ld4(a.run_var, c4);
+    const f32x4 rs = f32x4{1.f / sqrtf(rv.x + a.eps), 1.f / sqrtf(rv.y + a.eps), 1.f / sqrtf(rv.z + a.eps), 1.f / sqrtf(rv.w + a.eps)};
     a.out[e] = tanh4((a.x[e] - ld4(a.run_mean, c4)) * (ld4(a.gamma, c4) * rs) + ld4(a.beta, c4));
   }
 }
@@ -336,7 +273,7 @@ extern "C" int pxr_mf_pair_fwd_f32(const float* ufeat, const float* ifeat, const
   PXR_REQUIRE(B > 0 && B <= (1 << 28), "pxr_mf_pair_fwd_f32: bad batch size %d", B);
   PXR_REQUIRE((((uintptr_t)ufeat | (uintptr_t)ifeat) & 15) == 0, "pxr_mf_pair_fwd_f32: features must be 16-byte aligned");
   MfPairArgs a{};
-  a.ufeat = (const mf4*)ufeat; a.ifeat = (const mf4*)ifeat; a.rows = rows; a.hv = H / 4; a.B = B;
+  a.ufeat = (const f32x4*)ufeat; a.ifeat = (const f32x4*)ifeat; a.rows = rows; a.hv = H / 4; a.B = B;
   a.coef = coef; a.lossrow = lossrow;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(mf_pair_fwd_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a);
@@ -353,8 +290,8 @@ extern "C" int pxr_mf_pair_bwd_f32(const float* ufeat, const float* ifeat, const
   PXR_REQUIRE((((uintptr_t)ufeat | (uintptr_t)ifeat | (uintptr_t)du | (uintptr_t)di) & 15) == 0,
               "pxr_mf_pair_bwd_f32: operands must be 16-byte aligned");
   MfPairArgs a{};
-  a.ufeat = (const mf4*)ufeat; a.ifeat = (const mf4*)ifeat; a.hv = H / 4; a.B = B; a.coef = (float*)coef;
-  a.gscale = grad_scale; a.gscale_dev = grad_scale_dev; a.du = (mf4*)du; a.di = (mf4*)di;
+  a.ufeat = (const f32x4*)ufeat; a.ifeat = (const f32x4*)ifeat; a.hv = H / 4; a.B = B; a.coef = (float*)coef;
+  a.gscale = grad_scale; a.gscale_dev = grad_scale_dev; a.du = (f32x4*)du; a.di = (f32x4*)di;
   hipLaunchKernelGGL(mf_pair_bwd_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
   return pxr_check_launch("pxr_mf_pair_bwd_f32");
 }
@@ -370,16 +307,12 @@ extern "C" int pxr_mf_table_grad_f32(const float* table, int64_t n_table, int D,
               3 * (long long)B);
   PXR_REQUIRE(occ || n_table > 1, "pxr_mf_table_grad_f32: bad table size");
   MfTableGradArgs a{};
-  a.table = (const mf4*)table; a.rows = rows; a.coef = coef; a.occ = (const mf4*)occ; a.dv = D / 4; a.B = B;
-  a.gscale = grad_scale; a.gscale_dev = grad_scale_dev; a.sp_idx = sp_idx; a.sp_rows = (mf4*)sp_rows; a.sp_n = sp_n;
-  const int CH = (a.dv + 63) / 64;
-  const dim3 g((unsigned)((3 * B + 3) / 4));
-  hipStream_t st = (hipStream_t)stream;
-  if (CH <= 1) hipLaunchKernelGGL(mf_table_grad_kernel<1>, g, dim3(256), 0, st, a);
-  else if (CH <= 2) hipLaunchKernelGGL(mf_table_grad_kernel<2>, g, dim3(256), 0, st, a);
-  else if (CH <= 4) hipLaunchKernelGGL(mf_table_grad_kernel<4>, g, dim3(256), 0, st, a);
-  else if (CH <= 8) hipLaunchKernelGGL(mf_table_grad_kernel<8>, g, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(mf_table_grad_kernel<16>, g, dim3(256), 0, st, a);
+  a.table = (const f32x4*)table; a.rows = rows; a.coef = coef; a.occ = (const f32x4*)occ; a.dv = D / 4; a.B = B;
+  a.gscale = grad_scale; a.gscale_dev = grad_scale_dev; a.sp_idx = sp_idx; a.sp_rows = (f32x4*)sp_rows; a.sp_n = sp_n;
+  dispatch_ch<16>(a.dv, [&](auto ch) {
+    hipLaunchKernelGGL(mf_table_grad_kernel<decltype(ch)::value>, dim3((unsigned)((3 * B + 3) / 4)), dim3(256), 0,
+                       (hipStream_t)stream, a);
+  });
   return pxr_check_launch("pxr_mf_table_grad_f32");
 }
 
@@ -396,7 +329,7 @@ extern "C" int pxr_mf_bn_tanh_fwd_f32(const float* x, int R, int H, const float*
   PXR_REQUIRE(R >= 2, "pxr_mf_bn_tanh_fwd_f32: training statistics need more than one row (R=%d)", R);
   PXR_REQUIRE(x != y, "pxr_mf_bn_tanh_fwd_f32: y must not alias x (the backward reads both)");
   BnArgs a{};
-  a.x = (const mf4*)x; a.out = (mf4*)y; a.gamma = gamma; a.beta = beta; a.mean = mean; a.rstd = rstd;
+  a.x = (const f32x4*)x; a.out = (f32x4*)y; a.gamma = gamma; a.beta = beta; a.mean = mean; a.rstd = rstd;
   a.run_mean = running_mean; a.run_var = running_var; a.n_tracked = num_batches_tracked; a.R = R; a.hv = H / 4;
   a.eps = eps; a.momentum = momentum;
   const int hv = H / 4;
@@ -410,7 +343,7 @@ extern "C" int pxr_mf_bn_tanh_bwd_f32(const float* dy, const float* x, const flo
   if (int rc = mf_bn_shape_ok("pxr_mf_bn_tanh_bwd_f32", R, H)) return rc;
   PXR_REQUIRE(dx != dy && dx != x && dx != y, "pxr_mf_bn_tanh_bwd_f32: dx must not alias an input (columns are read twice)");
   BnArgs a{};
-  a.x = (const mf4*)x; a.y = (const mf4*)y; a.dy = (const mf4*)dy; a.out = (mf4*)dx; a.gamma = gamma;
+  a.x = (const f32x4*)x; a.y = (const f32x4*)y; a.dy = (const f32x4*)dy; a.out = (f32x4*)dx; a.gamma = gamma;
   a.mean = (float*)mean; a.rstd = (float*)rstd; a.dgamma = dgamma; a.dbeta = dbeta; a.R = R; a.hv = H / 4;
   const int hv = H / 4;
   hipLaunchKernelGGL(mf_bn_tanh_bwd_kernel, dim3((unsigned)((hv + BN_CC - 1) / BN_CC)), dim3(256), 0, (hipStream_t)stream, a);
@@ -423,7 +356,7 @@ extern "C" int pxr_mf_bn_tanh_eval_f32(const float* x, int64_t R, int H, const f
   PXR_REQUIRE(R > 0 && R < (1ll << 31) && H > 0 && H % 4 == 0 && H <= 4096,
               "pxr_mf_bn_tanh_eval_f32: need 0 < R < 2^31 and H %% 4 == 0, 0 < H <= 4096 (H=%d)", H);
   BnArgs a{};
-  a.x = (const mf4*)x; a.out = (mf4*)y; a.gamma = gamma; a.beta = beta; a.run_mean = (float*)running_mean;
+  a.x = (const f32x4*)x; a.out = (f32x4*)y; a.gamma = gamma; a.beta = beta; a.run_mean = (float*)running_mean;
   a.run_var = (float*)running_var; a.R = (int)R; a.hv = H / 4; a.eps = eps;
   int64_t blocks = (R * (H / 4) + 255) / 256;
   if (blocks > 256 * 64) blocks = 256 * 64;

@@ -8,11 +8,10 @@
 //   edges  = x[i] -> x[i+1] for i + 1 < s, s = the first j >= 1 with x[j] == 0 (the collate's `break`); a repeat counts once
 //   A      = [A_in | A_out] [L, 2L]: A_in[v][u] = edge(u, v) / indeg(v), A_out[u][v] = edge(u, v) / outdeg(u) (degree 0 -> 1)
 // A padding node has no edges: zero rows and columns, so no output it does not own changes.
-#include "pxr_common.h"
+#include "pair_head.cuh"
 
 namespace pxr {
 
-typedef float sf4 __attribute__((ext_vector_type(4)));
 
 constexpr int SRGNN_MAX_L = 64;
 
@@ -42,14 +41,7 @@ __global__ void __launch_bounds__(256) srgnn_graph_kernel(GraphArgs a) {
   const int L = a.L;
   const bool live = lane < L;
   int x = 0;
-  if (live) {
-    int64_t v = a.seq[b * L + lane];
-    if (v < 0 || v >= a.n_items) {                       // an id outside the table: flag it, clamp it
-      if (a.status) atomicOr(a.status, PXR_STATUS_BAD_INDEX);
-      v = v < 0 ? 0 : a.n_items - 1;
-    }
-    x = (int)v;
-  }
+  if (live) x = (int)checked_id(a.seq[b * L + lane], a.n_items, a.status, true);
   // first occurrences, then rank = number of distinct ids below x (np.unique order)
   bool first = live;
   for (int j = 0; j < L; ++j) {
@@ -110,17 +102,17 @@ __global__ void __launch_bounds__(256) srgnn_prop_kernel(const float* __restrict
   for (int i = threadIdx.x; i < 2 * L * L; i += blockDim.x) sA[i] = Ab[i];
   __syncthreads();
   const int dv = D / 4, n_chunks = 2 * dv;
-  const sf4* xb = reinterpret_cast<const sf4*>(x + b * (int64_t)L * 2 * D);
-  sf4* yb = reinterpret_cast<sf4*>(y + b * (int64_t)L * 2 * D);
+  const f32x4* xb = reinterpret_cast<const f32x4*>(x + b * (int64_t)L * 2 * D);
+  f32x4* yb = reinterpret_cast<f32x4*>(y + b * (int64_t)L * 2 * D);
   for (int q = threadIdx.x; q < n_chunks; q += blockDim.x) {
     const int h = q >= dv ? 1 : 0;
-    const sf4 bv = bias ? reinterpret_cast<const sf4*>(bias)[q] : sf4{0.f, 0.f, 0.f, 0.f};
+    const f32x4 bv = bias ? reinterpret_cast<const f32x4*>(bias)[q] : f32x4{0.f, 0.f, 0.f, 0.f};
     for (int i0 = 0; i0 < L; i0 += 8) {
-      sf4 acc[8];
+      f32x4 acc[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) acc[k] = sf4{0.f, 0.f, 0.f, 0.f};
+      for (int k = 0; k < 8; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
       for (int j = 0; j < L; ++j) {
-        const sf4 xv = xb[(int64_t)j * n_chunks + q];
+        const f32x4 xv = xb[(int64_t)j * n_chunks + q];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const int i = i0 + k;
@@ -151,11 +143,10 @@ __device__ __forceinline__ int srgnn_last(const int64_t* mask, int L) {
   return (int)(last < 0 ? 0 : (last >= L ? L - 1 : last));
 }
 
-__device__ __forceinline__ sf4 sigmoid4(const sf4& v) {
-  return sf4{1.f / (1.f + expf(-v.x)), 1.f / (1.f + expf(-v.y)), 1.f / (1.f + expf(-v.z)), 1.f / (1.f + expf(-v.w))};
+__device__ __forceinline__ f32x4 sigmoid4(const f32x4& v) {
+  return f32x4{1.f / (1.f + expf(-v.x)), 1.f / (1.f + expf(-v.y)), 1.f / (1.f + expf(-v.z)), 1.f / (1.f + expf(-v.w))};
 }
 
-__device__ __forceinline__ float dot4s(const sf4& p, const sf4& q) { return p.x * q.x + p.y * q.y + p.z * q.z + p.w * q.w; }
 
 struct ReadoutArgs {
   const float* Hn;         // [B*L, D]
@@ -188,16 +179,16 @@ __global__ void __launch_bounds__(256) srgnn_readout_fwd_kernel(ReadoutArgs a) {
   __syncthreads();
   const int64_t nb = b * L;
   const int al = s_alias[s_last];
-  const sf4* P = reinterpret_cast<const sf4*>(a.P);
-  const sf4* H = reinterpret_cast<const sf4*>(a.Hn);
-  const sf4* w3 = reinterpret_cast<const sf4*>(a.w3);
+  const f32x4* P = reinterpret_cast<const f32x4*>(a.P);
+  const f32x4* H = reinterpret_cast<const f32x4*>(a.Hn);
+  const f32x4* w3 = reinterpret_cast<const f32x4*>(a.w3);
   for (int t = wave; t < L; t += 4) {
     const int64_t rq1 = (nb + al) * 2 * dv, rq2 = (nb + s_alias[t]) * 2 * dv + dv;
     float d = 0.f;
     for (int c = lane; c < dv; c += 64) {
-      const sf4 sv = sigmoid4(P[rq1 + c] + P[rq2 + c]);
-      if (a.sig) reinterpret_cast<sf4*>(a.sig)[(b * L + t) * dv + c] = sv;
-      d += dot4s(w3[c], sv);
+      const f32x4 sv = sigmoid4(P[rq1 + c] + P[rq2 + c]);
+      if (a.sig) reinterpret_cast<f32x4*>(a.sig)[(b * L + t) * dv + c] = sv;
+      d += dot4(w3[c], sv);
     }
     d = wave_sum(d);
     if (lane == 0) {
@@ -206,9 +197,9 @@ __global__ void __launch_bounds__(256) srgnn_readout_fwd_kernel(ReadoutArgs a) {
     }
   }
   __syncthreads();
-  sf4* cat = reinterpret_cast<sf4*>(a.cat) + b * 2 * dv;
+  f32x4* cat = reinterpret_cast<f32x4*>(a.cat) + b * 2 * dv;
   for (int c = threadIdx.x; c < dv; c += blockDim.x) {
-    sf4 acc = sf4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int t = 0; t < L; ++t) acc += (s_alpha[t] * H[(nb + s_alias[t]) * dv + c]) * (float)a.mask[b * L + t];
     cat[c] = acc;
     cat[dv + c] = H[(nb + al) * dv + c];
@@ -247,37 +238,37 @@ __global__ void __launch_bounds__(256) srgnn_readout_bwd_kernel(ReadoutArgs a) {
     }
   }
   const int64_t nb = b * L;
-  const sf4* H = reinterpret_cast<const sf4*>(a.Hn);
-  const sf4* da = reinterpret_cast<const sf4*>(a.dcat) + b * 2 * dv;
+  const f32x4* H = reinterpret_cast<const f32x4*>(a.Hn);
+  const f32x4* da = reinterpret_cast<const f32x4*>(a.dcat) + b * 2 * dv;
   for (int t = wave; t < L; t += 4) {
     float d = 0.f;
     const int64_t r = (nb + s_alias[t]) * dv;
-    for (int c = lane; c < dv; c += 64) d += dot4s(da[c], H[r + c]);
+    for (int c = lane; c < dv; c += 64) d += dot4(da[c], H[r + c]);
     d = wave_sum(d);
     if (lane == 0) s_dalpha[t] = s_mask[t] * d;
   }
   __syncthreads();
   const int al = s_alias[s_last];
-  const sf4* sig = reinterpret_cast<const sf4*>(a.sig) + b * L * dv;
-  const sf4* w3 = reinterpret_cast<const sf4*>(a.w3);
-  sf4* dP = reinterpret_cast<sf4*>(a.dP);
-  sf4* dH = reinterpret_cast<sf4*>(a.dH);
-  sf4* dw3p = reinterpret_cast<sf4*>(a.dw3p) + b * dv;
-  const sf4 z4 = sf4{0.f, 0.f, 0.f, 0.f};
+  const f32x4* sig = reinterpret_cast<const f32x4*>(a.sig) + b * L * dv;
+  const f32x4* w3 = reinterpret_cast<const f32x4*>(a.w3);
+  f32x4* dP = reinterpret_cast<f32x4*>(a.dP);
+  f32x4* dH = reinterpret_cast<f32x4*>(a.dH);
+  f32x4* dw3p = reinterpret_cast<f32x4*>(a.dw3p) + b * dv;
+  const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int c = threadIdx.x; c < dv; c += blockDim.x) {
-    const sf4 w = w3[c], dac = da[c], dht = da[dv + c];
-    sf4 g1 = z4, gw = z4;
+    const f32x4 w = w3[c], dac = da[c], dht = da[dv + c];
+    f32x4 g1 = z4, gw = z4;
     for (int t = 0; t < L; ++t) {
-      const sf4 s = sig[t * dv + c];
+      const f32x4 s = sig[t * dv + c];
       g1 += (s_dalpha[t] * w) * (s * (1.f - s));
       gw += s_dalpha[t] * s;
     }
     dw3p[c] = gw;
     for (int j = 0; j < L; ++j) {
-      sf4 g2 = z4, gh = z4;
+      f32x4 g2 = z4, gh = z4;
       for (int k = s_start[j]; k < s_start[j + 1]; ++k) {
         const int t = s_perm[k];
-        const sf4 s = sig[t * dv + c];
+        const f32x4 s = sig[t * dv + c];
         g2 += (s_dalpha[t] * w) * (s * (1.f - s));
         gh += (s_alpha[t] * dac) * s_mask[t];
       }
@@ -290,16 +281,8 @@ __global__ void __launch_bounds__(256) srgnn_readout_bwd_kernel(ReadoutArgs a) {
 }
 
 // ---------------------------------------------------------------- pair head (srgnn.py:60-66)
-// x_b = <o_b, e[pos_b]> - <o_b, e[neg_b]>, loss = -mean(1e-8 + log sigmoid(x_b)): LightGCN's head with the query rows o_b
-// taken from `out` (row stride ld_out) and both target rows from the table.
-__device__ __forceinline__ int64_t srgnn_check_id(int64_t id, int64_t n, int32_t* status, bool flag_lane) {
-  if (id < 0 || id >= n) {
-    if (status && flag_lane) atomicOr(status, PXR_STATUS_BAD_INDEX);
-    return id < 0 ? 0 : n - 1;
-  }
-  return id;
-}
-
+// x_b = <o_b, e[pos_b]> - <o_b, e[neg_b]> into the tail with the 1e-8 outside the log: the query rows o_b are taken from `out`
+// (row stride ld_out), both target rows from the table.  One wave per b.
 __global__ void __launch_bounds__(256) srgnn_pair_fwd_kernel(const float* __restrict__ out, int64_t ld_out, const float* __restrict__ table,
                                                              int64_t n_table, int D, const int64_t* __restrict__ target, int B,
                                                              float* __restrict__ lossrow, float* __restrict__ coef, int32_t* status) {
@@ -307,26 +290,14 @@ __global__ void __launch_bounds__(256) srgnn_pair_fwd_kernel(const float* __rest
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
   const int dv = D / 4;
-  const int64_t ip = srgnn_check_id(target[2 * (int64_t)b], n_table, status, lane == 0);
-  const int64_t in = srgnn_check_id(target[2 * (int64_t)b + 1], n_table, status, lane == 0);
-  const sf4* o = reinterpret_cast<const sf4*>(out + (int64_t)b * ld_out);
-  const sf4* tp = reinterpret_cast<const sf4*>(table + ip * D);
-  const sf4* tn = reinterpret_cast<const sf4*>(table + in * D);
-  float sp = 0.f, sn = 0.f;
-  for (int c = lane; c < dv; c += 64) {
-    const sf4 ov = o[c];
-    sp += dot4s(ov, tp[c]);
-    sn += dot4s(ov, tn[c]);
-  }
-  sp = wave_sum(sp);
-  sn = wave_sum(sn);
-  if (lane != 0) return;
-  const float x = sp - sn;
-  const float e = expf(-fabsf(x));
-  const float ls = fminf(x, 0.f) - log1pf(e);                                // log sigmoid(x)
-  const float sneg = x >= 0.f ? e / (1.f + e) : 1.f / (1.f + e);            // 1 - sigmoid(x)
-  lossrow[b] = -(1e-8f + ls);
-  coef[b] = -sneg / (float)B;
+  const int64_t ip = checked_id(target[2 * (int64_t)b], n_table, status, lane == 0);
+  const int64_t in = checked_id(target[2 * (int64_t)b + 1], n_table, status, lane == 0);
+  const f32x4* o = reinterpret_cast<const f32x4*>(out + (int64_t)b * ld_out);
+  const f32x4* tp = reinterpret_cast<const f32x4*>(table + ip * D);
+  const f32x4* tn = reinterpret_cast<const f32x4*>(table + in * D);
+  float sp, sn;
+  pair_dots(o, tp, tn, dv, lane, sp, sn);
+  if (lane == 0) bpr_tail_log_outside(sp - sn, B, lossrow[b], coef[b]);
 }
 
 // dout[b] = c_b (e[pos] - e[neg]) and coef_out[b * coef_stride] = c_b, c_b = coef[b] * grad_scale * (*grad_scale_dev): the
@@ -339,12 +310,12 @@ __global__ void __launch_bounds__(256) srgnn_pair_bwd_kernel(const float* __rest
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
   const int dv = D / 4;
-  const int64_t ip = srgnn_check_id(target[2 * (int64_t)b], n_table, nullptr, false);
-  const int64_t in = srgnn_check_id(target[2 * (int64_t)b + 1], n_table, nullptr, false);
+  const int64_t ip = checked_id(target[2 * (int64_t)b], n_table, nullptr, false);
+  const int64_t in = checked_id(target[2 * (int64_t)b + 1], n_table, nullptr, false);
   const float c = coef[b] * gscale * (gscale_dev ? gscale_dev[0] : 1.f);
-  const sf4* tp = reinterpret_cast<const sf4*>(table + ip * D);
-  const sf4* tn = reinterpret_cast<const sf4*>(table + in * D);
-  sf4* d = reinterpret_cast<sf4*>(dout + (int64_t)b * ld_dout);
+  const f32x4* tp = reinterpret_cast<const f32x4*>(table + ip * D);
+  const f32x4* tn = reinterpret_cast<const f32x4*>(table + in * D);
+  f32x4* d = reinterpret_cast<f32x4*>(dout + (int64_t)b * ld_dout);
   for (int k = lane; k < dv; k += 64) d[k] = c * (tp[k] - tn[k]);
   if (lane == 0 && coef_out) coef_out[(int64_t)b * coef_stride] = c;
 }

@@ -7,16 +7,11 @@
 // sparse-row machinery (embed_grad.hip, adamw.hip) treats id 0 as padding / an empty slot, and VBPR has no padding id.
 //
 // A step's occurrences are laid out as rows[4B] = [id row of user b | modal row of user b | id rows of item.view(-1): (i+_b, i-_b)],
-// three segments whose row ranges are disjoint.  The sparse table gradient has one slot per occurrence, as mf.hip's: the FIRST
-// occurrence of a row sums all of that row's occurrences in ascending order and writes (row, sum); the slots of the other
-// occurrences are written as (0, zeros).  No float atomics: every output is bit-identical from run to run.
-#include "pxr_common.h"
+// three segments whose row ranges are disjoint.  The sparse table gradient has one slot per occurrence, summed by pair_head.cuh's
+// first-occurrence scheme: (row, sum) in the slot of a row's first occurrence, (0, zeros) in the others.
+#include "pair_head.cuh"
 
 namespace pxr {
-
-typedef float vb4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float vb_dot4(const vb4& p, const vb4& q) { return p.x * q.x + p.y * q.y + p.z * q.z + p.w * q.w; }
 
 // rows[o] of occurrence o (layout above; item == NULL: the 2B user rows only); an id outside its range flags the status word and
 // is clamped
@@ -27,67 +22,59 @@ __global__ void __launch_bounds__(256) vbpr_rows_kernel(const int64_t* __restric
   const int64_t n_occ = item ? 4 * (int64_t)B : 2 * (int64_t)B;
   if (o >= n_occ) return;
   const bool is_user = o < 2 * (int64_t)B;
-  int64_t id = is_user ? user[o < B ? o : o - B] : item[o - 2 * (int64_t)B];
-  const int64_t n = is_user ? n_users : n_items;
-  if (id < 0 || id >= n) {
-    if (status) atomicOr(status, PXR_STATUS_BAD_INDEX);
-    id = id < 0 ? 0 : n - 1;
-  }
+  const int64_t id = checked_id(is_user ? user[o < B ? o : o - B] : item[o - 2 * (int64_t)B], is_user ? n_users : n_items, status,
+                                true);
   rows[o] = 1 + id + (o < B ? 0 : is_user ? n_users + n_items : n_users);
 }
 
 // out[r, :] = feat[item[r], :] and beta[r] = <feat[item[r], :], wb> from the same registers: the feature row is read once.  One
 // wave per row.  item == NULL: row r itself (the whole catalogue); out == NULL: beta only (compute_item_all's total_visual_bias).
-__global__ void __launch_bounds__(256) vbpr_gather_kernel(const vb4* __restrict__ feat, int64_t n_items, int fv,
-                                                           const int64_t* __restrict__ item, int64_t n, const vb4* __restrict__ wb,
-                                                           vb4* __restrict__ out, float* __restrict__ beta, int32_t* status) {
+__global__ void __launch_bounds__(256) vbpr_gather_kernel(const f32x4* __restrict__ feat, int64_t n_items, int fv,
+                                                           const int64_t* __restrict__ item, int64_t n, const f32x4* __restrict__ wb,
+                                                           f32x4* __restrict__ out, float* __restrict__ beta, int32_t* status) {
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= n) return;
-  int64_t id = item ? item[r] : r;
-  if (id < 0 || id >= n_items) {
-    if (status && lane == 0) atomicOr(status, PXR_STATUS_BAD_INDEX);
-    id = id < 0 ? 0 : n_items - 1;
-  }
-  const vb4* src = feat + id * fv;
+  const f32x4* src = feat + checked_id(item ? item[r] : r, n_items, status, lane == 0) * fv;
   float s = 0.f;
   for (int c = lane; c < fv; c += 64) {
-    const vb4 v = src[c];
+    const f32x4 v = src[c];
     if (out) out[r * fv + c] = v;
-    s += vb_dot4(v, wb[c]);
+    s += dot4(v, wb[c]);
   }
   s = wave_sum(s);
   if (lane == 0) beta[r] = s;
 }
 
 // s_{b,t} = <uid_b, iid_{b,t}> + <um_b, e_{b,t}> + beta_{b,t} with the id rows straight from the table; x_b = s_{b,0} - s_{b,1};
-// lossrow[b] = -log(1e-8 + sigmoid(x_b)) (the 1e-8 INSIDE the log, vbpr.py forward); coef[b] = d loss / d x_b =
-// -(1/B) sigmoid(x)(1 - sigmoid(x)) / (1e-8 + sigmoid(x)), both sigmoids in forms that stay finite for any |x|.  One wave per b.
-__global__ void __launch_bounds__(256) vbpr_pair_fwd_kernel(const vb4* __restrict__ table, const int64_t* __restrict__ rows,
-                                                             const vb4* __restrict__ e, const float* __restrict__ beta, int dv, int B,
+// into the tail with the 1e-8 inside the log (vbpr.py forward).  One wave per b; two terms per side, so the loop is its own.  The
+// tail is spelled out here: with it inlined from pair_head.cuh the compiler fuses the loop's multiply-adds in another order and
+// x_b moves by an ulp (profiles/pair_head/README.md).
+__global__ void __launch_bounds__(256) vbpr_pair_fwd_kernel(const f32x4* __restrict__ table, const int64_t* __restrict__ rows,
+                                                             const f32x4* __restrict__ e, const float* __restrict__ beta, int dv, int B,
                                                              float* __restrict__ coef, float* __restrict__ lossrow) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
-  const vb4* uid = table + rows[b] * dv;
-  const vb4* um = table + rows[B + b] * dv;
-  const vb4* ip = table + rows[2 * (int64_t)B + 2 * (int64_t)b] * dv;
-  const vb4* in = table + rows[2 * (int64_t)B + 2 * (int64_t)b + 1] * dv;
-  const vb4* ep = e + 2 * (int64_t)b * dv;
-  const vb4* en = ep + dv;
+  const f32x4* uid = table + rows[b] * dv;
+  const f32x4* um = table + rows[B + b] * dv;
+  const f32x4* ip = table + rows[2 * (int64_t)B + 2 * (int64_t)b] * dv;
+  const f32x4* in = table + rows[2 * (int64_t)B + 2 * (int64_t)b + 1] * dv;
+  const f32x4* ep = e + 2 * (int64_t)b * dv;
+  const f32x4* en = ep + dv;
   float sp = 0.f, sn = 0.f;
   for (int c = lane; c < dv; c += 64) {
-    const vb4 u = uid[c], m = um[c];
-    sp += vb_dot4(u, ip[c]) + vb_dot4(m, ep[c]);
-    sn += vb_dot4(u, in[c]) + vb_dot4(m, en[c]);
+    const f32x4 u = uid[c], m = um[c];
+    sp += dot4(u, ip[c]) + dot4(m, ep[c]);
+    sn += dot4(u, in[c]) + dot4(m, en[c]);
   }
   sp = wave_sum(sp);
   sn = wave_sum(sn);
   if (lane != 0) return;
   const float x = (sp + beta[2 * (int64_t)b]) - (sn + beta[2 * (int64_t)b + 1]);
-  const float ex = expf(-fabsf(x));
+  const float ex = expf(-fabsf(x));                                         // bpr_tail_log_inside, kept in place (see above)
   const float sig = x >= 0.f ? 1.f / (1.f + ex) : ex / (1.f + ex);
-  const float sneg = x >= 0.f ? ex / (1.f + ex) : 1.f / (1.f + ex);         // 1 - sigmoid(x)
+  const float sneg = x >= 0.f ? ex / (1.f + ex) : 1.f / (1.f + ex);
   lossrow[b] = -logf(1e-8f + sig);
   coef[b] = -(sig * sneg / (1e-8f + sig)) / (float)B;
 }
@@ -98,18 +85,20 @@ __global__ void __launch_bounds__(256) vbpr_pair_fwd_kernel(const vb4* __restric
 //   then the sparse table gradient, contribution of occurrence k:
 //     id row of user b: c_b (iid+_b - iid-_b);  modal row of user b: c_b (e+_b - e-_b);  item row (b, t): +-c_b uid_b.
 // Rows of different segments never coincide, so both scans stay inside the occurrence's own segment.
+// The first-occurrence scheme of pair_head.cuh is spelled out here: through the shared walk and register row the compiler fuses
+// the multiply-adds of vbpr_pair_bwd_kernel<2> in another order and the row sums move by an ulp (profiles/pair_head/README.md).
 struct VbprBwdArgs {
-  const vb4* table;
+  const f32x4* table;
   const int64_t* rows;
-  const vb4* e;                // [2B, dv]
+  const f32x4* e;              // [2B, dv]
   const float* coef;           // [B]
   int dv, B;
   float gscale;
   const float* gscale_dev;
-  vb4* de;                     // [2B, dv]
+  f32x4* de;                   // [2B, dv]
   float* csign;                // [2B]
   int64_t* sp_idx;             // [4B]
-  vb4* sp_rows;                // [4B, dv]
+  f32x4* sp_rows;              // [4B, dv]
   int32_t* sp_n;
 };
 
@@ -120,12 +109,12 @@ __global__ void __launch_bounds__(256) vbpr_pair_bwd_kernel(VbprBwdArgs a) {
   const int B = a.B, n_occ = 4 * a.B;
   if (o == 0 && lane == 0) a.sp_n[0] = n_occ;
   if (o >= n_occ) return;
-  const float g = a.gscale * (a.gscale_dev ? a.gscale_dev[0] : 1.f);
+  const float g = grad_scale(a.gscale, a.gscale_dev);
   if (o >= 2 * B) {
     const int j = o - 2 * B, b = j >> 1;
     const float cs = (j & 1) ? -(a.coef[b] * g) : a.coef[b] * g;
-    const vb4* um = a.table + a.rows[B + b] * a.dv;
-    vb4* d = a.de + (int64_t)j * a.dv;
+    const f32x4* um = a.table + a.rows[B + b] * a.dv;
+    f32x4* d = a.de + (int64_t)j * a.dv;
 #pragma unroll
     for (int h = 0; h < CH; ++h) {
       const int ch = lane + h * 64;
@@ -141,26 +130,26 @@ __global__ void __launch_bounds__(256) vbpr_pair_bwd_kernel(VbprBwdArgs a) {
     const int k = k0 + lane;
     if (__ballot(k < o && a.rows[k] == node)) first = false;
   }
-  vb4* dst = a.sp_rows + (int64_t)o * a.dv;
+  f32x4* dst = a.sp_rows + (int64_t)o * a.dv;
   if (!first) {
 #pragma unroll
     for (int h = 0; h < CH; ++h) {
       const int ch = lane + h * 64;
-      if (ch < a.dv) dst[ch] = vb4{0.f, 0.f, 0.f, 0.f};
+      if (ch < a.dv) dst[ch] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     if (lane == 0) a.sp_idx[o] = 0;
     return;
   }
-  vb4 s[CH];
+  f32x4 s[CH];
 #pragma unroll
-  for (int h = 0; h < CH; ++h) s[h] = vb4{0.f, 0.f, 0.f, 0.f};
+  for (int h = 0; h < CH; ++h) s[h] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int k0 = o; k0 < seg_hi; k0 += 64) {
     const int k = k0 + lane;
     unsigned long long m = __ballot(k < seg_hi && a.rows[k] == node);
     while (m) {
       const int kk = k0 + __builtin_ctzll(m);
       m &= m - 1;
-      const vb4 *p, *n;                      // contribution = c (p - n), n == NULL: c p
+      const f32x4 *p, *n;                      // contribution = c (p - n), n == NULL: c p
       float c;
       if (kk < 2 * B) {
         const int b = kk < B ? kk : kk - B;
@@ -205,19 +194,19 @@ __global__ void __launch_bounds__(256) vbpr_pair_bwd_kernel(VbprBwdArgs a) {
 // with VB_RL row lanes; the VB_RL partial sums of a column are added in lane order through LDS (one fixed summation order).
 constexpr int VB_CC = 8, VB_RL = 32;
 
-__global__ void __launch_bounds__(256) vbpr_bias_grad_kernel(const vb4* __restrict__ x, const float* __restrict__ csign, int R, int fv,
-                                                              vb4* __restrict__ dwb) {
-  __shared__ vb4 red[VB_RL][VB_CC];
+__global__ void __launch_bounds__(256) vbpr_bias_grad_kernel(const f32x4* __restrict__ x, const float* __restrict__ csign, int R, int fv,
+                                                              f32x4* __restrict__ dwb) {
+  __shared__ f32x4 red[VB_RL][VB_CC];
   const int cc = threadIdx.x % VB_CC, rl = threadIdx.x / VB_CC;
   const int c4 = blockIdx.x * VB_CC + cc;
   const bool ok = c4 < fv;
-  vb4 s = vb4{0.f, 0.f, 0.f, 0.f};
+  f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
   if (ok)
     for (int r = rl; r < R; r += VB_RL) s += csign[r] * x[(int64_t)r * fv + c4];
   red[rl][cc] = s;
   __syncthreads();
   if (rl != 0 || !ok) return;
-  vb4 t = red[0][cc];
+  f32x4 t = red[0][cc];
 #pragma unroll
   for (int k = 1; k < VB_RL; ++k) t += red[k][cc];
   dwb[c4] = t;
@@ -226,20 +215,20 @@ __global__ void __launch_bounds__(256) vbpr_bias_grad_kernel(const vb4* __restri
 // out[r, :] = [a[ra, :] | b[rb, :] | s_r | 0 ...] of width 4 pv (ra = a_rows ? a_rows[r] : r, rb likewise; s_r = s ? s[r] : 1): the
 // item side (item id row | projected feature | visual bias) and the query side (user id row | user modal row | 1) of the score
 // as one inner product.  One wave per row.
-__global__ void __launch_bounds__(256) vbpr_pack_kernel(const vb4* __restrict__ a, const int64_t* __restrict__ a_rows,
-                                                         const vb4* __restrict__ b, const int64_t* __restrict__ b_rows,
-                                                         const float* __restrict__ s, int64_t R, int dv, int pv, vb4* __restrict__ out) {
+__global__ void __launch_bounds__(256) vbpr_pack_kernel(const f32x4* __restrict__ a, const int64_t* __restrict__ a_rows,
+                                                         const f32x4* __restrict__ b, const int64_t* __restrict__ b_rows,
+                                                         const float* __restrict__ s, int64_t R, int dv, int pv, f32x4* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
-  const vb4* pa = a + (a_rows ? a_rows[r] : r) * dv;
-  const vb4* pb = b + (b_rows ? b_rows[r] : r) * dv;
-  vb4* dst = out + r * pv;
+  const f32x4* pa = a + (a_rows ? a_rows[r] : r) * dv;
+  const f32x4* pb = b + (b_rows ? b_rows[r] : r) * dv;
+  f32x4* dst = out + r * pv;
   for (int c = lane; c < dv; c += 64) {
     dst[c] = pa[c];
     dst[dv + c] = pb[c];
   }
-  for (int c = 2 * dv + lane; c < pv; c += 64) dst[c] = vb4{c == 2 * dv ? (s ? s[r] : 1.f) : 0.f, 0.f, 0.f, 0.f};
+  for (int c = 2 * dv + lane; c < pv; c += 64) dst[c] = f32x4{c == 2 * dv ? (s ? s[r] : 1.f) : 0.f, 0.f, 0.f, 0.f};
 }
 
 }  // namespace pxr
@@ -263,8 +252,8 @@ extern "C" int pxr_vbpr_gather_f32(const float* feat, int64_t n_items, int F, co
   PXR_REQUIRE(F > 0 && F % 4 == 0, "pxr_vbpr_gather_f32: need F %% 4 == 0 (F=%d)", F);
   PXR_REQUIRE(n_items > 0 && n > 0 && n < (1ll << 31) && (item || n <= n_items), "pxr_vbpr_gather_f32: bad row count");
   PXR_REQUIRE((((uintptr_t)feat | (uintptr_t)wb | (uintptr_t)out) & 15) == 0, "pxr_vbpr_gather_f32: operands must be 16-byte aligned");
-  hipLaunchKernelGGL(vbpr_gather_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const vb4*)feat, n_items,
-                     F / 4, item, n, (const vb4*)wb, (vb4*)out, beta, pxr_status_word());
+  hipLaunchKernelGGL(vbpr_gather_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)feat, n_items,
+                     F / 4, item, n, (const f32x4*)wb, (f32x4*)out, beta, pxr_status_word());
   return pxr_check_launch("pxr_vbpr_gather_f32");
 }
 
@@ -274,8 +263,8 @@ extern "C" int pxr_vbpr_pair_fwd_f32(const float* table, const int64_t* rows, co
   PXR_REQUIRE(Dh > 0 && Dh % 4 == 0 && Dh <= 4096, "pxr_vbpr_pair_fwd_f32: need Dh %% 4 == 0 and 0 < Dh <= 4096 (Dh=%d)", Dh);
   PXR_REQUIRE(B > 0 && B <= (1 << 26), "pxr_vbpr_pair_fwd_f32: bad batch size %d", B);
   PXR_REQUIRE((((uintptr_t)table | (uintptr_t)e) & 15) == 0, "pxr_vbpr_pair_fwd_f32: operands must be 16-byte aligned");
-  hipLaunchKernelGGL(vbpr_pair_fwd_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const vb4*)table, rows,
-                     (const vb4*)e, beta, Dh / 4, B, coef, lossrow);
+  hipLaunchKernelGGL(vbpr_pair_fwd_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)table, rows,
+                     (const f32x4*)e, beta, Dh / 4, B, coef, lossrow);
   const int rc = pxr_check_launch("pxr_vbpr_pair_fwd_f32");
   if (rc) return rc;
   return pxr_bpr_loss_reduce(lossrow, B, 1, loss, stream);        // loss = (1/B) sum_b lossrow[b], fixed order
@@ -291,17 +280,12 @@ extern "C" int pxr_vbpr_pair_bwd_f32(const float* table, const int64_t* rows, co
   PXR_REQUIRE((((uintptr_t)table | (uintptr_t)e | (uintptr_t)de | (uintptr_t)sp_rows) & 15) == 0,
               "pxr_vbpr_pair_bwd_f32: operands must be 16-byte aligned");
   VbprBwdArgs a{};
-  a.table = (const vb4*)table; a.rows = rows; a.e = (const vb4*)e; a.coef = coef; a.dv = Dh / 4; a.B = B;
-  a.gscale = grad_scale; a.gscale_dev = grad_scale_dev; a.de = (vb4*)de; a.csign = csign;
-  a.sp_idx = sp_idx; a.sp_rows = (vb4*)sp_rows; a.sp_n = sp_n;
-  const int CH = (a.dv + 63) / 64;
-  const dim3 g((unsigned)B);                                       // 4B occurrences, 4 waves per workgroup
-  hipStream_t st = (hipStream_t)stream;
-  if (CH <= 1) hipLaunchKernelGGL(vbpr_pair_bwd_kernel<1>, g, dim3(256), 0, st, a);
-  else if (CH <= 2) hipLaunchKernelGGL(vbpr_pair_bwd_kernel<2>, g, dim3(256), 0, st, a);
-  else if (CH <= 4) hipLaunchKernelGGL(vbpr_pair_bwd_kernel<4>, g, dim3(256), 0, st, a);
-  else if (CH <= 8) hipLaunchKernelGGL(vbpr_pair_bwd_kernel<8>, g, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(vbpr_pair_bwd_kernel<16>, g, dim3(256), 0, st, a);
+  a.table = (const f32x4*)table; a.rows = rows; a.e = (const f32x4*)e; a.coef = coef; a.dv = Dh / 4; a.B = B;
+  a.gscale = grad_scale; a.gscale_dev = grad_scale_dev; a.de = (f32x4*)de; a.csign = csign;
+  a.sp_idx = sp_idx; a.sp_rows = (f32x4*)sp_rows; a.sp_n = sp_n;
+  dispatch_ch<16>(a.dv, [&](auto ch) {                             // 4B occurrences, 4 waves per workgroup
+    hipLaunchKernelGGL(vbpr_pair_bwd_kernel<decltype(ch)::value>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
+  });
   return pxr_check_launch("pxr_vbpr_pair_bwd_f32");
 }
 
@@ -311,7 +295,7 @@ extern "C" int pxr_vbpr_bias_grad_f32(const float* x, const float* csign, int R,
   PXR_REQUIRE((((uintptr_t)x | (uintptr_t)dwb) & 15) == 0, "pxr_vbpr_bias_grad_f32: operands must be 16-byte aligned");
   const int fv = F / 4;
   hipLaunchKernelGGL(vbpr_bias_grad_kernel, dim3((unsigned)((fv + VB_CC - 1) / VB_CC)), dim3(256), 0, (hipStream_t)stream,
-                     (const vb4*)x, csign, R, fv, (vb4*)dwb);
+                     (const f32x4*)x, csign, R, fv, (f32x4*)dwb);
   return pxr_check_launch("pxr_vbpr_bias_grad_f32");
 }
 
@@ -322,7 +306,7 @@ extern "C" int pxr_vbpr_pack_f32(const float* a, const int64_t* a_rows, const fl
   PXR_REQUIRE(Dp % 4 == 0 && Dp > 2 * Dh, "pxr_vbpr_pack_f32: need Dp %% 4 == 0 and Dp > 2 Dh (Dp=%d, Dh=%d)", Dp, Dh);
   PXR_REQUIRE(R > 0 && R < (1ll << 31), "pxr_vbpr_pack_f32: bad row count");
   PXR_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0, "pxr_vbpr_pack_f32: operands must be 16-byte aligned");
-  hipLaunchKernelGGL(vbpr_pack_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const vb4*)a, a_rows,
-                     (const vb4*)b, b_rows, s, R, Dh / 4, Dp / 4, (vb4*)out);
+  hipLaunchKernelGGL(vbpr_pack_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)a, a_rows,
+                     (const f32x4*)b, b_rows, s, R, Dh / 4, Dp / 4, (f32x4*)out);
   return pxr_check_launch("pxr_vbpr_pack_f32");
 }
