@@ -134,6 +134,17 @@ int pxr_seq_occ_sort(const int64_t* items, int B, int L, int64_t id_bstride, int
 int pxr_sasrec_occ_segsum(const void* ws, int64_t ws_bytes, int B, int L, const float* dx0, const float* out,
                           const float* coef, int D, int64_t n_table, float scale, const int32_t* n_uniq_dev,
                           float* uniq_rows, void* stream);
+/* Phase 2 with the lazy AdamW row update inside (one rank, lazy table update, scale 1): one launch leaves in table / m / v / last
+ * what pxr_sasrec_occ_segsum followed by pxr_adamw_rows_f32(rows = uniq_idx, grows = uniq_rows, t_apply = t_prev + 1) leaves there
+ * for rows that are current through t_prev, bit for bit; the summed rows are applied where they are formed and never written.
+ * uniq_idx / n_uniq_dev: phase 1's output.  hyper: the per-step scalars (pxr_adamw_hyper_append; entry t_prev + 1 must exist);
+ * step_dev != NULL: t_prev = *step_dev.  A row with last[row] != t_prev is left untouched and raises status bit 256
+ * (PXR_STATUS_ROWS_STALE); id 0 and ids outside [0, table_rows) are skipped.  Every segment is summed by one workgroup: batches
+ * that want pxr_sasrec_occ_segsum_split keep the two launches. */
+int pxr_sasrec_occ_segsum_apply(const void* ws, int64_t ws_bytes, int B, int L, const float* dx0, const float* out,
+                                const float* coef, int D, int64_t n_table, const int32_t* n_uniq_dev, const int64_t* uniq_idx,
+                                float* table, float* m, float* v, int32_t* last, int64_t table_rows, const void* hyper,
+                                int64_t t_prev, const int64_t* step_dev, double beta1, double beta2, double eps, void* stream);
 
 /* Phase 2 for big batches (round 5): the same sums, with the rows of more than 1 024 occurrences (a Zipf-popular item of a
  * 2 048-sequence batch has 13 000) cut into parts of 512 occurrences that many workgroups sum, the parts of a row added in part

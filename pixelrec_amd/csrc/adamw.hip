@@ -17,21 +17,12 @@
 //     The kernel clears the slots it consumes, so the map is all -1 again afterwards.
 #include <string.h>
 
+#include "adam_row.cuh"
 #include "planes.cuh"
 
 #include <cstdlib>
 
 namespace pxr {
-
-struct AdamHyper {
-  float decay;        // 1 - lr*wd
-  float one_m_b1;     // 1 - beta1
-  float b2;           // beta2
-  float one_m_b2;     // 1 - beta2
-  float step_size;    // lr / (1 - beta1^t)
-  float inv_sqrt_bc2; // 1 / sqrt(1 - beta2^t)
-  float eps;
-};
 
 static AdamHyper make_hyper(double lr, double b1, double b2, double eps, double wd, int64_t step) {
   AdamHyper h;
@@ -45,28 +36,6 @@ static AdamHyper make_hyper(double lr, double b1, double b2, double eps, double 
   h.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   h.eps = (float)eps;
   return h;
-}
-
-// The operation order is PINNED with explicit fmaf / __fmul_rn so that every kernel that updates a row (dense sweep,
-// lazy replay, lazy apply) produces bit-identical results regardless of how the compiler would contract a*b+c.
-// sqrt and the division are the hardware's 1-ulp v_sqrt_f32 / v_rcp_f32 (2 quarter-rate instructions) instead of the
-// correctly rounded sequences (~25 VALU instructions): a lazily updated row REPLAYS this body once per missed step, so
-// its cost is what the lazy schedule pays per step (bench.py `roofline_adamw_rows`).  The update term is <= lr in
-// magnitude, so a 1-ulp relative difference in it is ~1e-11 absolute against the +-1e-5 parity bar on parameters.
-__device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g, const AdamHyper& h) {
-  p = __fmul_rn(p, h.decay);
-  m = fmaf(g - m, h.one_m_b1, m);
-  v = fmaf(v, h.b2, __fmul_rn(__fmul_rn(h.one_m_b2, g), g));
-  const float denom = fmaf(__builtin_amdgcn_sqrtf(v), h.inv_sqrt_bc2, h.eps);
-  p = fmaf(-h.step_size, __fmul_rn(m, __builtin_amdgcn_rcpf(denom)), p);
-}
-// zero-gradient form of adam_elem (same values bit for bit: fmaf(v, b2, +0) == v * b2, g - m == -m)
-__device__ __forceinline__ void adam_elem0(float& p, float& m, float& v, const AdamHyper& h) {
-  p = __fmul_rn(p, h.decay);
-  m = fmaf(-m, h.one_m_b1, m);
-  v = __fmul_rn(v, h.b2);
-  const float denom = fmaf(__builtin_amdgcn_sqrtf(v), h.inv_sqrt_bc2, h.eps);
-  p = fmaf(-h.step_size, __fmul_rn(m, __builtin_amdgcn_rcpf(denom)), p);
 }
 
 __global__ void __launch_bounds__(256) adamw_flat_kernel(float4* __restrict__ p, const float4* __restrict__ g,
@@ -410,22 +379,20 @@ __global__ void __launch_bounds__((LPR > 256 ? LPR : 256)) adamw_rows_kernel(Row
 #pragma unroll
         for (int e = 0; e < EPL; ++e) { pe[e] *= fp; me[e] *= fm; ve[e] *= fv; }
       }
-      if (a.t_apply) {
-        const float4 hs = hyper[a.t_apply];
-        h.decay = hs.x; h.step_size = hs.y; h.inv_sqrt_bc2 = hs.z;
+      if (a.t_apply) {   // adam_row.cuh: the apply shared with the segment sum that updates its rows itself (embed_grad.hip)
+        const AdamHyper ha = adam_step_hyper(AdamConsts{a.one_m_b1, a.b2, a.one_m_b2, a.eps}, hyper[a.t_apply]);
         float ge[EPL];
 #pragma unroll
         for (int e = 0; e < EPL; ++e) ge[e] = 0.f;
         if (a.grows && col_ok) row_ld<EPL>(a.grows + i * a.D + c, ge);
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) adam_elem(pe[e], me[e], ve[e], ge[e], h);
+        adam_apply_row<EPL>(pe, me, ve, ge, ha);
       }
       if (col_ok) {
         row_st<EPL>(a.p + o, pe); row_st<EPL>(a.m + o, me); row_st<EPL>(a.v + o, ve);
       }
     }
     if constexpr (LPR > 64) __syncthreads();   // every wave of the row has read last[row]
-    if (work && !a.claim && (threadIdx.x % LPR) == 0) a.last[row] = a.t_apply ? a.t_apply : a.t_prev;
+    if (work && !a.claim && (threadIdx.x % LPR) == 0) adam_row_mark(a.last, row, a.t_apply ? a.t_apply : a.t_prev);
   }
 }
 

@@ -17,6 +17,7 @@
 //
 // Everything is launched with worst-case grids and reads the device-side counts, so the sequence is
 // hipGraph-capturable and needs no host synchronisation.
+#include "adam_row.cuh"
 #include "pxr_common.h"
 
 #include <cstdlib>
@@ -490,13 +491,91 @@ __device__ __forceinline__ const float* seg_row(const SegSumArgs& a, int64_t off
 
 constexpr int SEG_EPOCH = 16;    // passes between two looks at the long rows (no barrier inside an epoch)
 
+// What the segment sums do with a finished row sum is a SINK, so that the summation below exists once:
+//   SegStoreRows : uniq_rows[u,:] = scale * sum -- the table gradient as sparse rows, for an exchange or a later row update;
+//   SegApplyRows : the lazy AdamW step of table row uniq_idx[u] with the sum as its gradient (adam_row.cuh), for a row that is
+//                  current through the step before; nothing is written to uniq_rows.
+// A sink names the row (row_id), reads what it needs of it as soon as the row is known (begin: the loads then travel under the
+// occurrence loads instead of behind them), takes the sum of one float4 column (finish) and, once EVERY lane of the row has
+// called begin, closes the row from one lane (mark).
+struct SegStoreRows {
+  static constexpr bool kApply = false;
+  struct Row {};
+  __device__ __forceinline__ void init() {}
+  __device__ __forceinline__ int row_id(int) const { return 0; }
+  __device__ __forceinline__ Row begin(int, int) const { return Row{}; }
+  __device__ __forceinline__ void finish(const SegSumArgs& a, const Row&, int u, int col, float4 acc) const {
+    acc.x *= a.scale; acc.y *= a.scale; acc.z *= a.scale; acc.w *= a.scale;
+    *reinterpret_cast<float4*>(a.uniq_rows + (int64_t)u * a.D + col) = acc;
+  }
+  __device__ __forceinline__ bool closes(const Row&) const { return false; }
+  __device__ __forceinline__ void mark(int) const {}
+};
+
+struct SegApplyRows {
+  static constexpr bool kApply = true;
+  float* p; float* m; float* v; int* last;
+  const int64_t* uniq_idx;       // [n_uniq] table row of unique id u (0: padding, skipped like a row outside the table)
+  int64_t n_table;               // rows of p / m / v / last
+  const float4* hyper;           // per-step scalars (adamw.hip): the step applied is entry t_prev + 1
+  const int64_t* step_dev;       // optional: t_prev = *step_dev (completed steps)
+  int t_prev, D;
+  AdamConsts c;
+  int32_t* status;               // PXR_STATUS_ROWS_STALE: a row that was not current through t_prev was left untouched
+  AdamHyper h;                   // (init)
+  struct Row { float4 p, m, v; int64_t o; int last; bool ok; };
+  __device__ __forceinline__ void init() {
+    if (step_dev) t_prev = (int)step_dev[0];
+    h = adam_step_hyper(c, hyper[t_prev + 1]);
+  }
+  __device__ __forceinline__ int row_id(int u) const { return (int)uniq_idx[u]; }
+  // p / m / v of the row's float4 column `col` and last[row]: every lane of the row asks for last[row] (one address per wave)
+  __device__ __forceinline__ Row begin(int row, int col) const {
+    Row r;
+    r.ok = row > 0 && (int64_t)row < n_table;
+    r.o = (int64_t)row * D + col;
+    r.last = 0;
+    r.p = r.m = r.v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r.ok) {
+      r.last = last[row];
+      r.p = *reinterpret_cast<const float4*>(p + r.o);
+      r.m = *reinterpret_cast<const float4*>(m + r.o);
+      r.v = *reinterpret_cast<const float4*>(v + r.o);
+    }
+    return r;
+  }
+  __device__ __forceinline__ bool closes(const Row& r) const { return r.ok && r.last == t_prev; }
+  // the gradient is the plain sum (the entry point serves scale == 1 only)
+  __device__ __forceinline__ void finish(const SegSumArgs&, const Row& r, int, int, const float4 acc) const {
+    if (!closes(r)) return;          // padding / outside the table: dropped; not current: left as it is (lane_stale flags it)
+    float pe[4] = {r.p.x, r.p.y, r.p.z, r.p.w}, me[4] = {r.m.x, r.m.y, r.m.z, r.m.w}, ve[4] = {r.v.x, r.v.y, r.v.z, r.v.w};
+    const float ge[4] = {acc.x, acc.y, acc.z, acc.w};
+    adam_apply_row<4>(pe, me, ve, ge, h);
+    *reinterpret_cast<float4*>(p + r.o) = make_float4(pe[0], pe[1], pe[2], pe[3]);
+    *reinterpret_cast<float4*>(m + r.o) = make_float4(me[0], me[1], me[2], me[3]);
+    *reinterpret_cast<float4*>(v + r.o) = make_float4(ve[0], ve[1], ve[2], ve[3]);
+  }
+  // one lane of the row: a row that is in the table but not current raises the status bit
+  __device__ __forceinline__ void lane_stale(const Row& r) const {
+    if (r.ok && r.last != t_prev && status) atomicOr(status, PXR_STATUS_ROWS_STALE);
+  }
+  __device__ __forceinline__ void mark(int row) const { adam_row_mark(last, row, t_prev + 1); }
+};
+
 // one unique row summed by the WHOLE workgroup (a long segment, or D too wide for row groups).  Block-uniform call.
-template <int MODE>
-__device__ __forceinline__ void seg_long_row(const SegSumArgs& a, int u, int dv, int G, int g, int c0, bool active, float4* sred,
-                                             int64_t* s_off, float* s_cf) {
+template <int MODE, class SINK>
+__device__ __forceinline__ void seg_long_row(const SegSumArgs& a, const SINK& sink, int u, int dv, int G, int g, int c0, bool active,
+                                             float4* sred, int64_t* s_off, float* s_cf) {
   const int s0 = a.seg_start[u], s1 = a.seg_start[u + 1];
+  const int row = (SINK::kApply && g == 0) ? sink.row_id(u) : 0;
+  bool close = false;
   for (int cb = 0; cb < dv; cb += SEG_THREADS) {  // dv > 512 (D > 2048): column blocks
     const int c4 = cb + c0;
+    // the sink's loads of the row are asked for before the occurrences: they arrive under the chunk loop.  Every lane that
+    // will finish a column has read the row's state before the first barrier below, so the closing store after the last
+    // column cannot be seen by a lane that has not looked yet
+    typename SINK::Row r{};
+    if (g == 0 && c4 < dv) r = sink.begin(row, c4 * 4);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int sb = s0; sb < s1; sb += SEG_CHUNK) {
       const int cnt = min(SEG_CHUNK, s1 - sb);
@@ -534,22 +613,32 @@ __device__ __forceinline__ void seg_long_row(const SegSumArgs& a, int u, int dv,
       }
     }
     if (g == 0 && c4 < dv) {
-      acc.x *= a.scale; acc.y *= a.scale; acc.z *= a.scale; acc.w *= a.scale;
-      *reinterpret_cast<float4*>(a.uniq_rows + (int64_t)u * a.D + c4 * 4) = acc;
+      sink.finish(a, r, u, c4 * 4, acc);
+      if constexpr (SINK::kApply) {
+        if (threadIdx.x == 0 && cb == 0) { close = sink.closes(r); sink.lane_stale(r); }
+      }
     }
+  }
+  if constexpr (SINK::kApply) {
+    if (close) sink.mark(row);       // thread 0, behind at least one barrier that every reader of the row's state has passed
   }
 }
 
 // The short path is a chain of three dependent loads (seg_start -> sorted ids -> coefficient and row) of which only the last
 // moves data: round 5 keeps the first two links of the NEXT two passes in flight while the rows of this pass are summed (the
 // segment bounds two passes ahead, the first two ids one pass ahead), and looks at the long rows once per SEG_EPOCH passes instead
-// of synchronising the eight waves twice per pass.  Same sums in the same order.
-template <int MODE>
-__global__ void __launch_bounds__(SEG_THREADS) segsum_kernel(SegSumArgs a) {
+// of synchronising the eight waves twice per pass.  Same sums in the same order.  The body of segsum_kernel and of
+// segsum_apply_kernel: they differ in the sink alone.
+template <int MODE, class SINK>
+__device__ __forceinline__ void segsum_body(const SegSumArgs& a, SINK sink) {
   extern __shared__ __attribute__((aligned(16))) float4 sred[];  // [G][dv]
   __shared__ int64_t s_off[SEG_CHUNK];
   __shared__ float s_cf[SEG_CHUNK];
   __shared__ int s_longrow[SEG_EPOCH * (SEG_THREADS / 64)];
+  // apply sink: the rows a group closed in this epoch.  A row's lanes are several waves that no barrier holds together inside an
+  // epoch, so the store that marks the row as updated waits for the epoch's barrier: no lane then still has to read the mark
+  __shared__ int s_close[SINK::kApply ? SEG_EPOCH * (SEG_THREADS / 64) : 1];
+  sink.init();
   const int nu = *a.n_uniq;
   const int dv = a.D >> 2;
   const bool wide = dv > SEG_THREADS;                 // D > 2048: one row per workgroup, column blocks
@@ -559,37 +648,41 @@ __global__ void __launch_bounds__(SEG_THREADS) segsum_kernel(SegSumArgs a) {
   const bool active = g < G;
   if (wide || G > SEG_THREADS / 64) {                 // one row per pass, the whole workgroup on it
     for (int u = blockIdx.x; u < nu; u += gridDim.x) {
-      seg_long_row<MODE>(a, u, dv, G, g, c0, active, sred, s_off, s_cf);
+      seg_long_row<MODE>(a, sink, u, dv, G, g, c0, active, sred, s_off, s_cf);
       __syncthreads();
     }
     return;
   }
   const int stride = gridDim.x * G;
-  auto bounds = [&](int u, int& s0, int& cnt) {
-    s0 = 0; cnt = 0;
-    if (active && u < nu) { s0 = a.seg_start[u]; cnt = a.seg_start[u + 1] - s0; }
+  auto bounds = [&](int u, int& s0, int& cnt, int& row) {
+    s0 = 0; cnt = 0; row = 0;
+    if (active && u < nu) {
+      s0 = a.seg_start[u]; cnt = a.seg_start[u + 1] - s0;
+      if constexpr (SINK::kApply) row = sink.row_id(u);
+    }
   };
   auto first_ids = [&](int s0, int cnt, int& i0, int& i1) {
     i0 = 0; i1 = 0;
     if (cnt > 0 && cnt <= SEG_SHORT) { i0 = a.vals[s0]; if (cnt > 1) i1 = a.vals[s0 + 1]; }
   };
   int base = blockIdx.x * G;
-  int s0C, cntC, i0C, i1C, s0B, cntB;
-  bounds(base + g, s0C, cntC);
+  int s0C, cntC, rowC, i0C, i1C, s0B, cntB, rowB;
+  bounds(base + g, s0C, cntC, rowC);
   first_ids(s0C, cntC, i0C, i1C);
-  bounds(base + stride + g, s0B, cntB);
+  bounds(base + stride + g, s0B, cntB, rowB);
   while (base < nu) {                                  // block-uniform
     int e = 0;
     for (; e < SEG_EPOCH && base < nu; ++e, base += stride) {
       const int u = base + g;
-      int s0A, cntA, i0B, i1B;
-      bounds(u + 2 * stride, s0A, cntA);               // two passes ahead
+      int s0A, cntA, rowA, i0B, i1B;
+      bounds(u + 2 * stride, s0A, cntA, rowA);         // two passes ahead
       first_ids(s0B, cntB, i0B, i1B);                  // one pass ahead
-      int longrow = -1;
+      int longrow = -1, closed = -1;
       if (active && u < nu) {
         if (cntC > SEG_SHORT) {
           longrow = u;
         } else {
+          const typename SINK::Row r = sink.begin(rowC, c0 * 4);
           float4 v[SEG_SHORT];
           float cf[SEG_SHORT];
 #pragma unroll
@@ -607,14 +700,22 @@ __global__ void __launch_bounds__(SEG_THREADS) segsum_kernel(SegSumArgs a) {
 #pragma unroll
           for (int j = 0; j < SEG_SHORT; ++j)
             if (j < cntC) { acc.x += cf[j] * v[j].x; acc.y += cf[j] * v[j].y; acc.z += cf[j] * v[j].z; acc.w += cf[j] * v[j].w; }
-          acc.x *= a.scale; acc.y *= a.scale; acc.z *= a.scale; acc.w *= a.scale;
-          *reinterpret_cast<float4*>(a.uniq_rows + (int64_t)u * a.D + c0 * 4) = acc;
+          sink.finish(a, r, u, c0 * 4, acc);
+          if constexpr (SINK::kApply) {
+            if (c0 == 0) { if (sink.closes(r)) closed = rowC; sink.lane_stale(r); }
+          }
         }
       }
-      if (active && c0 == 0) s_longrow[e * G + g] = longrow;
-      s0C = s0B; cntC = cntB; i0C = i0B; i1C = i1B; s0B = s0A; cntB = cntA;
+      if (active && c0 == 0) {
+        s_longrow[e * G + g] = longrow;
+        if constexpr (SINK::kApply) s_close[e * G + g] = closed;
+      }
+      s0C = s0B; cntC = cntB; rowC = rowB; i0C = i0B; i1C = i1B; s0B = s0A; cntB = cntA; rowB = rowA;
     }
     __syncthreads();
+    if constexpr (SINK::kApply) {
+      if ((int)threadIdx.x < e * G && s_close[threadIdx.x] >= 0) sink.mark(s_close[threadIdx.x]);
+    }
     for (int q = 0; q < e * G; ++q) {
       const int u = s_longrow[q];                      // block-uniform
       if (u < 0) continue;
@@ -625,10 +726,21 @@ __global__ void __launch_bounds__(SEG_THREADS) segsum_kernel(SegSumArgs a) {
         }
         continue;
       }
-      seg_long_row<MODE>(a, u, dv, G, g, c0, active, sred, s_off, s_cf);
+      seg_long_row<MODE>(a, sink, u, dv, G, g, c0, active, sred, s_off, s_cf);
     }
     __syncthreads();                                   // s_longrow is rewritten by the next epoch
   }
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(SEG_THREADS) segsum_kernel(SegSumArgs a) {
+  segsum_body<MODE>(a, SegStoreRows{});
+}
+
+// The segment sums with the row update done where the sum is formed: no uniq_rows store, no second launch reading it back.
+// split must be 0 (every segment is summed here).
+__global__ void __launch_bounds__(SEG_THREADS) segsum_apply_kernel(SegSumArgs a, SegApplyRows s) {
+  segsum_body<MODE_SASREC>(a, s);
 }
 
 // ---- very long segments on many workgroups (round 5) --------------------------------------------------------------------------
@@ -1004,6 +1116,38 @@ extern "C" int pxr_sasrec_occ_segsum(const void* ws, int64_t ws_bytes, int B, in
   const int grid = n < 4096 ? n : 4096;
   hipLaunchKernelGGL(segsum_kernel<MODE_SASREC>, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, (hipStream_t)stream, a);
   return pxr_check_launch("pxr_sasrec_occ_segsum");
+}
+
+// Phase 2 with the lazy AdamW row update inside (segsum_apply_kernel): what pxr_sasrec_occ_segsum(scale = 1) followed by
+// pxr_adamw_rows_f32(rows = uniq_idx, grows = uniq_rows, t_apply = t_prev + 1) leaves in table / m / v / last for rows that are
+// current through t_prev, bit for bit, in one launch and without the round trip of the summed rows through uniq_rows (which is not
+// written).  uniq_idx / n_uniq_dev: pxr_seq_occ_sort's output.  hyper: the per-step scalar table (pxr_adamw_hyper_append), entry
+// t_prev + 1 must exist.  step_dev != NULL: t_prev = *step_dev (hipGraph-replayable).  A row with last[row] != t_prev is left
+// untouched and raises PXR_STATUS_ROWS_STALE; id 0 and ids outside [0, table_rows) are skipped.
+extern "C" int pxr_sasrec_occ_segsum_apply(const void* ws, int64_t ws_bytes, int B, int L, const float* dx0, const float* out,
+                                           const float* coef, int D, int64_t n_table, const int32_t* n_uniq_dev,
+                                           const int64_t* uniq_idx, float* table, float* m, float* v, int32_t* last,
+                                           int64_t table_rows, const void* hyper, int64_t t_prev, const int64_t* step_dev,
+                                           double beta1, double beta2, double eps, void* stream) {
+  PXR_REQUIRE(ws && dx0 && out && coef && n_uniq_dev && uniq_idx && table && m && v && last && hyper,
+              "pxr_sasrec_occ_segsum_apply: null pointer");
+  PXR_REQUIRE(B > 0 && L > 0 && D > 0 && D % 4 == 0 && D <= 4096, "pxr_sasrec_occ_segsum_apply: bad shape (D <= 4096)");
+  PXR_REQUIRE(table_rows > 0 && table_rows < (1ll << 31) && t_prev >= 0 && t_prev < (1ll << 31) - 1,
+              "pxr_sasrec_occ_segsum_apply: bad table size / step");
+  const int n = 3 * B * L;
+  SortWs w;
+  if (carve(const_cast<void*>(ws), n, &w) > ws_bytes) { pxr_set_error("pxr_sasrec_occ_segsum_apply: workspace too small"); return PXR_ERR_WORKSPACE; }
+  SegSumArgs a{};
+  a.vals = sasrec_sorted_vals(w, n, n_table); a.seg_start = w.seg_start; a.n_uniq = n_uniq_dev; a.src0 = dx0; a.src1 = out;
+  a.coef = coef; a.scale = 1.f; a.D = D; a.T = B * L;
+  SegApplyRows s{};
+  s.p = table; s.m = m; s.v = v; s.last = last; s.uniq_idx = uniq_idx; s.n_table = table_rows;
+  s.hyper = (const float4*)hyper; s.step_dev = step_dev; s.t_prev = (int)t_prev; s.D = D;
+  s.c = AdamConsts{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps};
+  s.status = pxr_status_word();
+  const int grid = n < 4096 ? n : 4096;
+  hipLaunchKernelGGL(segsum_apply_kernel, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, (hipStream_t)stream, a, s);
+  return pxr_check_launch("pxr_sasrec_occ_segsum_apply");
 }
 
 // Phase 2 for big batches: the same sums with the rows of more than 1 024 occurrences cut into parts that many workgroups sum

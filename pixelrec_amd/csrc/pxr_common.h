@@ -35,6 +35,7 @@ int pxr_cu_count(void);          // api.cpp: compute units of the current device
 #define PXR_STATUS_H2_RANGE 64       /* a producer of fp16 two-plane operands (planes.cuh "h2") met a value outside the fp16 range */
 #define PXR_STATUS_H2_STALE 128      /* h2 planes written under the previous step's scale: a value outgrew its headroom and was saturated */
 #define PXR_STATUS_SHARD_OVERFLOW 16 /* row-sharded table: more hit rows owned by ONE rank than the per-pair request capacity */
+#define PXR_STATUS_ROWS_STALE 256    /* the segment sum that applies its rows met a table row that was not current: the row was left untouched */
 
 static inline int pxr_check_launch(const char* what) {
   hipError_t e = hipGetLastError();

@@ -28,6 +28,8 @@ class GraphedTrainStep:
             self.model.split_catch_up = True             # sasrec.SASRec._forward_train: fork / join are graph edges here
         if hasattr(self.model, "trust_optimizer_planes"):
             self.model.trust_optimizer_planes = True     # the captured forward has no split launch (seqcore._weight_planes)
+        if self.clip and hasattr(self.model, "fuse_row_update"):
+            self.model.fuse_row_update = False           # clipping reads (and scales) the gradient rows in front of the row update
         if hasattr(self.model, "h2_stale_scales"):
             # ... and its backward no gradient split launches (seqcore, ops.H2Sites).  An owner that manages the switch itself (the
             # Trainer: exact scales for a while after an overflow) says which it wants; None: on

@@ -147,6 +147,9 @@ class TableHooks:
 
     sparse_table_grad = None    # the table gradient of the last backward, as sparse rows
     _table_hooks = None         # the lazy optimizer (catch_up_* / flush) when one is attached
+    # False: something reads the step's gradient rows between backward() and the optimizer's step() (gradient clipping), so the
+    # backward must not apply them to the table itself (PxrAdamW.rows_apply_handle)
+    fuse_row_update = True
 
     def register_table_hooks(self, opt):
         """Attach a lazy table optimizer: it is asked to bring rows up to date before they are read."""

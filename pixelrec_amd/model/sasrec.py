@@ -242,7 +242,17 @@ class SASRec(TableHooks, SeqRecCore):
     def _after_input_grads(self, dx0, coef, s):
         sp = self._local_sparse
         self._join_sort()
-        ops.sasrec_occ_segsum(self._occ_ws, dx0, s["out"], coef, self._table_rows(), sp, 1.0, ws2=self._occ_ws2)
+        # one rank, lazy table update, every backward followed by the optimizer's step (PxrAdamW.rows_apply_handle): the rows take
+        # this step's update inside the segment-sum launch.  Not with the split route of big batches (the long rows' sums are
+        # finished by later launches) and not beside a look-ahead catch-up that may still be reading rows on its side stream
+        hooks = self._table_hooks
+        apply_rows = (hooks.rows_apply_handle() if (hasattr(hooks, "rows_apply_handle") and self._occ_ws2 is None
+                                                    and self._prefetched is None) else None)
+        if apply_rows is not None:
+            apply_rows(self._occ_ws, dx0, s["out"], coef, self._table_rows(), sp)
+        else:
+            sp.applied = False
+            ops.sasrec_occ_segsum(self._occ_ws, dx0, s["out"], coef, self._table_rows(), sp, 1.0, ws2=self._occ_ws2)
         self.sparse_table_grad = sp
         hook = getattr(self, "_sparse_ready_hook", None)
         if hook is not None:

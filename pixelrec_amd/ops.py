@@ -91,6 +91,7 @@ def device_status(device=None) -> torch.Tensor:
 
 
 STATUS_SHARD_OVERFLOW = 16      # PXR_STATUS_SHARD_OVERFLOW (csrc/pxr_common.h)
+STATUS_ROWS_STALE = 256         # PXR_STATUS_ROWS_STALE
 
 
 def clear_status_bits(device, bits: int):
@@ -162,6 +163,11 @@ def raise_on_bad_indices(device=None):
     if v & 2:
         raise RuntimeError("data-parallel row exchange: a rank's batch touched more unique table rows than the configured "
                            "exchange capacity (GradSync(exchange_rows=...)); gradient rows were dropped -- raise the bound")
+    if v & STATUS_ROWS_STALE:
+        raise RuntimeError("fused segment sum + row update: a table row of the batch was not current through the previous step "
+                           "when its gradient was applied (its update was skipped, nothing was written from stale state); the "
+                           "rows of a batch must be caught up before its backward pass -- set PXR_ROWS_FUSED=0 for the two-launch "
+                           "path, which replays such rows")
 
 
 # ------------------------------------------------------------------------------------------------ K1 gather
@@ -1324,6 +1330,9 @@ class SparseRows:
     def __init__(self, cap: int, D: int, device, packed: bool = False):
         self.cap = cap
         self.packed = None
+        # True: this step's rows were applied to the table where they were summed (sasrec_occ_segsum_apply) -- `rows` was not
+        # written and the optimizer's step() has no row launch left to do
+        self.applied = False
         if packed:
             # idx | n | rows are views of ONE buffer laid out as pxr.h's packed block, so a data-parallel exchange
             # sends it with a single all-gather (parallel.GradSync) and pxr_merge_packed_rows_f32 reads it as it is
@@ -1512,6 +1521,23 @@ def sasrec_occ_segsum(ws: torch.Tensor, dx0, out, coef, n_table, sp: SparseRows,
     _l.check(Lb.pxr_sasrec_occ_segsum(_l.ptr(ws), ws.numel(), B, L, _l.ptr(dx0), _l.ptr(out), _l.ptr(coef), D,
                                       n_table, float(scale), _l.ptr(sp.n), _l.ptr(sp.rows), _l.stream_ptr()),
              "pxr_sasrec_occ_segsum")
+
+
+def sasrec_occ_segsum_apply(ws: torch.Tensor, dx0, out, coef, n_table, sp: SparseRows, table, m, v, last, hyper, t_prev, beta1, beta2,
+                            eps, step_dev=None):
+    """Phase 2 and the lazy row update in ONE launch (pxr_sasrec_occ_segsum_apply): the sums sasrec_occ_segsum(scale=1) would leave
+    in sp.rows are applied where they are formed -- adamw_rows(t_prev, t_prev + 1, rows=sp.idx, grows=sp.rows) on rows that are
+    current through t_prev, bit for bit -- and sp.rows is NOT written.  A row that is not current is left untouched and raises
+    STATUS_ROWS_STALE.  Segments of any length on one workgroup each (no split route)."""
+    Lb = _l.load()
+    B, L, D = out.shape
+    device_status(table.device)       # a stale row flags the status word (raise_on_bad_indices)
+    with _gemm_timer(0.0, "segsum_apply_kernel (segment sums + apply: batch rows)"):
+        _l.check(Lb.pxr_sasrec_occ_segsum_apply(_l.ptr(ws), ws.numel(), B, L, _l.ptr(dx0), _l.ptr(out), _l.ptr(coef), D, n_table,
+                                                _l.ptr(sp.n), _l.ptr(sp.idx), _l.ptr(table), _l.ptr(m), _l.ptr(v), _l.ptr(last),
+                                                table.shape[0], _l.ptr(hyper), t_prev, _l.ptr(step_dev), beta1, beta2, eps,
+                                                _l.stream_ptr()),
+                 "pxr_sasrec_occ_segsum_apply")
 
 
 # ------------------------------------------------------------------------------------------------ PixelNet pieces

@@ -258,6 +258,8 @@ class PxrAdamW:
         self._cur_hyper, self._cur_for = None, None      # scalars of the step in flight, parked by catch_up_input_ids
         self._dirty = False          # lazy mode: some rows lag behind step_count (set by step, cleared by flush)
         self._seeded_cfg = None      # hyper-parameters the table entry of step_count+1 was written with (None: not yet)
+        self._early_seed = False     # that entry was (re)written by apply_rows_in_segsum, ahead of step()
+        self._applied_cfg = None     # hyper-parameters the rows of the step in flight were applied with (apply_rows_in_segsum)
         self.param_groups = [{"lr": self.lr, "weight_decay": self.weight_decay, "betas": self.betas, "eps": self.eps}]
         self.has_table = has_lazy_table(model)
         if table_update == "lazy" and self.has_table:
@@ -332,6 +334,52 @@ class PxrAdamW:
         self._cur_for = self.step_count + 1 if self._seeded_cfg is not None else None
         return True
 
+    def _cfg(self):
+        g = self.param_groups[0]
+        return (g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"])
+
+    def _seed_step(self, cfg) -> bool:
+        """The scalar-table entry of step step_count + 1, (re)written if it was not prepared with `cfg` (first step, after
+        load_state_dict, or the hyper-parameters changed since the end of the previous step).  True when it was written."""
+        if self._seeded_cfg == cfg:
+            return False
+        ops.adamw_hyper_append(self._hyper, self._cumlog, self.step_count + 1, *cfg, step_dev=self._step_dev)
+        self._seeded_cfg = cfg
+        return True
+
+    def rows_apply_handle(self):
+        """The bound `apply_rows_in_segsum` when this step's row update can run inside the segment-sum launch of the model's
+        backward (one launch and an 18 MB round trip of the summed rows less), else None.  It can when the table is updated
+        lazily, on one rank without a row exchange between the two launches, in a loop whose every backward is followed by step()
+        (the captured step and the Trainer say so with `defer_weight_grad_join`), and the knob PXR_ROWS_FUSED is not 0.  The exact
+        replay mode (PXR_LAZY_REPLAY=exact) keeps the two launches."""
+        m = self.model
+        if (self.table_update != "lazy" or not has_item_table(m) or table_spans(m)
+                or os.environ.get("PXR_ROWS_FUSED", "1") == "0" or os.environ.get("PXR_LAZY_REPLAY") == "exact"):
+            return None
+        import torch.distributed as dist
+
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            return None
+        if getattr(m, "_sparse_ready_hook", None) is not None or getattr(m, "_sharded", False):
+            return None          # a row exchange sits between the sums and the update (forced collectives on one rank included)
+        if not getattr(m, "defer_weight_grad_join", False) or not getattr(m, "fuse_row_update", True):
+            return None
+        return self.apply_rows_in_segsum
+
+    def apply_rows_in_segsum(self, ws, dx0, out, coef, n_table, sp):
+        """ops.sasrec_occ_segsum + the row launch of step() in one launch: the rows of `sp` take this step's update where their
+        gradient is summed; sp.rows is not written and sp.applied tells step() that its row launch is done."""
+        _, table = self._ensure_state()
+        cfg = self._cfg()
+        if self._seed_step(cfg):
+            self._early_seed = True
+        _, b1, b2, eps, _ = cfg
+        ops.sasrec_occ_segsum_apply(ws, dx0, out, coef, n_table, sp, table, self._tm, self._tv, self._last, self._hyper,
+                                    self.step_count, b1, b2, eps, step_dev=self._step_dev)
+        sp.applied = True
+        self._applied_cfg = cfg
+
     def flush(self):
         """Bring EVERY row up to date (before evaluation, checkpointing, or reading the table as a whole)."""
         if self.table_update != "lazy" or not self._dirty or self._last is None:
@@ -350,13 +398,11 @@ class PxrAdamW:
         if self.step_count + 2 >= HYPER_CAPACITY:
             raise RuntimeError("PxrAdamW: per-step scalar table exhausted (raise optim.HYPER_CAPACITY)")
         sd = self._step_dev
-        cfg = (g["lr"], b1, b2, g["eps"], g["weight_decay"])
-        reseeded = self._seeded_cfg != cfg
-        if self._seeded_cfg != cfg:
-            # first step, after load_state_dict, or the hyper-parameters changed since the entry of this step was
-            # prepared (at the end of the previous step): (re)write it now
-            ops.adamw_hyper_append(self._hyper, self._cumlog, self.step_count + 1, *cfg, step_dev=sd)
-            self._seeded_cfg = cfg
+        cfg = self._cfg()
+        # first step, after load_state_dict, or the hyper-parameters changed since the entry of this step was prepared (at the end
+        # of the previous step): (re)written now -- or already by the backward's fused row update
+        reseeded = self._seed_step(cfg) or self._early_seed
+        self._early_seed = False
         # table rows first, flat buffer last: the two updates are independent, and under data parallelism the flat
         # gradient's all-reduce may still be in flight (GradSync.sync(defer_flat=True)) -- it then runs under the
         # row update instead of in front of it
@@ -372,9 +418,17 @@ class PxrAdamW:
             ops.adamw_table(table, self._tm, self._tv, self._slot, sp, g["lr"], b1, b2, g["eps"], g["weight_decay"],
                             self.step_count + 1)
         elif sp is not None:
-            ops.adamw_rows(table, self._tm, self._tv, self._last, self._hyper, self._cumlog, self.step_count,
-                           self.step_count + 1, b1, b2, g["eps"], rows=sp.idx, n_rows=sp.n, max_rows=sp.cap,
-                           grows=sp.rows, step_dev=sd)
+            if getattr(sp, "applied", False):
+                # the backward's segment-sum launch applied this step to the rows already (apply_rows_in_segsum)
+                sp.applied = False
+                if self._applied_cfg != cfg:
+                    raise RuntimeError("PxrAdamW: the hyper-parameters changed between backward() and step(), and the table rows "
+                                       "of this step were already updated inside the backward pass; change them before the "
+                                       "forward pass, or set PXR_ROWS_FUSED=0")
+            else:
+                ops.adamw_rows(table, self._tm, self._tv, self._last, self._hyper, self._cumlog, self.step_count,
+                               self.step_count + 1, b1, b2, g["eps"], rows=sp.idx, n_rows=sp.n, max_rows=sp.cap,
+                               grows=sp.rows, step_dev=sd)
             self._dirty = True
             if pre is not None:
                 # rows of the NEXT batch (caught up through the previous step beside this step's GEMMs) advance through
@@ -524,6 +578,10 @@ def clip_grad_norm_(model, max_norm, norm_type=2.0, **_ignored):
     _, gflat = model.flat_parameters()
     sq = gflat.pow(2).sum()
     sp = getattr(model, "sparse_table_grad", None) if has_lazy_table(model) else None
+    if getattr(sp, "applied", False):
+        raise RuntimeError("clip_grad_norm_: the table rows of this step were updated inside the backward pass, their gradient rows "
+                           "were never written; set model.fuse_row_update = False (GraphedTrainStep(clip_grad_norm=...) and the "
+                           "Trainer do) or PXR_ROWS_FUSED=0")
     live = None
     if sp is not None:
         ar = torch.arange(sp.rows.shape[0], device=sp.rows.device, dtype=torch.int32)

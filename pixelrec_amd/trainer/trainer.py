@@ -152,6 +152,8 @@ class Trainer:
                 model.module.trust_optimizer_planes = True   # only the optimizer / load_state_dict touch the weights here
             if hasattr(model.module, "h2_stale_scales"):
                 model.module.h2_stale_scales = True          # consecutive training steps: gradient planes under the previous step's scales
+        if self.clip_grad_norm and hasattr(model.module, "fuse_row_update"):
+            model.module.fuse_row_update = False             # clipping reads the gradient rows in front of the row update
         if type(self.optimizer).__name__ == "FragmentAdamW":     # decay_check_name: host scalars per tensor, no plane upkeep
             self.use_graph = False
             if hasattr(model.module, "trust_optimizer_planes"):
