@@ -876,6 +876,42 @@ int pxr_din_topk_f32(const float* table, int N, int D, const int64_t* window, in
                      const int32_t* hist_ptr, const int64_t* hist_items, int K, int64_t* topk_idx, float* topk_val, void* ws,
                      int64_t ws_bytes, void* stream);
 
+/* ---- DSSM and FM (model/IDNet/dssm.py, fm.py; csrc/pool.hip, MODE_POOL of csrc/embed_grad.hip) ------------------------------ */
+/* Occurrences of a batch, as for DIN: o in [0, B L) = history position (b, l); o = B L + 2 b + c = target c of sample b (0
+ * positive, 1 negative).  rows int64 [B L + 2 B] = the row of `table` [n_table, D] every occurrence reads; a history entry equal
+ * to pad_row is "no item" (training: pxr_acf_rows_i64's rows over the [1 + I, D] table, pad_row 1; evaluation windows over an item
+ * matrix: the ids themselves, pad_row 0).  Any other entry outside [0, n_table) ORs bit 0 into the status word and is clamped;
+ * nothing is read out of range.  Limits of all four: D % 4 == 0, 0 < D <= 4096, L >= 1, B (L + 2) < 2^30; table, U, G and
+ * uniq_rows 16-byte aligned.  One fixed summation order (l ascending), no float atomics: bit-identical from run to run.
+ *
+ * Masked pooling (dssm.py:46-55 avg_emb, fm.py:47-55 mask_emb + the sum): U[b, :] = sum over the real positions of
+ * table[rows[b, l], :]; mean != 0 divides by (cnt + 1e-8f), cnt the number of real positions -- an fp32 division (torch.div); an
+ * empty profile gives exactly 0.  w[b] = the factor the backward multiplies a history occurrence's gradient by: 1 / (cnt + 1e-8f)
+ * (mean) or 1 (sum), and 0 for an empty profile.  rows [B, L] (only the B L history entries are read), U [B, D], w [B]. */
+int pxr_pool_rows_f32(const float* table, int64_t n_table, int D, const int64_t* rows, int64_t pad_row, int B, int L, int mean,
+                      float* U, float* w, void* stream);
+/* The step without an MLP in one launch: the pooling above (same arithmetic: U and w are bit-identical to pxr_pool_rows_f32's),
+ * x_b = <U_b, table[p_b]> - <U_b, table[n_b]> over the target rows rows[B L + 2 b + {0, 1}], lossrow[b] = -log(1e-8 + sigmoid(x_b))
+ * (the 1e-8 INSIDE the log: dssm.py:68, fm.py:66), coef[b] = d loss / d x_b, loss = the mean of lossrow in
+ * pxr_mf_pair_fwd_f32's reduction order.  rows [B L + 2 B]; U [B, D]; w, coef, lossrow [B]; loss [1].  No output may alias the
+ * table. */
+int pxr_pool_pair_fwd_f32(const float* table, int64_t n_table, int D, const int64_t* rows, int64_t pad_row, int B, int L, int mean,
+                          float* U, float* w, float* coef, float* lossrow, float* loss, void* stream);
+/* Its backward as the COMPACT gradient block G [3 B, D]: with c_b = coef[b] * grad_scale * (grad_scale_dev ? *grad_scale_dev : 1),
+ * G[b] = c_b (table[p_b] - table[n_b]) -- the gradient of U_b, ONE row for all L history occurrences of sample b --
+ * G[B + 2 b] = c_b U_b and G[B + 2 b + 1] = -c_b U_b.  The pooling weight w[b] is NOT folded in: pxr_pool_table_grad_f32 applies
+ * it.  U [B, D] as the forward wrote it; G must not alias U or the table. */
+int pxr_pool_pair_bwd_f32(const float* table, int64_t n_table, int D, const int64_t* rows, int B, int L, const float* U,
+                          const float* coef, float grad_scale, const float* grad_scale_dev, float* G, void* stream);
+/* The table gradient in sparse form from the compact block, without one row per occurrence: gidx int64 [B L + 2 B] = the table row
+ * every occurrence's gradient goes to (pxr_acf_rows_i64's gidx: 0 at padding, dropped; ids outside [0, n_table) are dropped too).
+ * Sorted as pxr_embed_grad_rows_f32 sorts its idx (same keys, same stable order), then summed in occurrence order with occurrence
+ * o < B L reading w[o / L] * G[o / L, :] and occurrence o >= B L reading G[B + (o - B L), :].  What it writes equals
+ * pxr_embed_grad_rows_f32 on the materialised [B (L + 2), D] rows up to the rounding of w * G (bit for bit where every w is 1).
+ * uniq_idx / uniq_rows hold B (L + 2) entries / rows; ws: pxr_embed_grad_ws_bytes(B (L + 2)).  uniq_rows must not alias G. */
+int pxr_pool_table_grad_f32(const int64_t* gidx, int B, int L, const float* G, const float* w, int D, int64_t n_table,
+                            int64_t* uniq_idx, float* uniq_rows, int32_t* n_uniq_dev, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,11 @@
 //        o in [T,2T)   target id items[b,0,t+1]   adds  +coef[r] * out[r,:]      (d pos_score)
 //        o in [2T,3T)  negative id items[b,1,t+1] adds  -coef[r] * out[r,:]      (d neg_score)
 //     which never materialises the [B,2,L+1,D] gather nor its gradient.
+//   MODE_POOL   : the pooled-history pair models (pool.hip), idx [B*L + 2B] = history rows | target rows, T = B*L, one COMPACT
+//        gradient block G [3B, D] (one row per sample for its whole history, one per target):
+//        o in [0,T)      history position (b, l) = o / L, o % L   adds  w[b] * G[b,:]     (the pooling weight of sample b)
+//        o in [T,T+2B)   target j = o - T                         adds  G[B + j,:]
+//     so the L copies of a sample's history gradient are never written out.
 //
 // Everything is launched with worst-case grids and reads the device-side counts, so the sequence is
 // hipGraph-capturable and needs no host synchronisation.
@@ -437,15 +442,15 @@ __global__ void __launch_bounds__(RS_THREADS) fused_segments_kernel(const int* _
 }
 
 // ------------------------------------------------------------------------------------------------ segmented sum
-enum { MODE_ROWS = 0, MODE_SASREC = 1 };
+enum { MODE_ROWS = 0, MODE_SASREC = 1, MODE_POOL = 2 };
 
 struct SegSumArgs {
   const int* vals;         // sorted occurrence ids
   const int* seg_start;    // [n_uniq + 1]
   const int* n_uniq;
-  const float* src0;       // MODE_ROWS: rows [n, D];  MODE_SASREC: dx0 [T, D]
+  const float* src0;       // MODE_ROWS: rows [n, D];  MODE_SASREC: dx0 [T, D];  MODE_POOL: G [3B, D]
   const float* src1;       // MODE_SASREC: out [T, D]
-  const float* coef;       // MODE_SASREC: [T]
+  const float* coef;       // MODE_SASREC: [T];  MODE_POOL: w [B]
   float* uniq_rows;        // [n_uniq, D]
   float scale;             // applied to the summed row (1/world_size for gradient averaging; 1 otherwise)
   int D, T;
@@ -455,7 +460,10 @@ struct SegSumArgs {
   int* big_count;          // [0] cursor, [1] the count as the parts kernel saw it
   int* big_rows;           // [big_cap]
   float* partials;         // [max_parts, D]
-  int big_cap, max_parts;
+  int big_cap;
+  // MODE_POOL is never split, so its history length L (T = B * L) takes max_parts' place: the argument block, and with it every
+  // kernel of the other modes, keeps the layout it had before this mode existed
+  union { int max_parts; int L; };
 };
 
 // 512 threads = G = 512/dv groups of dv threads (dv = D/4 float4 columns; D = 512: 4 groups of 128).
@@ -476,6 +484,10 @@ __device__ __forceinline__ void seg_resolve(const SegSumArgs& a, int o, int64_t&
   if constexpr (MODE == MODE_ROWS) {
     off = (int64_t)o * a.D;
     cf = 1.f;
+  } else if constexpr (MODE == MODE_POOL) {
+    const int b = o / a.L;                                      // only meaningful for o < T
+    off = (int64_t)(o < a.T ? b : a.T / a.L + (o - a.T)) * a.D;
+    cf = o < a.T ? a.coef[b] : 1.f;
   } else {
     const int type = o / a.T, r = o - type * a.T;
     // type 0 reads src0 (dx0); types 1/2 read src1 (out): the source is encoded in the sign bit of the offset
@@ -485,8 +497,8 @@ __device__ __forceinline__ void seg_resolve(const SegSumArgs& a, int o, int64_t&
 }
 template <int MODE>
 __device__ __forceinline__ const float* seg_row(const SegSumArgs& a, int64_t off) {
-  if constexpr (MODE == MODE_ROWS) return a.src0 + off;
-  else return off >= 0 ? a.src0 + off : a.src1 + ~off;
+  if constexpr (MODE == MODE_SASREC) return off >= 0 ? a.src0 + off : a.src1 + ~off;
+  else return a.src0 + off;
 }
 
 constexpr int SEG_EPOCH = 16;    // passes between two looks at the long rows (no barrier inside an epoch)
@@ -1063,6 +1075,37 @@ extern "C" int pxr_embed_grad_rows_f32(const int64_t* idx, int64_t n, const floa
   return pxr_check_launch("pxr_embed_grad_rows_f32");
 }
 
+// The table gradient of the pooled-history pair models (pool.hip) without one gradient row per occurrence: gidx [B L + 2 B] (the
+// row every occurrence's gradient goes to, 0 = padding: dropped) is sorted exactly as pxr_embed_grad_rows_f32 sorts its idx, and
+// the segment sum resolves occurrence o to (G row o / L, w[o / L]) for o < B L and to (G row B + (o - B L), 1) beyond (MODE_POOL).
+extern "C" int pxr_pool_table_grad_f32(const int64_t* gidx, int B, int L, const float* G, const float* w, int D, int64_t n_table,
+                                       int64_t* uniq_idx, float* uniq_rows, int32_t* n_uniq_dev, void* ws, int64_t ws_bytes,
+                                       void* stream) {
+  PXR_REQUIRE(gidx && G && w && uniq_idx && uniq_rows && n_uniq_dev && ws, "pxr_pool_table_grad_f32: null pointer");
+  PXR_REQUIRE(B > 0 && L >= 1 && (int64_t)B * (L + 2) < (1ll << 30) && D > 0 && D % 4 == 0 && D <= 4096 && n_table > 0 &&
+              n_table < (1ll << 31), "pxr_pool_table_grad_f32: bad shape (B=%d, L=%d, D=%d)", B, L, D);
+  PXR_REQUIRE((((uintptr_t)G | (uintptr_t)uniq_rows) & 15) == 0, "pxr_pool_table_grad_f32: G and uniq_rows must be 16-byte aligned");
+  PXR_REQUIRE(G != uniq_rows, "pxr_pool_table_grad_f32: uniq_rows must not alias G");
+  const int n = B * (L + 2);
+  SortWs sw;
+  if (carve(ws, n, &sw) > ws_bytes) { pxr_set_error("pxr_pool_table_grad_f32: workspace too small"); return PXR_ERR_WORKSPACE; }
+  hipStream_t st = (hipStream_t)stream;
+  const int* sorted_vals = nullptr;
+  int rc;
+  if (use_fused_sort(n)) {
+    rc = fused_sort<MODE_ROWS>(gidx, n, 0, 0, n_table, sw, uniq_idx, n_uniq_dev, st, &sorted_vals);
+  } else {
+    hipLaunchKernelGGL(occ_keys_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, st, gidx, n, sw.keysA, sw.valsA, n_table);
+    rc = sort_and_segment(sw, n, n_table, uniq_idx, n_uniq_dev, st, &sorted_vals);
+  }
+  if (rc) return rc;
+  SegSumArgs a{};
+  a.vals = sorted_vals; a.seg_start = sw.seg_start; a.n_uniq = n_uniq_dev; a.src0 = G; a.coef = w; a.uniq_rows = uniq_rows;
+  a.scale = 1.f; a.D = D; a.T = B * L; a.L = L;
+  const int grid = n < 4096 ? n : 4096;
+  hipLaunchKernelGGL(segsum_kernel<MODE_POOL>, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, st, a);
+  return pxr_check_launch("pxr_pool_table_grad_f32");
+}
 
 // Phase 1 of the table gradient: occurrence keys -> stable sort -> unique ids + segments.  Depends on `items` only, so it can
 // run BEFORE the forward pass (the lazy table optimizer needs the unique rows of the batch to bring them up to date before they

@@ -20,7 +20,8 @@ from .dataset import (AcfEvalBatcher, BERT4RecTrainBatcher, CuratorTrainBatcher,
 
 SUPPORTED = {"SASRec": "SEQ", "MOSASRec": "SEQ", "FSASRec": "SEQ", "GRU4Rec": "SEQ", "NextItNet": "SEQ",
              "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR", "MF": "PAIR", "VBPR": "PAIR",
-             "SRGNN": "AUGSEQ", "LightSANs": "TWOTOWER", "ACF": "SEQ", "VISRANK": "EVALONLY", "CuratorNet": "SEQ", "DIN": "SEQ"}      # REC/data/utils.py:24-31
+             "SRGNN": "AUGSEQ", "LightSANs": "TWOTOWER", "ACF": "SEQ", "VISRANK": "EVALONLY", "CuratorNet": "SEQ", "DIN": "SEQ",
+             "DSSM": "SEQ", "FM": "SEQ"}      # REC/data/utils.py:24-33
 
 
 def load_data(config):
@@ -96,10 +97,14 @@ def bulid_dataloader(config, dataload):
                 GraphEvalBatcher(config, dataload, phase="test", rank=rank, world=world))
     # BERT4Rec masks its windows (REC/data/utils.py:25: BERT4RecTrainDataset); LightSANs (AUGSEQ, so Data built every prefix)
     # reads TwoTowerTrainDataset's rows of those prefixes (:35); CuratorNet (:39 names a TwoTowerTrainDataset2 that does not exist)
-    # reads the same row format over the SEQ chunks; DIN (:33 SampleTwoTowerTrainDataset) reads ACF's leave-one-out samples without the
-    # user id; evaluation is SeqEvalDataset's for all of them (DIN: CandiEvalDataset's per-item repetition happens inside the kernel)
+    # reads the same row format over the SEQ chunks; DIN and DSSM (:31-32 SampleTwoTowerTrainDataset) and FM (:33
+    # SampleOneTowerTrainDataset: the same samples as [profile | positive], [profile | negative] planes) read ACF's leave-one-out
+    # samples without the user id -- a batch is `train_batch_size` samples (ACF's decision) where the reference stacks
+    # `train_batch_size` chunks; evaluation is SeqEvalDataset's for all of them (DIN: CandiEvalDataset's per-item repetition happens
+    # inside the kernel)
     batcher = {"BERT4Rec": BERT4RecTrainBatcher, "LightSANs": TwoTowerTrainBatcher,
-               "ACF": SampleAcfTrainBatcher, "CuratorNet": CuratorTrainBatcher, "DIN": DinTrainBatcher}.get(model_name, SeqTrainBatcher)
+               "ACF": SampleAcfTrainBatcher, "CuratorNet": CuratorTrainBatcher, "DIN": DinTrainBatcher, "DSSM": DinTrainBatcher,
+               "FM": DinTrainBatcher}.get(model_name, SeqTrainBatcher)
     train_loader = _TrainLoader(batcher(config, dataload, rank=rank, world=world))
     if model_name == "ACF":
         # SampleACFTrainDataset / ACFEvalDataset (REC/data/utils.py:24-31): leave-one-out samples of the chunks; windows + user id

@@ -2703,3 +2703,97 @@ def din_topk(table, window, aq, bm, cm, w2, b2, wd, bd, K: int, hist_ptr=None, h
                                      _l.ptr(idx[lo:hi]), _l.ptr(val[lo:hi]), _l.ptr(ws), ws_bytes, _l.stream_ptr()),
                  "pxr_din_topk_f32")
     return idx, val
+
+
+# ------------------------------------------------------------------------------------------------ DSSM / FM (csrc/pool.hip)
+def _pool_shapes(table, rows, B: int, L: int, n_rows: int, who: str):
+    _req(table, torch.float32, "table"); _req(rows, torch.int64, "rows")
+    if table.dim() != 2:
+        raise _l.PxrError(f"{who}: table must be [rows, D], got {tuple(table.shape)}")
+    D = table.shape[1]
+    if D <= 0 or D % 4 or D > 4096:
+        raise _l.PxrError(f"{who}: need D % 4 == 0 and 0 < D <= 4096, got D={D}")
+    if B < 1 or L < 1 or rows.numel() != n_rows:
+        raise _l.PxrError(f"{who}: rows must hold {n_rows} entries for B={B}, L={L} (L >= 1), got {rows.numel()}")
+    return D
+
+
+def _pool_out(t, shape, device, name: str):
+    if t is None:
+        return torch.empty(*shape, dtype=torch.float32, device=device)
+    _req(t, torch.float32, name)
+    if tuple(t.shape) != tuple(shape):
+        raise _l.PxrError(f"pool: {name} must be float32 {list(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def pool_rows(table, rows, B: int, L: int, mean: bool, pad_row: int = 1, U=None, w=None):
+    """Masked pooling (pxr_pool_rows_f32): table [T, D], rows int64 [B, L] (a longer list's first B L entries) whose entries equal
+    to pad_row are "no item" -> (U [B, D] = the sum over the real positions, divided by (cnt + 1e-8) when mean; w [B] = the
+    backward's factor: 1 / (cnt + 1e-8) or 1, and 0 for an empty profile).  din_rows' rows over the [1 + I, D] table: pad_row 1;
+    evaluation windows over an item matrix: pad_row 0.  A bad id flags the status word (ops.raise_on_bad_indices) and is clamped."""
+    if rows.numel() < B * L:
+        raise _l.PxrError(f"pool rows: rows must hold at least B L = {B * L} entries, got {rows.numel()}")
+    D = _pool_shapes(table, rows, B, L, rows.numel(), "pool rows")
+    U = _pool_out(U, (B, D), table.device, "U")
+    w = _pool_out(w, (B,), table.device, "w")
+    device_status(table.device)
+    _l.check(_l.load().pxr_pool_rows_f32(_l.ptr(table), table.shape[0], D, _l.ptr(rows), int(pad_row), B, L, int(bool(mean)),
+                                         _l.ptr(U), _l.ptr(w), _l.stream_ptr()), "pxr_pool_rows_f32")
+    if _CHECK_IDX:
+        raise_on_bad_indices(table.device)
+    return U, w
+
+
+def pool_pair_fwd(table, rows, B: int, L: int, mean: bool, pad_row: int = 1, U=None, w=None, out=None):
+    """The pooled pair step without an MLP in one launch (pxr_pool_pair_fwd_f32): rows int64 [B L + 2 B] (din_rows) ->
+    (loss [1] = -mean log(1e-8 + sigmoid(x_b)), coef [B] = d loss / d x_b, U [B, D], w [B], lossrow [B]).  out: a float32
+    [2B + 1] buffer (coef | lossrow | loss) to reuse."""
+    D = _pool_shapes(table, rows, B, L, B * (L + 2), "pool pair forward")
+    U = _pool_out(U, (B, D), table.device, "U")
+    w = _pool_out(w, (B,), table.device, "w")
+    f = _pool_out(out, (2 * B + 1,), table.device, "out")
+    coef, lossrow, loss = f[:B], f[B:2 * B], f[2 * B:]
+    device_status(table.device)
+    _l.check(_l.load().pxr_pool_pair_fwd_f32(_l.ptr(table), table.shape[0], D, _l.ptr(rows), int(pad_row), B, L, int(bool(mean)),
+                                             _l.ptr(U), _l.ptr(w), _l.ptr(coef), _l.ptr(lossrow), _l.ptr(loss), _l.stream_ptr()),
+             "pxr_pool_pair_fwd_f32")
+    return loss, coef, U, w, lossrow
+
+
+def pool_pair_bwd(table, rows, B: int, L: int, U, coef, grad_scale=1.0, grad_scale_dev=None, G=None):
+    """The pair head's backward as the compact block G [3B, D] (pxr_pool_pair_bwd_f32): G[b] = c_b (e[p_b] - e[n_b]),
+    G[B + 2b] = c_b U_b, G[B + 2b + 1] = -c_b U_b with c_b = coef[b] grad_scale grad_scale_dev[0]; the pooling weight is applied
+    by pool_table_grad."""
+    D = _pool_shapes(table, rows, B, L, B * (L + 2), "pool pair backward")
+    _req(U, torch.float32, "U"); _req(coef, torch.float32, "coef")
+    if tuple(U.shape) != (B, D) or coef.numel() != B:
+        raise _l.PxrError(f"pool pair backward: U must be [B, D] = [{B}, {D}] and coef [B]")
+    if grad_scale_dev is not None:
+        _req(grad_scale_dev, torch.float32, "grad_scale_dev")
+    G = _pool_out(G, (3 * B, D), table.device, "G")
+    device_status(table.device)
+    _l.check(_l.load().pxr_pool_pair_bwd_f32(_l.ptr(table), table.shape[0], D, _l.ptr(rows), B, L, _l.ptr(U), _l.ptr(coef),
+                                             float(grad_scale), _l.ptr(grad_scale_dev), _l.ptr(G), _l.stream_ptr()),
+             "pxr_pool_pair_bwd_f32")
+    return G
+
+
+def pool_table_grad(gidx, B: int, L: int, G, w, n_table: int, out: SparseRows | None = None) -> SparseRows:
+    """The table gradient from the compact block (pxr_pool_table_grad_f32): gidx int64 [B L + 2 B] (din_rows; 0 = padding, dropped),
+    G [3B, D], w [B] -> SparseRows(cap >= B (L + 2)).  Occurrence o < B L adds w[o / L] G[o / L], occurrence o >= B L adds
+    G[B + o - B L]: what embed_grad_rows gives on the materialised [B (L + 2), D] rows, which are never built."""
+    Lb = _l.load()
+    _req(gidx, torch.int64, "gidx"); _req(G, torch.float32, "G"); _req(w, torch.float32, "w")
+    n = B * (L + 2)
+    if B < 1 or L < 1 or gidx.numel() != n or G.dim() != 2 or G.shape[0] != 3 * B or w.numel() != B:
+        raise _l.PxrError(f"pool table grad: need gidx [B (L + 2)] = [{n}], G [3B, D] and w [B] for B={B}, L={L}")
+    D = G.shape[1]
+    sp = out if out is not None else SparseRows(n, D, G.device)
+    if sp.cap < n or sp.rows.shape[1] != D:
+        raise _l.PxrError(f"pool table grad: out must hold {n} rows of width {D}")
+    ws_bytes = int(Lb.pxr_embed_grad_ws_bytes(n))
+    ws = _ws.get(ws_bytes, G.device)
+    _l.check(Lb.pxr_pool_table_grad_f32(_l.ptr(gidx), B, L, _l.ptr(G), _l.ptr(w), D, int(n_table), _l.ptr(sp.idx), _l.ptr(sp.rows),
+                                        _l.ptr(sp.n), _l.ptr(ws), ws_bytes, _l.stream_ptr()), "pxr_pool_table_grad_f32")
+    return sp
