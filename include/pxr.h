@@ -912,6 +912,47 @@ int pxr_pool_pair_bwd_f32(const float* table, int64_t n_table, int D, const int6
 int pxr_pool_table_grad_f32(const int64_t* gidx, int B, int L, const float* G, const float* w, int D, int64_t n_table,
                             int64_t* uniq_idx, float* uniq_rows, int32_t* n_uniq_dev, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- WideDeep (model/IDNet/widedeep.py with MLPLayers, model/layers.py:239-281; csrc/widedeep.hip) ------------------------- */
+/* Rows of every [2 B, *] operand: r = 2 b + c, c = 0 the plane [profile_b | positive], c = 1 the plane [profile_b | negative]
+ * (widedeep.py:55 view(batch_size * 2, -1)).  The first Linear W1 [h1, (L + 1) D] splits over the concatenation into the history
+ * block W1[:, :L D] and the target block W1[:, L D:]; the two planes of a sample share the history, so its product is made once.
+ * Join (widedeep.py:56, the first Dropout(0) / Linear / ReLU of MLPLayers): zh [B, h1] = Xh W1[:, :L D]^T, zt [2 B, h1] =
+ * Xt W1[:, L D:]^T (library GEMMs) -> a1[r, :] = relu(zh[r / 2] + zt[r] + b1), der = [a1 > 0] (what the backward multiplies by). */
+int pxr_wd_join_f32(const float* zh, const float* zt, const float* b1, int B, int h1, float* a1, float* der, void* stream);
+/* Its backward towards the shared history product: dzh[b, :] = dz1[2 b, :] + dz1[2 b + 1, :]   (autograd of widedeep.py:55-56). */
+int pxr_wd_join_bwd_f32(const float* dz1, int B, int h1, float* dzh, void* stream);
+/* Head forward (widedeep.py:53 the wide sum, :57 deep_predict_layer, :60-62 the loss) in the cancelled form: the history's wide
+ * terms, wide_bias and the predict bias are the same in both planes of a sample, so
+ *   x_b = <alast[2 b] - alast[2 b + 1], wp> + wide[p_b] - wide[n_b],   loss = -mean_b log(1e-8 + sigmoid(x_b)),
+ * alast [2 B, hl] the last hidden layer's activations, wp [hl] = deep_predict_layer.weight, wide [n_items] =
+ * wide_item_embedding.weight, target int64 [B, 2] = (p_b, n_b).  head [1 + 2 B] = loss | coef [B] = d loss / d x_b | x [B].  A
+ * target outside [0, n_items) ORs bit 0 into the status word and is clamped.  One fixed reduction order. */
+int pxr_wd_head_fwd_f32(const float* alast, const float* wp, const float* wide, int64_t n_items, const int64_t* target, int B,
+                        int hl, float* head, void* stream);
+/* Head backward (autograd of the above), g = grad_scale * grad_scale_dev[0]: dz [2 B, hl] = (c ? -g : g) coef_b wp act' (dact =
+ * the derivative the forward saved), dwp [hl] = sum_b g coef_b (alast[2 b] - alast[2 b + 1]) in ascending b, dbp [1] and
+ * dwide_bias [1] exactly 0 (both cancel in x_b), dwide [n_items] dense: zero except + g coef_b at p_b and - g coef_b at n_b, the
+ * occurrences of one id summed in ascending 2 b + c; entry 0 (padding_idx) and flagged ids get nothing.  No float atomics. */
+int pxr_wd_head_bwd_f32(const float* alast, const float* dact, const float* wp, const int64_t* target, int64_t n_items,
+                        const float* head, int B, int hl, float grad_scale, const float* grad_scale_dev, float* dz, float* dwp,
+                        float* dbp, float* dwide, float* dwide_bias, void* stream);
+/* Workspace of the call below in bytes; -1 outside the fused limits (h1 % 4 == 0, 4 <= h1 <= 128, 0 <= h2 <= 128, 1 <= L <= 64,
+ * 1 <= K <= 32).  Grows with B, K and the number of item splits only. */
+int64_t pxr_wd_topk_ws_bytes(int B, int L, int N, int h1, int h2, int K);
+/* Fused WideDeep evaluation (widedeep.py:66-79 predict over CandiEvalDataset's [item_num, L + 1] id matrix per user +
+ * trainer.py:333-336 masks + the collector's torch.topk) on the factorised first Linear: T [N, h1] = deep W1[:, L D:]^T + b1,
+ * hb [B, h1] = sum_l W1[:, l D:(l + 1) D] deep[window[b, l]] (padding reads row 0, like the reference), and per user
+ *   s_b = sum_l wide[window[b, l]] + wide_bias + bp,
+ *   score[b, n] = s_b + wide[n] + <wp, relu(W2 relu(T[n] + hb[b]) + b2)>      (h2 == 0: <wp, relu(T[n] + hb[b])>)
+ * with w2 [h2, h1], b2 [h2], wp [h_last], wide [N], wide_bias / bp [1].  score[b, 0] = -inf and score[b, i] = -inf for i in
+ * hist_items[hist_ptr[b] .. hist_ptr[b + 1]) (the CSR of pxr_score_topk_f32; may be NULL); topk_idx int64 / topk_val [B, K] = the
+ * K best, descending (fewer than K unmasked items: id -1, value -inf).  No [B, N, *] value reaches memory.  A window or history
+ * id outside [0, N) ORs bit 0 into the status word and leaves both outputs untouched; nothing is read out of range. */
+int pxr_wd_topk_f32(const float* T, int N, int h1, const float* hb, const int64_t* window, int B, int L, const float* wide,
+                    const float* wide_bias, const float* w2, const float* b2, int h2, const float* wp, const float* bp,
+                    const int32_t* hist_ptr, const int64_t* hist_items, int K, int64_t* topk_idx, float* topk_val, void* ws,
+                    int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,7 @@ from .dataset import (AcfEvalBatcher, BERT4RecTrainBatcher, CuratorTrainBatcher,
 SUPPORTED = {"SASRec": "SEQ", "MOSASRec": "SEQ", "FSASRec": "SEQ", "GRU4Rec": "SEQ", "NextItNet": "SEQ",
              "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR", "MF": "PAIR", "VBPR": "PAIR",
              "SRGNN": "AUGSEQ", "LightSANs": "TWOTOWER", "ACF": "SEQ", "VISRANK": "EVALONLY", "CuratorNet": "SEQ", "DIN": "SEQ",
-             "DSSM": "SEQ", "FM": "SEQ"}      # REC/data/utils.py:24-33
+             "DSSM": "SEQ", "FM": "SEQ", "WideDeep": "SEQ"}      # REC/data/utils.py:24-33
 
 
 def load_data(config):
@@ -104,7 +104,7 @@ def bulid_dataloader(config, dataload):
     # inside the kernel)
     batcher = {"BERT4Rec": BERT4RecTrainBatcher, "LightSANs": TwoTowerTrainBatcher,
                "ACF": SampleAcfTrainBatcher, "CuratorNet": CuratorTrainBatcher, "DIN": DinTrainBatcher, "DSSM": DinTrainBatcher,
-               "FM": DinTrainBatcher}.get(model_name, SeqTrainBatcher)
+               "FM": DinTrainBatcher, "WideDeep": CuratorTrainBatcher}.get(model_name, SeqTrainBatcher)
     train_loader = _TrainLoader(batcher(config, dataload, rank=rank, world=world))
     if model_name == "ACF":
         # SampleACFTrainDataset / ACFEvalDataset (REC/data/utils.py:24-31): leave-one-out samples of the chunks; windows + user id

@@ -2797,3 +2797,128 @@ def pool_table_grad(gidx, B: int, L: int, G, w, n_table: int, out: SparseRows | 
     _l.check(Lb.pxr_pool_table_grad_f32(_l.ptr(gidx), B, L, _l.ptr(G), _l.ptr(w), D, int(n_table), _l.ptr(sp.idx), _l.ptr(sp.rows),
                                         _l.ptr(sp.n), _l.ptr(ws), ws_bytes, _l.stream_ptr()), "pxr_pool_table_grad_f32")
     return sp
+
+
+# ------------------------------------------------------------------------------------------------ WideDeep (csrc/widedeep.hip)
+def _wd_out(t, shape, device, name: str):
+    if t is None:
+        return torch.empty(*shape, dtype=torch.float32, device=device)
+    _req(t, torch.float32, name)
+    if tuple(t.shape) != tuple(shape):
+        raise _l.PxrError(f"widedeep: {name} must be float32 {list(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def wd_join(zh, zt, b1, a1=None, der=None):
+    """The split first Linear joined (pxr_wd_join_f32): zh [B, h1] the history product, zt [2 B, h1] the target product, b1 [h1] ->
+    (a1 [2 B, h1] = relu(zh[r / 2] + zt[r] + b1), der = [a1 > 0])."""
+    for t, n in ((zh, "zh"), (zt, "zt"), (b1, "b1")):
+        _req(t, torch.float32, n)
+    if zh.dim() != 2 or zt.dim() != 2 or zt.shape[0] != 2 * zh.shape[0] or zt.shape[1] != zh.shape[1] or b1.numel() != zh.shape[1]:
+        raise _l.PxrError(f"widedeep join: need zh [B, h1], zt [2 B, h1], b1 [h1]; got {tuple(zh.shape)}, {tuple(zt.shape)}, "
+                          f"{tuple(b1.shape)}")
+    B, h1 = zh.shape
+    a1 = _wd_out(a1, (2 * B, h1), zh.device, "a1")
+    der = _wd_out(der, (2 * B, h1), zh.device, "der")
+    _l.check(_l.load().pxr_wd_join_f32(_l.ptr(zh), _l.ptr(zt), _l.ptr(b1), B, h1, _l.ptr(a1), _l.ptr(der), _l.stream_ptr()),
+             "pxr_wd_join_f32")
+    return a1, der
+
+
+def wd_join_bwd(dz1, dzh=None):
+    """dzh[b] = dz1[2 b] + dz1[2 b + 1] (pxr_wd_join_bwd_f32): dz1 [2 B, h1] -> dzh [B, h1]."""
+    _req(dz1, torch.float32, "dz1")
+    if dz1.dim() != 2 or dz1.shape[0] % 2:
+        raise _l.PxrError(f"widedeep join backward: dz1 must be [2 B, h1], got {tuple(dz1.shape)}")
+    B, h1 = dz1.shape[0] // 2, dz1.shape[1]
+    dzh = _wd_out(dzh, (B, h1), dz1.device, "dzh")
+    _l.check(_l.load().pxr_wd_join_bwd_f32(_l.ptr(dz1), B, h1, _l.ptr(dzh), _l.stream_ptr()), "pxr_wd_join_bwd_f32")
+    return dzh
+
+
+def _wd_head_shapes(alast, wp, target, who: str):
+    _req(alast, torch.float32, "alast"); _req(wp, torch.float32, "wp"); _req(target, torch.int64, "target")
+    if target.dim() != 2 or target.shape[1] != 2 or alast.dim() != 2 or alast.shape[0] != 2 * target.shape[0] or wp.numel() != alast.shape[1]:
+        raise _l.PxrError(f"{who}: need alast [2 B, hl], wp [hl], target int64 [B, 2]; got {tuple(alast.shape)}, {tuple(wp.shape)}, "
+                          f"{tuple(target.shape)}")
+    return target.shape[0], alast.shape[1]
+
+
+def wd_head_fwd(alast, wp, wide, target, head=None):
+    """Head forward in the cancelled form (pxr_wd_head_fwd_f32): alast [2 B, hl], wp [hl], wide [I], target int64 [B, 2] ->
+    (loss [1], head [1 + 2 B] = loss | coef | x).  A bad target flags the status word (ops.raise_on_bad_indices) and is clamped."""
+    B, hl = _wd_head_shapes(alast, wp, target, "widedeep head")
+    _req(wide, torch.float32, "wide")
+    head = _wd_out(head, (1 + 2 * B,), alast.device, "head")
+    device_status(alast.device)
+    _l.check(_l.load().pxr_wd_head_fwd_f32(_l.ptr(alast), _l.ptr(wp), _l.ptr(wide), wide.numel(), _l.ptr(target), B, hl,
+                                           _l.ptr(head), _l.stream_ptr()), "pxr_wd_head_fwd_f32")
+    return head[:1], head
+
+
+def wd_head_bwd(alast, dact, wp, target, head, dwp, dbp, dwide, dwide_bias, grad_scale=1.0, grad_scale_dev=None, dz=None):
+    """Head backward (pxr_wd_head_bwd_f32) -> dz [2 B, hl]; dwp [hl], dbp [1], dwide [I] (dense, zero off the targets) and
+    dwide_bias [1] are written in place (the two biases exactly 0: they cancel in x_b)."""
+    B, hl = _wd_head_shapes(alast, wp, target, "widedeep head backward")
+    for t, n in ((dact, "dact"), (head, "head"), (dwp, "dwp"), (dbp, "dbp"), (dwide, "dwide"), (dwide_bias, "dwide_bias")):
+        _req(t, torch.float32, n)
+    if dact.shape != alast.shape or head.numel() != 1 + 2 * B or dwp.numel() != hl or dbp.numel() != 1 or dwide_bias.numel() != 1:
+        raise _l.PxrError("widedeep head backward: dact must be [2 B, hl], head [1 + 2 B], dwp [hl], dbp / dwide_bias [1]")
+    gsd = grad_scale_dev if grad_scale_dev is not None else torch.ones(1, dtype=torch.float32, device=alast.device)
+    dz = _wd_out(dz, (2 * B, hl), alast.device, "dz")
+    _l.check(_l.load().pxr_wd_head_bwd_f32(_l.ptr(alast), _l.ptr(dact), _l.ptr(wp), _l.ptr(target), dwide.numel(), _l.ptr(head), B, hl,
+                                           float(grad_scale), _l.ptr(gsd), _l.ptr(dz), _l.ptr(dwp), _l.ptr(dbp), _l.ptr(dwide),
+                                           _l.ptr(dwide_bias), _l.stream_ptr()), "pxr_wd_head_bwd_f32")
+    return dz
+
+
+WD_MAX_HIDDEN, WD_MAX_L = 128, 64
+
+
+def wd_topk_supported(hidden, L: int, K: int = 10) -> bool:
+    """Whether pxr_wd_topk_f32 takes this shape: one or two hidden layers of at most 128 units (the first a multiple of 4), L <= 64,
+    K <= 32."""
+    hidden = list(hidden)
+    if len(hidden) not in (1, 2):
+        return False
+    h1, h2 = hidden[0], (hidden[1] if len(hidden) == 2 else 0)
+    return int(_l.load().pxr_wd_topk_ws_bytes(1, int(L), 1, int(h1), int(h2), int(K))) >= 0 and (len(hidden) == 1 or h2 >= 1)
+
+
+def wd_topk(T, hb, window, wide, wide_bias, w2, b2, wp, bp, K: int, hist_ptr=None, hist_items=None):
+    """Fused WideDeep scoring + masks + top-K (pxr_wd_topk_f32): T [N, h1] = deep W1t^T + b1, hb [B, h1] = W1h xh_b, window int64
+    [B, L] left-padded with 0, wide [N], wide_bias [1], w2 [h2, h1] / b2 [h2] or None (one hidden layer), wp [h_last], bp [1],
+    hist_ptr int32 [B + 1] / hist_items int64 the CSR of the full histories.  Returns (topk_idx int64 [B, K], topk_val fp32 [B, K]).
+    Bad ids flag the status word (ops.raise_on_bad_indices) and leave both outputs untouched."""
+    Lb = _l.load()
+    for t, n in ((T, "T"), (hb, "hb"), (wide, "wide"), (wide_bias, "wide_bias"), (wp, "wp"), (bp, "bp")):
+        _req(t, torch.float32, n)
+    _req(window, torch.int64, "window")
+    if T.dim() != 2 or window.dim() != 2:
+        raise _l.PxrError("widedeep top-k: T must be [N, h1] and window [B, L]")
+    N, h1 = T.shape
+    B, L = window.shape
+    h2 = 0
+    if w2 is not None:
+        _req(w2, torch.float32, "w2"); _req(b2, torch.float32, "b2")
+        h2 = w2.shape[0]
+        if tuple(w2.shape) != (h2, h1) or b2.numel() != h2:
+            raise _l.PxrError(f"widedeep top-k: w2 must be [h2, h1] = [{h2}, {h1}] and b2 [h2]")
+    if tuple(hb.shape) != (B, h1) or wide.numel() != N or wide_bias.numel() != 1 or wp.numel() != (h2 or h1) or bp.numel() != 1:
+        raise _l.PxrError(f"widedeep top-k: need hb [B, h1], wide [N], wp [h_last], wide_bias / bp [1] (B={B}, N={N}, h1={h1}, h2={h2})")
+    if hist_ptr is not None:
+        _req(hist_ptr, torch.int32, "hist_ptr"); _req(hist_items, torch.int64, "hist_items")
+        if hist_ptr.numel() != B + 1:
+            raise _l.PxrError(f"widedeep top-k: hist_ptr must have B + 1 = {B + 1} entries")
+    ws_bytes = int(Lb.pxr_wd_topk_ws_bytes(B, L, N, h1, h2, K))
+    if ws_bytes < 0:
+        raise _l.PxrError(f"widedeep top-k: outside the fused limits (hidden widths up to 128, the first a multiple of 4, L <= 64, "
+                          f"K <= 32): hidden=({h1}, {h2}), L={L}, K={K}")
+    device_status(T.device)
+    idx = torch.empty(B, K, dtype=torch.int64, device=T.device)
+    val = torch.empty(B, K, dtype=torch.float32, device=T.device)
+    ws = _ws.get(ws_bytes, T.device)
+    _l.check(Lb.pxr_wd_topk_f32(_l.ptr(T), N, h1, _l.ptr(hb), _l.ptr(window), B, L, _l.ptr(wide), _l.ptr(wide_bias), _l.ptr(w2),
+                                _l.ptr(b2), h2, _l.ptr(wp), _l.ptr(bp), _l.ptr(hist_ptr), _l.ptr(hist_items), K, _l.ptr(idx),
+                                _l.ptr(val), _l.ptr(ws), ws_bytes, _l.stream_ptr()), "pxr_wd_topk_f32")
+    return idx, val
