@@ -911,6 +911,15 @@ int pxr_pool_pair_bwd_f32(const float* table, int64_t n_table, int D, const int6
  * uniq_idx / uniq_rows hold B (L + 2) entries / rows; ws: pxr_embed_grad_ws_bytes(B (L + 2)).  uniq_rows must not alias G. */
 int pxr_pool_table_grad_f32(const int64_t* gidx, int B, int L, const float* G, const float* w, int D, int64_t n_table,
                             int64_t* uniq_idx, float* uniq_rows, int32_t* n_uniq_dev, void* ws, int64_t ws_bytes, void* stream);
+/* The same gradient as a DENSE block over a batch-local row space (MODSSM / MOFM: the rows are the visual encoder's outputs for the
+ * batch's distinct images, row 0 the zero image = "no item"): same inputs, same sort and the same segment sums in the same order,
+ * written to d_rows[row, :] for every referenced row in (0, n_rows) -- bit for bit what pxr_pool_table_grad_f32 puts into
+ * uniq_rows for that row.  Every other row of d_rows [n_rows, D] (row 0, unreferenced rows) is exactly +0.0 when the call returns,
+ * whatever it held before: the entry zeroes the block itself.  Ids equal to 0 or outside [0, n_rows) are dropped.  No float
+ * atomics, no [B (L + 2), D] buffer.  Limits: D % 4 == 0, 0 < D <= 4096, L >= 1, B (L + 2) < 2^30, 16-byte aligned G and d_rows;
+ * ws: pxr_embed_grad_ws_bytes(B (L + 2)) (it also holds the unique-row list).  d_rows must not overlap G. */
+int pxr_pool_dense_grad_f32(const int64_t* gidx, int B, int L, const float* G, const float* w, int D, int64_t n_rows, float* d_rows,
+                            void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- WideDeep (model/IDNet/widedeep.py with MLPLayers, model/layers.py:239-281; csrc/widedeep.hip) ------------------------- */
 /* Rows of every [2 B, *] operand: r = 2 b + c, c = 0 the plane [profile_b | positive], c = 1 the plane [profile_b | negative]

@@ -18,7 +18,9 @@
 //        gradient block G [3B, D] (one row per sample for its whole history, one per target):
 //        o in [0,T)      history position (b, l) = o / L, o % L   adds  w[b] * G[b,:]     (the pooling weight of sample b)
 //        o in [T,T+2B)   target j = o - T                         adds  G[B + j,:]
-//     so the L copies of a sample's history gradient are never written out.
+//     so the L copies of a sample's history gradient are never written out.  The same sums land either in sparse rows
+//     (pxr_pool_table_grad_f32) or in a dense [n_rows, D] block over a batch-local row space (pxr_pool_dense_grad_f32: the "table"
+//     is the visual encoder's output of the batch, whose gradient autograd takes dense).
 //
 // Everything is launched with worst-case grids and reads the device-side counts, so the sequence is
 // hipGraph-capturable and needs no host synchronisation.
@@ -507,11 +509,14 @@ constexpr int SEG_EPOCH = 16;    // passes between two looks at the long rows (n
 //   SegStoreRows : uniq_rows[u,:] = scale * sum -- the table gradient as sparse rows, for an exchange or a later row update;
 //   SegApplyRows : the lazy AdamW step of table row uniq_idx[u] with the sum as its gradient (adam_row.cuh), for a row that is
 //                  current through the step before; nothing is written to uniq_rows.
+//   SegStoreDense: d_rows[uniq_idx[u],:] = sum -- the gradient as a dense block whose other rows the entry point has zeroed;
+//                  nothing is written to uniq_rows.
+// kRowId: the sink needs the row's id (row_id) and not only its rank u among the unique rows.
 // A sink names the row (row_id), reads what it needs of it as soon as the row is known (begin: the loads then travel under the
 // occurrence loads instead of behind them), takes the sum of one float4 column (finish) and, once EVERY lane of the row has
 // called begin, closes the row from one lane (mark).
 struct SegStoreRows {
-  static constexpr bool kApply = false;
+  static constexpr bool kApply = false, kRowId = false;
   struct Row {};
   __device__ __forceinline__ void init() {}
   __device__ __forceinline__ int row_id(int) const { return 0; }
@@ -525,7 +530,7 @@ struct SegStoreRows {
 };
 
 struct SegApplyRows {
-  static constexpr bool kApply = true;
+  static constexpr bool kApply = true, kRowId = true;
   float* p; float* m; float* v; int* last;
   const int64_t* uniq_idx;       // [n_uniq] table row of unique id u (0: padding, skipped like a row outside the table)
   int64_t n_table;               // rows of p / m / v / last
@@ -574,12 +579,32 @@ struct SegApplyRows {
   __device__ __forceinline__ void mark(int row) const { adam_row_mark(last, row, t_prev + 1); }
 };
 
+struct SegStoreDense {
+  static constexpr bool kApply = false, kRowId = true;
+  float* d_rows;                 // [n_rows, D]
+  const int64_t* uniq_idx;       // [n_uniq] row of unique id u: in (0, n_rows) by the sort's keys; anything else is dropped
+  int64_t n_rows;
+  int D;
+  struct Row { int64_t o; bool ok; };
+  __device__ __forceinline__ void init() {}
+  __device__ __forceinline__ int row_id(int u) const { return (int)uniq_idx[u]; }
+  __device__ __forceinline__ Row begin(int row, int col) const {
+    return Row{(int64_t)row * D + col, row > 0 && (int64_t)row < n_rows};
+  }
+  // the plain sum: MODE_POOL's scale is 1
+  __device__ __forceinline__ void finish(const SegSumArgs&, const Row& r, int, int, const float4 acc) const {
+    if (r.ok) *reinterpret_cast<float4*>(d_rows + r.o) = acc;
+  }
+  __device__ __forceinline__ bool closes(const Row&) const { return false; }
+  __device__ __forceinline__ void mark(int) const {}
+};
+
 // one unique row summed by the WHOLE workgroup (a long segment, or D too wide for row groups).  Block-uniform call.
 template <int MODE, class SINK>
 __device__ __forceinline__ void seg_long_row(const SegSumArgs& a, const SINK& sink, int u, int dv, int G, int g, int c0, bool active,
                                              float4* sred, int64_t* s_off, float* s_cf) {
   const int s0 = a.seg_start[u], s1 = a.seg_start[u + 1];
-  const int row = (SINK::kApply && g == 0) ? sink.row_id(u) : 0;
+  const int row = (SINK::kRowId && g == 0) ? sink.row_id(u) : 0;
   bool close = false;
   for (int cb = 0; cb < dv; cb += SEG_THREADS) {  // dv > 512 (D > 2048): column blocks
     const int c4 = cb + c0;
@@ -670,7 +695,7 @@ __device__ __forceinline__ void segsum_body(const SegSumArgs& a, SINK sink) {
     s0 = 0; cnt = 0; row = 0;
     if (active && u < nu) {
       s0 = a.seg_start[u]; cnt = a.seg_start[u + 1] - s0;
-      if constexpr (SINK::kApply) row = sink.row_id(u);
+      if constexpr (SINK::kRowId) row = sink.row_id(u);
     }
   };
   auto first_ids = [&](int s0, int cnt, int& i0, int& i1) {
@@ -753,6 +778,16 @@ __global__ void __launch_bounds__(SEG_THREADS) segsum_kernel(SegSumArgs a) {
 // split must be 0 (every segment is summed here).
 __global__ void __launch_bounds__(SEG_THREADS) segsum_apply_kernel(SegSumArgs a, SegApplyRows s) {
   segsum_body<MODE_SASREC>(a, s);
+}
+
+// +0.0 over the dense block in front of its segment sums (a kernel, not a memset node: h2.hip's h2_zero_kernel says why)
+__global__ void __launch_bounds__(256) dense_zero_kernel(float4* __restrict__ p, int64_t n4) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) p[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// MODE_POOL's segment sums into a dense block (SegStoreDense): the sums and their order are segsum_kernel<MODE_POOL>'s.
+__global__ void __launch_bounds__(SEG_THREADS) segsum_dense_kernel(SegSumArgs a, SegStoreDense s) {
+  segsum_body<MODE_POOL>(a, s);
 }
 
 // ---- very long segments on many workgroups (round 5) --------------------------------------------------------------------------
@@ -1105,6 +1140,51 @@ extern "C" int pxr_pool_table_grad_f32(const int64_t* gidx, int B, int L, const 
   const int grid = n < 4096 ? n : 4096;
   hipLaunchKernelGGL(segsum_kernel<MODE_POOL>, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, st, a);
   return pxr_check_launch("pxr_pool_table_grad_f32");
+}
+
+// The same gradient as a DENSE block over a batch-local row space (the pixel versions of the pooled pair models: the rows are the
+// visual encoder's outputs for the batch's distinct images): d_rows [n_rows, D] gets the segment sum of every referenced row in
+// (0, n_rows) -- pxr_pool_table_grad_f32's sums bit for bit (the same sort, segsum_body<MODE_POOL>, another sink) -- and exactly
+// +0.0 everywhere else (row 0 and every unreferenced row), whatever it held before: the block is zeroed here, by a launch in front of
+// the segment sums on the same stream.  The unique-row list the sort needs lives in the workspace: the four key / value buffers are
+// handed to the sort as (keysA, valsA | keysB, valsB), so the ping-pong pair that does not hold the final order is one contiguous
+// stretch of >= 8 n bytes, and the count takes the spare last entry of the block-count buffer.
+extern "C" int pxr_pool_dense_grad_f32(const int64_t* gidx, int B, int L, const float* G, const float* w, int D, int64_t n_rows,
+                                       float* d_rows, void* ws, int64_t ws_bytes, void* stream) {
+  PXR_REQUIRE(gidx && G && w && d_rows && ws, "pxr_pool_dense_grad_f32: null pointer");
+  PXR_REQUIRE(B > 0 && L >= 1 && (int64_t)B * (L + 2) < (1ll << 30) && D > 0 && D % 4 == 0 && D <= 4096 && n_rows > 0 &&
+              n_rows < (1ll << 31), "pxr_pool_dense_grad_f32: bad shape (B=%d, L=%d, D=%d)", B, L, D);
+  PXR_REQUIRE((((uintptr_t)G | (uintptr_t)d_rows) & 15) == 0, "pxr_pool_dense_grad_f32: G and d_rows must be 16-byte aligned");
+  const char *g0 = (const char*)G, *g1 = g0 + (int64_t)3 * B * D * 4, *d0 = (const char*)d_rows, *d1 = d0 + n_rows * D * 4;
+  PXR_REQUIRE(d1 <= g0 || g1 <= d0, "pxr_pool_dense_grad_f32: d_rows must not alias G");
+  const int n = B * (L + 2);
+  SortWs sw;
+  if (carve(ws, n, &sw) > ws_bytes) { pxr_set_error("pxr_pool_dense_grad_f32: workspace too small"); return PXR_ERR_WORKSPACE; }
+  { int* t = sw.keysB; sw.keysB = sw.valsA; sw.valsA = t; }     // slots (0, 1) = pair A, (2, 3) = pair B
+  const int* final_vals = sasrec_sorted_vals(sw, n, n_rows);
+  int64_t* uniq_idx = (int64_t*)(final_vals == sw.valsB ? sw.keysA : sw.keysB);
+  int32_t* n_uniq_dev = sw.blk + sw.nblk;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n4 = n_rows * (D / 4);
+  hipLaunchKernelGGL(dense_zero_kernel, dim3((unsigned)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096)), dim3(256), 0, st, (float4*)d_rows, n4);
+  const int* sorted_vals = nullptr;
+  int rc;
+  if (use_fused_sort(n)) {
+    rc = fused_sort<MODE_ROWS>(gidx, n, 0, 0, n_rows, sw, uniq_idx, n_uniq_dev, st, &sorted_vals);
+  } else {
+    hipLaunchKernelGGL(occ_keys_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, st, gidx, n, sw.keysA, sw.valsA, n_rows);
+    rc = sort_and_segment(sw, n, n_rows, uniq_idx, n_uniq_dev, st, &sorted_vals);
+  }
+  if (rc) return rc;
+  if (sorted_vals != final_vals) { pxr_set_error("pxr_pool_dense_grad_f32: internal buffer parity"); return PXR_ERR_LAUNCH; }
+  SegSumArgs a{};
+  a.vals = sorted_vals; a.seg_start = sw.seg_start; a.n_uniq = n_uniq_dev; a.src0 = G; a.coef = w;
+  a.scale = 1.f; a.D = D; a.T = B * L; a.L = L;
+  SegStoreDense s{};
+  s.d_rows = d_rows; s.uniq_idx = uniq_idx; s.n_rows = n_rows; s.D = D;
+  const int grid = n < 4096 ? n : 4096;
+  hipLaunchKernelGGL(segsum_dense_kernel, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, st, a, s);
+  return pxr_check_launch("pxr_pool_dense_grad_f32");
 }
 
 // Phase 1 of the table gradient: occurrence keys -> stable sort -> unique ids + segments.  Depends on `items` only, so it can

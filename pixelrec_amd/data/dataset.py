@@ -355,6 +355,46 @@ class DinTrainBatcher(SampleAcfTrainBatcher):
         return profile, np.ascontiguousarray(tail[:, :2])
 
 
+class MoPoolTrainBatcher(DinTrainBatcher):
+    """Vectorised MOSampleTwoTowerTrainDataset / MOSampleOneTowerTrainDataset + mosampletower_train_collate (reference
+    REC/data/dataset/trainset.py:656-813, collate_fn.py:95-107) for MODSSM and MOFM.  A batch is `train_batch_size` whole SEQ chunks
+    -- the reference's batch unit -- in SeqTrainBatcher's chunk order and rank split; every position of every chunk is one
+    leave-one-out sample, formed by DinTrainBatcher.make_batch over the chunks' samples in chunk order (profile = the chunk without
+    the item, order kept, left-padded; one negative outside the chunk; the rng keyed by (seed, epoch, rank)), so S = the sum of
+    the chunk lengths.
+
+    Yields (index int64 [S, L + 2] = [profile | positive | negative], image_ids int64 [M]): image_ids[0] == 0 (the zero image,
+    "no item"), image_ids[1:] the batch's distinct item ids, ascending; `index` holds positions into image_ids.  Each distinct
+    image is therefore fetched and encoded ONCE per batch.  The reference lists 1 + 2 n images per chunk of n items and so
+    dedups inside a chunk only; here the dedup runs across the whole batch.  The CLIP tower is a per-image function without batch
+    statistics or dropout, so an image encoded once and read by several chunks receives the sum of the gradients its copies
+    would have received: the same parameter gradients."""
+
+    def __init__(self, config, dataload, rank=0, world=1, seed=0, drop_last=False):
+        super().__init__(config, dataload, rank=rank, world=world, seed=seed, drop_last=drop_last)
+        self.lens = (self.windows != 0).sum(1)                        # chunk lengths (item ids are >= 1)
+        self.first = np.cumsum(self.lens) - self.lens                 # first sample of each chunk
+        self.n_samples = self.n
+        self.n = len(self.windows)                                    # the unit of the order and of a batch: the chunk
+        self.num_samples = -(-self.n // world)
+
+    def make_batch(self, chunks, rng):
+        lens = self.lens[chunks]
+        rows = np.repeat(self.first[chunks] - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()), dtype=np.int64)
+        profile, target = super().make_batch(rows, rng)
+        items = np.concatenate((profile, target), axis=1)             # [S, L + 2] item ids
+        uniq = np.unique(items)
+        image_ids = np.concatenate((np.zeros(1, dtype=np.int64), uniq[uniq != 0]))
+        return np.searchsorted(image_ids, items), image_ids
+
+    def __iter__(self):
+        idx = self._indices()
+        rng = np.random.default_rng([self.neg_seed, self.epoch, self.rank])
+        for b in range(len(self)):
+            index, image_ids = self.make_batch(idx[b * self.batch_size:(b + 1) * self.batch_size], rng)
+            yield torch.from_numpy(index), torch.from_numpy(image_ids)
+
+
 class CuratorTrainBatcher:
     """Vectorised TwoTowerTrainDataset (reference REC/data/dataset/trainset.py:256-290) over the SEQ chunks, under torch's
     DistributedSampler order.  The reference maps CuratorNet to a `TwoTowerTrainDataset2` that does not exist

@@ -190,6 +190,7 @@ _SIGNATURES = {
     "pxr_pool_pair_fwd_f32": (_I, [_P, _I64, _I, _P, _I64, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "pxr_pool_pair_bwd_f32": (_I, [_P, _I64, _I, _P, _I, _I, _P, _P, _F, _P, _P, _P]),
     "pxr_pool_table_grad_f32": (_I, [_P, _I, _I, _P, _P, _I, _I64, _P, _P, _P, _P, _I64, _P]),
+    "pxr_pool_dense_grad_f32": (_I, [_P, _I, _I, _P, _P, _I, _I64, _P, _P, _I64, _P]),
     "pxr_wd_join_f32": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     "pxr_wd_join_bwd_f32": (_I, [_P, _I, _I, _P, _P]),
     "pxr_wd_head_fwd_f32": (_I, [_P, _P, _P, _I64, _P, _I, _I, _P, _P]),

@@ -43,6 +43,27 @@ from ..utils.enum_type import InputType
 from .packed import LazyTableModel, TrainStep, _Rows
 
 
+def pool_queries(name, feat, item_seq, mean):
+    """item_seq int64 [B, L] left-padded with 0 -> the pooled rows of feat [N, D] (masked sum, or masked mean), [B, D]: the
+    evaluation form of the training kernel, shared by the ID models here and the pixel models of mopooled.py."""
+    item_seq = item_seq.to(feat.device).contiguous()
+    if item_seq.dim() != 2 or item_seq.shape[1] < 1:
+        raise ValueError(f"{name}: item_seq must be [B, L] with L >= 1, got {tuple(item_seq.shape)}")
+    B, L = item_seq.shape
+    q, _ = ops.pool_rows(feat, item_seq, B, L, mean, pad_row=0)
+    return q
+
+
+def pool_scores(q, feat):
+    """scores [B, N] = q feat^T in the library GEMM; an id outside the catalogue raises, like the reference's indexing."""
+    B, D = q.shape
+    N = feat.shape[0]
+    scores = torch.empty(B, N, dtype=torch.float32, device=q.device)
+    ops.gemm(True, True, B, N, D, q, D, feat, D, scores, N, ops.EPI_NONE, use_ws=False)
+    ops.raise_on_bad_indices(q.device)
+    return scores
+
+
 class _ReluMLP(nn.Module):
     """MLPLayers(sizes, dropout) with the reference's module layout (mlp_layers.{3k: Dropout, 3k + 1: Linear, 3k + 2: ReLU});
     never called -- the kernels read its parameters."""
@@ -198,14 +219,10 @@ class _PooledPair(LazyTableModel):
         self._ensure_packed()
         feat = item_feature if item_feature is not None else self.compute_item_all()
         feat = (feat if feat.is_contiguous() else feat.contiguous()).data
-        item_seq = item_seq.to(feat.device).contiguous()
-        if item_seq.dim() != 2 or item_seq.shape[1] < 1:
-            raise ValueError(f"{type(self).__name__}: item_seq must be [B, L] with L >= 1, got {tuple(item_seq.shape)}")
-        B, L = item_seq.shape
-        q, _ = ops.pool_rows(feat, item_seq, B, L, self.pool_mean, pad_row=0)
+        q = pool_queries(type(self).__name__, feat, item_seq, self.pool_mean)
         if self.n_layers:
             q, _ = self._mlp_fwd(q, False)
-        return q.view(B, 1, -1), q
+        return q.view(q.shape[0], 1, -1), q
 
     @torch.no_grad()
     def predict(self, item_seq, item_feature=None):
@@ -213,12 +230,7 @@ class _PooledPair(LazyTableModel):
         feat = item_feature if item_feature is not None else self.compute_item_all()
         feat = (feat if feat.is_contiguous() else feat.contiguous()).data
         _, q = self.encode_last(item_seq, feat)
-        B, D = q.shape
-        N = feat.shape[0]
-        scores = torch.empty(B, N, dtype=torch.float32, device=q.device)
-        ops.gemm(True, True, B, N, D, q, D, feat, D, scores, N, ops.EPI_NONE, use_ws=False)
-        ops.raise_on_bad_indices(q.device)     # an id outside the catalogue raises, like the reference's indexing
-        return scores
+        return pool_scores(q, feat)
 
 
 class DSSM(_PooledPair):

@@ -2799,6 +2799,24 @@ def pool_table_grad(gidx, B: int, L: int, G, w, n_table: int, out: SparseRows | 
     return sp
 
 
+def pool_dense_grad(gidx, B: int, L: int, G, w, n_rows: int, out=None):
+    """The same gradient as a dense block over a batch-local row space (pxr_pool_dense_grad_f32): gidx int64 [B L + 2 B] holds rows
+    of an [n_rows, D] matrix (0 = "no item", dropped; ids outside [0, n_rows) dropped) -> d_rows float32 [n_rows, D]: pool_table_grad's
+    row sums, bit for bit, at their rows and exactly +0.0 everywhere else (row 0, unreferenced rows), whatever `out` held before."""
+    Lb = _l.load()
+    _req(gidx, torch.int64, "gidx"); _req(G, torch.float32, "G"); _req(w, torch.float32, "w")
+    n = B * (L + 2)
+    if B < 1 or L < 1 or gidx.numel() != n or G.dim() != 2 or G.shape[0] != 3 * B or w.numel() != B or n_rows < 1:
+        raise _l.PxrError(f"pool dense grad: need gidx [B (L + 2)] = [{n}], G [3B, D], w [B] and n_rows >= 1 for B={B}, L={L}")
+    D = G.shape[1]
+    d_rows = _pool_out(out, (int(n_rows), D), G.device, "d_rows")
+    ws_bytes = int(Lb.pxr_embed_grad_ws_bytes(n))
+    ws = _ws.get(ws_bytes, G.device)
+    _l.check(Lb.pxr_pool_dense_grad_f32(_l.ptr(gidx), B, L, _l.ptr(G), _l.ptr(w), D, int(n_rows), _l.ptr(d_rows), _l.ptr(ws),
+                                        ws_bytes, _l.stream_ptr()), "pxr_pool_dense_grad_f32")
+    return d_rows
+
+
 # ------------------------------------------------------------------------------------------------ WideDeep (csrc/widedeep.hip)
 def _wd_out(t, shape, device, name: str):
     if t is None:

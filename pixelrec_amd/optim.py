@@ -575,8 +575,8 @@ def clip_grad_norm_(model, max_norm, norm_type=2.0, **_ignored):
     model = model.module if hasattr(model, "module") else model
     if hasattr(model, "wait_flat_grads"):
         model.wait_flat_grads()
-    _, gflat = model.flat_parameters()
-    sq = gflat.pow(2).sum()
+    gflat = model.flat_parameters()[1] if hasattr(model, "flat_parameters") else None     # (MODSSM / MOFM: the encoder only)
+    sq = gflat.pow(2).sum() if gflat is not None else torch.zeros((), dtype=torch.float32, device=next(model.parameters()).device)
     sp = getattr(model, "sparse_table_grad", None) if has_lazy_table(model) else None
     if getattr(sp, "applied", False):
         raise RuntimeError("clip_grad_norm_: the table rows of this step were updated inside the backward pass, their gradient rows "
@@ -595,7 +595,8 @@ def clip_grad_norm_(model, max_norm, norm_type=2.0, **_ignored):
         sq = sq + g.pow(2).sum()
     total = sq.sqrt()
     coef = torch.clamp(float(max_norm) / (total + 1e-6), max=1.0)
-    gflat.mul_(coef)
+    if gflat is not None:
+        gflat.mul_(coef)
     if sp is not None:
         sp.rows.mul_(coef)
     for g in extra:
@@ -711,6 +712,58 @@ class VisualAdamW:
         self.step_count = steps.pop() if steps else 0
         self._step_dev.fill_(self.step_count)
         self._seeded_cfg = None          # the entry of step_count + 1 is rewritten by the next step()
+
+
+class VisualOnlyAdamW(VisualAdamW):
+    """The optimizer of a model whose only parameters are `visual_encoder.*` (MODSSM, MOFM): the visual-encoder group alone.
+    Under four `optim_args` the reference still builds torch.optim.AdamW over TWO groups -- the encoder's and an empty rec group
+    (trainer.py:86-96; torch accepts an empty group) -- so `empty_trailing_group` ({lr, weight_decay} of that group) keeps the
+    torch-layout state_dict in that shape, and such a dict loads back.  With every encoder parameter frozen there is nothing to
+    train: construction raises."""
+
+    def __init__(self, encoder, lr=1e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, empty_trailing_group=None):
+        super().__init__(encoder, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps)
+        if not self._trainable():
+            raise ValueError("nothing to train")
+        self.empty_trailing_group = dict(empty_trailing_group) if empty_trailing_group is not None else None
+
+    def flush(self):
+        return None
+
+    def _unstepped_on_host(self):
+        """No step taken and the encoder not on a HIP device: there are no moments yet and no packed buffers to read them from,
+        so the torch-layout dict (empty state, as torch.optim.AdamW's before its first step) needs no tower."""
+        return self.step_count == 0 and next(self.encoder.parameters()).device.type != "cuda"
+
+    def state_dict(self, layout: str = "torch"):
+        if self._unstepped_on_host():
+            g = self.param_groups[0]
+            sd = {"state": {}, "param_groups": [{"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"],
+                                                 "weight_decay": g["weight_decay"], **_TORCH_GROUP_DEFAULTS,
+                                                 "params": list(range(len(self._trainable())))}]}
+        else:
+            sd = super().state_dict()
+        t = self.empty_trailing_group
+        if t is not None:
+            g = self.param_groups[0]
+            sd["param_groups"] = sd["param_groups"] + [{"lr": t["lr"], "betas": tuple(g["betas"]), "eps": g["eps"],
+                                                        "weight_decay": t["weight_decay"], **_TORCH_GROUP_DEFAULTS, "params": []}]
+        return sd
+
+    def load_state_dict(self, sd):
+        groups = list(sd["param_groups"])
+        if len(groups) > 2 or (len(groups) == 2 and groups[1]["params"]):
+            raise ValueError("visual-only optimizer state: expected the visual_encoder group and at most one EMPTY rec group, got "
+                             f"{[len(g['params']) for g in groups]} parameters per group")
+        if self._unstepped_on_host() and not sd["state"]:
+            g = groups[0]
+            if len(g["params"]) != len(self._trainable()):
+                raise ValueError(f"visual optimizer state has {len(g['params'])} parameters, this encoder trains {len(self._trainable())}")
+            self.param_groups = [{"lr": g["lr"], "weight_decay": g["weight_decay"], "betas": tuple(g["betas"]), "eps": g["eps"]}]
+        else:
+            super().load_state_dict({"state": sd["state"], "param_groups": groups[:1]})
+        if len(groups) == 2:
+            self.empty_trailing_group = {"lr": groups[1]["lr"], "weight_decay": groups[1]["weight_decay"]}
 
 
 class OptimizerGroup:

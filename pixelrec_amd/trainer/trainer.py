@@ -183,6 +183,15 @@ class Trainer:
 
             return FragmentAdamW(self.model, self.config["decay_check_name"], a["modal_lr"], a["modal_decay"], a["rec_lr"],
                                  a["rec_decay"])
+        if all("visual_encoder" in n for n, _ in m.named_parameters()):
+            # a model without a rec parameter (MODSSM, MOFM): the visual-encoder group alone; with four keys the reference still
+            # builds its two groups, the second one empty (trainer.py:86-96), and torch-layout checkpoints keep that shape
+            from ..optim import VisualOnlyAdamW
+
+            if len(a) == 4:
+                return VisualOnlyAdamW(m.visual_encoder, lr=a["modal_lr"], weight_decay=a["modal_decay"],
+                                       empty_trailing_group={"lr": a["rec_lr"], "weight_decay": a["rec_decay"]})
+            return VisualOnlyAdamW(m.visual_encoder, lr=a["learning_rate"], weight_decay=a["weight_decay"])
         if len(a) == 4:
             rec = PxrAdamW(m, lr=a["rec_lr"], weight_decay=a["rec_decay"])
             modal = [p for n, p in m.named_parameters() if "visual_encoder" in n and p.requires_grad]
@@ -238,7 +247,10 @@ class Trainer:
                         self._h2_stale_fallback(e)
                     continue
             self.optimizer.zero_grad()
-            if self.use_modality:   # assemble the image batch on the device from the HBM-resident store
+            if self.use_modality and hasattr(self.model.module, "modal_inputs"):
+                # a model that says itself how a batch becomes its forward input (MODSSM / MOFM: positions + the distinct images)
+                data = self.model.module.modal_inputs(self._image_store(train_data), data)
+            elif self.use_modality:   # assemble the image batch on the device from the HBM-resident store
                 from ..data.images import interleave_pos_neg
 
                 data = (self._image_store(train_data).batch(interleave_pos_neg(data[0])), data[1])

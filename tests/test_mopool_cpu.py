@@ -1,0 +1,278 @@
+"""MODSSM and MOFM without a GPU: the batcher (whole chunks, batch-wide image dedup, DinTrainBatcher's samples), the fixtures of the
+reference's own classes against the float64 restatement on the torch-module tower's output (which pins the composition: which row
+of E an index means, what 0 means, which pooling, which loss), the state_dict, and the visual-encoder-only optimizer."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import pool_restate as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+PFX = "visual_encoder.item_encoder."
+CASES = {"modssm_tiny": ("MODSSM", "DSSM"), "mofm_tiny": ("MOFM", "FM")}
+TOWER = 2e-5         # per-entry budget of the torch-module tower against the reference's (test_mosasrec_golden.py's CPU part)
+
+
+def _config(D, L, tune):
+    return {"embedding_size": D, "mlp_hidden_size": [], "dropout_prob": 0, "MAX_ITEM_LIST_LENGTH": L, "seed": 2020,
+            "encoder_name": "clip-vit-tiny-test", "encoder_source": "transformers", "pretrain_path": None,
+            "fine_tune_arg": {"tune_scale": tune, "pre_trained": True, "activation": "relu", "dnn_layers": [], "method": "mean"}}
+
+
+def build_from_fixture(name, g):
+    """The model with the fixture's state.  The fixture carries transformers-5.x key names and the unused post_layernorm pair; the
+    build, like the reference under its pinned transformers, has `vision_model.` in the names and no post_layernorm."""
+    import pixelrec_amd.model as M
+
+    I, D, L = (int(x) for x in g["meta"][:3])
+
+    class DL:
+        item_num = I
+
+    m = getattr(M, name)(_config(D, L, int(g["meta"][6])), DL())
+    sd = {}
+    for k in (str(x) for x in g["sd.keys"]):
+        if "post_layernorm" in k:
+            continue
+        sd[(PFX + "vision_model." + k[len(PFX):]) if k.startswith(PFX) else k] = torch.from_numpy(g["sd." + k])
+    m.load_state_dict(sd, strict=True)
+    return m
+
+
+@pytest.fixture(scope="module", params=list(CASES))
+def case(request):
+    name, kind = CASES[request.param]
+    return name, kind, np.load(os.path.join(GOLD, request.param + ".npz"))
+
+
+# ------------------------------------------------------------------------------------------------------------ batcher
+@pytest.fixture(scope="module")
+def tiny(tmp_path_factory):
+    from pixelrec_amd.config import Config
+    from pixelrec_amd.data import load_data
+
+    d = tmp_path_factory.mktemp("mopool")
+    (d / "m.yaml").write_text("model: MODSSM\nembedding_size: 8\n")
+    (d / "o.yaml").write_text(f"seed: 2020\ndata_path: {GOLD}/\ndataset: TinyInter\nMAX_ITEM_LIST_LENGTH: 6\ntrain_batch_size: 4\n"
+                              "eval_batch_size: 16\nuse_modality: True\n")
+    config = Config([str(d / "m.yaml"), str(d / "o.yaml")])
+    data = load_data(config)
+    data.build()
+    return config, data
+
+
+def test_batcher_yields_whole_chunks_as_positions_into_the_batchs_distinct_images(tiny):
+    from pixelrec_amd.data.dataset import DinTrainBatcher, MoPoolTrainBatcher, SeqTrainBatcher
+
+    config, data = tiny
+    b, din, seq = MoPoolTrainBatcher(config, data), DinTrainBatcher(config, data), SeqTrainBatcher(config, data)
+    L, bs = 6, 4
+    chunk_len = np.array([len(s) for s in data.train_feat["item_seq"]])
+    first = np.cumsum(chunk_len) - chunk_len
+    assert b.n == len(chunk_len) and len(b) == -(-len(chunk_len) // bs)
+    order = seq._indices()                                         # SeqTrainBatcher's order, over chunks
+    assert np.array_equal(b._indices(), order)
+    rng = np.random.default_rng([2020, 0, 0])                      # (seed, epoch, rank)
+    total = 0
+    for k, (index, image_ids) in enumerate(b):
+        chunks = order[k * bs:(k + 1) * bs]
+        S = int(chunk_len[chunks].sum())                           # whole chunks: every position of each is a sample
+        total += S
+        assert index.dtype == torch.int64 and image_ids.dtype == torch.int64 and tuple(index.shape) == (S, L + 2)
+        ids = image_ids.numpy()
+        assert ids[0] == 0 and (np.diff(ids) > 0).all()            # 0 first, the rest strictly ascending (so distinct)
+        assert 0 <= int(index.min()) and int(index.max()) < len(ids)
+        assert set(np.unique(index.numpy()).tolist()) | {0} == set(range(len(ids)))        # no image listed without a reader
+        rows = np.concatenate([np.arange(first[c], first[c] + chunk_len[c]) for c in chunks])
+        profile, target = din.make_batch(rows, rng)                # the same chunks, the same rng stream
+        items = ids[index.numpy()]
+        assert np.array_equal(items[:, :L], profile) and np.array_equal(items[:, L:], target)
+        at = 0
+        for c in chunks:                                           # every negative lies outside its chunk
+            own = set(data.train_feat["item_seq"][c])
+            for s in range(at, at + chunk_len[c]):
+                assert int(items[s, L + 1]) not in own and int(items[s, L]) in own and int(items[s, L + 1]) >= 1
+            at += chunk_len[c]
+    assert total == int(chunk_len.sum())
+    first_epoch = [(i.clone(), j.clone()) for i, j in b]
+    again = [(i.clone(), j.clone()) for i, j in b]
+    assert all(torch.equal(x[0], y[0]) and torch.equal(x[1], y[1]) for x, y in zip(first_epoch, again))     # same (seed, epoch)
+    b.set_epoch(1)
+    other = [(i.clone(), j.clone()) for i, j in b]
+    assert any(x[0].shape != y[0].shape or not torch.equal(x[0], y[0]) for x, y in zip(first_epoch, other))  # two epochs differ
+
+
+def test_models_are_registered_with_the_chunk_batcher_and_the_sequence_evaluation(tiny):
+    from pixelrec_amd.data.dataset import MoPoolTrainBatcher, SeqEvalBatcher
+    from pixelrec_amd.data.utils import SUPPORTED, bulid_dataloader
+    from pixelrec_amd.utils import get_model
+
+    config, data = tiny
+    assert SUPPORTED["MODSSM"] == "SEQ" and SUPPORTED["MOFM"] == "SEQ"
+    assert get_model("MODSSM").__name__ == "MODSSM" and get_model("MOFM").__name__ == "MOFM"
+    train, valid, test = bulid_dataloader(config, data)
+    assert isinstance(train.batcher, MoPoolTrainBatcher) and isinstance(valid, SeqEvalBatcher) and isinstance(test, SeqEvalBatcher)
+
+
+# ------------------------------------------------------------------------------------------------------------ fixtures
+def test_fixture_pins_the_composition_on_the_cpu_tower(case):
+    """E from the build's torch-module tower (visual.py's CPU path) on the fixture's state, then pool_restate in float64 on it,
+    against the reference's stored loss and predict.  Budget: the stored ref_err plus what a per-entry tower error of TOWER does
+    to the quantity -- x = <U, p> - <U, n> moves by at most TOWER (c (sum|p| + sum|n|) + 2 sum|U|) with c = 1 under mean pooling
+    and cnt under sum pooling, the loss is 1-Lipschitz in x; a score <q, f> by TOWER (c sum|f| + sum|q|)."""
+    name, kind, g = case
+    m = build_from_fixture(name, g).eval()
+    store = torch.from_numpy(g["store"].astype(np.float32))
+    mean = kind == "DSSM"
+    with torch.no_grad():
+        feat = m.visual_encoder(store)
+    err = float((feat - torch.from_numpy(g["eval.item_feature"])).abs().max())
+    print(name, "item features: CPU tower vs reference", err)
+    assert err <= TOWER + float(g["ref_err.item_feature"])
+    assert float(feat[0].abs().max()) > 0                           # the zero image's encoding is not zero
+    for j in range(2):
+        index, image_ids = g[f"b{j}.index"], torch.from_numpy(g[f"b{j}.image_ids"])
+        E = feat[image_ids].double()
+        loss = float(R.loss_of(kind, {R.TABLE: E}, index))
+        prof, pos, neg = index[:, :-2], index[:, -2], index[:, -1]
+        cnt = torch.from_numpy((prof != 0).sum(1)).double()
+        c = torch.ones_like(cnt) if mean else cnt
+        U = R.pooled(E, torch.from_numpy(prof), mean)
+        bound_x = TOWER * (c * (E[pos].abs().sum(-1) + E[neg].abs().sum(-1)) + 2 * U.abs().sum(-1))
+        budget = float(g[f"ref_err.b{j}.loss"]) + float(bound_x.mean())
+        print(name, "batch", j, "loss", loss, float(g[f"b{j}.loss"]), "budget", budget)
+        assert abs(loss - float(g[f"b{j}.loss"])) <= budget
+    win = torch.from_numpy(g["eval.windows"])
+    f64 = feat.double()
+    scores = R.predict(kind, {R.TABLE: f64}, win)
+    cnt = (win != 0).sum(1).double()
+    c = (cnt > 0).double() if mean else cnt
+    q = R.pooled(f64, win, mean)
+    bound = TOWER * (c[:, None] * f64.abs().sum(-1)[None, :] + q.abs().sum(-1)[:, None]) + float(g["ref_err.scores"])
+    got = (scores - torch.from_numpy(g["eval.scores"]).double()).abs()
+    print(name, "scores", float(got.max()), "budget up to", float(bound.max()))
+    assert bool((got <= bound).all())
+    assert float(scores[5].abs().max()) == 0                        # the all-padding window
+
+
+def test_fixture_batches_hold_the_cases_they_are_there_for(case):
+    _, _, g = case
+    L = int(g["meta"][2])
+    for j in range(2):
+        index, M = g[f"b{j}.index"], len(g[f"b{j}.image_ids"])
+        prof, tgt = index[:, :L], index[:, L:]
+        assert sorted((prof != 0).sum(1).tolist()) == [0, 1, 2, 3, 4, 4]                    # full, 1..3 pads, empty
+        assert any(len(set(r[r != 0].tolist())) < int((r != 0).sum()) for r in prof)        # a repeat inside a profile
+        assert set(prof[prof != 0].tolist()) & set(tgt.reshape(-1).tolist())                # history here, target there
+        assert set(range(1, M)) - set(index.reshape(-1).tolist())                           # a listed image nobody reads
+        assert (tgt != 0).all() and int(index.max()) < M
+    assert os.path.getsize(os.path.join(GOLD, "modssm_tiny.npz")) < 1_000_000 and os.path.getsize(os.path.join(GOLD, "mofm_tiny.npz")) < 1_000_000
+
+
+# ------------------------------------------------------------------------------------------------------------ parameters, optimizer
+def test_state_dict_is_the_encoders_alone(case):
+    name, _, g = case
+    m = build_from_fixture(name, g)
+    keys = list(m.state_dict())
+    assert keys and all(k.startswith("visual_encoder.") for k in keys)
+    assert [n for n, _ in m.named_parameters()] == keys              # no buffer, no parameter of the head's own
+    frozen = [n for n, p in m.named_parameters() if not p.requires_grad]
+    assert len(frozen) == int(g["meta"][6]) == len(g["frozen"])
+
+
+class _Wrap:
+    def __init__(self, m):
+        self.module = m
+
+
+def _trainer_optimizer(m, optim_args):
+    from pixelrec_amd.trainer import Trainer
+
+    t = Trainer.__new__(Trainer)
+    t.optim_args, t.model, t.config = optim_args, _Wrap(m), {"decay_check_name": None}
+    return t._build_optimizer()
+
+
+FOUR = {"modal_lr": 1e-4, "rec_lr": 3e-4, "modal_decay": 0.0, "rec_decay": 0.1}
+
+
+def test_optimizer_is_the_visual_group_with_an_empty_second_group(case):
+    from pixelrec_amd.optim import VisualAdamW, VisualOnlyAdamW
+
+    name, _, g = case
+    m = build_from_fixture(name, g)
+    opt = _trainer_optimizer(m, FOUR)
+    assert isinstance(opt, VisualOnlyAdamW) and isinstance(opt, VisualAdamW)
+    assert (opt.param_groups[0]["lr"], opt.param_groups[0]["weight_decay"]) == (1e-4, 0.0)
+    sd = opt.state_dict(layout="torch")
+    n_train = sum(p.requires_grad for p in m.parameters())
+    assert len(sd["param_groups"]) == 2 and sd["param_groups"][0]["params"] == list(range(n_train)) and sd["param_groups"][1]["params"] == []
+    assert (sd["param_groups"][1]["lr"], sd["param_groups"][1]["weight_decay"]) == (3e-4, 0.1) and sd["state"] == {}
+    # torch's own AdamW over the reference's two groups takes the dict: that is the layout the reference stores
+    tor = torch.optim.AdamW([{"params": [p for p in m.parameters() if p.requires_grad], "lr": 1.0, "weight_decay": 0.5},
+                             {"params": [], "lr": 2.0, "weight_decay": 0.25}])
+    tor.load_state_dict(sd)
+    assert [(x["lr"], x["weight_decay"]) for x in tor.param_groups] == [(1e-4, 0.0), (3e-4, 0.1)]
+    back = tor.state_dict()
+    assert [x["params"] for x in back["param_groups"]] == [x["params"] for x in sd["param_groups"]]
+    opt2 = _trainer_optimizer(build_from_fixture(name, g), {**FOUR, "modal_lr": 5.0, "rec_lr": 7.0})
+    opt2.load_state_dict(back)                                       # ... and it loads back
+    assert opt2.state_dict(layout="torch") == sd
+    with pytest.raises(ValueError):
+        bad = {"state": {}, "param_groups": [sd["param_groups"][0], {**sd["param_groups"][1], "params": [n_train]}]}
+        opt2.load_state_dict(bad)                                    # a rec group with parameters is not this model's
+
+
+def test_two_optim_args_give_one_group(case):
+    name, _, g = case
+    opt = _trainer_optimizer(build_from_fixture(name, g), {"learning_rate": 2e-4, "weight_decay": 0.05})
+    sd = opt.state_dict(layout="torch")
+    assert len(sd["param_groups"]) == 1 and (sd["param_groups"][0]["lr"], sd["param_groups"][0]["weight_decay"]) == (2e-4, 0.05)
+
+
+def test_all_frozen_encoder_has_nothing_to_train(case):
+    name, _, g = case
+    m = build_from_fixture(name, g)
+    for p in m.parameters():
+        p.requires_grad_(False)
+    with pytest.raises(ValueError, match="nothing to train"):
+        _trainer_optimizer(m, FOUR)
+
+
+def test_other_models_keep_their_optimizers():
+    """A model with a rec parameter does not take the new branch: MOSASRec still gets the OptimizerGroup of both groups."""
+    import pixelrec_amd.model as M
+    from pixelrec_amd.optim import OptimizerGroup
+
+    class DL:
+        item_num = 13
+
+    cfg = dict(_config(64, 4, 37), n_layers=1, n_heads=2, inner_size=2, hidden_dropout_prob=0.0, attn_dropout_prob=0.0,
+               hidden_act="gelu", layer_norm_eps=1e-12, initializer_range=0.02)
+    opt = _trainer_optimizer(M.MOSASRec(cfg, DL()), FOUR)
+    assert isinstance(opt, OptimizerGroup)
+
+
+def test_input_forms_and_mismatched_planes():
+    import pixelrec_amd.model as M
+
+    class DL:
+        item_num = 13
+
+    fm, ds = M.MOFM(_config(8, 4, 37), DL()), M.MODSSM(_config(8, 4, 37), DL())
+    rows = torch.tensor([[0, 1, 2, 3, 4, 5], [0, 0, 2, 2, 1, 3]])
+    p, t = fm._split_index(R.fm_form(rows))
+    assert torch.equal(p, rows[:, :4]) and torch.equal(t, rows[:, 4:])
+    for m in (fm, ds):
+        p, t = m._split_index(rows)                                  # the batcher's form
+        assert torch.equal(p, rows[:, :4]) and torch.equal(t, rows[:, 4:])
+    planes = R.fm_form(rows).clone()
+    planes[1, 1, 0] = 9
+    with pytest.raises(ValueError):
+        fm._split_index(planes)
+    with pytest.raises(ValueError):
+        ds._split_index(R.fm_form(rows))
+    assert not hasattr(ds, "mlp_layers") and ds.mlp_hidden_size == [] and ds.pool_mean and not fm.pool_mean
