@@ -170,3 +170,88 @@ def topk_histories(s64, hist):
     top, _ = masked_topk(s64[:1], hist[:1], 3)
     out = [sorted(set(hist[0]) | set(int(i) for i, v in zip(top.indices[0].tolist(), top.values[0].tolist()) if v > float("-inf")))]
     return out + [list(h) for h in hist[1:]]
+
+
+# ---- the inputs of the multi-tile walk tests (tests/test_gpu_topk_walk.py; tests/test_topk_walk_cases.py checks them on the CPU) ----
+WALK_K = 10
+WALK_BORDERS = (127, 128, 129, 255, 256)                     # the last / first items of the 128-item tiles
+WALK_KEEP = (100, 120, 127, 128, 130, 200)                   # what the "fewer than K" user keeps: two tiles, both sides of a border
+WALK_STALE_USERS = range(5, 69)                              # the users walk_histories() may give a stale-bitmap item
+# name -> (item_num, B, L, hidden, D, seed): the smallest shapes that reach each regime of the split rule
+# n_split = min(ceil(512 / B), tiles).  Seeds: the first for which float64 alone excuses well under 2 % of the cells.
+WALK_CASES = {
+    "one split, small": (300, 512, 10, (12, 4), 16, 0),      # 3 tiles (the last holds 44 items), n_split 1, per 3
+    "one split, shipped": (300, 512, 10, (80, 40), 64, 0),
+    "short splits": (600, 128, 10, (12, 4), 16, 0),          # 5 tiles, n_split 4, per 2: the splits own 2, 2, 1, 0 tiles
+    "short splits, one layer": (600, 128, 4, (16,), 8, 0),
+    "limits": (257, 3, 64, (128, 128), 128, 0),              # one tile per workgroup from here on
+    "hidden 5": (257, 3, 4, (5,), 16, 0),
+    "hidden 127 33": (257, 3, 4, (127, 33), 16, 0),
+    "hidden 1": (257, 3, 4, (1,), 16, 0),
+    "chunks": (300, 5, 4, (12, 4), 16, 0),
+}
+
+
+def walk_users(item_num, B, L, g):
+    """-> (window int64 [B, L] left-padded with 0, histories: one sorted id list per user), shared by the DIN and WideDeep cases.
+    Pad lengths are random (1..L real positions) except: user 0 has a full window, user 4 an all-padding one.  Every history holds
+    the window's items plus L + 3 random ones; user 1's is longer than 256 items where the catalogue allows (the stride of the
+    kernels' history loop), user 2 keeps only WALK_KEEP (fewer than K items, in two tiles), user 3's holds WALK_BORDERS."""
+    window = torch.randint(1, item_num, (B, L), generator=g)
+    n_real = torch.randint(1, L + 1, (B,), generator=g)
+    n_real[0] = L
+    if B > 4:
+        n_real[4] = 0
+    window[torch.arange(L)[None, :] < (L - n_real)[:, None]] = 0
+    hist = []
+    for b in range(B):
+        h = set(window[b][window[b] != 0].tolist()) | set(torch.randint(1, item_num, (L + 3,), generator=g).tolist())
+        if b == 1:
+            h |= set(torch.randperm(item_num - 1, generator=g)[:min(260, item_num - 30)].add(1).tolist())
+        if b == 2:
+            h = set(range(1, item_num)) - (set(WALK_KEEP) - h)
+        if b == 3:
+            h |= set(i for i in WALK_BORDERS if i < item_num)
+        hist.append(sorted(h))
+    return window, hist
+
+
+def walk_histories(s64, hist, tol_abs, users=WALK_STALE_USERS):
+    """-> (histories, stale): user 0's float64 top-3 masked (topk_histories), and for every user u of `users` whose float64 best
+    unmasked item y is >= 129, the item y - 128 -- the same bit of the history bitmap one tile earlier -- added to its history,
+    provided the float64 gaps at ranks 1 and 2 then exceed 2 tol_abs.  stale = [(u, y)]: y must come back at rank 1."""
+    out = topk_histories(s64, hist)
+    stale = []
+    for u in users:
+        if u >= len(out):
+            break
+        top, _ = masked_topk(s64[u:u + 1], out[u:u + 1], 1)
+        y = int(top.indices[0, 0])
+        if y < 129 or top.values[0, 0] == float("-inf") or (y - 128) in out[u]:
+            continue
+        h = sorted(set(out[u]) | {y - 128})
+        v = masked_topk(s64[u:u + 1], [h], 3)[0].values[0]
+        if float(v[0] - v[1]) > 2 * tol_abs and float(v[1] - v[2]) > 2 * tol_abs:
+            out[u] = h
+            stale.append((u, y))
+    return out, stale
+
+
+def walk_case(item_num, B, L, hidden, D, seed):
+    """-> (P float32 xavier-normal state with small random biases, window, histories) -- topk_case's weights, walk_users' users."""
+    g = torch.Generator().manual_seed(1000003 * seed + 7 * item_num + 31 * B + 101 * L + 13 * D + sum(hidden) + len(hidden))
+    P = {}
+    sizes = [4 * D] + list(hidden) + [1]
+    keys = names(len(hidden))
+    for i, (a, b) in enumerate(zip(sizes[:-1], sizes[1:])):
+        P[keys[2 * i]] = torch.randn(b, a, generator=g) * (2.0 / (a + b)) ** 0.5
+        P[keys[2 * i + 1]] = torch.randn(b, generator=g) * 0.1
+    P[TABLE] = torch.randn(item_num, D, generator=g) * (2.0 / (item_num + D)) ** 0.5
+    window, hist = walk_users(item_num, B, L, g)
+    return P, window, hist
+
+
+def scores64(P, window, device="cpu", chunk=32):
+    """predict_factorised on .double() parameters, `chunk` users at a time ([B, L, N, h1] in float64 is large), on `device`."""
+    P64 = {k: v.to(device=device, dtype=torch.float64) for k, v in P.items()}
+    return torch.cat([predict_factorised(P64, window[lo:lo + chunk].to(device)) for lo in range(0, window.shape[0], chunk)]).cpu()

@@ -71,3 +71,63 @@ def metrics(ids, targets, ks=(5, 10)):
         rank = np.where(hk.any(1), hk.argmax(1), 0)
         out[f"ndcg@{k}"] = float(np.where(hk.any(1), 1.0 / np.log2(rank + 2.0), 0.0).mean())
     return out
+
+
+# ---- the inputs of the multi-tile walk tests (tests/test_gpu_topk_walk.py; tests/test_topk_walk_cases.py checks them on the CPU) ----
+WALK_H, WALK_K = 50, 10
+WALK_BORDERS = (127, 128, 129, 255, 256)                     # the last / first items of the 128-item tiles
+WALK_KEEP = (100, 120, 127, 128, 130, 200)                   # what the "fewer than K" user keeps: two tiles, both sides of a border
+WALK_STALE_USERS = range(5, 69)                              # the users walk_histories() may give a stale-bitmap item
+# name -> (B, N, F, seed): the smallest shapes that reach each regime of n_split = min(ceil(512 / ceil(B / 2)), tiles)
+WALK_CASES = {
+    "one split": (1024, 300, 12, 0),                         # 3 tiles, n_split 1, per 3
+    "short splits": (256, 600, 12, 0),                       # 5 tiles, n_split 4, per 2: the splits own 2, 2, 1, 0 tiles
+    "short splits, odd batch": (255, 600, 12, 0),            # the last 2-user row block holds one user
+}
+
+
+def method_of(top_k):
+    return ("mean", None) if top_k == 0 else (("maximum", None) if top_k == 1 else ("average_top_k", top_k))
+
+
+def walk_case(B, N, F, seed, H=WALK_H):
+    """-> (features float32 [N, F], histories: one id array per user, 1..89 items).  User 0 and WALK_STALE_USERS have at least H
+    items (an item put in front of such a history stays outside the window), user 1's history is longer than 256 items (the
+    stride of the kernel's history loop), user 2 keeps only WALK_KEEP (fewer than K items, in two tiles), user 3's starts with
+    WALK_BORDERS."""
+    rng = np.random.default_rng(1000 * seed + 7 * B + N + F)
+    v = rng.standard_normal((N, F)).astype(np.float32)
+    lens = rng.integers(1, 90, size=B)
+    lens[0] = 60
+    for u in WALK_STALE_USERS:
+        lens[u] = rng.integers(H, 90)
+    hists = [rng.integers(1, N, size=int(n)) for n in lens]
+    hists[1] = rng.permutation(np.arange(1, N))[:min(260, N - 30)]
+    hists[2] = rng.permutation(np.array([i for i in range(1, N) if i not in WALK_KEEP]))
+    hists[3] = np.concatenate((np.array(WALK_BORDERS), hists[3]))
+    return v, hists
+
+
+def walk_histories(v, hists, top_k, unit, H=WALK_H, users=WALK_STALE_USERS):
+    """-> (histories, stale) for one reduction: user 0's float64 top-3 put in front of its history (masked, outside the window),
+    and for every user u of `users` whose float64 best unmasked item y is >= 129 the item y - 128 -- the same bit of the history
+    bitmap one tile earlier -- put in front of its history, provided the float64 gaps at ranks 1 and 2 then exceed 2 tol(F).
+    stale = [(u, y)]: y must come back at rank 1."""
+    method, top_num = method_of(top_k)
+    F = v.shape[1]
+    out = [np.asarray(h) for h in hists]
+    assert len(out[0]) >= H
+    out[0] = np.concatenate((topk(v, out[0], 3, method, top_num, H, unit)[0], out[0]))
+    stale = []
+    for u in users:
+        h = out[u]
+        assert len(h) >= H
+        y = int(topk(v, h, 1, method, top_num, H, unit)[0][0])
+        if y < 129 or (y - 128) in h:
+            continue
+        h2 = np.concatenate((np.array([y - 128]), h))
+        vals = topk(v, h2, 3, method, top_num, H, unit)[1]
+        if vals[0] - vals[1] > 2 * tol(F) and vals[1] - vals[2] > 2 * tol(F):
+            out[u] = h2
+            stale.append((u, y))
+    return out, stale

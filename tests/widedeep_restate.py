@@ -14,6 +14,8 @@ Two forms of the same function:
 import torch
 import torch.nn.functional as F
 
+from tests.din_restate import WALK_K, walk_histories, walk_users  # noqa: F401  (the walk cases share DIN's users and histories)
+
 WBIAS, WIDE, DEEP = "wide_bias", "wide_item_embedding.weight", "deep_item_embedding.weight"
 PRED_W, PRED_B = "deep_predict_layer.weight", "deep_predict_layer.bias"
 
@@ -203,3 +205,37 @@ def topk_grid():
             for D, L in TOPK_DL:
                 for B in TOPK_BS:
                     yield item_num, hidden, D, L, B
+
+
+# ---- the inputs of the multi-tile walk tests (tests/test_gpu_topk_walk.py; tests/test_topk_walk_cases.py checks them on the CPU) ----
+# name -> (item_num, B, L, hidden, D, seed); see tests/din_restate.py WALK_CASES for the regimes
+WALK_CASES = {
+    "one split, small": (300, 512, 10, (12, 4), 16, 0),
+    "one split, shipped": (300, 512, 10, (80, 40), 64, 0),
+    "one split, one layer": (300, 512, 10, (12,), 16, 0),
+    "short splits": (600, 128, 10, (12, 4), 16, 0),
+    "limits": (257, 3, 64, (128, 128), 8, 0),
+    "hidden 4": (257, 3, 64, (4,), 8, 0),
+}
+
+
+def walk_case(item_num, B, L, hidden, D, seed):
+    """-> (P as topk_case builds it, window, histories) with walk_users' users: random pad lengths, an all-padding window (user 4: it
+    reads row 0 of both tables and is ranked like any other), a history longer than 256 items, a user who keeps fewer than K items."""
+    g = torch.Generator().manual_seed(1000003 * seed + 7 * item_num + 31 * B + 1009 * D + 101 * L + 13 * sum(hidden) + len(hidden))
+    P = {}
+    keys = names(len(hidden))
+    P[WBIAS] = torch.randn(1, generator=g) * 0.1
+    P[WIDE] = torch.randn(item_num, 1, generator=g) * (2.0 / (item_num + 1)) ** 0.5
+    P[DEEP] = torch.randn(item_num, D, generator=g) * (2.0 / (item_num + D)) ** 0.5
+    sizes = [(L + 1) * D] + list(hidden) + [1]
+    for i, (a, b) in enumerate(zip(sizes[:-1], sizes[1:])):
+        P[keys[3 + 2 * i]] = torch.randn(b, a, generator=g) * (2.0 / (a + b)) ** 0.5
+        P[keys[4 + 2 * i]] = torch.randn(b, generator=g) * 0.1
+    window, hist = walk_users(item_num, B, L, g)
+    return P, window, hist
+
+
+def scores64(P, window, device="cpu"):
+    """predict_factorised on .double() parameters, on `device`."""
+    return predict_factorised({k: v.to(device=device, dtype=torch.float64) for k, v in P.items()}, window.to(device)).cpu()
