@@ -131,20 +131,38 @@ int pxr_shard_first_rows_i64(const int64_t* ids_all, int W, int64_t cap, int ran
  * atomics, row 0 dropped, every other row (BERT4Rec's mask token item_num included) ordinary. */
 int pxr_seq_occ_sort(const int64_t* items, int B, int L, int64_t id_bstride, int64_t in_off, int64_t pos_off, int64_t neg_off,
                      int64_t n_table, int64_t* uniq_idx, int32_t* n_uniq_dev, void* ws, int64_t ws_bytes, void* stream);
+/* A TAIL RIDER: small reductions that close a backward pass and share no byte with the segment sums, run by extra workgroups
+ * appended to the grid of the ONE phase-2 launch instead of by launches of their own.  n (0..16) partial-reduction problems with
+ * the meaning of pxr_reduce_partials_multi_f32's arguments (out_b[i] NULL: single output; bump_counter optional), and, when
+ * loss != NULL, the loss sum loss[0] = (1/B) sum_b sum_t lossrow[b*L + t] that pxr_ln_residual_bpr_fwd_f32(loss = NULL) left
+ * undone.  Same code, same association, same bits as the stand-alone launches.  The descriptor is host memory, read during the
+ * call only.  The caller guarantees that none of its buffers is one the carrier reads or writes. */
+typedef struct pxr_tail_rider {
+  int32_t n, B, L, reserved;
+  const float* part[16];
+  float* out_a[16];
+  float* out_b[16];
+  int32_t P[16], N[16], split[16];
+  int64_t* bump_counter;
+  const float* lossrow;
+  float* loss;
+} pxr_tail_rider;
+/* rider: a pxr_tail_rider or NULL (none) */
 int pxr_sasrec_occ_segsum(const void* ws, int64_t ws_bytes, int B, int L, const float* dx0, const float* out,
                           const float* coef, int D, int64_t n_table, float scale, const int32_t* n_uniq_dev,
-                          float* uniq_rows, void* stream);
+                          float* uniq_rows, void* stream, const void* rider);
 /* Phase 2 with the lazy AdamW row update inside (one rank, lazy table update, scale 1): one launch leaves in table / m / v / last
  * what pxr_sasrec_occ_segsum followed by pxr_adamw_rows_f32(rows = uniq_idx, grows = uniq_rows, t_apply = t_prev + 1) leaves there
  * for rows that are current through t_prev, bit for bit; the summed rows are applied where they are formed and never written.
  * uniq_idx / n_uniq_dev: phase 1's output.  hyper: the per-step scalars (pxr_adamw_hyper_append; entry t_prev + 1 must exist);
  * step_dev != NULL: t_prev = *step_dev.  A row with last[row] != t_prev is left untouched and raises status bit 256
  * (PXR_STATUS_ROWS_STALE); id 0 and ids outside [0, table_rows) are skipped.  Every segment is summed by one workgroup: batches
- * that want pxr_sasrec_occ_segsum_split keep the two launches. */
+ * that want pxr_sasrec_occ_segsum_split keep the two launches.  rider: a pxr_tail_rider or NULL (none). */
 int pxr_sasrec_occ_segsum_apply(const void* ws, int64_t ws_bytes, int B, int L, const float* dx0, const float* out,
                                 const float* coef, int D, int64_t n_table, const int32_t* n_uniq_dev, const int64_t* uniq_idx,
                                 float* table, float* m, float* v, int32_t* last, int64_t table_rows, const void* hyper,
-                                int64_t t_prev, const int64_t* step_dev, double beta1, double beta2, double eps, void* stream);
+                                int64_t t_prev, const int64_t* step_dev, double beta1, double beta2, double eps, void* stream,
+                                const void* rider);
 
 /* Phase 2 for big batches (round 5): the same sums, with the rows of more than 1 024 occurrences (a Zipf-popular item of a
  * 2 048-sequence batch has 13 000) cut into parts of 512 occurrences that many workgroups sum, the parts of a row added in part
@@ -471,7 +489,8 @@ int pxr_bpr_loss_bwd_f32(const float* pos_score, const float* neg_score, const f
                          int64_t neg_off, void* stream);
 /* The block's LAST LayerNorm (reference layers.py:670-671, the output sasrec.py:86 names) with the loss head's forward
  * (sasrec.py:88-92) fused in: y = LN(dropout(x) + res) over B*L rows, pos / neg scores and the loss as pxr_bpr_loss_fwd_f32
- * would compute them from y -- bit-identical, one launch and one pass over y less.  Same id layout. */
+ * would compute them from y -- bit-identical, one launch and one pass over y less.  Same id layout.  loss == NULL: lossrow is
+ * written and the one-workgroup sum over it is left to the caller (a pxr_tail_rider of the same step's backward). */
 int pxr_ln_residual_bpr_fwd_f32(const float* x, const float* res, const float* gamma, const float* beta, float eps, int B, int L,
                                 int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed, uint32_t stream_id,
                                 const int64_t* step_dev, const float* table, int64_t n_table, const int64_t* items,

@@ -12,6 +12,7 @@
 //     d out[b,t,:]   = coef * (E[pos_id] - E[neg_id])
 //     d E[pos_id,:] += coef * out[b,t,:],  d E[neg_id,:] -= coef * out[b,t,:]   (done by embed_grad.hip from coef)
 #include "pxr_common.h"
+#include "reduce_multi.cuh"
 
 namespace pxr {
 
@@ -75,28 +76,7 @@ __global__ void __launch_bounds__(256) bpr_fwd_kernel(BprArgs a) {
 __global__ void __launch_bounds__(256) bpr_reduce_kernel(const float* __restrict__ lossrow, int B, int L,
                                                          float* __restrict__ loss) {
   __shared__ float red[256];
-  float s = 0.f;
-  for (int b = threadIdx.x; b < B; b += 256) {
-    const float* row = lossrow + (int64_t)b * L;
-    float sb = 0.f;
-    int t = 0;
-    for (; t + 8 <= L; t += 8) {   // 8 independent loads per round trip, added in position order
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = row[t + u];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) sb += v[u];
-    }
-    for (; t < L; ++t) sb += row[t];
-    s += sb;
-  }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = red[0] / (float)B;
+  pxr_bpr_reduce_block(lossrow, B, L, loss, red, (int)threadIdx.x);   // reduce_multi.cuh: shared with the rider blocks (embed_grad.hip)
 }
 
 __global__ void __launch_bounds__(256) bpr_bwd_kernel(BprArgs a) {

@@ -26,6 +26,7 @@
 // hipGraph-capturable and needs no host synchronisation.
 #include "adam_row.cuh"
 #include "pxr_common.h"
+#include "reduce_multi.cuh"
 
 #include <cstdlib>
 
@@ -665,9 +666,10 @@ __device__ __forceinline__ void seg_long_row(const SegSumArgs& a, const SINK& si
 // moves data: round 5 keeps the first two links of the NEXT two passes in flight while the rows of this pass are summed (the
 // segment bounds two passes ahead, the first two ids one pass ahead), and looks at the long rows once per SEG_EPOCH passes instead
 // of synchronising the eight waves twice per pass.  Same sums in the same order.  The body of segsum_kernel and of
-// segsum_apply_kernel: they differ in the sink alone.
+// segsum_apply_kernel: they differ in the sink alone.  nblk: the workgroups that run it, blocks [0, nblk) of the grid (a launch
+// that carries a rider has more blocks than that: segsum_rider below).
 template <int MODE, class SINK>
-__device__ __forceinline__ void segsum_body(const SegSumArgs& a, SINK sink) {
+__device__ __forceinline__ void segsum_body(const SegSumArgs& a, SINK sink, const int nblk) {
   extern __shared__ __attribute__((aligned(16))) float4 sred[];  // [G][dv]
   __shared__ int64_t s_off[SEG_CHUNK];
   __shared__ float s_cf[SEG_CHUNK];
@@ -684,13 +686,13 @@ __device__ __forceinline__ void segsum_body(const SegSumArgs& a, SINK sink) {
   const int c0 = wide ? threadIdx.x : threadIdx.x - g * dv;
   const bool active = g < G;
   if (wide || G > SEG_THREADS / 64) {                 // one row per pass, the whole workgroup on it
-    for (int u = blockIdx.x; u < nu; u += gridDim.x) {
+    for (int u = blockIdx.x; u < nu; u += nblk) {
       seg_long_row<MODE>(a, sink, u, dv, G, g, c0, active, sred, s_off, s_cf);
       __syncthreads();
     }
     return;
   }
-  const int stride = gridDim.x * G;
+  const int stride = nblk * G;
   auto bounds = [&](int u, int& s0, int& cnt, int& row) {
     s0 = 0; cnt = 0; row = 0;
     if (active && u < nu) {
@@ -769,15 +771,36 @@ __device__ __forceinline__ void segsum_body(const SegSumArgs& a, SINK sink) {
   }
 }
 
+// ---- the tail rider (reduce_multi.cuh) -----------------------------------------------------------------------------------
+// The single phase-2 launch of a step may carry the small reductions that close the backward pass (LayerNorm dgamma|dbeta, bias
+// and position column sums, the dropout counter bump, the loss sum): blocks [0, seg_grid) are the segment sums, unchanged;
+// blocks [seg_grid, seg_grid + r.blocks) run the rider and nothing else.  The branch is block-uniform and comes first.  The two
+// kinds of block share no byte (the launch sites say which buffers are whose), so there is nothing to order between them: no
+// atomics on data, no fences, no flags.  A rider block borrows the dynamic LDS of the carrier (sred, SEG_THREADS * 16 bytes).
+static_assert(PXR_RIDER_THREADS == SEG_THREADS, "a rider block has the carrier's shape");
+static_assert(PXR_RIDER_LDS <= SEG_THREADS * 16, "a rider block fits the carrier's dynamic LDS");
+// true: this block was a rider block and is done.  seg_grid: the carrier's block count
+__device__ __forceinline__ bool segsum_rider(const TailRider& r, int& seg_grid) {
+  extern __shared__ __attribute__((aligned(16))) float4 sred[];
+  seg_grid = (int)gridDim.x - r.blocks;
+  if (r.blocks == 0 || (int)blockIdx.x < seg_grid) return false;
+  pxr_tail_rider_block(r, (int)blockIdx.x - seg_grid, sred);
+  return true;
+}
+
 template <int MODE>
-__global__ void __launch_bounds__(SEG_THREADS) segsum_kernel(SegSumArgs a) {
-  segsum_body<MODE>(a, SegStoreRows{});
+__global__ void __launch_bounds__(SEG_THREADS) segsum_kernel(SegSumArgs a, TailRider r) {
+  int seg_grid;
+  if (segsum_rider(r, seg_grid)) return;
+  segsum_body<MODE>(a, SegStoreRows{}, seg_grid);
 }
 
 // The segment sums with the row update done where the sum is formed: no uniq_rows store, no second launch reading it back.
 // split must be 0 (every segment is summed here).
-__global__ void __launch_bounds__(SEG_THREADS) segsum_apply_kernel(SegSumArgs a, SegApplyRows s) {
-  segsum_body<MODE_SASREC>(a, s);
+__global__ void __launch_bounds__(SEG_THREADS) segsum_apply_kernel(SegSumArgs a, SegApplyRows s, TailRider r) {
+  int seg_grid;
+  if (segsum_rider(r, seg_grid)) return;
+  segsum_body<MODE_SASREC>(a, s, seg_grid);
 }
 
 // +0.0 over the dense block in front of its segment sums (a kernel, not a memset node: h2.hip's h2_zero_kernel says why)
@@ -787,7 +810,7 @@ __global__ void __launch_bounds__(256) dense_zero_kernel(float4* __restrict__ p,
 
 // MODE_POOL's segment sums into a dense block (SegStoreDense): the sums and their order are segsum_kernel<MODE_POOL>'s.
 __global__ void __launch_bounds__(SEG_THREADS) segsum_dense_kernel(SegSumArgs a, SegStoreDense s) {
-  segsum_body<MODE_POOL>(a, s);
+  segsum_body<MODE_POOL>(a, s, (int)gridDim.x);
 }
 
 // ---- very long segments on many workgroups (round 5) --------------------------------------------------------------------------
@@ -1106,7 +1129,7 @@ extern "C" int pxr_embed_grad_rows_f32(const int64_t* idx, int64_t n, const floa
   a.vals = sorted_vals; a.seg_start = w.seg_start; a.n_uniq = n_uniq_dev; a.src0 = rows; a.uniq_rows = uniq_rows;
   a.scale = scale; a.D = D; a.T = (int)n;
   const int grid = (int)(n < 4096 ? n : 4096);
-  hipLaunchKernelGGL(segsum_kernel<MODE_ROWS>, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, st, a);
+  hipLaunchKernelGGL(segsum_kernel<MODE_ROWS>, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, st, a, TailRider{});
   return pxr_check_launch("pxr_embed_grad_rows_f32");
 }
 
@@ -1138,7 +1161,7 @@ extern "C" int pxr_pool_table_grad_f32(const int64_t* gidx, int B, int L, const 
   a.vals = sorted_vals; a.seg_start = sw.seg_start; a.n_uniq = n_uniq_dev; a.src0 = G; a.coef = w; a.uniq_rows = uniq_rows;
   a.scale = 1.f; a.D = D; a.T = B * L; a.L = L;
   const int grid = n < 4096 ? n : 4096;
-  hipLaunchKernelGGL(segsum_kernel<MODE_POOL>, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, st, a);
+  hipLaunchKernelGGL(segsum_kernel<MODE_POOL>, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, st, a, TailRider{});
   return pxr_check_launch("pxr_pool_table_grad_f32");
 }
 
@@ -1227,7 +1250,7 @@ extern "C" int pxr_seq_occ_sort(const int64_t* items, int B, int L, int64_t id_b
 // Phase 2: uniq_rows[u,:] = scale * sum over the occurrences of unique id u (see the header comment for the terms).
 extern "C" int pxr_sasrec_occ_segsum(const void* ws, int64_t ws_bytes, int B, int L, const float* dx0, const float* out,
                                      const float* coef, int D, int64_t n_table, float scale,
-                                     const int32_t* n_uniq_dev, float* uniq_rows, void* stream) {
+                                     const int32_t* n_uniq_dev, float* uniq_rows, void* stream, const void* rider) {
   PXR_REQUIRE(ws && dx0 && out && coef && n_uniq_dev && uniq_rows, "pxr_sasrec_occ_segsum: null pointer");
   PXR_REQUIRE(B > 0 && L > 0 && D > 0 && D % 4 == 0, "pxr_sasrec_occ_segsum: bad shape");
   const int n = 3 * B * L;
@@ -1237,7 +1260,13 @@ extern "C" int pxr_sasrec_occ_segsum(const void* ws, int64_t ws_bytes, int B, in
   a.vals = sasrec_sorted_vals(w, n, n_table); a.seg_start = w.seg_start; a.n_uniq = n_uniq_dev; a.src0 = dx0; a.src1 = out;
   a.coef = coef; a.uniq_rows = uniq_rows; a.scale = scale; a.D = D; a.T = B * L;
   const int grid = n < 4096 ? n : 4096;
-  hipLaunchKernelGGL(segsum_kernel<MODE_SASREC>, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, (hipStream_t)stream, a);
+  TailRider r;
+  if (int rc = pxr_tail_rider_prepare(rider, "pxr_sasrec_occ_segsum", &r)) return rc;
+  // who touches what (nothing is shared, so the rider blocks need no ordering against the carrier's):
+  //   carrier: reads the occurrence workspace ws (sorted ids, segment bounds), n_uniq_dev, dx0, out, coef; writes uniq_rows;
+  //   rider:   reads the partial workspaces of the LayerNorm / column-sum first stages and lossrow; writes the slices of the
+  //            flat gradient buffer (LN gamma|beta, biases, positions), the dropout step counter and the loss scalar.
+  hipLaunchKernelGGL(segsum_kernel<MODE_SASREC>, dim3(grid + r.blocks), dim3(SEG_THREADS), SEG_THREADS * 16, (hipStream_t)stream, a, r);
   return pxr_check_launch("pxr_sasrec_occ_segsum");
 }
 
@@ -1251,7 +1280,7 @@ extern "C" int pxr_sasrec_occ_segsum_apply(const void* ws, int64_t ws_bytes, int
                                            const float* coef, int D, int64_t n_table, const int32_t* n_uniq_dev,
                                            const int64_t* uniq_idx, float* table, float* m, float* v, int32_t* last,
                                            int64_t table_rows, const void* hyper, int64_t t_prev, const int64_t* step_dev,
-                                           double beta1, double beta2, double eps, void* stream) {
+                                           double beta1, double beta2, double eps, void* stream, const void* rider) {
   PXR_REQUIRE(ws && dx0 && out && coef && n_uniq_dev && uniq_idx && table && m && v && last && hyper,
               "pxr_sasrec_occ_segsum_apply: null pointer");
   PXR_REQUIRE(B > 0 && L > 0 && D > 0 && D % 4 == 0 && D <= 4096, "pxr_sasrec_occ_segsum_apply: bad shape (D <= 4096)");
@@ -1269,7 +1298,16 @@ extern "C" int pxr_sasrec_occ_segsum_apply(const void* ws, int64_t ws_bytes, int
   s.c = AdamConsts{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps};
   s.status = pxr_status_word();
   const int grid = n < 4096 ? n : 4096;
-  hipLaunchKernelGGL(segsum_apply_kernel, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, (hipStream_t)stream, a, s);
+  TailRider r;
+  if (int rc = pxr_tail_rider_prepare(rider, "pxr_sasrec_occ_segsum_apply", &r)) return rc;
+  // who touches what (nothing is shared, so the rider blocks need no ordering against the carrier's):
+  //   carrier: reads the occurrence workspace ws (sorted ids, segment bounds), n_uniq_dev, uniq_idx, dx0, out, coef, the hyper
+  //            slot of step t_prev + 1 and the optimizer's step counter step_dev; reads and writes the touched rows of table / m /
+  //            v and their last[] marks; may raise the status word;
+  //   rider:   reads the partial workspaces of the LayerNorm / column-sum first stages and lossrow; writes the slices of the
+  //            flat gradient buffer (LN gamma|beta, biases, positions), the DROPOUT step counter (another word than step_dev: no
+  //            segment-sum kernel reads it) and the loss scalar.
+  hipLaunchKernelGGL(segsum_apply_kernel, dim3(grid + r.blocks), dim3(SEG_THREADS), SEG_THREADS * 16, (hipStream_t)stream, a, s, r);
   return pxr_check_launch("pxr_sasrec_occ_segsum_apply");
 }
 
@@ -1312,7 +1350,7 @@ extern "C" int pxr_sasrec_occ_segsum_split(const void* ws, int64_t ws_bytes, int
   a.big_count = (int*)ws2; a.big_rows = (int*)((char*)ws2 + o1); a.partials = (float*)((char*)ws2 + o2);
   hipStream_t st = (hipStream_t)stream;
   const int grid = n < 4096 ? n : 4096;
-  hipLaunchKernelGGL(segsum_kernel<MODE_SASREC>, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, st, a);
+  hipLaunchKernelGGL(segsum_kernel<MODE_SASREC>, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, st, a, TailRider{});
   hipLaunchKernelGGL(segsum_parts_kernel<MODE_SASREC>, dim3(a.max_parts < 1024 ? a.max_parts : 1024), dim3(SEG_THREADS), SEG_THREADS * 16, st, a);
   hipLaunchKernelGGL(segsum_big_kernel, dim3(a.big_cap < 64 ? a.big_cap : 64), dim3(SEG_THREADS), 0, st, a);
   return pxr_check_launch("pxr_sasrec_occ_segsum_split");

@@ -13,6 +13,8 @@
 //   dgamma = sum_rows dy*xhat, dbeta = sum_rows dy  -> per-block partials, summed in fixed order by
 //   pxr_colsum-style stage 2 (deterministic, no float atomics).
 #include "planes.cuh"
+#include "reduce_multi.cuh"
+#include "../../include/pxr.h"   // pxr_tail_rider
 
 #include <cstdlib>
 
@@ -628,7 +630,7 @@ extern "C" int pxr_ln_residual_bpr_fwd_f32(const float* x, const float* res, con
                                            float* neg_score, float* lossrow, float* loss, int64_t id_bstride, int64_t pos_off,
                                            int64_t neg_off, void* stream) {
   PXR_REQUIRE(pxr_bpr_layout_ok(L, id_bstride, pos_off, neg_off), "pxr_ln_residual_bpr_fwd_f32: bad id layout");
-  PXR_REQUIRE(x && gamma && beta && y && table && items && masked_index && pos_score && neg_score && lossrow && loss,
+  PXR_REQUIRE(x && gamma && beta && y && table && items && masked_index && pos_score && neg_score && lossrow,
               "pxr_ln_residual_bpr_fwd_f32: null pointer");
   PXR_REQUIRE(D > 0 && D % 4 == 0 && B > 0 && L > 0 && n_table > 0, "pxr_ln_residual_bpr_fwd_f32: bad shape");
   PXR_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "pxr_ln_residual_bpr_fwd_f32: bad dropout p");
@@ -643,6 +645,7 @@ extern "C" int pxr_ln_residual_bpr_fwd_f32(const float* x, const float* res, con
   a.status = pxr_status_word();   // the head's bad-index flag (no planes here, so nothing else of this launch writes it)
   const int rc = launch_ln_fwd<false>(a, (hipStream_t)stream);
   if (rc) return rc;
+  if (!loss) return PXR_OK;      // the sum over lossrow rides in the tail launch of the same step's backward (pxr_tail_rider)
   return pxr_bpr_loss_reduce(lossrow, B, L, loss, stream);
 }
 
@@ -783,29 +786,50 @@ static int ln_bwd_impl(int gather_mode, const float* dy, const float* xhat, cons
 }
 
 // ---- several partial reductions in one launch ------------------------------------------------------------------
-struct MultiReduce {
-  const float* part[16]; float* out_a[16]; float* out_b[16];
-  int P[16], N[16], split[16], blk_begin[17];
-  int n;
-  int64_t* bump;   // optional device counter incremented by one (e.g. the dropout step counter: this is the last
-                   // kernel of a backward pass that could read it, so the separate 1-thread launch is saved)
-};
+// (MultiReduce and the body of the kernel: reduce_multi.cuh, shared with the rider blocks of the segment sums, embed_grad.hip)
 __global__ void __launch_bounds__(256) reduce_partials_multi_kernel(MultiReduce m) {
   __shared__ float red[PXR_RED_CY][PXR_RED_CX + 1];
-  int pi = 0;
-  for (int i = 1; i < m.n; ++i)
-    if ((int)blockIdx.x >= m.blk_begin[i]) pi = i;
-  const float* part = m.part[pi];
-  const int P = m.P[pi], N = m.N[pi];
-  const int tx = threadIdx.x % PXR_RED_CX, ty = threadIdx.x / PXR_RED_CX;
-  const int col = ((int)blockIdx.x - m.blk_begin[pi]) * PXR_RED_CX + tx;
-  const float s = (col < N) ? pxr_strided_column_sum(part, P, N, col, ty) : 0.f;
-  const float v = pxr_combine_row_lanes(s, red, tx, ty);
-  if (ty == 0 && col < N) {
-    if (col < m.split[pi]) m.out_a[pi][col] = v;
-    else m.out_b[pi][col - m.split[pi]] = v;
+  pxr_reduce_multi_group(m, (int)blockIdx.x, (int)threadIdx.x, red);
+}
+
+// problems -> kernel argument (checked); returns the number of column groups in *groups
+static int multi_reduce_fill(const char* what, int n, const float* const* part, const int* P, const int* N, float* const* out_a,
+                             float* const* out_b, const int* split, int64_t* bump_counter, MultiReduce* m, int* groups) {
+  m->n = n;
+  m->bump = bump_counter;
+  int blocks = 0;
+  for (int i = 0; i < n; ++i) {
+    PXR_REQUIRE(part[i] && out_a[i] && P[i] > 0 && N[i] > 0, "%s: problem %d is bad", what, i);
+    m->part[i] = part[i]; m->out_a[i] = out_a[i]; m->out_b[i] = out_b[i] ? out_b[i] : out_a[i];
+    m->P[i] = P[i]; m->N[i] = N[i]; m->split[i] = out_b[i] ? split[i] : N[i];
+    m->blk_begin[i] = blocks;
+    blocks += (N[i] + PXR_RED_CX - 1) / PXR_RED_CX;
   }
-  if (m.bump && blockIdx.x == 0 && threadIdx.x == 0) m.bump[0] += 1;
+  m->blk_begin[n] = blocks;
+  *groups = blocks;
+  return PXR_OK;
+}
+
+int pxr_tail_rider_prepare(const void* rider, const char* what, TailRider* out) {
+  *out = TailRider{};
+  if (!rider) return PXR_OK;
+  const pxr_tail_rider* r = (const pxr_tail_rider*)rider;
+  PXR_REQUIRE(r->n >= 0 && r->n <= 16, "%s: a rider carries at most 16 reduction problems (n=%d)", what, r->n);
+  PXR_REQUIRE(r->n > 0 || !r->bump_counter, "%s: the rider's counter bump travels with its reductions (n = 0)", what);
+  int groups = 0;
+  if (r->n > 0) {
+    int32_t P[16], N[16], split[16];
+    for (int i = 0; i < r->n; ++i) { P[i] = r->P[i]; N[i] = r->N[i]; split[i] = r->split[i]; }
+    const int rc = multi_reduce_fill(what, r->n, r->part, P, N, r->out_a, r->out_b, split, r->bump_counter, &out->m, &groups);
+    if (rc) return rc;
+  }
+  out->red_blocks = (groups + 1) / 2;
+  if (r->loss) {
+    PXR_REQUIRE(r->lossrow && r->B > 0 && r->L > 0, "%s: the rider's loss problem is bad", what);
+    out->lossrow = r->lossrow; out->loss = r->loss; out->B = r->B; out->L = r->L;
+  }
+  out->blocks = out->red_blocks + (r->loss ? 1 : 0);
+  return PXR_OK;
 }
 
 // out_a[i][c] (c < split[i]) / out_b[i][c - split[i]] = sum_p part[i][p][c], c < N[i], for up to 16 independent
@@ -815,17 +839,8 @@ extern "C" int pxr_reduce_partials_multi_f32(int n, const float* const* part, co
                                              int64_t* bump_counter, void* stream) {
   PXR_REQUIRE(n >= 1 && n <= 16 && part && P && N && out_a && out_b && split, "pxr_reduce_partials_multi_f32: bad args");
   MultiReduce m{};
-  m.n = n;
-  m.bump = bump_counter;
   int blocks = 0;
-  for (int i = 0; i < n; ++i) {
-    PXR_REQUIRE(part[i] && out_a[i] && P[i] > 0 && N[i] > 0, "pxr_reduce_partials_multi_f32: problem %d is bad", i);
-    m.part[i] = part[i]; m.out_a[i] = out_a[i]; m.out_b[i] = out_b[i] ? out_b[i] : out_a[i];
-    m.P[i] = P[i]; m.N[i] = N[i]; m.split[i] = out_b[i] ? split[i] : N[i];
-    m.blk_begin[i] = blocks;
-    blocks += (N[i] + PXR_RED_CX - 1) / PXR_RED_CX;
-  }
-  m.blk_begin[n] = blocks;
+  if (int rc = multi_reduce_fill("pxr_reduce_partials_multi_f32", n, part, P, N, out_a, out_b, split, bump_counter, &m, &blocks)) return rc;
   hipLaunchKernelGGL(reduce_partials_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, m);
   return pxr_check_launch("pxr_reduce_partials_multi_f32");
 }

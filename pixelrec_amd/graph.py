@@ -24,6 +24,8 @@ class GraphedTrainStep:
         # every step goes through optimizer.step(): the join with the weight-gradient side stream can wait until the
         # flat gradient is consumed (seqcore.SeqRecCore.wait_flat_grads) -- inside the capture, so the graph is closed
         self.model.defer_weight_grad_join = True
+        if hasattr(self.model, "defer_loss_reduce"):
+            self.model.defer_loss_reduce = True          # the loss is read after the replay: its sum rides in the backward's tail launch
         if hasattr(self.model, "split_catch_up") and getattr(self.model, "_split_env", None) is None:
             self.model.split_catch_up = True             # sasrec.SASRec._forward_train: fork / join are graph edges here
         if hasattr(self.model, "trust_optimizer_planes"):

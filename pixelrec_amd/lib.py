@@ -47,9 +47,9 @@ _SIGNATURES = {
     "pxr_packed_rows_bytes": (_I64, [_I64, _I]),
     "pxr_merge_packed_rows_f32": (_I, [_P, _I, _I64, _I, _I64, _F, _P, _P, _P, _P, _I64, _P]),
     "pxr_seq_occ_sort": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _I64, _P]),
-    "pxr_sasrec_occ_segsum": (_I, [_P, _I64, _I, _I, _P, _P, _P, _I, _I64, _F, _P, _P, _P]),
+    "pxr_sasrec_occ_segsum": (_I, [_P, _I64, _I, _I, _P, _P, _P, _I, _I64, _F, _P, _P, _P, _P]),
     "pxr_sasrec_occ_segsum_apply": (_I, [_P, _I64, _I, _I, _P, _P, _P, _I, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _D, _D, _D,
-                                         _P]),
+                                         _P, _P]),
     "pxr_sasrec_occ_split_ws_bytes": (_I64, [_I, _I, _I]),
     "pxr_sasrec_occ_segsum_split": (_I, [_P, _I64, _I, _I, _P, _P, _P, _I, _I64, _F, _P, _P, _P, _I64, _P]),
     "pxr_input_ln_fwd_f32": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _I64, _I,

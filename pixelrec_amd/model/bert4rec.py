@@ -40,6 +40,7 @@ class BERT4Rec(SASRec):
     # the bidirectional mask and the aligned [B, 3, P] id layout
     _causal = False
     _split_catch_up_ok = False   # (the split catch-up reads SASRec's [B, 2, L+1] input window; the plain catch-up serves)
+    _tail_carrier = False        # the closing reductions of its backward stay launches of their own
 
     def __init__(self, config, dataload):
         # SASRec.__init__ with the table and position counts of BERT4Rec (bert4rec.py:29-35)

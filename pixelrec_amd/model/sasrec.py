@@ -21,6 +21,7 @@ import torch.nn as nn
 from .. import ops
 from ..utils.enum_type import InputType
 from .packed import TableHooks, TrainStep
+from ..lib import PxrError
 from .seqcore import SeqRecCore
 
 
@@ -239,9 +240,22 @@ class SASRec(TableHooks, SeqRecCore):
         self._issue_fork()       # (an encoder without the _after_input_ln hook: issue now, no overlap)
         self._join_sort()        # split catch-up: the loss head reads the target / negative rows the side stream brought current
 
+    # the phase-2 launch of the table gradient carries the backward's closing reductions (ops.TailRider) on its single-launch routes
+    _tail_carrier = True
+
+    def _tail_has_carrier(self):
+        """Whether this step's _after_input_grads is ONE segment-sum launch (rows_apply_handle's, or the plain route without the
+        split workspace of big batches): known once _forward_train has sized the workspaces.  Not in a step with collectives (a
+        row exchange hooked behind the segment sums, parallel.GradSync): it keeps the launches it had."""
+        return (self._tail_carrier and not getattr(self, "_sharded", False) and self._occ_ws2 is None
+                and getattr(self, "_sparse_ready_hook", None) is None)
+
     def _after_input_grads(self, dx0, coef, s):
         sp = self._local_sparse
         self._join_sort()
+        rider, self._tail_rider = self._tail_rider, None      # (the join above now also precedes these reductions)
+        if rider is not None and self._occ_ws2 is not None:
+            raise PxrError("a tail rider was prepared for a step whose segment sums take the split route")
         # one rank, lazy table update, every backward followed by the optimizer's step (PxrAdamW.rows_apply_handle): the rows take
         # this step's update inside the segment-sum launch.  Not with the split route of big batches (the long rows' sums are
         # finished by later launches) and not beside a look-ahead catch-up that may still be reading rows on its side stream
@@ -249,10 +263,10 @@ class SASRec(TableHooks, SeqRecCore):
         apply_rows = (hooks.rows_apply_handle() if (hasattr(hooks, "rows_apply_handle") and self._occ_ws2 is None
                                                     and self._prefetched is None) else None)
         if apply_rows is not None:
-            apply_rows(self._occ_ws, dx0, s["out"], coef, self._table_rows(), sp)
+            apply_rows(self._occ_ws, dx0, s["out"], coef, self._table_rows(), sp, **({"rider": rider} if rider is not None else {}))
         else:
             sp.applied = False
-            ops.sasrec_occ_segsum(self._occ_ws, dx0, s["out"], coef, self._table_rows(), sp, 1.0, ws2=self._occ_ws2)
+            ops.sasrec_occ_segsum(self._occ_ws, dx0, s["out"], coef, self._table_rows(), sp, 1.0, ws2=self._occ_ws2, rider=rider)
         self.sparse_table_grad = sp
         hook = getattr(self, "_sparse_ready_hook", None)
         if hook is not None:

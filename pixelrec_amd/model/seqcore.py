@@ -115,6 +115,10 @@ class SeqRecCore(PackedModel):
         # also runs beside the weight-gradient GEMMs.  Opt-in (GraphedTrainStep / Trainer / bench.py set it): code that
         # reads p.grad right after backward() must not race with the side stream.
         self.defer_weight_grad_join = False
+        # leave the one-workgroup sum of the loss to the tail launch of the same step's backward (ops.TailRider): the loss tensor a
+        # training forward returns is then UNWRITTEN until backward() has been issued.  Opt-in (GraphedTrainStep / Trainer set it):
+        # for loops that read the loss after the step.  Without a carrier in the tail (_tail_has_carrier) nothing is deferred.
+        self.defer_loss_reduce = False
         self._drop_seed = int(config["seed"]) if config["seed"] is not None else 2020
         # GEMM operands as pre-split bf16x3 planes (csrc/gemm_p3.cuh): every producer of a GEMM operand (LayerNorm, attention,
         # GEMM epilogues) writes the three bf16 terms once, in the panel layout the GEMM tiles copy linearly, instead of every
@@ -204,6 +208,38 @@ class SeqRecCore(PackedModel):
         """Hook: runs inside the backward right after the gradient w.r.t. the gathered rows is known and BEFORE the
         grouped weight-gradient GEMM (so whatever it launches -- e.g. a data-parallel row exchange -- overlaps it)."""
         return None
+
+    # ---- tail riders: the backward's closing reductions inside a launch the tail runs anyway (ops.TailRider)
+    _tail_rider = None      # prepared by _backward_core for _after_input_grads, which must take it (only when _tail_has_carrier)
+    _loss_defer = None      # a list while a forward may leave the loss sum to the backward's tail (ops.ln_residual_bpr_fwd)
+
+    def _tail_has_carrier(self):
+        """Whether _after_input_grads of the step being set up is ONE launch that accepts a rider (SASRec's segment sums)."""
+        return False
+
+    def _close_reductions(self, defer, s):
+        """End of the input-gradient chain: the deferred second-stage reductions, the dropout counter bump and a deferred loss sum
+        either ride in the tail launch (-> self._tail_rider, decided by the forward: s["tail_riders"]) or run now, as launches of
+        their own.  -> whether the dropout step counter is bumped by them."""
+        loss = s.get("loss_deferred")
+        if not s.get("tail_riders"):
+            assert loss is None
+            return defer.flush(bump=self._drop_dev)
+        rider = defer.flush(bump=self._drop_dev, prepare=True)
+        if rider is None:
+            # nothing to reduce, or more than one rider holds: the reductions run on their own; the loss sum still rides
+            bumped = defer.flush(bump=self._drop_dev)
+            rider = ops.TailRider(loss=loss) if loss is not None else None
+        else:
+            bumped = True
+            rider.loss = loss
+        self._tail_rider = rider
+        return bumped
+
+    def _tail_rider_taken(self):
+        if self._tail_rider is not None:
+            self._tail_rider = None
+            raise PxrError("the backward's tail did not run the reductions prepared for it (a rider without a carrier)")
 
     # ------------------------------------------------------------------------------------------ planes mode
     def _planes_on(self) -> bool:
@@ -406,7 +442,7 @@ class SeqRecCore(PackedModel):
                 self._before_head()
                 h2, xhat2, rstd2, *self._head_out = ops.ln_residual_bpr_fwd(
                     f2, h1, self._p(f"{i}.ln2.w"), self._p(f"{i}.ln2.b"), eps, *head, p_drop=ph, seed=seed, stream_id=3 + 3 * i,
-                    save=train, step_dev=sdv, layout=self._head_layout)
+                    save=train, step_dev=sdv, layout=self._head_layout, defer_loss=self._loss_defer)
                 r = (h2, xhat2, rstd2, None)
             else:
                 r = ops.ln_residual_fwd(f2, h1, self._p(f"{i}.ln2.w"), self._p(f"{i}.ln2.b"), eps, ph, seed, 3 + 3 * i,
@@ -467,7 +503,7 @@ class SeqRecCore(PackedModel):
                 self._before_head()
                 h2, xhat2, rstd2, *self._head_out = ops.ln_residual_bpr_fwd(
                     f2, h1, self._p(f"{i}.ln2.w"), self._p(f"{i}.ln2.b"), eps, *head, p_drop=ph, seed=seed, stream_id=3 + 3 * i,
-                    save=train, step_dev=sdv, layout=self._head_layout)
+                    save=train, step_dev=sdv, layout=self._head_layout, defer_loss=self._loss_defer)
             else:
                 h2, xhat2, rstd2 = ops.ln_residual_fwd(f2, h1, self._p(f"{i}.ln2.w"), self._p(f"{i}.ln2.b"), eps, ph, seed,
                                                        3 + 3 * i, save=train, step_dev=sdv)
@@ -484,8 +520,16 @@ class SeqRecCore(PackedModel):
         L = self.max_seq_length
         fused = self._fused_head and os.environ.get("PXR_FUSED_HEAD", "1") != "0"
         idx_bstride, keymask, km_bstride = self._train_inputs(items, masked_index)
+        # the tail of this step's backward is one launch that can carry the closing reductions (knob PXR_TAIL_RIDERS, read per step)
+        riders = train and ops.tail_riders_on() and self._tail_has_carrier()
+        deferred = None
         if fused:
-            out, saved = self._encode(table, items, idx_bstride, B, keymask, km_bstride, train=train, head=(table, items, masked_index))
+            self._loss_defer = [] if (riders and self.defer_loss_reduce) else None
+            try:
+                out, saved = self._encode(table, items, idx_bstride, B, keymask, km_bstride, train=train, head=(table, items, masked_index))
+                deferred = self._loss_defer[0] if self._loss_defer else None
+            finally:
+                self._loss_defer = None
             loss, pos, neg = self._head_out
             self._head_out = None
         else:
@@ -495,7 +539,8 @@ class SeqRecCore(PackedModel):
         if saved is None:  # eval-mode forward (dropout off): activations are not kept, backward is unavailable
             self._saved = None
         else:
-            saved.update(out=out, pos=pos, neg=neg, items=items, mask=masked_index, B=B, fused_head=fused)
+            saved.update(out=out, pos=pos, neg=neg, items=items, mask=masked_index, B=B, fused_head=fused, tail_riders=riders,
+                         loss_deferred=deferred)
             self._saved = saved
         self._last_scores = (pos, neg)
         return loss
@@ -654,11 +699,12 @@ class SeqRecCore(PackedModel):
             dx0, _ = ops.ln_bwd(1, dh, s["xhat0"], s["rstd0"], self._p("ln0.w"), g("ln0.w"), g("ln0.b"), ph, seed, 0,
                                 step_dev=sdv, defer=defer)
             ops.colsum(dx0.view(B, L * D), out=g("pos").view(-1), defer=defer)
-            bumped = defer.flush(bump=self._drop_dev)
+            bumped = self._close_reductions(defer, s)
             # (round 5: "fork_tail" was tried here too -- the grouped launch on a side stream beside the segmented sum and the row
             # update.  Nothing overlaps: the 256x128 ping-pong workgroups hold a CU's whole register file and LDS, so the side
             # branch's kernels queue behind them (profiles/r05/README.md); the planes path keeps one stream.)
             self._after_input_grads(dx0, coef, s)
+            self._tail_rider_taken()
             ops.grouped_dw_planes(pend)
             if sites is not None:
                 # behind the last reader of the site exponents: next step's scales from this step's partial maxima (one launch)
@@ -712,8 +758,9 @@ class SeqRecCore(PackedModel):
         ops.colsum(dx0.view(B, L * D), out=g("pos").view(-1), defer=defer)
         # every dropout-mask consumer of this pass has been issued: the reduction launch also advances the dropout
         # step counter (saves a 1-thread launch per step)
-        bumped = defer.flush(bump=self._drop_dev)
+        bumped = self._close_reductions(defer, s)
         self._after_input_grads(dx0, coef, s)   # model-specific tail that only needs dx0/coef (table rows, exchange)
+        self._tail_rider_taken()
         if pending:
             ops.grouped_linear_bwd_weight(pending)
         if use_side:

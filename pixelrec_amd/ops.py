@@ -1033,12 +1033,14 @@ def ln_residual_fwd(x, res, gamma, beta, eps, p_drop=0.0, seed=0, stream_id=0, s
 
 
 def ln_residual_bpr_fwd(x, res, gamma, beta, eps, table, items, masked_index, p_drop=0.0, seed=0, stream_id=0, save=True,
-                        step_dev=None, layout=None):
+                        step_dev=None, layout=None, defer_loss: list | None = None):
     """The block's last LayerNorm with the loss head's forward fused in (pxr_ln_residual_bpr_fwd_f32):
     -> (y [B,L,D], xhat, rstd, loss [1], pos [B,L], neg [B,L]) -- what ln_residual_fwd + bpr_loss_fwd return, bit for bit for
     D <= 1024; beyond, y / xhat / rstd bit for bit and the scores / loss within the fp32 rounding of the dot product.
     layout = (id_bstride, pos_off, neg_off) of the target / negative ids in `items` (None: SASRec's shifted [B, 2, L+1] windows;
-    BERT4Rec's aligned [B, 3, L]: (3L, L, 2L))."""
+    BERT4Rec's aligned [B, 3, L]: (3L, L, 2L)).
+    defer_loss (a list): the one-workgroup sum over the per-position terms is NOT launched; the returned loss tensor stays unwritten
+    until the problem (lossrow, B, L, loss) appended to the list has run -- as part of a TailRider in the same step's backward."""
     Lb = _l.load()
     _req(x, torch.float32, "x"); _req(table, torch.float32, "table")
     _req(items, torch.int64, "items"); _req(masked_index, torch.int64, "masked_index")
@@ -1056,8 +1058,11 @@ def ln_residual_bpr_fwd(x, res, gamma, beta, eps, table, items, masked_index, p_
         _l.check(Lb.pxr_ln_residual_bpr_fwd_f32(_l.ptr(x), _l.ptr(res), _l.ptr(gamma), _l.ptr(beta), eps, B, L, D, _l.ptr(y),
                                                 _l.ptr(xhat), _l.ptr(rstd), p_drop, seed, stream_id, _l.ptr(step_dev), _l.ptr(table),
                                                 table.shape[0], _l.ptr(items), _l.ptr(masked_index), _l.ptr(pos), _l.ptr(neg),
-                                                _l.ptr(lossrow), _l.ptr(loss), *_head_layout(L, layout), _l.stream_ptr()),
+                                                _l.ptr(lossrow), None if defer_loss is not None else _l.ptr(loss),
+                                                *_head_layout(L, layout), _l.stream_ptr()),
                  "pxr_ln_residual_bpr_fwd_f32")
+    if defer_loss is not None:
+        defer_loss.append((lossrow, B, L, loss))
     return y, xhat, rstd, loss, pos, neg
 
 
@@ -1091,6 +1096,48 @@ def bpr_ln_bwd(pos, neg, table, items, masked_index, grad_scale, grad_scale_dev,
     return dz, dx, gp, coef
 
 
+def tail_riders_on() -> bool:
+    """The knob PXR_TAIL_RIDERS (default 1), read per call: the reductions that close a backward pass ride in the segment-sum launch
+    of the table gradient (TailRider) instead of running as launches of their own."""
+    return os.environ.get("PXR_TAIL_RIDERS", "1") != "0"
+
+
+class _CTailRider(ctypes.Structure):
+    """include/pxr.h: pxr_tail_rider."""
+    _fields_ = [("n", ctypes.c_int32), ("B", ctypes.c_int32), ("L", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("part", ctypes.c_void_p * 16), ("out_a", ctypes.c_void_p * 16), ("out_b", ctypes.c_void_p * 16),
+                ("P", ctypes.c_int32 * 16), ("N", ctypes.c_int32 * 16), ("split", ctypes.c_int32 * 16),
+                ("bump_counter", ctypes.c_void_p), ("lossrow", ctypes.c_void_p), ("loss", ctypes.c_void_p)]
+
+
+class TailRider:
+    """Small reductions prepared for a launch that runs anyway (the segment sums of the table gradient: sasrec_occ_segsum /
+    sasrec_occ_segsum_apply take one as `rider`): up to 16 problems of DeferredReductions, the counter bump that travels with them,
+    and the loss sum a forward left undone (ln_residual_bpr_fwd(defer_loss=...)).  Holds its tensors until it is handed over."""
+
+    def __init__(self, items=(), bump=None, loss=None):
+        assert len(items) <= 16 and (bump is None or items)
+        self.items, self.bump, self.loss = list(items), bump, loss     # loss: (lossrow, B, L, loss) | None
+
+    def __bool__(self):
+        return bool(self.items) or self.loss is not None
+
+    def c_arg(self):
+        """(pointer argument for the entry point, the structure to keep alive across the call)."""
+        if not self:
+            return None, None
+        r = _CTailRider()
+        r.n = len(self.items)
+        for i, (part, P, N, out_a, out_b, split) in enumerate(self.items):
+            r.part[i], r.out_a[i], r.out_b[i] = part.data_ptr(), out_a.data_ptr(), (out_b.data_ptr() if out_b is not None else None)
+            r.P[i], r.N[i], r.split[i] = P, N, split
+        r.bump_counter = self.bump.data_ptr() if self.bump is not None else None
+        if self.loss is not None:
+            lossrow, B, L, loss = self.loss
+            r.lossrow, r.B, r.L, r.loss = lossrow.data_ptr(), B, L, loss.data_ptr()
+        return ctypes.cast(ctypes.pointer(r), ctypes.c_void_p), r
+
+
 class DeferredReductions:
     """Collects the second stage of several partial reductions (LayerNorm dgamma|dbeta, column sums) so that one
     launch finishes all of them at the end of a backward pass."""
@@ -1101,11 +1148,17 @@ class DeferredReductions:
     def add(self, part, P, N, out_a, out_b=None, split=0):
         self.items.append((part, P, N, out_a, out_b, split))
 
-    def flush(self, bump: torch.Tensor | None = None) -> bool:
+    def flush(self, bump: torch.Tensor | None = None, prepare: bool = False):
         """One launch (per 16 problems).  `bump`: an int64 device counter the LAST launch increments by one; returns
-        whether it did (False when there was nothing to reduce: the caller then bumps it itself)."""
-        import ctypes
-
+        whether it did (False when there was nothing to reduce: the caller then bumps it itself).
+        prepare=True launches NOTHING: the collected problems (and the bump) are returned as a TailRider for a launch that will
+        carry them, and the collector is left empty -- or None, with the collector untouched, when one rider cannot hold them
+        (none, or more than 16): the caller then flushes as usual."""
+        if prepare:
+            if not self.items or len(self.items) > 16:
+                return None
+            rider, self.items = TailRider(self.items, bump), []
+            return rider
         if not self.items:
             return False
         Lb = _l.load()
@@ -1508,36 +1561,45 @@ def occ_split_ws_bytes(B: int, L: int, D: int) -> int:
     return int(_l.load().pxr_sasrec_occ_split_ws_bytes(B, L, D))
 
 
-def sasrec_occ_segsum(ws: torch.Tensor, dx0, out, coef, n_table, sp: SparseRows, scale=1.0, ws2: torch.Tensor | None = None):
+def sasrec_occ_segsum(ws: torch.Tensor, dx0, out, coef, n_table, sp: SparseRows, scale=1.0, ws2: torch.Tensor | None = None,
+                      rider: TailRider | None = None):
     """Phase 2: sp.rows from the sorted occurrences in `ws`.  ws2 (occ_split_ws_bytes zero-initialised bytes, persistent): very long
-    segments are summed by many workgroups (big batches: a popular item's thousands of occurrences)."""
+    segments are summed by many workgroups (big batches: a popular item's thousands of occurrences).  rider: reductions the ONE
+    launch of the plain route carries on extra workgroups (not with ws2)."""
     Lb = _l.load()
     B, L, D = out.shape
+    rarg, rkeep = rider.c_arg() if rider is not None else (None, None)
     if ws2 is not None:
+        if rarg is not None:
+            raise _l.PxrError("sasrec_occ_segsum: the split route (ws2) is three launches and carries no rider")
         _l.check(Lb.pxr_sasrec_occ_segsum_split(_l.ptr(ws), ws.numel(), B, L, _l.ptr(dx0), _l.ptr(out), _l.ptr(coef), D, n_table,
                                                 float(scale), _l.ptr(sp.n), _l.ptr(sp.rows), _l.ptr(ws2), ws2.numel(), _l.stream_ptr()),
                  "pxr_sasrec_occ_segsum_split")
         return
     _l.check(Lb.pxr_sasrec_occ_segsum(_l.ptr(ws), ws.numel(), B, L, _l.ptr(dx0), _l.ptr(out), _l.ptr(coef), D,
-                                      n_table, float(scale), _l.ptr(sp.n), _l.ptr(sp.rows), _l.stream_ptr()),
+                                      n_table, float(scale), _l.ptr(sp.n), _l.ptr(sp.rows), _l.stream_ptr(), rarg),
              "pxr_sasrec_occ_segsum")
+    del rkeep
 
 
 def sasrec_occ_segsum_apply(ws: torch.Tensor, dx0, out, coef, n_table, sp: SparseRows, table, m, v, last, hyper, t_prev, beta1, beta2,
-                            eps, step_dev=None):
+                            eps, step_dev=None, rider: TailRider | None = None):
     """Phase 2 and the lazy row update in ONE launch (pxr_sasrec_occ_segsum_apply): the sums sasrec_occ_segsum(scale=1) would leave
     in sp.rows are applied where they are formed -- adamw_rows(t_prev, t_prev + 1, rows=sp.idx, grows=sp.rows) on rows that are
     current through t_prev, bit for bit -- and sp.rows is NOT written.  A row that is not current is left untouched and raises
-    STATUS_ROWS_STALE.  Segments of any length on one workgroup each (no split route)."""
+    STATUS_ROWS_STALE.  Segments of any length on one workgroup each (no split route).  rider: reductions the launch carries on
+    extra workgroups."""
     Lb = _l.load()
     B, L, D = out.shape
+    rarg, rkeep = rider.c_arg() if rider is not None else (None, None)
     device_status(table.device)       # a stale row flags the status word (raise_on_bad_indices)
     with _gemm_timer(0.0, "segsum_apply_kernel (segment sums + apply: batch rows)"):
         _l.check(Lb.pxr_sasrec_occ_segsum_apply(_l.ptr(ws), ws.numel(), B, L, _l.ptr(dx0), _l.ptr(out), _l.ptr(coef), D, n_table,
                                                 _l.ptr(sp.n), _l.ptr(sp.idx), _l.ptr(table), _l.ptr(m), _l.ptr(v), _l.ptr(last),
                                                 table.shape[0], _l.ptr(hyper), t_prev, _l.ptr(step_dev), beta1, beta2, eps,
-                                                _l.stream_ptr()),
+                                                _l.stream_ptr(), rarg),
                  "pxr_sasrec_occ_segsum_apply")
+    del rkeep
 
 
 # ------------------------------------------------------------------------------------------------ PixelNet pieces

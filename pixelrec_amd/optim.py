@@ -367,16 +367,17 @@ class PxrAdamW:
             return None
         return self.apply_rows_in_segsum
 
-    def apply_rows_in_segsum(self, ws, dx0, out, coef, n_table, sp):
+    def apply_rows_in_segsum(self, ws, dx0, out, coef, n_table, sp, rider=None):
         """ops.sasrec_occ_segsum + the row launch of step() in one launch: the rows of `sp` take this step's update where their
-        gradient is summed; sp.rows is not written and sp.applied tells step() that its row launch is done."""
+        gradient is summed; sp.rows is not written and sp.applied tells step() that its row launch is done.  rider: an
+        ops.TailRider the launch carries."""
         _, table = self._ensure_state()
         cfg = self._cfg()
         if self._seed_step(cfg):
             self._early_seed = True
         _, b1, b2, eps, _ = cfg
         ops.sasrec_occ_segsum_apply(ws, dx0, out, coef, n_table, sp, table, self._tm, self._tv, self._last, self._hyper,
-                                    self.step_count, b1, b2, eps, step_dev=self._step_dev)
+                                    self.step_count, b1, b2, eps, step_dev=self._step_dev, rider=rider)
         sp.applied = True
         self._applied_cfg = cfg
 
