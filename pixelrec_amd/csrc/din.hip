@@ -21,6 +21,7 @@
 // per-thread top-K list follow; the lists are merged by wave shuffles and the shared merge kernel (topk_select.cuh: pxr_topk_merge).
 // No [B, L, N, *] value reaches memory.
 #include "gemm_f32.cuh"
+#include "topk_mlp_tail.cuh"
 #include "topk_select.cuh"
 
 namespace pxr {
@@ -28,6 +29,9 @@ namespace pxr {
 typedef float df4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float din_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+struct DinSigmoid {
+  __device__ __forceinline__ float operator()(float v) const { return din_sigmoid(v); }
+};
 
 // fixed-order block sum of one value per thread (256 threads); the total is returned to every thread
 __device__ __forceinline__ float din_block_sum(float v, float* red) {
@@ -227,12 +231,9 @@ __global__ void __launch_bounds__(256) din_fold_w1_kernel(const float* __restric
   C[e] = w[3 * D + d];
 }
 
-constexpr int DN_BM = 128, DN_BN = 128;
-constexpr int DN_LD = 132;                     // LDS row stride of the activation tile and of W2 (16-byte rows for ds_read_b128)
+constexpr int DN_BM = MT_BM, DN_BN = 128;
 using DnCfg = GemmCfg<DN_BM, DN_BN, true, true>;
-constexpr int DN_TILE = DN_BM * DN_LD;
-static_assert(DN_TILE >= 2 * DnCfg::STAGE, "the activation tile overlays the staging buffers");
-constexpr int DN_SMEM_FLOATS = 2 * DN_TILE + 3 * 128 + 4;
+constexpr int DN_SMEM_FLOATS = 2 * MT_TILE + 3 * 128 + 4;
 constexpr int DN_MAX_D = 128, DN_MAX_H = 128, DN_MAX_L = 64;
 
 struct DinTopkArgs {
@@ -259,17 +260,8 @@ __global__ void __launch_bounds__(256) din_prep_kernel(DinTopkArgs a) {
   const int bl = blockIdx.x, b = bl / a.L, l = bl - b * a.L, tid = threadIdx.x;
   const int64_t id = a.window[bl];
   bool bad = id < 0 || id >= a.N;
-  if (l == 0 && a.hist_ptr) {
-    const int hb = a.hist_ptr[b], he = a.hist_ptr[b + 1];
-    for (int p = hb + tid; p < he; p += 256) {
-      const int64_t it = a.hist_items[p];
-      bad |= it < 0 || it >= a.N;
-    }
-  }
-  if (bad) {
-    *a.bad = 1;
-    if (a.status) atomicOr(a.status, PXR_STATUS_BAD_INDEX);
-  }
+  if (l == 0) bad |= hist_ids_bad<256>(a.hist_ptr, a.hist_items, b, a.N, tid);
+  if (bad) raise_bad_input(a.bad, a.status);
   if (id <= 0 || id >= a.N) return;            // padding (or flagged): this row takes no part
   const float* k = a.table + id * a.D;
   float* cs = a.cs + (int64_t)bl * a.h1 * a.D;
@@ -288,34 +280,23 @@ template <int KT, bool TWO>
 __global__ void __launch_bounds__(GEMM_THREADS) din_topk_kernel(DinTopkArgs a) {
   __shared__ __attribute__((aligned(16))) float smem[DN_SMEM_FLOATS];
   if (*a.bad) return;
-  float* tile = smem;                          // staging buffers of the main loop, then the [128 items][DN_LD] activations
-  float* w2s = smem + DN_TILE;                 // W2 [128][DN_LD], zero outside [h2][h1]
-  float* wds = w2s + DN_TILE;                  // dense.weight, zero beyond h_last
+  float* tile = smem;                          // staging buffers of the main loop, then the [128 items][MT_LD] activations
+  float* w2s = smem + MT_TILE;                 // W2 [128][MT_LD], zero outside [h2][h1]
+  float* wds = w2s + MT_TILE;                  // dense.weight, zero beyond h_last
   float* b2s = wds + 128;
   float* ks = b2s + 128;                       // the window row k_l
   unsigned* bitmap = reinterpret_cast<unsigned*>(ks + 128);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1, hh = lane >> 5, r = lane & 31;
   const int b = blockIdx.x % a.B, sp = blockIdx.x / a.B;      // user fastest: neighbours share the item tiles
-  const int per = (a.tiles_n + a.n_split - 1) / a.n_split;
-  const int tn0 = sp * per, tn1 = min(a.tiles_n, tn0 + per);
+  const TileRange tr = split_tile_range(a.tiles_n, a.n_split, sp);
   const int hl = TWO ? a.h2 : a.h1;
   const int D = a.D, h1 = a.h1;
 
-  if constexpr (TWO) {
-    for (int e = tid; e < DN_TILE; e += GEMM_THREADS) {
-      const int j2 = e / DN_LD, k = e - j2 * DN_LD;
-      w2s[e] = (j2 < a.h2 && k < h1) ? a.w2[j2 * h1 + k] : 0.f;
-    }
-  }
-  if (tid < 128) {
-    wds[tid] = tid < hl ? a.wd[tid] : 0.f;
-    b2s[tid] = (TWO && tid < a.h2) ? a.b2[tid] : 0.f;
-  }
+  mlp_tail_stage<TWO>(w2s, wds, b2s, a.w2, a.b2, a.wd, h1, a.h2, tid);
   const float bd = a.bd[0];
-  const int jstart = tid % hl;                 // every item thread starts its dense sum at another column: no LDS bank conflicts
-  const int nb2 = TWO ? (a.h2 + 31) >> 5 : 0;
-  const int ksteps = (h1 + 7) >> 3;
+  const int jstart = tid % hl;                 // mlp_tail_dot: every item thread starts at another column
+  const int nb2 = (a.h2 + 31) >> 5, ksteps = (h1 + 7) >> 3;
   int hb = 0, he = 0;
   if (a.hist_ptr) { hb = a.hist_ptr[b]; he = a.hist_ptr[b + 1]; }
   const int64_t* win = a.window + (int64_t)b * a.L;
@@ -323,7 +304,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) din_topk_kernel(DinTopkArgs a) {
   TopList<KT> top;
   top.init();
 
-  for (int tn = tn0; tn < tn1; ++tn) {
+  for (int tn = tr.tn0; tn < tr.tn1; ++tn) {
     const int n0 = tn * DN_BM;
     if (tid < 4) bitmap[tid] = 0u;
     // the per-item term A q + b1 of this tile, in the accumulator layout: read once per tile, used by every window row
@@ -341,13 +322,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) din_topk_kernel(DinTopkArgs a) {
     }
     __syncthreads();
     // history mask over the user's FULL history: items of this tile as bits
-    for (int p = hb + tid; p < he; p += GEMM_THREADS) {
-      const int64_t it = a.hist_items[p];
-      if (it >= n0 && it < n0 + DN_BM) {
-        const int il = (int)(it - n0);
-        atomicOr(&bitmap[il >> 5], 1u << (il & 31));
-      }
-    }
+    hist_bitmap_rows<DN_BM, GEMM_THREADS>(bitmap, a.hist_items, hb, he, n0, tid, [](int) { return 0; });
     float score = 0.f;
     for (int l = 0; l < a.L; ++l) {
       const int64_t w = win[l];
@@ -367,56 +342,19 @@ __global__ void __launch_bounds__(GEMM_THREADS) din_topk_kernel(DinTopkArgs a) {
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
             const int rl = wm * DnCfg::WM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-            tile[rl * DN_LD + col] = din_sigmoid(accs.v[i][j][e] + aqr[i][j][e] + bkv);
+            tile[rl * MT_LD + col] = din_sigmoid(accs.v[i][j][e] + aqr[i][j][e] + bkv);
           }
       }
       __syncthreads();
       if constexpr (TWO) {
-        // second layer on the MFMA: the wave owns 32 items x every column block of h2; lanes 0-31 feed k 0..3, lanes 32-63 k 4..7
         f32x16 acc2[4];
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) acc2[jb][e] = 0.f;
-        const float* arow = tile + (wave * 32 + r) * DN_LD + hh * 4;
-        const float* brow = w2s + r * DN_LD + hh * 4;
-        for (int k8 = 0; k8 < ksteps; ++k8) {
-          const float4 av = *reinterpret_cast<const float4*>(arow + k8 * 8);
-#pragma unroll
-          for (int jb = 0; jb < 4; ++jb) {
-            if (jb < nb2) {
-              const float4 bv = *reinterpret_cast<const float4*>(brow + jb * 32 * DN_LD + k8 * 8);
-              acc2[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc2[jb], 0, 0, 0);
-              acc2[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc2[jb], 0, 0, 0);
-              acc2[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc2[jb], 0, 0, 0);
-              acc2[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc2[jb], 0, 0, 0);
-            }
-          }
-        }
+        mlp_tail_layer2(acc2, tile, w2s, ksteps, nb2, wave, r, hh);
         __syncthreads();                       // every wave has read the first layer's activations
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb) {
-          if (jb < nb2) {
-            const int col = jb * 32 + r;
-            const float bb = b2s[col];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-              const int rl = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-              tile[rl * DN_LD + col] = din_sigmoid(acc2[jb][e] + bb);
-            }
-          }
-        }
+        mlp_tail_layer2_store(tile, acc2, b2s, nb2, wave, r, hh, DinSigmoid{});
         __syncthreads();
       }
       if (tid < DN_BM) {
-        const float* row = tile + tid * DN_LD;
-        float s = 0.f;
-        int j = jstart;
-        for (int jj = 0; jj < hl; ++jj) {
-          s += wds[j] * row[j];
-          j = j + 1 == hl ? 0 : j + 1;
-        }
-        s = (s + bd) / a.sqrt_d;
+        const float s = (mlp_tail_dot(wds, tile + tid * MT_LD, hl, jstart) + bd) / a.sqrt_d;
         const int item = n0 + tid;
         if (item < a.N) {
           const float4* q = reinterpret_cast<const float4*>(a.table + (int64_t)item * D);
@@ -432,9 +370,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) din_topk_kernel(DinTopkArgs a) {
     }
     __syncthreads();                           // (an all-padding window: the bitmap still has to be complete)
     if (tid < DN_BM) {
-      const int col = n0 + tid;
-      const bool dead = col >= a.N || col == 0 || ((bitmap[tid >> 5] >> (tid & 31)) & 1u);
-      if (!dead) top.insert(score, col);
+      if (item_alive(bitmap, n0 + tid, tid, a.N)) top.insert(score, n0 + tid);
     }
     __syncthreads();
   }
@@ -444,12 +380,9 @@ __global__ void __launch_bounds__(GEMM_THREADS) din_topk_kernel(DinTopkArgs a) {
   wave_collapse_lists(top, lane, a.part_val + o, a.part_idx + o);
 }
 
-static int dn_pick_split(int B, int N) {
-  const int tiles_n = (N + DN_BM - 1) / DN_BM;
-  int s = (512 + B - 1) / B;                   // one resident workgroup per CU (its LDS): about two rounds of the chip
-  if (s > tiles_n) s = tiles_n;
-  return s < 1 ? 1 : s;
-}
+static int dn_tiles(int N) { return (N + DN_BM - 1) / DN_BM; }
+static int64_t dn_bk_bytes(int B, int L) { return a256((int64_t)B * L * 128 * 4); }
+static int64_t dn_own_bytes(int B, int L, int h1, int D) { return dn_bk_bytes(B, L) + a256((int64_t)B * L * h1 * D * 4); }
 static bool dn_shape_ok(int B, int L, int N, int D, int h1, int h2, int K) {
   return B > 0 && B <= (1 << 20) && L >= 1 && L <= DN_MAX_L && N > 0 && D >= 4 && D % 4 == 0 && D <= DN_MAX_D && h1 >= 1 &&
          h1 <= DN_MAX_H && h2 >= 0 && h2 <= DN_MAX_H && K >= 1 && K <= 32 && (int64_t)N * D * 4 < 0x7FFFFFF0ll;
@@ -537,8 +470,8 @@ extern "C" int pxr_din_fold_w1_f32(const float* w1, int h1, int D, float* A, flo
 // input flag | Bm k | C * k | partial values | partial ids
 extern "C" int64_t pxr_din_topk_ws_bytes(int B, int L, int N, int D, int h1, int h2, int K) {
   if (!dn_shape_ok(B, L, N, D, h1, h2, K)) return -1;
-  const int64_t cand = (int64_t)dn_pick_split(B, N) * 2 * pick_kt(K);
-  return 256 + a256((int64_t)B * L * 128 * 4) + a256((int64_t)B * L * h1 * D * 4) + 2 * a256((int64_t)B * cand * 4);
+  const int64_t cand = (int64_t)topk_pick_split(B, dn_tiles(N)) * 2 * pick_kt(K);
+  return topk_ws_bytes(dn_own_bytes(B, L, h1, D), B, cand);
 }
 
 extern "C" int pxr_din_topk_f32(const float* table, int N, int D, const int64_t* window, int B, int L, const float* aq,
@@ -556,33 +489,24 @@ extern "C" int pxr_din_topk_f32(const float* table, int N, int D, const int64_t*
   DinTopkArgs a{};
   a.table = table; a.window = window; a.hist_ptr = hist_ptr; a.hist_items = hist_items; a.aq = aq; a.bm = bm; a.cm = cm;
   a.w2 = w2; a.b2 = b2; a.wd = wd; a.bd = bd; a.B = B; a.L = L; a.N = N; a.D = D; a.h1 = h1; a.h2 = h2;
-  a.tiles_n = (N + DN_BM - 1) / DN_BM;
-  a.n_split = dn_pick_split(B, N);
+  a.tiles_n = dn_tiles(N);
+  a.n_split = topk_pick_split(B, a.tiles_n);
   a.status = pxr_status_word();
   a.sqrt_d = sqrtf((float)D);
   const int64_t cand = (int64_t)a.n_split * 2 * kt;
-  char* w = (char*)ws;
-  a.bad = (int*)w;                     w += 256;
-  a.bk = (float*)w;                    w += a256((int64_t)B * L * 128 * 4);
-  a.cs = (float*)w;                    w += a256((int64_t)B * L * h1 * D * 4);
-  a.part_val = (float*)w;              w += a256((int64_t)B * cand * 4);
-  a.part_idx = (int*)w;
+  const TopkWs w = topk_ws_carve(ws, dn_own_bytes(B, L, h1, D), B, cand);
+  a.bad = w.bad; a.part_val = w.part_val; a.part_idx = w.part_idx;
+  a.bk = (float*)w.own;
+  a.cs = (float*)(w.own + dn_bk_bytes(B, L));
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(a.bad, 0, 256, st) != hipSuccess) return pxr_check_launch("pxr_din_topk_f32(memset)");
+  if (int rc = topk_ws_clear_flag(w, "pxr_din_topk_f32(memset)", st)) return rc;
   hipLaunchKernelGGL(din_prep_kernel, dim3((unsigned)(B * L)), dim3(256), 0, st, a);
-  int rc = pxr_check_launch("pxr_din_topk_f32(prep)");
-  if (rc) return rc;
+  if (int rc = pxr_check_launch("pxr_din_topk_f32(prep)")) return rc;
   const dim3 grid((unsigned)(B * a.n_split));
-#define PXR_DN(KT_)                                                                                          \
-  if (h2 > 0) hipLaunchKernelGGL((din_topk_kernel<KT_, true>), grid, dim3(GEMM_THREADS), 0, st, a);          \
-  else hipLaunchKernelGGL((din_topk_kernel<KT_, false>), grid, dim3(GEMM_THREADS), 0, st, a);
-  switch (kt) {
-    case 10: PXR_DN(10); break;
-    case 16: PXR_DN(16); break;
-    default: PXR_DN(32); break;
-  }
-#undef PXR_DN
-  rc = pxr_check_launch("pxr_din_topk_f32");
-  if (rc) return rc;
-  return pxr_topk_merge(a.bad, a.part_val, a.part_idx, B, (int)cand, K, topk_idx, topk_val, "pxr_din_topk_f32(merge)", stream);
+  topk_for_kt(kt, [&](auto k) {
+    constexpr int KT = decltype(k)::value;
+    if (h2 > 0) hipLaunchKernelGGL((din_topk_kernel<KT, true>), grid, dim3(GEMM_THREADS), 0, st, a);
+    else hipLaunchKernelGGL((din_topk_kernel<KT, false>), grid, dim3(GEMM_THREADS), 0, st, a);
+  });
+  return topk_ws_merge(w, B, cand, K, topk_idx, topk_val, "pxr_din_topk_f32", "pxr_din_topk_f32(merge)", stream);
 }

@@ -401,14 +401,7 @@ static int topk_variant() {
   return (v == 1 || v == 3) ? v : 2;
 }
 static int lists_per_split() { return topk_variant() == 2 ? 4 : (topk_variant() == 3 ? 8 : 2); }
-static int pick_split(int B, int N) {
-  const int row_blocks = (B + ST_BM - 1) / ST_BM;
-  const int tiles_n = (N + ST_BN - 1) / ST_BN;
-  int s = (512 + row_blocks - 1) / row_blocks;  // ~2 resident workgroups per CU
-  if (s > tiles_n) s = tiles_n;
-  if (s < 1) s = 1;
-  return s;
-}
+static int pick_split(int B, int N) { return topk_pick_split((B + ST_BM - 1) / ST_BM, (N + ST_BN - 1) / ST_BN); }
 
 }  // namespace pxr
 
@@ -1004,11 +997,7 @@ static int score_topk_thresh(ScoreTopkArgs a, int K, int kt, int64_t* topk_idx, 
   a.n_split = sample_splits(a.N, kt);
   a.tile_stride = (a.tiles_n + a.n_split - 1) / a.n_split;     // == the kernel's tiles-per-split: exactly one tile each
   const dim3 grid_s(a.row_blocks * a.n_split);
-  switch (kt) {
-    case 10: hipLaunchKernelGGL(score_topk_kernel<10>, grid_s, dim3(GEMM_THREADS), 0, st, a); break;
-    case 16: hipLaunchKernelGGL(score_topk_kernel<16>, grid_s, dim3(GEMM_THREADS), 0, st, a); break;
-    default: hipLaunchKernelGGL(score_topk_kernel<32>, grid_s, dim3(GEMM_THREADS), 0, st, a); break;
-  }
+  topk_for_kt(kt, [&](auto k) { hipLaunchKernelGGL(score_topk_kernel<decltype(k)::value>, grid_s, dim3(GEMM_THREADS), 0, st, a); });
   const int64_t cand = (int64_t)a.n_split * 2 * kt;
   if (int rc = pxr_topk_merge(nullptr, a.part_val, a.part_idx, a.B, (int)cand, K, s_idx, s_val, "pxr_score_topk_f32(sample merge)", st)) return rc;
   if (fast)      // tau lowered by the rigorous margin of the reduced-product pass (see score_thresh_fast_kernel)
@@ -1153,25 +1142,12 @@ extern "C" int pxr_score_topk_f32(const float* users, int64_t ld_users, int B, c
   a.part_idx = (int*)((char*)ws + (((int64_t)B * cand * 4 + 255) & ~(int64_t)255));
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(a.row_blocks * a.n_split);
-  if (topk_variant() == 2) {
-    switch (kt) {
-      case 10: hipLaunchKernelGGL((score_topk2_kernel<10, 2>), grid, dim3(512), 0, st, a); break;
-      case 16: hipLaunchKernelGGL((score_topk2_kernel<16, 2>), grid, dim3(512), 0, st, a); break;
-      default: hipLaunchKernelGGL((score_topk2_kernel<32, 2>), grid, dim3(512), 0, st, a); break;
-    }
-  } else if (topk_variant() == 3) {
-    switch (kt) {
-      case 10: hipLaunchKernelGGL((score_topk2_kernel<10, 1>), grid, dim3(1024), 0, st, a); break;
-      case 16: hipLaunchKernelGGL((score_topk2_kernel<16, 1>), grid, dim3(1024), 0, st, a); break;
-      default: hipLaunchKernelGGL((score_topk2_kernel<32, 1>), grid, dim3(1024), 0, st, a); break;
-    }
-  } else {
-    switch (kt) {
-      case 10: hipLaunchKernelGGL(score_topk_kernel<10>, grid, dim3(GEMM_THREADS), 0, st, a); break;
-      case 16: hipLaunchKernelGGL(score_topk_kernel<16>, grid, dim3(GEMM_THREADS), 0, st, a); break;
-      default: hipLaunchKernelGGL(score_topk_kernel<32>, grid, dim3(GEMM_THREADS), 0, st, a); break;
-    }
-  }
+  topk_for_kt(kt, [&](auto k) {
+    constexpr int KT = decltype(k)::value;
+    if (topk_variant() == 2) hipLaunchKernelGGL((score_topk2_kernel<KT, 2>), grid, dim3(512), 0, st, a);
+    else if (topk_variant() == 3) hipLaunchKernelGGL((score_topk2_kernel<KT, 1>), grid, dim3(1024), 0, st, a);
+    else hipLaunchKernelGGL(score_topk_kernel<KT>, grid, dim3(GEMM_THREADS), 0, st, a);
+  });
   int rc = pxr_check_launch("pxr_score_topk_f32");
   if (rc) return rc;
   return pxr_topk_merge(nullptr, a.part_val, a.part_idx, B, (int)cand, K, topk_idx, topk_val, "pxr_score_topk_f32(merge)", stream);

@@ -75,19 +75,10 @@ __global__ void __launch_bounds__(64) visrank_prep_kernel(VisrankArgs a) {
   const int h = __popcll(m);
   const unsigned long long want = h == 0 ? 0ull : (h == 64 ? ~0ull : (~0ull << (64 - h)));
   bad |= (m != want) || h == 0;
-  if (a.hist_ptr) {
-    const int hb = a.hist_ptr[u], he = a.hist_ptr[u + 1];
-    for (int p = hb + r; p < he; p += 64) {
-      const int64_t it = a.hist_items[p];
-      bad |= it < 0 || it >= a.N;
-    }
-  }
+  bad |= hist_ids_bad<64>(a.hist_ptr, a.hist_items, u, a.N, r);
   a.rows[u * VR_ROWS + r] = (valid && !bad) ? (int)id : -1;
   if (r == 0) a.hlen[u] = h;
-  if (__any(bad) && r == 0) {
-    *a.bad = 1;
-    if (a.status) atomicOr(a.status, PXR_STATUS_BAD_INDEX);
-  }
+  if (__any(bad) && r == 0) raise_bad_input(a.bad, a.status);
 }
 
 // KT = length of the top-K lists; TK = length of the k-largest list of the history reduction (0: the mean over all h rows)
@@ -101,8 +92,7 @@ __global__ void __launch_bounds__(GEMM_THREADS, (KT <= 16 ? 2 : 1)) visrank_topk
   const int t = xcd_remap(blockIdx.x, a.row_blocks * a.n_split);
   const int rb = t % a.row_blocks, sp = t / a.row_blocks;   // row-block fastest: neighbours share the item tiles
   const int m0 = rb * VR_BM, u0 = rb * VR_UPT;
-  const int per = (a.tiles_n + a.n_split - 1) / a.n_split;
-  const int tn0 = sp * per, tn1 = min(a.tiles_n, tn0 + per);
+  const TileRange tr = split_tile_range(a.tiles_n, a.n_split, sp);
 
   const int my_u = tid >> 7, my_c = tid & 127;              // (user in tile, column): the user is wave-uniform
   const int user = u0 + my_u;
@@ -120,7 +110,7 @@ __global__ void __launch_bounds__(GEMM_THREADS, (KT <= 16 ? 2 : 1)) visrank_topk
     he = a.hist_ptr[min(a.B, u0 + VR_UPT)];
   }
 
-  for (int tn = tn0; tn < tn1; ++tn) {
+  for (int tn = tr.tn0; tn < tr.tn1; ++tn) {
     const int n0 = tn * VR_BN;
     if (tid < VR_BITMAP_WORDS) bitmap[tid] = 0u;
     typename VrCfg::Acc accs;
@@ -140,17 +130,10 @@ __global__ void __launch_bounds__(GEMM_THREADS, (KT <= 16 ? 2 : 1)) visrank_topk
         }
     }
     // history mask (trainer.py:335-336) over the users' FULL histories: pairs of this tile as bits
-    for (int p = hb + tid; p < he; p += GEMM_THREADS) {
-      const int64_t it = a.hist_items[p];
-      if (it >= n0 && it < n0 + VR_BN) {
-        const int il = (int)(it - n0);
-        atomicOr(&bitmap[(p >= hm ? 1 : 0) * (VR_BN / 32) + (il >> 5)], 1u << (il & 31));
-      }
-    }
+    hist_bitmap_rows<VR_BN, GEMM_THREADS>(bitmap, a.hist_items, hb, he, n0, tid, [hm](int p) { return p >= hm ? 1 : 0; });
     __syncthreads();
     const int col = n0 + my_c;
-    const bool dead = user >= a.B || col >= a.N || col == 0 || ((bitmap[my_u * (VR_BN / 32) + (my_c >> 5)] >> (my_c & 31)) & 1u);
-    if (!dead) {
+    if (user < a.B && item_alive(bitmap + my_u * (VR_BN / 32), col, my_c, a.N)) {
       const float* colp = smem + (my_u * VR_ROWS) * VR_LD + my_c;
       float s = 0.f;
       if constexpr (TK == 0) {
@@ -182,13 +165,10 @@ __global__ void __launch_bounds__(GEMM_THREADS, (KT <= 16 ? 2 : 1)) visrank_topk
   wave_collapse_lists(top, lane, a.part_val + o, a.part_idx + o);
 }
 
-static int vr_pick_split(int B, int N) {
-  const int row_blocks = (B + VR_UPT - 1) / VR_UPT;
-  const int tiles_n = (N + VR_BN - 1) / VR_BN;
-  int s = (512 + row_blocks - 1) / row_blocks;   // ~2 resident workgroups per CU
-  if (s > tiles_n) s = tiles_n;
-  return s < 1 ? 1 : s;
-}
+static int vr_row_blocks(int B) { return (B + VR_UPT - 1) / VR_UPT; }
+static int vr_tiles(int N) { return (N + VR_BN - 1) / VR_BN; }
+static int64_t vr_hlen_bytes(int B) { return a256((int64_t)B * 4); }
+static int64_t vr_own_bytes(int B) { return vr_hlen_bytes(B) + a256((int64_t)vr_row_blocks(B) * VR_BM * 4); }
 static bool vr_shape_ok(int B, int H, int N, int K) {
   return B > 0 && B <= (1 << 22) && H >= 1 && H <= VR_ROWS && N > 0 && K >= 1 && K <= 32;
 }
@@ -209,9 +189,8 @@ extern "C" int pxr_visrank_unit_rows_f32(const float* feat, int64_t N, int F, fl
 // input flag | window lengths | row list | partial values | partial ids
 extern "C" int64_t pxr_visrank_topk_ws_bytes(int B, int H, int N, int K) {
   if (!vr_shape_ok(B, H, N, K)) return -1;
-  const int row_blocks = (B + VR_UPT - 1) / VR_UPT;
-  const int64_t cand = (int64_t)vr_pick_split(B, N) * 2 * pick_kt(K);
-  return 256 + a256((int64_t)B * 4) + a256((int64_t)row_blocks * VR_BM * 4) + 2 * a256((int64_t)B * cand * 4);
+  const int64_t cand = (int64_t)topk_pick_split(vr_row_blocks(B), vr_tiles(N)) * 2 * pick_kt(K);
+  return topk_ws_bytes(vr_own_bytes(B), B, cand);
 }
 
 extern "C" int pxr_visrank_topk_f32(const float* unit, int N, int F, const int64_t* window, int B, int H, int top_k,
@@ -228,38 +207,29 @@ extern "C" int pxr_visrank_topk_f32(const float* unit, int N, int F, const int64
   VisrankArgs a{};
   a.unit = unit; a.window = window; a.hist_ptr = hist_ptr; a.hist_items = hist_items;
   a.B = B; a.H = H; a.N = N; a.F = F; a.top_k = top_k;
-  a.row_blocks = (B + VR_UPT - 1) / VR_UPT;
-  a.tiles_n = (N + VR_BN - 1) / VR_BN;
-  a.n_split = vr_pick_split(B, N);
+  a.row_blocks = vr_row_blocks(B);
+  a.tiles_n = vr_tiles(N);
+  a.n_split = topk_pick_split(a.row_blocks, a.tiles_n);
   a.status = pxr_status_word();
   const int64_t cand = (int64_t)a.n_split * 2 * kt;
-  char* w = (char*)ws;
-  a.bad = (int*)w;                     w += 256;
-  a.hlen = (int*)w;                    w += a256((int64_t)B * 4);
-  a.rows = (int*)w;                    w += a256((int64_t)a.row_blocks * VR_BM * 4);
-  a.part_val = (float*)w;              w += a256((int64_t)B * cand * 4);
-  a.part_idx = (int*)w;
+  const TopkWs w = topk_ws_carve(ws, vr_own_bytes(B), B, cand);
+  a.bad = w.bad; a.part_val = w.part_val; a.part_idx = w.part_idx;
+  a.hlen = (int*)w.own;
+  a.rows = (int*)(w.own + vr_hlen_bytes(B));
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(a.bad, 0, 256, st) != hipSuccess) return pxr_check_launch("pxr_visrank_topk_f32(memset)");
+  if (int rc = topk_ws_clear_flag(w, "pxr_visrank_topk_f32(memset)", st)) return rc;
   hipLaunchKernelGGL(visrank_prep_kernel, dim3(a.row_blocks * VR_UPT), dim3(64), 0, st, a);
-  int rc = pxr_check_launch("pxr_visrank_topk_f32(prep)");
-  if (rc) return rc;
+  if (int rc = pxr_check_launch("pxr_visrank_topk_f32(prep)")) return rc;
   const dim3 grid(a.row_blocks * a.n_split);
   const int tk = top_k == 0 ? 0 : (top_k == 1 ? 1 : (top_k <= 4 ? 4 : 16));
-#define PXR_VR(KT_)                                                                                              \
-  switch (tk) {                                                                                                  \
-    case 0: hipLaunchKernelGGL((visrank_topk_kernel<KT_, 0>), grid, dim3(GEMM_THREADS), 0, st, a); break;        \
-    case 1: hipLaunchKernelGGL((visrank_topk_kernel<KT_, 1>), grid, dim3(GEMM_THREADS), 0, st, a); break;        \
-    case 4: hipLaunchKernelGGL((visrank_topk_kernel<KT_, 4>), grid, dim3(GEMM_THREADS), 0, st, a); break;        \
-    default: hipLaunchKernelGGL((visrank_topk_kernel<KT_, 16>), grid, dim3(GEMM_THREADS), 0, st, a); break;      \
-  }
-  switch (kt) {
-    case 10: PXR_VR(10); break;
-    case 16: PXR_VR(16); break;
-    default: PXR_VR(32); break;
-  }
-#undef PXR_VR
-  rc = pxr_check_launch("pxr_visrank_topk_f32");
-  if (rc) return rc;
-  return pxr_topk_merge(a.bad, a.part_val, a.part_idx, B, (int)cand, K, topk_idx, topk_val, "pxr_visrank_topk_f32(merge)", stream);
+  topk_for_kt(kt, [&](auto k) {
+    constexpr int KT = decltype(k)::value;
+    switch (tk) {
+      case 0: hipLaunchKernelGGL((visrank_topk_kernel<KT, 0>), grid, dim3(GEMM_THREADS), 0, st, a); break;
+      case 1: hipLaunchKernelGGL((visrank_topk_kernel<KT, 1>), grid, dim3(GEMM_THREADS), 0, st, a); break;
+      case 4: hipLaunchKernelGGL((visrank_topk_kernel<KT, 4>), grid, dim3(GEMM_THREADS), 0, st, a); break;
+      default: hipLaunchKernelGGL((visrank_topk_kernel<KT, 16>), grid, dim3(GEMM_THREADS), 0, st, a); break;
+    }
+  });
+  return topk_ws_merge(w, B, cand, K, topk_idx, topk_val, "pxr_visrank_topk_f32", "pxr_visrank_topk_f32(merge)", stream);
 }

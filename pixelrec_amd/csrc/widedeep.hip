@@ -21,6 +21,7 @@
 // full history as a bitmap) and a per-thread top-K list; the lists are merged by wave shuffles and pxr_topk_merge.  No [B, N, *]
 // value reaches memory.
 #include "gemm_f32.cuh"
+#include "topk_mlp_tail.cuh"
 #include "topk_select.cuh"
 
 namespace pxr {
@@ -181,10 +182,11 @@ __global__ void __launch_bounds__(256) wd_wide_grad_kernel(const int64_t* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------- evaluation
-constexpr int WD_BM = 128;
-constexpr int WD_LD = 132;                     // LDS row stride of the activation tile and of W2 (16-byte rows for ds_read_b128)
-constexpr int WD_TILE = WD_BM * WD_LD;
-constexpr int WD_SMEM_FLOATS = 2 * WD_TILE + 3 * 128 + 4;
+constexpr int WD_BM = MT_BM;
+constexpr int WD_SMEM_FLOATS = 2 * MT_TILE + 3 * 128 + 4;
+struct WdRelu {
+  __device__ __forceinline__ float operator()(float v) const { return fmaxf(v, 0.f); }
+};
 constexpr int WD_MAX_H = 128, WD_MAX_L = 64;
 
 struct WdTopkArgs {
@@ -212,17 +214,8 @@ __global__ void __launch_bounds__(64) wd_prep_kernel(WdTopkArgs a) {
     const int64_t id = a.window[(int64_t)b * a.L + l];
     bad |= id < 0 || id >= a.N;
   }
-  if (a.hist_ptr) {
-    const int hb = a.hist_ptr[b], he = a.hist_ptr[b + 1];
-    for (int p = hb + lane; p < he; p += 64) {
-      const int64_t it = a.hist_items[p];
-      bad |= it < 0 || it >= a.N;
-    }
-  }
-  if (bad) {
-    *a.bad = 1;
-    if (a.status) atomicOr(a.status, PXR_STATUS_BAD_INDEX);
-  }
+  bad |= hist_ids_bad<64>(a.hist_ptr, a.hist_items, b, a.N, lane);
+  if (bad) raise_bad_input(a.bad, a.status);
   if (lane == 0) {
     float s = 0.f;
     for (int l = 0; l < a.L; ++l) {
@@ -238,35 +231,24 @@ template <int KT, bool TWO>
 __global__ void __launch_bounds__(GEMM_THREADS) wd_topk_kernel(WdTopkArgs a) {
   __shared__ __attribute__((aligned(16))) float smem[WD_SMEM_FLOATS];
   if (*a.bad) return;
-  float* tile = smem;                          // [128 items][WD_LD] activations
-  float* w2s = smem + WD_TILE;                 // W2 [128][WD_LD], zero outside [h2][h1]
-  float* wps = w2s + WD_TILE;                  // w_p, zero beyond h_last
+  float* tile = smem;                          // [128 items][MT_LD] activations
+  float* w2s = smem + MT_TILE;                 // W2 [128][MT_LD], zero outside [h2][h1]
+  float* wps = w2s + MT_TILE;                  // w_p, zero beyond h_last
   float* b2s = wps + 128;
   float* hbs = b2s + 128;                      // h_b, zero beyond h1
   unsigned* bitmap = reinterpret_cast<unsigned*>(hbs + 128);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hh = lane >> 5, r = lane & 31;
   const int b = blockIdx.x % a.B, sp = blockIdx.x / a.B;      // user fastest: neighbours share the T tiles
-  const int per = (a.tiles_n + a.n_split - 1) / a.n_split;
-  const int tn0 = sp * per, tn1 = min(a.tiles_n, tn0 + per);
+  const TileRange tr = split_tile_range(a.tiles_n, a.n_split, sp);
   const int hl = TWO ? a.h2 : a.h1;
   const int h1 = a.h1;
 
-  if constexpr (TWO) {
-    for (int e = tid; e < WD_TILE; e += GEMM_THREADS) {
-      const int j2 = e / WD_LD, k = e - j2 * WD_LD;
-      w2s[e] = (j2 < a.h2 && k < h1) ? a.w2[j2 * h1 + k] : 0.f;
-    }
-  }
-  if (tid < 128) {
-    wps[tid] = tid < hl ? a.wp[tid] : 0.f;
-    b2s[tid] = (TWO && tid < a.h2) ? a.b2[tid] : 0.f;
-    hbs[tid] = tid < h1 ? a.hb[(int64_t)b * h1 + tid] : 0.f;
-  }
+  mlp_tail_stage<TWO>(w2s, wps, b2s, a.w2, a.b2, a.wp, h1, a.h2, tid);
+  if (tid < 128) hbs[tid] = tid < h1 ? a.hb[(int64_t)b * h1 + tid] : 0.f;
   const float sb = a.sb[b];
-  const int jstart = tid % hl;                 // every item thread starts its w_p sum at another column: no LDS bank conflicts
-  const int nb2 = TWO ? (a.h2 + 31) >> 5 : 0;
-  const int ksteps = (h1 + 7) >> 3;
+  const int jstart = tid % hl;                 // mlp_tail_dot: every item thread starts at another column
+  const int nb2 = (a.h2 + 31) >> 5, ksteps = (h1 + 7) >> 3;
   const int vper = 2 * ksteps;                 // float4 columns of a tile row that anything reads
   int hb = 0, he = 0;
   if (a.hist_ptr) { hb = a.hist_ptr[b]; he = a.hist_ptr[b + 1]; }
@@ -275,7 +257,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) wd_topk_kernel(WdTopkArgs a) {
   TopList<KT> top;
   top.init();
 
-  for (int tn = tn0; tn < tn1; ++tn) {
+  for (int tn = tr.tn0; tn < tr.tn1; ++tn) {
     const int n0 = tn * WD_BM;
     if (tid < 4) bitmap[tid] = 0u;
     // first layer: relu(T[n] + h_b) -> tile (zero beyond h1 and beyond the catalogue)
@@ -289,67 +271,22 @@ __global__ void __launch_bounds__(GEMM_THREADS) wd_topk_kernel(WdTopkArgs a) {
         t.x = fmaxf(tv.x + hv.x, 0.f); t.y = fmaxf(tv.y + hv.y, 0.f);
         t.z = fmaxf(tv.z + hv.z, 0.f); t.w = fmaxf(tv.w + hv.w, 0.f);
       }
-      *reinterpret_cast<float4*>(tile + rl * WD_LD + col) = t;
+      *reinterpret_cast<float4*>(tile + rl * MT_LD + col) = t;
     }
     __syncthreads();
     // history mask over the user's FULL history: items of this tile as bits
-    for (int p = hb + tid; p < he; p += GEMM_THREADS) {
-      const int64_t it = a.hist_items[p];
-      if (it >= n0 && it < n0 + WD_BM) {
-        const int il = (int)(it - n0);
-        atomicOr(&bitmap[il >> 5], 1u << (il & 31));
-      }
-    }
+    hist_bitmap_rows<WD_BM, GEMM_THREADS>(bitmap, a.hist_items, hb, he, n0, tid, [](int) { return 0; });
     if constexpr (TWO) {
-      // second layer on the MFMA: the wave owns 32 items x every column block of h2; lanes 0-31 feed k 0..3, lanes 32-63 k 4..7
       f32x16 acc2[4];
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc2[jb][e] = 0.f;
-      const float* arow = tile + (wave * 32 + r) * WD_LD + hh * 4;
-      const float* brow = w2s + r * WD_LD + hh * 4;
-      for (int k8 = 0; k8 < ksteps; ++k8) {
-        const float4 av = *reinterpret_cast<const float4*>(arow + k8 * 8);
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb) {
-          if (jb < nb2) {
-            const float4 bv = *reinterpret_cast<const float4*>(brow + jb * 32 * WD_LD + k8 * 8);
-            acc2[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc2[jb], 0, 0, 0);
-            acc2[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc2[jb], 0, 0, 0);
-            acc2[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc2[jb], 0, 0, 0);
-            acc2[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc2[jb], 0, 0, 0);
-          }
-        }
-      }
+      mlp_tail_layer2(acc2, tile, w2s, ksteps, nb2, wave, r, hh);
       __syncthreads();                         // every wave has read the first layer's activations
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) {
-        if (jb < nb2) {
-          const int col = jb * 32 + r;
-          const float bb = b2s[col];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int rl = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-            tile[rl * WD_LD + col] = fmaxf(acc2[jb][e] + bb, 0.f);
-          }
-        }
-      }
+      mlp_tail_layer2_store(tile, acc2, b2s, nb2, wave, r, hh, WdRelu{});
     }
     __syncthreads();                           // the last layer's activations and the bitmap are complete
     if (tid < WD_BM) {
       const int item = n0 + tid;
-      const bool dead = item >= a.N || item == 0 || ((bitmap[tid >> 5] >> (tid & 31)) & 1u);
-      if (!dead) {
-        const float* row = tile + tid * WD_LD;
-        float s = 0.f;
-        int j = jstart;
-        for (int jj = 0; jj < hl; ++jj) {
-          s += wps[j] * row[j];
-          j = j + 1 == hl ? 0 : j + 1;
-        }
-        top.insert((sb + a.wide[item]) + s, item);
-      }
+      if (item_alive(bitmap, item, tid, a.N))
+        top.insert((sb + a.wide[item]) + mlp_tail_dot(wps, tile + tid * MT_LD, hl, jstart), item);
     }
     __syncthreads();                           // the tile and the bitmap are rewritten by the next item tile
   }
@@ -359,12 +296,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) wd_topk_kernel(WdTopkArgs a) {
   wave_collapse_lists(top, lane, a.part_val + o, a.part_idx + o);
 }
 
-static int wd_pick_split(int B, int N) {
-  const int tiles_n = (N + WD_BM - 1) / WD_BM;
-  int s = (512 + B - 1) / B;                   // one resident workgroup per CU (its LDS): about two rounds of the chip
-  if (s > tiles_n) s = tiles_n;
-  return s < 1 ? 1 : s;
-}
+static int wd_tiles(int N) { return (N + WD_BM - 1) / WD_BM; }
 static bool wd_shape_ok(int B, int L, int N, int h1, int h2, int K) {
   return B > 0 && B <= (1 << 20) && L >= 1 && L <= WD_MAX_L && N > 0 && h1 >= 4 && h1 % 4 == 0 && h1 <= WD_MAX_H && h2 >= 0 &&
          h2 <= WD_MAX_H && K >= 1 && K <= 32 && (int64_t)N * h1 * 4 < 0x7FFFFFFFF0ll;
@@ -439,8 +371,8 @@ extern "C" int pxr_wd_head_bwd_f32(const float* alast, const float* dact, const 
 // input flag | per-user scalars | partial values | partial ids
 extern "C" int64_t pxr_wd_topk_ws_bytes(int B, int L, int N, int h1, int h2, int K) {
   if (!wd_shape_ok(B, L, N, h1, h2, K)) return -1;
-  const int64_t cand = (int64_t)wd_pick_split(B, N) * 2 * pick_kt(K);
-  return 256 + a256((int64_t)B * 4) + 2 * a256((int64_t)B * cand * 4);
+  const int64_t cand = (int64_t)topk_pick_split(B, wd_tiles(N)) * 2 * pick_kt(K);
+  return topk_ws_bytes(a256((int64_t)B * 4), B, cand);
 }
 
 extern "C" int pxr_wd_topk_f32(const float* T, int N, int h1, const float* hb, const int64_t* window, int B, int L, const float* wide,
@@ -458,31 +390,22 @@ extern "C" int pxr_wd_topk_f32(const float* T, int N, int h1, const float* hb, c
   WdTopkArgs a{};
   a.T = T; a.hb = hb; a.wide = wide; a.wide_bias = wide_bias; a.bp = bp; a.window = window; a.hist_ptr = hist_ptr;
   a.hist_items = hist_items; a.w2 = w2; a.b2 = b2; a.wp = wp; a.B = B; a.L = L; a.N = N; a.h1 = h1; a.h2 = h2;
-  a.tiles_n = (N + WD_BM - 1) / WD_BM;
-  a.n_split = wd_pick_split(B, N);
+  a.tiles_n = wd_tiles(N);
+  a.n_split = topk_pick_split(B, a.tiles_n);
   a.status = pxr_status_word();
   const int64_t cand = (int64_t)a.n_split * 2 * kt;
-  char* w = (char*)ws;
-  a.bad = (int*)w;                     w += 256;
-  a.sb = (float*)w;                    w += a256((int64_t)B * 4);
-  a.part_val = (float*)w;              w += a256((int64_t)B * cand * 4);
-  a.part_idx = (int*)w;
+  const TopkWs w = topk_ws_carve(ws, a256((int64_t)B * 4), B, cand);
+  a.bad = w.bad; a.part_val = w.part_val; a.part_idx = w.part_idx;
+  a.sb = (float*)w.own;
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(a.bad, 0, 256, st) != hipSuccess) return pxr_check_launch("pxr_wd_topk_f32(memset)");
+  if (int rc = topk_ws_clear_flag(w, "pxr_wd_topk_f32(memset)", st)) return rc;
   hipLaunchKernelGGL(wd_prep_kernel, dim3((unsigned)B), dim3(64), 0, st, a);
-  int rc = pxr_check_launch("pxr_wd_topk_f32(prep)");
-  if (rc) return rc;
+  if (int rc = pxr_check_launch("pxr_wd_topk_f32(prep)")) return rc;
   const dim3 grid((unsigned)(B * a.n_split));
-#define PXR_WD(KT_)                                                                                         \
-  if (h2 > 0) hipLaunchKernelGGL((wd_topk_kernel<KT_, true>), grid, dim3(GEMM_THREADS), 0, st, a);          \
-  else hipLaunchKernelGGL((wd_topk_kernel<KT_, false>), grid, dim3(GEMM_THREADS), 0, st, a);
-  switch (kt) {
-    case 10: PXR_WD(10); break;
-    case 16: PXR_WD(16); break;
-    default: PXR_WD(32); break;
-  }
-#undef PXR_WD
-  rc = pxr_check_launch("pxr_wd_topk_f32");
-  if (rc) return rc;
-  return pxr_topk_merge(a.bad, a.part_val, a.part_idx, B, (int)cand, K, topk_idx, topk_val, "pxr_wd_topk_f32(merge)", stream);
+  topk_for_kt(kt, [&](auto k) {
+    constexpr int KT = decltype(k)::value;
+    if (h2 > 0) hipLaunchKernelGGL((wd_topk_kernel<KT, true>), grid, dim3(GEMM_THREADS), 0, st, a);
+    else hipLaunchKernelGGL((wd_topk_kernel<KT, false>), grid, dim3(GEMM_THREADS), 0, st, a);
+  });
+  return topk_ws_merge(w, B, cand, K, topk_idx, topk_val, "pxr_wd_topk_f32", "pxr_wd_topk_f32(merge)", stream);
 }

@@ -1659,6 +1659,21 @@ def topk_products() -> int:
     return v if v in (1, 3, 6) else 3
 
 
+def _topk_hist_csr(who: str, hist_ptr, hist_items, B: int):
+    """The history CSR of a fused top-k call, where one is given: hist_ptr int32 [B + 1], hist_items int64."""
+    if hist_ptr is not None:
+        _req(hist_ptr, torch.int32, "hist_ptr"); _req(hist_items, torch.int64, "hist_items")
+        if hist_ptr.numel() != B + 1:
+            raise _l.PxrError(f"{who}: hist_ptr must have B + 1 = {B + 1} entries")
+
+
+def _topk_out(B: int, K: int, device):
+    """The outputs of a fused top-k call (topk_idx int64 [B, K], topk_val fp32 [B, K]); the device's status word, which the
+    kernels flag bad ids in, is registered first."""
+    device_status(device)
+    return torch.empty(B, K, dtype=torch.int64, device=device), torch.empty(B, K, dtype=torch.float32, device=device)
+
+
 def score_topk(users: torch.Tensor, ld_users: int, B: int, table: torch.Tensor, K: int, hist_ptr=None,
                hist_items=None, table_planes: Planes | None = None, table_norm_max: torch.Tensor | None = None):
     """Fused full-catalog scoring + masking + top-K (see pxr.h).  `users` may be a strided view (row stride
@@ -1669,9 +1684,7 @@ def score_topk(users: torch.Tensor, ld_users: int, B: int, table: torch.Tensor, 
     Lb = _l.load()
     _req(users, torch.float32, "users", contiguous=False); _req(table, torch.float32, "table")
     N, D = table.shape
-    device_status(table.device)
-    idx = torch.empty(B, K, dtype=torch.int64, device=table.device)
-    val = torch.empty(B, K, dtype=torch.float32, device=table.device)
+    idx, val = _topk_out(B, K, table.device)
     ws_bytes = int(Lb.pxr_score_topk_ws_bytes(B, N, K))
     if ws_bytes < 0:
         raise _l.PxrError("score_topk: K must be in [1, 32]")
@@ -2570,16 +2583,11 @@ def visrank_topk(unit, window, top_k: int, K: int, hist_ptr=None, hist_items=Non
         raise _l.PxrError("visrank top-k: unit must be [N, F] and window [B, H]")
     N, F = unit.shape
     B, H = window.shape
-    if hist_ptr is not None:
-        _req(hist_ptr, torch.int32, "hist_ptr"); _req(hist_items, torch.int64, "hist_items")
-        if hist_ptr.numel() != B + 1:
-            raise _l.PxrError(f"visrank top-k: hist_ptr must have B + 1 = {B + 1} entries")
+    _topk_hist_csr("visrank top-k", hist_ptr, hist_items, B)
     ws_bytes = int(Lb.pxr_visrank_topk_ws_bytes(B, H, N, K))
     if ws_bytes < 0:
         raise _l.PxrError(f"visrank top-k: need B >= 1, 1 <= H <= 64, 1 <= K <= 32 (B={B}, H={H}, K={K})")
-    device_status(unit.device)
-    idx = torch.empty(B, K, dtype=torch.int64, device=unit.device)
-    val = torch.empty(B, K, dtype=torch.float32, device=unit.device)
+    idx, val = _topk_out(B, K, unit.device)
     ws = _ws.get(ws_bytes, unit.device)
     _l.check(Lb.pxr_visrank_topk_f32(_l.ptr(unit), N, F, _l.ptr(window), B, H, int(top_k), _l.ptr(hist_ptr), _l.ptr(hist_items), K,
                                      _l.ptr(idx), _l.ptr(val), _l.ptr(ws), ws_bytes, _l.stream_ptr()), "pxr_visrank_topk_f32")
@@ -2743,16 +2751,11 @@ def din_topk(table, window, aq, bm, cm, w2, b2, wd, bd, K: int, hist_ptr=None, h
         raise _l.PxrError(f"din top-k: aq must be [N, h1] and bm / cm [h1, D] (N={N}, D={D}, h1={h1})")
     if wd.numel() != (h2 or h1) or bd.numel() != 1:
         raise _l.PxrError("din top-k: wd must hold h_last floats and bd one")
-    if hist_ptr is not None:
-        _req(hist_ptr, torch.int32, "hist_ptr"); _req(hist_items, torch.int64, "hist_items")
-        if hist_ptr.numel() != B + 1:
-            raise _l.PxrError(f"din top-k: hist_ptr must have B + 1 = {B + 1} entries")
+    _topk_hist_csr("din top-k", hist_ptr, hist_items, B)
     if int(Lb.pxr_din_topk_ws_bytes(1, L, N, D, h1, h2, K)) < 0:
         raise _l.PxrError(f"din top-k: outside the fused limits (D % 4 == 0 up to 128, hidden widths up to 128, L <= 64, K <= 32): "
                           f"D={D}, hidden=({h1}, {h2}), L={L}, K={K}")
-    device_status(table.device)
-    idx = torch.empty(B, K, dtype=torch.int64, device=table.device)
-    val = torch.empty(B, K, dtype=torch.float32, device=table.device)
+    idx, val = _topk_out(B, K, table.device)
     chunk = max(1, min(B, DIN_WS_CAP // max(1, L * (h1 * D + 128) * 4)))
     for lo in range(0, B, chunk):
         hi = min(B, lo + chunk)
@@ -2986,17 +2989,12 @@ def wd_topk(T, hb, window, wide, wide_bias, w2, b2, wp, bp, K: int, hist_ptr=Non
             raise _l.PxrError(f"widedeep top-k: w2 must be [h2, h1] = [{h2}, {h1}] and b2 [h2]")
     if tuple(hb.shape) != (B, h1) or wide.numel() != N or wide_bias.numel() != 1 or wp.numel() != (h2 or h1) or bp.numel() != 1:
         raise _l.PxrError(f"widedeep top-k: need hb [B, h1], wide [N], wp [h_last], wide_bias / bp [1] (B={B}, N={N}, h1={h1}, h2={h2})")
-    if hist_ptr is not None:
-        _req(hist_ptr, torch.int32, "hist_ptr"); _req(hist_items, torch.int64, "hist_items")
-        if hist_ptr.numel() != B + 1:
-            raise _l.PxrError(f"widedeep top-k: hist_ptr must have B + 1 = {B + 1} entries")
+    _topk_hist_csr("widedeep top-k", hist_ptr, hist_items, B)
     ws_bytes = int(Lb.pxr_wd_topk_ws_bytes(B, L, N, h1, h2, K))
     if ws_bytes < 0:
         raise _l.PxrError(f"widedeep top-k: outside the fused limits (hidden widths up to 128, the first a multiple of 4, L <= 64, "
                           f"K <= 32): hidden=({h1}, {h2}), L={L}, K={K}")
-    device_status(T.device)
-    idx = torch.empty(B, K, dtype=torch.int64, device=T.device)
-    val = torch.empty(B, K, dtype=torch.float32, device=T.device)
+    idx, val = _topk_out(B, K, T.device)
     ws = _ws.get(ws_bytes, T.device)
     _l.check(Lb.pxr_wd_topk_f32(_l.ptr(T), N, h1, _l.ptr(hb), _l.ptr(window), B, L, _l.ptr(wide), _l.ptr(wide_bias), _l.ptr(w2),
                                 _l.ptr(b2), h2, _l.ptr(wp), _l.ptr(bp), _l.ptr(hist_ptr), _l.ptr(hist_items), K, _l.ptr(idx),

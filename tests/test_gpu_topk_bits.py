@@ -19,8 +19,20 @@ ops.raise_on_bad_indices at the end of every run shows that no status bit was se
   * VISRANK: B 5 x N 300 x F 8, H 4, ragged window lengths, top_k 0 / 1 / 3, K 10, and a catalogue with fewer than K unmasked
     items (inputs by tests/test_gpu_visrank.py's helpers);
   * DIN: item_num 257 and 13 (fewer than K real items), B 3, L 4, hidden (16,) and (12, 4), K 10 (inputs by
-    tests/din_restate.topk_case; the last user keeps fewer than K items unmasked)."""
+    tests/din_restate.topk_case; the last user keeps fewer than K items unmasked).
+
+The walk groups (din_walk, wd_walk, vr_walk) pin the tile-to-tile carry of din_topk_kernel, wd_topk_kernel and visrank_topk_kernel --
+the cases above give a workgroup one tile at most, and none of them is WideDeep.  Their entries were recorded by the same --record
+path on the build of commit 06ea9af, where each of the three kernels still carried its own walk frame (tile range, bitmap fill,
+MLP tail, workspace carve); the frame shared since computes the same bits.  Per case a SHA-256 of the int64 id bytes and one of the
+fp32 value bytes, both equal.  Cases, inputs and histories are those of tests/test_gpu_topk_walk.py (its case objects are shared:
+one build per session), run the way that module runs them:
+  * din_walk: every din_restate.WALK_CASES entry at K 10 (the odd hidden widths through ops.din_topk, "chunks" as users 0-1, 2-3,
+    4 under a lowered ops.DIN_WS_CAP), "short splits" also at K 16 and 32;
+  * wd_walk: every widedeep_restate.WALK_CASES entry at K 10, "short splits" also at K 16 and 32;
+  * vr_walk: every visrank_restate.WALK_CASES entry with top_k 0, 1 and 3 at K 10."""
 import contextlib
+import hashlib
 import json
 import os
 import subprocess
@@ -30,9 +42,16 @@ import numpy as np
 import pytest
 import torch
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if __name__ == "__main__":                               # --record / --emit: run as a script, from anywhere
+    sys.path.insert(0, ROOT)
+
+from tests import din_restate as RD  # noqa: E402
+from tests import visrank_restate as RV  # noqa: E402
+from tests import widedeep_restate as RW  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "topk_core_bits.json")
 REG = {"reg/b130_n777_d32_k10": (130, 777, 32, 10, 21), "reg/b3_n20_d4_k32": (3, 20, 4, 32, 22)}
 VARIANT_CASE = "reg/b130_n777_d32_k10"
@@ -152,6 +171,45 @@ GROUPS = {"reg": lambda: {name: _register_list_case(name) for name in REG}, "thr
           "din": _din_cases, "variant": lambda: {f"variant/{v}/{VARIANT_CASE}": _variant_child(v) for v in (1, 3)}}
 
 
+def _digests(idx, val):
+    """SHA-256 of the id bytes and of the value bytes (the callers have synchronised and read the status word)"""
+    idx, val = idx.cpu().contiguous(), val.cpu().contiguous()
+    assert idx.dtype == torch.int64 and val.dtype == torch.float32
+    return {"ids_sha256": hashlib.sha256(idx.numpy().tobytes()).hexdigest(),
+            "val_sha256": hashlib.sha256(val.numpy().tobytes()).hexdigest()}
+
+
+def _mlp_walk(model_name, name, k):
+    from pixelrec_amd import ops
+    from tests import test_gpu_topk_walk as W
+
+    c = (W.DIN_CASES if model_name == "din" else W.WD_CASES).get(name)
+    prev = ops.DIN_WS_CAP
+    if name == "chunks":                                 # as test_din_user_chunks_equal_the_unchunked_call: chunks of 2, 2 and 1 users
+        ops.DIN_WS_CAP = 2 * c.L * (c.hidden[0] * c.D + 128) * 4
+    try:
+        return _digests(*W._fused(model_name, c, k))     # (_fused checks the status word)
+    finally:
+        ops.DIN_WS_CAP = prev
+
+
+def _vr_walk(name, top_k):
+    from tests import test_gpu_topk_walk as W
+
+    return _digests(*W._vr_fused(W.VR_CASES.get(name, top_k), RV.WALK_K))
+
+
+# case -> how to run it; the part of the name before the first "/" is the group
+WALK = {}
+for _model, _R in (("din", RD), ("wd", RW)):
+    for _name in _R.WALK_CASES:
+        for _k in (10, 16, 32) if _name == "short splits" else (10,):
+            WALK[f"{_model}_walk/{_name}/k{_k}"] = (_mlp_walk, "din" if _model == "din" else "widedeep", _name, _k)
+for _name in RV.WALK_CASES:
+    for _top_k in (0, 1, 3):
+        WALK[f"vr_walk/{_name}/top_k{_top_k}"] = (_vr_walk, _name, _top_k)
+
+
 @pytest.fixture(scope="module")
 def golden():
     with open(GOLDEN) as f:
@@ -175,8 +233,17 @@ def test_bits_of_the_separate_copies_are_kept(group, golden):
         assert (ids[:, N - 1:] == -1).all() and (ids[:, :N - 6] >= 1).all()
 
 
+@pytest.mark.parametrize("name", list(WALK))
+def test_bits_of_the_walks_are_kept(name, golden):
+    run, *args = WALK[name]
+    assert run(*args) == golden[name], name
+
+
+def test_the_golden_file_holds_exactly_these_walks(golden):
+    assert sorted(k for k in golden if k.split("/")[0] in ("din_walk", "wd_walk", "vr_walk")) == sorted(WALK)
+
+
 if __name__ == "__main__":
-    sys.path.insert(0, ROOT)
     if len(sys.argv) == 3 and sys.argv[1] == "--emit":
         print(json.dumps(_register_list_case(sys.argv[2])))
     else:
@@ -184,5 +251,7 @@ if __name__ == "__main__":
         cases = {}
         for make in GROUPS.values():
             cases.update(make())
+        for name, (run, *args) in WALK.items():
+            cases[name] = run(*args)
         with open(sys.argv[2], "w") as f:                # one case per line
             f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(cases[k], sort_keys=True)}" for k in sorted(cases)) + "\n}\n")

@@ -104,14 +104,17 @@ class _MlpCases:
         return self.built[name]
 
 
+DIN_CASES, WD_CASES = _MlpCases(RD, TD, DIN_TOL), _MlpCases(RW, TW, WD_TOL)   # also read by tests/test_gpu_topk_bits.py: one build
+
+
 @pytest.fixture(scope="module")
 def din_cases():
-    return _MlpCases(RD, TD, DIN_TOL)
+    return DIN_CASES
 
 
 @pytest.fixture(scope="module")
 def wd_cases():
-    return _MlpCases(RW, TW, WD_TOL)
+    return WD_CASES
 
 
 def _din_operands(c):
@@ -356,9 +359,12 @@ class _VrCases:
         return self.built[(name, top_k)]
 
 
+VR_CASES = _VrCases()
+
+
 @pytest.fixture(scope="module")
 def vr_cases():
-    return _VrCases()
+    return VR_CASES
 
 
 def _vr_fused(c, k, users=None):
