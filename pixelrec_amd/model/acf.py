@@ -36,9 +36,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..lib import PxrError
-from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .packed import LazyTableModel, TrainStep, _Rows
+from .packed import LazyTableModel, TrainStep, _Rows, check_width16, dense_scores, linear_names, linear_specs, one_process, split_tail
 
 
 class _FeatNet(nn.Module):
@@ -79,11 +78,9 @@ class ACF(LazyTableModel):
 
     def __init__(self, config, dataload):
         super().__init__()
-        if world_info()[1] > 1:
-            raise NotImplementedError("ACF runs on one process: data parallelism is not built for this model")
+        one_process(self)
         self.embedding_size = E = int(config["embedding_size"])
-        if E <= 0 or E % 4 or E > 4096:
-            raise ValueError(f"embedding_size must be a positive multiple of 4, at most 4096 (16-byte vector accesses); got {E}")
+        check_width16(E)
         self.max_seq_length = int(config["MAX_ITEM_LIST_LENGTH"])
         self.user_num = dataload.user_num
         self.item_num = dataload.item_num
@@ -111,25 +108,19 @@ class ACF(LazyTableModel):
         self._x_cache = self._xt_cache = None
 
     # ------------------------------------------------------------------------------------------ packing
+    def _linears(self):
+        return [(key, path, self.get_submodule(path)) for key, path in _LINEARS]
+
     def _flat_specs(self):
         """Flat layout: the 16 Linear tensors in the reference's parameter order."""
-        out = []
-        for key, path in _LINEARS:
-            lin = self.get_submodule(path)
-            out += [(key + ".w", lin.weight), (key + ".b", lin.bias)]
-        return out
+        return linear_specs(self._linears())
 
     def rec_parameter_names(self):
         """{reference parameter name: flat-buffer key} in the reference's registration order (optim.native_to_torch_state); the
         tables map to None -- their state is the table's (optim.table_spans).  18 entries: the alias
         user_model.profile_embedding.weight is item_model.weight and is not a parameter of its own."""
-        out = {"item_model.weight": None}
-        for key, path in _LINEARS:
-            if key == "wu":
-                out["user_model.user_embedding.weight"] = None
-            out[path + ".weight"] = key + ".w"
-            out[path + ".bias"] = key + ".b"
-        return out
+        lin = self._linears()                              # the four of `feats`, then the user table, then the user net's four
+        return {"item_model.weight": None, **linear_names(lin[:4]), "user_model.user_embedding.weight": None, **linear_names(lin[4:])}
 
     def table_parameter_spans(self):
         """Rows of the table buffer each table parameter occupies (optim.table_spans), in the reference's order."""
@@ -138,29 +129,15 @@ class ACF(LazyTableModel):
 
     def _after_pack(self, dev):
         self.v_feat = self.v_feat.to(dev)
-        self._x_cache = self._xt_cache = None
 
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        self._x_cache = self._xt_cache = None
-        return super().load_state_dict(state_dict, strict=strict, **kwargs)
-
-    def train(self, mode: bool = True):
-        if mode:
-            self._x_cache = self._xt_cache = None          # the evaluation caches go when training resumes
-        return super().train(mode)
+    def _drop_eval_cache(self):
+        self._x_cache = self._xt_cache = None              # the per-item projections go when training resumes
 
     # ------------------------------------------------------------------------------------------ training
     def _split_input(self, input, n_tail):
         """The reference's single [B, L + n_tail] tensor, or (profile [B, L], tail [B, n_tail]) -> contiguous (profile, tail)."""
-        if isinstance(input, (tuple, list)):
-            profile, tail = input
-            tail = tail.reshape(profile.shape[0], -1)
-        else:
-            profile, tail = input[:, :-n_tail], input[:, -n_tail:]
-        if tail.shape[1] != n_tail or profile.dim() != 2 or profile.shape[1] < 1:
-            raise ValueError(f"ACF: expected [B, L + {n_tail}] ids (profile, then {n_tail} trailing columns), got profile "
-                             f"{tuple(profile.shape)} and tail {tuple(tail.shape)}")
-        return profile.contiguous(), tail.contiguous()
+        return split_tail(input, n_tail, f"ACF: expected [B, L + {n_tail}] ids (profile, then {n_tail} trailing columns), got profile "
+                                         "{profile} and tail {tail}")
 
     def forward(self, input):
         if not self.training:
@@ -206,14 +183,11 @@ class ACF(LazyTableModel):
         self._saved = s
         return loss
 
-    def _backward_train(self, grad_out):
-        s = self._saved
-        if s is None:
-            raise PxrError("backward() without a training-mode forward()")
+    def _backward_train(self, gsd):
+        s = self._take_saved()
         B, P, E, H = s["B"], s["P"], self.embedding_size, self.regions
         R = B * P
         n = R + 3 * B
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         G = lambda k: self._p(k, grad=True)
         occ = self._buf("occ", (n, E))                     # one gradient row per occurrence: profile | positive, negative | user
         duser = self._buf("duser", (B, E))
@@ -241,9 +215,7 @@ class ACF(LazyTableModel):
                                        (da, s["prof"], G("wp.w"), G("wp.b")), (da, s["pooled"], G("wx.w"), G("wx.b"))])
         # the table gradient: stable sort of the occurrence rows + segmented sum (O(n log n), not MF's first-occurrence scan)
         self.sparse_table_grad = ops.embed_grad_rows(s["gidx"], occ, self._table.shape[0], out=self._sparse_rows(n))
-        self._saved = None
-        ops.counter_add(self._drop_dev, 1)
-        self._step_counter += 1
+        self._step_done()
 
     # ------------------------------------------------------------------------------------------ evaluation
     @torch.no_grad()
@@ -296,9 +268,4 @@ class ACF(LazyTableModel):
             raise PxrError("ACF: call compute_item_all() before scoring")
         feat = feat if feat.is_contiguous() else feat.contiguous()
         _, u = self.encode_last(inputs, feat)
-        B, E = u.shape
-        N = feat.shape[0]
-        scores = torch.empty(B, N, dtype=torch.float32, device=u.device)
-        ops.gemm(True, True, B, N, E, u, E, feat, E, scores, N, ops.EPI_NONE, use_ws=False)
-        ops.raise_on_bad_indices(u.device)     # an id outside the tables raises, like the reference's indexing
-        return scores
+        return dense_scores(u, feat)

@@ -43,13 +43,13 @@ import torch.nn as nn
 
 from .. import ops
 from ..lib import PxrError
-from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .packed import PackedModel, TrainStep
+from .packed import PackedModel, TrainStep, check_width16, dense_scores, linear_names, linear_specs, one_process, split_tail
 
 
 # flat-buffer key -> the Linear's attribute, in the reference's parameter order (curatornet.py:29-37)
 _LINEARS = (("c1", "selu_common1"), ("c2", "selu_common2"), ("p1", "selu_pu1"), ("p2", "selu_pu2"), ("p3", "selu_pu3"))
+_COMMON, _TOWER = ("c1", "c2"), ("p1", "p2", "p3")     # the item tower (shared with the profile rows) and the profile tower
 
 
 class CuratorNet(PackedModel):
@@ -59,11 +59,9 @@ class CuratorNet(PackedModel):
 
     def __init__(self, config, dataload):
         super().__init__()
-        if world_info()[1] > 1:
-            raise NotImplementedError("CuratorNet runs on one process: data parallelism is not built for this model")
+        one_process(self)
         self.embedding_size = E = int(config["embedding_size"])
-        if E <= 0 or E % 4 or E > 4096:
-            raise ValueError(f"embedding_size must be a positive multiple of 4, at most 4096 (16-byte vector accesses); got {E}")
+        check_width16(E)
         mult = config["hidden_size"]
         if isinstance(mult, bool) or not isinstance(mult, (int, np.integer)) or mult < 1:
             raise ValueError(f"hidden_size is a multiplier of embedding_size and must be an integer >= 1; got {mult!r}")
@@ -95,48 +93,27 @@ class CuratorNet(PackedModel):
         self.store_ifeatures = None
 
     # ------------------------------------------------------------------------------------------ packing
+    def _linears(self):
+        return [(key, attr, getattr(self, attr)) for key, attr in _LINEARS]
+
     def _flat_specs(self):
         """Flat layout: the ten Linear tensors in the reference's parameter order."""
-        out = []
-        for key, attr in _LINEARS:
-            lin = getattr(self, attr)
-            out += [(key + ".w", lin.weight), (key + ".b", lin.bias)]
-        return out
+        return linear_specs(self._linears())
 
     def rec_parameter_names(self):
         """{reference parameter name: flat-buffer key} of the TRAINABLE parameters in the reference's registration order
         (optim.native_to_torch_state): the reference trainer hands its optimizer the parameters with requires_grad only, so the
         frozen `embedding.weight` is not among them."""
-        out = {}
-        for key, attr in _LINEARS:
-            out[attr + ".weight"] = key + ".w"
-            out[attr + ".bias"] = key + ".b"
-        return out
+        return linear_names(self._linears())
 
-    def _after_pack(self, dev):
-        self.store_ifeatures = None
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        self.store_ifeatures = None
-        return super().load_state_dict(state_dict, strict=strict, **kwargs)
-
-    def train(self, mode: bool = True):
-        if mode:
-            self.store_ifeatures = None                    # the evaluation cache goes when training resumes
-        return super().train(mode)
+    def _drop_eval_cache(self):
+        self.store_ifeatures = None                        # the catalogue matrix goes when training resumes
 
     # ------------------------------------------------------------------------------------------ training
     def _split_input(self, input):
         """The reference's single [B, L + 2] tensor, or (profile [B, L], target [B, 2]) -> contiguous (profile, target)."""
-        if isinstance(input, (tuple, list)):
-            profile, target = input
-            target = target.reshape(profile.shape[0], -1)
-        else:
-            profile, target = input[:, :-2], input[:, -2:]
-        if target.shape[1] != 2 or profile.dim() != 2 or not 1 <= profile.shape[1] <= 255:
-            raise ValueError(f"CuratorNet: expected [B, L + 2] ids (profile of 1..255 positions, positive, negative), got profile "
-                             f"{tuple(profile.shape)} and target {tuple(target.shape)}")
-        return profile.contiguous(), target.contiguous()
+        return split_tail(input, 2, "CuratorNet: expected [B, L + 2] ids (profile of 1..255 positions, positive, negative), got profile "
+                                    "{profile} and target {tail}", max_len=255)
 
     def forward(self, input):
         if not self.training:
@@ -146,11 +123,8 @@ class CuratorNet(PackedModel):
         return TrainStep.apply(self._anchor, self, profile, target)
 
     def _profile_tower(self, cat):
-        """[B, 2E] pooled profile -> the three SELU Linears; returns the activations and their derivatives."""
-        a1, e1 = ops.linear_fwd(cat, self._p("p1.w"), self._p("p1.b"), act="selu")
-        a2, e2 = ops.linear_fwd(a1, self._p("p2.w"), self._p("p2.b"), act="selu")
-        u, e3 = ops.linear_fwd(a2, self._p("p3.w"), self._p("p3.b"), act="selu")
-        return a1, e1, a2, e2, u, e3
+        """[B, 2E] pooled profile -> the three SELU Linears: (activations, derivatives); the last activation is the user vector."""
+        return self._act_chain(cat, _TOWER, "selu")
 
     def _forward_train(self, profile, target):
         B, L = profile.shape
@@ -160,29 +134,24 @@ class CuratorNet(PackedModel):
         x = self._buf("x", (n, F))                         # rows: [B L profile | positive, negative per sample]
         ops.embed_gather(feat, profile.view(-1), out=x[:R])
         ops.embed_gather(feat, target.view(-1), out=x[R:])
-        h1, d1 = ops.linear_fwd(x, self._p("c1.w"), self._p("c1.b"), act="selu")
-        h2, d2 = ops.linear_fwd(h1, self._p("c2.w"), self._p("c2.b"), act="selu")
+        (h1, h2), (d1, d2) = self._act_chain(x, _COMMON, "selu")
         cat, arg = ops.curator_pool(h2, B, L, cat=self._buf("cat", (B, 2 * self.embedding_size)),
                                     argmax=self._buf("arg", (B, self.embedding_size), torch.uint8))
-        a1, e1, a2, e2, u, e3 = self._profile_tower(cat)
+        acts, ders = self._profile_tower(cat)
         ie = h2[R:]
-        loss, coef = ops.curator_pair_fwd(u, ie, B, out=self._buf("head", (2 * B + 1,)))
-        self._saved = dict(B=B, L=L, x=x, h1=h1, d1=d1, d2=d2, cat=cat, arg=arg, a1=a1, e1=e1, a2=a2, e2=e2, u=u, e3=e3, ie=ie,
-                           coef=coef)
+        loss, coef = ops.curator_pair_fwd(acts[-1], ie, B, out=self._buf("head", (2 * B + 1,)))
+        self._saved = dict(B=B, L=L, x=x, h1=h1, d1=d1, d2=d2, cat=cat, arg=arg, acts=acts, ders=ders, ie=ie, coef=coef)
         return loss
 
-    def _backward_train(self, grad_out):
-        s = self._saved
-        if s is None:
-            raise PxrError("backward() without a training-mode forward()")
+    def _backward_train(self, gsd):
+        s = self._take_saved()
         B, L, E = s["B"], s["L"], self.embedding_size
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         G = lambda k: self._p(k, grad=True)
         du, di = self._buf("du", (B, E)), self._buf("di", (2 * B, E))
-        ops.mf_pair_bwd(s["u"], s["ie"], s["coef"], du, di, self.grad_scale, gsd)
-        dz3 = ops.mul(du, s["e3"], out=du)                                        # through selu_pu3's SELU
-        dz2 = ops.linear_bwd_input(dz3, self._p("p3.w"), mul=s["e2"])
-        dz1 = ops.linear_bwd_input(dz2, self._p("p2.w"), mul=s["e1"])
+        (a1, a2, u), ders = s["acts"], s["ders"]
+        ops.mf_pair_bwd(u, s["ie"], s["coef"], du, di, self.grad_scale, gsd)
+        dz3 = ops.mul(du, ders[-1], out=du)                                       # through selu_pu3's SELU
+        dz1, dz2, dz3 = self._act_chain_bwd(dz3, _TOWER, ders)
         dcat = ops.linear_bwd_input(dz1, self._p("p1.w"))
         dpre2 = ops.curator_pool_bwd(dcat, s["arg"], di, s["d2"], B, L, out=self._buf("dpre2", (B * (L + 2), E)))
         dpre1 = ops.linear_bwd_input(dpre2, self._p("c2.w"), mul=s["d1"])
@@ -190,11 +159,9 @@ class CuratorNet(PackedModel):
         # (their token range may be split); the three over B rows share one grouped launch
         ops.grouped_linear_bwd_weight([(dpre1, s["x"], G("c1.w"), G("c1.b"))])
         ops.grouped_linear_bwd_weight([(dpre2, s["h1"], G("c2.w"), G("c2.b"))])
-        ops.grouped_linear_bwd_weight([(dz1, s["cat"], G("p1.w"), G("p1.b")), (dz2, s["a1"], G("p2.w"), G("p2.b")),
-                                       (dz3, s["a2"], G("p3.w"), G("p3.b"))])
-        self._saved = None
-        ops.counter_add(self._drop_dev, 1)
-        self._step_counter += 1
+        ops.grouped_linear_bwd_weight([(dz1, s["cat"], G("p1.w"), G("p1.b")), (dz2, a1, G("p2.w"), G("p2.b")),
+                                       (dz3, a2, G("p3.w"), G("p3.b"))])
+        self._step_done()
 
     # ------------------------------------------------------------------------------------------ evaluation
     @torch.no_grad()
@@ -209,9 +176,7 @@ class CuratorNet(PackedModel):
         out = torch.empty(I, self.embedding_size, dtype=torch.float32, device=feat.device)
         for lo in range(0, I, self.EVAL_CHUNK_ROWS):
             hi = min(I, lo + self.EVAL_CHUNK_ROWS)
-            h1, _ = ops.linear_fwd(feat[lo:hi], self._p("c1.w"), self._p("c1.b"), act="selu")
-            h2, _ = ops.linear_fwd(h1, self._p("c2.w"), self._p("c2.b"), act="selu")
-            out[lo:hi].copy_(h2)
+            out[lo:hi].copy_(self._act_chain(feat[lo:hi], _COMMON, "selu")[0][-1])
         self.store_ifeatures = out
         return out
 
@@ -231,7 +196,7 @@ class CuratorNet(PackedModel):
             raise ValueError(f"CuratorNet: item_seq must be [B, L] with 1 <= L <= 255, got {tuple(item_seq.shape)}")
         B, L = item_seq.shape
         cat, _ = ops.curator_pool(feat, B, L, ids=item_seq, want_argmax=False)
-        u = self._profile_tower(cat)[4]
+        u = self._profile_tower(cat)[0][-1]
         return u.view(B, 1, -1), u
 
     @torch.no_grad()
@@ -240,9 +205,4 @@ class CuratorNet(PackedModel):
         feat = item_feature if item_feature is not None else self.compute_item_all()
         feat = feat if feat.is_contiguous() else feat.contiguous()
         _, u = self.encode_last(item_seq, feat)
-        B, E = u.shape
-        N = feat.shape[0]
-        scores = torch.empty(B, N, dtype=torch.float32, device=u.device)
-        ops.gemm(True, True, B, N, E, u, E, feat, E, scores, N, ops.EPI_NONE, use_ws=False)
-        ops.raise_on_bad_indices(u.device)     # an id outside the catalogue raises, like the reference's indexing
-        return scores
+        return dense_scores(u, feat)

@@ -38,21 +38,9 @@ import torch.nn as nn
 
 from .. import ops
 from ..lib import PxrError
-from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .packed import LazyTableModel, TrainStep, _Rows
-
-
-class _AttMLP(nn.Module):
-    """MLPLayers(sizes, activation='Sigmoid', bn=False) with the reference's module layout (mlp_layers.{3k: Dropout, 3k + 1:
-    Linear, 3k + 2: Sigmoid}); never called -- the kernels read its parameters."""
-
-    def __init__(self, sizes):
-        super().__init__()
-        mods = []
-        for i, o in zip(sizes[:-1], sizes[1:]):
-            mods += [nn.Dropout(p=0.0), nn.Linear(i, o), nn.Sigmoid()]
-        self.mlp_layers = nn.Sequential(*mods)
+from .packed import (LazyTableModel, TrainStep, _ActMLP, _Rows, check_width16, hidden_sizes, linear_names, linear_specs, one_process,
+                     split_tail)
 
 
 class _Attention(nn.Module):
@@ -60,7 +48,7 @@ class _Attention(nn.Module):
 
     def __init__(self, sizes):
         super().__init__()
-        self.att_mlp_layers = _AttMLP(sizes)
+        self.att_mlp_layers = _ActMLP(sizes, nn.Sigmoid)       # MLPLayers(sizes, activation='Sigmoid', bn=False)
         self.dense = nn.Linear(sizes[-1], 1)
 
 
@@ -71,15 +59,10 @@ class DIN(LazyTableModel):
 
     def __init__(self, config, dataload):
         super().__init__()
-        if world_info()[1] > 1:
-            raise NotImplementedError("DIN runs on one process: data parallelism is not built for this model")
+        one_process(self)
         self.embedding_size = D = int(config["embedding_size"])
-        if D <= 0 or D % 4 or D > 4096:
-            raise ValueError(f"embedding_size must be a positive multiple of 4, at most 4096 (16-byte vector accesses); got {D}")
-        hidden = config["mlp_hidden_size"]
-        if isinstance(hidden, int):
-            hidden = [hidden]
-        self.mlp_hidden_size = hidden = [int(h) for h in hidden]
+        check_width16(D)
+        self.mlp_hidden_size = hidden = hidden_sizes(config["mlp_hidden_size"])
         if not hidden or any(h <= 0 or h % 4 or h > 4096 for h in hidden):
             raise ValueError(f"mlp_hidden_size must hold one or more positive multiples of 4, at most 4096 each (the weight-gradient "
                              f"GEMMs' vector accesses); got {hidden}")
@@ -96,6 +79,7 @@ class DIN(LazyTableModel):
                 if getattr(mod, "bias", None) is not None:
                     nn.init.zeros_(mod.bias.data)
         self._eval_cache = None
+        self._mlp_keys = [f"l{i}" for i in range(len(hidden))]     # the flat-buffer keys of the attention MLP's Linears
 
     # ------------------------------------------------------------------------------------------ packing
     def _linears(self):
@@ -108,49 +92,24 @@ class DIN(LazyTableModel):
         return out
 
     def _flat_specs(self):
-        out = []
-        for key, _, lin in self._linears():
-            out += [(key + ".w", lin.weight), (key + ".b", lin.bias)]
-        return out
+        return linear_specs(self._linears())
 
     def rec_parameter_names(self):
         """{reference parameter name: flat-buffer key} in the reference's registration order (optim.native_to_torch_state); the
         table maps to None -- its state is the table buffer's (optim.table_spans)."""
-        out = {}
-        for key, path, _ in self._linears():
-            out[path + ".weight"] = key + ".w"
-            out[path + ".bias"] = key + ".b"
-        out["item_embedding.weight"] = None
-        return out
+        return {**linear_names(self._linears()), "item_embedding.weight": None}
 
     def table_parameter_spans(self):
         """Rows of the table buffer the table parameter occupies (optim.table_spans)."""
         return {"item_embedding.weight": (1, 1 + self.item_num)}
 
-    def _after_pack(self, dev):
-        self._eval_cache = None
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        self._eval_cache = None
-        return super().load_state_dict(state_dict, strict=strict, **kwargs)
-
-    def train(self, mode: bool = True):
-        if mode:
-            self._eval_cache = None            # the A q + b1 matrix goes when training resumes
-        return super().train(mode)
+    def _drop_eval_cache(self):
+        self._eval_cache = None                # the A q + b1 matrix goes when training resumes
 
     # ------------------------------------------------------------------------------------------ training
     def _split_input(self, input):
         """The reference's single [B, L + 2] tensor, or (profile [B, L], target [B, 2]) -> contiguous (profile, target)."""
-        if isinstance(input, (tuple, list)):
-            profile, target = input
-            target = target.reshape(profile.shape[0], -1)
-        else:
-            profile, target = input[:, :-2], input[:, -2:]
-        if target.shape[1] != 2 or profile.dim() != 2 or profile.shape[1] < 1:
-            raise ValueError(f"DIN: expected [B, L + 2] ids (profile, positive, negative), got profile {tuple(profile.shape)} and "
-                             f"target {tuple(target.shape)}")
-        return profile.contiguous(), target.contiguous()
+        return split_tail(input, 2, "DIN: expected [B, L + 2] ids (profile, positive, negative), got profile {profile} and target {tail}")
 
     def forward(self, input):
         if not self.training:
@@ -161,12 +120,7 @@ class DIN(LazyTableModel):
 
     def _mlp(self, x):
         """x [M, 4 D] -> lists of the hidden layers' activations and derivatives (library GEMMs, sigmoid epilogue)."""
-        acts, ders = [], []
-        for i in range(len(self.mlp_hidden_size)):
-            x, d = ops.linear_fwd(x, self._p(f"l{i}.w"), self._p(f"l{i}.b"), act="sigmoid")
-            acts.append(x)
-            ders.append(d)
-        return acts, ders
+        return self._act_chain(x, self._mlp_keys, "sigmoid")
 
     def _forward_train(self, profile, target):
         B, L = profile.shape
@@ -183,23 +137,17 @@ class DIN(LazyTableModel):
         self._saved = dict(B=B, L=L, profile=profile, gidx=gidx, emb=emb, x=x, acts=acts, ders=ders, s=s, kq=kq, head=head)
         return loss
 
-    def _backward_train(self, grad_out):
-        s = self._saved
-        if s is None:
-            raise PxrError("backward() without a training-mode forward()")
+    def _backward_train(self, gsd):
+        s = self._take_saved()
         B, L, D = s["B"], s["L"], self.embedding_size
         n = B * (L + 2)
         nl = len(self.mlp_hidden_size)
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         G = lambda k: self._p(k, grad=True)
         acts, ders = s["acts"], s["ders"]
         dz, _ = ops.din_head_bwd(acts[-1], ders[-1], self._p("dense.w").view(-1), s["profile"], s["kq"], s["head"], D,
                                  G("dense.w").view(-1), G("dense.b"), self.grad_scale, gsd,
                                  dsraw=self._buf("dsraw", (2 * B * L,)))
-        dzs = [None] * nl
-        dzs[-1] = dz
-        for i in range(nl - 1, 0, -1):
-            dzs[i - 1] = ops.linear_bwd_input(dzs[i], self._p(f"l{i}.w"), mul=ders[i - 1])
+        dzs = self._act_chain_bwd(dz, self._mlp_keys, ders)
         dx = ops.linear_bwd_input(dzs[0], self._p("l0.w"))
         occ = ops.din_fold_bwd(dx, s["emb"], s["profile"], s["s"], s["head"], self.grad_scale, gsd, occ=self._buf("occ", (n, D)))
         # the first layer's reduction runs over 2 B L rows of 4 D inputs: a launch of its own (its token range may be split)
@@ -208,9 +156,7 @@ class DIN(LazyTableModel):
             ops.grouped_linear_bwd_weight([(dzs[i], acts[i - 1], G(f"l{i}.w"), G(f"l{i}.b")) for i in range(1, nl)])
         # the table gradient: stable sort of the occurrence rows + segmented sum (O(n log n); id 0 = the padding item: dropped)
         self.sparse_table_grad = ops.embed_grad_rows(s["gidx"], occ, self._table.shape[0], out=self._sparse_rows(n))
-        self._saved = None
-        ops.counter_add(self._drop_dev, 1)
-        self._step_counter += 1
+        self._step_done()
 
     # ------------------------------------------------------------------------------------------ evaluation
     @torch.no_grad()

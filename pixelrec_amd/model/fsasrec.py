@@ -247,9 +247,9 @@ class FSASRec(SeqRecCore):
         self._enc_saved = (table, saved)
         return self._forward_core(table, idx, masked_index, train=True)
 
-    def _backward_train(self, grad_out):
+    def _backward_train(self, gsd):
         (table, saved), self._enc_saved = self._enc_saved, None
-        dx0, coef, s = self._backward_core(grad_out, table)
+        dx0, coef, s = self._backward_core(gsd, table)
         d_emb = ops.mosasrec_emb_grad(dx0, s["out"], coef)            # [B, L+1, 2, D] = the order the ids were encoded in
         self._encode_items_bwd(d_emb.view(-1, d_emb.shape[-1]), saved)
 

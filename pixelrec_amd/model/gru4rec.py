@@ -30,7 +30,7 @@ import torch.nn as nn
 from .. import ops
 from ..utils.enum_type import InputType
 from .sasrec import SASRec
-from .seqcore import PxrError, SeqRecCore
+from .seqcore import SeqRecCore
 
 
 class GRUBlock:
@@ -121,15 +121,12 @@ class GRUBlock:
         out = out_tm.transpose(0, 1).contiguous()                                        # [B, L, E]: what the BPR head reads
         return out, (dict(layers=layers, ids_tm=ids_tm, drop=drop) if train else None)
 
-    def _backward_core(self, grad_out, table):
+    def _backward_core(self, gsd, table):
         """Backward of SeqRecCore._forward_core for the recurrent block: fills the flat gradient buffer, hands the gradient
         w.r.t. the gathered input rows to the table machinery (`_after_input_grads`)."""
-        s = self._saved
-        if s is None:
-            raise PxrError("backward() without a training-mode forward()")
+        s = self._take_saved()
         B, L, E, Hh = s["B"], self.max_seq_length, self.embedding_size, self.gru_hidden
         g = lambda name: self._p(name, grad=True)
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         dout, coef = ops.bpr_loss_bwd(s["pos"], s["neg"], table, s["items"], s["mask"], E, self.grad_scale, gsd)
         dout_tm = dout.transpose(0, 1).contiguous()                                      # [L, B, E]
         top = s["layers"][-1]
@@ -158,9 +155,7 @@ class GRUBlock:
         dx0 = dh_out.transpose(0, 1).contiguous()                                        # [B, L, E]
         self._after_input_grads(dx0, coef, s)
         ops.grouped_linear_bwd_weight(pend)        # every weight (and the dense bias) gradient of the step: one launch
-        self._saved = None
-        ops.counter_add(self._drop_dev, 1)
-        self._step_counter += 1
+        self._step_done()
         return dx0, coef, s
 
 

@@ -23,9 +23,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..lib import PxrError
-from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .packed import PackedModel, TrainStep, _Rows
+from .packed import PackedModel, TrainStep, _Rows, dense_scores, one_process
 
 
 class LightGCN(PackedModel):
@@ -33,8 +32,7 @@ class LightGCN(PackedModel):
 
     def __init__(self, config, dataload):
         super().__init__()
-        if world_info()[1] > 1:
-            raise NotImplementedError("LightGCN runs on one process: data parallelism is not built for the graph models")
+        one_process(self, "the graph models")
         self.latent_dim = config["embedding_size"]
         self.n_layers = int(config["n_layers"])
         if self.latent_dim % 4:
@@ -116,16 +114,11 @@ class LightGCN(PackedModel):
         self._saved = (ef, coef, nodes)
         return loss
 
-    def _backward_train(self, grad_out):
-        if self._saved is None:
-            raise PxrError("backward() without a training-mode forward()")
-        ef, coef, nodes = self._saved
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
+    def _backward_train(self, gsd):
+        ef, coef, nodes = self._take_saved()
         gfin = ops.lgcn_pair_bwd(ef, nodes, coef, self._work("gf"), self.grad_scale, gsd)
         self.propagate_grad(gfin, self._table(self._gflat))
-        self._saved = None
-        ops.counter_add(self._drop_dev, 1)
-        self._step_counter += 1
+        self._step_done()
 
     # ------------------------------------------------------------------------------------------ evaluation
     @torch.no_grad()
@@ -147,10 +140,4 @@ class LightGCN(PackedModel):
     def predict(self, user, item_feature=None):
         """scores [B, I] = E_final_u[user] E_final_i^T (lightgcn.py:82-86)."""
         _, rows = self.encode_last(user)
-        feat = self.store_ifeatures
-        B, D = rows.shape
-        N = feat.shape[0]
-        scores = torch.empty(B, N, dtype=torch.float32, device=rows.device)
-        ops.gemm(True, True, B, N, D, rows, D, feat, D, scores, N, ops.EPI_NONE, use_ws=False)
-        ops.raise_on_bad_indices(rows.device)     # a user id outside the table raises, like the reference's indexing
-        return scores
+        return dense_scores(rows, self.store_ifeatures)

@@ -28,10 +28,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..lib import PxrError
-from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .packed import TrainStep
+from .packed import TrainStep, one_process
 from .sasrec import SASRec
 from .seqcore import SeqRecCore, _FeedForwardParams
 
@@ -228,18 +226,15 @@ class LightSANsBlock:
             h = h2
         return h, saved
 
-    def _backward_core(self, grad_out, table):
+    def _backward_core(self, gsd, table):
         """Backward of SeqRecCore._forward_core for the LightSANs block: fills the flat gradient buffer, hands the gradient w.r.t.
         the gathered input rows to the table machinery (`_after_input_grads`)."""
-        s = self._saved
-        if s is None:
-            raise PxrError("backward() without a training-mode forward()")
+        s = self._take_saved()
         B, L, D, H, K = s["B"], self.max_seq_length, self.hidden_size, self.n_heads, self.k_interests
         T = B * L
         seed, ph, pa = s["seed"], s["ph"], s["pa"]
         sdv = self._drop_dev
         g = lambda name, span=1: self._p(name, grad=True, span=span)
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         defer = ops.DeferredReductions()
         pend = []
         fused = bool(s.get("fused_head"))
@@ -286,10 +281,7 @@ class LightSANsBlock:
         bumped = defer.flush(bump=self._drop_dev)
         self._after_input_grads(dx0, coef, s)
         ops.grouped_linear_bwd_weight(pend)        # every weight (and bias) gradient of the step: one launch
-        self._saved = None
-        if not bumped:
-            ops.counter_add(self._drop_dev, 1)
-        self._step_counter += 1
+        self._step_done(bumped)
         return dx0, coef, s
 
 
@@ -298,8 +290,7 @@ class LightSANs(LightSANsBlock, SASRec):
 
     def __init__(self, config, dataload):
         SeqRecCore.__init__(self)
-        if world_info()[1] > 1:
-            raise NotImplementedError("LightSANs runs on one process: data parallelism is not built for this model")
+        one_process(self)
         self._build_lightsans(config, dataload)
         self.apply(self._init_weights)       # Linear / Embedding N(0, initializer_range) incl. row 0, LayerNorm (1, 0)
         self._copy_first_layer_thetas()

@@ -30,9 +30,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..lib import PxrError
-from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .packed import LazyTableModel, TrainStep, _Rows
+from .packed import LazyTableModel, TrainStep, _Rows, dense_scores, hidden_sizes, one_process
 
 
 class _MLP(nn.Module):
@@ -57,10 +56,9 @@ class MF(LazyTableModel):
 
     def __init__(self, config, dataload):
         super().__init__()
-        if world_info()[1] > 1:
-            raise NotImplementedError("MF runs on one process: data parallelism is not built for this model")
+        one_process(self)
         self.embedding_size = int(config["embedding_size"])
-        self.mlp_hidden_size = [int(h) for h in (config["mlp_hidden_size"] or [])]
+        self.mlp_hidden_size = hidden_sizes(config["mlp_hidden_size"])
         self.dropout_prob = float(config["dropout_prob"] or 0.0)
         D = self.embedding_size
         if D % 4 or D > 4096:
@@ -186,12 +184,9 @@ class MF(LazyTableModel):
         self._saved = dict(B=B, rows=rows, coef=coef, hu=hu, hi=hi, su=su, si=si)
         return loss
 
-    def _backward_train(self, grad_out):
-        s = self._saved
-        if s is None:
-            raise PxrError("backward() without a training-mode forward()")
+    def _backward_train(self, gsd):
+        s = self._take_saved()
         B = s["B"]
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         sp = self._sparse_rows(3 * B)
         if not self.mlp_hidden_size:
             ops.mf_table_grad(s["rows"], B, sp, table=self._table, coef=s["coef"], grad_scale=self.grad_scale, grad_scale_dev=gsd)
@@ -206,9 +201,7 @@ class MF(LazyTableModel):
             ops.grouped_linear_bwd_weight(problems)
             ops.mf_table_grad(s["rows"], B, sp, occ=occ)
         self.sparse_table_grad = sp
-        self._saved = None
-        ops.counter_add(self._drop_dev, 1)
-        self._step_counter += 1
+        self._step_done()
 
     # ------------------------------------------------------------------------------------------ evaluation
     @torch.no_grad()
@@ -242,9 +235,4 @@ class MF(LazyTableModel):
             raise PxrError("MF: call compute_item_all() before scoring")
         feat = feat if feat.is_contiguous() else feat.contiguous()
         _, u = self.encode_last(user, feat)
-        B, H = u.shape
-        N = feat.shape[0]
-        scores = torch.empty(B, N, dtype=torch.float32, device=u.device)
-        ops.gemm(True, True, B, N, H, u, H, feat, H, scores, N, ops.EPI_NONE, use_ws=False)
-        ops.raise_on_bad_indices(u.device)     # a user id outside the table raises, like the reference's indexing
-        return scores
+        return dense_scores(u, feat)

@@ -35,11 +35,10 @@ import torch
 
 from .. import ops
 from ..lib import PxrError
-from ..parallel import world_info
 from ..utils.enum_type import InputType
 from .basemodel import BaseModel
-from .packed import TrainStep
-from .pooled import pool_queries, pool_scores
+from .packed import TrainStep, check_width16, dense_scores, one_process, take_saved
+from .pooled import pool_queries
 from .visual import load_model
 
 
@@ -51,12 +50,9 @@ class _MoPooledPair(BaseModel):
 
     def __init__(self, config, dataload):
         super().__init__()
-        name = type(self).__name__
-        if world_info()[1] > 1:
-            raise NotImplementedError(f"{name} runs on one process: data parallelism is not built for this model")
-        self.embedding_size = D = int(config["embedding_size"])
-        if D <= 0 or D % 4 or D > 4096:
-            raise ValueError(f"embedding_size must be a positive multiple of 4, at most 4096 (16-byte vector accesses); got {D}")
+        one_process(self)
+        self.embedding_size = int(config["embedding_size"])
+        check_width16(self.embedding_size)
         self.mlp_hidden_size = config["mlp_hidden_size"] if "mlp_hidden_size" in config else []      # read, never used
         self.dropout_prob = config["dropout_prob"] if "dropout_prob" in config else 0.0              # (modssm.py:15-16, mofm.py:17-18)
         L = config["MAX_ITEM_LIST_LENGTH"] if "MAX_ITEM_LIST_LENGTH" in config else None
@@ -132,14 +128,11 @@ class _MoPooledPair(BaseModel):
         self._saved = dict(S=S, L=L, rows=rows, U=U, w=w, coef=coef)
         return loss
 
-    def _backward_train(self, grad_out):
+    def _backward_train(self, gsd):
         """-> d loss / d E [M, D] (the bridge's anchor is the encoder's output)."""
-        s, table = self._saved, self._train_table
-        if s is None or table is None:
-            raise PxrError("backward() without a training-mode forward()")
+        s, table = take_saved(self, self._train_table), self._train_table
         S, L = s["S"], s["L"]
         M, D = table.shape
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         G = self._buf("G", (3 * S, D), table.device)
         ops.pool_pair_bwd(table, s["rows"], S, L, s["U"], s["coef"], self.grad_scale, gsd, G=G)
         dE = ops.pool_dense_grad(s["rows"], S, L, G, s["w"], M)
@@ -160,7 +153,7 @@ class _MoPooledPair(BaseModel):
         """scores [B, N] = q item_feature^T (predict of modssm.py / mofm.py); an all-padding window pools to exactly 0."""
         feat = (item_feature if item_feature.is_contiguous() else item_feature.contiguous()).data
         _, q = self.encode_last(item_seq, feat)
-        return pool_scores(q, feat)
+        return dense_scores(q, feat)
 
     @torch.no_grad()
     def compute_item(self, item):

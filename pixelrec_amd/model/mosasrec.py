@@ -70,10 +70,10 @@ class MOSASRec(SeqRecCore):
     def _forward_train(self, idx, masked_index):
         return self._forward_core(self._train_table, idx, masked_index, train=True)
 
-    def _backward_train(self, grad_out):
+    def _backward_train(self, gsd):
         """-> the gradient of the encoder's output [B, L+1, 2, D] (the bridge's anchor)."""
         table, self._train_table = self._train_table, None
-        dx0, coef, s = self._backward_core(grad_out, table)
+        dx0, coef, s = self._backward_core(gsd, table)
         return ops.mosasrec_emb_grad(dx0, s["out"], coef)
 
     @torch.no_grad()

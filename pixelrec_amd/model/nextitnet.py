@@ -26,7 +26,7 @@ import torch.nn as nn
 from .. import ops
 from ..utils.enum_type import InputType
 from .sasrec import SASRec
-from .seqcore import PxrError, SeqRecCore
+from .seqcore import SeqRecCore
 
 
 class ResidualBlock_b(nn.Module):
@@ -164,12 +164,9 @@ class NextItBlock:
         dxc = ops.linear_bwd_input(da, self._p(f"rb.{i}.c{which}.w").view(C, C * k))    # [B, L, C k]
         return ops.causal_col2im(dxc, k, dilation)
 
-    def _backward_core(self, grad_out, table):
-        s = self._saved
-        if s is None:
-            raise PxrError("backward() without a training-mode forward()")
+    def _backward_core(self, gsd, table):
+        s = self._take_saved()
         B, L, E = s["B"], self.max_seq_length, self.embedding_size
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         d, coef = ops.bpr_loss_bwd(s["pos"], s["neg"], table, s["items"], s["mask"], E, self.grad_scale, gsd)
         pend = []
         defer = ops.DeferredReductions()
@@ -186,9 +183,7 @@ class NextItBlock:
         self._after_input_grads(dx0, coef, s)
         ops.grouped_linear_bwd_weight(pend)        # every conv / final-layer weight and bias gradient of the step: one launch
         defer.flush()
-        self._saved = None
-        ops.counter_add(self._drop_dev, 1)
-        self._step_counter += 1
+        self._step_done()
         return dx0, coef, s
 
 

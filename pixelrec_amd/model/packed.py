@@ -1,9 +1,13 @@
 """What every model on the flat-buffer / hand-written-backward machinery shares (DESIGN.md "The packed-parameter base"):
 
   * `_Rows`, the parameter container with nn.Embedding's `weight` name;
+  * `_ActMLP`, the reference's MLPLayers parameter layout, and `linear_specs` / `linear_names` over a model's `_linears()`;
   * `TrainStep`, the one autograd bridge from `loss.backward()` to a model's `_backward_train`;
+  * `split_tail` / `split_planes` (the two input forms of the pair models), `dense_gemm` / `dense_scores` (the predict tail), `take_saved` and the
+    constructor checks `one_process`, `check_width16`, `hidden_sizes`;
   * `flat_layout` (pure) and `pack_flat`: the layout of the flat parameter buffer and the allocate / copy / re-point loop;
-  * `PackedModel`: a model that owns a flat buffer -- private state, `_ensure_packed`, `flat_parameters`, `_p`, `_buf`;
+  * `PackedModel`: a model that owns a flat buffer -- private state, `_ensure_packed`, `flat_parameters`, `_p`, `_buf`, the
+    step bracket (`_take_saved`, `_step_done`), the activation-epilogue Linear chain and the evaluation-cache hook;
   * `TableHooks` and `LazyTableModel`: the surface a lazy table optimizer (optim.PxrAdamW) drives, and the ONE
     [1 + rows, D] table buffer built from `table_parameter_spans()`.
 
@@ -20,6 +24,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..lib import PxrError
+from ..parallel import world_info
 from .basemodel import BaseModel
 
 
@@ -31,10 +36,112 @@ class _Rows(nn.Module):
         self.weight = nn.Parameter(torch.empty(n, d))
 
 
+class _ActMLP(nn.Module):
+    """MLPLayers(sizes, dropout, activation, bn=False) with the reference's module layout (mlp_layers.{3k: Dropout, 3k + 1:
+    Linear, 3k + 2: act_cls}); never called -- the kernels read its parameters."""
+
+    def __init__(self, sizes, act_cls, dropout=0.0):
+        super().__init__()
+        mods = []
+        for i, o in zip(sizes[:-1], sizes[1:]):
+            mods += [nn.Dropout(p=dropout), nn.Linear(i, o), act_cls()]
+        self.mlp_layers = nn.Sequential(*mods)
+
+
+def linear_specs(linears):
+    """[(flat-buffer key, reference path, Linear)] -> the `_flat_specs()` entries [(key.w, weight), (key.b, bias)]."""
+    return [spec for key, _, lin in linears for spec in ((key + ".w", lin.weight), (key + ".b", lin.bias))]
+
+
+def linear_names(linears):
+    """[(flat-buffer key, reference path, Linear)] -> the `rec_parameter_names()` entries {path.weight: key.w, path.bias: key.b}."""
+    out = {}
+    for key, path, _ in linears:
+        out[path + ".weight"] = key + ".w"
+        out[path + ".bias"] = key + ".b"
+    return out
+
+
+def one_process(model, what="this model"):
+    """The constructor guard of a model whose data-parallel exchange is not built."""
+    if world_info()[1] > 1:
+        raise NotImplementedError(f"{type(model).__name__} runs on one process: data parallelism is not built for {what}")
+
+
+def check_width16(D):
+    """embedding_size of a model whose kernels read rows in 16-byte vectors."""
+    if D <= 0 or D % 4 or D > 4096:
+        raise ValueError(f"embedding_size must be a positive multiple of 4, at most 4096 (16-byte vector accesses); got {D}")
+
+
+def hidden_sizes(hidden):
+    """config's `mlp_hidden_size` -> a list of ints: an int is a one-entry list, None is []."""
+    if isinstance(hidden, int):
+        hidden = [hidden]
+    return [int(h) for h in (hidden or [])]
+
+
+def _split_checked(profile, tail, n_tail, min_len, max_len, text):
+    if profile.dim() != 2 or tail.dim() != 2 or tail.shape != (profile.shape[0], n_tail) or not min_len <= profile.shape[1] <= max_len:
+        raise ValueError(text.format(profile=tuple(profile.shape), tail=tuple(tail.shape)))
+    return profile.contiguous(), tail.contiguous()
+
+
+def split_tail(input, n_tail, text, max_len=math.inf):
+    """The reference's single [B, L + n_tail] id tensor, or (profile [B, L], tail [B, n_tail]) -> contiguous (profile, tail),
+    1 <= L <= max_len.  `text` is the caller's own error text, with {profile} and {tail} where the two shapes go."""
+    if isinstance(input, (tuple, list)):
+        profile, tail = input
+        tail = tail.reshape(profile.shape[0], -1)
+    else:
+        profile, tail = input[:, :-n_tail], input[:, -n_tail:]
+    return _split_checked(profile, tail, n_tail, 1, max_len, text)
+
+
+def split_planes(input, name, pair_text, min_len=1):
+    """The reference's [B, 2, L + 1] id tensor -- plane 0 = [profile | positive], plane 1 = [profile | negative], the same profile
+    in both -- or (profile [B, L], target [B, 2]) -> contiguous (profile, target), L >= min_len.  `pair_text` is the caller's own
+    error text for a pair of the wrong shapes, with {profile} and {tail} where the shapes go."""
+    if isinstance(input, (tuple, list)):
+        profile, target = input
+        target = target.reshape(profile.shape[0], -1)
+    else:
+        if input.dim() != 3 or input.shape[1] != 2 or input.shape[2] < 2:
+            raise ValueError(f"{name}: expected [B, 2, L + 1] ids ([profile | positive], [profile | negative]), got {tuple(input.shape)}")
+        if not torch.equal(input[:, 0, :-1], input[:, 1, :-1]):
+            raise ValueError(f"{name}: the two planes of the [B, 2, L + 1] input must hold the same profile in their first L columns")
+        profile, target = input[:, 0, :-1], input[:, :, -1]
+    return _split_checked(profile, target, 2, min_len, math.inf, pair_text)
+
+
+def dense_gemm(q, feat):
+    """scores [B, N] = q feat^T in the library GEMM."""
+    B, D = q.shape
+    N = feat.shape[0]
+    scores = torch.empty(B, N, dtype=torch.float32, device=q.device)
+    ops.gemm(True, True, B, N, D, q, D, feat, D, scores, N, ops.EPI_NONE, use_ws=False)
+    return scores
+
+
+def dense_scores(q, feat):
+    """The tail of `predict`: scores [B, N] = q feat^T, then the bad-index flag -- an id outside the catalogue raises, like the
+    reference's indexing."""
+    scores = dense_gemm(q, feat)
+    ops.raise_on_bad_indices(q.device)
+    return scores
+
+
+def take_saved(model, *also):
+    """What the training forward left in `model._saved` for this backward (`also`: what else it must have left)."""
+    if model._saved is None or any(x is None for x in also):
+        raise PxrError("backward() without a training-mode forward()")
+    return model._saved
+
+
 class TrainStep(torch.autograd.Function):
     """Bridges `loss.backward()` to the hand-written backward chain: apply(anchor, model, *inputs).  The anchor is what makes
     the loss require a gradient; it receives whatever `_backward_train` returns -- None, except for the pixel model, whose
-    anchor is the visual encoder's output."""
+    anchor is the visual encoder's output.  `_backward_train` gets the upstream gradient as the [1] fp32 tensor the kernels read."""
 
     @staticmethod
     def forward(ctx, anchor, model, *inputs):
@@ -43,7 +150,8 @@ class TrainStep(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        return (ctx.model._backward_train(grad_out),) + (None,) * (1 + ctx.n_inputs)
+        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
+        return (ctx.model._backward_train(gsd),) + (None,) * (1 + ctx.n_inputs)
 
 
 def flat_layout(specs, align=1):
@@ -77,7 +185,8 @@ def pack_flat(specs, dev, align=1):
 class PackedModel(BaseModel):
     """A model whose trainable non-table parameters live in ONE flat fp32 buffer with a gradient twin (PxrAdamW's one launch).
     A subclass supplies `_flat_specs()` -> [(flat-buffer key, parameter)] and, where it needs them, `flat_align`,
-    `_first_flat_parameter()`, `_pack_tables(dev)` and `_after_pack(dev)`."""
+    `_first_flat_parameter()`, `_pack_tables(dev)`, `_after_pack(dev)` and `_drop_eval_cache()`.  Its `_forward_train` leaves
+    `_saved`; its `_backward_train(gsd)` opens with `_take_saved()` and closes with `_step_done()`."""
 
     flat_align = 1          # elements every tensor's start is rounded up to (flat_layout)
 
@@ -107,6 +216,18 @@ class PackedModel(BaseModel):
     def _after_pack(self, dev):
         """Hook: runs after every (re)pack -- whatever else follows the parameters to their device or goes stale with them."""
 
+    def _drop_eval_cache(self):
+        """Hook: drop what evaluation derived from the parameters -- after a repack, on train(True), before load_state_dict."""
+
+    def train(self, mode: bool = True):
+        if mode:
+            self._drop_eval_cache()
+        return super().train(mode)
+
+    def load_state_dict(self, state_dict, strict=True, **kwargs):
+        self._drop_eval_cache()
+        return super().load_state_dict(state_dict, strict=strict, **kwargs)
+
     def _ensure_packed(self):
         """(Re)build the buffers when the parameters moved (e.g. after .to(device))."""
         p, at = self._pack_probe()
@@ -121,6 +242,7 @@ class PackedModel(BaseModel):
         self._drop_dev = torch.full((1,), self._step_counter, dtype=torch.int64, device=dev)
         self._bufs = {}
         self._after_pack(dev)
+        self._drop_eval_cache()
 
     def flat_parameters(self):
         self._ensure_packed()
@@ -140,6 +262,37 @@ class PackedModel(BaseModel):
         if b is None or tuple(b.shape) != tuple(shape) or b.dtype != dtype:
             b = self._bufs[name] = (torch.zeros if zero else torch.empty)(*shape, dtype=dtype, device=self._flat.device)
         return b
+
+    # ---- the step bracket: the two counters are what graph.py snapshots and what seeds the dropout masks
+    def _take_saved(self):
+        """What the training forward left for this backward."""
+        return take_saved(self)
+
+    def _step_done(self, bumped=False):
+        """Close a backward pass: the device counter advances here unless a launch of the step already carried it (`bumped`)."""
+        self._saved = None
+        if not bumped:
+            ops.counter_add(self._drop_dev, 1)
+        self._step_counter += 1
+
+    # ---- Linears with an activation epilogue (activation and derivative in one pass), chained
+    def _act_chain(self, x, keys, act):
+        """x -> (activations, derivatives) of Linear `k` + `act` for k in keys, each reading the one before."""
+        acts, ders = [], []
+        for k in keys:
+            x, d = ops.linear_fwd(x, self._p(k + ".w"), self._p(k + ".b"), act=act)
+            acts.append(x)
+            ders.append(d)
+        return acts, ders
+
+    def _act_chain_bwd(self, dz_last, keys, ders):
+        """The gradient at the last Linear's output (before its activation) -> the same for every Linear of `keys`:
+        dz[i - 1] = (dz[i] W_i) * ders[i - 1].  The first Linear's input gradient is the caller's."""
+        dzs = [None] * len(keys)
+        dzs[-1] = dz_last
+        for i in range(len(keys) - 1, 0, -1):
+            dzs[i - 1] = ops.linear_bwd_input(dzs[i], self._p(keys[i] + ".w"), mul=ders[i - 1])
+        return dzs
 
 
 class TableHooks:

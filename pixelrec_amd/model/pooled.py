@@ -38,9 +38,9 @@ import torch.nn as nn
 
 from .. import ops
 from ..lib import PxrError
-from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .packed import LazyTableModel, TrainStep, _Rows
+from .packed import (LazyTableModel, TrainStep, _ActMLP, _Rows, check_width16, dense_scores, hidden_sizes, linear_names, linear_specs,
+                     one_process, split_planes, split_tail)
 
 
 def pool_queries(name, feat, item_seq, mean):
@@ -54,26 +54,7 @@ def pool_queries(name, feat, item_seq, mean):
     return q
 
 
-def pool_scores(q, feat):
-    """scores [B, N] = q feat^T in the library GEMM; an id outside the catalogue raises, like the reference's indexing."""
-    B, D = q.shape
-    N = feat.shape[0]
-    scores = torch.empty(B, N, dtype=torch.float32, device=q.device)
-    ops.gemm(True, True, B, N, D, q, D, feat, D, scores, N, ops.EPI_NONE, use_ws=False)
-    ops.raise_on_bad_indices(q.device)
-    return scores
-
-
-class _ReluMLP(nn.Module):
-    """MLPLayers(sizes, dropout) with the reference's module layout (mlp_layers.{3k: Dropout, 3k + 1: Linear, 3k + 2: ReLU});
-    never called -- the kernels read its parameters."""
-
-    def __init__(self, sizes, dropout):
-        super().__init__()
-        mods = []
-        for i, o in zip(sizes[:-1], sizes[1:]):
-            mods += [nn.Dropout(p=dropout), nn.Linear(i, o), nn.ReLU()]
-        self.mlp_layers = nn.Sequential(*mods)
+_PAIR_TEXT = "{name}: expected a profile [B, L] (L >= 1) and targets [B, 2] (positive, negative), got {{profile}} and {{tail}}"
 
 
 class _PooledPair(LazyTableModel):
@@ -84,16 +65,10 @@ class _PooledPair(LazyTableModel):
     flat_align = 4
 
     def _init_common(self, config, dataload):
-        name = type(self).__name__
-        if world_info()[1] > 1:
-            raise NotImplementedError(f"{name} runs on one process: data parallelism is not built for this model")
+        one_process(self)
         self.embedding_size = D = int(config["embedding_size"])
-        if D <= 0 or D % 4 or D > 4096:
-            raise ValueError(f"embedding_size must be a positive multiple of 4, at most 4096 (16-byte vector accesses); got {D}")
-        hidden = config["mlp_hidden_size"] if "mlp_hidden_size" in config else []
-        if isinstance(hidden, int):
-            hidden = [hidden]
-        self.mlp_hidden_size = [int(h) for h in (hidden or [])]
+        check_width16(D)
+        self.mlp_hidden_size = hidden_sizes(config["mlp_hidden_size"] if "mlp_hidden_size" in config else None)
         p = config["dropout_prob"] if "dropout_prob" in config else 0.0
         self.dropout_prob = float(p or 0.0)
         self.item_num = dataload.item_num
@@ -120,12 +95,6 @@ class _PooledPair(LazyTableModel):
         return {"item_embedding.weight": (1, 1 + self.item_num)}
 
     # ------------------------------------------------------------------------------------------ training
-    def _check_pair(self, profile, target):
-        if target.dim() != 2 or target.shape[1] != 2 or profile.dim() != 2 or profile.shape[1] < 1 or target.shape[0] != profile.shape[0]:
-            raise ValueError(f"{type(self).__name__}: expected a profile [B, L] (L >= 1) and targets [B, 2] (positive, negative), got "
-                             f"{tuple(profile.shape)} and {tuple(target.shape)}")
-        return profile.contiguous(), target.contiguous()
-
     def forward(self, input):
         if not self.training:
             raise PxrError(f"{type(self).__name__}.forward is the training loss; use encode_last / predict to score")
@@ -167,12 +136,9 @@ class _PooledPair(LazyTableModel):
         occurrence is written (tools/pool_bench.py overrides this with the materialised form to price the difference)."""
         return ops.pool_table_grad(gidx, B, L, G, w, self._table.shape[0], out=self._sparse_rows(B * (L + 2)))
 
-    def _backward_train(self, grad_out):
-        s = self._saved
-        if s is None:
-            raise PxrError("backward() without a training-mode forward()")
+    def _backward_train(self, gsd):
+        s = self._take_saved()
         B, L, D = s["B"], s["L"], self.embedding_size
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         G = self._buf("G", (3 * B, D))
         if not self.n_layers:
             ops.pool_pair_bwd(self._table, s["rows"], B, L, s["U"], s["coef"], self.grad_scale, gsd, G=G)
@@ -199,9 +165,7 @@ class _PooledPair(LazyTableModel):
                     dz = ops.mul(dx, saved[k - 1][1], out=dx)
             ops.grouped_linear_bwd_weight(problems)
         self.sparse_table_grad = self._table_grad(s["gidx"], B, L, G, s["w"])
-        self._saved = None
-        ops.counter_add(self._drop_dev, 1)
-        self._step_counter += 1
+        self._step_done()
 
     # ------------------------------------------------------------------------------------------ evaluation
     @torch.no_grad()
@@ -230,7 +194,7 @@ class _PooledPair(LazyTableModel):
         feat = item_feature if item_feature is not None else self.compute_item_all()
         feat = (feat if feat.is_contiguous() else feat.contiguous()).data
         _, q = self.encode_last(item_seq, feat)
-        return pool_scores(q, feat)
+        return dense_scores(q, feat)
 
 
 class DSSM(_PooledPair):
@@ -252,37 +216,25 @@ class DSSM(_PooledPair):
         self.out_size = D
         self.item_embedding = _Rows(self.item_num, D)
         self.user_embedding = self.item_embedding           # dssm.py:25: one table under two names
-        self.mlp_layers = _ReluMLP(hidden, self.dropout_prob)
+        self.mlp_layers = _ActMLP(hidden, nn.ReLU, self.dropout_prob)    # MLPLayers(mlp_hidden_size, dropout_prob)
         self._init_weights()
 
     def _linears(self):
         return [(f"l{k}", f"mlp_layers.mlp_layers.{3 * k + 1}", self.mlp_layers.mlp_layers[3 * k + 1]) for k in range(self.n_layers)]
 
     def _flat_specs(self):
-        out = []
-        for key, _, lin in self._linears():
-            out += [(key + ".w", lin.weight), (key + ".b", lin.bias)]
-        return out
+        return linear_specs(self._linears())
 
     def rec_parameter_names(self):
         """{reference parameter name: flat-buffer key} in the reference's registration order (optim.native_to_torch_state): the
         table first (its state is the table buffer's: None), then the MLP.  `user_embedding.weight` is `item_embedding.weight`
         and is not a parameter of its own."""
-        out = {"item_embedding.weight": None}
-        for key, path, _ in self._linears():
-            out[path + ".weight"] = key + ".w"
-            out[path + ".bias"] = key + ".b"
-        return out
+        return {"item_embedding.weight": None, **linear_names(self._linears())}
 
     def _split_input(self, input):
-        if isinstance(input, (tuple, list)):
-            profile, target = input
-            target = target.reshape(profile.shape[0], -1)
-        else:
-            if input.dim() != 2 or input.shape[1] < 3:
-                raise ValueError(f"DSSM: expected [B, L + 2] ids (profile, positive, negative), got {tuple(input.shape)}")
-            profile, target = input[:, :-2], input[:, -2:]
-        return self._check_pair(profile, target)
+        if torch.is_tensor(input) and (input.dim() != 2 or input.shape[1] < 3):
+            raise ValueError(f"DSSM: expected [B, L + 2] ids (profile, positive, negative), got {tuple(input.shape)}")
+        return split_tail(input, 2, _PAIR_TEXT.format(name="DSSM"))
 
 
 class FM(_PooledPair):
@@ -304,13 +256,4 @@ class FM(_PooledPair):
         return {"item_embedding.weight": None}
 
     def _split_input(self, input):
-        if isinstance(input, (tuple, list)):
-            profile, target = input
-            target = target.reshape(profile.shape[0], -1)
-        else:
-            if input.dim() != 3 or input.shape[1] != 2 or input.shape[2] < 2:
-                raise ValueError(f"FM: expected [B, 2, L + 1] ids ([profile | positive], [profile | negative]), got {tuple(input.shape)}")
-            if not torch.equal(input[:, 0, :-1], input[:, 1, :-1]):
-                raise ValueError("FM: the two planes of the [B, 2, L + 1] input must hold the same profile in their first L columns")
-            profile, target = input[:, 0, :-1], input[:, :, -1]
-        return self._check_pair(profile, target)
+        return split_planes(input, "FM", _PAIR_TEXT.format(name="FM"))

@@ -272,8 +272,8 @@ class SASRec(TableHooks, SeqRecCore):
         if hook is not None:
             hook()
 
-    def _backward_train(self, grad_out):
-        self._backward_core(grad_out, self.item_embedding.weight.data)
+    def _backward_train(self, gsd):
+        self._backward_core(gsd, self.item_embedding.weight.data)
 
     # ------------------------------------------------------------------------------------------ inference
     @torch.no_grad()

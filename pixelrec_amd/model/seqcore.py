@@ -546,19 +546,16 @@ class SeqRecCore(PackedModel):
         return loss
 
     # ------------------------------------------------------------------------------------------ backward
-    def _backward_core(self, grad_out, table):
+    def _backward_core(self, gsd, table):
         """Backward of _forward_core: fills the flat gradient buffer and returns (dx0 [B,L,D] = gradient w.r.t. the
         gathered input rows, coef [B,L] = d loss / d(pos_score - neg_score), saved dict)."""
-        s = self._saved
-        if s is None:
-            raise PxrError("backward() without a training-mode forward()")
+        s = self._take_saved()
         B, L, D, H = s["B"], self.max_seq_length, self.hidden_size, self.n_heads
         d = D // H
         T = B * L
         seed, ph, pa = s["seed"], s["ph"], s["pa"]
         sdv = self._drop_dev
         g = lambda name, span=1: self._p(name, grad=True, span=span)
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         # Weight / bias gradients are off the critical path (only the optimizer consumes them): they are collected
         # and computed by ONE grouped launch at the end (all tiles of all layers in one grid: no split-K, no
         # separate bias reductions), or -- overlap_weight_grads -- per layer on a side stream.
@@ -713,10 +710,7 @@ class SeqRecCore(PackedModel):
                              [ops.ATTN_STAT_SLOTS if q in att else n_parts for q in range(3 * self.n_layers)],
                              [T] * (3 * self.n_layers), site_w, self._DU_BOUND)
                 sites.seeded_for = geom
-            self._saved = None
-            if not bumped:
-                ops.counter_add(self._drop_dev, 1)
-            self._step_counter += 1
+            self._step_done(bumped)
             return dx0, coef, s
         for i in reversed(range(self.n_layers)):
             a = s["layers"][i]
@@ -769,9 +763,6 @@ class SeqRecCore(PackedModel):
             self._dw_join, self._dw_keep = side, forked
             if not self.defer_weight_grad_join:
                 self.join_weight_grads()
-        self._saved = None
-        if not bumped:
-            ops.counter_add(self._drop_dev, 1)
-        self._step_counter += 1
+        self._step_done(bumped)
         return dx0, coef, s
 

@@ -246,10 +246,10 @@ class ShardedSASRec(SASRec):
         block[1:] = mine
         return block
 
-    def _backward_train(self, grad_out):
+    def _backward_train(self, gsd):
         if not self._sharded:
-            return super()._backward_train(grad_out)
-        self._backward_core(grad_out, self._block)
+            return super()._backward_train(gsd)
+        self._backward_core(gsd, self._block)
         self._block = None
 
     # ------------------------------------------------------------------------------------------ inference

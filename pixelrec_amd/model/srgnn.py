@@ -36,10 +36,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..lib import PxrError
-from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .packed import PackedModel, TableHooks, TrainStep
+from .packed import PackedModel, TableHooks, TrainStep, dense_scores, one_process
 
 
 class _GNN(nn.Module):
@@ -66,8 +64,7 @@ class SRGNN(TableHooks, PackedModel):
 
     def __init__(self, config, dataload):
         super().__init__()
-        if world_info()[1] > 1:
-            raise NotImplementedError("SRGNN runs on one process: data parallelism is not built for the graph models")
+        one_process(self, "the graph models")
         self.hidden_size = config["embedding_size"]
         self.step = int(config["step"])
         self.item_num = dataload.item_num
@@ -213,16 +210,13 @@ class SRGNN(TableHooks, PackedModel):
                                out_pad=out_pad, coef=coef)
         return loss
 
-    def _backward_train(self, grad_out):
-        s = self._saved
-        if s is None:
-            raise PxrError("backward() without a training-mode forward()")
+    def _backward_train(self, gsd):
+        s = self._take_saved()
         B, L, D, S = s["B"], self.max_seq_length, self.hidden_size, self.step
         BL = B * L
         dev = s["cat"].device
         table = self.embedding.weight.data
         g = lambda name, span=1: self._p(name, grad=True, span=span)
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         dout = self._buf("dout", (B, D))
         coef_pad = self._buf("coef_pad", (B, L), zero=True)
         ops.srgnn_pair_bwd(table, s["target"], s["coef"], dout, D, self.grad_scale, gsd, coef_out=coef_pad, coef_stride=L)
@@ -257,9 +251,7 @@ class SRGNN(TableHooks, PackedModel):
         sp = s["sp"]
         ops.sasrec_occ_segsum(self._occ_ws, dH.view(B, L, D), s["out_pad"], coef_pad, self.item_num, sp, 1.0, ws2=self._occ_ws2)
         self.sparse_table_grad = sp
-        self._saved = None
-        ops.counter_add(self._drop_dev, 1)
-        self._step_counter += 1
+        self._step_done()
 
     # ------------------------------------------------------------------------------------------ evaluation
     @torch.no_grad()
@@ -288,12 +280,7 @@ class SRGNN(TableHooks, PackedModel):
         """scores [B, N] = seq_output item_feature^T (srgnn.py predict: the node rows are read from item_feature)."""
         feat = item_feature if item_feature.is_contiguous() else item_feature.contiguous()
         _, out = self.encode_last(item_seq, feat)
-        B, D = out.shape
-        N = feat.shape[0]
-        scores = torch.empty(B, N, dtype=torch.float32, device=out.device)
-        ops.gemm(True, True, B, N, D, out, D, feat, D, scores, N, ops.EPI_NONE, use_ws=False)
-        ops.raise_on_bad_indices(out.device)     # an id outside the catalogue raises, like the reference's indexing
-        return scores
+        return dense_scores(out, feat)
 
     @torch.no_grad()
     def compute_item_all(self):

@@ -39,9 +39,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..lib import PxrError
-from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .packed import LazyTableModel, TrainStep, _Rows
+from .packed import LazyTableModel, TrainStep, _Rows, dense_gemm, one_process
 
 
 class VBPR(LazyTableModel):
@@ -51,8 +50,7 @@ class VBPR(LazyTableModel):
 
     def __init__(self, config, dataload):
         super().__init__()
-        if world_info()[1] > 1:
-            raise NotImplementedError("VBPR runs on one process: data parallelism is not built for this model")
+        one_process(self)
         self.mlp_hidden_size = config["mlp_hidden_size"] if "mlp_hidden_size" in config else None      # read and unused (vbpr.py:12-13)
         self.dropout_prob = config["dropout_prob"] if "dropout_prob" in config else None
         self.embedding_size = int(config["embedding_size"]) // 2
@@ -126,21 +124,16 @@ class VBPR(LazyTableModel):
         self._saved = dict(B=B, rows=rows, coef=coef, x=x, e=e)
         return loss
 
-    def _backward_train(self, grad_out):
-        s = self._saved
-        if s is None:
-            raise PxrError("backward() without a training-mode forward()")
+    def _backward_train(self, gsd):
+        s = self._take_saved()
         B, Dh = s["B"], self.embedding_size
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         sp = self._sparse_rows(4 * B)
         de, csign = self._buf("de", (2 * B, Dh)), self._buf("csign", (2 * B,))
         ops.vbpr_pair_bwd(self._table, s["rows"], s["e"], s["coef"], B, de, csign, sp, self.grad_scale, gsd)
         ops.vbpr_bias_grad(s["x"], csign, self._p("wb", grad=True).view(-1))
         ops.grouped_linear_bwd_weight([(de, s["x"], self._p("W", grad=True), None)])
         self.sparse_table_grad = sp
-        self._saved = None
-        ops.counter_add(self._drop_dev, 1)
-        self._step_counter += 1
+        self._step_done()
 
     # ------------------------------------------------------------------------------------------ evaluation
     @torch.no_grad()
@@ -183,13 +176,10 @@ class VBPR(LazyTableModel):
         self.sync_table()
         feat = feat if feat.is_contiguous() else feat.contiguous()
         user = user.reshape(-1).contiguous()
-        B, Dh, N = user.numel(), self.embedding_size, self.item_num
+        B = user.numel()
         rows = ops.vbpr_rows(user, None, self.user_num, self.item_num)
         u = ops.embed_gather(self._table, rows)                                    # [2B, Dh]: id rows | modal rows
         lo, hi = self.table_parameter_spans()["item_id_embedding.weight"]
-        s_id = torch.empty(B, N, dtype=torch.float32, device=u.device)
-        s_mo = torch.empty(B, N, dtype=torch.float32, device=u.device)
-        ops.gemm(True, True, B, N, Dh, u[:B], Dh, self._table[lo:hi], Dh, s_id, N, ops.EPI_NONE, use_ws=False)
-        ops.gemm(True, True, B, N, Dh, u[B:], Dh, feat, Dh, s_mo, N, ops.EPI_NONE, use_ws=False)
+        s_id, s_mo = dense_gemm(u[:B], self._table[lo:hi]), dense_gemm(u[B:], feat)
         ops.raise_on_bad_indices(u.device)     # a user id outside the table raises, like the reference's indexing
         return s_id.add_(s_mo).add_(self.total_visual_bias)

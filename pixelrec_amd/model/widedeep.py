@@ -59,21 +59,9 @@ import torch.nn as nn
 
 from .. import ops
 from ..lib import PxrError
-from ..parallel import world_info
 from ..utils.enum_type import InputType
-from .packed import LazyTableModel, TrainStep, _Rows
-
-
-class _MLP(nn.Module):
-    """MLPLayers(sizes, dropout, activation='relu', bn=False) with the reference's module layout (mlp_layers.{3k: Dropout, 3k + 1:
-    Linear, 3k + 2: ReLU}); never called -- the kernels read its parameters."""
-
-    def __init__(self, sizes):
-        super().__init__()
-        mods = []
-        for i, o in zip(sizes[:-1], sizes[1:]):
-            mods += [nn.Dropout(p=0.0), nn.Linear(i, o), nn.ReLU()]
-        self.mlp_layers = nn.Sequential(*mods)
+from .packed import (LazyTableModel, TrainStep, _ActMLP, _Rows, check_width16, hidden_sizes, linear_names, linear_specs, one_process,
+                     split_planes)
 
 
 class WideDeep(LazyTableModel):
@@ -83,15 +71,10 @@ class WideDeep(LazyTableModel):
 
     def __init__(self, config, dataload):
         super().__init__()
-        if world_info()[1] > 1:
-            raise NotImplementedError("WideDeep runs on one process: data parallelism is not built for this model")
+        one_process(self)
         self.embedding_size = D = int(config["embedding_size"])
-        if D <= 0 or D % 4 or D > 4096:
-            raise ValueError(f"embedding_size must be a positive multiple of 4, at most 4096 (16-byte vector accesses); got {D}")
-        hidden = config["mlp_hidden_size"] if "mlp_hidden_size" in config else None
-        if isinstance(hidden, int):
-            hidden = [hidden]
-        self.mlp_hidden_size = hidden = [int(h) for h in (hidden or [])]
+        check_width16(D)
+        self.mlp_hidden_size = hidden = hidden_sizes(config["mlp_hidden_size"] if "mlp_hidden_size" in config else None)
         if not hidden or any(h <= 0 or h % 4 or h > 4096 for h in hidden):
             raise ValueError(f"mlp_hidden_size must hold one or more positive multiples of 4, at most 4096 each (widedeep.py:33 reads "
                              f"its last entry; the weight-gradient GEMMs' vector accesses); got {hidden}")
@@ -108,7 +91,7 @@ class WideDeep(LazyTableModel):
         self.wide_item_embedding = _Rows(I, 1)      # nn.Embedding(padding_idx=0): the init overwrites row 0 (widedeep.py:41-43)
         self.wide_bias = nn.Parameter(torch.zeros(1))
         self.deep_item_embedding = _Rows(I, D)
-        self.mlp_layers = _MLP([(L + 1) * D] + hidden)
+        self.mlp_layers = _ActMLP([(L + 1) * D] + hidden, nn.ReLU)       # MLPLayers(sizes, dropout, activation='relu', bn=False)
         self.deep_predict_layer = nn.Linear(hidden[-1], 1)
         for mod in self.modules():
             if isinstance(mod, (nn.Linear, _Rows)):
@@ -116,6 +99,7 @@ class WideDeep(LazyTableModel):
                 if getattr(mod, "bias", None) is not None:
                     nn.init.zeros_(mod.bias.data)
         self._eval_cache = None
+        self._mlp_keys = [f"l{i}" for i in range(len(hidden))]     # the flat-buffer keys of the MLP's Linears
 
     # ------------------------------------------------------------------------------------------ packing
     def _linears(self):
@@ -127,57 +111,31 @@ class WideDeep(LazyTableModel):
         return out
 
     def _flat_specs(self):
-        out = [("wide.w", self.wide_item_embedding.weight), ("wide.b", self.wide_bias)]
-        for key, _, lin in self._linears():
-            out += [(key + ".w", lin.weight), (key + ".b", lin.bias)]
-        return out
+        return [("wide.w", self.wide_item_embedding.weight), ("wide.b", self.wide_bias)] + linear_specs(self._linears())
 
     def rec_parameter_names(self):
         """{reference parameter name: flat-buffer key} in the order the reference's .parameters() yields them (a module's own
         parameter, wide_bias, comes before its submodules'; optim.native_to_torch_state); the deep table maps to None -- its state is
         the table buffer's (optim.table_spans)."""
-        out = {"wide_bias": "wide.b", "wide_item_embedding.weight": "wide.w", "deep_item_embedding.weight": None}
-        for key, path, _ in self._linears():
-            out[path + ".weight"] = key + ".w"
-            out[path + ".bias"] = key + ".b"
-        return out
+        return {"wide_bias": "wide.b", "wide_item_embedding.weight": "wide.w", "deep_item_embedding.weight": None,
+                **linear_names(self._linears())}
 
     def table_parameter_spans(self):
         """Rows of the table buffer the deep table occupies (optim.table_spans)."""
         return {"deep_item_embedding.weight": (1, 1 + self.item_num)}
 
-    def _after_pack(self, dev):
-        self._eval_cache = None
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        self._eval_cache = None
-        return super().load_state_dict(state_dict, strict=strict, **kwargs)
-
-    def train(self, mode: bool = True):
-        if mode:
-            self._eval_cache = None            # the per-item term T goes when training resumes
-        return super().train(mode)
+    def _drop_eval_cache(self):
+        self._eval_cache = None                # the per-item term T goes when training resumes
 
     # ------------------------------------------------------------------------------------------ training
     def _split_input(self, input):
         """The reference's [B, 2, L + 1] tensor, or (profile [B, L], target [B, 2]) -> contiguous (profile, target)."""
-        if isinstance(input, (tuple, list)):
-            profile, target = input
-            target = target.reshape(profile.shape[0], -1)
-        else:
-            if input.dim() != 3 or input.shape[1] != 2 or input.shape[2] < 2:
-                raise ValueError(f"WideDeep: expected [B, 2, L + 1] ids ([profile | positive], [profile | negative]), got "
-                                 f"{tuple(input.shape)}")
-            if not torch.equal(input[:, 0, :-1], input[:, 1, :-1]):
-                raise ValueError("WideDeep: the two planes of the [B, 2, L + 1] input must hold the same profile in their first L columns")
-            profile, target = input[:, 0, :-1], input[:, :, -1]
-        if target.dim() != 2 or target.shape[1] != 2 or profile.dim() != 2 or target.shape[0] != profile.shape[0]:
-            raise ValueError(f"WideDeep: expected a profile [B, L] and targets [B, 2] (positive, negative), got {tuple(profile.shape)} "
-                             f"and {tuple(target.shape)}")
+        profile, target = split_planes(input, "WideDeep", "WideDeep: expected a profile [B, L] and targets [B, 2] (positive, negative), got "
+                                                          "{profile} and {tail}", min_len=0)
         if profile.shape[1] != self.max_seq_length:
             raise ValueError(f"WideDeep: the profile must have MAX_ITEM_LIST_LENGTH = {self.max_seq_length} positions (the first "
                              f"Linear is [(L + 1) D -> h_1]), got {profile.shape[1]}")
-        return profile.contiguous(), target.contiguous()
+        return profile, target
 
     def forward(self, input):
         if not self.training:
@@ -203,13 +161,11 @@ class WideDeep(LazyTableModel):
         ops.gemm(True, True, 2 * B, h1, D, xt, D, W1t, ld, zt, h1)
         return ops.wd_join(zh, zt, self._p("l0.b"), a1=a1, der=der)
 
-    def _deeper(self, x, acts=None, ders=None):
-        for i in range(1, len(self.mlp_hidden_size)):
-            x, d = ops.linear_fwd(x, self._p(f"l{i}.w"), self._p(f"l{i}.b"), act="relu")
-            if acts is not None:
-                acts.append(x)
-                ders.append(d)
-        return x
+    def _deeper(self, a1, der1=None):
+        """The first layer's activation (and derivative) -> (activations, derivatives) of every layer: the Linears after the first
+        are library GEMMs with the ReLU epilogue."""
+        acts, ders = self._act_chain(a1, self._mlp_keys[1:], "relu")
+        return [a1] + acts, [der1] + ders
 
     def _forward_train(self, profile, target):
         B, L = profile.shape
@@ -222,29 +178,23 @@ class WideDeep(LazyTableModel):
         xh, xt = emb[:B * L].view(B, L * D), emb[B * L:]
         a1, der = self._first_layer(xh, xt, a1=self._buf("a1", (2 * B, h1)), der=self._buf("der1", (2 * B, h1)),
                                     zh=self._buf("zh", (B, h1)), zt=self._buf("zt", (2 * B, h1)))
-        acts, ders = [a1], [der]
-        self._deeper(a1, acts, ders)
+        acts, ders = self._deeper(a1, der)
         loss, head = ops.wd_head_fwd(acts[-1], self._p("pred.w").view(-1), self._p("wide.w").view(-1), target,
                                      head=self._buf("head", (1 + 2 * B,)))
         self._saved = dict(B=B, L=L, target=target, gidx=gidx, xh=xh, xt=xt, acts=acts, ders=ders, head=head)
         return loss
 
-    def _backward_train(self, grad_out):
-        s = self._saved
-        if s is None:
-            raise PxrError("backward() without a training-mode forward()")
+    def _backward_train(self, gsd):
+        s = self._take_saved()
         B, L, D = s["B"], s["L"], self.embedding_size
         n, LD = B * (L + 2), L * D
         nl, h1 = len(self.mlp_hidden_size), self.mlp_hidden_size[0]
-        gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         G = lambda k: self._p(k, grad=True)
         acts, ders = s["acts"], s["ders"]
-        dzs = [None] * nl
-        dzs[-1] = ops.wd_head_bwd(acts[-1], ders[-1], self._p("pred.w").view(-1), s["target"], s["head"], G("pred.w").view(-1),
-                                  G("pred.b"), G("wide.w").view(-1), G("wide.b"), self.grad_scale, gsd,
-                                  dz=self._buf("dzl", (2 * B, self.mlp_hidden_size[-1])))
-        for i in range(nl - 1, 0, -1):
-            dzs[i - 1] = ops.linear_bwd_input(dzs[i], self._p(f"l{i}.w"), mul=ders[i - 1])
+        dzl = ops.wd_head_bwd(acts[-1], ders[-1], self._p("pred.w").view(-1), s["target"], s["head"], G("pred.w").view(-1),
+                              G("pred.b"), G("wide.w").view(-1), G("wide.b"), self.grad_scale, gsd,
+                              dz=self._buf("dzl", (2 * B, self.mlp_hidden_size[-1])))
+        dzs = self._act_chain_bwd(dzl, self._mlp_keys, ders)
         dz1 = dzs[0]
         dzh = ops.wd_join_bwd(dz1, dzh=self._buf("dzh", (B, h1)))
         # dXh [B, L D] and dXt [2 B, D] straight into the gradient rows, in occurrence order (history (b, l), then target 2 b + c)
@@ -262,9 +212,7 @@ class WideDeep(LazyTableModel):
             ops.grouped_linear_bwd_weight([(dzs[i], acts[i - 1], G(f"l{i}.w"), G(f"l{i}.b")) for i in range(1, nl)])
         # the table gradient: stable sort of the occurrence rows + segmented sum (id 0 = the padding item: dropped)
         self.sparse_table_grad = ops.embed_grad_rows(s["gidx"], occ, self._table.shape[0], out=self._sparse_rows(n))
-        self._saved = None
-        ops.counter_add(self._drop_dev, 1)
-        self._step_counter += 1
+        self._step_done()
 
     # ------------------------------------------------------------------------------------------ evaluation
     @torch.no_grad()
@@ -328,8 +276,8 @@ class WideDeep(LazyTableModel):
 
     def _tail(self, a1):
         """a1 [M, h1] the first layer's activations -> the deep output [M] (deeper Linears: library GEMMs; the predict layer)."""
-        x = self._deeper(a1)
-        return x @ self._p("pred.w").view(-1) + self._p("pred.b")
+        acts, _ = self._deeper(a1)
+        return acts[-1] @ self._p("pred.w").view(-1) + self._p("pred.b")
 
     @torch.no_grad()
     def predict(self, item_seq, item_feature=None):

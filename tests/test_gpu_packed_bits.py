@@ -7,7 +7,7 @@ the third step and a flush, the u32 checksums of the flat buffer, the flat gradi
 
 The recorder runs every case twice.  A case whose two runs on the recording build differ in any bit is listed under
 "first_step_only" in the golden file and compared on `_views`, keys and the first loss only; the families whose sources promise
-run-to-run identity (MF, VBPR, ACF, DIN, CuratorNet) may not be listed (asserted below).
+run-to-run identity (MF, VBPR, ACF, DIN, CuratorNet, WideDeep, DSSM, FM) may not be listed (asserted below).
 
 Cases: each family at the shape, the weights and the batches of its own fixture under tests/golden/ (built by the `_gold_model`
 helpers of its GPU test):
@@ -21,7 +21,17 @@ helpers of its GPU test):
   * curatornet aligned, no table;
   * srgnn      step 2: `_p(..., span=2)` fused views;
   * lightgcn   three layers: the flat buffer is the table;
-  * sasrec     two layers (SeqRecCore's pack)."""
+  * sasrec     two layers (SeqRecCore's pack);
+  * widedeep   the wide table and its bias in the flat buffer, the deep table lazy;
+  * dssm/plain, fm   no flat parameter: pooling fused with the pair head;
+  * dssm/mlp   hidden [8, 12, 8] with dropout_prob 0.25: the device step counter decides the second and third steps' masks;
+  * gru4rec, nextitnet, lightsans, bert4rec   the sequence blocks on SeqRecCore's bracket (their fixture's one batch three times
+               where it holds only one).
+
+Every case also records "steps": [m._step_counter, int(m._drop_dev)] after the last step -- the host and the device count of
+completed backward passes, [3, 3] ([2, 2] for mf/reload's second model) -- compared in full for a "first_step_only" case too.
+The second group of cases and the "steps" field were recorded on the build of the commit BEFORE the step bracket
+(`_take_saved` / `_step_done`), the Linear-stack helpers and the input, scoring and evaluation-cache helpers moved into packed.py."""
 import json
 import os
 import sys
@@ -36,7 +46,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "packed_model_bits.json")
 STEPS = 3
-MUST_BE_FULL = ("mf/plain", "mf/towers", "mf/reload", "vbpr", "acf", "din", "curatornet")
+MUST_BE_FULL = ("mf/plain", "mf/towers", "mf/reload", "vbpr", "acf", "din", "curatornet", "widedeep", "dssm/plain", "dssm/mlp", "fm")
 
 
 def _gold(name):
@@ -110,8 +120,55 @@ def _sasrec_model(tmp, dev="cuda"):
     return T._model(meta, dev=dev)[0].train()
 
 
+def _widedeep_model(tmp):
+    from tests import test_gpu_widedeep as T
+
+    return T._gold_model(_gold("widedeep"))
+
+
+def _pool_model(fixture, p=0.0):
+    def make(tmp):
+        from tests import test_gpu_pool as T
+
+        kind, hidden = T.CASES[fixture + "_tiny"]
+        return T._gold_model(kind, hidden, _gold(fixture), p=p)
+    return make
+
+
+def _gru4rec_model(tmp):
+    from pixelrec_amd.model import GRU4Rec
+    from tests import test_gpu_gru4rec as T
+
+    m = GRU4Rec(T._config(), type("DL", (), {"item_num": T.N})())
+    m.load_state_dict({k[6:]: torch.from_numpy(T.G[k]) for k in T.G.files if k.startswith("param/")}, strict=True)
+    return m.cuda().train()
+
+
+def _nextitnet_model(tmp):
+    from pixelrec_amd.model import NextItNet
+    from tests import test_gpu_nextitnet as T
+
+    m = NextItNet(T._config(False), type("DL", (), {"item_num": T.N})())
+    m.load_state_dict({k[12:]: torch.from_numpy(T.G[k]) for k in T.G.files if k.startswith("plain/param/")}, strict=True)
+    return m.cuda().train()
+
+
+def _lightsans_model(tmp):
+    from tests import test_gpu_lightsans as T
+
+    return T._model(_gold("lightsans"), 2)
+
+
+def _bert4rec_model(tmp):
+    from tests import test_gpu_bert4rec as T
+
+    return T._model(*T._golden())[0].train()
+
+
 MODELS = {"mf/plain": _mf_model("c0"), "mf/towers": _mf_model("c1"), "vbpr": _vbpr_model, "acf": _acf_model, "din": _din_model,
-          "curatornet": _curatornet_model, "srgnn": _srgnn_model, "lightgcn": _lightgcn_model, "sasrec": _sasrec_model}
+          "curatornet": _curatornet_model, "srgnn": _srgnn_model, "lightgcn": _lightgcn_model, "sasrec": _sasrec_model, "widedeep": _widedeep_model,
+          "dssm/plain": _pool_model("dssm"), "dssm/mlp": _pool_model("dssm_mlp", p=0.25), "fm": _pool_model("fm"),
+          "gru4rec": _gru4rec_model, "nextitnet": _nextitnet_model, "lightsans": _lightsans_model, "bert4rec": _bert4rec_model}
 CASES = sorted(list(MODELS) + ["mf/reload"])
 
 
@@ -150,6 +207,27 @@ def _training(name, m):
         return _adamw(m, lr=1e-2), [_batch(_gold("srgnn"), s) for s in range(STEPS)], lambda m: m.embedding.weight.data
     if name == "lightgcn":
         return _adamw(m), _pairs(_gold("lightgcn")), lambda m: m.item_embedding.weight.data
+    if name == "widedeep":
+        from tests.test_gpu_widedeep import _opt, _split
+
+        g = _gold("widedeep")
+        return _opt(m), [_split(torch.from_numpy(g["rows"][s]).cuda(), m.max_seq_length) for s in range(STEPS)], _lazy_table
+    if name in ("dssm/plain", "dssm/mlp", "fm"):
+        from tests.test_gpu_pool import _inp, _opt
+
+        g = _gold({"dssm/plain": "dssm", "dssm/mlp": "dssm_mlp", "fm": "fm"}[name])
+        return _opt(m), [_inp(type(m).__name__, g["rows"][s]) for s in range(STEPS)], _lazy_table
+    if name in ("gru4rec", "nextitnet"):
+        g = _gold(name)
+        batch = (torch.from_numpy(g["items"]).cuda(), torch.from_numpy(g["masked_index"]).cuda())
+        return _adamw(m), [batch] * STEPS, lambda m: m.item_embedding.weight.data
+    if name == "lightsans":
+        g = _gold("lightsans")
+        return _adamw(m), [torch.from_numpy(g[f"b{s}.items"]).cuda() for s in range(STEPS)], lambda m: m.item_embedding.weight.data
+    if name == "bert4rec":
+        z = _gold("bert4rec")
+        batches = [(torch.from_numpy(z["adamw.items"][s]).cuda(), torch.from_numpy(z["adamw.masks"][s]).cuda()) for s in range(STEPS)]
+        return _adamw(m, lr=1e-4), batches, lambda m: m.item_embedding.weight.data
     from tests.golden_util import load_case
 
     _, z = load_case("tiny")
@@ -188,7 +266,8 @@ def _record(m, opt, losses, table_of):
     if table_of is not None:
         sums["table"] = _u32_sum(table_of(m))
     return {"views": {k: [int(off), int(n), [int(x) for x in shape]] for k, (off, n, shape) in m._views.items()},
-            "keys": list(m.state_dict().keys()), "loss_bits": losses, "sums": sums}
+            "keys": list(m.state_dict().keys()), "loss_bits": losses, "sums": sums,
+            "steps": [int(m._step_counter), int(m._drop_dev)]}
 
 
 def run_case(name):
@@ -228,6 +307,7 @@ def test_layout_keys_and_training_bits_are_kept(name, golden):
     print(name, json.dumps(got, sort_keys=True))
     assert got["views"] == want["views"]
     assert got["keys"] == want["keys"]
+    assert got["steps"] == want["steps"] == [len(got["loss_bits"])] * 2
     if name in golden["first_step_only"]:
         assert got["loss_bits"][0] == want["loss_bits"][0]
         return

@@ -8,8 +8,8 @@ import torch
 
 from tests import test_gpu_packed_bits as P
 
-LAZY_TABLE = {"mf/plain", "mf/towers", "vbpr", "acf", "din"}
-ALIGNED = {"acf", "din", "curatornet"}
+LAZY_TABLE = {"mf/plain", "mf/towers", "vbpr", "acf", "din", "widedeep", "dssm/plain", "dssm/mlp", "fm"}
+ALIGNED = {"acf", "din", "curatornet", "widedeep", "dssm/plain", "dssm/mlp", "fm"}
 
 
 @pytest.fixture(scope="module")
@@ -41,7 +41,7 @@ def test_layout_and_probed_members(name, golden, on_cpu, tmp_path):
     assert hasattr(m, "running_state_buffers") == name.startswith("mf/")
     assert hasattr(m, "split_flat_table_groups") == (name == "vbpr")
     assert hasattr(m, "item_table_attr") == (name == "srgnn")
-    assert hasattr(m, "rec_parameter_names") == (name != "sasrec")
+    assert hasattr(m, "rec_parameter_names") == (name not in ("sasrec", "bert4rec"))
     assert hasattr(m, "sparse_table_grad") == hasattr(m, "register_table_hooks") == (name not in ("curatornet", "lightgcn"))
     # the bases register nothing: the reference's keys, in its order
     assert list(m.state_dict().keys()) == golden[name]["keys"]
