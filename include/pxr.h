@@ -38,7 +38,7 @@ extern "C" {
  * so a caller built against another revision must refuse to run instead of writing out of bounds (pixelrec_amd/lib.py does).
  * 0.3.0 -> 0.3.1: one entry per kernel family -- the plane-writing, h2, bidirectional and id-layout variants were folded into the
  * plain names, which now take the most general argument list (planes triple + planes_fmt, causal, id layout); the shims died. */
-#define PXR_ABI_VERSION 301
+#define PXR_ABI_VERSION 302
 int pxr_version(void);                 /* major*10000 + minor*100 + patch; == PXR_ABI_VERSION of the header it was built from */
 const char* pxr_last_error(void);      /* message of the last failing call on this thread */
 const char* pxr_target_arch(void);     /* "gfx950" */
@@ -695,13 +695,29 @@ int pxr_lightsans_bwd_f32(const float* dctx, const float* qkv, const float* thet
 int pxr_lightsans_pos_fwd_f32(const float* pqk, int L, int D, int H, float* A, void* stream);
 int pxr_lightsans_pos_bwd_f32(const float* pqk, const float* A, const float* dA, int L, int D, int H, float* dpqk, void* stream);
 
+/* ---- ids to rows of a table that holds several embeddings (csrc/rows.hip) --------------------------------------------------- */
+/* MF, VBPR, ACF, DIN and the pooled pair models keep their embeddings in ONE table buffer whose row 0 is a spare (the sparse-row
+ * kernels treat id 0 as padding / an empty slot).  A step's occurrences are 1 .. 4 segments of ids laid end to end: occurrence o of
+ * a segment reads rows[o] = base + id; gidx[o] (may be NULL) = the row its gradient is summed into: rows[o], or 0 (dropped by
+ * pxr_embed_grad_rows_f32) for id 0 of a segment with pad0 set.  An id outside [0, n) ORs bit 0 into the status word (clamped).
+ * A segment with count 0 may have ids == NULL; every base + n < 2^40; 0 < the sum of the counts < 2^31.  The descriptors are host
+ * memory, read during the call only.  The models' segment lists (U users, I items):
+ *   MF    [1 + U + I, D]       user -> 1 + u | item.view(-1) -> 1 + U + i            (item [B, 2] = (positive, negative))
+ *   VBPR  [1 + U + I + U, Dh]  user -> 1 + u | user -> 1 + U + I + u | item.view(-1) -> 1 + U + i
+ *   ACF   [1 + I + U, E]       profile -> 1 + i (pad0) | items -> 1 + i (pad0) | user -> 1 + I + u
+ *   DIN / pooled pair models [1 + I, D]: ACF's list without the user segment
+ * (evaluation passes the user segments alone). */
+typedef struct pxr_row_segment {
+  const int64_t* ids;
+  int64_t count, n, base;
+  int32_t pad0, reserved;
+} pxr_row_segment;
+/* segments: n_segments pxr_row_segment */
+int pxr_table_rows_i64(const void* segments, int n_segments, int64_t* rows, int64_t* gidx, void* stream);
+
 /* ---- MF (model/IDNet/mf.py, layers.py:239-294 MLPLayers; csrc/mf.hip) ------------------------------------------------------- */
-/* The table is ONE [1 + n_users + n_items, D] buffer: user u at row 1 + u, item i at row 1 + n_users + i, row 0 a spare (the
- * sparse-row kernels treat id 0 as padding / an empty slot).  rows[3B] = [1 + user[b] for b < B | the rows of item.view(-1)]
- * (item [B, 2] = (positive, negative)); item == NULL: the B user rows only.  An id outside [0, n_users) / [0, n_items) ORs bit 0
- * into the status word (clamped). */
-int pxr_mf_pair_rows_i64(const int64_t* user, const int64_t* item, int B, int64_t n_users, int64_t n_items, int64_t* rows,
-                         void* stream);
+/* The table is ONE [1 + n_users + n_items, D] buffer: user u at row 1 + u, item i at row 1 + n_users + i, row 0 a spare.
+ * rows[3B] (pxr_table_rows_i64) = [1 + user[b] for b < B | the rows of item.view(-1)]. */
 /* Pair loss head (mf.py forward): x_b = <u_b, i+_b> - <u_b, i-_b>, lossrow[b] = -(1e-8 + log sigmoid(x_b)), loss = mean,
  * coef[b] = d loss / d x_b = -(1 - sigmoid(x_b)) / B.  rows != NULL: u_b = ufeat[rows[b]], i+-_b = ifeat[rows[B + 2b (+1)]]
  * (the table, ufeat == ifeat); rows == NULL: the tower outputs, u_b = ufeat[b] ([B, H]), i+-_b = ifeat[2b (+1)] ([2B, H]).
@@ -735,12 +751,9 @@ int pxr_mf_bn_tanh_eval_f32(const float* x, int64_t R, int H, const float* gamma
 
 /* ---- VBPR (model/ViNet/vbpr.py; csrc/vbpr.hip) ----------------------------------------------------------------------------- */
 /* The tables are ONE [1 + 2 n_users + n_items, Dh] buffer in the reference's parameter order: user_id_embedding row u at 1 + u,
- * item_id_embedding row i at 1 + n_users + i, user_modal_embedding row u at 1 + n_users + n_items + u, row 0 a spare (the
- * sparse-row kernels treat id 0 as padding / an empty slot).  rows[4B] = [id row of user[b] | modal row of user[b] | id rows of
- * item.view(-1)] (item [B, 2] = (positive, negative)); item == NULL: the 2B user rows only (vbpr.py:57-60 forward's three
- * embedding lookups, :79-82 predict's).  An id outside [0, n_users) / [0, n_items) ORs bit 0 into the status word (clamped). */
-int pxr_vbpr_rows_i64(const int64_t* user, const int64_t* item, int B, int64_t n_users, int64_t n_items, int64_t* rows,
-                      void* stream);
+ * item_id_embedding row i at 1 + n_users + i, user_modal_embedding row u at 1 + n_users + n_items + u, row 0 a spare.  rows[4B]
+ * (pxr_table_rows_i64) = [id row of user[b] | modal row of user[b] | id rows of item.view(-1)]; the 2B user rows alone in
+ * evaluation (vbpr.py:57-60 forward's three embedding lookups, :79-82 predict's). */
 /* Feature gather with the visual bias fused (vbpr.py:61,65 self.v_feat[item] read twice, :94 compute_item_all's bias): out[r, :]
  * = feat[item[r], :] ([n, F], the projection GEMM's operand) and beta[r] = <feat[item[r], :], wb> from one read of the row.
  * item == NULL: row r itself (n <= n_items); out == NULL: beta only.  Item ids outside [0, n_items) flag and clamp.  F % 4 == 0. */
@@ -770,13 +783,9 @@ int pxr_vbpr_pack_f32(const float* a, const int64_t* a_rows, const float* b, con
 
 /* ---- ACF (model/ViNet/acf.py; csrc/acf.hip) ------------------------------------------------------------------------------- */
 /* The tables are ONE [1 + n_items + n_users, E] buffer in the reference's parameter order: item_model row i at 1 + i (item 0 is
- * the reference's padding row: read, decayed, never given a gradient), user_embedding row u at 1 + n_items + u, row 0 a spare (the
- * sparse-row kernels treat id 0 as padding / an empty slot).  Occurrences in the order [profile ids (n_profile) | item ids
- * (n_item_occ: positive, negative per sample) | user ids (n_user_occ)]; a list with count 0 may be NULL.  rows[o] = the table row
- * occurrence o reads; gidx[o] (may be NULL) = the row its gradient is summed into, 0 for item id 0 (dropped by
- * pxr_embed_grad_rows_f32).  An id outside [0, n_items) / [0, n_users) ORs bit 0 into the status word (clamped). */
-int pxr_acf_rows_i64(const int64_t* profile, int64_t n_profile, const int64_t* items, int64_t n_item_occ, const int64_t* user,
-                     int64_t n_user_occ, int64_t n_items, int64_t n_users, int64_t* rows, int64_t* gidx, void* stream);
+ * the reference's padding row: read, decayed, never given a gradient), user_embedding row u at 1 + n_items + u, row 0 a spare.
+ * Occurrences (pxr_table_rows_i64) in the order [profile ids | item ids (positive, negative per sample) | user ids], gidx 0 for
+ * item id 0. */
 /* Region attention (acf.py ACFFeatureNet.forward after the two Linears), r = b P + p: s_h = <w, relu(xt[r, h, :] + ut[b, :])>,
  * beta[r, :] = softmax_H(s), pooled[r, :] = sum_h beta[r, h] x[r, h, :]; a masked r (profile[r] == 0) gets beta = 0 and pooled =
  * 0.  x, xt [B P, H, E]; ut [B, E]; w [E] (feats.w.weight; its scalar bias cancels in the softmax).  One pass over x and xt,
@@ -849,7 +858,7 @@ int pxr_mul_f32(const float* a, const float* b, float* out, int64_t n, void* str
 /* ---- DIN (model/IDNet/din.py with SequenceAttLayer, model/layers.py:460-514; csrc/din.hip) --------------------------------- */
 /* Occurrences of a batch: o in [0, B L) = history position (b, l); o = B L + 2 b + c = candidate c of sample b (0 positive, 1
  * negative).  Pair rows of the attention MLP: r = (c B + b) L + l.  rows int64 [B L + 2 B] = the table row every occurrence reads
- * (already range-checked: pxr_acf_rows_i64 with no users).
+ * (already range-checked: pxr_table_rows_i64, DIN's segments).
  * Attention input (din.py:59-62 item_embedding(items); layers.py:486-491 repeat / cat): emb[o, :] = table[rows[o], :] and
  * x[r, :] = [q | k | q - k | q * k] with q = the candidate's row, k = the history row.  emb [B L + 2 B, D], x [2 B L, 4 D].
  * D % 4 == 0, D <= 4096. */
@@ -898,7 +907,7 @@ int pxr_din_topk_f32(const float* table, int N, int D, const int64_t* window, in
 /* ---- DSSM and FM (model/IDNet/dssm.py, fm.py; csrc/pool.hip, MODE_POOL of csrc/embed_grad.hip) ------------------------------ */
 /* Occurrences of a batch, as for DIN: o in [0, B L) = history position (b, l); o = B L + 2 b + c = target c of sample b (0
  * positive, 1 negative).  rows int64 [B L + 2 B] = the row of `table` [n_table, D] every occurrence reads; a history entry equal
- * to pad_row is "no item" (training: pxr_acf_rows_i64's rows over the [1 + I, D] table, pad_row 1; evaluation windows over an item
+ * to pad_row is "no item" (training: pxr_table_rows_i64's rows over the [1 + I, D] table, pad_row 1; evaluation windows over an item
  * matrix: the ids themselves, pad_row 0).  Any other entry outside [0, n_table) ORs bit 0 into the status word and is clamped;
  * nothing is read out of range.  Limits of all four: D % 4 == 0, 0 < D <= 4096, L >= 1, B (L + 2) < 2^30; table, U, G and
  * uniq_rows 16-byte aligned.  One fixed summation order (l ascending), no float atomics: bit-identical from run to run.
@@ -923,7 +932,7 @@ int pxr_pool_pair_fwd_f32(const float* table, int64_t n_table, int D, const int6
 int pxr_pool_pair_bwd_f32(const float* table, int64_t n_table, int D, const int64_t* rows, int B, int L, const float* U,
                           const float* coef, float grad_scale, const float* grad_scale_dev, float* G, void* stream);
 /* The table gradient in sparse form from the compact block, without one row per occurrence: gidx int64 [B L + 2 B] = the table row
- * every occurrence's gradient goes to (pxr_acf_rows_i64's gidx: 0 at padding, dropped; ids outside [0, n_table) are dropped too).
+ * every occurrence's gradient goes to (pxr_table_rows_i64's gidx: 0 at padding, dropped; ids outside [0, n_table) are dropped too).
  * Sorted as pxr_embed_grad_rows_f32 sorts its idx (same keys, same stable order), then summed in occurrence order with occurrence
  * o < B L reading w[o / L] * G[o / L, :] and occurrence o >= B L reading G[B + (o - B L), :].  What it writes equals
  * pxr_embed_grad_rows_f32 on the materialised [B (L + 2), D] rows up to the rounding of w * G (bit for bit where every w is 1).

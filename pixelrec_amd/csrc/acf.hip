@@ -24,23 +24,6 @@ __device__ __forceinline__ f32x4 acf_step4(const f32x4& z) {
 }
 constexpr int ACF_MAX_N = 1024;      // regions per item / history items per user held in LDS
 
-// rows[o] / gidx[o] of occurrence o in the layout [profile (B P) | items (B T) | users (B)]: rows = the table row to read, gidx =
-// the row the occurrence's gradient goes to (0 = none: the padding item).  An id outside its table flags the status word.
-__global__ void __launch_bounds__(256) acf_rows_kernel(const int64_t* __restrict__ profile, int64_t n_prof,
-                                                        const int64_t* __restrict__ items, int64_t n_it,
-                                                        const int64_t* __restrict__ user, int64_t n_u, int64_t n_items,
-                                                        int64_t n_users, int64_t* __restrict__ rows, int64_t* __restrict__ gidx,
-                                                        int32_t* status) {
-  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (o >= n_prof + n_it + n_u) return;
-  const bool is_user = o >= n_prof + n_it;
-  const int64_t id = checked_id(o < n_prof ? profile[o] : (is_user ? user[o - n_prof - n_it] : items[o - n_prof]),
-                                is_user ? n_users : n_items, status, true);
-  const int64_t row = 1 + (is_user ? n_items : 0) + id;
-  rows[o] = row;
-  if (gidx) gidx[o] = (!is_user && id == 0) ? 0 : row;
-}
-
 // softmax over s[0..n) held in LDS, computed by every thread alike (one fixed order): returns max and 1 / sum
 __device__ __forceinline__ void acf_softmax_stats(const float* s, int n, float& mx, float& inv) {
   mx = -INFINITY;
@@ -321,21 +304,6 @@ using namespace pxr;
   } while (0)
 
 static inline bool acf_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-extern "C" int pxr_acf_rows_i64(const int64_t* profile, int64_t n_profile, const int64_t* items, int64_t n_item_occ,
-                                const int64_t* user, int64_t n_user_occ, int64_t n_items, int64_t n_users, int64_t* rows,
-                                int64_t* gidx, void* stream) {
-  PXR_REQUIRE(rows, "pxr_acf_rows_i64: null pointer");
-  PXR_REQUIRE(n_profile >= 0 && n_item_occ >= 0 && n_user_occ >= 0, "pxr_acf_rows_i64: negative count");
-  PXR_REQUIRE((n_profile == 0 || profile) && (n_item_occ == 0 || items) && (n_user_occ == 0 || user),
-              "pxr_acf_rows_i64: null id list with a positive count");
-  PXR_REQUIRE(n_users > 0 && n_items > 0 && 1 + n_users + n_items < (1ll << 40), "pxr_acf_rows_i64: bad table size");
-  const int64_t n = n_profile + n_item_occ + n_user_occ;
-  PXR_REQUIRE(n > 0 && n < (1ll << 31), "pxr_acf_rows_i64: need 0 < occurrences < 2^31 (%lld)", (long long)n);
-  hipLaunchKernelGGL(acf_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, profile, n_profile,
-                     items, n_item_occ, user, n_user_occ, n_items, n_users, rows, gidx, pxr_status_word());
-  return pxr_check_launch("pxr_acf_rows_i64");
-}
 
 static int acf_region_shape_ok(const char* who, int B, int P, int H, int E) {
   PXR_REQUIRE(B > 0 && P > 0 && (int64_t)B * P < (1ll << 31), "%s: need B > 0, P > 0 and B P < 2^31 (B=%d, P=%d)", who, B, P);

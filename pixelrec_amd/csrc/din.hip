@@ -33,20 +33,6 @@ struct DinSigmoid {
   __device__ __forceinline__ float operator()(float v) const { return din_sigmoid(v); }
 };
 
-// fixed-order block sum of one value per thread (256 threads); the total is returned to every thread
-__device__ __forceinline__ float din_block_sum(float v, float* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int w = 128; w >= 1; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  const float t = red[0];
-  __syncthreads();
-  return t;
-}
-
 // ---------------------------------------------------------------------------------------------------- training: attention input
 // one workgroup per history occurrence (b, l): emb[o, :] = table[rows[o], :] for the occurrence and (l == 0) the sample's two
 // candidates; x[r, :] = [q | k | q - k | q * k] for both candidates
@@ -136,8 +122,8 @@ __global__ void __launch_bounds__(256) din_loss_kernel(float* __restrict__ head,
     q += head[2 + 2 * B + b];
     head[2 + b] = -(1.0f / (float)B) * sg * (1.0f - sg) / (sg + 1e-8f);
   }
-  t = din_block_sum(t, red);
-  q = din_block_sum(q, red);
+  t = block_sum256(t, red);
+  q = block_sum256(q, red);
   if (threadIdx.x == 0) {
     const float nrm = sqrtf(q);
     head[0] = -t / (float)B + 0.01f * nrm / (float)B;
@@ -169,7 +155,7 @@ __global__ void __launch_bounds__(256) din_dense_grad_kernel(const float* __rest
   const int j = blockIdx.x;
   float t = 0.f;
   for (int64_t r = threadIdx.x; r < R; r += 256) t += j < hl ? dsraw[r] * alast[r * hl + j] : dsraw[r];
-  t = din_block_sum(t, red);
+  t = block_sum256(t, red);
   if (threadIdx.x == 0) {
     if (j < hl) dwd[j] = t;
     else dbd[0] = t;

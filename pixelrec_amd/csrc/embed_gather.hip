@@ -27,13 +27,9 @@ __global__ void __launch_bounds__(256) embed_gather_kernel(const gvec4* __restri
     if (c < total_chunks) {
       const int64_t row = c / dv;
       const int col = (int)(c - row * dv);
-      int64_t r = idx[row];
       // an out-of-range id is an ERROR (nn.Embedding raises, sasrec.py:68): flag it in the device status word -- the
       // host raises IndexError at its next check (ops.raise_on_bad_indices) -- and clamp so the access stays in bounds
-      if (r < 0 || r >= n_rows_table) {
-        if (status && col == 0) atomicOr(status, PXR_STATUS_BAD_INDEX);
-        r = r < 0 ? 0 : n_rows_table - 1;
-      }
+      const int64_t r = pxr::checked_id(idx[row], n_rows_table, status, col == 0);
       if constexpr (NT & 1) v[u] = __builtin_nontemporal_load(&table[r * dv + col]);
       else v[u] = table[r * dv + col];
     }

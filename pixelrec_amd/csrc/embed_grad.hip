@@ -63,7 +63,7 @@ __global__ void __launch_bounds__(256) occ_keys_sasrec_kernel(const int64_t* __r
   const int b = r / L, t = r - b * L;
   const int64_t* row = items + (int64_t)b * lay.bstride;
   int64_t id = row[(type == 0 ? lay.off_in : (type == 1 ? lay.off_pos : lay.off_neg)) + t];
-  if (id < 0 || id >= n_table) {
+  if (id < 0 || id >= n_table) {   // not checked_id's rule: a bad id becomes key 0, "dropped", not the nearer end of the table
     if (status) atomicOr(status, PXR_STATUS_BAD_INDEX);
     id = 0;
   }

@@ -12,6 +12,7 @@
 // Backward (autograd of the above):   a = dy*gamma;  dz = rstd*(a - mean(a) - xhat*mean(a*xhat))
 //   dgamma = sum_rows dy*xhat, dbeta = sum_rows dy  -> per-block partials, summed in fixed order by
 //   pxr_colsum-style stage 2 (deterministic, no float atomics).
+#include "bpr_head.cuh"
 #include "planes.cuh"
 #include "reduce_multi.cuh"
 #include "../../include/pxr.h"   // pxr_tail_rider
@@ -22,27 +23,12 @@ namespace pxr {
 
 // The loss head fused into the LAST LayerNorm of the block (sasrec.py:86-92: the head reads exactly the rows this LayerNorm
 // writes): forward = the two target-row dot products + the per-position loss term of bpr_loss.hip's bpr_fwd_kernel in the wave
-// that holds the row; backward = bpr_bwd_kernel's d out row formed in registers instead of being written and read back.  Same
-// formulas, same order of operations as bpr_loss.hip.  The backward is bit-identical to bpr_bwd_kernel + ln_bwd_kernel at every D;
-// the forward's scores and loss are bit-identical to bpr_fwd_kernel's for D <= 1024 (VEC <= 4), while at VEC = 8 / 16 the two
-// separately compiled dot products do not round alike and the scores differ by a few ulp of the D-term sum (measured:
-// tests/test_gpu_bpr_ref.py).  items == null: no head.
-struct BprHead {
-  const float* table;      // [n_table, D]
-  const int64_t* items;    // [B, 2, L+1]
-  const int64_t* mask;     // [B, L]
-  float* pos; float* neg;  // [B*L] scores (fwd: written; bwd: read)
-  float* lossrow;          // fwd: [B*L] per-position loss term
-  float* coef;             // bwd: [B*L] d loss / d(pos - neg)
-  int64_t n_table;
-  int B, L;
-  float grad_scale;
-  const float* grad_scale_dev;
-  // id layout: position t of sequence b scores against items[b*id_bstride + pos_off + t] / [... + neg_off + t].  SASRec's shifted
-  // [B, 2, L+1] windows: (2(L+1), 1, L+2); BERT4Rec's aligned [B, 3, L] planes: (3L, L, 2L)
-  int64_t id_bstride, pos_off, neg_off;
-};
-__device__ __forceinline__ int64_t ln_clamp_id(int64_t r, int64_t n) { return r < 0 ? 0 : (r >= n ? n - 1 : r); }
+// that holds the row; backward = bpr_bwd_kernel's d out row formed in registers instead of being written and read back.  Both
+// forms are built from the helpers of bpr_head.cuh (BprHead lives there), so the formulas and their order of operations are the
+// same code.  The backward is bit-identical to bpr_bwd_kernel + ln_bwd_kernel at every D; the forward's scores and loss are
+// bit-identical to bpr_fwd_kernel's for D <= 1024 (VEC <= 4), while at VEC = 8 / 16 the dot products, inlined into two differently
+// unrolled loops, do not round alike and the scores differ by a few ulp of the D-term sum (measured: tests/test_gpu_bpr_ref.py).
+// head.items == null: no head.
 
 struct LnFwdArgs {
   const float* x;          // RESIDUAL: [rows, D]
@@ -106,12 +92,8 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs a) {
     if constexpr (GATHER) {
       const int rr = live[w] ? row : (STAGE ? a.rows - 1 : row0);     // (an idle wave of a staging workgroup re-reads the last row)
       const int b = rr / a.L, t = rr - b * a.L;
-      int64_t r = a.idx[(int64_t)b * a.idx_bstride + t];
-      if (r < 0 || r >= a.n_table) {   // an error in the reference (nn.Embedding raises): flag it, then clamp
-        if (a.status && lane == 0) atomicOr(a.status, PXR_STATUS_BAD_INDEX);
-        r = r < 0 ? 0 : a.n_table - 1;
-      }
-      src = a.table + r * D;
+      // (an id outside the table is an error in the reference -- nn.Embedding raises: flagged, then clamped)
+      src = a.table + checked_id(a.idx[(int64_t)b * a.idx_bstride + t], a.n_table, a.status, lane == 0) * D;
       add = a.pos + (int64_t)t * D;
     } else {
       const int rr = live[w] ? row : (STAGE ? a.rows - 1 : row0);
@@ -126,13 +108,8 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs a) {
         if (GATHER && (a.nt & 8)) t4 = pxr_ld_stream(src + c);
         else t4 = *reinterpret_cast<const float4*>(src + c);
         if constexpr (!GATHER) {
-          if (drop) {  // dropout on the sub-layer output BEFORE the residual add (layers.py:614, :670)
-            const uint64_t e = (uint64_t)row * D + c;
-            t4.x = pxr_keep(a.seed, a.stream, e + 0, a.drop_thr) ? t4.x * inv_keep : 0.f;
-            t4.y = pxr_keep(a.seed, a.stream, e + 1, a.drop_thr) ? t4.y * inv_keep : 0.f;
-            t4.z = pxr_keep(a.seed, a.stream, e + 2, a.drop_thr) ? t4.z * inv_keep : 0.f;
-            t4.w = pxr_keep(a.seed, a.stream, e + 3, a.drop_thr) ? t4.w * inv_keep : 0.f;
-          }
+          // dropout on the sub-layer output BEFORE the residual add (layers.py:614, :670)
+          if (drop) pxr_drop4(t4, a.seed, a.stream, (uint64_t)row * D + c, a.drop_thr, inv_keep);
         }
         if (add) {
           const float4 r4 = *reinterpret_cast<const float4*>(add + c);
@@ -167,14 +144,12 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs a) {
     float hp = 0.f, hn = 0.f;
     if constexpr (!GATHER) {
       if (a.head.items) {   // wave-uniform
-        const int b = row / a.head.L, t = row - b * a.head.L;
-        const int64_t* it = a.head.items + (int64_t)b * a.head.id_bstride;
-        const int64_t ip = it[a.head.pos_off + t], in = it[a.head.neg_off + t];
-        // (as bpr_fwd_kernel: an id outside the table is flagged, then clamped; the fused backward does not flag again)
-        if ((ip < 0 || ip >= a.head.n_table || in < 0 || in >= a.head.n_table) && a.status && lane == 0)
-          atomicOr(a.status, PXR_STATUS_BAD_INDEX);
-        ep = a.head.table + ln_clamp_id(ip, a.head.n_table) * D;
-        en = a.head.table + ln_clamp_id(in, a.head.n_table) * D;
+        int b, t;
+        int64_t ip, in;
+        bpr_bt(a.head, row, b, t);
+        bpr_ids(a.head, b, t, ip, in);
+        ep = bpr_row(a.head.table, a.head.n_table, ip, D, a.status, lane == 0);
+        en = bpr_row(a.head.table, a.head.n_table, in, D, a.status, lane == 0);
       }
     }
 #pragma unroll
@@ -193,13 +168,8 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs a) {
         float4 y;
         y.x = xh.x * g.x + be.x; y.y = xh.y * g.y + be.y; y.z = xh.z * g.z + be.z; y.w = xh.w * g.w + be.w;
         if constexpr (GATHER) {
-          if (drop) {  // dropout AFTER the input LayerNorm (sasrec.py:82)
-            const uint64_t e = (uint64_t)row * D + c;
-            y.x = pxr_keep(a.seed, a.stream, e + 0, a.drop_thr) ? y.x * inv_keep : 0.f;
-            y.y = pxr_keep(a.seed, a.stream, e + 1, a.drop_thr) ? y.y * inv_keep : 0.f;
-            y.z = pxr_keep(a.seed, a.stream, e + 2, a.drop_thr) ? y.z * inv_keep : 0.f;
-            y.w = pxr_keep(a.seed, a.stream, e + 3, a.drop_thr) ? y.w * inv_keep : 0.f;
-          }
+          // dropout AFTER the input LayerNorm (sasrec.py:82)
+          if (drop) pxr_drop4(y, a.seed, a.stream, (uint64_t)row * D + c, a.drop_thr, inv_keep);
         }
         if (a.y) {
           if (a.nt & 1) pxr_st_stream(a.y + (int64_t)row * D + c, y);
@@ -230,7 +200,8 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs a) {
           if (a.yp.p) px_store4s(a.yp, a.yp_fmt, a.status, row, c, y, (a.nt & 2) != 0);
         }
         if constexpr (!GATHER) {
-          if (ep) {   // (same association as bpr_fwd_kernel: per float4, then across a lane's chunks in column order)
+          if (ep) {   // bpr_fwd_kernel's association: per float4, then across a lane's chunks in column order.  (Written out at both
+                      // sites: through a shared helper the compiler swaps which sum gets which FMA pairing, and a score moves an ulp.)
             const float4 pv = *reinterpret_cast<const float4*>(ep + c);
             const float4 nv = *reinterpret_cast<const float4*>(en + c);
             hp += (y.x * pv.x + y.y * pv.y) + (y.z * pv.z + y.w * pv.w);
@@ -243,13 +214,7 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs a) {
       if (ep) {
         hp = wave_sum(hp);
         hn = wave_sum(hn);
-        if (lane == 0) {
-          a.head.pos[row] = hp;
-          a.head.neg[row] = hn;
-          const float x = hp - hn;
-          const float sg = 1.0f / (1.0f + expf(-x));
-          a.head.lossrow[row] = -logf(sg + 1e-8f) * (float)a.head.mask[row];
-        }
+        if (lane == 0) bpr_store_loss(a.head, row, hp, hn);
       }
     }
   }
@@ -330,16 +295,15 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(LnBwdArgs a) {
     const float* en = nullptr;
     float cf = 0.f;
     if constexpr (!GATHER) {
-      if (a.head.items) {   // wave-uniform; bpr_bwd_kernel's coefficient and rows
-        const int b = row / a.head.L, t = row - b * a.head.L;
-        const float x = a.head.pos[row] - a.head.neg[row];
-        const float sg = 1.0f / (1.0f + expf(-x));
-        cf = -((float)a.head.mask[row] / (float)a.head.B) * (sg * (1.0f - sg)) / (sg + 1e-8f) * a.head.grad_scale;
-        if (a.head.grad_scale_dev) cf *= a.head.grad_scale_dev[0];
+      if (a.head.items) {   // wave-uniform; bpr_bwd_kernel's coefficient and rows (the forward flagged the ids)
+        int b, t;
+        int64_t ip, in;
+        bpr_bt(a.head, row, b, t);
+        cf = bpr_coef(a.head.pos[row] - a.head.neg[row], (float)a.head.mask[row], a.head.B, a.head.grad_scale, a.head.grad_scale_dev);
         if (lane == 0) a.head.coef[row] = cf;
-        const int64_t* it = a.head.items + (int64_t)b * a.head.id_bstride;
-        ep = a.head.table + ln_clamp_id(it[a.head.pos_off + t], a.head.n_table) * D;
-        en = a.head.table + ln_clamp_id(it[a.head.neg_off + t], a.head.n_table) * D;
+        bpr_ids(a.head, b, t, ip, in);
+        ep = bpr_row(a.head.table, a.head.n_table, ip, D, nullptr, false);
+        en = bpr_row(a.head.table, a.head.n_table, in, D, nullptr, false);
       }
     }
 #pragma unroll
@@ -348,23 +312,12 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(LnBwdArgs a) {
       if (c < D) {
         float4 d;
         if (ep) {
-          d = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (cf != 0.f) {
-            const float4 pv = *reinterpret_cast<const float4*>(ep + c);
-            const float4 nv = *reinterpret_cast<const float4*>(en + c);
-            d.x = cf * (pv.x - nv.x); d.y = cf * (pv.y - nv.y); d.z = cf * (pv.z - nv.z); d.w = cf * (pv.w - nv.w);
-          }
+          d = bpr_dout4(cf, ep, en, c);
         } else {
           d = *reinterpret_cast<const float4*>(a.dy + (int64_t)row * D + c);
         }
         if constexpr (GATHER) {
-          if (drop) {
-            const uint64_t e = (uint64_t)row * D + c;
-            d.x = pxr_keep(a.seed, a.stream, e + 0, a.drop_thr) ? d.x * inv_keep : 0.f;
-            d.y = pxr_keep(a.seed, a.stream, e + 1, a.drop_thr) ? d.y * inv_keep : 0.f;
-            d.z = pxr_keep(a.seed, a.stream, e + 2, a.drop_thr) ? d.z * inv_keep : 0.f;
-            d.w = pxr_keep(a.seed, a.stream, e + 3, a.drop_thr) ? d.w * inv_keep : 0.f;
-          }
+          if (drop) pxr_drop4(d, a.seed, a.stream, (uint64_t)row * D + c, a.drop_thr, inv_keep);
         }
         const float4 x = *reinterpret_cast<const float4*>(a.xhat + (int64_t)row * D + c);
         xh[k] = x;
@@ -405,13 +358,7 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(LnBwdArgs a) {
           }
           if (has_dx) {
             float4 o = z;
-            if (drop) {
-              const uint64_t e = (uint64_t)row * D + c;
-              o.x = pxr_keep(a.seed, a.stream, e + 0, a.drop_thr) ? z.x * inv_keep : 0.f;
-              o.y = pxr_keep(a.seed, a.stream, e + 1, a.drop_thr) ? z.y * inv_keep : 0.f;
-              o.z = pxr_keep(a.seed, a.stream, e + 2, a.drop_thr) ? z.z * inv_keep : 0.f;
-              o.w = pxr_keep(a.seed, a.stream, e + 3, a.drop_thr) ? z.w * inv_keep : 0.f;
-            }
+            if (drop) pxr_drop4(o, a.seed, a.stream, (uint64_t)row * D + c, a.drop_thr, inv_keep);
             if (a.dx) *reinterpret_cast<float4*>(a.dx + (int64_t)row * D + c) = o;
             gmax = fmaxf(gmax, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
             if (a.gp.p) {
@@ -639,9 +586,8 @@ extern "C" int pxr_ln_residual_bpr_fwd_f32(const float* x, const float* res, con
   a.rows = B * L; a.D = D; a.L = 1; a.eps = eps;
   a.p_drop = p_drop; a.drop_thr = pxr_drop_threshold(p_drop); a.stream = stream_id; a.seed = seed;
   a.step_dev = step_dev;
-  a.head.table = table; a.head.items = items; a.head.mask = masked_index; a.head.pos = pos_score; a.head.neg = neg_score;
-  a.head.lossrow = lossrow; a.head.n_table = n_table; a.head.B = B; a.head.L = L;
-  a.head.id_bstride = id_bstride; a.head.pos_off = pos_off; a.head.neg_off = neg_off;
+  a.head = bpr_head_of(table, n_table, items, masked_index, B, L, id_bstride, pos_off, neg_off);
+  a.head.pos = pos_score; a.head.neg = neg_score; a.head.lossrow = lossrow;
   a.status = pxr_status_word();   // the head's bad-index flag (no planes here, so nothing else of this launch writes it)
   const int rc = launch_ln_fwd<false>(a, (hipStream_t)stream);
   if (rc) return rc;
@@ -711,10 +657,9 @@ extern "C" int pxr_bpr_ln_bwd_f32(const float* pos_score, const float* neg_score
   PXR_REQUIRE(pxr_bpr_layout_ok(L, id_bstride, pos_off, neg_off), "pxr_bpr_ln_bwd_f32: bad id layout");
   PXR_REQUIRE(pos_score && neg_score && table && items && masked_index && coef && B > 0 && L > 0 && n_table > 0,
               "pxr_bpr_ln_bwd_f32: null pointer / bad shape");
-  BprHead h{};
-  h.table = table; h.items = items; h.mask = masked_index; h.pos = const_cast<float*>(pos_score); h.neg = const_cast<float*>(neg_score);
-  h.coef = coef; h.n_table = n_table; h.B = B; h.L = L; h.grad_scale = grad_scale; h.grad_scale_dev = grad_scale_dev;
-  h.id_bstride = id_bstride; h.pos_off = pos_off; h.neg_off = neg_off;
+  BprHead h = bpr_head_of(table, n_table, items, masked_index, B, L, id_bstride, pos_off, neg_off);
+  h.pos = const_cast<float*>(pos_score); h.neg = const_cast<float*>(neg_score); h.coef = coef;
+  h.grad_scale = grad_scale; h.grad_scale_dev = grad_scale_dev;
   return ln_bwd_impl(0, nullptr, xhat, rstd, gamma, B * L, D, dz, dx, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws, ws_bytes,
                      g_planes, g_plane_stride, g_panel_rows, stat, stream, &h);
 }
@@ -737,9 +682,9 @@ extern "C" int pxr_ln_bwd_h2s_f32(const float* pos_score, const float* neg_score
   if (pos_score) {
     PXR_REQUIRE(neg_score && table && items && masked_index && coef && B > 0 && L > 0 && n_table > 0 && rows == B * L,
                 "pxr_ln_bwd_h2s_f32: null pointer / bad shape of the fused loss head");
-    h.table = table; h.items = items; h.mask = masked_index; h.pos = const_cast<float*>(pos_score); h.neg = const_cast<float*>(neg_score);
-    h.coef = coef; h.n_table = n_table; h.B = B; h.L = L; h.grad_scale = grad_scale; h.grad_scale_dev = grad_scale_dev;
-    h.id_bstride = id_bstride; h.pos_off = pos_off; h.neg_off = neg_off;
+    h = bpr_head_of(table, n_table, items, masked_index, B, L, id_bstride, pos_off, neg_off);
+    h.pos = const_cast<float*>(pos_score); h.neg = const_cast<float*>(neg_score); h.coef = coef;
+    h.grad_scale = grad_scale; h.grad_scale_dev = grad_scale_dev;
   }
   return ln_bwd_impl(0, pos_score ? nullptr : dy, xhat, rstd, gamma, rows, D, dz, nullptr, dgamma, dbeta, p_drop, seed, stream_id, step_dev, ws,
                      ws_bytes, g_planes, g_plane_stride, g_panel_rows, stat, stream, pos_score ? &h : nullptr, zero, zero_n, g_exp_dev,

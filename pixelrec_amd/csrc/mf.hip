@@ -12,18 +12,6 @@
 
 namespace pxr {
 
-// rows[o] of occurrence o (layout above); an id outside its range flags the status word and is clamped
-__global__ void __launch_bounds__(256) mf_pair_rows_kernel(const int64_t* __restrict__ user, const int64_t* __restrict__ item, int B,
-                                                            int64_t n_users, int64_t n_items, int64_t* __restrict__ rows,
-                                                            int32_t* status) {
-  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t n_occ = item ? 3 * (int64_t)B : (int64_t)B;
-  if (o >= n_occ) return;
-  const bool is_user = o < B;
-  const int64_t id = checked_id(is_user ? user[o] : item[o - B], is_user ? n_users : n_items, status, true);
-  rows[o] = 1 + (is_user ? 0 : n_users) + id;
-}
-
 // Feature rows of sample b: the user's, the positive's and the negative's.  rows != NULL: rows of the table (ufeat == ifeat);
 // rows == NULL: the towers' outputs, user b at ufeat row b, item j of item.view(-1) at ifeat row j.
 struct MfPairArgs {
@@ -254,17 +242,6 @@ __global__ void __launch_bounds__(256) mf_bn_tanh_eval_kernel(BnArgs a) {
 }  // namespace pxr
 
 using namespace pxr;
-
-extern "C" int pxr_mf_pair_rows_i64(const int64_t* user, const int64_t* item, int B, int64_t n_users, int64_t n_items,
-                                    int64_t* rows, void* stream) {
-  PXR_REQUIRE(user && rows, "pxr_mf_pair_rows_i64: null pointer");
-  PXR_REQUIRE(B > 0 && B <= (1 << 28), "pxr_mf_pair_rows_i64: bad batch size %d", B);
-  PXR_REQUIRE(n_users > 0 && n_items > 0 && 1 + n_users + n_items < (1ll << 40), "pxr_mf_pair_rows_i64: bad table size");
-  const int64_t n = item ? 3 * (int64_t)B : (int64_t)B;
-  hipLaunchKernelGGL(mf_pair_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, user, item, B,
-                     n_users, n_items, rows, pxr_status_word());
-  return pxr_check_launch("pxr_mf_pair_rows_i64");
-}
 
 extern "C" int pxr_mf_pair_fwd_f32(const float* ufeat, const float* ifeat, const int64_t* rows, int H, int B, float* coef,
                                    float* lossrow, float* loss, void* stream) {

@@ -1,5 +1,5 @@
 // pair_head.cuh -- the core shared by the pair-wise BPR kernels over float4 rows (mf.hip, vbpr.hip, lightgcn.hip, srgnn.hip,
-// curator.hip, acf.hip): the id clamp with its status flag, the two loss tails, the pair of wave dot products, the deterministic
+// curator.hip, acf.hip): the two loss tails, the pair of wave dot products, the deterministic
 // first-occurrence segment sum with its register row, the gradient scale and the host's choice of the CH instantiation.  No kernel
 // lives here.  A kernel of those files resolves its rows, calls the core and writes its outputs.
 //
@@ -32,16 +32,6 @@ static inline void dispatch_ch(int dv, F&& f) {
 
 #ifdef __HIPCC__
 __device__ __forceinline__ float dot4(const f32x4& p, const f32x4& q) { return p.x * q.x + p.y * q.y + p.z * q.z + p.w * q.w; }
-
-// id if it lies in [0, n), else the nearer end of the range; an id outside flags the status word from the lanes with flag_lane set
-// (a thread per id: true; a wave per id: lane == 0; status may be null)
-__device__ __forceinline__ int64_t checked_id(int64_t id, int64_t n, int32_t* status, bool flag_lane) {
-  if (id < 0 || id >= n) {
-    if (status && flag_lane) atomicOr(status, PXR_STATUS_BAD_INDEX);
-    return id < 0 ? 0 : n - 1;
-  }
-  return id;
-}
 
 // The two loss tails: x_b -> (lossrow[b], coef[b] = d loss / d x_b) of loss = mean_b lossrow[b].  Both take e = exp(-|x|) <= 1 and
 // pick sigmoid(x) and 1 - sigmoid(x) = sigmoid(-x) by the sign of x, so nothing overflows and no 1 - (nearly 1) cancels: every

@@ -54,7 +54,7 @@ static inline int pxr_check_launch(const char* what) {
     }                                \
   } while (0)
 
-// The loss head's id layout (bpr_loss.hip BprArgs / layernorm.hip BprHead): the target and negative ids of position t of sequence b
+// The loss head's id layout (bpr_head.cuh BprHead): the target and negative ids of position t of sequence b
 // at items[b*id_bstride + pos_off + t] and items[b*id_bstride + neg_off + t], both windows inside the row.
 static inline bool pxr_bpr_layout_ok(int L, int64_t id_bstride, int64_t pos_off, int64_t neg_off) {
   return id_bstride > 0 && pos_off >= 0 && neg_off >= 0 && pos_off + L <= id_bstride && neg_off + L <= id_bstride;
@@ -85,6 +85,16 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
   const int xcd = bid & 7, q = nblk >> 3, rem = nblk & 7;
   const int start = (xcd < rem) ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
   return start + (bid >> 3);
+}
+
+// id if it lies in [0, n), else the nearer end of the range; an id outside flags the status word from the lanes with flag_lane set
+// (a thread per id: true; a wave per id: lane == 0; status may be null)
+__device__ __forceinline__ int64_t checked_id(int64_t id, int64_t n, int32_t* status, bool flag_lane) {
+  if (id < 0 || id >= n) {
+    if (status && flag_lane) atomicOr(status, PXR_STATUS_BAD_INDEX);
+    return id < 0 ? 0 : n - 1;
+  }
+  return id;
 }
 }  // namespace pxr
 // Row-parallel producers (LayerNorm, attention, the plane split) use the SAME map as the GEMM tiles that read their output
@@ -121,6 +131,22 @@ __device__ __forceinline__ float wave_max(float v) {
   v = fmaxf(v, pxr_dpp<0x143, 0xc>(v, v));
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+
+namespace pxr {
+// fixed-order block sum of one value per thread (256 threads, red[256] in LDS); the total is returned to every thread
+__device__ __forceinline__ float block_sum256(float v, float* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+#pragma unroll
+  for (int w = 128; w >= 1; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  const float t = red[0];
+  __syncthreads();
+  return t;
+}
+}  // namespace pxr
 
 // ---------------------------------------------------------------- fixed-order reduction of per-block partials
 // out[n] = sum_p part[p][n] for n < N.  Block = PXR_RED_CX columns x PXR_RED_CY row-lanes; row-lane r sums
@@ -203,5 +229,12 @@ __device__ __host__ __forceinline__ uint32_t pxr_drop_threshold(float p) {
 }
 __device__ __host__ __forceinline__ bool pxr_keep(uint64_t seed, uint32_t stream, uint64_t idx, uint32_t thr) {
   return pxr_hash32(seed, stream, idx) >= thr;
+}
+// dropout of the four elements e .. e + 3: kept ones times inv_keep = 1 / (1 - p), the others 0
+__device__ __forceinline__ void pxr_drop4(float4& v, uint64_t seed, uint32_t stream, uint64_t e, uint32_t thr, float inv_keep) {
+  v.x = pxr_keep(seed, stream, e + 0, thr) ? v.x * inv_keep : 0.f;
+  v.y = pxr_keep(seed, stream, e + 1, thr) ? v.y * inv_keep : 0.f;
+  v.z = pxr_keep(seed, stream, e + 2, thr) ? v.z * inv_keep : 0.f;
+  v.w = pxr_keep(seed, stream, e + 3, thr) ? v.w * inv_keep : 0.f;
 }
 #endif  // __HIPCC__

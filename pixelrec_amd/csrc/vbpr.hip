@@ -13,20 +13,6 @@
 
 namespace pxr {
 
-// rows[o] of occurrence o (layout above; item == NULL: the 2B user rows only); an id outside its range flags the status word and
-// is clamped
-__global__ void __launch_bounds__(256) vbpr_rows_kernel(const int64_t* __restrict__ user, const int64_t* __restrict__ item, int B,
-                                                         int64_t n_users, int64_t n_items, int64_t* __restrict__ rows,
-                                                         int32_t* status) {
-  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t n_occ = item ? 4 * (int64_t)B : 2 * (int64_t)B;
-  if (o >= n_occ) return;
-  const bool is_user = o < 2 * (int64_t)B;
-  const int64_t id = checked_id(is_user ? user[o < B ? o : o - B] : item[o - 2 * (int64_t)B], is_user ? n_users : n_items, status,
-                                true);
-  rows[o] = 1 + id + (o < B ? 0 : is_user ? n_users + n_items : n_users);
-}
-
 // out[r, :] = feat[item[r], :] and beta[r] = <feat[item[r], :], wb> from the same registers: the feature row is read once.  One
 // wave per row.  item == NULL: row r itself (the whole catalogue); out == NULL: beta only (compute_item_all's total_visual_bias).
 __global__ void __launch_bounds__(256) vbpr_gather_kernel(const f32x4* __restrict__ feat, int64_t n_items, int fv,
@@ -234,17 +220,6 @@ __global__ void __launch_bounds__(256) vbpr_pack_kernel(const f32x4* __restrict_
 }  // namespace pxr
 
 using namespace pxr;
-
-extern "C" int pxr_vbpr_rows_i64(const int64_t* user, const int64_t* item, int B, int64_t n_users, int64_t n_items, int64_t* rows,
-                                 void* stream) {
-  PXR_REQUIRE(user && rows, "pxr_vbpr_rows_i64: null pointer");
-  PXR_REQUIRE(B > 0 && B <= (1 << 26), "pxr_vbpr_rows_i64: bad batch size %d", B);
-  PXR_REQUIRE(n_users > 0 && n_items > 0 && 1 + 2 * n_users + n_items < (1ll << 40), "pxr_vbpr_rows_i64: bad table size");
-  const int64_t n = item ? 4 * (int64_t)B : 2 * (int64_t)B;
-  hipLaunchKernelGGL(vbpr_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, user, item, B, n_users,
-                     n_items, rows, pxr_status_word());
-  return pxr_check_launch("pxr_vbpr_rows_i64");
-}
 
 extern "C" int pxr_vbpr_gather_f32(const float* feat, int64_t n_items, int F, const int64_t* item, int64_t n, const float* wb,
                                    float* out, float* beta, void* stream) {

@@ -264,11 +264,7 @@ __global__ void __launch_bounds__(256) dropout_kernel(const float4* __restrict__
   if (step_dev) seed += (uint64_t)step_dev[0];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     float4 v = x[i];
-    const uint64_t e = (uint64_t)i * 4;
-    v.x = pxr_keep(seed, stream_id, e, thr) ? v.x * inv_keep : 0.f;
-    v.y = pxr_keep(seed, stream_id, e + 1, thr) ? v.y * inv_keep : 0.f;
-    v.z = pxr_keep(seed, stream_id, e + 2, thr) ? v.z * inv_keep : 0.f;
-    v.w = pxr_keep(seed, stream_id, e + 3, thr) ? v.w * inv_keep : 0.f;
+    pxr_drop4(v, seed, stream_id, (uint64_t)i * 4, thr, inv_keep);
     y[i] = v;
   }
 }

@@ -26,29 +26,6 @@
 
 namespace pxr {
 
-// fixed-order block sum of one value per thread (256 threads); the total is returned to every thread
-__device__ __forceinline__ float wd_block_sum(float v, float* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int w = 128; w >= 1; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  const float t = red[0];
-  __syncthreads();
-  return t;
-}
-
-// a target id as an index of the wide vector: flagged and clamped when it lies outside [0, n)
-__device__ __forceinline__ int64_t wd_target_id(int64_t id, int64_t n, int32_t* status) {
-  if (id < 0 || id >= n) {
-    if (status) atomicOr(status, PXR_STATUS_BAD_INDEX);
-    return id < 0 ? 0 : n - 1;
-  }
-  return id;
-}
-
 // ---------------------------------------------------------------------------------------------------- training: the join
 // a1[r, j] = relu(zh[r / 2, j] + zt[r, j] + b1[j]),  der[r, j] = [a1 > 0]
 __global__ void __launch_bounds__(256) wd_join_kernel(const float* __restrict__ zh, const float* __restrict__ zt,
@@ -85,7 +62,8 @@ __global__ void __launch_bounds__(64) wd_head_fwd_kernel(const float* __restrict
   for (int j = lane; j < hl; j += 64) acc += (ap[j] - an[j]) * wp[j];
   acc = wave_sum(acc);
   if (lane == 0) {
-    const int64_t p = wd_target_id(target[2 * b], n_items, status), q = wd_target_id(target[2 * b + 1], n_items, status);
+    // a target id as an index of the wide vector: flagged and clamped when it lies outside [0, n_items)
+    const int64_t p = checked_id(target[2 * b], n_items, status, true), q = checked_id(target[2 * b + 1], n_items, status, true);
     head[1 + B + b] = (acc + wide[p]) - wide[q];
   }
 }
@@ -99,7 +77,7 @@ __global__ void __launch_bounds__(256) wd_loss_kernel(float* __restrict__ head, 
     t += logf(1e-8f + sg);
     head[1 + b] = -(1.0f / (float)B) * sg * (1.0f - sg) / (1e-8f + sg);
   }
-  t = wd_block_sum(t, red);
+  t = block_sum256(t, red);
   if (threadIdx.x == 0) head[0] = -t / (float)B;
 }
 

@@ -153,14 +153,13 @@ _SIGNATURES = {
     "pxr_lightsans_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _U64, _U32, _P, _P, _P, _P, _P, _P]),
     "pxr_lightsans_pos_fwd_f32": (_I, [_P, _I, _I, _I, _P, _P]),
     "pxr_lightsans_pos_bwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
-    "pxr_mf_pair_rows_i64": (_I, [_P, _P, _I, _I64, _I64, _P, _P]),
+    "pxr_table_rows_i64": (_I, [_P, _I, _P, _P, _P]),
     "pxr_mf_pair_fwd_f32": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "pxr_mf_pair_bwd_f32": (_I, [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P]),
     "pxr_mf_table_grad_f32": (_I, [_P, _I64, _I, _P, _I, _P, _P, _F, _P, _P, _P, _P, _I64, _P]),
     "pxr_mf_bn_tanh_fwd_f32": (_I, [_P, _I, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
     "pxr_mf_bn_tanh_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "pxr_mf_bn_tanh_eval_f32": (_I, [_P, _I64, _I, _P, _P, _P, _P, _F, _P, _P]),
-    "pxr_vbpr_rows_i64": (_I, [_P, _P, _I, _I64, _I64, _P, _P]),
     "pxr_vbpr_gather_f32": (_I, [_P, _I64, _I, _P, _I64, _P, _P, _P, _P]),
     "pxr_vbpr_pair_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "pxr_vbpr_pair_bwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _I64, _P]),
@@ -170,7 +169,6 @@ _SIGNATURES = {
     "pxr_curator_pool_bwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "pxr_mul_f32": (_I, [_P, _P, _P, _I64, _P]),
     "pxr_curator_pair_fwd_f32": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
-    "pxr_acf_rows_i64": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _P]),
     "pxr_acf_region_fwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "pxr_acf_region_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "pxr_acf_region_dx_f32": (_I, [_P, _P, _P, _P, _I64, _I, _I, _P]),
@@ -200,7 +198,7 @@ _SIGNATURES = {
 }
 
 
-ABI_VERSION = 301      # include/pxr.h PXR_ABI_VERSION (tests/test_abi.py pins header == binding == library)
+ABI_VERSION = 302      # include/pxr.h PXR_ABI_VERSION (tests/test_abi.py pins header == binding == library)
 
 
 def load():

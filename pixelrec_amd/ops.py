@@ -2120,25 +2120,46 @@ def lightsans_pos_bwd(pqk, A, dA):
     return dpqk
 
 
+# ------------------------------------------------------------------------------------------------ ids -> table rows (csrc/rows.hip)
+class _CRowSegment(ctypes.Structure):
+    """include/pxr.h: pxr_row_segment."""
+    _fields_ = [("ids", ctypes.c_void_p), ("count", ctypes.c_int64), ("n", ctypes.c_int64), ("base", ctypes.c_int64),
+                ("pad0", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+def _table_rows(who: str, segments, out, shape, want_gidx: bool = False):
+    """pxr_table_rows_i64 over segments = [(name, ids int64 tensor | None, n, base, pad0)] (None: left out) into `out` or a new
+    int64 tensor of `shape` ([n]: the rows; [2, n]: rows | gidx).  Bad ids flag the status word and are clamped."""
+    segments = [g for g in segments if g[1] is not None]
+    for name, ids, *_ in segments:
+        _req(ids, torch.int64, name)
+    dev = segments[0][1].device
+    buf = out if out is not None else torch.empty(*shape, dtype=torch.int64, device=dev)
+    if tuple(buf.shape) != tuple(shape) or buf.dtype != torch.int64:
+        raise _l.PxrError(f"{who}: out must be int64 {list(shape)}")
+    c = (_CRowSegment * len(segments))()
+    for g, (_, ids, n, base, pad0) in zip(c, segments):
+        g.ids, g.count, g.n, g.base, g.pad0 = ids.data_ptr(), ids.numel(), int(n), int(base), int(pad0)
+    two = len(shape) == 2
+    device_status(dev)
+    _l.check(_l.load().pxr_table_rows_i64(c, len(segments), _l.ptr(buf[0] if two else buf), _l.ptr(buf[1]) if want_gidx else None,
+                                          _l.stream_ptr()), "pxr_table_rows_i64")
+    return buf
+
+
+def _pair_items(who: str, item, B: int):
+    if item is not None and item.numel() != 2 * B:
+        raise _l.PxrError(f"{who}: item must be [B, 2] for B={B}, got {tuple(item.shape)}")
+
+
 # ------------------------------------------------------------------------------------------------ MF (csrc/mf.hip)
 def mf_pair_rows(user, item, n_users: int, n_items: int, out=None):
     """user int64 [B], item int64 [B, 2] | None -> rows int64 [3B] (or [B]) of the [1 + U + I, D] table: [1 + user | 1 + U +
     item.view(-1)].  Bad ids flag the status word (ops.raise_on_bad_indices) and are clamped."""
-    Lb = _l.load()
-    _req(user, torch.int64, "user")
     B = user.numel()
-    if item is not None:
-        _req(item, torch.int64, "item")
-        if item.numel() != 2 * B:
-            raise _l.PxrError(f"mf pair rows: item must be [B, 2] for B={B}, got {tuple(item.shape)}")
-    n = 3 * B if item is not None else B
-    rows = out if out is not None else torch.empty(n, dtype=torch.int64, device=user.device)
-    if rows.numel() != n or rows.dtype != torch.int64:
-        raise _l.PxrError(f"mf pair rows: out must be int64 [{n}]")
-    device_status(user.device)
-    _l.check(Lb.pxr_mf_pair_rows_i64(_l.ptr(user), _l.ptr(item), B, int(n_users), int(n_items), _l.ptr(rows), _l.stream_ptr()),
-             "pxr_mf_pair_rows_i64")
-    return rows
+    _pair_items("mf pair rows", item, B)
+    return _table_rows("mf pair rows", [("user", user, n_users, 1, 0), ("item", item, n_items, 1 + n_users, 0)], out,
+                       (3 * B if item is not None else B,))
 
 
 def mf_pair_fwd(ufeat, ifeat, B: int, rows=None, out=None):
@@ -2243,21 +2264,10 @@ def mf_bn_tanh_eval(x, gamma, beta, running_mean, running_var, eps=1e-5, y=None)
 def vbpr_rows(user, item, n_users: int, n_items: int, out=None):
     """user int64 [B], item int64 [B, 2] | None -> rows int64 [4B] (or [2B]) of the [1 + U + I + U, Dh] table: [1 + user | 1 + U + I
     + user | 1 + U + item.view(-1)].  Bad ids flag the status word (ops.raise_on_bad_indices) and are clamped."""
-    Lb = _l.load()
-    _req(user, torch.int64, "user")
     B = user.numel()
-    if item is not None:
-        _req(item, torch.int64, "item")
-        if item.numel() != 2 * B:
-            raise _l.PxrError(f"vbpr rows: item must be [B, 2] for B={B}, got {tuple(item.shape)}")
-    n = 4 * B if item is not None else 2 * B
-    rows = out if out is not None else torch.empty(n, dtype=torch.int64, device=user.device)
-    if rows.numel() != n or rows.dtype != torch.int64:
-        raise _l.PxrError(f"vbpr rows: out must be int64 [{n}]")
-    device_status(user.device)
-    _l.check(Lb.pxr_vbpr_rows_i64(_l.ptr(user), _l.ptr(item), B, int(n_users), int(n_items), _l.ptr(rows), _l.stream_ptr()),
-             "pxr_vbpr_rows_i64")
-    return rows
+    _pair_items("vbpr rows", item, B)
+    return _table_rows("vbpr rows", [("user", user, n_users, 1, 0), ("user", user, n_users, 1 + n_users + n_items, 0),
+                                     ("item", item, n_items, 1 + n_users, 0)], out, (4 * B if item is not None else 2 * B,))
 
 
 def vbpr_gather(feat, item, wb, out=None, beta=None, copy=True):
@@ -2373,20 +2383,9 @@ def acf_rows(profile, items, user, n_items: int, n_users: int, out=None, want_gi
     the [1 + I + U, E] table in the order profile | items | users: rows = the row an occurrence reads, gidx = the row its gradient
     goes to (0 for item id 0, the padding row).  Bad ids flag the status word (ops.raise_on_bad_indices) and are clamped.
     out: an int64 [2, n] buffer to reuse."""
-    Lb = _l.load()
-    _req(profile, torch.int64, "profile"); _req(user, torch.int64, "user")
-    n_p, n_u = profile.numel(), user.numel()
-    n_i = 0
-    if items is not None:
-        _req(items, torch.int64, "items")
-        n_i = items.numel()
-    n = n_p + n_i + n_u
-    buf = out if out is not None else torch.empty(2, n, dtype=torch.int64, device=user.device)
-    if tuple(buf.shape) != (2, n) or buf.dtype != torch.int64:
-        raise _l.PxrError(f"acf rows: out must be int64 [2, {n}]")
-    device_status(user.device)
-    _l.check(Lb.pxr_acf_rows_i64(_l.ptr(profile), n_p, _l.ptr(items), n_i, _l.ptr(user), n_u, int(n_items), int(n_users),
-                                 _l.ptr(buf[0]), _l.ptr(buf[1]) if want_gidx else None, _l.stream_ptr()), "pxr_acf_rows_i64")
+    n = profile.numel() + (items.numel() if items is not None else 0) + user.numel()
+    buf = _table_rows("acf rows", [("profile", profile, n_items, 1, 1), ("items", items, n_items, 1, 1),
+                                   ("user", user, n_users, 1 + n_items, 0)], out, (2, n), want_gidx)
     return buf[0], buf[1]
 
 
@@ -2599,16 +2598,8 @@ def din_rows(profile, target, n_items: int, out=None):
     """profile int64 [B, L], target int64 [B, 2] -> (rows, gidx) int64 [B L + 2 B] of the [1 + I, D] table (item i at row 1 + i)
     in the occurrence order history | candidates: rows = the row an occurrence reads, gidx = the row its gradient goes to (0 for
     item id 0, the padding row).  Bad ids flag the status word (ops.raise_on_bad_indices) and are clamped.  out: int64 [2, n]."""
-    Lb = _l.load()
-    _req(profile, torch.int64, "profile"); _req(target, torch.int64, "target")
-    n_p, n_i = profile.numel(), target.numel()
-    n = n_p + n_i
-    buf = out if out is not None else torch.empty(2, n, dtype=torch.int64, device=profile.device)
-    if tuple(buf.shape) != (2, n) or buf.dtype != torch.int64:
-        raise _l.PxrError(f"din rows: out must be int64 [2, {n}]")
-    device_status(profile.device)
-    _l.check(Lb.pxr_acf_rows_i64(_l.ptr(profile), n_p, _l.ptr(target), n_i, None, 0, int(n_items), 1, _l.ptr(buf[0]),
-                                 _l.ptr(buf[1]), _l.stream_ptr()), "pxr_acf_rows_i64")
+    buf = _table_rows("din rows", [("profile", profile, n_items, 1, 1), ("target", target, n_items, 1, 1)], out,
+                      (2, profile.numel() + target.numel()), True)
     return buf[0], buf[1]
 
 
@@ -2783,12 +2774,13 @@ def _pool_shapes(table, rows, B: int, L: int, n_rows: int, who: str):
     return D
 
 
-def _pool_out(t, shape, device, name: str):
+def _out_f32(t, shape, device, who: str, name: str):
+    """the caller's float32 output buffer `t`, checked against `shape`, or a new one"""
     if t is None:
         return torch.empty(*shape, dtype=torch.float32, device=device)
     _req(t, torch.float32, name)
     if tuple(t.shape) != tuple(shape):
-        raise _l.PxrError(f"pool: {name} must be float32 {list(shape)}, got {tuple(t.shape)}")
+        raise _l.PxrError(f"{who}: {name} must be float32 {list(shape)}, got {tuple(t.shape)}")
     return t
 
 
@@ -2800,8 +2792,8 @@ def pool_rows(table, rows, B: int, L: int, mean: bool, pad_row: int = 1, U=None,
     if rows.numel() < B * L:
         raise _l.PxrError(f"pool rows: rows must hold at least B L = {B * L} entries, got {rows.numel()}")
     D = _pool_shapes(table, rows, B, L, rows.numel(), "pool rows")
-    U = _pool_out(U, (B, D), table.device, "U")
-    w = _pool_out(w, (B,), table.device, "w")
+    U = _out_f32(U, (B, D), table.device, "pool", "U")
+    w = _out_f32(w, (B,), table.device, "pool", "w")
     device_status(table.device)
     _l.check(_l.load().pxr_pool_rows_f32(_l.ptr(table), table.shape[0], D, _l.ptr(rows), int(pad_row), B, L, int(bool(mean)),
                                          _l.ptr(U), _l.ptr(w), _l.stream_ptr()), "pxr_pool_rows_f32")
@@ -2815,9 +2807,9 @@ def pool_pair_fwd(table, rows, B: int, L: int, mean: bool, pad_row: int = 1, U=N
     (loss [1] = -mean log(1e-8 + sigmoid(x_b)), coef [B] = d loss / d x_b, U [B, D], w [B], lossrow [B]).  out: a float32
     [2B + 1] buffer (coef | lossrow | loss) to reuse."""
     D = _pool_shapes(table, rows, B, L, B * (L + 2), "pool pair forward")
-    U = _pool_out(U, (B, D), table.device, "U")
-    w = _pool_out(w, (B,), table.device, "w")
-    f = _pool_out(out, (2 * B + 1,), table.device, "out")
+    U = _out_f32(U, (B, D), table.device, "pool", "U")
+    w = _out_f32(w, (B,), table.device, "pool", "w")
+    f = _out_f32(out, (2 * B + 1,), table.device, "pool", "out")
     coef, lossrow, loss = f[:B], f[B:2 * B], f[2 * B:]
     device_status(table.device)
     _l.check(_l.load().pxr_pool_pair_fwd_f32(_l.ptr(table), table.shape[0], D, _l.ptr(rows), int(pad_row), B, L, int(bool(mean)),
@@ -2836,7 +2828,7 @@ def pool_pair_bwd(table, rows, B: int, L: int, U, coef, grad_scale=1.0, grad_sca
         raise _l.PxrError(f"pool pair backward: U must be [B, D] = [{B}, {D}] and coef [B]")
     if grad_scale_dev is not None:
         _req(grad_scale_dev, torch.float32, "grad_scale_dev")
-    G = _pool_out(G, (3 * B, D), table.device, "G")
+    G = _out_f32(G, (3 * B, D), table.device, "pool", "G")
     device_status(table.device)
     _l.check(_l.load().pxr_pool_pair_bwd_f32(_l.ptr(table), table.shape[0], D, _l.ptr(rows), B, L, _l.ptr(U), _l.ptr(coef),
                                              float(grad_scale), _l.ptr(grad_scale_dev), _l.ptr(G), _l.stream_ptr()),
@@ -2874,7 +2866,7 @@ def pool_dense_grad(gidx, B: int, L: int, G, w, n_rows: int, out=None):
     if B < 1 or L < 1 or gidx.numel() != n or G.dim() != 2 or G.shape[0] != 3 * B or w.numel() != B or n_rows < 1:
         raise _l.PxrError(f"pool dense grad: need gidx [B (L + 2)] = [{n}], G [3B, D], w [B] and n_rows >= 1 for B={B}, L={L}")
     D = G.shape[1]
-    d_rows = _pool_out(out, (int(n_rows), D), G.device, "d_rows")
+    d_rows = _out_f32(out, (int(n_rows), D), G.device, "pool", "d_rows")
     ws_bytes = int(Lb.pxr_embed_grad_ws_bytes(n))
     ws = _ws.get(ws_bytes, G.device)
     _l.check(Lb.pxr_pool_dense_grad_f32(_l.ptr(gidx), B, L, _l.ptr(G), _l.ptr(w), D, int(n_rows), _l.ptr(d_rows), _l.ptr(ws),
@@ -2883,15 +2875,6 @@ def pool_dense_grad(gidx, B: int, L: int, G, w, n_rows: int, out=None):
 
 
 # ------------------------------------------------------------------------------------------------ WideDeep (csrc/widedeep.hip)
-def _wd_out(t, shape, device, name: str):
-    if t is None:
-        return torch.empty(*shape, dtype=torch.float32, device=device)
-    _req(t, torch.float32, name)
-    if tuple(t.shape) != tuple(shape):
-        raise _l.PxrError(f"widedeep: {name} must be float32 {list(shape)}, got {tuple(t.shape)}")
-    return t
-
-
 def wd_join(zh, zt, b1, a1=None, der=None):
     """The split first Linear joined (pxr_wd_join_f32): zh [B, h1] the history product, zt [2 B, h1] the target product, b1 [h1] ->
     (a1 [2 B, h1] = relu(zh[r / 2] + zt[r] + b1), der = [a1 > 0])."""
@@ -2901,8 +2884,8 @@ def wd_join(zh, zt, b1, a1=None, der=None):
         raise _l.PxrError(f"widedeep join: need zh [B, h1], zt [2 B, h1], b1 [h1]; got {tuple(zh.shape)}, {tuple(zt.shape)}, "
                           f"{tuple(b1.shape)}")
     B, h1 = zh.shape
-    a1 = _wd_out(a1, (2 * B, h1), zh.device, "a1")
-    der = _wd_out(der, (2 * B, h1), zh.device, "der")
+    a1 = _out_f32(a1, (2 * B, h1), zh.device, "widedeep", "a1")
+    der = _out_f32(der, (2 * B, h1), zh.device, "widedeep", "der")
     _l.check(_l.load().pxr_wd_join_f32(_l.ptr(zh), _l.ptr(zt), _l.ptr(b1), B, h1, _l.ptr(a1), _l.ptr(der), _l.stream_ptr()),
              "pxr_wd_join_f32")
     return a1, der
@@ -2914,7 +2897,7 @@ def wd_join_bwd(dz1, dzh=None):
     if dz1.dim() != 2 or dz1.shape[0] % 2:
         raise _l.PxrError(f"widedeep join backward: dz1 must be [2 B, h1], got {tuple(dz1.shape)}")
     B, h1 = dz1.shape[0] // 2, dz1.shape[1]
-    dzh = _wd_out(dzh, (B, h1), dz1.device, "dzh")
+    dzh = _out_f32(dzh, (B, h1), dz1.device, "widedeep", "dzh")
     _l.check(_l.load().pxr_wd_join_bwd_f32(_l.ptr(dz1), B, h1, _l.ptr(dzh), _l.stream_ptr()), "pxr_wd_join_bwd_f32")
     return dzh
 
@@ -2932,7 +2915,7 @@ def wd_head_fwd(alast, wp, wide, target, head=None):
     (loss [1], head [1 + 2 B] = loss | coef | x).  A bad target flags the status word (ops.raise_on_bad_indices) and is clamped."""
     B, hl = _wd_head_shapes(alast, wp, target, "widedeep head")
     _req(wide, torch.float32, "wide")
-    head = _wd_out(head, (1 + 2 * B,), alast.device, "head")
+    head = _out_f32(head, (1 + 2 * B,), alast.device, "widedeep", "head")
     device_status(alast.device)
     _l.check(_l.load().pxr_wd_head_fwd_f32(_l.ptr(alast), _l.ptr(wp), _l.ptr(wide), wide.numel(), _l.ptr(target), B, hl,
                                            _l.ptr(head), _l.stream_ptr()), "pxr_wd_head_fwd_f32")
@@ -2948,7 +2931,7 @@ def wd_head_bwd(alast, dact, wp, target, head, dwp, dbp, dwide, dwide_bias, grad
     if dact.shape != alast.shape or head.numel() != 1 + 2 * B or dwp.numel() != hl or dbp.numel() != 1 or dwide_bias.numel() != 1:
         raise _l.PxrError("widedeep head backward: dact must be [2 B, hl], head [1 + 2 B], dwp [hl], dbp / dwide_bias [1]")
     gsd = grad_scale_dev if grad_scale_dev is not None else torch.ones(1, dtype=torch.float32, device=alast.device)
-    dz = _wd_out(dz, (2 * B, hl), alast.device, "dz")
+    dz = _out_f32(dz, (2 * B, hl), alast.device, "widedeep", "dz")
     _l.check(_l.load().pxr_wd_head_bwd_f32(_l.ptr(alast), _l.ptr(dact), _l.ptr(wp), _l.ptr(target), dwide.numel(), _l.ptr(head), B, hl,
                                            float(grad_scale), _l.ptr(gsd), _l.ptr(dz), _l.ptr(dwp), _l.ptr(dbp), _l.ptr(dwide),
                                            _l.ptr(dwide_bias), _l.stream_ptr()), "pxr_wd_head_bwd_f32")

@@ -9,6 +9,23 @@ META_KEYS = ("n_items", "D", "L", "H", "inner", "n_layers", "B", "seed")
 CASES = ("tiny", "cfg1", "ns")
 
 
+def rec_bits(**tensors):
+    """The record of the bit-for-bit fixtures (tests/golden/*_bits.json): integer tensors in full; float tensors, which must be
+    finite, as [u32 sum, u32 sum weighted by index + 1] of the bit patterns (the second catches a permutation)."""
+    torch.cuda.synchronize()
+    out = {}
+    for name, t in tensors.items():
+        t = t.detach().cpu().contiguous().reshape(-1)
+        if t.dtype == torch.float32:
+            assert bool(torch.isfinite(t).all()), name
+            bits = t.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+            w = (bits * torch.arange(1, bits.numel() + 1, dtype=torch.int64)) & 0xFFFFFFFF     # < 2^32 * 2^21: no overflow
+            out[name] = {"u32_sum": int(bits.sum()) & 0xFFFFFFFF, "u32_wsum": int(w.sum()) & 0xFFFFFFFF}
+        else:
+            out[name] = t.to(torch.int64).tolist()
+    return out
+
+
 def load_case(name):
     z = np.load(os.path.join(GOLDEN_DIR, f"sasrec_{name}.npz"), allow_pickle=False)
     meta = dict(zip(META_KEYS, [int(x) for x in z["meta"]]))

@@ -21,7 +21,8 @@ def test_library_loads_and_reports_target():
     # general argument lists of their planes / h2 / bidirectional / id-layout twins, which are gone (0.3.0: the `stat` buffers of
     # pxr_ln_bwd_stat_f32 / pxr_attn_bwd_stat_f32 changed size under unchanged names)
     hdr = int(re.search(r"#define\s+PXR_ABI_VERSION\s+(\d+)", open(os.path.join(ROOT, "include", "pxr.h")).read()).group(1))
-    assert hdr == lib.ABI_VERSION == L.pxr_version() == 301
+    # 0.3.2: pxr_table_rows_i64 over segment descriptors replaced the three per-model row entries
+    assert hdr == lib.ABI_VERSION == L.pxr_version() == 302
     assert L.pxr_target_arch() == b"gfx950"
 
 

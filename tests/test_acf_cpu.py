@@ -245,7 +245,14 @@ def test_kernel_shape_limits_fail_loudly_without_a_gpu():
     assert b"regions" in L.pxr_last_error()
     assert L.pxr_acf_item_fwd_f32(one, one, one, one, one, one, 2, 3, 6, one, one, None) == -1
     assert b"E % 4" in L.pxr_last_error()
-    assert L.pxr_acf_rows_i64(None, 4, None, 0, one, 2, 5, 5, one, None, None) == -1
+    from pixelrec_amd import ops
+
+    segs = (ops._CRowSegment * 3)()                 # profile: a null id list with a positive count | no items | two users
+    segs[0].count, segs[0].n, segs[0].base, segs[0].pad0 = 4, 5, 1, 1
+    segs[1].n, segs[1].base, segs[1].pad0 = 5, 1, 1
+    segs[2].ids, segs[2].count, segs[2].n, segs[2].base = one, 2, 5, 6
+    assert L.pxr_table_rows_i64(segs, 3, one, None, None) == -1
+    assert b"null id list" in L.pxr_last_error()
 
 
 def test_acf_is_registered_and_the_yaml_parses():

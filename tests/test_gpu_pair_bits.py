@@ -39,20 +39,9 @@ SCALES = {"g1": (1.0, None), "g0.3x0.7": (0.3, 0.7)}
 BAD_INDEX = 1                                              # PXR_STATUS_BAD_INDEX
 
 
-def _rec(**tensors):
-    """integer tensors in full; float tensors as [u32 sum, u32 sum weighted by index + 1] of the bit patterns"""
-    torch.cuda.synchronize()
-    out = {}
-    for name, t in tensors.items():
-        t = t.detach().cpu().contiguous().reshape(-1)
-        if t.dtype == torch.float32:
-            assert bool(torch.isfinite(t).all()), name
-            bits = t.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-            w = (bits * torch.arange(1, bits.numel() + 1, dtype=torch.int64)) & 0xFFFFFFFF     # < 2^32 * 2^21: no overflow
-            out[name] = {"u32_sum": int(bits.sum()) & 0xFFFFFFFF, "u32_wsum": int(w.sum()) & 0xFFFFFFFF}
-        else:
-            out[name] = t.to(torch.int64).tolist()
-    return out
+if __name__ == "__main__":
+    sys.path.insert(0, ROOT)
+from tests.golden_util import rec_bits as _rec  # noqa: E402   (shared with tests/test_gpu_seq_head_bits.py)
 
 
 def _clean():
@@ -340,7 +329,6 @@ def test_bits_of_the_separate_copies_are_kept(group, golden):
 
 
 if __name__ == "__main__":
-    sys.path.insert(0, ROOT)
     assert len(sys.argv) == 3 and sys.argv[1] == "--record", "usage: test_gpu_pair_bits.py --record FILE"
     cases = {}
     for make in GROUPS.values():
