@@ -871,6 +871,12 @@ int pxr_din_att_input_f32(const float* table, const int64_t* rows, int B, int L,
  * B (L + 2) gathered rows (padding positions included), reduced in one fixed order. */
 int pxr_din_head_fwd_f32(const float* alast, const float* wd, const float* bd, const float* emb, const int64_t* profile, int B,
                          int L, int D, int hl, float* s, float* kq, float* head, void* stream);
+/* The same head with the regulariser's weight as an argument (PixelNet/modin.py:61: MODIN's loss is the first term alone, reg = 0;
+ * IDNet/din.py:79: reg = 0.01, and the entry above is this one with that value, bit for bit): loss = -mean log(sigmoid(x) + 1e-8) +
+ * reg ||emb||_2 / B and head[1] = reg / (B ||emb||_2), which is 0 when reg == 0 or the norm is 0 -- pxr_din_fold_bwd_f32 then adds an
+ * exact zero.  The head layout does not depend on reg.  reg >= 0 and finite. */
+int pxr_din_head_fwd_reg_f32(const float* alast, const float* wd, const float* bd, const float* emb, const int64_t* profile, int B,
+                             int L, int D, int hl, float* s, float* kq, float* head, float reg, void* stream);
 /* Head backward, first half (autograd of the above down to the last hidden layer): g = grad_scale * grad_scale_dev[0];
  * dsraw[r] = the gradient of dense's output (0 at padding), dz [2 B L, hl] = dsraw wd act' (dact = the derivative the forward
  * GEMM saved), dwd [hl] and dbd [1] = the gradients of attention.dense, summed over r in one fixed order. */
@@ -948,6 +954,16 @@ int pxr_pool_table_grad_f32(const int64_t* gidx, int B, int L, const float* G, c
  * ws: pxr_embed_grad_ws_bytes(B (L + 2)) (it also holds the unique-row list).  d_rows must not overlap G. */
 int pxr_pool_dense_grad_f32(const int64_t* gidx, int B, int L, const float* G, const float* w, int D, int64_t n_rows, float* d_rows,
                             void* ws, int64_t ws_bytes, void* stream);
+/* The dense sink for plain occurrence rows (PixelNet/modin.py:45-61 under autograd: DIN's backward leaves one gradient row per
+ * occurrence, and the rows they belong to are visual_encoder outputs of the batch's distinct images): idx int64 [n] holds rows of an
+ * [n_rows, D] matrix, rows [n, D] one gradient row per occurrence.  d_rows[row, :] for every referenced row in (0, n_rows) is bit
+ * for bit what pxr_embed_grad_rows_f32 (scale 1) puts into uniq_rows for that id -- the same sort, the same segment sums in the
+ * same order, another sink; every other row of d_rows [n_rows, D] (row 0, unreferenced rows) is exactly +0.0 when the call returns,
+ * whatever it held before: the entry zeroes the block itself, on the same stream.  Ids equal to 0 or outside [0, n_rows) are
+ * dropped.  No float atomics.  Limits: D % 4 == 0, 0 < D <= 4096, 0 < n < 2^30, 16-byte aligned rows and d_rows;
+ * ws: pxr_embed_grad_ws_bytes(n) (it also holds the unique-row list and its count).  d_rows must not overlap rows. */
+int pxr_embed_grad_dense_f32(const int64_t* idx, int64_t n, const float* rows, int D, int64_t n_rows, float* d_rows, void* ws,
+                             int64_t ws_bytes, void* stream);
 
 /* ---- WideDeep (model/IDNet/widedeep.py with MLPLayers, model/layers.py:239-281; csrc/widedeep.hip) ------------------------- */
 /* Rows of every [2 B, *] operand: r = 2 b + c, c = 0 the plane [profile_b | positive], c = 1 the plane [profile_b | negative]

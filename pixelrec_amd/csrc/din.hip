@@ -112,8 +112,9 @@ __global__ void __launch_bounds__(64) din_head_fwd_kernel(DinHeadArgs a) {
   }
 }
 
-// one workgroup: loss = -mean log(sigmoid(x) + 1e-8) + 0.01 sqrt(sum ssq) / B; coef[b] = d loss / d x_b; head[1] = 0.01 / (B norm)
-__global__ void __launch_bounds__(256) din_loss_kernel(float* __restrict__ head, int B) {
+// one workgroup: loss = -mean log(sigmoid(x) + 1e-8) + reg sqrt(sum ssq) / B; coef[b] = d loss / d x_b; head[1] = reg / (B norm)
+// (reg: DIN's 0.01, din.py:79; MODIN's 0, modin.py:61 -- head[1] is then +0.0 and the fold adds an exact zero)
+__global__ void __launch_bounds__(256) din_loss_kernel(float* __restrict__ head, int B, float reg) {
   __shared__ float red[256];
   float t = 0.f, q = 0.f;
   for (int b = threadIdx.x; b < B; b += 256) {
@@ -126,8 +127,8 @@ __global__ void __launch_bounds__(256) din_loss_kernel(float* __restrict__ head,
   q = block_sum256(q, red);
   if (threadIdx.x == 0) {
     const float nrm = sqrtf(q);
-    head[0] = -t / (float)B + 0.01f * nrm / (float)B;
-    head[1] = nrm > 0.f ? 0.01f / ((float)B * nrm) : 0.f;
+    head[0] = -t / (float)B + reg * nrm / (float)B;
+    head[1] = nrm > 0.f ? reg / ((float)B * nrm) : 0.f;
   }
 }
 
@@ -397,20 +398,30 @@ static int din_head_shape_ok(const char* who, int B, int L, int D, int hl) {
   return PXR_OK;
 }
 
-extern "C" int pxr_din_head_fwd_f32(const float* alast, const float* wd, const float* bd, const float* emb, const int64_t* profile,
-                                    int B, int L, int D, int hl, float* s, float* kq, float* head, void* stream) {
-  PXR_REQUIRE(alast && wd && bd && emb && profile && s && kq && head, "pxr_din_head_fwd_f32: null pointer");
-  if (int rc = din_head_shape_ok("pxr_din_head_fwd_f32", B, L, D, hl)) return rc;
-  PXR_REQUIRE(dn_aligned(emb), "pxr_din_head_fwd_f32: emb must be 16-byte aligned");
+// The head with the regulariser's weight as an argument: loss = -mean log(sigmoid(x) + 1e-8) + reg ||emb||_2 / B, head[1] =
+// reg / (B ||emb||_2) (0 when reg == 0 or the norm is 0).  The head layout does not depend on reg.
+extern "C" int pxr_din_head_fwd_reg_f32(const float* alast, const float* wd, const float* bd, const float* emb, const int64_t* profile,
+                                        int B, int L, int D, int hl, float* s, float* kq, float* head, float reg,
+                                        void* stream) {
+  PXR_REQUIRE(alast && wd && bd && emb && profile && s && kq && head, "pxr_din_head_fwd_reg_f32: null pointer");
+  if (int rc = din_head_shape_ok("pxr_din_head_fwd_reg_f32", B, L, D, hl)) return rc;
+  PXR_REQUIRE(reg >= 0.f && reg < INFINITY, "pxr_din_head_fwd_reg_f32: reg must be finite and >= 0");
+  PXR_REQUIRE(dn_aligned(emb), "pxr_din_head_fwd_reg_f32: emb must be 16-byte aligned");
   DinHeadArgs a{};
   a.alast = alast; a.wd = wd; a.bd = bd; a.emb = (const df4*)emb; a.profile = profile; a.s = s; a.kq = kq; a.head = head;
   a.B = B; a.L = L; a.dv = D / 4; a.hl = hl; a.sqrt_d = sqrtf((float)D);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(din_head_fwd_kernel, dim3((unsigned)B), dim3(64), 0, st, a);
-  int rc = pxr_check_launch("pxr_din_head_fwd_f32");
+  int rc = pxr_check_launch("pxr_din_head_fwd_reg_f32");
   if (rc) return rc;
-  hipLaunchKernelGGL(din_loss_kernel, dim3(1), dim3(256), 0, st, head, B);
-  return pxr_check_launch("pxr_din_head_fwd_f32 (loss)");
+  hipLaunchKernelGGL(din_loss_kernel, dim3(1), dim3(256), 0, st, head, B, reg);
+  return pxr_check_launch("pxr_din_head_fwd_reg_f32 (loss)");
+}
+
+// DIN's head: the regulariser of din.py:79
+extern "C" int pxr_din_head_fwd_f32(const float* alast, const float* wd, const float* bd, const float* emb, const int64_t* profile,
+                                    int B, int L, int D, int hl, float* s, float* kq, float* head, void* stream) {
+  return pxr_din_head_fwd_reg_f32(alast, wd, bd, emb, profile, B, L, D, hl, s, kq, head, 0.01f, stream);
 }
 
 extern "C" int pxr_din_head_bwd_f32(const float* alast, const float* dact, const float* wd, const int64_t* profile, const float* kq,

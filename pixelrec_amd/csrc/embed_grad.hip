@@ -8,7 +8,8 @@
 // result is bit-reproducible (no float atomics) and identical on every rank given identical inputs.
 //
 // Occurrences (what autograd would scatter-add):
-//   MODE_ROWS   : occurrence o adds  rows[o, :]                       to table row idx[o]   (plain embedding bwd)
+//   MODE_ROWS   : occurrence o adds  rows[o, :]                       to table row idx[o]   (plain embedding bwd); into sparse
+//        rows (pxr_embed_grad_rows_f32) or, over a batch-local row space, into a dense block (pxr_embed_grad_dense_f32: MODIN)
 //   MODE_SASREC : the three uses of the table in SASRec.forward (sasrec.py:68-74,88-89), T = B*L, r = o % T:
 //        o in [0,T)    input  id items[b,0,t]     adds  dx0[r,:]                 (grad of the LN'd input)
 //        o in [T,2T)   target id items[b,0,t+1]   adds  +coef[r] * out[r,:]      (d pos_score)
@@ -808,9 +809,11 @@ __global__ void __launch_bounds__(256) dense_zero_kernel(float4* __restrict__ p,
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) p[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// MODE_POOL's segment sums into a dense block (SegStoreDense): the sums and their order are segsum_kernel<MODE_POOL>'s.
+// MODE's segment sums into a dense block (SegStoreDense): the sums and their order are segsum_kernel<MODE>'s (MODE_POOL: the
+// pooled pair models' compact block; MODE_ROWS: one gradient row per occurrence).
+template <int MODE>
 __global__ void __launch_bounds__(SEG_THREADS) segsum_dense_kernel(SegSumArgs a, SegStoreDense s) {
-  segsum_body<MODE_POOL>(a, s, (int)gridDim.x);
+  segsum_body<MODE>(a, s, (int)gridDim.x);
 }
 
 // ---- very long segments on many workgroups (round 5) --------------------------------------------------------------------------
@@ -1165,29 +1168,21 @@ extern "C" int pxr_pool_table_grad_f32(const int64_t* gidx, int B, int L, const 
   return pxr_check_launch("pxr_pool_table_grad_f32");
 }
 
-// The same gradient as a DENSE block over a batch-local row space (the pixel versions of the pooled pair models: the rows are the
-// visual encoder's outputs for the batch's distinct images): d_rows [n_rows, D] gets the segment sum of every referenced row in
-// (0, n_rows) -- pxr_pool_table_grad_f32's sums bit for bit (the same sort, segsum_body<MODE_POOL>, another sink) -- and exactly
-// +0.0 everywhere else (row 0 and every unreferenced row), whatever it held before: the block is zeroed here, by a launch in front of
-// the segment sums on the same stream.  The unique-row list the sort needs lives in the workspace: the four key / value buffers are
-// handed to the sort as (keysA, valsA | keysB, valsB), so the ping-pong pair that does not hold the final order is one contiguous
-// stretch of >= 8 n bytes, and the count takes the spare last entry of the block-count buffer.
-extern "C" int pxr_pool_dense_grad_f32(const int64_t* gidx, int B, int L, const float* G, const float* w, int D, int64_t n_rows,
-                                       float* d_rows, void* ws, int64_t ws_bytes, void* stream) {
-  PXR_REQUIRE(gidx && G && w && d_rows && ws, "pxr_pool_dense_grad_f32: null pointer");
-  PXR_REQUIRE(B > 0 && L >= 1 && (int64_t)B * (L + 2) < (1ll << 30) && D > 0 && D % 4 == 0 && D <= 4096 && n_rows > 0 &&
-              n_rows < (1ll << 31), "pxr_pool_dense_grad_f32: bad shape (B=%d, L=%d, D=%d)", B, L, D);
-  PXR_REQUIRE((((uintptr_t)G | (uintptr_t)d_rows) & 15) == 0, "pxr_pool_dense_grad_f32: G and d_rows must be 16-byte aligned");
-  const char *g0 = (const char*)G, *g1 = g0 + (int64_t)3 * B * D * 4, *d0 = (const char*)d_rows, *d1 = d0 + n_rows * D * 4;
-  PXR_REQUIRE(d1 <= g0 || g1 <= d0, "pxr_pool_dense_grad_f32: d_rows must not alias G");
-  const int n = B * (L + 2);
+// What the two dense entries share: zero d_rows [n_rows, D], sort gidx [n] exactly as pxr_embed_grad_rows_f32 sorts its idx, and
+// run segsum_body<MODE> over `a` (the caller has filled the sources) into the dense sink.  The unique-row list the sort needs lives
+// in the workspace: the four key / value buffers are handed to the sort as (keysA, valsA | keysB, valsB), so the ping-pong pair
+// that does not hold the final order is one contiguous stretch of >= 8 n bytes, and the count takes the spare last entry of the
+// block-count buffer.
+template <int MODE>
+static int dense_grad(const char* who, const int64_t* gidx, int n, SegSumArgs a, int64_t n_rows, float* d_rows, void* ws,
+                      int64_t ws_bytes, hipStream_t st) {
+  const int D = a.D;
   SortWs sw;
-  if (carve(ws, n, &sw) > ws_bytes) { pxr_set_error("pxr_pool_dense_grad_f32: workspace too small"); return PXR_ERR_WORKSPACE; }
+  if (carve(ws, n, &sw) > ws_bytes) { pxr_set_error("%s: workspace too small", who); return PXR_ERR_WORKSPACE; }
   { int* t = sw.keysB; sw.keysB = sw.valsA; sw.valsA = t; }     // slots (0, 1) = pair A, (2, 3) = pair B
   const int* final_vals = sasrec_sorted_vals(sw, n, n_rows);
   int64_t* uniq_idx = (int64_t*)(final_vals == sw.valsB ? sw.keysA : sw.keysB);
   int32_t* n_uniq_dev = sw.blk + sw.nblk;
-  hipStream_t st = (hipStream_t)stream;
   const int64_t n4 = n_rows * (D / 4);
   hipLaunchKernelGGL(dense_zero_kernel, dim3((unsigned)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096)), dim3(256), 0, st, (float4*)d_rows, n4);
   const int* sorted_vals = nullptr;
@@ -1199,15 +1194,48 @@ extern "C" int pxr_pool_dense_grad_f32(const int64_t* gidx, int B, int L, const 
     rc = sort_and_segment(sw, n, n_rows, uniq_idx, n_uniq_dev, st, &sorted_vals);
   }
   if (rc) return rc;
-  if (sorted_vals != final_vals) { pxr_set_error("pxr_pool_dense_grad_f32: internal buffer parity"); return PXR_ERR_LAUNCH; }
-  SegSumArgs a{};
-  a.vals = sorted_vals; a.seg_start = sw.seg_start; a.n_uniq = n_uniq_dev; a.src0 = G; a.coef = w;
-  a.scale = 1.f; a.D = D; a.T = B * L; a.L = L;
+  if (sorted_vals != final_vals) { pxr_set_error("%s: internal buffer parity", who); return PXR_ERR_LAUNCH; }
+  a.vals = sorted_vals; a.seg_start = sw.seg_start; a.n_uniq = n_uniq_dev;
   SegStoreDense s{};
   s.d_rows = d_rows; s.uniq_idx = uniq_idx; s.n_rows = n_rows; s.D = D;
   const int grid = n < 4096 ? n : 4096;
-  hipLaunchKernelGGL(segsum_dense_kernel, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, st, a, s);
-  return pxr_check_launch("pxr_pool_dense_grad_f32");
+  hipLaunchKernelGGL(segsum_dense_kernel<MODE>, dim3(grid), dim3(SEG_THREADS), SEG_THREADS * 16, st, a, s);
+  return pxr_check_launch(who);
+}
+
+// The same gradient as a DENSE block over a batch-local row space (the pixel versions of the pooled pair models: the rows are the
+// visual encoder's outputs for the batch's distinct images): d_rows [n_rows, D] gets the segment sum of every referenced row in
+// (0, n_rows) -- pxr_pool_table_grad_f32's sums bit for bit (the same sort, segsum_body<MODE_POOL>, another sink) -- and exactly
+// +0.0 everywhere else (row 0 and every unreferenced row), whatever it held before: the block is zeroed here, by a launch in front of
+// the segment sums on the same stream (dense_grad).
+extern "C" int pxr_pool_dense_grad_f32(const int64_t* gidx, int B, int L, const float* G, const float* w, int D, int64_t n_rows,
+                                       float* d_rows, void* ws, int64_t ws_bytes, void* stream) {
+  PXR_REQUIRE(gidx && G && w && d_rows && ws, "pxr_pool_dense_grad_f32: null pointer");
+  PXR_REQUIRE(B > 0 && L >= 1 && (int64_t)B * (L + 2) < (1ll << 30) && D > 0 && D % 4 == 0 && D <= 4096 && n_rows > 0 &&
+              n_rows < (1ll << 31), "pxr_pool_dense_grad_f32: bad shape (B=%d, L=%d, D=%d)", B, L, D);
+  PXR_REQUIRE((((uintptr_t)G | (uintptr_t)d_rows) & 15) == 0, "pxr_pool_dense_grad_f32: G and d_rows must be 16-byte aligned");
+  const char *g0 = (const char*)G, *g1 = g0 + (int64_t)3 * B * D * 4, *d0 = (const char*)d_rows, *d1 = d0 + n_rows * D * 4;
+  PXR_REQUIRE(d1 <= g0 || g1 <= d0, "pxr_pool_dense_grad_f32: d_rows must not alias G");
+  SegSumArgs a{};
+  a.src0 = G; a.coef = w; a.scale = 1.f; a.D = D; a.T = B * L; a.L = L;
+  return dense_grad<MODE_POOL>("pxr_pool_dense_grad_f32", gidx, B * (L + 2), a, n_rows, d_rows, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// pxr_embed_grad_rows_f32's sums (scale 1) as a DENSE block over a batch-local row space (MODIN: DIN's backward leaves one gradient
+// row per occurrence, and the rows are the visual encoder's outputs): d_rows [n_rows, D] gets, at every referenced row in
+// (0, n_rows), the sparse entry's sum bit for bit -- the same sort, segsum_body<MODE_ROWS>, the dense sink -- and exactly +0.0
+// everywhere else, whatever it held before (zeroed here, on the same stream).  idx == 0 and ids outside [0, n_rows) are dropped.
+extern "C" int pxr_embed_grad_dense_f32(const int64_t* idx, int64_t n, const float* rows, int D, int64_t n_rows, float* d_rows,
+                                        void* ws, int64_t ws_bytes, void* stream) {
+  PXR_REQUIRE(idx && rows && d_rows && ws, "pxr_embed_grad_dense_f32: null pointer");
+  PXR_REQUIRE(n > 0 && n < (1ll << 30) && D > 0 && D % 4 == 0 && D <= 4096 && n_rows > 0 && n_rows < (1ll << 31),
+              "pxr_embed_grad_dense_f32: bad shape (n=%lld, D=%d)", (long long)n, D);
+  PXR_REQUIRE((((uintptr_t)rows | (uintptr_t)d_rows) & 15) == 0, "pxr_embed_grad_dense_f32: rows and d_rows must be 16-byte aligned");
+  const char *g0 = (const char*)rows, *g1 = g0 + n * D * 4, *d0 = (const char*)d_rows, *d1 = d0 + n_rows * D * 4;
+  PXR_REQUIRE(d1 <= g0 || g1 <= d0, "pxr_embed_grad_dense_f32: d_rows must not alias rows");
+  SegSumArgs a{};
+  a.src0 = rows; a.scale = 1.f; a.D = D; a.T = (int)n;
+  return dense_grad<MODE_ROWS>("pxr_embed_grad_dense_f32", idx, (int)n, a, n_rows, d_rows, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // Phase 1 of the table gradient: occurrence keys -> stable sort -> unique ids + segments.  Depends on `items` only, so it can

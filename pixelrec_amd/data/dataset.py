@@ -355,6 +355,16 @@ class DinTrainBatcher(SampleAcfTrainBatcher):
         return profile, np.ascontiguousarray(tail[:, :2])
 
 
+def positions_into_distinct_images(profile, target):
+    """(profile [S, L], target [S, 2]) item ids -> (index int64 [S, L + 2] = [profile | positive | negative], image_ids int64 [M]):
+    image_ids[0] == 0 (the zero image, "no item"), image_ids[1:] the batch's distinct item ids, ascending; `index` holds positions
+    into image_ids."""
+    items = np.concatenate((profile, target), axis=1)
+    uniq = np.unique(items)
+    image_ids = np.concatenate((np.zeros(1, dtype=np.int64), uniq[uniq != 0]))
+    return np.searchsorted(image_ids, items), image_ids
+
+
 class MoPoolTrainBatcher(DinTrainBatcher):
     """Vectorised MOSampleTwoTowerTrainDataset / MOSampleOneTowerTrainDataset + mosampletower_train_collate (reference
     REC/data/dataset/trainset.py:656-813, collate_fn.py:95-107) for MODSSM and MOFM.  A batch is `train_batch_size` whole SEQ chunks
@@ -381,11 +391,7 @@ class MoPoolTrainBatcher(DinTrainBatcher):
     def make_batch(self, chunks, rng):
         lens = self.lens[chunks]
         rows = np.repeat(self.first[chunks] - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()), dtype=np.int64)
-        profile, target = super().make_batch(rows, rng)
-        items = np.concatenate((profile, target), axis=1)             # [S, L + 2] item ids
-        uniq = np.unique(items)
-        image_ids = np.concatenate((np.zeros(1, dtype=np.int64), uniq[uniq != 0]))
-        return np.searchsorted(image_ids, items), image_ids
+        return positions_into_distinct_images(*super().make_batch(rows, rng))
 
     def __iter__(self):
         idx = self._indices()
@@ -449,6 +455,22 @@ class CuratorTrainBatcher:
         for b in range(len(self)):
             profile, target = self.make_batch(idx[b * self.batch_size:(b + 1) * self.batch_size], rng)
             yield torch.from_numpy(profile), torch.from_numpy(target)
+
+
+class MoTowerTrainBatcher(CuratorTrainBatcher):
+    """Vectorised MOTwoTowerTrainDataset (reference REC/data/utils.py:44 maps MODIN to it) over the SEQ chunks: CuratorTrainBatcher's
+    samples -- one per chunk: the chunk without its last item is the profile, the last item the positive, one negative outside the
+    chunk, the rng keyed by (seed, epoch, rank) -- as positions into the batch's distinct images.  The reference's dataset returns
+    the images alone while MODIN.forward unpacks (items_modal, items); here the batcher carries the ids.
+
+    Yields (index int64 [B, L + 2] = [profile | positive | negative], image_ids int64 [M]) with MoPoolTrainBatcher's batch-wide
+    dedup: image_ids[0] == 0 (the zero image, "no item"), image_ids[1:] the batch's distinct item ids, ascending; `index` holds
+    positions into image_ids, so each distinct image is fetched and encoded once per batch."""
+
+    def make_batch(self, rows, rng):
+        return positions_into_distinct_images(*super().make_batch(rows, rng))
+
+    __iter__ = MoPoolTrainBatcher.__iter__
 
 
 class SeqEvalDataset(Dataset):

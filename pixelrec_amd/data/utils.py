@@ -14,14 +14,15 @@ from torch.utils.data import DataLoader
 
 from ..parallel import world_info
 from .dataload import Data
-from .dataset import (AcfEvalBatcher, BERT4RecTrainBatcher, CuratorTrainBatcher, DinTrainBatcher, GraphEvalBatcher, GraphTrainBatcher, MoPoolTrainBatcher, PairEvalBatcher, PairTrainBatcher, SeqEvalBatcher,
+from .dataset import (AcfEvalBatcher, BERT4RecTrainBatcher, CuratorTrainBatcher, DinTrainBatcher, GraphEvalBatcher, GraphTrainBatcher, MoPoolTrainBatcher, MoTowerTrainBatcher, PairEvalBatcher, PairTrainBatcher, SeqEvalBatcher,
                       SampleAcfTrainBatcher, SeqEvalDataset, SeqTrainBatcher, TwoTowerTrainBatcher, VisRankEvalBatcher, _NoTraining,
                       seq_eval_collate)
 
 SUPPORTED = {"SASRec": "SEQ", "MOSASRec": "SEQ", "FSASRec": "SEQ", "GRU4Rec": "SEQ", "NextItNet": "SEQ",
              "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR", "MF": "PAIR", "VBPR": "PAIR",
              "SRGNN": "AUGSEQ", "LightSANs": "TWOTOWER", "ACF": "SEQ", "VISRANK": "EVALONLY", "CuratorNet": "SEQ", "DIN": "SEQ",
-             "DSSM": "SEQ", "FM": "SEQ", "WideDeep": "SEQ", "MODSSM": "SEQ", "MOFM": "SEQ"}      # REC/data/utils.py:24-33
+             "DSSM": "SEQ", "FM": "SEQ", "WideDeep": "SEQ", "MODSSM": "SEQ", "MOFM": "SEQ",
+             "MODIN": "SEQ"}      # REC/data/utils.py:24-33
 
 
 def load_data(config):
@@ -102,11 +103,12 @@ def bulid_dataloader(config, dataload):
     # samples without the user id -- a batch is `train_batch_size` samples (ACF's decision) where the reference stacks
     # `train_batch_size` chunks; evaluation is SeqEvalDataset's for all of them (DIN: CandiEvalDataset's per-item repetition happens
     # inside the kernel); MODSSM and MOFM (MOSampleTwoTowerTrainDataset / MOSampleOneTowerTrainDataset) read the same samples by
-    # whole chunks, as positions into the batch's distinct images (MoPoolTrainBatcher)
+    # whole chunks, as positions into the batch's distinct images (MoPoolTrainBatcher); MODIN (:44 MOTwoTowerTrainDataset) reads
+    # CuratorNet's one sample per chunk in the same positional form (MoTowerTrainBatcher)
     batcher = {"BERT4Rec": BERT4RecTrainBatcher, "LightSANs": TwoTowerTrainBatcher,
                "ACF": SampleAcfTrainBatcher, "CuratorNet": CuratorTrainBatcher, "DIN": DinTrainBatcher, "DSSM": DinTrainBatcher,
                "FM": DinTrainBatcher, "WideDeep": CuratorTrainBatcher, "MODSSM": MoPoolTrainBatcher,
-               "MOFM": MoPoolTrainBatcher}.get(model_name, SeqTrainBatcher)
+               "MOFM": MoPoolTrainBatcher, "MODIN": MoTowerTrainBatcher}.get(model_name, SeqTrainBatcher)
     train_loader = _TrainLoader(batcher(config, dataload, rank=rank, world=world))
     if model_name == "ACF":
         # SampleACFTrainDataset / ACFEvalDataset (REC/data/utils.py:24-31): leave-one-out samples of the chunks; windows + user id

@@ -179,6 +179,7 @@ _SIGNATURES = {
     "pxr_visrank_topk_f32": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I64, _P]),
     "pxr_din_att_input_f32": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "pxr_din_head_fwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "pxr_din_head_fwd_reg_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _F, _P]),
     "pxr_din_head_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
     "pxr_din_fold_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P]),
     "pxr_din_fold_w1_f32": (_I, [_P, _I, _I, _P, _P, _P, _P]),
@@ -189,6 +190,7 @@ _SIGNATURES = {
     "pxr_pool_pair_bwd_f32": (_I, [_P, _I64, _I, _P, _I, _I, _P, _P, _F, _P, _P, _P]),
     "pxr_pool_table_grad_f32": (_I, [_P, _I, _I, _P, _P, _I, _I64, _P, _P, _P, _P, _I64, _P]),
     "pxr_pool_dense_grad_f32": (_I, [_P, _I, _I, _P, _P, _I, _I64, _P, _P, _I64, _P]),
+    "pxr_embed_grad_dense_f32": (_I, [_P, _I64, _P, _I, _I64, _P, _P, _I64, _P]),
     "pxr_wd_join_f32": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     "pxr_wd_join_bwd_f32": (_I, [_P, _I, _I, _P, _P]),
     "pxr_wd_head_fwd_f32": (_I, [_P, _P, _P, _I64, _P, _I, _I, _P, _P]),

@@ -1426,6 +1426,26 @@ def embed_grad_rows(idx, rows, n_table, scale=1.0, out: SparseRows | None = None
     return sp
 
 
+def embed_grad_dense(idx, rows, n_rows: int, out=None):
+    """embed_grad_rows (scale 1) as a dense block over a batch-local row space (pxr_embed_grad_dense_f32): idx int64 [n] holds rows
+    of an [n_rows, D] matrix (0 = "no item", dropped; ids outside [0, n_rows) dropped), rows [n, D] one gradient row per occurrence
+    -> d_rows float32 [n_rows, D]: embed_grad_rows' row sums, bit for bit, at their rows and exactly +0.0 everywhere else (row 0,
+    unreferenced rows), whatever `out` held before."""
+    Lb = _l.load()
+    _req(idx, torch.int64, "idx"); _req(rows, torch.float32, "rows")
+    n = idx.numel()
+    if n < 1 or rows.dim() != 2 or rows.shape[0] != n or n_rows < 1:
+        raise _l.PxrError(f"embed grad dense: need idx [n], rows [n, D] and n_rows >= 1, got idx {tuple(idx.shape)}, rows {tuple(rows.shape)}, "
+                          f"n_rows={n_rows}")
+    D = rows.shape[1]
+    d_rows = _out_f32(out, (int(n_rows), D), rows.device, "embed grad dense", "d_rows")
+    ws_bytes = int(Lb.pxr_embed_grad_ws_bytes(n))
+    ws = _ws.get(ws_bytes, rows.device)
+    _l.check(Lb.pxr_embed_grad_dense_f32(_l.ptr(idx), n, _l.ptr(rows), D, int(n_rows), _l.ptr(d_rows), _l.ptr(ws), ws_bytes,
+                                         _l.stream_ptr()), "pxr_embed_grad_dense_f32")
+    return d_rows
+
+
 def merge_sorted_rows(idx_all, rows_all, world, n_table, scale=1.0, out: SparseRows | None = None) -> SparseRows:
     """Merge `world` sorted-unique sparse gradients (idx_all [world*cap] padded with ids >= n_table, rows_all
     [world*cap, D]) without re-sorting; the result keeps world*cap slots, empty ones carry id 0 (see pxr.h)."""
@@ -2603,6 +2623,16 @@ def din_rows(profile, target, n_items: int, out=None):
     return buf[0], buf[1]
 
 
+def din_positions(profile, target, n_rows: int, out=None):
+    """din_rows over a batch-local [n_rows, D] row matrix (MODIN: the encoder's output, row 0 the zero image = "no item"): profile
+    int64 [S, L] and target int64 [S, 2] hold positions in [0, n_rows) -> (rows, gidx) int64 [S L + 2 S]: rows = the position
+    itself, gidx = the same (0 takes no gradient).  A position outside [0, n_rows) flags the status word
+    (ops.raise_on_bad_indices) and is clamped: nothing downstream reads out of range.  out: int64 [2, n]."""
+    buf = _table_rows("din positions", [("profile", profile, n_rows, 0, 1), ("target", target, n_rows, 0, 1)], out,
+                      (2, profile.numel() + target.numel()), True)
+    return buf[0], buf[1]
+
+
 def _din_shapes(B, L, D, emb=None, profile=None):
     if emb is not None and (tuple(emb.shape) != (B * (L + 2), D) or not emb.is_contiguous()):
         raise _l.PxrError(f"din: emb must be a contiguous [B (L + 2), D] = [{B * (L + 2)}, {D}], got {tuple(emb.shape)}")
@@ -2628,9 +2658,10 @@ def din_att_input(table, rows, B: int, L: int, emb=None, x=None):
     return emb, x
 
 
-def din_head_fwd(alast, wd, bd, emb, profile, s=None, kq=None, head=None):
-    """Head forward (pxr_din_head_fwd_f32): alast [2 B L, hl], wd [hl], bd [1], emb [B (L + 2), D], profile int64 [B, L] ->
-    (loss [1], s [2 B L], kq [2 B L], head [2 + 3 B] = loss | regulariser coefficient | coef | score differences | squares)."""
+def din_head_fwd(alast, wd, bd, emb, profile, s=None, kq=None, head=None, reg: float = 0.01):
+    """Head forward (pxr_din_head_fwd_reg_f32): alast [2 B L, hl], wd [hl], bd [1], emb [B (L + 2), D], profile int64 [B, L] ->
+    (loss [1], s [2 B L], kq [2 B L], head [2 + 3 B] = loss | regulariser coefficient | coef | score differences | squares).
+    reg: the weight of ||emb||_2 / B in the loss -- DIN's 0.01 (the default: pxr_din_head_fwd_f32's bits), MODIN's 0."""
     for t, n in ((alast, "alast"), (wd, "wd"), (bd, "bd"), (emb, "emb")):
         _req(t, torch.float32, n)
     _req(profile, torch.int64, "profile")
@@ -2645,8 +2676,9 @@ def din_head_fwd(alast, wd, bd, emb, profile, s=None, kq=None, head=None):
     head = head if head is not None else torch.empty(2 + 3 * B, dtype=torch.float32, device=dev)
     if s.numel() != 2 * B * L or kq.numel() != 2 * B * L or head.numel() != 2 + 3 * B:
         raise _l.PxrError("din head: s / kq must hold 2 B L floats and head 2 + 3 B")
-    _l.check(_l.load().pxr_din_head_fwd_f32(_l.ptr(alast), _l.ptr(wd), _l.ptr(bd), _l.ptr(emb), _l.ptr(profile), B, L, D, hl,
-                                            _l.ptr(s), _l.ptr(kq), _l.ptr(head), _l.stream_ptr()), "pxr_din_head_fwd_f32")
+    _l.check(_l.load().pxr_din_head_fwd_reg_f32(_l.ptr(alast), _l.ptr(wd), _l.ptr(bd), _l.ptr(emb), _l.ptr(profile), B, L, D, hl,
+                                                _l.ptr(s), _l.ptr(kq), _l.ptr(head), float(reg), _l.stream_ptr()),
+             "pxr_din_head_fwd_reg_f32")
     return head[:1], s, kq, head
 
 

@@ -463,6 +463,9 @@ class Trainer:
             self.item_feature = torch.cat(feats)
         else:
             self.item_feature = self.model.module.compute_item_all()
+        if hasattr(self.model.module, "set_item_feature"):
+            # a model whose fused scoring of its own reads the encoded catalogue (MODIN: pxr_din_topk_f32 on item_feature)
+            self.model.module.set_item_feature(self.item_feature)
         # what the fused scoring multiplies the queries of encode_last with: the item feature itself, or the packed matrix of a
         # model whose score is more than one product (VBPR.scoring_item_matrix); the literal path keeps predict(item_feature)
         hook = getattr(self.model.module, "scoring_item_matrix", None)
