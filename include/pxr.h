@@ -964,6 +964,19 @@ int pxr_pool_dense_grad_f32(const int64_t* gidx, int B, int L, const float* G, c
  * ws: pxr_embed_grad_ws_bytes(n) (it also holds the unique-row list and its count).  d_rows must not overlap rows. */
 int pxr_embed_grad_dense_f32(const int64_t* idx, int64_t n, const float* rows, int D, int64_t n_rows, float* d_rows, void* ws,
                              int64_t ws_bytes, void* stream);
+/* The dense sink for the sequence models' three-term table gradient (PixelNet/mobert4rec.py under autograd, each distinct image
+ * encoded once: the "table" is E [n_rows, D] = visual_encoder(images), items holds positions into it).  items, B, L and the layout
+ * (id_bstride, in_off, pos_off, neg_off) are pxr_seq_occ_sort's; dx0 [B L, D], out [B L, D], coef [B L] are pxr_sasrec_occ_segsum's.
+ * d_rows[row, :] for every referenced row in (0, n_rows) is bit for bit what pxr_seq_occ_sort + pxr_sasrec_occ_segsum (scale 1)
+ * leave in uniq_rows for that id -- the same keys, the same sort, the same segment sums in the same order, another sink; every
+ * other row of d_rows [n_rows, D] (row 0, unreferenced rows) is exactly +0.0 when the call returns, whatever it held before: the
+ * entry zeroes the block itself, on the same stream.  Key 0 and ids outside [0, n_rows) are dropped; the latter also set the
+ * bad-index bit of the status word.  No float atomics.  Limits: D % 4 == 0, 0 < D <= 4096, 3 B L < 2^30, 16-byte aligned dx0, out
+ * and d_rows; ws: pxr_embed_grad_ws_bytes(3 B L) (it also holds the unique-row list and its count).  d_rows must not overlap dx0
+ * or out. */
+int pxr_seq_occ_dense_f32(const int64_t* items, int B, int L, int64_t id_bstride, int64_t in_off, int64_t pos_off, int64_t neg_off,
+                          const float* dx0, const float* out, const float* coef, int D, int64_t n_rows, float* d_rows, void* ws,
+                          int64_t ws_bytes, void* stream);
 
 /* ---- WideDeep (model/IDNet/widedeep.py with MLPLayers, model/layers.py:239-281; csrc/widedeep.hip) ------------------------- */
 /* Rows of every [2 B, *] operand: r = 2 b + c, c = 0 the plane [profile_b | positive], c = 1 the plane [profile_b | negative]

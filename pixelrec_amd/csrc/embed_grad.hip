@@ -14,7 +14,9 @@
 //        o in [0,T)    input  id items[b,0,t]     adds  dx0[r,:]                 (grad of the LN'd input)
 //        o in [T,2T)   target id items[b,0,t+1]   adds  +coef[r] * out[r,:]      (d pos_score)
 //        o in [2T,3T)  negative id items[b,1,t+1] adds  -coef[r] * out[r,:]      (d neg_score)
-//     which never materialises the [B,2,L+1,D] gather nor its gradient.
+//     which never materialises the [B,2,L+1,D] gather nor its gradient.  The ids sit wherever the caller's layout says
+//     (pxr_seq_occ_sort).  Sinks: sparse rows (pxr_sasrec_occ_segsum[_split]), the lazy row update (pxr_sasrec_occ_segsum_apply),
+//     or, over a batch-local row space, a dense block (pxr_seq_occ_dense_f32: MOBERT4Rec, each image encoded once).
 //   MODE_POOL   : the pooled-history pair models (pool.hip), idx [B*L + 2B] = history rows | target rows, T = B*L, one COMPACT
 //        gradient block G [3B, D] (one row per sample for its whole history, one per target):
 //        o in [0,T)      history position (b, l) = o / L, o % L   adds  w[b] * G[b,:]     (the pooling weight of sample b)
@@ -810,7 +812,7 @@ __global__ void __launch_bounds__(256) dense_zero_kernel(float4* __restrict__ p,
 }
 
 // MODE's segment sums into a dense block (SegStoreDense): the sums and their order are segsum_kernel<MODE>'s (MODE_POOL: the
-// pooled pair models' compact block; MODE_ROWS: one gradient row per occurrence).
+// pooled pair models' compact block; MODE_ROWS: one gradient row per occurrence; MODE_SASREC: the sequence models' three terms).
 template <int MODE>
 __global__ void __launch_bounds__(SEG_THREADS) segsum_dense_kernel(SegSumArgs a, SegStoreDense s) {
   segsum_body<MODE>(a, s, (int)gridDim.x);
@@ -1168,14 +1170,16 @@ extern "C" int pxr_pool_table_grad_f32(const int64_t* gidx, int B, int L, const 
   return pxr_check_launch("pxr_pool_table_grad_f32");
 }
 
-// What the two dense entries share: zero d_rows [n_rows, D], sort gidx [n] exactly as pxr_embed_grad_rows_f32 sorts its idx, and
-// run segsum_body<MODE> over `a` (the caller has filled the sources) into the dense sink.  The unique-row list the sort needs lives
-// in the workspace: the four key / value buffers are handed to the sort as (keysA, valsA | keysB, valsB), so the ping-pong pair
-// that does not hold the final order is one contiguous stretch of >= 8 n bytes, and the count takes the spare last entry of the
-// block-count buffer.
-template <int MODE>
-static int dense_grad(const char* who, const int64_t* gidx, int n, SegSumArgs a, int64_t n_rows, float* d_rows, void* ws,
-                      int64_t ws_bytes, hipStream_t st) {
+// What the dense entries share: zero d_rows [n_rows, D], sort the n occurrence keys of `src` -- SORT == MODE_ROWS: src is gidx [n],
+// sorted exactly as pxr_embed_grad_rows_f32 sorts its idx; SORT == MODE_SASREC: src is items under (B, L, lay), n = 3 B L, sorted
+// exactly as pxr_seq_occ_sort sorts them, bad-index bit included -- and run segsum_body<MODE> over `a` (the caller has filled the
+// sources) into the dense sink.  The unique-row list the sort needs lives in the workspace: the four key / value buffers are handed
+// to the sort as (keysA, valsA | keysB, valsB), so the ping-pong pair that does not hold the final order is one contiguous stretch
+// of >= 8 n bytes, and the count takes the spare last entry of the block-count buffer.
+template <int MODE, int SORT>
+static int dense_grad(const char* who, const int64_t* src, int n, int B, int L, const OccLayout& lay, SegSumArgs a, int64_t n_rows,
+                      float* d_rows, void* ws, int64_t ws_bytes, hipStream_t st) {
+  static_assert(SORT == MODE_ROWS || SORT == MODE_SASREC, "the sorts that exist: plain row keys, or the three sequence occurrence kinds");
   const int D = a.D;
   SortWs sw;
   if (carve(ws, n, &sw) > ws_bytes) { pxr_set_error("%s: workspace too small", who); return PXR_ERR_WORKSPACE; }
@@ -1188,9 +1192,13 @@ static int dense_grad(const char* who, const int64_t* gidx, int n, SegSumArgs a,
   const int* sorted_vals = nullptr;
   int rc;
   if (use_fused_sort(n)) {
-    rc = fused_sort<MODE_ROWS>(gidx, n, 0, 0, n_rows, sw, uniq_idx, n_uniq_dev, st, &sorted_vals);
+    rc = fused_sort<SORT>(src, n, B, L, n_rows, sw, uniq_idx, n_uniq_dev, st, &sorted_vals, lay);
   } else {
-    hipLaunchKernelGGL(occ_keys_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, st, gidx, n, sw.keysA, sw.valsA, n_rows);
+    if constexpr (SORT == MODE_SASREC)
+      hipLaunchKernelGGL(occ_keys_sasrec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, src, B, L, sw.keysA, sw.valsA, n_rows, lay,
+                         pxr_status_word());
+    else
+      hipLaunchKernelGGL(occ_keys_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, st, src, n, sw.keysA, sw.valsA, n_rows);
     rc = sort_and_segment(sw, n, n_rows, uniq_idx, n_uniq_dev, st, &sorted_vals);
   }
   if (rc) return rc;
@@ -1218,7 +1226,7 @@ extern "C" int pxr_pool_dense_grad_f32(const int64_t* gidx, int B, int L, const 
   PXR_REQUIRE(d1 <= g0 || g1 <= d0, "pxr_pool_dense_grad_f32: d_rows must not alias G");
   SegSumArgs a{};
   a.src0 = G; a.coef = w; a.scale = 1.f; a.D = D; a.T = B * L; a.L = L;
-  return dense_grad<MODE_POOL>("pxr_pool_dense_grad_f32", gidx, B * (L + 2), a, n_rows, d_rows, ws, ws_bytes, (hipStream_t)stream);
+  return dense_grad<MODE_POOL, MODE_ROWS>("pxr_pool_dense_grad_f32", gidx, B * (L + 2), 0, 0, OccLayout{}, a, n_rows, d_rows, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // pxr_embed_grad_rows_f32's sums (scale 1) as a DENSE block over a batch-local row space (MODIN: DIN's backward leaves one gradient
@@ -1235,7 +1243,7 @@ extern "C" int pxr_embed_grad_dense_f32(const int64_t* idx, int64_t n, const flo
   PXR_REQUIRE(d1 <= g0 || g1 <= d0, "pxr_embed_grad_dense_f32: d_rows must not alias rows");
   SegSumArgs a{};
   a.src0 = rows; a.scale = 1.f; a.D = D; a.T = (int)n;
-  return dense_grad<MODE_ROWS>("pxr_embed_grad_dense_f32", idx, (int)n, a, n_rows, d_rows, ws, ws_bytes, (hipStream_t)stream);
+  return dense_grad<MODE_ROWS, MODE_ROWS>("pxr_embed_grad_dense_f32", idx, (int)n, 0, 0, OccLayout{}, a, n_rows, d_rows, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // Phase 1 of the table gradient: occurrence keys -> stable sort -> unique ids + segments.  Depends on `items` only, so it can
@@ -1273,6 +1281,32 @@ extern "C" int pxr_seq_occ_sort(const int64_t* items, int B, int L, int64_t id_b
   if (rc) return rc;
   if (sorted_vals != sasrec_sorted_vals(w, n, n_table)) { pxr_set_error("pxr_seq_occ_sort: internal buffer parity"); return PXR_ERR_LAUNCH; }
   return PXR_OK;
+}
+
+// pxr_seq_occ_sort + pxr_sasrec_occ_segsum(scale = 1) in one call with the DENSE sink (MOBERT4Rec: the "table" is E =
+// visual_encoder(the batch's distinct images), whose gradient autograd takes dense): d_rows [n_rows, D] gets, at every referenced
+// row in (0, n_rows), the row the two phases leave in uniq_rows for that id, bit for bit -- the same keys under the same layout, the
+// same sort, segsum_body<MODE_SASREC>, another sink -- and exactly +0.0 everywhere else, whatever it held before (zeroed here, on the
+// same stream).  Key 0 and ids outside [0, n_rows) are dropped; the latter set the bad-index bit, as in pxr_seq_occ_sort.
+extern "C" int pxr_seq_occ_dense_f32(const int64_t* items, int B, int L, int64_t id_bstride, int64_t in_off, int64_t pos_off,
+                                     int64_t neg_off, const float* dx0, const float* out, const float* coef, int D, int64_t n_rows,
+                                     float* d_rows, void* ws, int64_t ws_bytes, void* stream) {
+  PXR_REQUIRE(id_bstride > 0 && in_off >= 0 && pos_off >= 0 && neg_off >= 0 && in_off + L <= id_bstride && pos_off + L <= id_bstride &&
+              neg_off + L <= id_bstride, "pxr_seq_occ_dense_f32: bad id layout");
+  PXR_REQUIRE(items && dx0 && out && coef && d_rows && ws, "pxr_seq_occ_dense_f32: null pointer");
+  const int64_t n64 = (int64_t)3 * B * L;
+  PXR_REQUIRE(B > 0 && L > 0 && n64 < (1ll << 30) && D > 0 && D % 4 == 0 && D <= 4096 && n_rows > 0 && n_rows < (1ll << 31),
+              "pxr_seq_occ_dense_f32: bad shape (B=%d, L=%d, D=%d)", B, L, D);
+  PXR_REQUIRE((((uintptr_t)dx0 | (uintptr_t)out | (uintptr_t)d_rows) & 15) == 0,
+              "pxr_seq_occ_dense_f32: dx0, out and d_rows must be 16-byte aligned");
+  const int64_t src_bytes = (int64_t)B * L * D * 4;
+  const char *d0 = (const char*)d_rows, *d1 = d0 + n_rows * D * 4;
+  PXR_REQUIRE((d1 <= (const char*)dx0 || (const char*)dx0 + src_bytes <= d0) && (d1 <= (const char*)out || (const char*)out + src_bytes <= d0),
+              "pxr_seq_occ_dense_f32: d_rows must not alias dx0 or out");
+  SegSumArgs a{};
+  a.src0 = dx0; a.src1 = out; a.coef = coef; a.scale = 1.f; a.D = D; a.T = B * L;
+  return dense_grad<MODE_SASREC, MODE_SASREC>("pxr_seq_occ_dense_f32", items, (int)n64, B, L, OccLayout{id_bstride, in_off, pos_off, neg_off},
+                                              a, n_rows, d_rows, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // Phase 2: uniq_rows[u,:] = scale * sum over the occurrences of unique id u (see the header comment for the terms).

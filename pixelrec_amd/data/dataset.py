@@ -365,6 +365,18 @@ def positions_into_distinct_images(profile, target):
     return np.searchsorted(image_ids, items), image_ids
 
 
+def positions_into_distinct_images_masked(items, mask_token):
+    """BERT4Rec's items [B, 3, P] (masked sequence | original sequence | negatives; `mask_token` = item_num where a position is
+    masked) -> (index int64 [B, 3, P], image_ids int64 [M]): image_ids[0] == 0 (the zero image, "no item"), image_ids[1] ==
+    mask_token (it stands for the ones image, which no store holds), image_ids[2:] the batch's other distinct item ids, ascending;
+    `index` holds positions into image_ids.  The two leading rows are there whether or not the batch reads them."""
+    uniq = np.unique(items)
+    image_ids = np.concatenate((np.asarray([0, mask_token], dtype=np.int64), uniq[(uniq != 0) & (uniq != mask_token)]))
+    index = 2 + np.searchsorted(image_ids[2:], items)
+    index = np.where(items == 0, 0, np.where(items == mask_token, 1, index))
+    return index.astype(np.int64), image_ids
+
+
 class MoPoolTrainBatcher(DinTrainBatcher):
     """Vectorised MOSampleTwoTowerTrainDataset / MOSampleOneTowerTrainDataset + mosampletower_train_collate (reference
     REC/data/dataset/trainset.py:656-813, collate_fn.py:95-107) for MODSSM and MOFM.  A batch is `train_batch_size` whole SEQ chunks
@@ -471,6 +483,29 @@ class MoTowerTrainBatcher(CuratorTrainBatcher):
         return positions_into_distinct_images(*super().make_batch(rows, rng))
 
     __iter__ = MoPoolTrainBatcher.__iter__
+
+
+class MoBert4RecTrainBatcher(BERT4RecTrainBatcher):
+    """Vectorised MOBERT4RecTrainDataset (reference REC/data/dataset/trainset.py:836-935) for MOBERT4Rec: BERT4RecTrainBatcher's
+    batches -- the same windows, masking, negatives and random stream -- as positions into the batch's distinct images.
+
+    Yields (index int64 [B, 3, L+1], masked_index int64 [B, L+1], image_ids int64 [M]): image_ids[index] is
+    BERT4RecTrainBatcher's `items`; image_ids[0] == 0 (the zero image), image_ids[1] == item_num (the mask token: the ones image),
+    image_ids[2:] the batch's other distinct ids, ascending.  The reference lists one image per (position, input | positive |
+    negative): 3 B (L+1) per batch; here each distinct image is fetched and encoded once.  It feeds the ones image at padded
+    input positions too (trainset.py:907); those are masked keys outside the loss, so they hold position 0 here -- the same loss
+    and the same gradients (README "MOBERT4Rec")."""
+
+    def make_batch(self, rows, rng):
+        items, masked = super().make_batch(rows, rng)
+        index, image_ids = positions_into_distinct_images_masked(items, self.mask_token)
+        return index, masked, image_ids
+
+    def __iter__(self):
+        idx = self._indices()
+        rng = np.random.default_rng([self.neg_seed, self.epoch, self.rank])
+        for b in range(len(self)):
+            yield tuple(torch.from_numpy(x) for x in self.make_batch(idx[b * self.batch_size:(b + 1) * self.batch_size], rng))
 
 
 class SeqEvalDataset(Dataset):

@@ -14,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from ..parallel import world_info
 from .dataload import Data
-from .dataset import (AcfEvalBatcher, BERT4RecTrainBatcher, CuratorTrainBatcher, DinTrainBatcher, GraphEvalBatcher, GraphTrainBatcher, MoPoolTrainBatcher, MoTowerTrainBatcher, PairEvalBatcher, PairTrainBatcher, SeqEvalBatcher,
+from .dataset import (AcfEvalBatcher, BERT4RecTrainBatcher, CuratorTrainBatcher, DinTrainBatcher, GraphEvalBatcher, GraphTrainBatcher, MoBert4RecTrainBatcher, MoPoolTrainBatcher, MoTowerTrainBatcher, PairEvalBatcher, PairTrainBatcher, SeqEvalBatcher,
                       SampleAcfTrainBatcher, SeqEvalDataset, SeqTrainBatcher, TwoTowerTrainBatcher, VisRankEvalBatcher, _NoTraining,
                       seq_eval_collate)
 
@@ -22,7 +22,7 @@ SUPPORTED = {"SASRec": "SEQ", "MOSASRec": "SEQ", "FSASRec": "SEQ", "GRU4Rec": "S
              "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR", "MF": "PAIR", "VBPR": "PAIR",
              "SRGNN": "AUGSEQ", "LightSANs": "TWOTOWER", "ACF": "SEQ", "VISRANK": "EVALONLY", "CuratorNet": "SEQ", "DIN": "SEQ",
              "DSSM": "SEQ", "FM": "SEQ", "WideDeep": "SEQ", "MODSSM": "SEQ", "MOFM": "SEQ",
-             "MODIN": "SEQ"}      # REC/data/utils.py:24-33
+             "MODIN": "SEQ", "MOBERT4Rec": "SEQ"}      # REC/data/utils.py:24-33
 
 
 def load_data(config):
@@ -104,11 +104,12 @@ def bulid_dataloader(config, dataload):
     # `train_batch_size` chunks; evaluation is SeqEvalDataset's for all of them (DIN: CandiEvalDataset's per-item repetition happens
     # inside the kernel); MODSSM and MOFM (MOSampleTwoTowerTrainDataset / MOSampleOneTowerTrainDataset) read the same samples by
     # whole chunks, as positions into the batch's distinct images (MoPoolTrainBatcher); MODIN (:44 MOTwoTowerTrainDataset) reads
-    # CuratorNet's one sample per chunk in the same positional form (MoTowerTrainBatcher)
+    # CuratorNet's one sample per chunk in the same positional form (MoTowerTrainBatcher); MOBERT4Rec (:48 MOBERT4RecTrainDataset)
+    # reads BERT4Rec's masked windows in that form, the mask token standing for the ones image (MoBert4RecTrainBatcher)
     batcher = {"BERT4Rec": BERT4RecTrainBatcher, "LightSANs": TwoTowerTrainBatcher,
                "ACF": SampleAcfTrainBatcher, "CuratorNet": CuratorTrainBatcher, "DIN": DinTrainBatcher, "DSSM": DinTrainBatcher,
                "FM": DinTrainBatcher, "WideDeep": CuratorTrainBatcher, "MODSSM": MoPoolTrainBatcher,
-               "MOFM": MoPoolTrainBatcher, "MODIN": MoTowerTrainBatcher}.get(model_name, SeqTrainBatcher)
+               "MOFM": MoPoolTrainBatcher, "MODIN": MoTowerTrainBatcher, "MOBERT4Rec": MoBert4RecTrainBatcher}.get(model_name, SeqTrainBatcher)
     train_loader = _TrainLoader(batcher(config, dataload, rank=rank, world=world))
     if model_name == "ACF":
         # SampleACFTrainDataset / ACFEvalDataset (REC/data/utils.py:24-31): leave-one-out samples of the chunks; windows + user id

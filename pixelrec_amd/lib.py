@@ -191,6 +191,7 @@ _SIGNATURES = {
     "pxr_pool_table_grad_f32": (_I, [_P, _I, _I, _P, _P, _I, _I64, _P, _P, _P, _P, _I64, _P]),
     "pxr_pool_dense_grad_f32": (_I, [_P, _I, _I, _P, _P, _I, _I64, _P, _P, _I64, _P]),
     "pxr_embed_grad_dense_f32": (_I, [_P, _I64, _P, _I, _I64, _P, _P, _I64, _P]),
+    "pxr_seq_occ_dense_f32": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _P, _P, _P, _I, _I64, _P, _P, _I64, _P]),
     "pxr_wd_join_f32": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     "pxr_wd_join_bwd_f32": (_I, [_P, _I, _I, _P, _P]),
     "pxr_wd_head_fwd_f32": (_I, [_P, _P, _P, _I64, _P, _I, _I, _P, _P]),

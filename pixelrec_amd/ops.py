@@ -1576,6 +1576,32 @@ def occ_sort(items, L: int, layout, n_table, sp: SparseRows, ws: torch.Tensor):
                                  _l.ptr(sp.n), _l.ptr(ws), ws.numel(), _l.stream_ptr()), "pxr_seq_occ_sort")
 
 
+def seq_occ_dense_grad(items, layout, dx0, out, coef, n_rows: int, d_rows=None, ws: torch.Tensor | None = None):
+    """occ_sort + sasrec_occ_segsum(scale=1) as a dense block over a batch-local row space (pxr_seq_occ_dense_f32): items int64
+    [B, ...] holds rows of an [n_rows, D] matrix under layout = (id_bstride, in_off, pos_off, neg_off) (None: SASRec's windows),
+    dx0 / out [B, L, D], coef [B, L] -> d_rows float32 [n_rows, D]: the sparse route's row sums, bit for bit, at their rows and
+    exactly +0.0 everywhere else (row 0, unreferenced rows), whatever `d_rows` held before.  Key 0 is dropped; an id outside
+    [0, n_rows) is dropped and flags the status word (raise_on_bad_indices).  ws: occ_ws_bytes(B, L) bytes (default: the shared
+    workspace)."""
+    Lb = _l.load()
+    _req(items, torch.int64, "items"); _req(dx0, torch.float32, "dx0"); _req(out, torch.float32, "out"); _req(coef, torch.float32, "coef")
+    if out.dim() != 3 or items.shape[0] != out.shape[0] or dx0.shape != out.shape or coef.numel() != out.shape[0] * out.shape[1] or \
+            out.numel() < 1 or n_rows < 1:
+        raise _l.PxrError(f"seq occ dense grad: need items [B, ...], dx0 / out [B, L, D], coef [B, L] and n_rows >= 1, got items "
+                          f"{tuple(items.shape)}, dx0 {tuple(dx0.shape)}, out {tuple(out.shape)}, coef {tuple(coef.shape)}, n_rows={n_rows}")
+    B, L, D = out.shape
+    lay = _sasrec_layout(L) if layout is None else tuple(int(x) for x in layout)
+    if items.numel() < B * lay[0]:
+        raise _l.PxrError(f"seq occ dense grad: items {tuple(items.shape)} holds fewer than id_bstride={lay[0]} ids per sequence")
+    d_rows = _out_f32(d_rows, (int(n_rows), D), out.device, "seq occ dense grad", "d_rows")
+    if ws is None:
+        ws = _ws.get(occ_ws_bytes(B, L), out.device)
+    device_status(items.device)       # an id outside the row space flags the status word (raise_on_bad_indices)
+    _l.check(Lb.pxr_seq_occ_dense_f32(_l.ptr(items), B, L, *lay, _l.ptr(dx0), _l.ptr(out), _l.ptr(coef), D, int(n_rows),
+                                      _l.ptr(d_rows), _l.ptr(ws), ws.numel(), _l.stream_ptr()), "pxr_seq_occ_dense_f32")
+    return d_rows
+
+
 def occ_split_ws_bytes(B: int, L: int, D: int) -> int:
     """Bytes of the second workspace of sasrec_occ_segsum's split route (0: shape not served).  Allocate it with torch.zeros."""
     return int(_l.load().pxr_sasrec_occ_split_ws_bytes(B, L, D))

@@ -460,6 +460,10 @@ class Trainer:
             for s in range(0, store.n, 100):
                 ids = torch.arange(s, min(store.n, s + 100), device=self.device)
                 feats.append(self.model.module.compute_item(store.batch(ids)))   # id 0 -> zero image (batchset.py:58-60)
+            extra = getattr(self.model.module, "extra_item_images", None)
+            if extra is not None:
+                # a model whose catalogue holds images no store has (MOBERT4Rec: the ones image of the mask token, batchset.py:53)
+                feats.append(self.model.module.compute_item(extra(*store.images.shape[1:3], self.device)))
             self.item_feature = torch.cat(feats)
         else:
             self.item_feature = self.model.module.compute_item_all()
