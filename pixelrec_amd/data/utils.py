@@ -1,6 +1,6 @@
-"""load_data / bulid_dataloader with the reference's names (REC/data/utils.py:15-114) for the SASRec family.
+"""load_data / bulid_dataloader with the reference's names (REC/data/utils.py:15-114).
 
-Train side: `SeqTrainBatcher` (vectorised whole batches; order = torch DistributedSampler's).  Eval side: the
+Train side: one `TrainBatcher` per model, LOADERS below (vectorised whole batches; order = torch DistributedSampler's).  Eval side: the
 reference's NonConsecutiveSequentialDistributedSampler sharding -- rank r takes users r, r+W, r+2W, ... with
 no padding (utils.py:126-156) -- over SeqEvalDataset + seq_eval_collate.
 """
@@ -46,7 +46,7 @@ class NonConsecutiveSequentialDistributedSampler(torch.utils.data.sampler.Sample
 
 
 class _TrainLoader:
-    """DataLoader-shaped facade over SeqTrainBatcher: `.sampler.set_epoch`, `len()`, iteration."""
+    """DataLoader-shaped facade over a TrainBatcher: `.sampler.set_epoch`, `len()`, iteration."""
 
     def __init__(self, batcher):
         self.batcher = batcher
@@ -70,6 +70,36 @@ class _GraphTrainLoader(_TrainLoader):
             yield item_seq, torch.cat((mask, target), dim=1)
 
 
+# model -> (train batcher or None = not trained, eval batcher, train loader facade); on the right the reference's dataset classes
+# (REC/data/utils.py:24-48).  A batcher's docstring says how its batches differ from that dataset's.
+def _seq_eval(train_batcher):
+    return train_batcher, SeqEvalBatcher, _TrainLoader                 # SeqEvalDataset: last-L windows, full histories masked
+
+
+_SEQ = _seq_eval(SeqTrainBatcher)                                      # SEQTrainDataset: a negative per target position
+_POOL = _seq_eval(DinTrainBatcher)                                     # ACF's leave-one-out samples without the user id
+_PAIR = (PairTrainBatcher, PairEvalBatcher, _TrainLoader)              # PairTrainDataset / PairEvalDataset: users scored
+LOADERS = {
+    "SASRec": _SEQ, "MOSASRec": _SEQ, "FSASRec": _SEQ, "GRU4Rec": _SEQ, "NextItNet": _SEQ, "MOGRU4Rec": _SEQ, "MONextItNet": _SEQ,
+    "LightGCN": _PAIR, "MF": _PAIR, "VBPR": _PAIR,
+    "BERT4Rec": _seq_eval(BERT4RecTrainBatcher),                       # :25 BERT4RecTrainDataset: masked windows
+    "SRGNN": (GraphTrainBatcher, GraphEvalBatcher, _GraphTrainLoader),  # Graph{Train,Eval}Dataset: AUGSEQ prefixes, right-padded
+    "LightSANs": _seq_eval(TwoTowerTrainBatcher),                      # :35 TwoTowerTrainDataset over the AUGSEQ prefixes
+    "ACF": (SampleAcfTrainBatcher, AcfEvalBatcher, _TrainLoader),      # SampleACFTrainDataset / ACFEvalDataset: windows + user id
+    "VISRANK": (None, VisRankEvalBatcher, None),                       # :37 BaseDataset / VisRankEvalDataset: nothing to train
+    "CuratorNet": _seq_eval(CuratorTrainBatcher),                      # :39 names a TwoTowerTrainDataset2 that does not exist
+    "DIN": _POOL,                                                      # :31 SampleTwoTowerTrainDataset; CandiEvalDataset's per-item repetition is the kernel's
+    "DSSM": _POOL,                                                     # :32 SampleTwoTowerTrainDataset
+    "FM": _POOL,                                                       # :33 SampleOneTowerTrainDataset: the same samples as planes
+    "WideDeep": _seq_eval(CuratorTrainBatcher),                        # CuratorNet's one sample per chunk
+    "MODSSM": _seq_eval(MoPoolTrainBatcher),                           # MOSampleTwoTowerTrainDataset: DIN's samples by whole chunks
+    "MOFM": _seq_eval(MoPoolTrainBatcher),                             # MOSampleOneTowerTrainDataset: the same
+    "MODIN": _seq_eval(MoTowerTrainBatcher),                           # :44 MOTwoTowerTrainDataset: CuratorNet's samples
+    "MOBERT4Rec": _seq_eval(MoBert4RecTrainBatcher),                   # :48 MOBERT4RecTrainDataset: BERT4Rec's masked windows
+}                                                                      # MO*: as positions into the batch's distinct images
+assert LOADERS.keys() == SUPPORTED.keys()
+
+
 def bulid_dataloader(config, dataload):
     """-> (train_loader, valid_loader, test_loader).  (The misspelt name is the reference's, utils.py:20.)"""
     model_name = config["model"]
@@ -80,50 +110,23 @@ def bulid_dataloader(config, dataload):
     logger = getLogger()
     logger.info(f"[Training]: train_batch_size = [{config['train_batch_size']}]")
     logger.info(f"[Evaluation]: eval_batch_size = [{config['eval_batch_size']}]")
-    if SUPPORTED[model_name] == "EVALONLY":
-        # BaseDataset / VisRankEvalDataset (REC/data/utils.py:37): nothing to train, windows + full histories to score
+    train_batcher, eval_batcher, facade = LOADERS[model_name]
+    if train_batcher is None:
         if config["need_training"] is not False:
             raise ValueError(f"{model_name} is not trained: set `need_training: False` (reference ViNet/visrank.yaml)")
-        return (_NoTraining(dataload), VisRankEvalBatcher(config, dataload, phase="valid", rank=rank, world=world),
-                VisRankEvalBatcher(config, dataload, phase="test", rank=rank, world=world))
-    if SUPPORTED[model_name] == "PAIR":
-        # PairTrainDataset / PairEvalDataset (REC/data/utils.py:24-31): one sample per training interaction, users scored
-        train_loader = _TrainLoader(PairTrainBatcher(config, dataload, rank=rank, world=world))
-        return (train_loader, PairEvalBatcher(config, dataload, phase="valid", rank=rank, world=world),
-                PairEvalBatcher(config, dataload, phase="test", rank=rank, world=world))
-    if SUPPORTED[model_name] == "AUGSEQ":
-        # GraphTrainDataset / GraphEvalDataset (REC/data/utils.py:24-31): every prefix a sample, right-padded windows
-        train_loader = _GraphTrainLoader(GraphTrainBatcher(config, dataload, rank=rank, world=world))
-        return (train_loader, GraphEvalBatcher(config, dataload, phase="valid", rank=rank, world=world),
-                GraphEvalBatcher(config, dataload, phase="test", rank=rank, world=world))
-    # BERT4Rec masks its windows (REC/data/utils.py:25: BERT4RecTrainDataset); LightSANs (AUGSEQ, so Data built every prefix)
-    # reads TwoTowerTrainDataset's rows of those prefixes (:35); CuratorNet (:39 names a TwoTowerTrainDataset2 that does not exist)
-    # reads the same row format over the SEQ chunks; DIN and DSSM (:31-32 SampleTwoTowerTrainDataset) and FM (:33
-    # SampleOneTowerTrainDataset: the same samples as [profile | positive], [profile | negative] planes) read ACF's leave-one-out
-    # samples without the user id -- a batch is `train_batch_size` samples (ACF's decision) where the reference stacks
-    # `train_batch_size` chunks; evaluation is SeqEvalDataset's for all of them (DIN: CandiEvalDataset's per-item repetition happens
-    # inside the kernel); MODSSM and MOFM (MOSampleTwoTowerTrainDataset / MOSampleOneTowerTrainDataset) read the same samples by
-    # whole chunks, as positions into the batch's distinct images (MoPoolTrainBatcher); MODIN (:44 MOTwoTowerTrainDataset) reads
-    # CuratorNet's one sample per chunk in the same positional form (MoTowerTrainBatcher); MOBERT4Rec (:48 MOBERT4RecTrainDataset)
-    # reads BERT4Rec's masked windows in that form, the mask token standing for the ones image (MoBert4RecTrainBatcher)
-    batcher = {"BERT4Rec": BERT4RecTrainBatcher, "LightSANs": TwoTowerTrainBatcher,
-               "ACF": SampleAcfTrainBatcher, "CuratorNet": CuratorTrainBatcher, "DIN": DinTrainBatcher, "DSSM": DinTrainBatcher,
-               "FM": DinTrainBatcher, "WideDeep": CuratorTrainBatcher, "MODSSM": MoPoolTrainBatcher,
-               "MOFM": MoPoolTrainBatcher, "MODIN": MoTowerTrainBatcher, "MOBERT4Rec": MoBert4RecTrainBatcher}.get(model_name, SeqTrainBatcher)
-    train_loader = _TrainLoader(batcher(config, dataload, rank=rank, world=world))
-    if model_name == "ACF":
-        # SampleACFTrainDataset / ACFEvalDataset (REC/data/utils.py:24-31): leave-one-out samples of the chunks; windows + user id
-        return (train_loader, AcfEvalBatcher(config, dataload, phase="valid", rank=rank, world=world),
-                AcfEvalBatcher(config, dataload, phase="test", rank=rank, world=world))
+        train_loader = _NoTraining(dataload)
+    else:
+        train_loader = facade(train_batcher(config, dataload, rank=rank, world=world))
     loaders = []
-    workers = int(config["eval_num_workers"] or 0)
     for phase in ("valid", "test"):
-        if config["eval_vectorized"] is None or bool(config["eval_vectorized"]):
-            loaders.append(SeqEvalBatcher(config, dataload, phase=phase, rank=rank, world=world))
+        if eval_batcher is not SeqEvalBatcher or config["eval_vectorized"] is None or bool(config["eval_vectorized"]):
+            loaders.append(eval_batcher(config, dataload, phase=phase, rank=rank, world=world))
             continue
         # literal form of the reference's loaders (data/utils.py:95-110); `eval_vectorized: False` selects it
         ds = SeqEvalDataset(config, dataload, phase=phase)
         sampler = NonConsecutiveSequentialDistributedSampler(ds, rank=rank, num_replicas=world)
-        loaders.append(DataLoader(ds, batch_size=config["eval_batch_size"], num_workers=workers, pin_memory=False,
-                                  sampler=sampler, collate_fn=seq_eval_collate))
+        loaders.append(DataLoader(ds, batch_size=config["eval_batch_size"], num_workers=int(config["eval_num_workers"] or 0),
+                                  pin_memory=False, sampler=sampler, collate_fn=seq_eval_collate))
     return train_loader, loaders[0], loaders[1]
+
+
