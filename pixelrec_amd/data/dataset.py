@@ -557,6 +557,23 @@ class GraphTrainBatcher(TrainBatcher):
         return item_seq, real.astype(np.int64), np.stack((pos, neg), axis=1)
 
 
+class MoGraphTrainBatcher(GraphTrainBatcher):
+    """Vectorised MOGraphTrainDataset + mograph_train_collate (reference REC/data/dataset/trainset.py, collate_fn.py) for MOSRGNN:
+    GraphTrainBatcher's batches -- the same AUGSEQ prefixes, negatives and random stream -- as positions into the batch's distinct
+    images.  The mask is not carried: the prefixes are right-padded, so it is index != 0 and the graph build derives it.
+
+    Yields (index int64 [B, L + 2] = [item_seq | positive | negative], image_ids int64 [M]): image_ids[index] is
+    GraphTrainBatcher's [item_seq | target]; image_ids[0] == 0 (the zero image, "no item"), image_ids[1:] the batch's distinct item
+    ids, ascending -- so a session's node order by position is its node order by id, np.unique's order in the reference collate.
+    The reference stacks one image per node slot and target, B (n + 2) per batch with n the batch's largest node count, pad images
+    included; here each distinct image is fetched and encoded once.  The batch unit stays the reference's: `train_batch_size`
+    shuffled prefixes (README "MOSRGNN")."""
+
+    def make_batch(self, rows, rng):
+        item_seq, _, target = super().make_batch(rows, rng)
+        return positions_into_distinct_images(item_seq, target)
+
+
 class _NoTraining:
     """The train side of a model that is not trained (VISRANK): a `_TrainLoader`-shaped object without batches."""
 

@@ -26,6 +26,9 @@ uniform(-1/sqrt(D), 1/sqrt(D)).  `gnn.linear_edge_f` is read by nothing: it gets
 is never updated (torch.optim.AdamW skips a parameter without a gradient, weight decay included).
 An empty history (sum(mask) = 0) reads its `ht` from the last slot, as torch's index -1 does in the reference.
 One process: the data-parallel exchange is not built for this model.
+
+Everything between the graph dict and the node gradients lives in the mixin `SrgnnStep`, which MOSRGNN (mosrgnn.py) shares: it
+feeds the same step the visual encoder's rows and sums the node gradients into a dense block instead of sparse table rows.
 """
 from __future__ import annotations
 
@@ -58,16 +61,18 @@ class _GNN(nn.Module):
         self.linear_edge_f = nn.Linear(hidden_size, hidden_size, bias=True)
 
 
-class SRGNN(TableHooks, PackedModel):
-    input_type = InputType.AUGSEQ
-    item_table_attr = "embedding"          # the reference's table name (optim.item_table_name)
+class SrgnnStep:
+    """Mixin over PackedModel: SRGNN's step between "a graph dict `g` (ops.srgnn_graph's nodes / alias / A) and a row matrix" and
+    "the node gradients dH [B, L, D], out_pad and coef_pad" -- the parameters behind the row matrix, their flat packing, the gated
+    cells, the readout, the padded linear_transform GEMM, the pair head and their backward with the grouped weight gradients.  Where
+    the rows live is the subclass's: SRGNN reads its lazily updated item table and leaves sparse rows, MOSRGNN (mosrgnn.py) reads the
+    visual encoder's output and returns a dense block.  The subclass registers whatever precedes `gnn` in the reference's
+    state_dict (the table, the encoder) before it calls `_build_gnn`."""
 
-    def __init__(self, config, dataload):
-        super().__init__()
-        one_process(self, "the graph models")
+    def _build_gnn(self, config):
+        """embedding_size, step and MAX_ITEM_LIST_LENGTH under the kernels' limits, then the reference's modules in its order."""
         self.hidden_size = config["embedding_size"]
         self.step = int(config["step"])
-        self.item_num = dataload.item_num
         self.max_seq_length = config["MAX_ITEM_LIST_LENGTH"]
         D = self.hidden_size
         if D % 4:
@@ -76,23 +81,17 @@ class SRGNN(TableHooks, PackedModel):
             raise ValueError("step must be >= 1")
         if not 1 <= self.max_seq_length <= ops.SRGNN_MAX_L:
             raise ValueError(f"MAX_ITEM_LIST_LENGTH must be in 1..{ops.SRGNN_MAX_L} for SRGNN's session graphs")
-        self.embedding = nn.Embedding(self.item_num, D)
         self.gnn = _GNN(D, self.step)
         self.linear_one = nn.Linear(D, D, bias=True)
         self.linear_two = nn.Linear(D, D, bias=True)
         self.linear_three = nn.Linear(D, 1, bias=False)
         self.linear_transform = nn.Linear(2 * D, D, bias=True)
-        stdv = 1.0 / math.sqrt(D)
-        for w in self.parameters():                       # srgnn.py _reset_parameters, in parameter order
-            w.data.uniform_(-stdv, stdv)
         self._gbufs = {}                                   # the session graph's buffers (ops.srgnn_graph)
-        self._local_sparse = None                          # the sparse table (SASRec's bookkeeping)
-        self._occ_ws = self._occ_ws2 = None
 
     # ------------------------------------------------------------------------------------------ flat packing
     def _flat_specs(self):
         """Flat layout: the two edge Linears side by side (E is one GEMM), b_iah | b_oah (one bias of the propagation),
-        linear_one | linear_two (P is one GEMM).  linear_edge_f and the table stay outside."""
+        linear_one | linear_two (P is one GEMM).  linear_edge_f and the rows stay outside."""
         g = self.gnn
         return [("ein.w", g.linear_edge_in.weight), ("eout.w", g.linear_edge_out.weight),
                 ("ein.b", g.linear_edge_in.bias), ("eout.b", g.linear_edge_out.bias),
@@ -102,10 +101,10 @@ class SRGNN(TableHooks, PackedModel):
                 ("one.b", self.linear_one.bias), ("two.b", self.linear_two.bias),
                 ("three.w", self.linear_three.weight), ("t.w", self.linear_transform.weight), ("t.b", self.linear_transform.bias)]
 
-    def rec_parameter_names(self):
-        """{reference parameter name: flat-buffer key} in the reference's registration order (optim.native_to_torch_state):
-        the table and linear_edge_f (no gradient, no optimizer state) map to None."""
-        return {"embedding.weight": None, "gnn.w_ih": "w_ih", "gnn.w_hh": "w_hh", "gnn.b_ih": "b_ih", "gnn.b_hh": "b_hh",
+    def _gnn_parameter_names(self):
+        """{reference parameter name: flat-buffer key} of gnn.* and the four Linears in the reference's registration order:
+        linear_edge_f (no gradient, no optimizer state) maps to None."""
+        return {"gnn.w_ih": "w_ih", "gnn.w_hh": "w_hh", "gnn.b_ih": "b_ih", "gnn.b_hh": "b_hh",
                 "gnn.b_iah": "iah", "gnn.b_oah": "oah", "gnn.linear_edge_in.weight": "ein.w", "gnn.linear_edge_in.bias": "ein.b",
                 "gnn.linear_edge_out.weight": "eout.w", "gnn.linear_edge_out.bias": "eout.b", "gnn.linear_edge_f.weight": None,
                 "gnn.linear_edge_f.bias": None, "linear_one.weight": "one.w", "linear_one.bias": "one.b",
@@ -114,27 +113,6 @@ class SRGNN(TableHooks, PackedModel):
 
     def _after_pack(self, dev):
         self._gbufs = {}
-
-    # ------------------------------------------------------------------------------------------ the table (SASRec's machinery)
-    def _table_prepare(self, g, B, L, D, device):
-        """Occurrence sort of the batch's node and target ids, then the lazy catch-up of exactly those rows."""
-        cap = B * (L + 2)
-        sp = self._local_sparse
-        if sp is None or sp.cap != cap or sp.rows.shape[1] != D or sp.rows.device != device:
-            sp = self._local_sparse = ops.SparseRows(cap, D, device, packed=True)
-        need = ops.occ_ws_bytes(B, L)
-        if self._occ_ws is None or self._occ_ws.numel() < need or self._occ_ws.device != device:
-            self._occ_ws = torch.empty(need, dtype=torch.uint8, device=device)
-        env = os.environ.get("PXR_SEGSUM_SPLIT", "auto")
-        need2 = ops.occ_split_ws_bytes(B, L, D) if (env == "1" or (env != "0" and 3 * B * L >= 30000)) else 0
-        if need2 == 0:
-            self._occ_ws2 = None
-        elif self._occ_ws2 is None or self._occ_ws2.numel() != need2 or self._occ_ws2.device != device:
-            self._occ_ws2 = torch.zeros(need2, dtype=torch.uint8, device=device)
-        ops.occ_sort(g["occ"], L, (3 * L, 0, L, 2 * L), self.item_num, sp, self._occ_ws)
-        if self._table_hooks is not None:
-            self._table_hooks.catch_up_rows(sp.idx, sp.n, sp.cap)
-        return sp
 
     # ------------------------------------------------------------------------------------------ the network
     def _gnn_forward(self, table, nodes, A, B, train):
@@ -165,38 +143,10 @@ class SRGNN(TableHooks, PackedModel):
         cat = ops.srgnn_readout_fwd(Hn, P, alias, mask, self._p("three.w").view(-1), sig=sig, alpha=alpha)
         return cat, sig, alpha
 
-    # ------------------------------------------------------------------------------------------ training
-    def forward(self, interaction):
-        """interaction = (item_seq [B, L], mask [B, L], target [B, 2]) or (item_seq, mask | target [B, L + 2]) -> 0-dim loss."""
-        if len(interaction) == 3:
-            item_seq, mask, target = interaction
-        else:
-            item_seq, tail = interaction
-            L = self.max_seq_length
-            mask, target = tail[:, :L], tail[:, L:L + 2]
-        L = self.max_seq_length
-        if item_seq.dim() != 2 or item_seq.shape[1] != L:
-            raise ValueError(f"item_seq must be [B, {L}], got {tuple(item_seq.shape)}")
-        self._ensure_packed()
-        item_seq, mask, target = item_seq.contiguous(), mask.contiguous(), target.contiguous()
-        if torch.is_grad_enabled() and self.training:
-            return TrainStep.apply(self._anchor, self, item_seq, mask, target)
-        was = self.training
-        try:
-            self.training = False
-            return self._forward_train(item_seq, mask, target).view(())
-        finally:
-            self.training = was
-
-    def _forward_train(self, item_seq, mask, target):
-        B, L, D = item_seq.shape[0], self.max_seq_length, self.hidden_size
-        dev = item_seq.device
-        table = self.embedding.weight.data
-        g = ops.srgnn_graph(item_seq, self.item_num, target, want_occ=self.training, out=self._gbufs)
-        if self.training:
-            sp = self._table_prepare(g, B, L, D, dev)
-        elif self._table_hooks is not None:
-            self.sync_table()
+    def _step_forward(self, table, g, mask, target):
+        """The graph dict `g`, mask [B, L] and target [B, 2] rows of `table` -> loss [1]; in training mode `_saved` holds what
+        `_step_backward` reads."""
+        B, L, D = mask.shape[0], self.max_seq_length, self.hidden_size
         Hs, Xs, saves = self._gnn_forward(table, g["nodes"], g["A"], B, self.training)
         Hn = Hs[self.step]
         cat, sig, alpha = self._readout(Hn, g["alias"], mask, B, self.training)
@@ -206,16 +156,16 @@ class SRGNN(TableHooks, PackedModel):
                  use_ws=False)
         loss, coef = ops.srgnn_pair_fwd(out_pad, L * D, table, target, B)
         if self.training:
-            self._saved = dict(B=B, g=g, sp=sp, Hs=Hs, Xs=Xs, saves=saves, cat=cat, sig=sig, alpha=alpha, mask=mask, target=target,
+            self._saved = dict(B=B, g=g, Hs=Hs, Xs=Xs, saves=saves, cat=cat, sig=sig, alpha=alpha, mask=mask, target=target,
                                out_pad=out_pad, coef=coef)
         return loss
 
-    def _backward_train(self, gsd):
-        s = self._take_saved()
+    def _step_backward(self, gsd, table, s):
+        """What `_step_forward` saved -> (dH [B L, D] = d loss / d H_0 per node, coef_pad [B, L]): with s["out_pad"] the three
+        terms of the rows' gradient, which the caller's segment sum joins.  The 17 weight gradients land in the flat buffer."""
         B, L, D, S = s["B"], self.max_seq_length, self.hidden_size, self.step
         BL = B * L
         dev = s["cat"].device
-        table = self.embedding.weight.data
         g = lambda name, span=1: self._p(name, grad=True, span=span)
         dout = self._buf("dout", (B, D))
         coef_pad = self._buf("coef_pad", (B, L), zero=True)
@@ -248,6 +198,105 @@ class SRGNN(TableHooks, PackedModel):
             (dgh.view(S * BL, 3 * D), Hprev, g("w_hh"), g("b_hh")),
             (dE.view(S * BL, 2 * D), Hprev, g("ein.w", span=2), g("ein.b", span=2)),
         ])
+        return dH, coef_pad
+
+    # ------------------------------------------------------------------------------------------ evaluation
+    @torch.no_grad()
+    def _encode(self, item_seq, table):
+        """item_seq int64 [B, L] (right-padded; mask = item_seq != 0) with its node rows in `table` -> out [B, D]."""
+        if item_seq.dim() != 2 or item_seq.shape[1] != self.max_seq_length:
+            raise ValueError(f"item_seq must be [B, {self.max_seq_length}], got {tuple(item_seq.shape)}")
+        item_seq = item_seq.contiguous()
+        B = item_seq.shape[0]
+        g = ops.srgnn_graph(item_seq, table.shape[0], want_mask=True)
+        Hs, _, _ = self._gnn_forward(table, g["nodes"], g["A"], B, train=False)
+        cat, _, _ = self._readout(Hs[self.step], g["alias"], g["mask"], B, train=False)
+        return ops.linear_fwd(cat, self._p("t.w"), self._p("t.b"))                         # [B, D]
+
+
+class SRGNN(SrgnnStep, TableHooks, PackedModel):
+    input_type = InputType.AUGSEQ
+    item_table_attr = "embedding"          # the reference's table name (optim.item_table_name)
+
+    def __init__(self, config, dataload):
+        super().__init__()
+        one_process(self, "the graph models")
+        self.item_num = dataload.item_num
+        D = config["embedding_size"]
+        self.embedding = nn.Embedding(self.item_num, D)
+        self._build_gnn(config)
+        stdv = 1.0 / math.sqrt(D)
+        for w in self.parameters():                       # srgnn.py _reset_parameters, in parameter order
+            w.data.uniform_(-stdv, stdv)
+        self._local_sparse = None                          # the sparse table (SASRec's bookkeeping)
+        self._occ_ws = self._occ_ws2 = None
+
+    def rec_parameter_names(self):
+        """{reference parameter name: flat-buffer key} in the reference's registration order (optim.native_to_torch_state):
+        the table and linear_edge_f (no gradient, no optimizer state) map to None."""
+        return {"embedding.weight": None, **self._gnn_parameter_names()}
+
+    # ------------------------------------------------------------------------------------------ the table (SASRec's machinery)
+    def _table_prepare(self, g, B, L, D, device):
+        """Occurrence sort of the batch's node and target ids, then the lazy catch-up of exactly those rows."""
+        cap = B * (L + 2)
+        sp = self._local_sparse
+        if sp is None or sp.cap != cap or sp.rows.shape[1] != D or sp.rows.device != device:
+            sp = self._local_sparse = ops.SparseRows(cap, D, device, packed=True)
+        need = ops.occ_ws_bytes(B, L)
+        if self._occ_ws is None or self._occ_ws.numel() < need or self._occ_ws.device != device:
+            self._occ_ws = torch.empty(need, dtype=torch.uint8, device=device)
+        env = os.environ.get("PXR_SEGSUM_SPLIT", "auto")
+        need2 = ops.occ_split_ws_bytes(B, L, D) if (env == "1" or (env != "0" and 3 * B * L >= 30000)) else 0
+        if need2 == 0:
+            self._occ_ws2 = None
+        elif self._occ_ws2 is None or self._occ_ws2.numel() != need2 or self._occ_ws2.device != device:
+            self._occ_ws2 = torch.zeros(need2, dtype=torch.uint8, device=device)
+        ops.occ_sort(g["occ"], L, (3 * L, 0, L, 2 * L), self.item_num, sp, self._occ_ws)
+        if self._table_hooks is not None:
+            self._table_hooks.catch_up_rows(sp.idx, sp.n, sp.cap)
+        return sp
+
+    # ------------------------------------------------------------------------------------------ training
+    def forward(self, interaction):
+        """interaction = (item_seq [B, L], mask [B, L], target [B, 2]) or (item_seq, mask | target [B, L + 2]) -> 0-dim loss."""
+        if len(interaction) == 3:
+            item_seq, mask, target = interaction
+        else:
+            item_seq, tail = interaction
+            L = self.max_seq_length
+            mask, target = tail[:, :L], tail[:, L:L + 2]
+        L = self.max_seq_length
+        if item_seq.dim() != 2 or item_seq.shape[1] != L:
+            raise ValueError(f"item_seq must be [B, {L}], got {tuple(item_seq.shape)}")
+        self._ensure_packed()
+        item_seq, mask, target = item_seq.contiguous(), mask.contiguous(), target.contiguous()
+        if torch.is_grad_enabled() and self.training:
+            return TrainStep.apply(self._anchor, self, item_seq, mask, target)
+        was = self.training
+        try:
+            self.training = False
+            return self._forward_train(item_seq, mask, target).view(())
+        finally:
+            self.training = was
+
+    def _forward_train(self, item_seq, mask, target):
+        B, L, D = item_seq.shape[0], self.max_seq_length, self.hidden_size
+        table = self.embedding.weight.data
+        g = ops.srgnn_graph(item_seq, self.item_num, target, want_occ=self.training, out=self._gbufs)
+        if self.training:
+            sp = self._table_prepare(g, B, L, D, item_seq.device)
+        elif self._table_hooks is not None:
+            self.sync_table()
+        loss = self._step_forward(table, g, mask, target)
+        if self.training:
+            self._saved["sp"] = sp
+        return loss
+
+    def _backward_train(self, gsd):
+        s = self._take_saved()
+        B, L, D = s["B"], self.max_seq_length, self.hidden_size
+        dH, coef_pad = self._step_backward(gsd, self.embedding.weight.data, s)
         sp = s["sp"]
         ops.sasrec_occ_segsum(self._occ_ws, dH.view(B, L, D), s["out_pad"], coef_pad, self.item_num, sp, 1.0, ws2=self._occ_ws2)
         self.sparse_table_grad = sp
@@ -255,22 +304,11 @@ class SRGNN(TableHooks, PackedModel):
 
     # ------------------------------------------------------------------------------------------ evaluation
     @torch.no_grad()
-    def _encode(self, item_seq, table):
-        B = item_seq.shape[0]
-        g = ops.srgnn_graph(item_seq, table.shape[0], want_mask=True)
-        Hs, _, _ = self._gnn_forward(table, g["nodes"], g["A"], B, train=False)
-        cat, _, _ = self._readout(Hs[self.step], g["alias"], g["mask"], B, train=False)
-        return ops.linear_fwd(cat, self._p("t.w"), self._p("t.b"))                         # [B, D]
-
-    @torch.no_grad()
     def encode_last(self, item_seq, item_feature=None):
         """item_seq int64 [B, L] (right-padded; mask = item_seq != 0) -> (out [B, 1, D], out [B, D]): the query vectors of the
         fused scoring (`last` with row stride D)."""
         self._ensure_packed()
         self.sync_table()
-        item_seq = item_seq.contiguous()
-        if item_seq.dim() != 2 or item_seq.shape[1] != self.max_seq_length:
-            raise ValueError(f"item_seq must be [B, {self.max_seq_length}], got {tuple(item_seq.shape)}")
         table = self.embedding.weight.data if item_feature is None else item_feature.contiguous()
         out = self._encode(item_seq, table)
         return out.view(out.shape[0], 1, -1), out

@@ -1,0 +1,322 @@
+"""MOSRGNN without a GPU: the registration, the shipped yaml, the batcher (GraphTrainBatcher's batches as positions into the
+batch's distinct images), the state_dict, the torch restatement (tests/mosrgnn_restate.py) against SRGNN's NumPy restatement with
+the table set to E and against the fixture of the reference's own class, the padding rows' exact zeros, and the CPU refusal."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import mosrgnn_restate as R
+from tests import srgnn_restate as SR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+PFX = "visual_encoder.item_encoder."
+TOWER = 2e-5         # per-entry budget of the torch-module tower against the reference's (tests/test_mopool_cpu.py)
+
+
+def _config(D, L, step, tune):
+    return {"embedding_size": D, "step": step, "MAX_ITEM_LIST_LENGTH": L, "seed": 2020,
+            "encoder_name": "clip-vit-tiny-test", "encoder_source": "transformers", "pretrain_path": None,
+            "fine_tune_arg": {"tune_scale": tune, "pre_trained": True, "activation": "relu", "dnn_layers": [], "method": "mean"}}
+
+
+def my_name(k):
+    """A fixture key (transformers-5.x names) -> this build's parameter name (`vision_model.` in the encoder's names)."""
+    return (PFX + "vision_model." + k[len(PFX):]) if k.startswith(PFX) else k
+
+
+def fixture_state(g):
+    """The fixture's state_dict under this build's names, without the unused post_layernorm pair."""
+    return {my_name(k): torch.from_numpy(g["sd." + k]) for k in (str(x) for x in g["sd.keys"]) if "post_layernorm" not in k}
+
+
+def build_from_fixture(g, step=1, tune=None):
+    import pixelrec_amd.model as M
+
+    I, D, L = (int(x) for x in g["meta"][:3])
+
+    class DL:
+        item_num = I
+
+    m = M.MOSRGNN(_config(D, L, step, int(g["meta"][6]) if tune is None else tune), DL())
+    m.load_state_dict(fixture_state(g), strict=True)
+    return m
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(os.path.join(GOLD, "mosrgnn_tiny.npz"))
+
+
+# ------------------------------------------------------------------------------------------------------------ registration, batcher
+@pytest.fixture(scope="module")
+def tiny(tmp_path_factory):
+    from pixelrec_amd.config import Config
+    from pixelrec_amd.data import load_data
+
+    d = tmp_path_factory.mktemp("mosrgnn")
+    (d / "m.yaml").write_text("model: MOSRGNN\nembedding_size: 8\nstep: 2\n")
+    (d / "o.yaml").write_text(f"seed: 2020\ndata_path: {GOLD}/\ndataset: TinyInter\nMAX_ITEM_LIST_LENGTH: 5\ntrain_batch_size: 4\n"
+                              "eval_batch_size: 16\nuse_modality: True\n")
+    config = Config([str(d / "m.yaml"), str(d / "o.yaml")])
+    data = load_data(config)
+    data.build()
+    return config, data
+
+
+def test_model_is_registered_as_augseq_with_its_batcher_and_the_graph_evaluation(tiny):
+    from pixelrec_amd.data.dataset import GraphEvalBatcher, GraphTrainBatcher, MoGraphTrainBatcher
+    from pixelrec_amd.data.utils import LOADERS, SUPPORTED, _TrainLoader, bulid_dataloader
+    from pixelrec_amd.utils import get_model
+    from pixelrec_amd.utils.enum_type import InputType
+
+    config, data = tiny
+    cls = get_model("MOSRGNN")
+    assert SUPPORTED["MOSRGNN"] == "AUGSEQ" and cls.__name__ == "MOSRGNN" and cls.input_type == InputType.AUGSEQ
+    assert LOADERS["MOSRGNN"] == (MoGraphTrainBatcher, GraphEvalBatcher, _TrainLoader) and issubclass(MoGraphTrainBatcher, GraphTrainBatcher)
+    train, valid, test = bulid_dataloader(config, data)
+    assert isinstance(train.batcher, MoGraphTrainBatcher) and isinstance(valid, GraphEvalBatcher) and isinstance(test, GraphEvalBatcher)
+
+
+def test_shipped_yaml_selects_the_class_and_the_batcher():
+    from pixelrec_amd.config import Config
+    from pixelrec_amd.data.utils import SUPPORTED
+    from pixelrec_amd.utils import get_model
+
+    config = Config([os.path.join(ROOT, "configs", "PixelNet", "srgnn.yaml"), os.path.join(ROOT, "configs", "overall", "ViT.yaml")])
+    assert config["model"] == "MOSRGNN" and get_model(config["model"]).__name__ == "MOSRGNN" and SUPPORTED[config["model"]] == "AUGSEQ"
+    assert (config["embedding_size"], config["step"]) == (512, 2)
+    assert config["use_modality"] and len(config["optim_args"]) == 4
+
+
+def test_batcher_yields_the_graph_batchers_batches_as_positions_into_the_batchs_distinct_images(tiny):
+    from pixelrec_amd.data.dataset import GraphTrainBatcher, MoGraphTrainBatcher
+
+    config, data = tiny
+    b, ref = MoGraphTrainBatcher(config, data), GraphTrainBatcher(config, data)
+    assert len(b) == len(ref) and b.n == ref.n and np.array_equal(b._indices(), ref._indices())
+    L, seen = 5, 0
+    for (index, image_ids), (item_seq, mask, target) in zip(b, ref):       # the same seed: the same prefixes and negatives
+        assert index.dtype == torch.int64 and image_ids.dtype == torch.int64 and tuple(index.shape) == (len(item_seq), L + 2)
+        ids = image_ids.numpy()
+        assert ids[0] == 0 and (np.diff(ids) > 0).all()                     # 0 first, the rest strictly ascending (so distinct)
+        assert 0 <= int(index.min()) and int(index.max()) < len(ids)
+        assert set(np.unique(index.numpy()).tolist()) | {0} == set(range(len(ids)))        # no image listed without a reader
+        items = ids[index.numpy()]
+        assert np.array_equal(items[:, :L], item_seq.numpy()) and np.array_equal(items[:, L:], target.numpy())
+        assert np.array_equal(index.numpy()[:, :L] != 0, mask.numpy() != 0)  # the mask is index != 0
+        # node order by position is node order by id: the two session graphs are one graph
+        n_pos, a_pos, A_pos = SR.session_graph(index.numpy()[:, :L])
+        n_id, a_id, A_id = SR.session_graph(item_seq.numpy())
+        assert np.array_equal(ids[n_pos], n_id) and np.array_equal(a_pos, a_id) and np.array_equal(A_pos, A_id)
+        seen += len(item_seq)
+    assert seen == ref.n
+    first_epoch = [(i.clone(), j.clone()) for i, j in b]
+    b.set_epoch(1)
+    other = [(i.clone(), j.clone()) for i, j in b]
+    assert any(x[0].shape != y[0].shape or not torch.equal(x[0], y[0]) for x, y in zip(first_epoch, other))  # two epochs differ
+
+
+# ------------------------------------------------------------------------------------------------------------ model surface
+def test_state_dict_is_the_references_and_loads_strictly(gold):
+    g = gold
+    m = build_from_fixture(g)
+    keys = list(m.state_dict())
+    want = [my_name(str(k)) for k in g["sd.keys"] if "post_layernorm" not in str(k)]
+    rec = [k for k in keys if not k.startswith("visual_encoder.")]
+    assert keys == want and keys[-19:] == rec                        # the encoder first, then gnn.* (12), then the four Linears (7)
+    assert [k for k in rec if k not in R.EDGE_F] == R.NAMES and rec[10:12] == R.EDGE_F
+    assert [n for n, _ in m.named_parameters()] == keys              # no buffer
+    names = m.rec_parameter_names()
+    assert list(names) == rec and [k for k, v in names.items() if v is None] == R.EDGE_F      # no table entry
+    for k, v in fixture_state(g).items():
+        assert torch.equal(m.state_dict()[k], v)
+    frozen = [n for n, p in m.named_parameters() if not p.requires_grad]
+    assert len(frozen) == int(g["meta"][6]) == len(g["frozen"]) and all("visual_encoder" in n for n in frozen)
+
+
+def test_fresh_block_is_uniform_in_one_over_sqrt_d_with_default_linear_biases():
+    import pixelrec_amd.model as M
+
+    class DL:
+        item_num = 13
+
+    torch.manual_seed(3)
+    D = 64
+    m = M.MOSRGNN(_config(D, 10, 2, 37), DL())
+    stdv = 1.0 / D ** 0.5
+    uniform = [p for p in m.gnn.parameters()] + [lin.weight for lin in (m.linear_one, m.linear_two, m.linear_three, m.linear_transform)]
+    uniform += list(m.visual_encoder.rec_fc.parameters())
+    for p in uniform:
+        assert float(p.detach().abs().max()) <= stdv
+        if p.numel() >= 1024:
+            assert abs(float(p.detach().std()) - stdv / 3 ** 0.5) < 0.1 * stdv      # uniform(-a, a) has std a / sqrt(3)
+    # nn.Linear's default bias bound is 1 / sqrt(fan_in): linear_transform's is below stdv, which a re-draw would not be
+    assert float(m.linear_transform.bias.detach().abs().max()) <= 1.0 / (2 * D) ** 0.5
+    assert (m.step, m.max_seq_length, m.hidden_size) == (2, 10, D)
+
+
+@pytest.mark.parametrize("D,L,step", [(10, 5, 1), (8, 0, 1), (8, 65, 1), (8, 5, 0)])
+def test_constructor_refuses_what_the_kernels_cannot_serve(D, L, step):
+    import pixelrec_amd.model as M
+
+    class DL:
+        item_num = 13
+
+    with pytest.raises(ValueError):
+        M.MOSRGNN(_config(D, L, step, 37), DL())
+
+
+def test_cpu_model_raises_before_the_tower_runs(gold):
+    from pixelrec_amd.lib import PxrError
+
+    m = build_from_fixture(gold)
+    called = []
+    m.visual_encoder.register_forward_pre_hook(lambda *a: called.append(1))
+    index = torch.zeros(2, 7, dtype=torch.int64)
+    with pytest.raises(PxrError):
+        m((index, torch.zeros(3, 3, 64, 64)))
+    with pytest.raises(PxrError):
+        m((index[:, :5], torch.zeros(2, 5, 10), index[:, :5], torch.zeros(14, 3, 64, 64)))
+    assert not called
+    with pytest.raises(PxrError):
+        m.loss_from_embeddings(torch.zeros(3, 8), index[:, :5], index[:, 5:])
+    with pytest.raises(ValueError):
+        m.loss_from_embeddings(torch.zeros(3, 12), index[:, :5], index[:, 5:])
+
+
+# ------------------------------------------------------------------------------------------------------------ restatement, fixture
+def _random_case(seed, B, L, D, M, dtype):
+    gen = torch.Generator().manual_seed(seed)
+    P = {k: (torch.rand(*s, generator=gen, dtype=torch.float64) * 2 - 1) * D ** -0.5 for k, s in R.shapes(D).items()}
+    E = torch.randn(M, D, generator=gen, dtype=torch.float64) * 0.5
+    rng = np.random.default_rng(seed)
+    seq = np.zeros((B, L), dtype=np.int64)
+    for b in range(B):
+        n = 1 + b % L
+        seq[b, :n] = rng.integers(1, M - 1, size=n)                  # row M - 1 is read by nobody
+    target = rng.integers(1, M - 1, size=(B, 2))
+    return {k: v.to(dtype) for k, v in P.items()}, E.to(dtype), seq, target
+
+
+@pytest.mark.parametrize("step", [1, 2])
+def test_restatement_is_srgnns_with_the_table_set_to_e(step):
+    """mosrgnn_restate in float64 under autograd == srgnn_restate.forward_backward (hand-written NumPy) with embedding.weight := E,
+    to 1e-12: the loss, the 17 gradients and dE."""
+    P, E, seq, target = _random_case(11, 7, 5, 8, 12, torch.float64)
+    loss, grads = R.loss_and_grads(P, E, seq, target, step)
+    Pn = {k: v.numpy() for k, v in P.items()}
+    Pn["embedding.weight"] = E.numpy()
+    want, G, _ = SR.forward_backward(Pn, seq, (seq != 0).astype(np.int64), target, step)
+    assert abs(float(loss) - want) <= 1e-12
+    for k in R.NAMES:
+        assert float(np.abs(grads[k].numpy() - G[k]).max()) <= 1e-12, k
+    assert float(np.abs(grads[R.E_KEY].numpy() - G["embedding.weight"]).max()) <= 1e-12
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_padding_rows_get_exact_zeros_and_the_pad_image_changes_no_bit(dtype):
+    P, E, seq, target = _random_case(12, 7, 5, 8, 12, dtype)
+    assert (seq == 0).any() and (seq[4] != 0).all()
+    loss, grads = R.loss_and_grads(P, E, seq, target, 2)
+    dE = grads[R.E_KEY]
+    assert float(dE[0].abs().max()) == 0 and float(dE[11].abs().max()) == 0 and float(dE[1:11].abs().max()) > 0
+    E2 = E.clone()
+    E2[0] = torch.randn(E.shape[1], dtype=dtype) * 3                  # another pad image
+    loss2, grads2 = R.loss_and_grads(P, E2, seq, target, 2)
+    assert torch.equal(loss, loss2)
+    for k in grads:
+        assert torch.equal(grads[k], grads2[k]), k
+
+
+def test_fixture_pins_the_composition_on_the_float64_cpu_tower(gold):
+    """The build's torch-module tower (visual.py's CPU path) in float64 on the fixture's state, then mosrgnn_restate in float64 on
+    its output -- autograd through both -- against the reference's stored losses, all 27 gradients, item features and predict, for
+    both step values: each within its stored ref_err (the reference's own float32 distance from float64) plus TOWER."""
+    g = gold
+    m = build_from_fixture(g).double().eval()
+    store = torch.from_numpy(g["store"].astype(np.float64))
+    P = {k: m.get_parameter(k) for k in R.NAMES}
+    feat = m.visual_encoder(store).detach()
+    err = float((feat - torch.from_numpy(g["eval.item_feature"]).double()).abs().max())
+    print("item features: float64 CPU tower vs reference", err, "ref_err", float(g["ref_err.item_feature"]))
+    assert err <= TOWER + float(g["ref_err.item_feature"])
+    assert float(feat[0].abs().max()) > 0                            # the zero image's encoding is not zero
+    names = [str(k) for k in g["param.keys"]]
+    assert len(names) == 27 and names[-17:] == R.NAMES
+    for step in (int(s) for s in g["steps"]):
+        p = f"s{step}."
+        for j in range(2):
+            m.zero_grad()
+            loss = R.loss_of(P, m.visual_encoder(store), g[f"b{j}.item_seq"], g[f"b{j}.target"], step)     # an id IS its row
+            loss.backward()
+            ref = float(g[p + f"b{j}.loss"])
+            print("step", step, "batch", j, "loss", float(loss), ref, "ref_err", float(g[f"ref_err.{p}b{j}.loss"]))
+            assert abs(float(loss) - ref) <= TOWER + float(g[f"ref_err.{p}b{j}.loss"])
+            for k in names:
+                got, want = m.get_parameter(my_name(k)).grad, torch.from_numpy(g[p + f"b{j}.grad." + k]).double()
+                e = float((got - want).abs().max())
+                assert e <= TOWER + float(g[f"ref_err.{p}b{j}.grad." + k]), (k, e)
+            assert m.gnn.linear_edge_f.weight.grad is None and m.gnn.linear_edge_f.bias.grad is None
+        with torch.no_grad():
+            s = R.predict({k: v.detach() for k, v in P.items()}, feat, g["eval.windows"], step)
+        e = float((s - torch.from_numpy(g[p + "eval.scores"]).double()).abs().max())
+        print("step", step, "scores", e, "ref_err", float(g[f"ref_err.{p}scores"]))
+        assert e <= TOWER + float(g[f"ref_err.{p}scores"])
+
+
+def test_fixture_batches_hold_the_cases_they_are_there_for(gold):
+    g = gold
+    I, D, L, B = (int(x) for x in g["meta"][:4])
+    assert (I, D, L, B) == (13, 8, 5, 6) and g["steps"].tolist() == [1, 2] and tuple(g["store"].shape) == (13, 3, 64, 64)
+    seq, tgt = g["b0.item_seq"], g["b0.target"]
+    real = [r[r != 0].tolist() for r in seq]
+    assert any(len(r) >= 3 and r[0] in r[2:] for r in real)                                     # a revisit
+    assert any(a == b for r in real for a, b in zip(r, r[1:]))                                  # a self-loop
+    assert any(len(set(zip(r, r[1:]))) < len(r) - 1 for r in real)                              # a repeated transition
+    assert any(len(r) == 1 for r in real)                                                       # a one-item session
+    assert any(len(r) == L and len(set(r)) == L for r in real)                                  # full length, no padding node
+    nodes_of = [set(r) for r in real]
+    assert any(int(tgt[b, 0]) in nodes_of[c] for b in range(B) for c in range(B) if c != b)     # a node here, a positive there
+    assert any(int(tgt[b, 1]) in nodes_of[c] for b in range(B) for c in range(B) if c != b)     # a node here, a negative there
+    assert max(sum(i in s for s in nodes_of) for i in range(1, I)) >= 3                         # a node in three sessions
+    assert g["b0.A"].shape == (B, L, 2 * L) and g["b1.A"].shape[1] < L                          # batch 1: the reference's graphs are smaller
+    for j in range(2):
+        n = g[f"b{j}.A"].shape[1]
+        nd, al, A = SR.session_graph(g[f"b{j}.item_seq"], n)                                   # the collate's own graph
+        assert np.array_equal(nd, g[f"b{j}.nodes"]) and np.array_equal(al, g[f"b{j}.alias"]) and np.allclose(A, g[f"b{j}.A"], atol=1e-7)
+        assert (g[f"b{j}.target"] != 0).all() and int(g[f"b{j}.target"].max()) < I
+    assert tuple(g["s2.eval.scores"].shape) == (6, I) and (g["eval.windows"][:, 0] != 0).all()
+    assert os.path.getsize(os.path.join(GOLD, "mosrgnn_tiny.npz")) < 1_000_000
+
+
+# ------------------------------------------------------------------------------------------------------------ optimizer
+class _Wrap:
+    def __init__(self, m):
+        self.module = m
+
+
+def _trainer_optimizer(m, optim_args):
+    from pixelrec_amd.trainer import Trainer
+
+    t = Trainer.__new__(Trainer)
+    t.optim_args, t.model, t.config = optim_args, _Wrap(m), {"decay_check_name": None}
+    return t._build_optimizer()
+
+
+FOUR = {"modal_lr": 1e-4, "rec_lr": 3e-4, "modal_decay": 0.0, "rec_decay": 0.1}
+
+
+def test_four_optim_args_give_the_encoder_group_and_a_rec_group_without_a_table(gold):
+    from pixelrec_amd.optim import OptimizerGroup, PxrAdamW, VisualAdamW, has_lazy_table, reference_rec_parameter_names
+
+    m = build_from_fixture(gold, tune=37)
+    opt = _trainer_optimizer(m, FOUR)
+    assert isinstance(opt, OptimizerGroup)
+    vis, rec = opt._split()
+    assert isinstance(vis, VisualAdamW) and isinstance(rec, PxrAdamW) and rec.has_table is False and not has_lazy_table(m)
+    assert [len(vis._trainable()), len(reference_rec_parameter_names(m))] == [18, 19]
+    assert (vis.param_groups[0]["lr"], vis.param_groups[0]["weight_decay"]) == (1e-4, 0.0)
+    assert (rec.param_groups[0]["lr"], rec.param_groups[0]["weight_decay"]) == (3e-4, 0.1)
