@@ -512,7 +512,8 @@ int pxr_bpr_ln_bwd_f32(const float* pos_score, const float* neg_score, const flo
 int pxr_mosasrec_emb_grad_f32(const float* dx0, const float* out, const float* coef, int B, int L, int D, float* d_emb,
                               void* stream);
 /* The reference's image transform on the GPU (data/dataset/trainset.py:85-96): uint8 HWC store [n_store,H,W,3] gathered
- * by item id -> fp32 [n,3,H,W] = (x/255 - 0.5)/0.5; id 0 (padding) -> zeros. */
+ * by item id -> fp32 [n,3,H,W] = (x/255 - 0.5)/0.5; id 0 (padding) -> zeros.  An id outside [0, n_store) -> zeros too
+ * (nothing is read) and PXR_STATUS_BAD_INDEX in the status word of pxr_set_status_word. */
 int pxr_image_u8_to_f32(const uint8_t* store, int64_t n_store, int H, int W, const int64_t* ids, int n, float* out,
                         void* stream);
 

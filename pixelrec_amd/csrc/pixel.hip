@@ -11,7 +11,8 @@
 // (2) pxr_image_u8_to_f32: the reference's per-item image transform (trainset.py:85-90: Resize(224) is the identity
 //     on the 224x224 LMDB images of generate_lmdb.py, ToTensor = /255 and HWC->CHW, Normalize(mean=std=0.5)) done on
 //     the GPU for a whole batch of uint8 HWC images gathered by item id; id 0 (padding) yields the all-zero image
-//     (`self.pad_image = torch.zeros((3,224,224))`, trainset.py:96).
+//     (`self.pad_image = torch.zeros((3,224,224))`, trainset.py:96).  An id outside [0, n_store) also yields the zero image
+//     (nothing is read) and sets PXR_STATUS_BAD_INDEX in the device status word, like every other gather.
 #include "pxr_common.h"
 
 namespace pxr {
@@ -43,7 +44,7 @@ __global__ void __launch_bounds__(256) mosasrec_emb_grad_kernel(const float4* __
 // out[n, c, y, x] = (img[ids[n], y, x, c] / 255 - 0.5) / 0.5   (0 for ids[n] == 0)
 __global__ void __launch_bounds__(256) image_u8_to_f32_kernel(const uint8_t* __restrict__ store,
                                                               const int64_t* __restrict__ ids, int n, int64_t n_store,
-                                                              int H, int W, float* __restrict__ out) {
+                                                              int H, int W, float* __restrict__ out, int32_t* status) {
   const int64_t hw = (int64_t)H * W;
   const int64_t per = hw * 3;
   const int64_t total = (int64_t)n * per;
@@ -54,7 +55,13 @@ __global__ void __launch_bounds__(256) image_u8_to_f32_kernel(const uint8_t* __r
     const int64_t p = rem - (int64_t)c * hw;
     const int64_t id = ids[img];
     float v = 0.f;
-    if (id > 0 && id < n_store) v = ((float)store[id * per + p * 3 + c] / 255.0f - 0.5f) / 0.5f;
+    if (id > 0 && id < n_store) {
+      v = ((float)store[id * per + p * 3 + c] / 255.0f - 0.5f) / 0.5f;
+    } else if (id != 0 && rem == 0 && status) {
+      // an id outside the store is an ERROR (the reference fails on an item without an image): nothing is read and the zero
+      // image is written, and the lane of the image's first element flags the status word (ops.raise_on_bad_indices)
+      atomicOr(status, PXR_STATUS_BAD_INDEX);
+    }
     out[i] = v;
   }
 }
@@ -85,6 +92,6 @@ extern "C" int pxr_image_u8_to_f32(const uint8_t* store, int64_t n_store, int H,
   int64_t blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(image_u8_to_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, store, ids, n,
-                     n_store, H, W, out);
+                     n_store, H, W, out, pxr_status_word());
   return pxr_check_launch("pxr_image_u8_to_f32");
 }

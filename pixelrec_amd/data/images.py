@@ -106,7 +106,8 @@ class ImageStore:
         return ImageStore(out.to(device))
 
     def batch(self, ids: torch.Tensor) -> torch.Tensor:
-        """ids int64 [...] on the store's device -> fp32 [..., 3, H, W], reference-normalised, on the device."""
+        """ids int64 [...] on the store's device -> fp32 [..., 3, H, W], reference-normalised, on the device.  An id outside the
+        store gets the zero image and flags the device status word: IndexError at the next ops.raise_on_bad_indices."""
         from .. import ops
 
         return ops.image_u8_to_f32(self.images, ids.contiguous())

@@ -450,16 +450,37 @@ def causal_col2im(dxcol: torch.Tensor, k: int, dilation: int) -> torch.Tensor:
     return out
 
 
+def _gru_operands(who: str, B: int, H: int, operands):
+    """The operands of one GRU step beside its [B, H] anchor, as (name, tensor, width, optional): each contiguous fp32 [B, width]
+    on the device, None only where the entry point takes a null pointer."""
+    for name, t, width, optional in operands:
+        if t is None and optional:
+            continue
+        _req(t, torch.float32, name)
+        if tuple(t.shape) != (B, width):
+            raise _l.PxrError(f"{who}: {name} must be [{B}, {width}], got {list(t.shape)}")
+
+
 def gru_gates_fwd(gi, gh, h_prev, h_out, save=None):
     """One GRU step's gates (pxr_gru_gates_fwd_f32): gi, gh [B, 3H]; h_prev [B, H] | None; writes h_out [B, H] (and save [B, 4H])."""
+    _req(h_out, torch.float32, "h_out")
+    if h_out.dim() != 2:
+        raise _l.PxrError("gru_gates_fwd: h_out must be [B, H]")
     B, H = h_out.shape
+    _gru_operands("gru_gates_fwd", B, H, (("gi", gi, 3 * H, False), ("gh", gh, 3 * H, False), ("h_prev", h_prev, H, True),
+                                          ("save", save, 4 * H, True)))
     _l.check(_l.load().pxr_gru_gates_fwd_f32(_l.ptr(gi), _l.ptr(gh), _l.ptr(h_prev), _l.ptr(h_out), _l.ptr(save), B, H,
                                              _l.stream_ptr()), "pxr_gru_gates_fwd_f32")
 
 
 def gru_gates_bwd(dh, save, h_prev, dgi, dgh, dh_prev):
     """Backward of gru_gates_fwd (pxr_gru_gates_bwd_f32): dh [B, H] -> dgi, dgh [B, 3H], dh_prev [B, H] = dh * z."""
+    _req(dh, torch.float32, "dh")
+    if dh.dim() != 2:
+        raise _l.PxrError("gru_gates_bwd: dh must be [B, H]")
     B, H = dh.shape
+    _gru_operands("gru_gates_bwd", B, H, (("save", save, 4 * H, False), ("h_prev", h_prev, H, True), ("dgi", dgi, 3 * H, False),
+                                          ("dgh", dgh, 3 * H, False), ("dh_prev", dh_prev, H, False)))
     _l.check(_l.load().pxr_gru_gates_bwd_f32(_l.ptr(dh), _l.ptr(save), _l.ptr(h_prev), _l.ptr(dgi), _l.ptr(dgh), _l.ptr(dh_prev),
                                              B, H, _l.stream_ptr()), "pxr_gru_gates_bwd_f32")
 
@@ -1652,7 +1673,15 @@ def sasrec_occ_segsum_apply(ws: torch.Tensor, dx0, out, coef, n_table, sp: Spars
 def mosasrec_emb_grad(dx0, out, coef):
     """-> d_emb [B, L+1, 2, D] (see pxr.h)."""
     Lb = _l.load()
+    _req(dx0, torch.float32, "dx0"); _req(out, torch.float32, "out"); _req(coef, torch.float32, "coef")
+    if out.dim() != 3:
+        raise _l.PxrError("mosasrec_emb_grad: out must be [B, L, D]")
     B, L, D = out.shape
+    if D % 4 != 0:
+        raise _l.PxrError(f"mosasrec_emb_grad: D must be a multiple of 4 (D={D})")
+    if dx0.numel() != B * L * D or coef.numel() != B * L:
+        raise _l.PxrError(f"mosasrec_emb_grad: dx0 must hold B*L*D = {B * L * D} and coef B*L = {B * L} elements, got "
+                          f"{dx0.numel()} and {coef.numel()}")
     d = torch.empty(B, L + 1, 2, D, dtype=torch.float32, device=out.device)
     _l.check(Lb.pxr_mosasrec_emb_grad_f32(_l.ptr(dx0), _l.ptr(out), _l.ptr(coef), B, L, D, _l.ptr(d), _l.stream_ptr()),
              "pxr_mosasrec_emb_grad_f32")
@@ -1666,6 +1695,7 @@ def image_u8_to_f32(store: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     n_store, H, W, C = store.shape
     if C != 3:
         raise _l.PxrError("image store must be HWC with 3 channels")
+    device_status(store.device)       # an id outside the store is flagged on the device (zero image), raised at the next check
     out = torch.empty(*ids.shape, 3, H, W, dtype=torch.float32, device=store.device)
     _l.check(Lb.pxr_image_u8_to_f32(_l.ptr(store), n_store, H, W, _l.ptr(ids), ids.numel(), _l.ptr(out),
                                     _l.stream_ptr()), "pxr_image_u8_to_f32")

@@ -181,3 +181,45 @@ def test_trainer_runs_gru4rec_end_to_end(tmp_path, fused):
     topt = torch.optim.AdamW(tparams, lr=1.0, weight_decay=0.5)
     topt.load_state_dict(ck["optimizer"])
     assert topt.param_groups[0]["lr"] == 0.003 and topt.state[tparams[1]]["exp_avg"].shape == tparams[1].shape
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 1, 4, 1), (2, 3, 3, 8, 1)], ids=str)
+def test_gru4rec_single_step_at_one_position_and_through_three_layers(shape):
+    """(L, layers, B, E, mult): L = 1 never runs the recurrent GEMM nor the carry of the backward; L = 2 with three layers has a
+    middle layer that is handed its input by a layer below AND hands its gradient to one (the two-layer fixture has no such layer).
+    Loss and every gradient of one step, the table's included, against the float64 oracle."""
+    from oracle import gru4rec_oracle as GO
+    from pixelrec_amd.model import GRU4Rec
+
+    l, nl, b, e, mult = shape
+    n = 40
+
+    class DL:
+        item_num = n
+
+    torch.manual_seed(5)
+    m = GRU4Rec(_config(e, mult, nl, l), DL())
+    ref = {k: v.detach().clone().double().requires_grad_(True) for k, v in m.state_dict().items()}
+    assert sum(k.startswith("gru_layers.weight_hh") for k in ref) == nl
+    m = m.cuda().train()
+    rng = np.random.default_rng(8)
+    items = torch.from_numpy(rng.integers(1, n, size=(b, 2, l + 1)).astype(np.int64))
+    mask = torch.ones(b, l, dtype=torch.int64)
+    loss = m((items.cuda(), mask.cuda()))
+    loss.backward()
+    rl = GO.forward_loss(ref, items, mask, nl)
+    rl.backward()
+    assert abs(float(loss.detach()) - float(rl.detach())) <= 2e-6 + 2e-5 * abs(float(rl.detach()))
+    for name, p in m.named_parameters():
+        want = ref[name].grad.clone()
+        if name == "item_embedding.weight":                                     # sparse table gradient: densify; padding row zeroed
+            sp = m.sparse_table_grad
+            cnt = int(sp.n)
+            got = torch.zeros(n, e)
+            got[sp.idx[:cnt].cpu()] = sp.rows[:cnt].cpu()
+            want[0] = 0
+        else:
+            got = p.grad.cpu()
+        assert want.abs().max().item() > 0 or (l == 1 and "weight_hh" in name), name    # h_{-1} = 0: no recurrent gradient at L = 1
+        err = (got.double() - want).abs().max().item()
+        assert err <= 2e-6 + 2e-5 * want.abs().max().item(), (name, err)
