@@ -9,8 +9,8 @@ sequence, plane 1 the original sequence, plane 2 the negatives):
 
 Row 0 of E is the zero image's encoding ("no item"; it is not zero), row 1 the mask image's (all ones after normalisation), rows
 2.. the batch's distinct item images.  That is bert4rec.BERT4Rec's arithmetic on E, so the model is a composition: the id layout,
-the uncausal attention and the P positions are BERT4Rec's, the shell that hands E to the block (`_train_table`, the autograd
-bridge anchored at E) is MOSASRec's.  One step closes it: each image is encoded ONCE and read by many positions, so the gradient
+the uncausal attention and the P positions are BERT4Rec's, and E reaches the block through packed.EncoderRows (`_train_table`, the
+autograd bridge anchored at E).  One step closes it: each image is encoded ONCE and read by many positions, so the gradient
 with respect to E is a segment sum over a batch-local row space that has to come out DENSE ([M, D]: autograd hands it to the
 native tower) and in a fixed order -- pxr_seq_occ_dense_f32, the sums of BERT4Rec's sparse table gradient (dx0[r], +coef[r] out[r],
 -coef[r] out[r]) through the dense sink.  Row 0 and every row nobody reads get exactly +0.0; no float atomic is used.
@@ -37,12 +37,12 @@ from .. import ops
 from ..lib import PxrError
 from ..utils.enum_type import InputType
 from .bert4rec import _WithPositions
-from .packed import TrainStep, one_process, take_saved
+from .packed import EncoderRows, dense_scores, one_process
 from .seqcore import SeqRecCore
 from .visual import load_model
 
 
-class MOBERT4Rec(SeqRecCore):
+class MOBERT4Rec(EncoderRows, SeqRecCore):
     input_type = InputType.SEQ
     # BERT4Rec's bidirectional mask (key padding only)
     _causal = False
@@ -65,7 +65,6 @@ class MOBERT4Rec(SeqRecCore):
         self.LayerNorm.weight.data.fill_(1.0)
         self._head_layout = (3 * P, P, 2 * P)       # targets = idx[:, 1, t], negatives = idx[:, 2, t]
         self._occ_layout = (3 * P, 0, P, 2 * P)     # + the inputs idx[:, 0, t]
-        self._train_table = None
         self._item_feature = None
 
     def rec_parameter_names(self):
@@ -129,10 +128,7 @@ class MOBERT4Rec(SeqRecCore):
         masked_index int64 [B, P] -> 0-dim loss; under autograd its backward leaves d loss / d E [M, D] on E and the block's
         gradients in the flat gradient buffer."""
         P = self.max_seq_length
-        if E.dim() != 2 or E.dtype != torch.float32 or E.shape[1] != self.hidden_size:
-            raise ValueError(f"MOBERT4Rec: E must be float32 [M, {self.hidden_size}], got {tuple(E.shape)} {E.dtype}")
-        if E.device.type != "cuda":
-            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with .to('cuda') first")
+        self._check_rows(E, self.hidden_size)
         if index.dim() != 3 or index.shape[1] != 3 or index.shape[2] != P:
             raise ValueError(f"MOBERT4Rec: index must be [B, 3, {P}], got {tuple(index.shape)}")
         if tuple(masked_index.shape) != (index.shape[0], P):
@@ -142,10 +138,7 @@ class MOBERT4Rec(SeqRecCore):
         masked_index = masked_index.to(E.device).contiguous()
         table = E.detach().contiguous()
         if torch.is_grad_enabled() and self.training:
-            if not E.requires_grad:      # fully frozen encoder (or a plain tensor): still drive the backward of the block
-                E = E + self._anchor * 0
-            self._train_table = table
-            return TrainStep.apply(E, self, index, masked_index)
+            return self._encoded_step(E, table, index, masked_index)
         return self._forward_core(table, index, masked_index, train=False).view(())
 
     def _forward_train(self, index, masked_index):
@@ -153,17 +146,12 @@ class MOBERT4Rec(SeqRecCore):
 
     def _backward_train(self, gsd):
         """-> d loss / d E [M, D] (the bridge's anchor is the encoder's output)."""
-        take_saved(self, self._train_table)          # (backward() without a forward() raises here)
-        table, self._train_table = self._train_table, None
+        _, table = self._take_table()                # (backward() without a forward() raises here)
         dx0, coef, s = self._backward_core(gsd, table)
         # the gradient of E: stable sort of the 3 B P occurrences + segmented sum into a dense block (position 0: dropped)
         return ops.seq_occ_dense_grad(s["items"], self._occ_layout, dx0.view_as(s["out"]), s["out"], coef, table.shape[0])
 
     # ------------------------------------------------------------------------------------------ evaluation
-    @torch.no_grad()
-    def compute_item(self, item):
-        return self.visual_encoder(item)                                              # mobert4rec.py:134-136
-
     @staticmethod
     def extra_item_images(H, W, device):
         """What the catalogue holds behind the store's rows (reference BatchDataset: item_num + 1 entries for the BERT4Rec
@@ -212,8 +200,4 @@ class MOBERT4Rec(SeqRecCore):
         """scores [B, item_num] = state of the appended mask position x item_feature[:item_num]^T (mobert4rec.py:113-132)."""
         out, last = self.encode_last(item_seq, item_feature)
         B, P, D = out.shape
-        N = self.item_num
-        scores = torch.empty(B, N, dtype=torch.float32, device=out.device)
-        ops.gemm(True, True, B, N, D, last, P * D, item_feature[:N].contiguous(), D, scores, N, ops.EPI_NONE, use_ws=False)
-        ops.raise_on_bad_indices(out.device)     # an id outside the catalogue raises, like the reference's indexing (:117)
-        return scores
+        return dense_scores(last, item_feature[:self.item_num].contiguous(), ldq=P * D)

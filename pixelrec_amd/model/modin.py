@@ -24,8 +24,8 @@ The reference's dataset (MOTwoTowerTrainDataset, REC/data/utils.py:44) returns t
 distinct image of a batch is encoded ONCE and the gradients of its occurrences are summed into it -- the same parameter
 gradients as the reference's one image per position, which `forward` also accepts.
 
-The step between the row list and the occurrence rows is DIN's code (din.DinStep), and so is the evaluation (din.DinEval), on the
-encoded catalogue: `set_item_feature(feat)` hands the [item_num, D] matrix over, and
+The step between the row list and the occurrence rows is DIN's code (din.DinStep); E reaches it through packed.EncoderRows
+(`_train_table`, the autograd bridge anchored at E).  The evaluation is DIN's as well (din.DinEval), on the encoded catalogue: `set_item_feature(feat)` hands the [item_num, D] matrix over, and
 `fused_topk_batch` scores and ranks a batch of users in one launch of pxr_din_topk_f32; A q + b1 is made once per evaluation and
 cached until train(), load_state_dict or a new set_item_feature.  `predict` takes the reference's [B, item_num, L + 1] id tensor or
 [B, L] windows, in candidate chunks.
@@ -45,11 +45,11 @@ from .. import ops
 from ..lib import PxrError
 from ..utils.enum_type import InputType
 from .din import DinEval, DinStep
-from .packed import PackedModel, TrainStep, linear_names, split_tail, take_saved
+from .packed import EncoderRows, PackedModel, linear_names, split_tail, store_modal_inputs
 from .visual import load_model
 
 
-class MODIN(DinStep, DinEval, PackedModel):
+class MODIN(EncoderRows, DinStep, DinEval, PackedModel):
     input_type = InputType.SEQ
 
     def __init__(self, config, dataload):
@@ -61,7 +61,6 @@ class MODIN(DinStep, DinEval, PackedModel):
                 nn.init.zeros_(mod.bias.data)
         self.visual_encoder = load_model(config=config)
         self._item_feature = None
-        self._train_table = None
 
     # ------------------------------------------------------------------------------------------ packing
     def rec_parameter_names(self):
@@ -75,11 +74,7 @@ class MODIN(DinStep, DinEval, PackedModel):
         return split_tail(index, 2, "MODIN: expected [S, L + 2] positions (profile, positive, negative), got profile {profile} and "
                                     "target {tail}")
 
-    @staticmethod
-    def modal_inputs(store, data):
-        """The batcher's (index [S, L + 2], image_ids [M]) -> the forward's (index, all_item_modal [M, 3, H, W]): each distinct
-        image of the batch is fetched, and later encoded, once."""
-        return data[0], store.batch(data[1])
+    modal_inputs = staticmethod(store_modal_inputs)
 
     @staticmethod
     def _reference_form(items_modal, items):
@@ -109,42 +104,33 @@ class MODIN(DinStep, DinEval, PackedModel):
         """The head without the tower: E float32 [M, D] on the HIP device, profile_idx int64 [S, L] and target_idx int64 [S, 2]
         positions into E (0 = no item) -> 0-dim loss; under autograd its backward leaves d loss / d E [M, D] on E and the
         attention gradients in the flat gradient buffer."""
-        if E.dim() != 2 or E.dtype != torch.float32 or E.shape[1] != self.embedding_size:
-            raise ValueError(f"MODIN: E must be float32 [M, {self.embedding_size}], got {tuple(E.shape)} {E.dtype}")
-        if E.device.type != "cuda":
-            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with .to('cuda') first")
+        self._check_rows(E, self.embedding_size)
         self._ensure_packed()
         profile, target = self._split_index((profile_idx.to(E.device), target_idx.to(E.device)))
-        self._train_table = E.detach().contiguous()
-        if not torch.is_grad_enabled():
-            loss = self._forward_train(profile, target).view(()).clone()
-            self._saved = self._train_table = None
-            return loss
-        if not E.requires_grad:          # fully frozen encoder (or a plain tensor): still drive the backward of the head
-            E = E + self._anchor * 0
-        return TrainStep.apply(E, self, profile, target)
+        table = E.detach().contiguous()
+        if torch.is_grad_enabled():
+            return self._encoded_step(E, table, profile, target)
+        loss = self._head_fwd(table, profile, target).view(()).clone()
+        self._saved = None
+        return loss
 
     def _forward_train(self, profile, target):
-        E = self._train_table
+        return self._head_fwd(self._train_table, profile, target)
+
+    def _head_fwd(self, E, profile, target):
         rows, gidx = ops.din_positions(profile, target, E.shape[0], out=self._buf("rows", (2, profile.numel() + target.numel()), torch.int64))
         return self._attention_fwd(E, rows, gidx, profile, 0.0)      # modin.py:61: no regulariser
 
     def _backward_train(self, gsd):
         """-> d loss / d E [M, D] (the bridge's anchor is the encoder's output)."""
-        take_saved(self, self._train_table)          # (backward() without a forward() raises here)
-        M = self._train_table.shape[0]
+        _, table = self._take_table()                # (backward() without a forward() raises here)
         gidx, occ = self._attention_bwd(gsd)
         # the gradient of E: stable sort of the occurrence rows + segmented sum into a dense block (position 0: dropped)
-        dE = ops.embed_grad_dense(gidx, occ, M)
-        self._train_table = None
+        dE = ops.embed_grad_dense(gidx, occ, table.shape[0])
         self._step_done()
         return dE
 
     # ------------------------------------------------------------------------------------------ evaluation
-    @torch.no_grad()
-    def compute_item(self, item):
-        return self.visual_encoder(item)
-
     @torch.no_grad()
     def set_item_feature(self, feat):
         """The encoded catalogue [item_num, D] the fused scoring reads (Trainer.compute_item_feature hands it over); what the

@@ -16,7 +16,8 @@ What differs from pooled.py is where the rows live.  One encoder row is read by 
 samples, the target of another -- so the gradient with respect to E is a segment sum over a batch-local row space, and it has to
 come out DENSE ([M, D]: autograd hands it to the native tower) and in a fixed order: pxr_pool_dense_grad_f32, the MODE_POOL sums
 through a third sink.  Row 0 and every row no sample points at get exactly +0.0.  A step: encoder forward -> pooling fused with
-the pair head (one launch) -> the compact block G [3S, D] -> stable sort + segment sum into dE -> encoder backward.  No
+the pair head (one launch) -> the compact block G [3S, D] -> stable sort + segment sum into dE -> encoder backward; E reaches the
+step, and dE autograd, through packed.EncoderRows.  No
 [S (L + 2), D] buffer is written and no float atomic is used.  A target position equal to 0 does not occur in the batcher's
 output (targets are real items); its gradient would be dropped like padding's.
 
@@ -34,16 +35,16 @@ from __future__ import annotations
 import torch
 
 from .. import ops
-from ..lib import PxrError
 from ..utils.enum_type import InputType
 from .basemodel import BaseModel
-from .packed import TrainStep, check_width16, dense_scores, one_process, take_saved
+from .packed import EncoderRows, check_width16, dense_scores, one_process, split_planes, split_tail, store_modal_inputs
 from .pooled import pool_queries
 from .visual import load_model
 
 
-class _MoPooledPair(BaseModel):
-    """What MODSSM and MOFM share: the encoder, the pooled pair step over its output and the evaluation."""
+class _MoPooledPair(EncoderRows, BaseModel):
+    """What MODSSM and MOFM share: the encoder, the pooled pair step over its output (handed over through packed.EncoderRows) and
+    the evaluation.  No flat buffer: the encoder's parameters are all there is."""
 
     input_type = InputType.SEQ
     pool_mean = False                  # MODSSM: masked mean; MOFM: masked sum
@@ -64,26 +65,18 @@ class _MoPooledPair(BaseModel):
             self.load_weights(self.pretrain_weights)
         self.grad_scale = 1.0
         self._bufs = {}
-        self._anchor = None
         self._saved = None
-        self._train_table = None
 
     # ------------------------------------------------------------------------------------------ input forms
     def _split_index(self, index):
-        """-> (profile [S, L], target [S, 2])."""
-        raise NotImplementedError
+        """[S, L + 2] positions = [profile | positive | negative], or (profile [S, L], target [S, 2]) -> contiguous pair, L >= 1."""
+        return split_tail(index, 2, self._pair_text())
 
-    def _check_pair(self, profile, target):
-        if target.dim() != 2 or target.shape[1] != 2 or profile.dim() != 2 or profile.shape[1] < 1 or target.shape[0] != profile.shape[0]:
-            raise ValueError(f"{type(self).__name__}: expected a profile [S, L] (L >= 1) and targets [S, 2] (positive, negative), got "
-                             f"{tuple(profile.shape)} and {tuple(target.shape)}")
-        return profile.contiguous(), target.contiguous()
+    def _pair_text(self):
+        return (f"{type(self).__name__}: expected [S, L + 2] positions (profile, positive, negative) or a profile [S, L] (L >= 1) and "
+                "targets [S, 2], got profile {profile} and target {tail}")
 
-    @staticmethod
-    def modal_inputs(store, data):
-        """The batcher's (index [S, L + 2], image_ids [M]) -> the forward's (index, all_item_modal [M, 3, H, W]): each distinct
-        image of the batch is fetched, and later encoded, once."""
-        return data[0], store.batch(data[1])
+    modal_inputs = staticmethod(store_modal_inputs)
 
     # ------------------------------------------------------------------------------------------ training
     def forward(self, interaction):
@@ -102,25 +95,20 @@ class _MoPooledPair(BaseModel):
     def loss_from_embeddings(self, E, profile_idx, target_idx):
         """The head without the tower: E float32 [M, D] on the HIP device, profile_idx int64 [S, L] and target_idx int64 [S, 2]
         positions into E (0 = no item) -> 0-dim loss; under autograd its backward leaves d loss / d E [M, D] on E."""
-        if E.dim() != 2 or E.dtype != torch.float32 or E.shape[1] != self.embedding_size:
-            raise ValueError(f"{type(self).__name__}: E must be float32 [M, {self.embedding_size}], got {tuple(E.shape)} {E.dtype}")
-        if E.device.type != "cuda":
-            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with .to('cuda') first")
-        profile, target = self._check_pair(profile_idx.to(E.device), target_idx.to(E.device))
-        self._train_table = E.detach().contiguous()
-        if not torch.is_grad_enabled():
-            loss = self._forward_train(profile, target).view(()).clone()
-            self._saved = self._train_table = None
-            return loss
-        if not E.requires_grad:          # fully frozen encoder: still drive the backward of the head
-            if self._anchor is None or self._anchor.device != E.device:
-                self._anchor = torch.zeros((), dtype=torch.float32, device=E.device, requires_grad=True)
-            E = E + self._anchor * 0
-        return TrainStep.apply(E, self, profile, target)
+        self._check_rows(E, self.embedding_size)
+        profile, target = split_tail((profile_idx.to(E.device), target_idx.to(E.device)), 2, self._pair_text())
+        table = E.detach().contiguous()
+        if torch.is_grad_enabled():
+            return self._encoded_step(E, table, profile, target)
+        loss = self._pair_fwd(table, profile, target).view(()).clone()
+        self._saved = None
+        return loss
 
     def _forward_train(self, profile, target):
+        return self._pair_fwd(self._train_table, profile, target)
+
+    def _pair_fwd(self, table, profile, target):
         S, L = profile.shape
-        table = self._train_table
         D, dev = table.shape[1], table.device
         rows = torch.cat((profile.flatten(), target.flatten()))       # history [S L] | targets [2 S]: also the gradient's row list
         U, w, head = self._buf("U", (S, D), dev), self._buf("w", (S,), dev), self._buf("head", (2 * S + 1,), dev)
@@ -130,13 +118,13 @@ class _MoPooledPair(BaseModel):
 
     def _backward_train(self, gsd):
         """-> d loss / d E [M, D] (the bridge's anchor is the encoder's output)."""
-        s, table = take_saved(self, self._train_table), self._train_table
+        s, table = self._take_table()                # (backward() without a forward() raises here)
         S, L = s["S"], s["L"]
         M, D = table.shape
         G = self._buf("G", (3 * S, D), table.device)
         ops.pool_pair_bwd(table, s["rows"], S, L, s["U"], s["coef"], self.grad_scale, gsd, G=G)
         dE = ops.pool_dense_grad(s["rows"], S, L, G, s["w"], M)
-        self._saved = self._train_table = None
+        self._saved = None
         return dE
 
     # ------------------------------------------------------------------------------------------ evaluation
@@ -155,26 +143,12 @@ class _MoPooledPair(BaseModel):
         _, q = self.encode_last(item_seq, feat)
         return dense_scores(q, feat)
 
-    @torch.no_grad()
-    def compute_item(self, item):
-        return self.visual_encoder(item)
-
 
 class MODSSM(_MoPooledPair):
     """modssm.py: masked-mean pooling of encoder rows -> pair head.  index: [S, L + 2] = [profile | positive | negative], or
     (profile [S, L], target [S, 2])."""
 
     pool_mean = True
-
-    def _split_index(self, index):
-        if isinstance(index, (tuple, list)):
-            profile, target = index
-            target = target.reshape(profile.shape[0], -1)
-        else:
-            if index.dim() != 2 or index.shape[1] < 3:
-                raise ValueError(f"MODSSM: expected [S, L + 2] positions (profile, positive, negative), got {tuple(index.shape)}")
-            profile, target = index[:, :-2], index[:, -2:]
-        return self._check_pair(profile, target)
 
 
 class MOFM(_MoPooledPair):
@@ -185,18 +159,6 @@ class MOFM(_MoPooledPair):
     pool_mean = False
 
     def _split_index(self, index):
-        if isinstance(index, (tuple, list)):
-            profile, target = index
-            target = target.reshape(profile.shape[0], -1)
-        elif index.dim() == 2:
-            if index.shape[1] < 3:
-                raise ValueError(f"MOFM: expected [S, L + 2] positions (profile, positive, negative), got {tuple(index.shape)}")
-            profile, target = index[:, :-2], index[:, -2:]
-        else:
-            if index.dim() != 3 or index.shape[1] != 2 or index.shape[2] < 2:
-                raise ValueError(f"MOFM: expected [S, 2, L + 1] positions ([profile | positive], [profile | negative]) or [S, L + 2], got "
-                                 f"{tuple(index.shape)}")
-            if not torch.equal(index[:, 0, :-1], index[:, 1, :-1]):
-                raise ValueError("MOFM: the two planes of the [S, 2, L + 1] input must hold the same profile in their first L columns")
-            profile, target = index[:, 0, :-1], index[:, :, -1]
-        return self._check_pair(profile, target)
+        if isinstance(index, torch.Tensor) and index.dim() >= 3:
+            return split_planes(index, "MOFM", self._pair_text())
+        return super()._split_index(index)

@@ -17,12 +17,12 @@ import torch
 
 from .. import ops
 from ..utils.enum_type import InputType
-from .packed import TrainStep
+from .packed import EncoderRows, dense_gemm
 from .seqcore import SeqRecCore
 from .visual import load_model
 
 
-class MOSASRec(SeqRecCore):
+class MOSASRec(EncoderRows, SeqRecCore):
     input_type = InputType.SEQ
 
     def __init__(self, config, dataload):
@@ -59,12 +59,9 @@ class MOSASRec(SeqRecCore):
         item_emb = self.visual_encoder(items.flatten(0, 1)).view(B, -1, 2, self.embedding_size)   # mosasrec.py:69
         idx = self._row_ids(B, item_emb.device)
         masked_index = masked_index.contiguous()
-        if torch.is_grad_enabled() and self.training:
-            if not item_emb.requires_grad:   # fully frozen encoder: still drive the backward of the sequence block
-                item_emb = item_emb + self._anchor * 0
-            self._train_table = item_emb.detach().reshape(-1, self.embedding_size).contiguous()
-            return TrainStep.apply(item_emb, self, idx, masked_index)
         table = item_emb.detach().reshape(-1, self.embedding_size).contiguous()
+        if torch.is_grad_enabled() and self.training:
+            return self._encoded_step(item_emb, table, idx, masked_index)
         return self._forward_core(table, idx, masked_index, train=False).view(())
 
     def _forward_train(self, idx, masked_index):
@@ -72,7 +69,7 @@ class MOSASRec(SeqRecCore):
 
     def _backward_train(self, gsd):
         """-> the gradient of the encoder's output [B, L+1, 2, D] (the bridge's anchor)."""
-        table, self._train_table = self._train_table, None
+        _, table = self._take_table()                # (backward() without a forward() raises here)
         dx0, coef, s = self._backward_core(gsd, table)
         return ops.mosasrec_emb_grad(dx0, s["out"], coef)
 
@@ -90,11 +87,4 @@ class MOSASRec(SeqRecCore):
         """scores [B, N] from a precomputed item_feature table (mosasrec.py:95-114)."""
         out, last = self.encode_last(item_seq, item_feature)
         B, L, D = out.shape
-        N = item_feature.shape[0]
-        scores = torch.empty(B, N, dtype=torch.float32, device=out.device)
-        ops.gemm(True, True, B, N, D, last, L * D, item_feature.contiguous(), D, scores, N, ops.EPI_NONE, use_ws=False)
-        return scores
-
-    @torch.no_grad()
-    def compute_item(self, item):
-        return self.visual_encoder(item)                                              # mosasrec.py:117-119
+        return dense_gemm(last, item_feature.contiguous(), ldq=L * D)

@@ -6,8 +6,8 @@ E = visual_encoder(images) [M, D] and idx [B, L + 2] = [item_seq (right-padded) 
     readout with mask = idx[:, :L] != 0;  out = linear_transform([a | ht])
     loss = -mean(1e-8 + log sigmoid(<out, E[p]> - <out, E[n]>))                                   (mosrgnn.py:64-74)
 
-The step between the graph and the node gradients is SRGNN's code (srgnn.SrgnnStep), launch for launch; the shell that hands E to
-it (`_train_table`, the autograd bridge anchored at E) is MOBERT4Rec's.  What closes it is the gradient of E: one encoder row is
+The step between the graph and the node gradients is SRGNN's code (srgnn.SrgnnStep), launch for launch; E reaches it through
+packed.EncoderRows (`_train_table`, the autograd bridge anchored at E).  What closes it is the gradient of E: one encoder row is
 read by many nodes and targets, so it is a segment sum over a batch-local row space that comes out DENSE ([M, D]: autograd hands
 it to the native tower) and in a fixed order -- pxr_seq_occ_dense_f32 over the id rows [B, 3L] = nodes | target | negative that the
 graph build writes, the sums of SRGNN's sparse table gradient through the dense sink.  No float atomic is used.
@@ -36,14 +36,13 @@ import math
 import torch
 
 from .. import ops
-from ..lib import PxrError
 from ..utils.enum_type import InputType
-from .packed import PackedModel, TrainStep, dense_scores, one_process, split_tail, take_saved
+from .packed import EncoderRows, PackedModel, dense_scores, one_process, split_tail, store_modal_inputs
 from .srgnn import SrgnnStep
 from .visual import load_model
 
 
-class MOSRGNN(SrgnnStep, PackedModel):
+class MOSRGNN(EncoderRows, SrgnnStep, PackedModel):
     input_type = InputType.AUGSEQ
 
     def __init__(self, config, dataload):
@@ -61,7 +60,6 @@ class MOSRGNN(SrgnnStep, PackedModel):
             lin.weight.data.uniform_(-stdv, stdv)
         for w in self.visual_encoder.rec_fc.parameters():
             w.data.uniform_(-stdv, stdv)
-        self._train_table = None
 
     def rec_parameter_names(self):
         """{reference parameter name: flat-buffer key} in the reference's registration order (optim.native_to_torch_state):
@@ -82,11 +80,7 @@ class MOSRGNN(SrgnnStep, PackedModel):
             raise ValueError(f"MOSRGNN: item_seq must be [B, {L}], got {tuple(seq.shape)}")
         return seq, target
 
-    @staticmethod
-    def modal_inputs(store, data):
-        """The batcher's (index [B, L + 2], image_ids [M]) -> the forward's (index, images [M, 3, H, W]): each distinct image of
-        the batch is fetched, and later encoded, once."""
-        return data[0], store.batch(data[1])
+    modal_inputs = staticmethod(store_modal_inputs)
 
     def _reference_form(self, alias_inputs, A, mask, items_all):
         """mosrgnn.py:64-70's input -> (graph dict at L nodes, mask, target [B, 2], images): a zero image goes in front, node slot
@@ -128,30 +122,21 @@ class MOSRGNN(SrgnnStep, PackedModel):
         item_idx, target_idx = self._split_index(index)
         return self.loss_from_embeddings(self.visual_encoder(images), item_idx, target_idx)
 
-    def _check_rows(self, E):
-        if E.dim() != 2 or E.dtype != torch.float32 or E.shape[1] != self.hidden_size:
-            raise ValueError(f"MOSRGNN: E must be float32 [M, {self.hidden_size}], got {tuple(E.shape)} {E.dtype}")
-        if E.device.type != "cuda":
-            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with .to('cuda') first")
-
     def loss_from_embeddings(self, E, item_idx, target_idx):
         """The head without the tower: E float32 [M, D] on the HIP device, item_idx int64 [B, L] (right-padded) and target_idx
         int64 [B, 2] positions into E (0 = no item) -> 0-dim loss; under autograd its backward leaves d loss / d E [M, D] on E and
         the 17 gradients of the block in the flat gradient buffer.  A position outside [0, M) flags the status word."""
-        self._check_rows(E)
+        self._check_rows(E, self.hidden_size)
         self._ensure_packed()
         item_idx, target_idx = self._split_index((item_idx.to(E.device), target_idx.to(E.device)))
         g = ops.srgnn_graph(item_idx, E.shape[0], target_idx, want_occ=True, want_mask=True, out=self._gbufs)
         return self._loss_from_graph(E, g, g["mask"], target_idx)
 
     def _loss_from_graph(self, E, g, mask, target):
-        self._check_rows(E)
+        self._check_rows(E, self.hidden_size)
         table = E.detach().contiguous()
         if torch.is_grad_enabled() and self.training:
-            if not E.requires_grad:      # fully frozen encoder (or a plain tensor): still drive the backward of the block
-                E = E + self._anchor * 0
-            self._train_table = table
-            return TrainStep.apply(E, self, g, mask, target)
+            return self._encoded_step(E, table, g, mask, target)
         was = self.training
         try:
             self.training = False        # (nothing is saved for a backward)
@@ -164,8 +149,7 @@ class MOSRGNN(SrgnnStep, PackedModel):
 
     def _backward_train(self, gsd):
         """-> d loss / d E [M, D] (the bridge's anchor is the encoder's output)."""
-        s = take_saved(self, self._train_table)      # (backward() without a forward() raises here)
-        table, self._train_table = self._train_table, None
+        s, table = self._take_table()                # (backward() without a forward() raises here)
         B, L, D = s["B"], self.max_seq_length, self.hidden_size
         dH, coef_pad = self._step_backward(gsd, table, s)
         # the gradient of E: stable sort of the 3 B L occurrences + segmented sum into a dense block (position 0: dropped)
@@ -175,15 +159,11 @@ class MOSRGNN(SrgnnStep, PackedModel):
 
     # ------------------------------------------------------------------------------------------ evaluation
     @torch.no_grad()
-    def compute_item(self, item):
-        return self.visual_encoder(item)                                              # mosrgnn.py:85-88
-
-    @torch.no_grad()
     def encode_last(self, item_seq, item_feature):
         """item_seq int64 [B, L] (right-padded; mask = item_seq != 0), item_feature [N, D] -> (out [B, 1, D], out [B, D]): the
         query vectors of the fused scoring, H_0 = item_feature[nodes] (mosrgnn.py:80)."""
         self._ensure_packed()
-        self._check_rows(item_feature)
+        self._check_rows(item_feature, self.hidden_size)
         out = self._encode(item_seq, item_feature.contiguous())
         return out.view(out.shape[0], 1, -1), out
 

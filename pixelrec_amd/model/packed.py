@@ -2,7 +2,8 @@
 
   * `_Rows`, the parameter container with nn.Embedding's `weight` name;
   * `_ActMLP`, the reference's MLPLayers parameter layout, and `linear_specs` / `linear_names` over a model's `_linears()`;
-  * `TrainStep`, the one autograd bridge from `loss.backward()` to a model's `_backward_train`;
+  * `TrainStep`, the one autograd bridge from `loss.backward()` to a model's `_backward_train`, and `EncoderRows`, what the pixel
+    models put between the visual encoder's output and it (`store_modal_inputs` is their batcher-to-forward input form);
   * `split_tail` / `split_planes` (the two input forms of the pair models), `dense_gemm` / `dense_scores` (the predict tail), `take_saved` and the
     constructor checks `one_process`, `check_width16`, `hidden_sizes`;
   * `flat_layout` (pure) and `pack_flat`: the layout of the flat parameter buffer and the allocate / copy / re-point loop;
@@ -13,7 +14,8 @@
 
 None of these registers a parameter, a buffer or a submodule, and none defines a member the surrounding code probes for by
 attribute (`table_parameter_spans`, `rec_parameter_names`, `running_state_buffers`, `split_flat_table_groups`,
-`item_table_attr`): a model has those exactly when it writes them itself.
+`item_table_attr`, `modal_inputs`, `set_item_feature`, `scoring_item_matrix`, `extra_item_images`): a model has those exactly
+when it writes them itself.
 """
 from __future__ import annotations
 
@@ -94,6 +96,8 @@ def split_tail(input, n_tail, text, max_len=math.inf):
         profile, tail = input
         tail = tail.reshape(profile.shape[0], -1)
     else:
+        if input.dim() < 2:
+            raise ValueError(text.format(profile=tuple(input.shape), tail=()))
         profile, tail = input[:, :-n_tail], input[:, -n_tail:]
     return _split_checked(profile, tail, n_tail, 1, max_len, text)
 
@@ -114,19 +118,20 @@ def split_planes(input, name, pair_text, min_len=1):
     return _split_checked(profile, target, 2, min_len, math.inf, pair_text)
 
 
-def dense_gemm(q, feat):
-    """scores [B, N] = q feat^T in the library GEMM."""
+def dense_gemm(q, feat, ldq=None):
+    """scores [B, N] = q feat^T in the library GEMM.  `ldq` is the row stride of q in elements (default: its width) -- the last
+    position of a [B, L, D] block of states is a [B, D] view with stride L D."""
     B, D = q.shape
     N = feat.shape[0]
     scores = torch.empty(B, N, dtype=torch.float32, device=q.device)
-    ops.gemm(True, True, B, N, D, q, D, feat, D, scores, N, ops.EPI_NONE, use_ws=False)
+    ops.gemm(True, True, B, N, D, q, D if ldq is None else ldq, feat, D, scores, N, ops.EPI_NONE, use_ws=False)
     return scores
 
 
-def dense_scores(q, feat):
+def dense_scores(q, feat, ldq=None):
     """The tail of `predict`: scores [B, N] = q feat^T, then the bad-index flag -- an id outside the catalogue raises, like the
     reference's indexing."""
-    scores = dense_gemm(q, feat)
+    scores = dense_gemm(q, feat, ldq)
     ops.raise_on_bad_indices(q.device)
     return scores
 
@@ -152,6 +157,47 @@ class TrainStep(torch.autograd.Function):
     def backward(ctx, grad_out):
         gsd = grad_out.reshape(1).to(torch.float32).contiguous()
         return (ctx.model._backward_train(gsd),) + (None,) * (1 + ctx.n_inputs)
+
+
+def store_modal_inputs(store, data):
+    """The batcher's (index, image_ids [M]) -> the forward's (index, images [M, 3, H, W]): each distinct image of the batch is
+    fetched, and later encoded, once.  A pixel model takes it with `modal_inputs = staticmethod(store_modal_inputs)`."""
+    return data[0], store.batch(data[1])
+
+
+class EncoderRows:
+    """Mixin of the models trained from pixels: what lies between the visual encoder's output E [M, D] and the native step.  The
+    training branch of a model is `_encoded_step(E, E.detach().contiguous(), *inputs)`; its `_forward_train(*inputs)` reads
+    `self._train_table`; its `_backward_train(gsd)` opens with `_take_table()` and returns d loss / d E, which TrainStep hands to
+    autograd as the gradient of E.  Which calls take the training branch, and what the other branch does, is the model's own."""
+
+    _train_table = None     # E, detached, between a training forward and its backward
+
+    def _check_rows(self, E, width):
+        if E.dim() != 2 or E.dtype != torch.float32 or E.shape[1] != width:
+            raise ValueError(f"{type(self).__name__}: E must be float32 [M, {width}], got {tuple(E.shape)} {E.dtype}")
+        if E.device.type != "cuda":
+            raise PxrError("pixelrec_amd models run on a HIP device only (no CPU fallback); move the model with .to('cuda') first")
+
+    def _encoded_step(self, E, table, *inputs):
+        """-> 0-dim loss of `_forward_train(*inputs)` over `table`, with `_backward_train`'s return as the gradient of E."""
+        if not E.requires_grad:      # fully frozen encoder (or a plain tensor): still drive the backward of the step
+            anchor = getattr(self, "_anchor", None)
+            if anchor is None or anchor.device != E.device:
+                anchor = self._anchor = torch.zeros((), dtype=torch.float32, device=E.device, requires_grad=True)
+            E = E + anchor * 0
+        self._train_table = table
+        return TrainStep.apply(E, self, *inputs)
+
+    def _take_table(self, *also):
+        """-> (what the training forward left in `_saved`, its table); a backward() without a forward() raises here."""
+        saved = take_saved(self, self._train_table, *also)
+        table, self._train_table = self._train_table, None
+        return saved, table
+
+    @torch.no_grad()
+    def compute_item(self, item):
+        return self.visual_encoder(item)
 
 
 def flat_layout(specs, align=1):

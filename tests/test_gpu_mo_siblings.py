@@ -10,6 +10,7 @@ import torch
 from oracle import gru4rec_oracle as GO
 from oracle import mosasrec_oracle as MO
 from oracle import nextitnet_oracle as NO
+from tests.mo_common import tower_config
 
 pytestmark = pytest.mark.gpu
 
@@ -18,11 +19,7 @@ TUNE = 5 + 16 * 2            # tiny tower: train block 2 + rec_fc
 
 
 def _config(extra):
-    cfg = {"embedding_size": D, "initializer_range": 0.02, "MAX_ITEM_LIST_LENGTH": L, "seed": 2020,
-           "encoder_name": "clip-vit-tiny-test", "encoder_source": "transformers", "pretrain_path": None,
-           "fine_tune_arg": {"tune_scale": TUNE, "pre_trained": True, "activation": "relu", "dnn_layers": [], "method": "mean"}}
-    cfg.update(extra)
-    return cfg
+    return tower_config(TUNE, embedding_size=D, initializer_range=0.02, MAX_ITEM_LIST_LENGTH=L, **extra)
 
 
 CASES = {

@@ -5,9 +5,6 @@ position; bit identity with BERT4Rec's launches; the model against the fixture o
 forms (loss, all 53 gradients, compute_item with the mask row, predict, the generic fused top-k); dropout; the optimizer's two
 groups; main.py end to end.  Every test here needs the new entry, the new op or the new class, so each fails without the feature."""
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,27 +13,17 @@ import torch
 from pixelrec_amd import ops
 from tests import mobert4rec_restate as R
 from tests.test_gpu_bert4rec import MODES, mode  # noqa: F401  (the GEMM-mode fixture of the ID model's tests)
-from tests.test_mobert4rec_cpu import FOUR, GOLD, N_BLOCK, ROOT, _config, _trainer_optimizer, build_from_fixture, my_name, restate_cfg
+from tests.mo_common import (GOLD, assert_optimizer_state_round_trips, assert_two_fresh_models_agree, bits as _bits, my_name, run_main_py,
+                              sort_constants as _sort_constants)
+from tests.test_mobert4rec_cpu import N_BLOCK, _config, build_from_fixture
 
 pytestmark = pytest.mark.gpu
 U32 = 2.0 ** -24
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
 # ------------------------------------------------------------------------------------------------------------ 1. the dense sink
 def _layouts(L):
     return {"bert4rec": (3 * L, 0, L, 2 * L), "sasrec": (2 * (L + 1), 0, 1, L + 2), "lightsans": (L + 2, 0, 1, 2)}
-
-
-def _sort_constants():
-    src = open(os.path.join(ROOT, "pixelrec_amd", "csrc", "embed_grad.hip")).read()
-    val = lambda k: int(re.search(r"constexpr int %s = (\d+);" % k, src).group(1))
-    mult = int(re.search(r"constexpr int FP_MAX_N = (\d+) \* RS_TILE;", src).group(1))
-    assert "enabled && n <= FP_MAX_N" in src                       # use_fused_sort's cut-over
-    return mult * val("RS_THREADS") * val("RS_ITEMS"), val("SEG_SHORT"), val("SEG_CHUNK")
 
 
 def _occ_case(B, L, D, n_rows, layout, seed, p_zero=0.15, p_mask=0.0):
@@ -487,18 +474,8 @@ def test_model_matches_the_reference_fixture(gold, form):
 
 def test_two_fresh_models_give_the_same_bits(gold):
     store = R.golden_store(gold).cuda()
-    runs = []
-    for _ in range(2):
-        m = build_from_fixture(gold).cuda().train()
-        out = []
-        for j in range(2):
-            loss, grads = _step(m, gold, j, store, "positions")
-            out += [loss] + [grads[k] for k in sorted(grads)]
-        runs.append(out)
-    n = 1 + N_BLOCK + 18
-    assert len(runs[0]) == len(runs[1]) == 2 * n and float(runs[0][0]) != float(runs[0][n])
-    for x, y in zip(*runs):
-        assert torch.equal(_bits(x), _bits(y))
+    assert_two_fresh_models_agree(lambda: build_from_fixture(gold).cuda().train(), lambda m, j: _step(m, gold, j, store, "positions"),
+                                  1 + N_BLOCK + 18)
 
 
 # ------------------------------------------------------------------------------------------------------------ 10. dropout
@@ -526,80 +503,28 @@ def test_dropout_runs_reproducibly_and_draws_fresh_masks(gold):
 def test_optimizer_steps_both_groups_and_its_state_round_trips(gold):
     """Four optim_args: the encoder group and a rec group without a table, [18, 35] parameters; one step moves both; the torch-layout
     state loads into torch.optim.AdamW over the reference's two groups and back."""
-    from pixelrec_amd.optim import OptimizerGroup
-
-    m = build_from_fixture(gold).cuda().train()
-    opt = _trainer_optimizer(m, FOUR)
-    assert isinstance(opt, OptimizerGroup)
     store = R.golden_store(gold).cuda()
-    before = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    opt.zero_grad()
-    _step(m, gold, 0, store, "positions")
-    opt.step()
-    after = m.state_dict()
-    trainable = {n for n, p in m.named_parameters() if p.requires_grad}
-    moved = {k for k in before if not torch.equal(before[k], after[k])}
     blk = R.names(2)
-    # (a key projection's bias has a zero gradient by the softmax's shift invariance: it may stay where it is)
-    assert moved <= trainable and {k for k in blk if ".key.bias" not in k} <= moved and any("visual_encoder" in k for k in moved)
-    n_all = 18 + N_BLOCK
-    sd = opt.state_dict(layout="torch")
-    assert [len(x["params"]) for x in sd["param_groups"]] == [18, N_BLOCK] and sorted(sd["state"]) == list(range(n_all))
-    assert [(x["lr"], x["weight_decay"]) for x in sd["param_groups"]] == [(1e-4, 0.0), (3e-4, 0.1)]
-    enc = [p for n, p in m.named_parameters() if "visual_encoder" in n and p.requires_grad]
-    rec = [m.get_parameter(k) for k in blk]                         # the reference's registration order
-    assert [tuple(sd["state"][18 + i]["exp_avg"].shape) for i in range(N_BLOCK)] == [tuple(p.shape) for p in rec]
-    tor = torch.optim.AdamW([{"params": enc, "lr": 1.0, "weight_decay": 0.5}, {"params": rec, "lr": 2.0, "weight_decay": 0.25}])
-    tor.load_state_dict(sd)                                         # the layout the reference stores
-    assert [(x["lr"], x["weight_decay"]) for x in tor.param_groups] == [(1e-4, 0.0), (3e-4, 0.1)]
-    opt2 = _trainer_optimizer(build_from_fixture(gold).cuda().train(), {**FOUR, "modal_lr": 5.0, "rec_lr": 7.0})
-    opt2.load_state_dict(tor.state_dict())
-    sd2 = opt2.state_dict(layout="torch")
-    assert [x["params"] for x in sd2["param_groups"]] == [x["params"] for x in sd["param_groups"]]
-    assert [(x["lr"], x["weight_decay"]) for x in sd2["param_groups"]] == [(1e-4, 0.0), (3e-4, 0.1)]
-    for i in range(n_all):
-        for key in ("exp_avg", "exp_avg_sq"):
-            assert torch.equal(sd2["state"][i][key].cpu(), sd["state"][i][key].cpu()), (i, key)
+
+    def moved(moved, trainable):
+        # (a key projection's bias has a zero gradient by the softmax's shift invariance: it may stay where it is)
+        assert moved <= trainable and {k for k in blk if ".key.bias" not in k} <= moved and any("visual_encoder" in k for k in moved)
+
+    assert_optimizer_state_round_trips(lambda: build_from_fixture(gold).cuda().train(), lambda m: _step(m, gold, 0, store, "positions"),
+                                       [18, N_BLOCK], list(range(18 + N_BLOCK)), moved=moved,
+                                       rec=lambda m: [m.get_parameter(k) for k in blk])     # the reference's registration order
 
 
 def test_main_py_trains_evaluates_and_the_checkpoint_reloads(tmp_path):
     """main.py on TinyInter with synthetic 64 x 64 images and the tiny tower, two epochs at mask_ratio 0.6, through the fused
     evaluation: finite losses that change, Recall@10 and NDCG@10 reported from the reloaded checkpoint, whose state_dict loads with
     strict=True."""
-    from pixelrec_amd.config import Config
-    from pixelrec_amd.data import load_data
     from pixelrec_amd.utils import get_model
 
-    my, ov = tmp_path / "m.yaml", tmp_path / "o.yaml"
-    my.write_text("model: MOBERT4Rec\nembedding_size: 32\nn_layers: 2\nn_heads: 2\ninner_size: 2\nhidden_dropout_prob: 0.1\n"
+    _, _, ck, config, data = run_main_py(
+        tmp_path, "model: MOBERT4Rec\nembedding_size: 32\nn_layers: 2\nn_heads: 2\ninner_size: 2\nhidden_dropout_prob: 0.1\n"
                   "attn_dropout_prob: 0.1\nhidden_act: 'gelu'\nlayer_norm_eps: 1e-12\ninitializer_range: 0.02\nmask_ratio: 0.6\n")
-    ov.write_text(f"seed: 2020\nstate: INFO\nuse_modality: True\nreproducibility: True\ncheckpoint_dir: '{tmp_path}/saved'\n"
-                  f"log_path: '{tmp_path}/log'\nshow_progress: False\nMAX_ITEM_LIST_LENGTH: 6\ndata_path: {GOLD}/\n"
-                  "dataset: TinyInter\nimage_path: 'synthetic:64'\nencoder_name: 'clip-vit-tiny-test'\n"
-                  "encoder_source: 'transformers'\nepochs: 2\ntrain_batch_size: 8\n"
-                  "fine_tune_arg: {tune_scale: 37, pre_trained: True, activation: 'relu', dnn_layers: [], method: 'mean'}\n"
-                  "optim_args: {modal_lr: 0.001, rec_lr: 0.001, modal_decay: 0, rec_decay: 0.1}\n"
-                  "eval_batch_size: 16\ntopk: [5,10]\nmetrics: ['Recall', 'NDCG']\nvalid_metric: NDCG@10\n"
-                  "metric_decimal_place: 7\neval_step: 1\nstopping_step: 30\n")
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "OMP_NUM_THREADS")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--device", "0", "--config_file", str(my), str(ov)],
-                       cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-3000:]
-    epochs = [float(x) for x in re.findall(r"epoch \d+ training \[time: [0-9.]+s, train loss: ([0-9.]+)\]", out)]
-    assert len(epochs) == 2 and all(np.isfinite(e) for e in epochs) and epochs[0] != epochs[1], out[-3000:]
-    assert "Loading model structure and parameters from" in out, out[-3000:]
-    for metric in ("recall@10", "ndcg@10"):
-        mm = re.search(r"test result: .*?'%s', ([0-9.]+)\)" % metric, out)
-        assert mm is not None and 0.0 <= float(mm.group(1)) <= 1.0, out[-2000:]
-    print("epoch losses", epochs, re.search(r"test result: .*", out).group(0))
-    files = os.listdir(tmp_path / "saved")
-    assert len(files) == 1
-    ck = torch.load(tmp_path / "saved" / files[0], map_location="cpu", weights_only=False)
     assert list(ck["state_dict"])[-N_BLOCK:] == R.names(2)
     assert [len(x["params"]) for x in ck["optimizer"]["param_groups"]] == [18, N_BLOCK]    # the reference's two groups
-    config = Config([str(my), str(ov)])
-    data = load_data(config)
-    data.build()
     fresh = get_model("MOBERT4Rec")(config, data)
     fresh.load_state_dict(ck["state_dict"], strict=True)

@@ -5,9 +5,6 @@ fixture of the reference's own MODIN in both input forms (loss, all 24 gradients
 top-k against DIN's, bad positions, the optimizer's two groups, and main.py end to end.  Every test here needs the new entries, the
 new op or the new class, so each fails without the feature."""
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,16 +14,14 @@ from pixelrec_amd import lib as _l
 from pixelrec_amd import ops
 from tests import din_restate as DR
 from tests import modin_restate as R
-from tests.test_modin_cpu import FOUR, GOLD, ROOT, _config, _trainer_optimizer, build_from_fixture, my_name
+from tests.mo_common import (GOLD, assert_optimizer_state_round_trips, assert_two_fresh_models_agree, bits as _bits, my_name, run_main_py,
+                              sort_constants as _sort_constants)
+from tests.test_modin_cpu import _config, build_from_fixture
 
 pytestmark = pytest.mark.gpu
 U32 = 2.0 ** -24
 FUSED_MEASURED = 2.284e-6          # tests/test_gpu_din.py: the reference's own float32 predict against float64, relative
 FUSED_TOL = 4 * FUSED_MEASURED     # ... and what the fused kernel is allowed there
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 # ------------------------------------------------------------------------------------------------------------ 1. the dense sink
@@ -93,14 +88,6 @@ def test_dense_sink_equals_the_sparse_sink_scattered(n, D, n_rows):
         d2 = _check_dense(idx2, rows, n_rows)
         same = torch.tensor([r not in touched for r in range(n_rows)], device="cuda")
         assert torch.equal(_bits(d2[same]), _bits(d[same]))
-
-
-def _sort_constants():
-    src = open(os.path.join(ROOT, "pixelrec_amd", "csrc", "embed_grad.hip")).read()
-    val = lambda k: int(re.search(r"constexpr int %s = (\d+);" % k, src).group(1))
-    mult = int(re.search(r"constexpr int FP_MAX_N = (\d+) \* RS_TILE;", src).group(1))
-    assert "enabled && n <= FP_MAX_N" in src                       # use_fused_sort's cut-over
-    return mult * val("RS_THREADS") * val("RS_ITEMS"), val("SEG_SHORT"), val("SEG_CHUNK")
 
 
 def test_dense_sink_above_the_fused_sort_cut_over():
@@ -437,17 +424,7 @@ def test_model_matches_the_reference_fixture(gold, form):
 
 def test_two_fresh_models_give_the_same_bits(gold):
     store = torch.from_numpy(gold["store"].astype(np.float32)).cuda()
-    runs = []
-    for _ in range(2):
-        m = build_from_fixture(gold).cuda().train()
-        out = []
-        for j in range(2):
-            loss, grads = _step(m, gold, j, store, "positions")
-            out += [loss] + [grads[k] for k in sorted(grads)]
-        runs.append(out)
-    assert len(runs[0]) == len(runs[1]) == 2 * 25 and float(runs[0][0]) != float(runs[0][25])
-    for x, y in zip(*runs):
-        assert torch.equal(_bits(x), _bits(y))
+    assert_two_fresh_models_agree(lambda: build_from_fixture(gold).cuda().train(), lambda m, j: _step(m, gold, j, store, "positions"), 25)
 
 
 # ------------------------------------------------------------------------------------------------------------ 7. the fused top-k
@@ -497,75 +474,23 @@ def test_fused_topk_is_dins():
 def test_optimizer_steps_both_groups_and_its_state_round_trips(gold):
     """Four optim_args: the encoder group and a rec group without a table, [18, 6] parameters; one step moves both; the torch-layout
     state loads into torch.optim.AdamW over the reference's two groups and back."""
-    from pixelrec_amd.optim import OptimizerGroup
-
-    m = build_from_fixture(gold).cuda().train()
-    opt = _trainer_optimizer(m, FOUR)
-    assert isinstance(opt, OptimizerGroup)
     store = torch.from_numpy(gold["store"].astype(np.float32)).cuda()
-    before = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    opt.zero_grad()
-    _step(m, gold, 0, store, "positions")
-    opt.step()
-    after = m.state_dict()
-    trainable = {n for n, p in m.named_parameters() if p.requires_grad}
-    moved = {k for k in before if not torch.equal(before[k], after[k])}
-    # (a key projection's bias has a zero gradient by the softmax's shift invariance: it may stay where it is)
-    assert moved <= trainable and len(moved) >= 21 and set(R.names(2)) <= moved and any("visual_encoder" in k for k in moved)
-    sd = opt.state_dict(layout="torch")
-    assert [len(x["params"]) for x in sd["param_groups"]] == [18, 6] and sorted(sd["state"]) == list(range(24))
-    assert [(x["lr"], x["weight_decay"]) for x in sd["param_groups"]] == [(1e-4, 0.0), (3e-4, 0.1)]
-    enc = [p for n, p in m.named_parameters() if "visual_encoder" in n and p.requires_grad]
-    rec = [p for n, p in m.named_parameters() if "visual_encoder" not in n]
-    tor = torch.optim.AdamW([{"params": enc, "lr": 1.0, "weight_decay": 0.5}, {"params": rec, "lr": 2.0, "weight_decay": 0.25}])
-    tor.load_state_dict(sd)                                         # the layout the reference stores
-    assert [(x["lr"], x["weight_decay"]) for x in tor.param_groups] == [(1e-4, 0.0), (3e-4, 0.1)]
-    opt2 = _trainer_optimizer(build_from_fixture(gold).cuda().train(), {**FOUR, "modal_lr": 5.0, "rec_lr": 7.0})
-    opt2.load_state_dict(tor.state_dict())
-    sd2 = opt2.state_dict(layout="torch")
-    assert [x["params"] for x in sd2["param_groups"]] == [x["params"] for x in sd["param_groups"]]
-    assert [(x["lr"], x["weight_decay"]) for x in sd2["param_groups"]] == [(1e-4, 0.0), (3e-4, 0.1)]
-    for i in range(24):
-        for key in ("exp_avg", "exp_avg_sq"):
-            assert torch.equal(sd2["state"][i][key].cpu(), sd["state"][i][key].cpu()), (i, key)
+
+    def moved(moved, trainable):
+        # (a key projection's bias has a zero gradient by the softmax's shift invariance: it may stay where it is)
+        assert moved <= trainable and len(moved) >= 21 and set(R.names(2)) <= moved and any("visual_encoder" in k for k in moved)
+
+    assert_optimizer_state_round_trips(lambda: build_from_fixture(gold).cuda().train(), lambda m: _step(m, gold, 0, store, "positions"),
+                                       [18, 6], list(range(24)), moved=moved)
 
 
 def test_main_py_trains_evaluates_and_the_checkpoint_reloads(tmp_path):
     """main.py on TinyInter with synthetic 64 x 64 images and the tiny tower, two epochs, through the fused evaluation: finite losses
     that change, Recall@10 and NDCG@10 reported from the reloaded checkpoint, whose state_dict loads with strict=True."""
-    from pixelrec_amd.config import Config
-    from pixelrec_amd.data import load_data
     from pixelrec_amd.utils import get_model
 
-    my, ov = tmp_path / "m.yaml", tmp_path / "o.yaml"
-    my.write_text("model: MODIN\nembedding_size: 32\ndropout_prob: 0\nmlp_hidden_size: [16, 8]\n")
-    ov.write_text(f"seed: 2020\nstate: INFO\nuse_modality: True\nreproducibility: True\ncheckpoint_dir: '{tmp_path}/saved'\n"
-                  f"log_path: '{tmp_path}/log'\nshow_progress: False\nMAX_ITEM_LIST_LENGTH: 6\ndata_path: {GOLD}/\n"
-                  "dataset: TinyInter\nimage_path: 'synthetic:64'\nencoder_name: 'clip-vit-tiny-test'\n"
-                  "encoder_source: 'transformers'\nepochs: 2\ntrain_batch_size: 8\n"
-                  "fine_tune_arg: {tune_scale: 37, pre_trained: True, activation: 'relu', dnn_layers: [], method: 'mean'}\n"
-                  "optim_args: {modal_lr: 0.001, rec_lr: 0.001, modal_decay: 0, rec_decay: 0.1}\n"
-                  "eval_batch_size: 16\ntopk: [5,10]\nmetrics: ['Recall', 'NDCG']\nvalid_metric: NDCG@10\n"
-                  "metric_decimal_place: 7\neval_step: 1\nstopping_step: 30\n")
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "OMP_NUM_THREADS")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--device", "0", "--config_file", str(my), str(ov)],
-                       cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-3000:]
-    epochs = [float(x) for x in re.findall(r"epoch \d+ training \[time: [0-9.]+s, train loss: ([0-9.]+)\]", out)]
-    assert len(epochs) == 2 and all(np.isfinite(e) for e in epochs) and epochs[0] != epochs[1], out[-3000:]
-    assert "Loading model structure and parameters from" in out, out[-3000:]
-    for metric in ("recall@10", "ndcg@10"):
-        mm = re.search(r"test result: .*?'%s', ([0-9.]+)\)" % metric, out)
-        assert mm is not None and 0.0 <= float(mm.group(1)) <= 1.0, out[-2000:]
-    print("epoch losses", epochs, re.search(r"test result: .*", out).group(0))
-    files = os.listdir(tmp_path / "saved")
-    assert len(files) == 1
-    ck = torch.load(tmp_path / "saved" / files[0], map_location="cpu", weights_only=False)
+    _, _, ck, config, data = run_main_py(tmp_path, "model: MODIN\nembedding_size: 32\ndropout_prob: 0\nmlp_hidden_size: [16, 8]\n")
     assert list(ck["state_dict"])[:6] == R.names(2)
     assert [len(x["params"]) for x in ck["optimizer"]["param_groups"]] == [18, 6]         # the reference's two groups
-    config = Config([str(my), str(ov)])
-    data = load_data(config)
-    data.build()
     fresh = get_model("MODIN")(config, data)
     fresh.load_state_dict(ck["state_dict"], strict=True)

@@ -4,9 +4,6 @@ reference's own MODSSM and MOFM (loss, every trainable encoder gradient, compute
 identity, bad ids, and main.py end to end.  Every test here needs the new kernel entry or the new models, so each fails without the
 feature."""
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,7 +11,8 @@ import torch
 
 from pixelrec_amd import ops
 from tests import pool_restate as R
-from tests.test_mopool_cpu import CASES, GOLD, PFX, ROOT, _config, build_from_fixture
+from tests.mo_common import GOLD, assert_two_fresh_models_agree, bits as _bits, my_name, run_main_py, sort_constants as _sort_constants
+from tests.test_mopool_cpu import CASES, _config, build_from_fixture
 
 pytestmark = pytest.mark.gpu
 U32 = 2.0 ** -24
@@ -44,10 +42,6 @@ def _edge_index(B, L, n_rows, seed):
 def _weights(prof, mean):
     cnt = (prof != 0).sum(1).float()
     return torch.where(cnt > 0, 1.0 / (cnt + 1e-8), torch.zeros(())) if mean else (cnt > 0).float()
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 def _check_dense(prof, tgt, G, w, n_rows):
@@ -104,14 +98,6 @@ def test_dense_sink_equals_the_sparse_sink_scattered(B, L, D, n_rows, mean):
         prof2[0, 1], tgt2[2, 1] = n_rows, -3
         d2 = _check_dense(prof2, tgt2, G, _weights(prof2, mean), n_rows)
         assert d2.shape == d.shape and keep_row >= 1
-
-
-def _sort_constants():
-    src = open(os.path.join(ROOT, "pixelrec_amd", "csrc", "embed_grad.hip")).read()
-    val = lambda k: int(re.search(r"constexpr int %s = (\d+);" % k, src).group(1))
-    mult = int(re.search(r"constexpr int FP_MAX_N = (\d+) \* RS_TILE;", src).group(1))
-    assert "enabled && n <= FP_MAX_N" in src                       # use_fused_sort's cut-over
-    return mult * val("RS_THREADS") * val("RS_ITEMS"), val("SEG_SHORT"), val("SEG_CHUNK")
 
 
 def test_dense_sink_above_the_fused_sort_cut_over():
@@ -244,7 +230,7 @@ def test_models_match_the_reference_fixtures(case):
         assert abs(float(loss) - ref) <= 3e-5 * max(1.0, abs(ref)) + float(g[f"ref_err.b{j}.loss"])
         checked = 0
         for k in names:
-            mine = (PFX + "vision_model." + k[len(PFX):]) if k.startswith(PFX) else k
+            mine = my_name(k)
             want = torch.from_numpy(g[f"b{j}.grad." + k])
             err = float((grads[mine].cpu() - want).abs().max())
             print(name, "batch", j, "grad", k, err, "max|g|", float(want.abs().max()), "ref_err", float(g[f"ref_err.b{j}.grad." + k]))
@@ -283,18 +269,7 @@ def test_models_match_the_reference_fixtures(case):
 def test_two_fresh_models_give_the_same_bits(case):
     name, _, g = case
     store = torch.from_numpy(g["store"].astype(np.float32)).cuda()
-    runs = []
-    for _ in range(2):
-        m = build_from_fixture(name, g).cuda().train()
-        out = []
-        for j in range(2):
-            loss, grads = _step(m, name, g, j, store)
-            out += [loss] + [grads[k] for k in sorted(grads)]
-        runs.append(out)
-    assert len(runs[0]) == len(runs[1]) == 2 * 19
-    assert float(runs[0][0]) != float(runs[0][19])                  # two batches, two losses
-    for x, y in zip(*runs):
-        assert torch.equal(_bits(x), _bits(y))
+    assert_two_fresh_models_agree(lambda: build_from_fixture(name, g).cuda().train(), lambda m, j: _step(m, name, g, j, store), 19)
 
 
 def test_gradient_clipping_covers_a_model_without_a_flat_buffer(case):
@@ -318,39 +293,10 @@ def test_gradient_clipping_covers_a_model_without_a_flat_buffer(case):
 def test_main_py_trains_evaluates_and_the_checkpoint_reloads(name, tmp_path):
     """main.py on TinyInter with synthetic 64 x 64 images and the tiny tower, two epochs: finite losses that change, Recall@10 and
     NDCG@10 reported from the reloaded checkpoint, whose state_dict is the encoder's and loads with strict=True."""
-    from pixelrec_amd.config import Config
-    from pixelrec_amd.data import load_data
     from pixelrec_amd.utils import get_model
 
-    my, ov = tmp_path / "m.yaml", tmp_path / "o.yaml"
-    my.write_text(f"model: {name}\nembedding_size: 32\ndropout_prob: 0\nmlp_hidden_size: []\n")
-    ov.write_text(f"seed: 2020\nstate: INFO\nuse_modality: True\nreproducibility: True\ncheckpoint_dir: '{tmp_path}/saved'\n"
-                  f"log_path: '{tmp_path}/log'\nshow_progress: False\nMAX_ITEM_LIST_LENGTH: 6\ndata_path: {GOLD}/\n"
-                  "dataset: TinyInter\nimage_path: 'synthetic:64'\nencoder_name: 'clip-vit-tiny-test'\n"
-                  "encoder_source: 'transformers'\nepochs: 2\ntrain_batch_size: 8\n"
-                  "fine_tune_arg: {tune_scale: 37, pre_trained: True, activation: 'relu', dnn_layers: [], method: 'mean'}\n"
-                  "optim_args: {modal_lr: 0.001, rec_lr: 0.001, modal_decay: 0, rec_decay: 0.1}\n"
-                  "eval_batch_size: 16\ntopk: [5,10]\nmetrics: ['Recall', 'NDCG']\nvalid_metric: NDCG@10\n"
-                  "metric_decimal_place: 7\neval_step: 1\nstopping_step: 30\n")
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "OMP_NUM_THREADS")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--device", "0", "--config_file", str(my), str(ov)],
-                       cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-3000:]
-    epochs = [float(x) for x in re.findall(r"epoch \d+ training \[time: [0-9.]+s, train loss: ([0-9.]+)\]", out)]
-    assert len(epochs) == 2 and all(np.isfinite(e) for e in epochs) and epochs[0] != epochs[1], out[-3000:]
-    assert "Loading model structure and parameters from" in out, out[-3000:]
-    for metric in ("recall@10", "ndcg@10"):
-        mm = re.search(r"test result: .*?'%s', ([0-9.]+)\)" % metric, out)
-        assert mm is not None and 0.0 <= float(mm.group(1)) <= 1.0, out[-2000:]
-    print(name, "epoch losses", epochs, re.search(r"test result: .*", out).group(0))
-    files = os.listdir(tmp_path / "saved")
-    assert len(files) == 1
-    ck = torch.load(tmp_path / "saved" / files[0], map_location="cpu", weights_only=False)
+    _, _, ck, config, data = run_main_py(tmp_path, f"model: {name}\nembedding_size: 32\ndropout_prob: 0\nmlp_hidden_size: []\n")
     assert all(k.startswith("visual_encoder.") for k in ck["state_dict"])
     assert [len(x["params"]) for x in ck["optimizer"]["param_groups"]] == [18, 0]       # the reference's two groups, the second empty
-    config = Config([str(my), str(ov)])
-    data = load_data(config)
-    data.build()
     fresh = get_model(name)(config, data)
     fresh.load_state_dict(ck["state_dict"], strict=True)

@@ -6,6 +6,7 @@ import torch
 
 from oracle import mosasrec_oracle as MO
 from oracle import sasrec_oracle as O
+from tests.mo_common import tower_config
 
 pytestmark = pytest.mark.gpu
 
@@ -14,11 +15,8 @@ TUNE = 5 + 16 * 2            # tiny tower has 3 blocks: freeze embeddings + bloc
 
 
 def _config(p_drop=0.0):
-    return {"n_layers": NL, "n_heads": H, "embedding_size": D, "inner_size": 2, "hidden_dropout_prob": p_drop,
-            "attn_dropout_prob": p_drop, "hidden_act": "gelu", "layer_norm_eps": 1e-12, "initializer_range": 0.02,
-            "MAX_ITEM_LIST_LENGTH": L, "seed": 2020, "encoder_name": "clip-vit-tiny-test",
-            "encoder_source": "transformers", "pretrain_path": None,
-            "fine_tune_arg": {"tune_scale": TUNE, "pre_trained": True, "activation": "relu", "dnn_layers": [], "method": "mean"}}
+    return tower_config(TUNE, n_layers=NL, n_heads=H, embedding_size=D, inner_size=2, hidden_dropout_prob=p_drop,
+                        attn_dropout_prob=p_drop, hidden_act="gelu", layer_norm_eps=1e-12, initializer_range=0.02, MAX_ITEM_LIST_LENGTH=L)
 
 
 def _build():
@@ -92,6 +90,24 @@ def test_loss_and_gradients_match_oracle():
         else:
             assert p.grad is None
     assert checked == 16
+
+
+def test_backward_without_a_training_forward_raises_before_any_launch():
+    """After a training step the table is gone: a second _backward_train raises like every other model's, and because the guard
+    stands in front of the first launch the status word stays clear."""
+    from pixelrec_amd import ops
+    from pixelrec_amd.lib import PxrError
+
+    m, _, _ = _build()
+    m = m.cuda().train()
+    g = torch.Generator().manual_seed(0)
+    images = torch.randn(B, 2 * (L + 1), 3, 64, 64, generator=g).cuda()
+    m((images, torch.ones(B, L, dtype=torch.int64).cuda())).backward()
+    ops.raise_on_bad_indices()
+    assert m._train_table is None and m._saved is None
+    with pytest.raises(PxrError, match="without a training-mode forward"):
+        m._backward_train(torch.ones(1, device="cuda"))
+    ops.raise_on_bad_indices()                            # nothing was launched, nothing was flagged
 
 
 def test_predict_and_compute_item():

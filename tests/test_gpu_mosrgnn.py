@@ -4,9 +4,6 @@ dedup, the model against the fixture of the reference's own MOSRGNN in both inpu
 predict, the fused top-k), determinism, bad positions, the optimizer's two groups, and main.py end to end.  Every test here needs
 the new class, so each fails without the feature."""
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,15 +12,12 @@ import torch
 from pixelrec_amd import ops
 from tests import mosrgnn_restate as R
 from tests import srgnn_restate as SR
-from tests.test_mosrgnn_cpu import FOUR, GOLD, ROOT, _config, _trainer_optimizer, build_from_fixture, my_name
+from tests.mo_common import GOLD, assert_optimizer_state_round_trips, assert_two_fresh_models_agree, bits as _bits, my_name, run_main_py
+from tests.test_mosrgnn_cpu import _config, build_from_fixture
 
 pytestmark = pytest.mark.gpu
 U32 = 2.0 ** -24
 SEG_SHORT = 8                      # csrc/embed_grad.hip: a longer segment takes the staged branch of the segment sum
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 # ------------------------------------------------------------------------------------------------------------ cases
@@ -314,17 +308,8 @@ def test_model_matches_the_reference_fixture(gold, form):
 # ------------------------------------------------------------------------------------------------------------ 5. determinism, errors
 def test_two_fresh_models_give_the_same_bits(gold):
     store = torch.from_numpy(gold["store"].astype(np.float32)).cuda()
-    runs = []
-    for _ in range(2):
-        m = build_from_fixture(gold, 2).cuda().train()
-        out = []
-        for j in range(2):
-            loss, grads = _step(m, gold, j, store, "positions")
-            out += [loss] + [grads[k] for k in sorted(grads)]
-        runs.append(out)
-    assert len(runs[0]) == len(runs[1]) == 2 * 28 and float(runs[0][0]) != float(runs[0][28])
-    for x, y in zip(*runs):
-        assert torch.equal(_bits(x), _bits(y))
+    assert_two_fresh_models_agree(lambda: build_from_fixture(gold, 2).cuda().train(), lambda m, j: _step(m, gold, j, store, "positions"),
+                                  28)
 
 
 def test_bad_position_raises_index_error():
@@ -352,79 +337,26 @@ def test_optimizer_steps_both_groups_and_its_state_round_trips(gold):
     """Four optim_args: the encoder group and a rec group without a table, [18, 19] parameters and 18 + 17 states; one step moves
     both and leaves gnn.linear_edge_f where it was; the torch-layout state loads into torch.optim.AdamW over the reference's two
     groups and back."""
-    from pixelrec_amd.optim import OptimizerGroup
-
-    m = build_from_fixture(gold, 2, tune=37).cuda().train()
-    opt = _trainer_optimizer(m, FOUR)
-    assert isinstance(opt, OptimizerGroup)
     store = torch.from_numpy(gold["store"].astype(np.float32)).cuda()
-    before = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    opt.zero_grad()
-    _step(m, gold, 0, store, "positions")
-    opt.step()
-    after = m.state_dict()
-    trainable = {n for n, p in m.named_parameters() if p.requires_grad}
-    moved = {k for k in before if not torch.equal(before[k], after[k])}
-    assert moved <= trainable and set(R.NAMES) <= moved and not set(R.EDGE_F) & moved
-    assert sum("visual_encoder" in k for k in moved) >= 15         # (a key projection's bias has a zero gradient: it may stay)
-    sd = opt.state_dict(layout="torch")
+
+    def moved(moved, trainable):
+        assert moved <= trainable and set(R.NAMES) <= moved and not set(R.EDGE_F) & moved
+        assert sum("visual_encoder" in k for k in moved) >= 15     # (a key projection's bias has a zero gradient: it may stay)
+
     with_state = [i for i in range(37) if i not in (18 + 10, 18 + 11)]                      # linear_edge_f: no state
-    assert [len(x["params"]) for x in sd["param_groups"]] == [18, 19] and sorted(sd["state"]) == with_state
-    assert [(x["lr"], x["weight_decay"]) for x in sd["param_groups"]] == [(1e-4, 0.0), (3e-4, 0.1)]
-    enc = [p for n, p in m.named_parameters() if "visual_encoder" in n and p.requires_grad]
-    rec = [p for n, p in m.named_parameters() if "visual_encoder" not in n]
-    tor = torch.optim.AdamW([{"params": enc, "lr": 1.0, "weight_decay": 0.5}, {"params": rec, "lr": 2.0, "weight_decay": 0.25}])
-    tor.load_state_dict(sd)                                         # the layout the reference stores
-    assert [(x["lr"], x["weight_decay"]) for x in tor.param_groups] == [(1e-4, 0.0), (3e-4, 0.1)]
-    opt2 = _trainer_optimizer(build_from_fixture(gold, 2, tune=37).cuda().train(), {**FOUR, "modal_lr": 5.0, "rec_lr": 7.0})
-    opt2.load_state_dict(tor.state_dict())
-    sd2 = opt2.state_dict(layout="torch")
-    assert [x["params"] for x in sd2["param_groups"]] == [x["params"] for x in sd["param_groups"]]
-    assert [(x["lr"], x["weight_decay"]) for x in sd2["param_groups"]] == [(1e-4, 0.0), (3e-4, 0.1)]
-    assert sorted(sd2["state"]) == with_state
-    for i in with_state:
-        for key in ("exp_avg", "exp_avg_sq"):
-            assert torch.equal(sd2["state"][i][key].cpu(), sd["state"][i][key].cpu()), (i, key)
+    assert_optimizer_state_round_trips(lambda: build_from_fixture(gold, 2, tune=37).cuda().train(),
+                                       lambda m: _step(m, gold, 0, store, "positions"), [18, 19], with_state, moved=moved)
 
 
 # ------------------------------------------------------------------------------------------------------------ 7. end to end
 def test_main_py_trains_evaluates_and_the_checkpoint_reloads(tmp_path):
     """main.py on TinyInter with synthetic 64 x 64 images and the tiny tower, two epochs, through the fused evaluation: finite losses
     that change, Recall@10 and NDCG@10 reported from the reloaded checkpoint, whose state_dict loads with strict=True."""
-    from pixelrec_amd.config import Config
-    from pixelrec_amd.data import load_data
     from pixelrec_amd.utils import get_model
 
-    my, ov = tmp_path / "m.yaml", tmp_path / "o.yaml"
-    my.write_text("model: MOSRGNN\nembedding_size: 32\nstep: 2\n")
-    ov.write_text(f"seed: 2020\nstate: INFO\nuse_modality: True\nreproducibility: True\ncheckpoint_dir: '{tmp_path}/saved'\n"
-                  f"log_path: '{tmp_path}/log'\nshow_progress: False\nMAX_ITEM_LIST_LENGTH: 6\ndata_path: {GOLD}/\n"
-                  "dataset: TinyInter\nimage_path: 'synthetic:64'\nencoder_name: 'clip-vit-tiny-test'\n"
-                  "encoder_source: 'transformers'\nepochs: 2\ntrain_batch_size: 8\n"
-                  "fine_tune_arg: {tune_scale: 37, pre_trained: True, activation: 'relu', dnn_layers: [], method: 'mean'}\n"
-                  "optim_args: {modal_lr: 0.001, rec_lr: 0.001, modal_decay: 0, rec_decay: 0.1}\n"
-                  "eval_batch_size: 16\ntopk: [5,10]\nmetrics: ['Recall', 'NDCG']\nvalid_metric: NDCG@10\n"
-                  "metric_decimal_place: 7\neval_step: 1\nstopping_step: 30\n")
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "OMP_NUM_THREADS")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py"), "--device", "0", "--config_file", str(my), str(ov)],
-                       cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-3000:]
-    epochs = [float(x) for x in re.findall(r"epoch \d+ training \[time: [0-9.]+s, train loss: ([0-9.]+)\]", out)]
-    assert len(epochs) == 2 and all(np.isfinite(e) for e in epochs) and epochs[0] != epochs[1], out[-3000:]
-    assert "Loading model structure and parameters from" in out, out[-3000:]
-    for metric in ("recall@10", "ndcg@10"):
-        mm = re.search(r"test result: .*?'%s', ([0-9.]+)\)" % metric, out)
-        assert mm is not None and 0.0 <= float(mm.group(1)) <= 1.0, out[-2000:]
-    print("epoch losses", epochs, re.search(r"test result: .*", out).group(0))
-    files = os.listdir(tmp_path / "saved")
-    assert len(files) == 1
-    ck = torch.load(tmp_path / "saved" / files[0], map_location="cpu", weights_only=False)
+    _, _, ck, config, data = run_main_py(tmp_path, "model: MOSRGNN\nembedding_size: 32\nstep: 2\n")
     rec = [k for k in ck["state_dict"] if not k.startswith("visual_encoder.")]
     assert list(ck["state_dict"])[-19:] == rec and [k for k in rec if k not in R.EDGE_F] == R.NAMES
     assert [len(x["params"]) for x in ck["optimizer"]["param_groups"]] == [18, 19]        # the reference's two groups
-    config = Config([str(my), str(ov)])
-    data = load_data(config)
-    data.build()
     fresh = get_model("MOSRGNN")(config, data)
     fresh.load_state_dict(ck["state_dict"], strict=True)

@@ -10,29 +10,15 @@ import pytest
 import torch
 
 from tests import mobert4rec_restate as R
+from tests.mo_common import FOUR, GOLD, ROOT, fixture_state, my_name, tower_config, trainer_optimizer
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
-PFX = "visual_encoder.item_encoder."
 N_BLOCK = 35          # position_embedding + 2 layers x 16 + LayerNorm x 2
 
 
 def _config(D, L, tune, heads=2, inner=2, layers=2, p_drop=0.0):
-    return {"n_layers": layers, "n_heads": heads, "embedding_size": D, "inner_size": inner, "hidden_dropout_prob": p_drop,
-            "attn_dropout_prob": p_drop, "hidden_act": "gelu", "layer_norm_eps": 1e-12, "initializer_range": 0.02, "mask_ratio": 0.6,
-            "MAX_ITEM_LIST_LENGTH": L, "seed": 2020,
-            "encoder_name": "clip-vit-tiny-test", "encoder_source": "transformers", "pretrain_path": None,
-            "fine_tune_arg": {"tune_scale": tune, "pre_trained": True, "activation": "relu", "dnn_layers": [], "method": "mean"}}
-
-
-def my_name(k):
-    """A fixture key (transformers-5.x names) -> this build's parameter name (`vision_model.` in the encoder's names)."""
-    return (PFX + "vision_model." + k[len(PFX):]) if k.startswith(PFX) else k
-
-
-def fixture_state(g):
-    """The fixture's state_dict under this build's names, without the unused post_layernorm pair."""
-    return {my_name(k): v for k, v in R.golden_state(g).items() if "post_layernorm" not in k}
+    return tower_config(tune, n_layers=layers, n_heads=heads, embedding_size=D, inner_size=inner, hidden_dropout_prob=p_drop,
+                        attn_dropout_prob=p_drop, hidden_act="gelu", layer_norm_eps=1e-12, initializer_range=0.02, mask_ratio=0.6,
+                        MAX_ITEM_LIST_LENGTH=L)
 
 
 def restate_cfg(g):
@@ -48,7 +34,7 @@ def build_from_fixture(g, p_drop=0.0):
         item_num = I
 
     m = M.MOBERT4Rec(_config(D, L, int(g["meta"][6]), int(g["meta"][7]), int(g["meta"][8]), int(g["meta"][9]), p_drop), DL())
-    m.load_state_dict(fixture_state(g), strict=True)
+    m.load_state_dict(fixture_state(g, R.golden_state(g)), strict=True)
     return m
 
 
@@ -264,7 +250,7 @@ def test_state_dict_is_the_references_and_loads_strictly(gold):
     assert keys[-N_BLOCK] == "position_embedding.weight" and keys[-2:] == ["LayerNorm.weight", "LayerNorm.bias"]
     assert [n for n, _ in m.named_parameters()] == keys              # no buffer
     assert list(m.rec_parameter_names()) == blk
-    for k, v in fixture_state(g).items():
+    for k, v in fixture_state(g, R.golden_state(g)).items():
         assert torch.equal(m.state_dict()[k], v)
     frozen = [n for n, p in m.named_parameters() if not p.requires_grad]
     assert len(frozen) == int(g["meta"][6]) == len(g["frozen"]) and all("visual_encoder" in n for n in frozen)
@@ -309,27 +295,11 @@ def test_reference_input_form_maps_to_one_row_per_position_behind_the_zero_image
         m._reference_form(input_ids, modal[:, :14], masked)
 
 
-class _Wrap:
-    def __init__(self, m):
-        self.module = m
-
-
-def _trainer_optimizer(m, optim_args):
-    from pixelrec_amd.trainer import Trainer
-
-    t = Trainer.__new__(Trainer)
-    t.optim_args, t.model, t.config = optim_args, _Wrap(m), {"decay_check_name": None}
-    return t._build_optimizer()
-
-
-FOUR = {"modal_lr": 1e-4, "rec_lr": 3e-4, "modal_decay": 0.0, "rec_decay": 0.1}
-
-
 def test_four_optim_args_give_the_encoder_group_and_a_rec_group_without_a_table(gold):
     from pixelrec_amd.optim import OptimizerGroup, PxrAdamW, VisualAdamW, reference_rec_parameter_names
 
     m = build_from_fixture(gold)
-    opt = _trainer_optimizer(m, FOUR)
+    opt = trainer_optimizer(m, FOUR)
     assert isinstance(opt, OptimizerGroup)
     vis, rec = opt._split()
     assert isinstance(vis, VisualAdamW) and isinstance(rec, PxrAdamW) and rec.has_table is False

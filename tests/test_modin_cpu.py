@@ -10,27 +10,13 @@ import torch
 
 from tests import din_restate as DR
 from tests import modin_restate as R
+from tests.mo_common import FOUR, GOLD, fixture_state, my_name, tower_config, trainer_optimizer
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
-PFX = "visual_encoder.item_encoder."
 TOWER = 2e-5         # per-entry budget of the torch-module tower against the reference's (tests/test_mopool_cpu.py)
 
 
 def _config(D, L, tune, hidden=(12, 4)):
-    return {"embedding_size": D, "mlp_hidden_size": list(hidden), "dropout_prob": 0, "MAX_ITEM_LIST_LENGTH": L, "seed": 2020,
-            "encoder_name": "clip-vit-tiny-test", "encoder_source": "transformers", "pretrain_path": None,
-            "fine_tune_arg": {"tune_scale": tune, "pre_trained": True, "activation": "relu", "dnn_layers": [], "method": "mean"}}
-
-
-def my_name(k):
-    """A fixture key (transformers-5.x names) -> this build's parameter name (`vision_model.` in the encoder's names)."""
-    return (PFX + "vision_model." + k[len(PFX):]) if k.startswith(PFX) else k
-
-
-def fixture_state(g):
-    """The fixture's state_dict under this build's names, without the unused post_layernorm pair."""
-    return {my_name(k): torch.from_numpy(g["sd." + k]) for k in (str(x) for x in g["sd.keys"]) if "post_layernorm" not in k}
+    return tower_config(tune, embedding_size=D, mlp_hidden_size=list(hidden), dropout_prob=0, MAX_ITEM_LIST_LENGTH=L)
 
 
 def build_from_fixture(g):
@@ -246,32 +232,16 @@ def test_reference_input_form_maps_to_positions_behind_the_zero_image():
         M.MODIN._reference_form(modal, items[:, :3])
 
 
-class _Wrap:
-    def __init__(self, m):
-        self.module = m
-
-
-def _trainer_optimizer(m, optim_args):
-    from pixelrec_amd.trainer import Trainer
-
-    t = Trainer.__new__(Trainer)
-    t.optim_args, t.model, t.config = optim_args, _Wrap(m), {"decay_check_name": None}
-    return t._build_optimizer()
-
-
-FOUR = {"modal_lr": 1e-4, "rec_lr": 3e-4, "modal_decay": 0.0, "rec_decay": 0.1}
-
-
 def test_four_optim_args_give_the_encoder_group_and_a_rec_group_without_a_table(gold):
     from pixelrec_amd.optim import OptimizerGroup, PxrAdamW, VisualAdamW, has_lazy_table, reference_rec_parameter_names
 
     m = build_from_fixture(gold)
-    opt = _trainer_optimizer(m, FOUR)
+    opt = trainer_optimizer(m, FOUR)
     assert isinstance(opt, OptimizerGroup)
     vis, rec = opt._split()
     assert isinstance(vis, VisualAdamW) and isinstance(rec, PxrAdamW) and rec.has_table is False and not has_lazy_table(m)
     assert [len(vis._trainable()), len(reference_rec_parameter_names(m))] == [18, 6]
     assert (vis.param_groups[0]["lr"], vis.param_groups[0]["weight_decay"]) == (1e-4, 0.0)
     assert (rec.param_groups[0]["lr"], rec.param_groups[0]["weight_decay"]) == (3e-4, 0.1)
-    one = _trainer_optimizer(build_from_fixture(gold), {"learning_rate": 2e-4, "weight_decay": 0.05})
+    one = trainer_optimizer(build_from_fixture(gold), {"learning_rate": 2e-4, "weight_decay": 0.05})
     assert isinstance(one, PxrAdamW) and (one.param_groups[0]["lr"], one.param_groups[0]["weight_decay"]) == (2e-4, 0.05)

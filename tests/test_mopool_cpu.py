@@ -8,18 +8,14 @@ import pytest
 import torch
 
 from tests import pool_restate as R
+from tests.mo_common import FOUR, GOLD, fixture_state, tower_config, trainer_optimizer
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
-PFX = "visual_encoder.item_encoder."
 CASES = {"modssm_tiny": ("MODSSM", "DSSM"), "mofm_tiny": ("MOFM", "FM")}
 TOWER = 2e-5         # per-entry budget of the torch-module tower against the reference's (test_mosasrec_golden.py's CPU part)
 
 
 def _config(D, L, tune):
-    return {"embedding_size": D, "mlp_hidden_size": [], "dropout_prob": 0, "MAX_ITEM_LIST_LENGTH": L, "seed": 2020,
-            "encoder_name": "clip-vit-tiny-test", "encoder_source": "transformers", "pretrain_path": None,
-            "fine_tune_arg": {"tune_scale": tune, "pre_trained": True, "activation": "relu", "dnn_layers": [], "method": "mean"}}
+    return tower_config(tune, embedding_size=D, mlp_hidden_size=[], dropout_prob=0, MAX_ITEM_LIST_LENGTH=L)
 
 
 def build_from_fixture(name, g):
@@ -33,12 +29,7 @@ def build_from_fixture(name, g):
         item_num = I
 
     m = getattr(M, name)(_config(D, L, int(g["meta"][6])), DL())
-    sd = {}
-    for k in (str(x) for x in g["sd.keys"]):
-        if "post_layernorm" in k:
-            continue
-        sd[(PFX + "vision_model." + k[len(PFX):]) if k.startswith(PFX) else k] = torch.from_numpy(g["sd." + k])
-    m.load_state_dict(sd, strict=True)
+    m.load_state_dict(fixture_state(g), strict=True)
     return m
 
 
@@ -183,28 +174,12 @@ def test_state_dict_is_the_encoders_alone(case):
     assert len(frozen) == int(g["meta"][6]) == len(g["frozen"])
 
 
-class _Wrap:
-    def __init__(self, m):
-        self.module = m
-
-
-def _trainer_optimizer(m, optim_args):
-    from pixelrec_amd.trainer import Trainer
-
-    t = Trainer.__new__(Trainer)
-    t.optim_args, t.model, t.config = optim_args, _Wrap(m), {"decay_check_name": None}
-    return t._build_optimizer()
-
-
-FOUR = {"modal_lr": 1e-4, "rec_lr": 3e-4, "modal_decay": 0.0, "rec_decay": 0.1}
-
-
 def test_optimizer_is_the_visual_group_with_an_empty_second_group(case):
     from pixelrec_amd.optim import VisualAdamW, VisualOnlyAdamW
 
     name, _, g = case
     m = build_from_fixture(name, g)
-    opt = _trainer_optimizer(m, FOUR)
+    opt = trainer_optimizer(m, FOUR)
     assert isinstance(opt, VisualOnlyAdamW) and isinstance(opt, VisualAdamW)
     assert (opt.param_groups[0]["lr"], opt.param_groups[0]["weight_decay"]) == (1e-4, 0.0)
     sd = opt.state_dict(layout="torch")
@@ -218,7 +193,7 @@ def test_optimizer_is_the_visual_group_with_an_empty_second_group(case):
     assert [(x["lr"], x["weight_decay"]) for x in tor.param_groups] == [(1e-4, 0.0), (3e-4, 0.1)]
     back = tor.state_dict()
     assert [x["params"] for x in back["param_groups"]] == [x["params"] for x in sd["param_groups"]]
-    opt2 = _trainer_optimizer(build_from_fixture(name, g), {**FOUR, "modal_lr": 5.0, "rec_lr": 7.0})
+    opt2 = trainer_optimizer(build_from_fixture(name, g), {**FOUR, "modal_lr": 5.0, "rec_lr": 7.0})
     opt2.load_state_dict(back)                                       # ... and it loads back
     assert opt2.state_dict(layout="torch") == sd
     with pytest.raises(ValueError):
@@ -228,7 +203,7 @@ def test_optimizer_is_the_visual_group_with_an_empty_second_group(case):
 
 def test_two_optim_args_give_one_group(case):
     name, _, g = case
-    opt = _trainer_optimizer(build_from_fixture(name, g), {"learning_rate": 2e-4, "weight_decay": 0.05})
+    opt = trainer_optimizer(build_from_fixture(name, g), {"learning_rate": 2e-4, "weight_decay": 0.05})
     sd = opt.state_dict(layout="torch")
     assert len(sd["param_groups"]) == 1 and (sd["param_groups"][0]["lr"], sd["param_groups"][0]["weight_decay"]) == (2e-4, 0.05)
 
@@ -239,7 +214,7 @@ def test_all_frozen_encoder_has_nothing_to_train(case):
     for p in m.parameters():
         p.requires_grad_(False)
     with pytest.raises(ValueError, match="nothing to train"):
-        _trainer_optimizer(m, FOUR)
+        trainer_optimizer(m, FOUR)
 
 
 def test_other_models_keep_their_optimizers():
@@ -252,7 +227,7 @@ def test_other_models_keep_their_optimizers():
 
     cfg = dict(_config(64, 4, 37), n_layers=1, n_heads=2, inner_size=2, hidden_dropout_prob=0.0, attn_dropout_prob=0.0,
                hidden_act="gelu", layer_norm_eps=1e-12, initializer_range=0.02)
-    opt = _trainer_optimizer(M.MOSASRec(cfg, DL()), FOUR)
+    opt = trainer_optimizer(M.MOSASRec(cfg, DL()), FOUR)
     assert isinstance(opt, OptimizerGroup)
 
 
@@ -275,4 +250,9 @@ def test_input_forms_and_mismatched_planes():
         fm._split_index(planes)
     with pytest.raises(ValueError):
         ds._split_index(R.fm_form(rows))
+    for m in (fm, ds):                                              # a rank or a width no input form has
+        for bad in (rows[0], rows[:, :2], R.fm_form(rows)[None]):
+            assert (bad.dim(), bad.shape[-1]) in ((1, 6), (2, 2), (4, 5))
+            with pytest.raises(ValueError):
+                m._split_index(bad)
     assert not hasattr(ds, "mlp_layers") and ds.mlp_hidden_size == [] and ds.pool_mean and not fm.pool_mean

@@ -9,27 +9,13 @@ import torch
 
 from tests import mosrgnn_restate as R
 from tests import srgnn_restate as SR
+from tests.mo_common import FOUR, GOLD, ROOT, fixture_state, my_name, tower_config, trainer_optimizer
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
-PFX = "visual_encoder.item_encoder."
 TOWER = 2e-5         # per-entry budget of the torch-module tower against the reference's (tests/test_mopool_cpu.py)
 
 
 def _config(D, L, step, tune):
-    return {"embedding_size": D, "step": step, "MAX_ITEM_LIST_LENGTH": L, "seed": 2020,
-            "encoder_name": "clip-vit-tiny-test", "encoder_source": "transformers", "pretrain_path": None,
-            "fine_tune_arg": {"tune_scale": tune, "pre_trained": True, "activation": "relu", "dnn_layers": [], "method": "mean"}}
-
-
-def my_name(k):
-    """A fixture key (transformers-5.x names) -> this build's parameter name (`vision_model.` in the encoder's names)."""
-    return (PFX + "vision_model." + k[len(PFX):]) if k.startswith(PFX) else k
-
-
-def fixture_state(g):
-    """The fixture's state_dict under this build's names, without the unused post_layernorm pair."""
-    return {my_name(k): torch.from_numpy(g["sd." + k]) for k in (str(x) for x in g["sd.keys"]) if "post_layernorm" not in k}
+    return tower_config(tune, embedding_size=D, step=step, MAX_ITEM_LIST_LENGTH=L)
 
 
 def build_from_fixture(g, step=1, tune=None):
@@ -293,27 +279,11 @@ def test_fixture_batches_hold_the_cases_they_are_there_for(gold):
 
 
 # ------------------------------------------------------------------------------------------------------------ optimizer
-class _Wrap:
-    def __init__(self, m):
-        self.module = m
-
-
-def _trainer_optimizer(m, optim_args):
-    from pixelrec_amd.trainer import Trainer
-
-    t = Trainer.__new__(Trainer)
-    t.optim_args, t.model, t.config = optim_args, _Wrap(m), {"decay_check_name": None}
-    return t._build_optimizer()
-
-
-FOUR = {"modal_lr": 1e-4, "rec_lr": 3e-4, "modal_decay": 0.0, "rec_decay": 0.1}
-
-
 def test_four_optim_args_give_the_encoder_group_and_a_rec_group_without_a_table(gold):
     from pixelrec_amd.optim import OptimizerGroup, PxrAdamW, VisualAdamW, has_lazy_table, reference_rec_parameter_names
 
     m = build_from_fixture(gold, tune=37)
-    opt = _trainer_optimizer(m, FOUR)
+    opt = trainer_optimizer(m, FOUR)
     assert isinstance(opt, OptimizerGroup)
     vis, rec = opt._split()
     assert isinstance(vis, VisualAdamW) and isinstance(rec, PxrAdamW) and rec.has_table is False and not has_lazy_table(m)
