@@ -725,6 +725,14 @@ int pxr_table_rows_i64(const void* segments, int n_segments, int64_t* rows, int6
  * H % 4 == 0, H <= 4096. */
 int pxr_mf_pair_fwd_f32(const float* ufeat, const float* ifeat, const int64_t* rows, int H, int B, float* coef, float* lossrow,
                         float* loss, void* stream);
+/* The same head with the shift as an argument: lossrow[b] = -(eps + log sigmoid(x_b)), coef unchanged; pxr_mf_pair_fwd_f32 is this
+ * entry with eps = 1e-8f, bit for bit.  eps = 0 is momf.py:59's loss, -mean log sigmoid(x_b).  ufeat and ifeat are indexed through
+ * the one rows[3B] list with two base pointers, so ufeat = MOMF's user table [1 + n_users, H], ifeat = the encoder's output
+ * E [M, H] and rows = [1 + user | idx.view(-1)] is MOMF's forward without a gather.  log sigmoid(x) is computed as min(x, 0) -
+ * log1p(exp(-|x|)) and stays finite for every finite x (about x for x << 0); the reference's log(sigmoid(x)) is -inf in float32
+ * once sigmoid(x) underflows (x below about -103.97), where the two differ by design.  eps finite and >= 0. */
+int pxr_mf_pair_fwd_eps_f32(const float* ufeat, const float* ifeat, const int64_t* rows, int H, int B, float eps, float* coef,
+                            float* lossrow, float* loss, void* stream);
 /* Its backward onto the tower outputs: du[b] = c_b (i+_b - i-_b), di[2b] = c_b u_b, di[2b + 1] = -c_b u_b with c_b = coef[b] *
  * grad_scale * (*grad_scale_dev if given). */
 int pxr_mf_pair_bwd_f32(const float* ufeat, const float* ifeat, const float* coef, int H, int B, float grad_scale,
@@ -737,6 +745,19 @@ int pxr_mf_pair_bwd_f32(const float* ufeat, const float* ifeat, const float* coe
 int pxr_mf_table_grad_f32(const float* table, int64_t n_table, int D, const int64_t* rows, int B, const float* coef,
                           const float* occ, float grad_scale, const float* grad_scale_dev, int64_t* sp_idx, float* sp_rows,
                           int32_t* sp_n, int64_t cap, void* stream);
+/* MOMF (model/PixelNet/momf.py): the same per-occurrence sums over TWO row spaces and into two sinks, one launch.  rows[3B] = [1 +
+ * user[b] for b < B | idx.view(-1)]: rows of utable [n_utable, D] (row 0 a spare), then positions into E [M, D] (base 0: there is
+ * no padding position).  Both already checked and clamped (pxr_table_rows_i64).
+ *   user sink (sparse, *sp_n = B): slot o < B = (rows[o], sum_b c_b (E[p_b] - E[n_b]) over the samples b of that user, ascending) at
+ *     the first occurrence of the row, (0, zeros) at the others -- pxr_mf_table_grad_f32's user slots, bit for bit;
+ *   item sink (dense): dE [M, D] is zeroed by this entry, then dE[m, :] = the sum over the occurrences of position m in ascending
+ *     order of +-c_b u_b, stored by the first occurrence; a row nobody reads is +0.0 whatever dE held.
+ * occ != NULL (towers): occurrence k contributes occ[k, :] ([3B, D]) to either sink and utable, E, coef may be NULL; occ == NULL:
+ * the head's formula, c_b = coef[b] * grad_scale * (*grad_scale_dev if given).  O(B D) work, vector stores only, no atomics, the
+ * same bits from run to run.  D % 4 == 0, D <= 4096, cap >= B; dE must not alias an operand. */
+int pxr_momf_pair_grad_f32(const float* utable, int64_t n_utable, const float* E, int64_t M, int D, const int64_t* rows, int B,
+                           const float* coef, const float* occ, float grad_scale, const float* grad_scale_dev, int64_t* sp_idx,
+                           float* sp_rows, int32_t* sp_n, int64_t cap, float* dE, void* stream);
 /* BatchNorm1d (training) + tanh over x [R, H]: batch mean and biased variance (eps), y = tanh(gamma xhat + beta); mean / rstd
  * [H] saved for the backward; running_mean / running_var updated with momentum and the unbiased variance, *num_batches_tracked
  * += 1 (may be NULL).  Column sums in a fixed order.  R >= 2, H % 4 == 0, H <= 4096; y must not alias x. */

@@ -23,6 +23,7 @@ struct MfPairArgs {
   float* lossrow;              // [B]
   float gscale;
   const float* gscale_dev;
+  float eps;                   // the shift outside the log (forward): 1e-8 for mf.py, 0 for momf.py:59
   f32x4* du;                   // [B, hv]   (tower backward)
   f32x4* di;                   // [2B, hv]
 };
@@ -39,7 +40,7 @@ __device__ __forceinline__ void mf_pair_rows_of(const MfPairArgs& a, int b, int6
   }
 }
 
-// x_b = <u_b, i+_b> - <u_b, i-_b> into the tail with the 1e-8 outside the log (mf.py forward).  One wave per b.
+// x_b = <u_b, i+_b> - <u_b, i-_b> into the tail with eps outside the log (mf.py forward: 1e-8).  One wave per b.
 __global__ void __launch_bounds__(256) mf_pair_fwd_kernel(MfPairArgs a) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -48,7 +49,7 @@ __global__ void __launch_bounds__(256) mf_pair_fwd_kernel(MfPairArgs a) {
   mf_pair_rows_of(a, b, ru, rp, rn);
   float sp, sn;
   pair_dots(a.ufeat + ru * a.hv, a.ifeat + rp * a.hv, a.ifeat + rn * a.hv, a.hv, lane, sp, sn);
-  if (lane == 0) bpr_tail_log_outside(sp - sn, a.B, a.lossrow[b], a.coef[b]);
+  if (lane == 0) bpr_tail_log_outside(sp - sn, a.B, a.eps, a.lossrow[b], a.coef[b]);
 }
 
 // Tower form of the head's backward: d u_b = c_b (i+_b - i-_b), d i+_b = c_b u_b, d i-_b = -c_b u_b (dense, one wave per b).
@@ -112,6 +113,65 @@ __global__ void __launch_bounds__(256) mf_table_grad_kernel(MfTableGradArgs a) {
   }
   row_store(s, a.sp_rows + (int64_t)o * a.dv, a.dv, lane);
   if (lane == 0) a.sp_idx[o] = first ? node : 0;
+}
+
+// MOMF (momf.py): the same occurrence list over TWO row spaces -- rows[0:B] are rows of the user table, rows[B:3B] positions into
+// the encoder's output E [M, D] -- and two sinks.  Occurrence o < B is mf_table_grad_kernel's user slot: (row, sum) at the first
+// occurrence of a user row, (0, zeros) at the others, scanned within rows[0:B].  Occurrence o >= B is scanned within rows[B:3B];
+// the first occurrence of position m stores its sum into dE[m, :] (zeroed by the entry before the launch) and the later ones write
+// nothing.  Contributions and their order are mf_table_grad_kernel's, so both sinks carry its bits.
+struct MomfGradArgs {
+  const f32x4* utable;         // [n_utable, dv]
+  const f32x4* E;              // [M, dv]
+  const int64_t* rows;         // [3B] = [user rows | positions (positive, negative) of b]
+  const float* coef;
+  const f32x4* occ;            // [3B, dv] | NULL
+  int dv, B;
+  int64_t M;
+  float gscale;
+  const float* gscale_dev;
+  int64_t* sp_idx;             // [B]
+  f32x4* sp_rows;              // [B, dv]
+  int32_t* sp_n;
+  f32x4* dE;                   // [M, dv]
+};
+
+template <int CH>
+__global__ void __launch_bounds__(256) momf_pair_grad_kernel(MomfGradArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int n_occ = 3 * a.B;
+  if (o == 0 && lane == 0) a.sp_n[0] = a.B;
+  if (o >= n_occ) return;
+  const bool user_sink = o < a.B;
+  const int lo = user_sink ? 0 : a.B, hi = user_sink ? a.B : n_occ;
+  const int64_t node = a.rows[o];
+  const bool first = is_first_occurrence(a.rows, lo, o, node, lane);
+  if (!first && !user_sink) return;                  // a later occurrence of a position: its sum is the first one's
+  f32x4 s[CH];
+  row_zero(s);
+  if (first) {
+    const float g = grad_scale(a.gscale, a.gscale_dev);
+    for_each_occurrence(a.rows, o, hi, node, lane, [&](int kk) {
+      if (a.occ) {
+        row_add_scaled(s, 1.f, a.occ + (int64_t)kk * a.dv, a.dv, lane);      // 1 x is x: the plain sum of the occurrences' rows
+        return;
+      }
+      const int b = user_sink ? kk : (kk - a.B) >> 1;
+      const float c = a.coef[b] * g;
+      if (user_sink)
+        row_add_scaled_diff(s, c, a.E + a.rows[a.B + 2 * (int64_t)b] * a.dv, a.E + a.rows[a.B + 2 * (int64_t)b + 1] * a.dv, a.dv,
+                            lane);
+      else
+        row_add_scaled(s, ((kk - a.B) & 1) ? -c : c, a.utable + a.rows[b] * a.dv, a.dv, lane);
+    });
+  }
+  if (user_sink) {
+    row_store(s, a.sp_rows + (int64_t)o * a.dv, a.dv, lane);
+    if (lane == 0) a.sp_idx[o] = first ? node : 0;
+  } else if (node >= 0 && node < a.M) {              // (the row list is checked and clamped upstream: never false there)
+    row_store(s, a.dE + node * a.dv, a.dv, lane);
+  }
 }
 
 // ---------------------------------------------------------------- BatchNorm1d + tanh over x [R, H] (MLPLayers: Linear -> BN -> Tanh)
@@ -243,20 +303,26 @@ __global__ void __launch_bounds__(256) mf_bn_tanh_eval_kernel(BnArgs a) {
 
 using namespace pxr;
 
-extern "C" int pxr_mf_pair_fwd_f32(const float* ufeat, const float* ifeat, const int64_t* rows, int H, int B, float* coef,
-                                   float* lossrow, float* loss, void* stream) {
-  PXR_REQUIRE(ufeat && ifeat && coef && lossrow && loss, "pxr_mf_pair_fwd_f32: null pointer");
-  PXR_REQUIRE(H > 0 && H % 4 == 0 && H <= 4096, "pxr_mf_pair_fwd_f32: need H %% 4 == 0 and 0 < H <= 4096 (H=%d)", H);
-  PXR_REQUIRE(B > 0 && B <= (1 << 28), "pxr_mf_pair_fwd_f32: bad batch size %d", B);
-  PXR_REQUIRE((((uintptr_t)ufeat | (uintptr_t)ifeat) & 15) == 0, "pxr_mf_pair_fwd_f32: features must be 16-byte aligned");
+extern "C" int pxr_mf_pair_fwd_eps_f32(const float* ufeat, const float* ifeat, const int64_t* rows, int H, int B, float eps,
+                                       float* coef, float* lossrow, float* loss, void* stream) {
+  PXR_REQUIRE(ufeat && ifeat && coef && lossrow && loss, "pxr_mf_pair_fwd_eps_f32: null pointer");
+  PXR_REQUIRE(H > 0 && H % 4 == 0 && H <= 4096, "pxr_mf_pair_fwd_eps_f32: need H %% 4 == 0 and 0 < H <= 4096 (H=%d)", H);
+  PXR_REQUIRE(B > 0 && B <= (1 << 28), "pxr_mf_pair_fwd_eps_f32: bad batch size %d", B);
+  PXR_REQUIRE(eps >= 0.f && eps < INFINITY, "pxr_mf_pair_fwd_eps_f32: eps must be finite and >= 0");
+  PXR_REQUIRE((((uintptr_t)ufeat | (uintptr_t)ifeat) & 15) == 0, "pxr_mf_pair_fwd_eps_f32: features must be 16-byte aligned");
   MfPairArgs a{};
   a.ufeat = (const f32x4*)ufeat; a.ifeat = (const f32x4*)ifeat; a.rows = rows; a.hv = H / 4; a.B = B;
-  a.coef = coef; a.lossrow = lossrow;
+  a.coef = coef; a.lossrow = lossrow; a.eps = eps;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(mf_pair_fwd_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a);
-  const int rc = pxr_check_launch("pxr_mf_pair_fwd_f32");
+  const int rc = pxr_check_launch("pxr_mf_pair_fwd_eps_f32");
   if (rc) return rc;
   return pxr_bpr_loss_reduce(lossrow, B, 1, loss, stream);        // loss = (1/B) sum_b lossrow[b], fixed order
+}
+
+extern "C" int pxr_mf_pair_fwd_f32(const float* ufeat, const float* ifeat, const int64_t* rows, int H, int B, float* coef,
+                                   float* lossrow, float* loss, void* stream) {
+  return pxr_mf_pair_fwd_eps_f32(ufeat, ifeat, rows, H, B, 1e-8f, coef, lossrow, loss, stream);
 }
 
 extern "C" int pxr_mf_pair_bwd_f32(const float* ufeat, const float* ifeat, const float* coef, int H, int B, float grad_scale,
@@ -291,6 +357,34 @@ extern "C" int pxr_mf_table_grad_f32(const float* table, int64_t n_table, int D,
                        (hipStream_t)stream, a);
   });
   return pxr_check_launch("pxr_mf_table_grad_f32");
+}
+
+extern "C" int pxr_momf_pair_grad_f32(const float* utable, int64_t n_utable, const float* E, int64_t M, int D, const int64_t* rows,
+                                      int B, const float* coef, const float* occ, float grad_scale, const float* grad_scale_dev,
+                                      int64_t* sp_idx, float* sp_rows, int32_t* sp_n, int64_t cap, float* dE, void* stream) {
+  PXR_REQUIRE(rows && sp_idx && sp_rows && sp_n && dE, "pxr_momf_pair_grad_f32: null pointer");
+  PXR_REQUIRE(occ || (utable && E && coef), "pxr_momf_pair_grad_f32: need occ, or utable, E and coef");
+  PXR_REQUIRE(D > 0 && D % 4 == 0 && D <= 4096, "pxr_momf_pair_grad_f32: need D %% 4 == 0 and 0 < D <= 4096 (D=%d)", D);
+  PXR_REQUIRE(B > 0 && B <= (1 << 28) / 3, "pxr_momf_pair_grad_f32: bad batch size %d", B);
+  PXR_REQUIRE(cap >= (int64_t)B, "pxr_momf_pair_grad_f32: sparse capacity %lld < B = %d", (long long)cap, B);
+  PXR_REQUIRE(M > 0 && M < (1ll << 40), "pxr_momf_pair_grad_f32: bad number of encoder rows %lld", (long long)M);
+  PXR_REQUIRE(occ || n_utable > 1, "pxr_momf_pair_grad_f32: bad user table size");
+  PXR_REQUIRE((((uintptr_t)utable | (uintptr_t)E | (uintptr_t)occ | (uintptr_t)sp_rows | (uintptr_t)dE) & 15) == 0,
+              "pxr_momf_pair_grad_f32: operands must be 16-byte aligned");
+  PXR_REQUIRE(dE != E && dE != occ && dE != utable && dE != sp_rows, "pxr_momf_pair_grad_f32: dE must not alias an operand");
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(dE, 0, (size_t)M * (size_t)D * sizeof(float), st) != hipSuccess) {      // rows nobody reads: +0.0
+    pxr_set_error("pxr_momf_pair_grad_f32: memset failed");
+    return PXR_ERR_LAUNCH;
+  }
+  MomfGradArgs a{};
+  a.utable = (const f32x4*)utable; a.E = (const f32x4*)E; a.rows = rows; a.coef = coef; a.occ = (const f32x4*)occ;
+  a.dv = D / 4; a.B = B; a.M = M; a.gscale = grad_scale; a.gscale_dev = grad_scale_dev;
+  a.sp_idx = sp_idx; a.sp_rows = (f32x4*)sp_rows; a.sp_n = sp_n; a.dE = (f32x4*)dE;
+  dispatch_ch<16>(a.dv, [&](auto ch) {
+    hipLaunchKernelGGL(momf_pair_grad_kernel<decltype(ch)::value>, dim3((unsigned)((3 * B + 3) / 4)), dim3(256), 0, st, a);
+  });
+  return pxr_check_launch("pxr_momf_pair_grad_f32");
 }
 
 static int mf_bn_shape_ok(const char* who, int R, int H) {

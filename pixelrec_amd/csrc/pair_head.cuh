@@ -38,14 +38,18 @@ __device__ __forceinline__ float dot4(const f32x4& p, const f32x4& q) { return p
 // value is finite for any |x|.
 //   log outside: lossrow = -(1e-8 + log sigmoid(x)), coef = -(1 - sigmoid(x)) / B -- mf.py, lightgcn.py:70-78 and srgnn.py:60-66 add
 //     the 1e-8 OUTSIDE the log, where it shifts the loss and leaves the gradient alone; log sigmoid(x) = min(x, 0) - log1p(e).
+//     The shift is the argument eps of the five-argument form (momf.py:59 has none: eps = 0).
 //   log inside: lossrow = -log(1e-8 + sigmoid(x)), coef = -sigmoid(x)(1 - sigmoid(x)) / (1e-8 + sigmoid(x)) / B -- vbpr.py and
 //     curatornet.py:86-88 add it INSIDE, so a badly ranked pair saturates at -log(1e-8) and its gradient fades.
-__device__ __forceinline__ void bpr_tail_log_outside(float x, int B, float& lossrow, float& coef) {
+__device__ __forceinline__ void bpr_tail_log_outside(float x, int B, float eps, float& lossrow, float& coef) {
   const float e = expf(-fabsf(x));
   const float ls = fminf(x, 0.f) - log1pf(e);
   const float sneg = x >= 0.f ? e / (1.f + e) : 1.f / (1.f + e);
-  lossrow = -(1e-8f + ls);
+  lossrow = -(eps + ls);
   coef = -sneg / (float)B;
+}
+__device__ __forceinline__ void bpr_tail_log_outside(float x, int B, float& lossrow, float& coef) {
+  bpr_tail_log_outside(x, B, 1e-8f, lossrow, coef);
 }
 __device__ __forceinline__ void bpr_tail_log_inside(float x, int B, float& lossrow, float& coef) {
   const float e = expf(-fabsf(x));

@@ -529,6 +529,30 @@ class PairTrainBatcher(TrainBatcher):
         return user, np.stack((self.items[rows], neg), axis=1)
 
 
+def positions_into_distinct_items(item):
+    """item [B, 2] item ids (positive, negative) -> (index int64 [B, 2], image_ids int64 [M]): image_ids the batch's distinct item
+    ids, ascending, WITHOUT a zero image in front (a pair model has no padding position); `index` holds positions into image_ids,
+    base 0, so image_ids[index] == item."""
+    image_ids, index = np.unique(item, return_inverse=True)
+    return index.reshape(item.shape).astype(np.int64), image_ids.astype(np.int64)
+
+
+class MoPairTrainBatcher(PairTrainBatcher):
+    """Vectorised MOPairTrainDataset (reference REC/data/dataset/trainset.py:202; REC/data/utils.py:42 maps MOMF to it) for MOMF:
+    PairTrainBatcher's batches -- the same users, positives, negatives and random stream -- with the items as positions into the
+    batch's distinct images.
+
+    Yields (user int64 [B], index int64 [B, 2], image_ids int64 [M]): image_ids[index] is PairTrainBatcher's `item`; image_ids is
+    the batch's distinct item ids, ascending, M <= 2B.  There is no zero image in front: MOMF has no padding position, and a
+    33rd image at B = 16 would be 3 % more tower work for a row nothing reads.  The reference stacks one image per (sample,
+    positive | negative), 2B per batch; here each distinct image is fetched and encoded once."""
+
+    def make_batch(self, rows, rng):
+        user, item = super().make_batch(rows, rng)
+        index, image_ids = positions_into_distinct_items(item)
+        return user, index, image_ids
+
+
 class GraphTrainBatcher(TrainBatcher):
     """Vectorised GraphTrainDataset (reference REC/data/dataset/trainset.py:939-981): one sample per AUGSEQ prefix
     (Data._build_aug_seq), yielded as whole (item_seq int64 [B, L], mask int64 [B, L], target int64 [B, 2]) batches.  item_seq =

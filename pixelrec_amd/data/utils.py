@@ -14,7 +14,7 @@ from torch.utils.data import DataLoader
 
 from ..parallel import world_info
 from .dataload import Data
-from .dataset import (AcfEvalBatcher, BERT4RecTrainBatcher, CuratorTrainBatcher, DinTrainBatcher, GraphEvalBatcher, GraphTrainBatcher, MoBert4RecTrainBatcher, MoGraphTrainBatcher, MoPoolTrainBatcher, MoTowerTrainBatcher, PairEvalBatcher, PairTrainBatcher, SeqEvalBatcher,
+from .dataset import (AcfEvalBatcher, BERT4RecTrainBatcher, CuratorTrainBatcher, DinTrainBatcher, GraphEvalBatcher, GraphTrainBatcher, MoBert4RecTrainBatcher, MoGraphTrainBatcher, MoPairTrainBatcher, MoPoolTrainBatcher, MoTowerTrainBatcher, PairEvalBatcher, PairTrainBatcher, SeqEvalBatcher,
                       SampleAcfTrainBatcher, SeqEvalDataset, SeqTrainBatcher, TwoTowerTrainBatcher, VisRankEvalBatcher, _NoTraining,
                       seq_eval_collate)
 
@@ -22,7 +22,7 @@ SUPPORTED = {"SASRec": "SEQ", "MOSASRec": "SEQ", "FSASRec": "SEQ", "GRU4Rec": "S
              "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR", "MF": "PAIR", "VBPR": "PAIR",
              "SRGNN": "AUGSEQ", "LightSANs": "TWOTOWER", "ACF": "SEQ", "VISRANK": "EVALONLY", "CuratorNet": "SEQ", "DIN": "SEQ",
              "DSSM": "SEQ", "FM": "SEQ", "WideDeep": "SEQ", "MODSSM": "SEQ", "MOFM": "SEQ",
-             "MODIN": "SEQ", "MOBERT4Rec": "SEQ", "MOSRGNN": "AUGSEQ"}      # REC/data/utils.py:24-33
+             "MODIN": "SEQ", "MOBERT4Rec": "SEQ", "MOSRGNN": "AUGSEQ", "MOMF": "PAIR"}      # REC/data/utils.py:24-33
 
 
 def load_data(config):
@@ -97,6 +97,7 @@ LOADERS = {
     "MODIN": _seq_eval(MoTowerTrainBatcher),                           # :44 MOTwoTowerTrainDataset: CuratorNet's samples
     "MOBERT4Rec": _seq_eval(MoBert4RecTrainBatcher),                   # :48 MOBERT4RecTrainDataset: BERT4Rec's masked windows
     "MOSRGNN": (MoGraphTrainBatcher, GraphEvalBatcher, _TrainLoader),  # :47 MOGraphTrainDataset: SRGNN's AUGSEQ prefixes
+    "MOMF": (MoPairTrainBatcher, PairEvalBatcher, _TrainLoader),       # MOPairTrainDataset / PairEvalDataset: MF's pairs, users scored
 }                                                                      # MO*: as positions into the batch's distinct images
 assert LOADERS.keys() == SUPPORTED.keys()
 

@@ -155,8 +155,10 @@ _SIGNATURES = {
     "pxr_lightsans_pos_bwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "pxr_table_rows_i64": (_I, [_P, _I, _P, _P, _P]),
     "pxr_mf_pair_fwd_f32": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "pxr_mf_pair_fwd_eps_f32": (_I, [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P]),
     "pxr_mf_pair_bwd_f32": (_I, [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P]),
     "pxr_mf_table_grad_f32": (_I, [_P, _I64, _I, _P, _I, _P, _P, _F, _P, _P, _P, _P, _I64, _P]),
+    "pxr_momf_pair_grad_f32": (_I, [_P, _I64, _P, _I64, _I, _P, _I, _P, _P, _F, _P, _P, _P, _P, _I64, _P, _P]),
     "pxr_mf_bn_tanh_fwd_f32": (_I, [_P, _I, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
     "pxr_mf_bn_tanh_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "pxr_mf_bn_tanh_eval_f32": (_I, [_P, _I64, _I, _P, _P, _P, _P, _F, _P, _P]),

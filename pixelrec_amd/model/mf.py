@@ -51,12 +51,13 @@ class _MLP(nn.Module):
         return [(m[4 * k + 1], m[4 * k + 2]) for k in range(len(m) // 4)]
 
 
-class MF(LazyTableModel):
-    input_type = InputType.PAIR
+class MfTowers:
+    """Mixin: the two MLPLayers towers of the pair models on a lazy table (MF, and MOMF of momf.py) -- their construction and
+    init, their tensors in PxrAdamW's flat buffer, the BatchNorm buffers a step advances, and the tower forward and backward on
+    the kernels of csrc/mf.hip.  The host class is a PackedModel; its tables, head and step are its own."""
 
-    def __init__(self, config, dataload):
-        super().__init__()
-        one_process(self)
+    def _build_towers(self, config):
+        """The config's three keys, the width checks and the two `_MLP`s (registered in the reference's order: user, item)."""
         self.embedding_size = int(config["embedding_size"])
         self.mlp_hidden_size = hidden_sizes(config["mlp_hidden_size"])
         self.dropout_prob = float(config["dropout_prob"] or 0.0)
@@ -66,22 +67,24 @@ class MF(LazyTableModel):
         if any(h % 4 or h <= 0 or h > 4096 for h in self.mlp_hidden_size):
             raise ValueError("every mlp_hidden_size entry must be a positive multiple of 4, at most 4096 (16-byte vector accesses)")
         self.out_size = self.mlp_hidden_size[-1] if self.mlp_hidden_size else D
-        self.user_num = dataload.user_num
-        self.item_num = dataload.item_num
         sizes = [D] + self.mlp_hidden_size
         self.user_mlp_layers = _MLP(sizes, self.dropout_prob)
         self.item_mlp_layers = _MLP(sizes, self.dropout_prob)
-        self.user_embedding = _Rows(self.user_num, D)
-        self.item_embedding = _Rows(self.item_num, D)
-        for mod in self.modules():                          # mf.py _init_weights, in module order
+        s = config["seed"] if "seed" in config else None
+        self._drop_seed = int(s) if s is not None else 2020
+
+    def _init_linears(self):
+        """_init_weights on the Linears, in module order (xavier-normal weights, zero biases)."""
+        for mod in self.modules():
             if isinstance(mod, nn.Linear):
                 nn.init.xavier_normal_(mod.weight.data)
                 nn.init.constant_(mod.bias.data, 0)
-        nn.init.xavier_normal_(self.user_embedding.weight)
-        nn.init.xavier_normal_(self.item_embedding.weight)
-        s = config["seed"] if "seed" in config else None
-        self._drop_seed = int(s) if s is not None else 2020
-        self.store_ifeatures = None
+
+    def _check_tower_batch(self, B):
+        """BatchNorm1d's own refusal of a one-row training batch."""
+        if self.mlp_hidden_size and B == 1:
+            raise ValueError("Expected more than 1 value per channel when training, got input size torch.Size([1, %d])"
+                             % self.mlp_hidden_size[0])
 
     # ------------------------------------------------------------------------------------------ packing
     def _flat_specs(self):
@@ -92,9 +95,8 @@ class MF(LazyTableModel):
                 out += [(f"{tag}{k}.w", lin.weight), (f"{tag}{k}.b", lin.bias), (f"{tag}{k}.g", bn.weight), (f"{tag}{k}.beta", bn.bias)]
         return out
 
-    def rec_parameter_names(self):
-        """{reference parameter name: flat-buffer key} in the reference's registration order (optim.native_to_torch_state); the
-        tables map to None -- their state is the table's (optim.table_spans)."""
+    def _tower_parameter_names(self):
+        """{reference parameter name: flat-buffer key} of the tower tensors in the reference's registration order."""
         out = {}
         for tag, pre in (("u", "user_mlp_layers.mlp_layers."), ("i", "item_mlp_layers.mlp_layers.")):
             for k in range(len(self.mlp_hidden_size)):
@@ -102,14 +104,7 @@ class MF(LazyTableModel):
                 out[f"{pre}{4 * k + 1}.bias"] = f"{tag}{k}.b"
                 out[f"{pre}{4 * k + 2}.weight"] = f"{tag}{k}.g"
                 out[f"{pre}{4 * k + 2}.bias"] = f"{tag}{k}.beta"
-        out["user_embedding.weight"] = None
-        out["item_embedding.weight"] = None
         return out
-
-    def table_parameter_spans(self):
-        """Rows of the table buffer each table parameter occupies (optim.table_spans), in the reference's order."""
-        U = self.user_num
-        return {"user_embedding.weight": (1, 1 + U), "item_embedding.weight": (1 + U, 1 + U + self.item_num)}
 
     def running_state_buffers(self):
         """The BatchNorm buffers a training step advances on the device (GraphedTrainStep's dry run restores them)."""
@@ -134,15 +129,17 @@ class MF(LazyTableModel):
             x = y
         return x, saved
 
-    def _tower_bwd(self, tag, dy, saved, sid0, dx_out, problems):
+    def _tower_bwd(self, tag, dy, saved, sid0, dx_out, problems, bias_grad=True):
         """Backward of _tower_fwd from dy [R, H]: the input gradient goes to dx_out [R, D]; the weight gradients are appended to
-        `problems` (one grouped launch for both towers)."""
+        `problems` (one grouped launch for both towers).  bias_grad=False leaves the Linear biases' gradient at the exact zero it
+        is in exact arithmetic -- the batch mean of the BatchNorm behind every Linear removes the bias -- instead of the column sums'
+        rounding noise (MF keeps the sums: its trajectories are pinned bit for bit)."""
         p = self.dropout_prob
         for k in reversed(range(len(saved))):
             xin, z, y, mean, rstd = saved[k]
             dz = ops.mf_bn_tanh_bwd(dy, z, y, mean, rstd, self._p(f"{tag}{k}.g"), self._p(f"{tag}{k}.g", grad=True),
                                     self._p(f"{tag}{k}.beta", grad=True))
-            problems.append((dz, xin, self._p(f"{tag}{k}.w", grad=True), self._p(f"{tag}{k}.b", grad=True)))
+            problems.append((dz, xin, self._p(f"{tag}{k}.w", grad=True), self._p(f"{tag}{k}.b", grad=True) if bias_grad else None))
             W = self._p(f"{tag}{k}.w")
             if k == 0 and p == 0:
                 ops.linear_bwd_input(dz, W, out=dx_out)
@@ -155,6 +152,38 @@ class MF(LazyTableModel):
                 return
             dy = dx
 
+
+class MF(MfTowers, LazyTableModel):
+    input_type = InputType.PAIR
+
+    def __init__(self, config, dataload):
+        super().__init__()
+        one_process(self)
+        self.user_num = dataload.user_num
+        self.item_num = dataload.item_num
+        self._build_towers(config)
+        D = self.embedding_size
+        self.user_embedding = _Rows(self.user_num, D)
+        self.item_embedding = _Rows(self.item_num, D)
+        self._init_linears()                                # mf.py _init_weights, in module order
+        nn.init.xavier_normal_(self.user_embedding.weight)
+        nn.init.xavier_normal_(self.item_embedding.weight)
+        self.store_ifeatures = None
+
+    # ------------------------------------------------------------------------------------------ packing
+    def rec_parameter_names(self):
+        """{reference parameter name: flat-buffer key} in the reference's registration order (optim.native_to_torch_state); the
+        tables map to None -- their state is the table's (optim.table_spans)."""
+        out = self._tower_parameter_names()
+        out["user_embedding.weight"] = None
+        out["item_embedding.weight"] = None
+        return out
+
+    def table_parameter_spans(self):
+        """Rows of the table buffer each table parameter occupies (optim.table_spans), in the reference's order."""
+        U = self.user_num
+        return {"user_embedding.weight": (1, 1 + U), "item_embedding.weight": (1 + U, 1 + U + self.item_num)}
+
     # ------------------------------------------------------------------------------------------ training
     def forward(self, input):
         user, item = input
@@ -162,9 +191,7 @@ class MF(LazyTableModel):
             raise PxrError("MF.forward is the training loss (mf.py forward); use compute_item_all / predict to score")
         self._ensure_packed()
         user, item = user.reshape(-1).contiguous(), item.contiguous()
-        if self.mlp_hidden_size and user.numel() == 1:
-            raise ValueError("Expected more than 1 value per channel when training, got input size torch.Size([1, %d])"
-                             % self.mlp_hidden_size[0])
+        self._check_tower_batch(user.numel())
         return TrainStep.apply(self._anchor, self, user, item)
 
     def _forward_train(self, user, item):

@@ -2238,9 +2238,11 @@ def mf_pair_rows(user, item, n_users: int, n_items: int, out=None):
                        (3 * B if item is not None else B,))
 
 
-def mf_pair_fwd(ufeat, ifeat, B: int, rows=None, out=None):
-    """MF's pair loss head (mf.py forward).  rows given: u / i+- read from the table ufeat (= ifeat) at rows [3B]; else ufeat [B, H],
-    ifeat [2B, H] (tower outputs).  -> (loss [1], coef [B] = d loss / d x_b).  out: a float32 [2B + 1] buffer to reuse."""
+def mf_pair_fwd(ufeat, ifeat, B: int, rows=None, out=None, eps=1e-8):
+    """MF's pair loss head (mf.py forward; pxr_mf_pair_fwd_eps_f32).  rows given: u read from ufeat at rows[:B] and i+- from ifeat at
+    rows[B:] (MF: both the one table; MOMF: the user table and the encoder's output); else ufeat [B, H], ifeat [2B, H] (tower
+    outputs).  eps: the shift outside the log, 1e-8 in mf.py and 0 in momf.py.  -> (loss [1], coef [B] = d loss / d x_b).  out: a
+    float32 [2B + 1] buffer to reuse."""
     Lb = _l.load()
     _req(ufeat, torch.float32, "ufeat"); _req(ifeat, torch.float32, "ifeat")
     H = ufeat.shape[-1]
@@ -2254,8 +2256,8 @@ def mf_pair_fwd(ufeat, ifeat, B: int, rows=None, out=None):
             raise _l.PxrError(f"mf pair head: rows must be [3B] for B={B}")
     f = out if out is not None else torch.empty(2 * B + 1, dtype=torch.float32, device=ufeat.device)
     coef, lossrow, loss = f[:B], f[B:2 * B], f[2 * B:]
-    _l.check(Lb.pxr_mf_pair_fwd_f32(_l.ptr(ufeat), _l.ptr(ifeat), _l.ptr(rows), H, B, _l.ptr(coef), _l.ptr(lossrow), _l.ptr(loss),
-                                    _l.stream_ptr()), "pxr_mf_pair_fwd_f32")
+    _l.check(Lb.pxr_mf_pair_fwd_eps_f32(_l.ptr(ufeat), _l.ptr(ifeat), _l.ptr(rows), H, B, float(eps), _l.ptr(coef), _l.ptr(lossrow),
+                                        _l.ptr(loss), _l.stream_ptr()), "pxr_mf_pair_fwd_eps_f32")
     return loss, coef
 
 
@@ -2293,6 +2295,47 @@ def mf_table_grad(rows, B: int, sp: SparseRows, table=None, coef=None, occ=None,
                                       _l.ptr(grad_scale_dev), _l.ptr(sp.idx), _l.ptr(sp.rows), _l.ptr(sp.n), sp.cap,
                                       _l.stream_ptr()), "pxr_mf_table_grad_f32")
     return sp
+
+
+def momf_pair_rows(user, index, n_users: int, n_rows: int, out=None):
+    """user int64 [B], index int64 [B, 2] positions into the encoder's output [n_rows, D] -> rows int64 [3B] = [1 + user |
+    index.view(-1)] (position base 0: MOMF has no padding position).  Bad ids flag the status word and are clamped."""
+    B = user.numel()
+    _pair_items("momf pair rows", index, B)
+    return _table_rows("momf pair rows", [("user", user, n_users, 1, 0), ("index", index, n_rows, 0, 0)], out, (3 * B,))
+
+
+def momf_pair_grad(rows, B: int, sp: SparseRows, n_rows: int, utable=None, E=None, coef=None, occ=None, grad_scale=1.0,
+                   grad_scale_dev=None, out=None):
+    """MOMF's backward into its two row spaces (pxr_momf_pair_grad_f32): the user rows' gradient as sparse rows in sp (cap >= B,
+    count B) and d loss / d E as a dense [n_rows, D] block (`out` or a new tensor; zeroed by the entry), from the head's formula on
+    `utable`, `E` and `coef`, or from the per-occurrence rows occ [3B, D].  -> dE."""
+    Lb = _l.load()
+    _req(rows, torch.int64, "rows")
+    if rows.numel() != 3 * B:
+        raise _l.PxrError(f"momf pair grad: rows must be [3B] for B={B}")
+    D = sp.rows.shape[1]
+    if sp.cap < B:
+        raise _l.PxrError(f"momf pair grad: the sparse rows hold {sp.cap} slots, B={B}")
+    n_utable = 0
+    if occ is not None:
+        _req(occ, torch.float32, "occ")
+        if occ.shape != (3 * B, D):
+            raise _l.PxrError(f"momf pair grad: occ must be [3B, D] = [{3 * B}, {D}], got {tuple(occ.shape)}")
+        utable = E = coef = None
+    else:
+        _req(utable, torch.float32, "utable"); _req(E, torch.float32, "E"); _req(coef, torch.float32, "coef")
+        if utable.dim() != 2 or utable.shape[1] != D or tuple(E.shape) != (n_rows, D) or coef.numel() != B:
+            raise _l.PxrError(f"momf pair grad: need utable [*, {D}], E [{n_rows}, {D}] and coef [{B}]")
+        n_utable = utable.shape[0]
+    dE = out if out is not None else torch.empty(n_rows, D, dtype=torch.float32, device=rows.device)
+    _req(dE, torch.float32, "dE")
+    if tuple(dE.shape) != (n_rows, D):
+        raise _l.PxrError(f"momf pair grad: dE must be [{n_rows}, {D}], got {tuple(dE.shape)}")
+    _l.check(Lb.pxr_momf_pair_grad_f32(_l.ptr(utable), n_utable, _l.ptr(E), n_rows, D, _l.ptr(rows), B, _l.ptr(coef), _l.ptr(occ),
+                                       float(grad_scale), _l.ptr(grad_scale_dev), _l.ptr(sp.idx), _l.ptr(sp.rows), _l.ptr(sp.n),
+                                       sp.cap, _l.ptr(dE), _l.stream_ptr()), "pxr_momf_pair_grad_f32")
+    return dE
 
 
 def mf_bn_tanh_fwd(x, gamma, beta, running_mean, running_var, num_batches_tracked, eps=1e-5, momentum=0.1, y=None, stats=None):
