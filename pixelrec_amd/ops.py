@@ -375,15 +375,16 @@ def linear_epi(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor, epi: int, aux:
 
 
 def gemm_batched(a_kc: bool, b_kc: bool, M: int, N: int, K: int, A, a_off, lda, B, b_off, ldb, C, c_off, ldc, batch, nb2,
-                 a12, b12, c12):
+                 a12, b12, c12, tile_hint=0):
     """`batch` GEMMs in one launch (pxr_gemm_batched_f32).  A/B/C are tensors, *_off element offsets of problem 0,
-    x12 = (stride1, stride2) in elements for the two batch levels (z // nb2, z % nb2)."""
+    x12 = (stride1, stride2) in elements for the two batch levels (z // nb2, z % nb2).  tile_hint: 0 = the mode's default
+    tile (bf16x3 64x64 / f32 64x64), otherwise a tile code of pxr_gemm_f32."""
     L = _l.load()
     cp = _l.c_void_p
     with _gemm_timer(2.0 * M * N * K * batch, "gemm_kernel (batched: attention contraction of the ViT encoder)"):
         _l.check(L.pxr_gemm_batched_f32(int(a_kc), int(b_kc), M, N, K, cp(A.data_ptr() + 4 * a_off), lda,
                                         cp(B.data_ptr() + 4 * b_off), ldb, cp(C.data_ptr() + 4 * c_off), ldc, batch, nb2,
-                                        a12[0], a12[1], b12[0], b12[1], c12[0], c12[1], 0, _l.stream_ptr()),
+                                        a12[0], a12[1], b12[0], b12[1], c12[0], c12[1], tile_hint, _l.stream_ptr()),
                  "pxr_gemm_batched_f32")
 
 

@@ -70,7 +70,7 @@ def _operand(t, off, ld, rows, cols, z, nb2, s12):
     return torch.as_strided(t.reshape(-1), (rows, cols), (ld, 1), base)
 
 
-def gemm_batched(a_kc, b_kc, M, N, K, A, a_off, lda, B, b_off, ldb, C, c_off, ldc, batch, nb2, a12, b12, c12):
+def gemm_batched(a_kc, b_kc, M, N, K, A, a_off, lda, B, b_off, ldb, C, c_off, ldc, batch, nb2, a12, b12, c12, tile_hint=0):
     for z in range(batch):
         a = _operand(A, a_off, lda, M, K, z, nb2, a12) if a_kc else _operand(A, a_off, lda, K, M, z, nb2, a12).t()
         b = _operand(B, b_off, ldb, N, K, z, nb2, b12).t() if b_kc else _operand(B, b_off, ldb, K, N, z, nb2, b12)

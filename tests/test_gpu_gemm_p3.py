@@ -7,7 +7,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-TILES = [0, 406406430, 406406431, 412806420, 406412820, 812812830, 825612820, 425612833, 425612832, 425625631]
+TILES = [0, 406406430, 406406431, 412806420, 406412820, 812812830, 825612820, 425612833, 425612832, 425625631,
+         406406461, 412806441]        # (the last two: deeper rings with early fragment reads, three accumulator sets)
 # the ping-pong tiles of gemm_p4.cuh: ...833 keeps gemm_p3's three accumulator sets (bit-identical), ...832 folds the small terms into
 # one set and ...631 (256x256) runs ONE accumulator set: same products, different rounding points -- held to the fp64 bound only
 NOT_BIT_IDENTICAL = {425612832, 425625631, 425612822}     # (...822: the weight gradient with the token reduction split in two)
