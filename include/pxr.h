@@ -256,8 +256,8 @@ int pxr_split_planes_multi_f32(int n, const float* const* x, const int64_t* rows
  * word (pxr_set_status_word) instead of silently becoming inf.  Same panel layout as the bf16 planes, planes 0 and 1.
  * Used by the forward-only blocks of the image tower (reference: the frozen CLIP blocks of code/REC/model/load.py:90-120).
  *   pxr_split_h2_multi_f32   up to 16 matrices, matrix i multiplied by 2^scale_exp[i] first
- *   pxr_gemm_h2_f32          C = epilogue(2^-(a_exp+b_exp) A~ B~), B~ [N][K] (b_kc: forward; epilogue NONE | BIAS | BIAS_GELU |
- *                            BIAS_GELU_GRAD | BIAS_ACT_GRAD | BIAS_ADD | BIAS_QGELU | BIAS_QGELU_GRAD | BIAS_RELU) or [K][N] (input gradient; NONE | ADD | MUL);
+ *   pxr_gemm_h2_f32          C = epilogue(2^-(a_exp+b_exp) A~ B~), B~ [N][K] (b_kc = 1: forward) or [K][N] (b_kc = 0: input gradient), with
+ *                            the epilogues pxr_gemm_planes_f32 takes for that flavour (one list for both: csrc/gemm_epi.cuh);
  *                            exponents immediate or read from *_exp_dev; c_fmt 0: output planes as three bf16 planes, 1: as two
  *                            fp16 planes holding C 2^(*c_exp_dev) (unit scale when null)
  *   pxr_ln_residual_fwd_f32 / pxr_input_ln_fwd_f32 / pxr_attn_fwd_f32 / pxr_tower_attn_fwd_f32 with planes_fmt 1: the

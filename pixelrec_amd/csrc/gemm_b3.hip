@@ -175,20 +175,17 @@ int gemm_b3_launch(int a_kc, int b_kc, int epilogue, int tile, const float* A, i
 #define PXR_B3(AK, BK_, E)                                                                                            \
   case E: return tile_b3<AK, BK_, E>(tile, A, lda, B, ldb, C, ldc, M, N, K, bias, aux, ldaux, splits, ksplit_len,     \
                                      split_stride, bt, batch, st)
+#define PXR_B3_FWD(E) PXR_B3(true, true, E);
+#define PXR_B3_BWD(E) PXR_B3(true, false, E);
   if (a_kc && b_kc) {
-    switch (epilogue) {
-      PXR_B3(true, true, EPI_NONE); PXR_B3(true, true, EPI_BIAS); PXR_B3(true, true, EPI_BIAS_GELU);
-      PXR_B3(true, true, EPI_BIAS_GELU_GRAD); PXR_B3(true, true, EPI_BIAS_ADD); PXR_B3(true, true, EPI_BIAS_QGELU_GRAD);
-      PXR_B3(true, true, EPI_BIAS_RELU); PXR_B3(true, true, EPI_BIAS_ACT_GRAD);
-    }
+    switch (epilogue) { PXR_EPI_FWD(PXR_B3_FWD) }
   } else if (a_kc && !b_kc) {
-    switch (epilogue) {
-      PXR_B3(true, false, EPI_NONE); PXR_B3(true, false, EPI_MUL_DGELU); PXR_B3(true, false, EPI_ADD);
-      PXR_B3(true, false, EPI_MUL);
-    }
+    switch (epilogue) { PXR_EPI_BWD_F32(PXR_B3_BWD) }
   } else if (!a_kc && !b_kc) {
     switch (epilogue) { PXR_B3(false, false, EPI_NONE); }
   }
+#undef PXR_B3_FWD
+#undef PXR_B3_BWD
 #undef PXR_B3
   pxr_set_error("pxr_gemm_f32(bf16x3): operand flavour (%d,%d) / epilogue %d is not instantiated", a_kc, b_kc, epilogue);
   return PXR_ERR_BAD_ARG;

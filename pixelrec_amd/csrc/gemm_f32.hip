@@ -448,11 +448,7 @@ extern "C" int pxr_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const float
   PXR_REQUIRE(ext_a % 4 == 0 || lda >= ((ext_a + 3) & ~3), "pxr_gemm_f32: A contiguous extent must be a multiple of 4 (or padded)");
   PXR_REQUIRE(ext_b % 4 == 0 || ldb >= ((ext_b + 3) & ~3), "pxr_gemm_f32: B contiguous extent must be a multiple of 4 (or padded)");
   PXR_REQUIRE(epilogue >= 0 && epilogue <= EPI_LAST, "pxr_gemm_f32: bad epilogue %d", epilogue);
-  PXR_REQUIRE(!(epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_GRAD ||
-                epilogue == EPI_BIAS_ADD || epilogue == EPI_BIAS_QGELU_GRAD || epilogue == EPI_BIAS_RELU ||
-                epilogue == EPI_BIAS_ACT_GRAD) || bias,
-              "pxr_gemm_f32: epilogue needs bias");
-  PXR_REQUIRE(!(epilogue >= EPI_BIAS_GELU && epilogue != EPI_BIAS_RELU) || aux, "pxr_gemm_f32: epilogue needs aux");
+  if (!epi_operands_ok("pxr_gemm_f32", epilogue, bias, aux)) return PXR_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
 
   const int64_t t128 = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
@@ -535,24 +531,16 @@ extern "C" int pxr_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const float
   rc = skw > 0 ? launch_gemm_sk<AK, BK_, E>(skw, A, lda, B, ldb, C, ldc, M, N, K, bias, aux, ldaux, st)        \
                : dispatch_tile<AK, BK_, E>(tile, A, lda, B, ldb, Cw, ldcw, M, N, K, bias, aux, ldaux, splits, ksplit_len, \
                                            split_stride, st)
+#define PXR_GEMM_FWD(E) case E: PXR_GEMM_CASE(true, true, E); break;
+#define PXR_GEMM_BWD(E) case E: PXR_GEMM_CASE(true, false, E); break;
   if (a_kc && b_kc) {
     switch (epilogue) {
-      case EPI_NONE: PXR_GEMM_CASE(true, true, EPI_NONE); break;
-      case EPI_BIAS: PXR_GEMM_CASE(true, true, EPI_BIAS); break;
-      case EPI_BIAS_GELU: PXR_GEMM_CASE(true, true, EPI_BIAS_GELU); break;
-      case EPI_BIAS_GELU_GRAD: PXR_GEMM_CASE(true, true, EPI_BIAS_GELU_GRAD); break;
-      case EPI_BIAS_ADD: PXR_GEMM_CASE(true, true, EPI_BIAS_ADD); break;
-      case EPI_BIAS_QGELU_GRAD: PXR_GEMM_CASE(true, true, EPI_BIAS_QGELU_GRAD); break;
-      case EPI_BIAS_RELU: PXR_GEMM_CASE(true, true, EPI_BIAS_RELU); break;
-      case EPI_BIAS_ACT_GRAD: PXR_GEMM_CASE(true, true, EPI_BIAS_ACT_GRAD); break;
+      PXR_EPI_FWD(PXR_GEMM_FWD)
       default: pxr_set_error("pxr_gemm_f32: epilogue %d unsupported for (KC,KC)", epilogue); return PXR_ERR_BAD_ARG;
     }
   } else if (a_kc && !b_kc) {
     switch (epilogue) {
-      case EPI_NONE: PXR_GEMM_CASE(true, false, EPI_NONE); break;
-      case EPI_MUL_DGELU: PXR_GEMM_CASE(true, false, EPI_MUL_DGELU); break;
-      case EPI_ADD: PXR_GEMM_CASE(true, false, EPI_ADD); break;
-      case EPI_MUL: PXR_GEMM_CASE(true, false, EPI_MUL); break;
+      PXR_EPI_BWD_F32(PXR_GEMM_BWD)
       default: pxr_set_error("pxr_gemm_f32: epilogue %d unsupported for (KC,XC)", epilogue); return PXR_ERR_BAD_ARG;
     }
   } else if (!a_kc && !b_kc) {
@@ -562,6 +550,8 @@ extern "C" int pxr_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const float
     pxr_set_error("pxr_gemm_f32: (XC,KC) operand combination is not instantiated");
     return PXR_ERR_BAD_ARG;
   }
+#undef PXR_GEMM_FWD
+#undef PXR_GEMM_BWD
 #undef PXR_GEMM_CASE
   if (rc != PXR_OK) return rc;
 

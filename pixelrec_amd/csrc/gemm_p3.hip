@@ -11,66 +11,6 @@
 
 namespace pxr {
 
-// one element of the epilogues of gemm_f32.cuh::epi_store (same formulas, same order of operations)
-template <int EPI>
-__device__ __forceinline__ float p3_epi_elem(float v, float bv, float av, float& aux_out, int act) {
-  if constexpr (EPI == EPI_BIAS) {
-    v += bv;
-  } else if constexpr (EPI == EPI_BIAS_GELU) {
-    v += bv;
-    aux_out = v;
-    v = gelu_erf(v);
-  } else if constexpr (EPI == EPI_BIAS_GELU_GRAD) {
-    v += bv;
-    aux_out = dgelu_erf(v);
-    v = gelu_erf(v);
-  } else if constexpr (EPI == EPI_MUL) {
-    v *= av;
-  } else if constexpr (EPI == EPI_MUL_DGELU) {
-    v *= dgelu_erf(av);
-  } else if constexpr (EPI == EPI_ADD) {
-    v += av;
-  } else if constexpr (EPI == EPI_BIAS_ADD) {
-    v = (v + bv) + av;
-  } else if constexpr (EPI == EPI_BIAS_QGELU_GRAD) {
-    v += bv;
-    const float sg = sigmoid_1702(v);
-    aux_out = sg + 1.702f * v * sg * (1.0f - sg);
-    v = v * sg;
-  } else if constexpr (EPI == EPI_BIAS_RELU) {
-    v = fmaxf(v + bv, 0.f);
-  } else if constexpr (EPI == EPI_BIAS_QGELU) {
-    v += bv;
-    v = v * sigmoid_1702(v);
-  } else if constexpr (EPI == EPI_BIAS_ACT_GRAD) {
-    v += bv;
-    float dv;
-    if (act == ACT_RELU) {
-      dv = v > 0.f ? 1.f : 0.f; v = fmaxf(v, 0.f);
-    } else if (act == ACT_SWISH) {
-      const float sg = 1.0f / (1.0f + __expf(-v));
-      dv = sg + v * sg * (1.0f - sg); v = v * sg;
-    } else if (act == ACT_TANH) {
-      const float th = tanhf(v);
-      dv = 1.0f - th * th; v = th;
-    } else if (act == ACT_SELU) {
-      const float sa = PXR_SELU_SCALE * PXR_SELU_ALPHA, ex = __expf(fminf(v, 0.f));
-      dv = v > 0.f ? PXR_SELU_SCALE : sa * ex;
-      v = v > 0.f ? PXR_SELU_SCALE * v : sa * (ex - 1.0f);
-    } else {
-      const float sg = 1.0f / (1.0f + __expf(-v));
-      dv = sg * (1.0f - sg); v = sg;
-    }
-    aux_out = dv;
-  }
-  return v;
-}
-template <int EPI>
-struct P3EpiTraits {
-  static constexpr bool WRITES_AUX = (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_GRAD || EPI == EPI_BIAS_QGELU_GRAD ||
-                                      EPI == EPI_BIAS_ACT_GRAD);
-};
-
 struct P3Args {
   P3Mat A, B, Cp;          // Cp.p == nullptr: no output planes
   float* C;                // nullptr: the fp32 output is not stored (the consumer reads the planes)
@@ -136,21 +76,13 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_p3_kernel(const P3Args g) {
   // every register an accumulator or a fragment the compiler parked them in scratch across the loop -- a store in the prologue and
   // a dependent scratch load per chunk in the epilogue, tools/isa_resources.py: 48 / 144 B per lane in the lockstep tiles.)
   if constexpr (EpiTraits<EPI>::HAS_BIAS && PRE) {
-    if (pre_ok) {
-      const float4 b0 = *reinterpret_cast<const float4*>(g.bias + pc), b1 = *reinterpret_cast<const float4*>(g.bias + pc + 4);
-      bpre[0] = b0.x; bpre[1] = b0.y; bpre[2] = b0.z; bpre[3] = b0.w; bpre[4] = b1.x; bpre[5] = b1.y; bpre[6] = b1.z; bpre[7] = b1.w;
-    }
+    if (pre_ok) f32_load8(bpre, g.bias + pc);
   }
   if constexpr (PRE_AUX && PRE) {
 #pragma unroll
     for (int it = 0; it < Map::CPT; ++it) {
       const int row = m0 + Map::row(it);
-      if (pre_ok && row < g.M) {
-        const float* ap = g.aux + (int64_t)row * g.ldaux + pc;
-        const float4 a0 = *reinterpret_cast<const float4*>(ap), a1 = *reinterpret_cast<const float4*>(ap + 4);
-        apre[it][0] = a0.x; apre[it][1] = a0.y; apre[it][2] = a0.z; apre[it][3] = a0.w;
-        apre[it][4] = a1.x; apre[it][5] = a1.y; apre[it][6] = a1.z; apre[it][7] = a1.w;
-      }
+      if (pre_ok && row < g.M) f32_load8(apre[it], g.aux + (int64_t)row * g.ldaux + pc);
     }
   }
   float c_scale = 1.0f;
@@ -184,8 +116,7 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_p3_kernel(const P3Args g) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) av[e] = apre[it][e];
         } else {
-          const float4 a0 = *reinterpret_cast<const float4*>(ap), a1 = *reinterpret_cast<const float4*>(ap + 4);
-          av[0] = a0.x; av[1] = a0.y; av[2] = a0.z; av[3] = a0.w; av[4] = a1.x; av[5] = a1.y; av[6] = a1.z; av[7] = a1.w;
+          f32_load8(av, ap);      // (the ping-pong tiles with many chunks per thread: read chunk by chunk)
         }
       } else {
 #pragma unroll
@@ -194,13 +125,12 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_p3_kernel(const P3Args g) {
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e)
-      v[e] = p3_epi_elem<EPI>(v[e], EpiTraits<EPI>::HAS_BIAS ? bv[e] : 0.f, EpiTraits<EPI>::READS_AUX ? av[e] : 0.f, ao[e], g.act);
+      v[e] = epi_elem<EPI>(v[e], EpiTraits<EPI>::HAS_BIAS ? bv[e] : 0.f, EpiTraits<EPI>::READS_AUX ? av[e] : 0.f, ao[e], g.act);
     if (g.dbg & 16) return;        // LAB: the epilogue's arithmetic and LDS trip, none of its stores
-    if constexpr (P3EpiTraits<EPI>::WRITES_AUX) {
+    if constexpr (EpiTraits<EPI>::WRITES_AUX) {
       float* ap = g.aux + (int64_t)row * g.ldaux + col;
       if (vec) {
-        *reinterpret_cast<float4*>(ap) = make_float4(ao[0], ao[1], ao[2], ao[3]);
-        *reinterpret_cast<float4*>(ap + 4) = make_float4(ao[4], ao[5], ao[6], ao[7]);
+        f32_store8(ap, ao);
       } else {
 #pragma unroll
         for (int e = 0; e < 8; ++e)
@@ -210,8 +140,7 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_p3_kernel(const P3Args g) {
     if (g.C != nullptr) {
       float* cp = g.C + (int64_t)row * g.ldc + col;
       if (vec) {
-        *reinterpret_cast<float4*>(cp) = make_float4(v[0], v[1], v[2], v[3]);
-        *reinterpret_cast<float4*>(cp + 4) = make_float4(v[4], v[5], v[6], v[7]);
+        f32_store8(cp, v);
       } else {
 #pragma unroll
         for (int e = 0; e < 8; ++e)
@@ -231,17 +160,9 @@ __global__ void __launch_bounds__(Cfg::NT) gemm_p3_kernel(const P3Args g) {
                          [&](int it, int row, int col, int nv) {
                            if (!(vec_ok && nv == 8)) return;
                            if constexpr (EpiTraits<EPI>::HAS_BIAS) {
-                             if (it == 0) {          // the thread's column chunk is the same for all its rows of a pass
-                               const float4 b0 = *reinterpret_cast<const float4*>(g.bias + col), b1 = *reinterpret_cast<const float4*>(g.bias + col + 4);
-                               bpre[0] = b0.x; bpre[1] = b0.y; bpre[2] = b0.z; bpre[3] = b0.w; bpre[4] = b1.x; bpre[5] = b1.y; bpre[6] = b1.z; bpre[7] = b1.w;
-                             }
+                             if (it == 0) f32_load8(bpre, g.bias + col);   // the thread's column chunk is the same for all its rows of a pass
                            }
-                           if constexpr (PRE_AUX) {
-                             const float* ap = g.aux + (int64_t)row * g.ldaux + col;
-                             const float4 a0 = *reinterpret_cast<const float4*>(ap), a1 = *reinterpret_cast<const float4*>(ap + 4);
-                             apre[it][0] = a0.x; apre[it][1] = a0.y; apre[it][2] = a0.z; apre[it][3] = a0.w;
-                             apre[it][4] = a1.x; apre[it][5] = a1.y; apre[it][6] = a1.z; apre[it][7] = a1.w;
-                           }
+                           if constexpr (PRE_AUX) f32_load8(apre[it], g.aux + (int64_t)row * g.ldaux + col);
                          },
                          chunk);
   } else {
@@ -534,50 +455,93 @@ static int launch_p3(P3Args& g, hipStream_t st) {
   return pxr_check_launch("pxr_gemm_planes_f32");
 }
 
+// the flavours of the planes and the fp16 two-plane GEMM: forward (weights k-contiguous) and input gradient (weights x-contiguous);
+// `who` = the entry point, for the error text
 template <class Cfg, bool EARLY>
-static int epi_p3(int b_kc, int epilogue, P3Args& g, hipStream_t st) {
-#define PXR_P3(BK_, E) \
-  case E: return launch_p3<Cfg, BK_, E, EARLY>(g, st)
+static int epi_p3(const char* who, int b_kc, int epilogue, P3Args& g, hipStream_t st) {
+#define PXR_P3_FWD(E) case E: return launch_p3<Cfg, true, E, EARLY>(g, st);
+#define PXR_P3_BWD(E) case E: return launch_p3<Cfg, false, E, EARLY>(g, st);
   if (b_kc) {
-    switch (epilogue) {
-      PXR_P3(true, EPI_NONE); PXR_P3(true, EPI_BIAS); PXR_P3(true, EPI_BIAS_GELU); PXR_P3(true, EPI_BIAS_GELU_GRAD);
-      PXR_P3(true, EPI_BIAS_ACT_GRAD); PXR_P3(true, EPI_BIAS_ADD); PXR_P3(true, EPI_BIAS_QGELU); PXR_P3(true, EPI_BIAS_QGELU_GRAD);
-      PXR_P3(true, EPI_BIAS_RELU);
-    }
+    switch (epilogue) { PXR_EPI_FWD_PLANES(PXR_P3_FWD) }
   } else {
-    switch (epilogue) {
-      PXR_P3(false, EPI_NONE); PXR_P3(false, EPI_ADD); PXR_P3(false, EPI_MUL);
-    }
+    switch (epilogue) { PXR_EPI_BWD(PXR_P3_BWD) }
   }
-#undef PXR_P3
-  pxr_set_error("pxr_gemm_planes_f32: flavour b_kc=%d / epilogue %d is not instantiated", b_kc, epilogue);
+#undef PXR_P3_FWD
+#undef PXR_P3_BWD
+  pxr_set_error("%s: flavour b_kc=%d / epilogue %d is not instantiated", who, b_kc, epilogue);
   return PXR_ERR_BAD_ARG;
 }
 
-// the flavours of the fp16 two-plane GEMM: forward (weights k-contiguous) and input gradient (weights x-contiguous)
-template <class Cfg>
-static int epi_h2(int b_kc, int epilogue, P3Args& g, hipStream_t st) {
-  if (b_kc) {
-    switch (epilogue) {
-      case EPI_NONE: return launch_p3<Cfg, true, EPI_NONE, false>(g, st);
-      case EPI_BIAS: return launch_p3<Cfg, true, EPI_BIAS, false>(g, st);
-      case EPI_BIAS_GELU: return launch_p3<Cfg, true, EPI_BIAS_GELU, false>(g, st);
-      case EPI_BIAS_GELU_GRAD: return launch_p3<Cfg, true, EPI_BIAS_GELU_GRAD, false>(g, st);
-      case EPI_BIAS_ACT_GRAD: return launch_p3<Cfg, true, EPI_BIAS_ACT_GRAD, false>(g, st);
-      case EPI_BIAS_ADD: return launch_p3<Cfg, true, EPI_BIAS_ADD, false>(g, st);
-      case EPI_BIAS_QGELU: return launch_p3<Cfg, true, EPI_BIAS_QGELU, false>(g, st);
-      case EPI_BIAS_QGELU_GRAD: return launch_p3<Cfg, true, EPI_BIAS_QGELU_GRAD, false>(g, st);
-      case EPI_BIAS_RELU: return launch_p3<Cfg, true, EPI_BIAS_RELU, false>(g, st);
-    }
-  } else {
-    switch (epilogue) {
-      case EPI_NONE: return launch_p3<Cfg, false, EPI_NONE, false>(g, st);
-      case EPI_ADD: return launch_p3<Cfg, false, EPI_ADD, false>(g, st);
-      case EPI_MUL: return launch_p3<Cfg, false, EPI_MUL, false>(g, st);
+// ---- argument checks and argument fill shared by the bf16x3 entries (planes = 3, no exponents) and the fp16 two-plane entries
+// (planes = 2, with exponents); `who` = the entry point, for the error text -------------------------------------------------------
+struct H2GemmExps {
+  int a_exp, b_exp;
+  const int* a_exp_dev;
+  const int* b_exp_dev;
+  const int* c_exp_dev;
+  int c_fmt;
+};
+static int p3_gemm_args(const char* who, int planes, const H2GemmExps* ex, P3Args& g, int b_kc, int M, int N, int K, const void* A,
+                        int64_t a_plane_stride, int64_t a_panel_rows, const void* B, int64_t b_plane_stride, int64_t b_panel_rows,
+                        float* C, int64_t ldc, int epilogue, const float* bias, float* aux, int64_t ldaux, void* c_planes,
+                        int64_t c_plane_stride, int64_t c_panel_rows, int act) {
+  PXR_REQUIRE(A && B && (C || c_planes), "%s: null operand", who);
+  PXR_REQUIRE(M >= 0 && N >= 0 && K >= 0 && K % 32 == 0, "%s: K must be a multiple of 32", who);
+  PXR_REQUIRE(b_kc || N % 32 == 0, "%s: an x-contiguous B needs N %% 32 == 0", who);
+  PXR_REQUIRE(a_panel_rows % 16 == 0 && b_panel_rows % 16 == 0 && a_plane_stride % 8 == 0 && b_plane_stride % 8 == 0,
+              "%s: panel rows must be multiples of 16, plane strides of 8 elements", who);
+  if (ex)
+    PXR_REQUIRE(a_panel_rows >= M && a_plane_stride >= a_panel_rows * K &&
+                    (b_kc ? (b_panel_rows >= N && b_plane_stride >= b_panel_rows * K) : (b_panel_rows >= K && b_plane_stride >= b_panel_rows * N)),
+                "%s: operand planes smaller than the matrices", who);
+  PXR_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)c_planes | (uintptr_t)aux | (uintptr_t)bias) & 15) == 0,
+              "%s: operands must be 16-byte aligned", who);
+  PXR_REQUIRE(a_plane_stride * 2 * planes < 0x7FFFFFF0ll && b_plane_stride * 2 * planes < 0x7FFFFFF0ll,
+              "%s: an operand's %s planes must span less than 2 GiB", who, planes == 2 ? "two" : "three");
+  PXR_REQUIRE(!c_planes || (N % 32 == 0 && c_panel_rows % 16 == 0 && c_panel_rows >= M), "%s: output planes need N %% 32 == 0", who);
+  if (ex) {
+    PXR_REQUIRE(ex->c_fmt == PXR_PLANES_BF16X3 || ex->c_fmt == PXR_PLANES_H2, "%s: c_fmt", who);
+    PXR_REQUIRE(!ex->c_exp_dev || (c_planes && ex->c_fmt == PXR_PLANES_H2), "%s: an output exponent needs h2 output planes", who);
+    PXR_REQUIRE(ex->a_exp >= -60 && ex->a_exp <= 60 && ex->b_exp >= -60 && ex->b_exp <= 60, "%s: scale exponents", who);
+  }
+  if (!epi_operands_ok(who, epilogue, bias, aux)) return PXR_ERR_BAD_ARG;
+  g.A = P3Mat{reinterpret_cast<__bf16*>(const_cast<void*>(A)), a_plane_stride, a_panel_rows};
+  g.B = P3Mat{reinterpret_cast<__bf16*>(const_cast<void*>(B)), b_plane_stride, b_panel_rows};
+  g.Cp = P3Mat{reinterpret_cast<__bf16*>(c_planes), c_plane_stride, c_panel_rows};
+  g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.bias = bias; g.aux = aux; g.ldaux = ldaux; g.act = act;
+  g.a_exp = ex ? ex->a_exp : 0; g.b_exp = ex ? ex->b_exp : 0;
+  g.a_exp_dev = ex ? ex->a_exp_dev : nullptr; g.b_exp_dev = ex ? ex->b_exp_dev : nullptr; g.c_exp_dev = ex ? ex->c_exp_dev : nullptr;
+  g.cp_fmt = ex ? ex->c_fmt : PXR_PLANES_BF16X3;
+  g.status = ex ? pxr_status_word() : nullptr;      // (the fp16 range check of h2 output planes)
+  return PXR_OK;
+}
+
+// the exponent arrays are all given (h2) or all null (bf16x3 planes)
+static int p3_dw_args(const char* who, int planes, P3DwGroup& g, int n, const void* const* dy, const int64_t* dy_plane_stride,
+                      const int64_t* dy_panel_rows, const int* dy_exp, const int* const* dy_exp_dev, const void* const* x,
+                      const int64_t* x_plane_stride, const int64_t* x_panel_rows, const int* x_exp, const int* const* x_exp_dev,
+                      float* const* dW, float* const* db, const int* T, const int* N, const int* K) {
+  const bool h2 = planes == 2;
+  PXR_REQUIRE(n >= 1 && n <= DW_MAX && dy && x && dW && db && T && N && K && dy_plane_stride && dy_panel_rows && x_plane_stride &&
+                  x_panel_rows && (!h2 || (dy_exp && x_exp && dy_exp_dev && x_exp_dev)), "%s: bad args (n=%d, max %d)", who, n, DW_MAX);
+  g.n = n;
+  for (int i = 0; i < n; ++i) {
+    PXR_REQUIRE(dy[i] && x[i] && dW[i] && T[i] > 0 && N[i] > 0 && K[i] > 0 && N[i] % 32 == 0 && K[i] % 32 == 0,
+                "%s: problem %d has a bad shape (N and K must be multiples of 32)", who, i);
+    PXR_REQUIRE(dy_panel_rows[i] % 32 == 0 && x_panel_rows[i] % 32 == 0 && dy_panel_rows[i] >= T[i] && x_panel_rows[i] >= T[i],
+                "%s: problem %d: panel rows must be multiples of 32 >= T", who, i);
+    PXR_REQUIRE((((uintptr_t)dy[i] | (uintptr_t)x[i] | (uintptr_t)dW[i]) & 15) == 0, "%s: unaligned operand", who);
+    PXR_REQUIRE(dy_plane_stride[i] * 2 * planes < 0x7FFFFFF0ll && x_plane_stride[i] * 2 * planes < 0x7FFFFFF0ll, "%s: planes too large", who);
+    P3DwProblem& P = g.p[i];
+    P.dy = P3Mat{reinterpret_cast<__bf16*>(const_cast<void*>(dy[i])), dy_plane_stride[i], dy_panel_rows[i]};
+    P.x = P3Mat{reinterpret_cast<__bf16*>(const_cast<void*>(x[i])), x_plane_stride[i], x_panel_rows[i]};
+    P.dW = dW[i]; P.db = db[i]; P.T = T[i]; P.N = N[i]; P.K = K[i];
+    if (h2) {
+      PXR_REQUIRE(dy_exp[i] >= -60 && dy_exp[i] <= 60 && x_exp[i] >= -60 && x_exp[i] <= 60, "%s: scale exponents", who);
+      P.dy_exp = dy_exp[i]; P.x_exp = x_exp[i]; P.dy_exp_dev = dy_exp_dev[i]; P.x_exp_dev = x_exp_dev[i];
     }
   }
-  pxr_set_error("pxr_gemm_h2_f32: flavour b_kc=%d / epilogue %d is not instantiated", b_kc, epilogue);
-  return PXR_ERR_BAD_ARG;
+  return PXR_OK;
 }
 
 }  // namespace pxr
@@ -654,43 +618,21 @@ extern "C" int pxr_split_h2_multi_f32(int n, const float* const* x, const int64_
 
 // C[M,N] = epilogue(2^-(a_exp + b_exp) * (A~ B~^T)) with both operands as TWO fp16 planes (A~ = A 2^a_exp, B~ = B 2^b_exp, [N][K]
 // k-contiguous): three products per multiply on v_mfma_f32_32x32x16_f16 -- 22 significant bits per operand, the accuracy of the
-// six-product bf16x3 GEMM at half its matrix-pipe work (profiles/r04/lab/h2_lab_run1.log).  Forward flavours only (epilogue:
-// EPI_NONE | EPI_BIAS | EPI_BIAS_GELU | EPI_BIAS_ADD | EPI_BIAS_QGELU | EPI_BIAS_RELU); output as fp32 and / or planes in either
-// format (c_fmt: 0 = three bf16 planes, 1 = two fp16 planes at unit scale).  Ping-pong tiles only (gemm_p4.cuh): meant for the tall
-// GEMMs of the image tower.
+// six-product bf16x3 GEMM at half its matrix-pipe work (profiles/r04/lab/h2_lab_run1.log).  The flavours and epilogues of
+// pxr_gemm_planes_f32 (b_kc = 1: forward, PXR_EPI_FWD_PLANES; b_kc = 0: input gradient, B~ [K][N], PXR_EPI_BWD -- gemm_epi.cuh); output
+// as fp32 and / or planes in either format (c_fmt: 0 = three bf16 planes, 1 = two fp16 planes, at the scale 2^(*c_exp_dev) or unit
+// scale).  Ping-pong tiles for the tall GEMMs of the image tower (gemm_p4.cuh), the lockstep tiles of the bf16x3 kernels below them.
 extern "C" int pxr_gemm_h2_f32(int b_kc, int M, int N, int K, const void* A, int64_t a_plane_stride, int64_t a_panel_rows, int a_exp,
                                const int* a_exp_dev, const void* B, int64_t b_plane_stride, int64_t b_panel_rows, int b_exp,
                                const int* b_exp_dev, float* C, int64_t ldc, int epilogue, const float* bias, float* aux,
                                int64_t ldaux, void* c_planes, int64_t c_plane_stride, int64_t c_panel_rows, int c_fmt,
                                const int* c_exp_dev, int act, int tile_hint, void* stream) {
-  PXR_REQUIRE(A && B && (C || c_planes), "pxr_gemm_h2_f32: null operand");
-  PXR_REQUIRE(M >= 0 && N >= 0 && K >= 0 && K % 32 == 0, "pxr_gemm_h2_f32: K must be a multiple of 32");
-  PXR_REQUIRE(b_kc || N % 32 == 0, "pxr_gemm_h2_f32: an x-contiguous B needs N %% 32 == 0");
-  PXR_REQUIRE(a_panel_rows % 16 == 0 && b_panel_rows % 16 == 0 && a_plane_stride % 8 == 0 && b_plane_stride % 8 == 0,
-              "pxr_gemm_h2_f32: panel rows must be multiples of 16, plane strides of 8 elements");
-  PXR_REQUIRE(a_panel_rows >= M && a_plane_stride >= a_panel_rows * K &&
-                  (b_kc ? (b_panel_rows >= N && b_plane_stride >= b_panel_rows * K) : (b_panel_rows >= K && b_plane_stride >= b_panel_rows * N)),
-              "pxr_gemm_h2_f32: operand planes smaller than the matrices");
-  PXR_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)c_planes | (uintptr_t)aux | (uintptr_t)bias) & 15) == 0,
-              "pxr_gemm_h2_f32: operands must be 16-byte aligned");
-  PXR_REQUIRE(a_plane_stride * 4 < 0x7FFFFFF0ll && b_plane_stride * 4 < 0x7FFFFFF0ll, "pxr_gemm_h2_f32: an operand's two planes must span less than 2 GiB");
-  PXR_REQUIRE(!c_planes || (N % 32 == 0 && c_panel_rows % 16 == 0 && c_panel_rows >= M), "pxr_gemm_h2_f32: output planes need N %% 32 == 0");
-  PXR_REQUIRE(c_fmt == PXR_PLANES_BF16X3 || c_fmt == PXR_PLANES_H2, "pxr_gemm_h2_f32: c_fmt");
-  PXR_REQUIRE(!c_exp_dev || (c_planes && c_fmt == PXR_PLANES_H2), "pxr_gemm_h2_f32: an output exponent needs h2 output planes");
-  PXR_REQUIRE(a_exp >= -60 && a_exp <= 60 && b_exp >= -60 && b_exp <= 60, "pxr_gemm_h2_f32: scale exponents");
-  PXR_REQUIRE(aux || !(epilogue == EPI_BIAS_ADD || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_QGELU_GRAD || epilogue == EPI_ADD ||
-                       epilogue == EPI_MUL || epilogue == EPI_BIAS_GELU_GRAD || epilogue == EPI_BIAS_ACT_GRAD),
-              "pxr_gemm_h2_f32: epilogue %d reads / writes aux", epilogue);
-  PXR_REQUIRE(bias || !b_kc || epilogue == EPI_NONE, "pxr_gemm_h2_f32: epilogue %d needs a bias", epilogue);
-  if (M == 0 || N == 0) return PXR_OK;
+  const char* who = "pxr_gemm_h2_f32";
+  const H2GemmExps ex{a_exp, b_exp, a_exp_dev, b_exp_dev, c_exp_dev, c_fmt};
   P3Args g;
-  g.A = P3Mat{reinterpret_cast<__bf16*>(const_cast<void*>(A)), a_plane_stride, a_panel_rows};
-  g.B = P3Mat{reinterpret_cast<__bf16*>(const_cast<void*>(B)), b_plane_stride, b_panel_rows};
-  g.Cp = P3Mat{reinterpret_cast<__bf16*>(c_planes), c_plane_stride, c_panel_rows};
-  g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.bias = bias; g.aux = aux; g.ldaux = ldaux; g.act = act;
-  g.a_exp = a_exp; g.b_exp = b_exp; g.a_exp_dev = a_exp_dev; g.b_exp_dev = b_exp_dev; g.c_exp_dev = c_exp_dev;
-  g.cp_fmt = c_fmt;
-  g.status = pxr_status_word();
+  const int rc = p3_gemm_args(who, 2, &ex, g, b_kc, M, N, K, A, a_plane_stride, a_panel_rows, B, b_plane_stride, b_panel_rows, C, ldc,
+                              epilogue, bias, aux, ldaux, c_planes, c_plane_stride, c_panel_rows, act);
+  if (rc != PXR_OK || M == 0 || N == 0) return rc;
   hipStream_t st = (hipStream_t)stream;
   // tiles: 2 | BM | BN | ring slots | accumulator sets.  256x256 (one set) when its rounds of 256 workgroups, each 1.75x as long as
   // a round of 256x128 tiles (two sets: hi*hi apart from the cross terms; measured: profiles/r04/lab/h2_lab_run1.log -- the square
@@ -705,12 +647,12 @@ extern "C" int pxr_gemm_h2_f32(int b_kc, int M, int N, int K, const void* A, int
     if (env_small && t128 < 512) tile_hint = N >= 1024 ? 212806420 : 206406430;
     else tile_hint = (env_sq && N >= 256 && 7 * ((t256 + 255) / 256) <= 4 * ((t128 + 255) / 256)) ? 225625641 : 225612842;
   }
-  if (tile_hint == 212806420) return epi_h2<P3Cfg<128, 64, 2, 2, 2, true>>(b_kc, epilogue, g, st);
-  if (tile_hint == 212806430) return epi_h2<P3Cfg<128, 64, 2, 2, 3, true>>(b_kc, epilogue, g, st);
-  if (tile_hint == 206406430) return epi_h2<P3Cfg<64, 64, 2, 2, 3, true>>(b_kc, epilogue, g, st);
-  if (tile_hint == 225625641) return epi_h2<P4Cfg<256, 256, 4, 2, 4, 1, 0, 2, true>>(b_kc, epilogue, g, st);
-  if (tile_hint == 225612842) return epi_h2<P4Cfg<256, 128, 4, 2, 4, 2, 0, 2, true>>(b_kc, epilogue, g, st);
-  if (tile_hint == 225612841) return epi_h2<P4Cfg<256, 128, 4, 2, 4, 1, 0, 2, true>>(b_kc, epilogue, g, st);
+  if (tile_hint == 212806420) return epi_p3<P3Cfg<128, 64, 2, 2, 2, true>, false>(who, b_kc, epilogue, g, st);
+  if (tile_hint == 212806430) return epi_p3<P3Cfg<128, 64, 2, 2, 3, true>, false>(who, b_kc, epilogue, g, st);
+  if (tile_hint == 206406430) return epi_p3<P3Cfg<64, 64, 2, 2, 3, true>, false>(who, b_kc, epilogue, g, st);
+  if (tile_hint == 225625641) return epi_p3<P4Cfg<256, 256, 4, 2, 4, 1, 0, 2, true>, false>(who, b_kc, epilogue, g, st);
+  if (tile_hint == 225612842) return epi_p3<P4Cfg<256, 128, 4, 2, 4, 2, 0, 2, true>, false>(who, b_kc, epilogue, g, st);
+  if (tile_hint == 225612841) return epi_p3<P4Cfg<256, 128, 4, 2, 4, 1, 0, 2, true>, false>(who, b_kc, epilogue, g, st);
   pxr_set_error("pxr_gemm_h2_f32: tile %d is not instantiated", tile_hint);
   return PXR_ERR_BAD_ARG;
 }
@@ -719,26 +661,11 @@ extern "C" int pxr_gemm_planes_f32(int b_kc, int M, int N, int K, const void* A,
                                    const void* B, int64_t b_plane_stride, int64_t b_panel_rows, float* C, int64_t ldc,
                                    int epilogue, const float* bias, float* aux, int64_t ldaux, void* c_planes,
                                    int64_t c_plane_stride, int64_t c_panel_rows, int act, int tile_hint, void* stream) {
-  PXR_REQUIRE(A && B && (C || c_planes), "pxr_gemm_planes_f32: null operand");
-  PXR_REQUIRE(M >= 0 && N >= 0 && K >= 0 && K % 32 == 0, "pxr_gemm_planes_f32: K must be a multiple of 32");
-  PXR_REQUIRE(b_kc || N % 32 == 0, "pxr_gemm_planes_f32: an x-contiguous B needs N %% 32 == 0");
-  PXR_REQUIRE(a_panel_rows % 16 == 0 && b_panel_rows % 16 == 0 && a_plane_stride % 8 == 0 && b_plane_stride % 8 == 0,
-              "pxr_gemm_planes_f32: panel rows must be multiples of 16, plane strides of 8 elements");
-  PXR_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)c_planes | (uintptr_t)aux | (uintptr_t)bias) & 15) == 0,
-              "pxr_gemm_planes_f32: operands must be 16-byte aligned");
-  PXR_REQUIRE(a_plane_stride * 6 < 0x7FFFFFF0ll && b_plane_stride * 6 < 0x7FFFFFF0ll,
-              "pxr_gemm_planes_f32: an operand's three planes must span less than 2 GiB");
-  PXR_REQUIRE(!c_planes || (N % 32 == 0 && c_panel_rows % 16 == 0 && c_panel_rows >= M), "pxr_gemm_planes_f32: output planes need N %% 32 == 0");
-  PXR_REQUIRE(aux || !(epilogue == EPI_ADD || epilogue == EPI_MUL || epilogue == EPI_BIAS_ADD || epilogue == EPI_BIAS_GELU ||
-                       epilogue == EPI_BIAS_GELU_GRAD || epilogue == EPI_BIAS_QGELU_GRAD || epilogue == EPI_BIAS_ACT_GRAD),
-              "pxr_gemm_planes_f32: epilogue %d reads / writes aux", epilogue);
-  if (M == 0 || N == 0) return PXR_OK;
+  const char* who = "pxr_gemm_planes_f32";
   P3Args g;
-  g.A = P3Mat{reinterpret_cast<__bf16*>(const_cast<void*>(A)), a_plane_stride, a_panel_rows};
-  g.B = P3Mat{reinterpret_cast<__bf16*>(const_cast<void*>(B)), b_plane_stride, b_panel_rows};
-  g.Cp = P3Mat{reinterpret_cast<__bf16*>(c_planes), c_plane_stride, c_panel_rows};
-  g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.bias = bias; g.aux = aux; g.ldaux = ldaux; g.act = act;
-  g.a_exp = g.b_exp = 0; g.a_exp_dev = g.b_exp_dev = g.c_exp_dev = nullptr; g.cp_fmt = PXR_PLANES_BF16X3; g.status = nullptr;
+  const int rc = p3_gemm_args(who, 3, nullptr, g, b_kc, M, N, K, A, a_plane_stride, a_panel_rows, B, b_plane_stride, b_panel_rows, C,
+                              ldc, epilogue, bias, aux, ldaux, c_planes, c_plane_stride, c_panel_rows, act);
+  if (rc != PXR_OK || M == 0 || N == 0) return rc;
   hipStream_t st = (hipStream_t)stream;
   // tile_hint digits: waves | BM (3) | BN (3) | stages | early fragment reads.  Heuristic (tools/p3_sweep.py on MI355X):
   // 256x128 tiles when they fill the chip more than twice; at M = B*L ~ 3200 tokens 128x64 (two workgroups per CU) for wide
@@ -760,7 +687,7 @@ extern "C" int pxr_gemm_planes_f32(int b_kc, int M, int N, int K, const void* A,
     }
   }
 #define PXR_P3_TILE(CODE, EARLY, ...) \
-  if (tile_hint == CODE) return epi_p3<P3Cfg<__VA_ARGS__>, EARLY>(b_kc, epilogue, g, st)
+  if (tile_hint == CODE) return epi_p3<P3Cfg<__VA_ARGS__>, EARLY>(who, b_kc, epilogue, g, st)
   PXR_P3_TILE(406406431, true, 64, 64, 2, 2, 3);
   PXR_P3_TILE(406406461, true, 64, 64, 2, 2, 6);
   PXR_P3_TILE(406406430, false, 64, 64, 2, 2, 3);
@@ -771,9 +698,9 @@ extern "C" int pxr_gemm_planes_f32(int b_kc, int M, int N, int K, const void* A,
   PXR_P3_TILE(825612820, false, 256, 128, 4, 2, 2);
 #undef PXR_P3_TILE
   // ping-pong tiles: 4 | BM | BN | ring slots | accumulator sets
-  if (tile_hint == 425612833) return epi_p3<P4Cfg<256, 128, 4, 2, 3, 3>, false>(b_kc, epilogue, g, st);
-  if (tile_hint == 425612832) return epi_p3<P4Cfg<256, 128, 4, 2, 3, 2>, false>(b_kc, epilogue, g, st);
-  if (tile_hint == 425625631) return epi_p3<P4Cfg<256, 256, 4, 2, 3, 1>, false>(b_kc, epilogue, g, st);
+  if (tile_hint == 425612833) return epi_p3<P4Cfg<256, 128, 4, 2, 3, 3>, false>(who, b_kc, epilogue, g, st);
+  if (tile_hint == 425612832) return epi_p3<P4Cfg<256, 128, 4, 2, 3, 2>, false>(who, b_kc, epilogue, g, st);
+  if (tile_hint == 425625631) return epi_p3<P4Cfg<256, 256, 4, 2, 3, 1>, false>(who, b_kc, epilogue, g, st);
   pxr_set_error("pxr_gemm_planes_f32: tile %d is not instantiated", tile_hint);
   return PXR_ERR_BAD_ARG;
 }
@@ -785,25 +712,13 @@ extern "C" int pxr_grouped_dw_h2_f32(int n, const void* const* dy, const int64_t
                                      const int64_t* x_plane_stride, const int64_t* x_panel_rows, const int* x_exp,
                                      const int* const* x_exp_dev, float* const* dW, float* const* db, const int* T, const int* N,
                                      const int* K, int tile_hint, void* stream) {
-  PXR_REQUIRE(n >= 1 && n <= DW_MAX && dy && x && dW && db && T && N && K && dy_plane_stride && dy_panel_rows && x_plane_stride &&
-                  x_panel_rows && dy_exp && x_exp && dy_exp_dev && x_exp_dev, "pxr_grouped_dw_h2_f32: bad args (n=%d, max %d)", n, DW_MAX);
   P3DwGroup g{};
-  g.n = n;
+  const int rc = p3_dw_args("pxr_grouped_dw_h2_f32", 2, g, n, dy, dy_plane_stride, dy_panel_rows, dy_exp, dy_exp_dev, x, x_plane_stride,
+                            x_panel_rows, x_exp, x_exp_dev, dW, db, T, N, K);
+  if (rc != PXR_OK) return rc;
   int64_t t256 = 0;
   int t_min = T[0];
   for (int i = 0; i < n; ++i) {
-    PXR_REQUIRE(dy[i] && x[i] && dW[i] && T[i] > 0 && N[i] > 0 && K[i] > 0 && N[i] % 32 == 0 && K[i] % 32 == 0,
-                "pxr_grouped_dw_h2_f32: problem %d has a bad shape (N and K must be multiples of 32)", i);
-    PXR_REQUIRE(dy_panel_rows[i] % 32 == 0 && x_panel_rows[i] % 32 == 0 && dy_panel_rows[i] >= T[i] && x_panel_rows[i] >= T[i],
-                "pxr_grouped_dw_h2_f32: problem %d: panel rows must be multiples of 32 >= T", i);
-    PXR_REQUIRE((((uintptr_t)dy[i] | (uintptr_t)x[i] | (uintptr_t)dW[i]) & 15) == 0, "pxr_grouped_dw_h2_f32: unaligned operand");
-    PXR_REQUIRE(dy_plane_stride[i] * 4 < 0x7FFFFFF0ll && x_plane_stride[i] * 4 < 0x7FFFFFF0ll, "pxr_grouped_dw_h2_f32: planes too large");
-    PXR_REQUIRE(dy_exp[i] >= -60 && dy_exp[i] <= 60 && x_exp[i] >= -60 && x_exp[i] <= 60, "pxr_grouped_dw_h2_f32: scale exponents");
-    P3DwProblem& P = g.p[i];
-    P.dy = P3Mat{reinterpret_cast<__bf16*>(const_cast<void*>(dy[i])), dy_plane_stride[i], dy_panel_rows[i]};
-    P.x = P3Mat{reinterpret_cast<__bf16*>(const_cast<void*>(x[i])), x_plane_stride[i], x_panel_rows[i]};
-    P.dW = dW[i]; P.db = db[i]; P.T = T[i]; P.N = N[i]; P.K = K[i];
-    P.dy_exp = dy_exp[i]; P.x_exp = x_exp[i]; P.dy_exp_dev = dy_exp_dev[i]; P.x_exp_dev = x_exp_dev[i];
     t256 += (int64_t)((N[i] + 255) / 256) * ((K[i] + 127) / 128);
     t_min = T[i] < t_min ? T[i] : t_min;
   }
@@ -820,24 +735,12 @@ extern "C" int pxr_grouped_dw_planes_f32(int n, const void* const* dy, const int
                                          const void* const* x, const int64_t* x_plane_stride, const int64_t* x_panel_rows,
                                          float* const* dW, float* const* db, const int* T, const int* N, const int* K,
                                          int tile_hint, void* stream) {
-  PXR_REQUIRE(n >= 1 && n <= DW_MAX && dy && x && dW && db && T && N && K && dy_plane_stride && dy_panel_rows && x_plane_stride &&
-                  x_panel_rows, "pxr_grouped_dw_planes_f32: bad args (n=%d, max %d)", n, DW_MAX);
   P3DwGroup g{};
-  g.n = n;
+  const int rc = p3_dw_args("pxr_grouped_dw_planes_f32", 3, g, n, dy, dy_plane_stride, dy_panel_rows, nullptr, nullptr, x, x_plane_stride,
+                            x_panel_rows, nullptr, nullptr, dW, db, T, N, K);
+  if (rc != PXR_OK) return rc;
   int64_t t128 = 0;
-  for (int i = 0; i < n; ++i) {
-    PXR_REQUIRE(dy[i] && x[i] && dW[i] && T[i] > 0 && N[i] > 0 && K[i] > 0 && N[i] % 32 == 0 && K[i] % 32 == 0,
-                "pxr_grouped_dw_planes_f32: problem %d has a bad shape (N and K must be multiples of 32)", i);
-    PXR_REQUIRE(dy_panel_rows[i] % 32 == 0 && x_panel_rows[i] % 32 == 0 && dy_panel_rows[i] >= T[i] && x_panel_rows[i] >= T[i],
-                "pxr_grouped_dw_planes_f32: problem %d: panel rows must be multiples of 32 >= T", i);
-    PXR_REQUIRE((((uintptr_t)dy[i] | (uintptr_t)x[i] | (uintptr_t)dW[i]) & 15) == 0, "pxr_grouped_dw_planes_f32: unaligned operand");
-    PXR_REQUIRE(dy_plane_stride[i] * 6 < 0x7FFFFFF0ll && x_plane_stride[i] * 6 < 0x7FFFFFF0ll, "pxr_grouped_dw_planes_f32: planes too large");
-    P3DwProblem& P = g.p[i];
-    P.dy = P3Mat{reinterpret_cast<__bf16*>(const_cast<void*>(dy[i])), dy_plane_stride[i], dy_panel_rows[i]};
-    P.x = P3Mat{reinterpret_cast<__bf16*>(const_cast<void*>(x[i])), x_plane_stride[i], x_panel_rows[i]};
-    P.dW = dW[i]; P.db = db[i]; P.T = T[i]; P.N = N[i]; P.K = K[i];
-    t128 += (int64_t)((N[i] + 127) / 128) * ((K[i] + 127) / 128);
-  }
+  for (int i = 0; i < n; ++i) t128 += (int64_t)((N[i] + 127) / 128) * ((K[i] + 127) / 128);
   hipStream_t st = (hipStream_t)stream;
   // 256x128 ping-pong tiles (two accumulator sets: the bias column sums need the third set's registers) when they fill >= 192 CUs
   // in ONE round (the ViT tower's blocks: 216 tiles); 128x128 lockstep tiles when those do; 64x64 below

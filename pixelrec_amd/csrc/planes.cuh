@@ -115,6 +115,15 @@ __device__ __forceinline__ void px_store8(const P3Mat& m, int fmt, int32_t* stat
     p3_store8(m, r, c, v);
   }
 }
+// 8 consecutive fp32 values at a 16-byte aligned address <-> registers: two 16-byte accesses
+__device__ __forceinline__ void f32_load8(float (&v)[8], const float* p) {
+  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+__device__ __forceinline__ void f32_store8(float* p, const float (&v)[8]) {
+  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
 __device__ __forceinline__ void px_store4(const P3Mat& m, int fmt, int32_t* status, int64_t r, int c, const float4& v) {
   if (fmt == PXR_PLANES_H2) {
     const bool bad = !(fabsf(v.x) <= 65504.f) | !(fabsf(v.y) <= 65504.f) | !(fabsf(v.z) <= 65504.f) | !(fabsf(v.w) <= 65504.f);

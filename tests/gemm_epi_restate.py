@@ -1,5 +1,4 @@
-"""Plain torch restatements of every GEMM epilogue (pixelrec_amd/csrc/gemm_f32.cuh::epi_store, gemm_p3.hip::p3_epi_elem) as
-functions of (pre, bias, aux, act) -> (C, aux_out): `pre` is the accumulator (the product), `bias` a row vector or None, `aux`
+"""Plain torch restatements of every GEMM epilogue (pixelrec_amd/csrc/gemm_epi.cuh::epi_elem, which all four GEMM families call) as functions of (pre, bias, aux, act) -> (C, aux_out): `pre` is the accumulator (the product), `bias` a row vector or None, `aux`
 the operand the epilogue reads (residual / saved derivative / saved pre-activation) or None, `act` one of the ACT_* codes of
 EPI_BIAS_ACT_GRAD.  aux_out is what the epilogue WRITES to aux (None when it writes nothing).
 

@@ -1,4 +1,4 @@
-"""The polynomial erf of the GELU epilogues (pixelrec_amd/csrc/gemm_f32.cuh::pxr_erff), restated in numpy with the SAME
+"""The polynomial erf of the GELU epilogues (pixelrec_amd/csrc/gemm_epi.cuh::pxr_erff), restated in numpy with the SAME
 coefficients (read out of the header, so that the two cannot drift apart) and fp32 FMAs emulated through fp64: maximum error
 against the fp64 erf over [-6, 6] below 1 ulp / 6e-8 absolute -- the error class of the library erff it replaces, far inside the
 +-2e-5 activation / +-1e-4 logit budgets (BASELINE.json).  Reference: REC/model/layers.py:651-660 (erf-GELU).  The kernels
@@ -18,7 +18,7 @@ def _fma(a, b, c):
 
 
 def _coefficients():
-    src = open(os.path.join(ROOT, "pixelrec_amd", "csrc", "gemm_f32.cuh")).read()
+    src = open(os.path.join(ROOT, "pixelrec_amd", "csrc", "gemm_epi.cuh")).read()
     body = src[src.index("float pxr_erff(float a)"):src.index("// erf-GELU as the reference writes it")]
     hexes = [float.fromhex(h) for h in re.findall(r"-?0x1\.[0-9a-f]+p[+-]?\d+", body)]
     assert len(hexes) == 13, hexes         # 7 of the large branch (incl. the switch point's neighbours), 6 of the small one
