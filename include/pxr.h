@@ -803,6 +803,49 @@ int pxr_vbpr_bias_grad_f32(const float* x, const float* csign, int R, int F, flo
 int pxr_vbpr_pack_f32(const float* a, const int64_t* a_rows, const float* b, const int64_t* b_rows, const float* s, int64_t R,
                       int Dh, int Dp, float* out, void* stream);
 
+/* ---- CNN-F: conv2d by im2col, 2x2 max-pool (model/PixelNet/dvbpr.py:113-137; csrc/conv2d.hip) -------------------------------- */
+/* A convolution is im2col over a chunk of images + the GEMMs above (y = col W^T + b with the ReLU epilogue, dW = dY^T col, dcol =
+ * dY W) + col2im.  Padding 0, dilation 1: Ho = (H - kh) / sh + 1, Wo = (W - kw) / sw + 1.  An activation is addressed through its
+ * four ELEMENT strides (n, c, h, w): the image is NCHW, a GEMM output [n Ho Wo, Cout] is NHWC.  Every offset is 64-bit; fp32; no
+ * atomics.  Bad geometry (a kernel larger than the input, a non-positive stride, ldk not K rounded up to a multiple of 4) is an
+ * error without a launch.
+ * im2col (dvbpr.py:113-114,127 nn.Conv2d's unfold): col[(img, ho, wo), (c, i, j)] = x[img, c, ho sh + i, wo sw + j], K = C kh kw
+ * columns in (c, i, j) order -- weight.view(Cout, K) is the GEMM's B operand as it stands -- in rows of ldk floats; columns
+ * [K, ldk) are written +0.0.  col 16-byte aligned. */
+int pxr_conv2d_im2col_f32(const float* x, int64_t x_sn, int64_t x_sc, int64_t x_sh, int64_t x_sw, int64_t n, int C, int H, int W,
+                          int kh, int kw, int sh, int sw, float* col, int64_t ldk, void* stream);
+/* col2im, the data gradient in gather form (autograd of dvbpr.py:127): dx[img, c, h, w] = the sum of the at most kh kw entries of
+ * dcol that im2col filled from that element, kh outer, kw inner; +0.0 where no window covers it (a stride remainder).  dx is
+ * addressed through its strides and written whole. */
+int pxr_conv2d_col2im_f32(const float* dcol, int64_t ldk, int64_t n, int C, int H, int W, int kh, int kw, int sh, int sw, float* dx,
+                          int64_t d_sn, int64_t d_sc, int64_t d_sh, int64_t d_sw, void* stream);
+/* nn.MaxPool2d(2) (dvbpr.py:117,129): p[img, c, hp, wp] = max of the 2x2 window, Hp = H / 2, Wp = W / 2 (floor: a trailing odd row /
+ * column is dropped).  Both sides through strides (the last pool writes (c, h, w) order for fcs.0).  H, W >= 2. */
+int pxr_maxpool2x2_fwd_f32(const float* y, int64_t y_sn, int64_t y_sc, int64_t y_sh, int64_t y_sw, int64_t n, int C, int H, int W,
+                           float* p, int64_t p_sn, int64_t p_sc, int64_t p_sh, int64_t p_sw, void* stream);
+/* Its backward fused with the mask of the ReLU in front of it (autograd of dvbpr.py:127-129): y = the ReLU'd conv output that was
+ * pooled; dy[pix] = dp[window of pix] where pix is the FIRST maximum of its window in row-major order (torch's rule) and y[pix] >
+ * 0, else +0.0; dropped rows / columns get +0.0.  dy has y's strides and is written whole. */
+int pxr_maxpool2x2_relu_bwd_f32(const float* y, int64_t y_sn, int64_t y_sc, int64_t y_sh, int64_t y_sw, const float* dp, int64_t p_sn,
+                                int64_t p_sc, int64_t p_sh, int64_t p_sw, int64_t n, int C, int H, int W, float* dy, void* stream);
+
+/* ---- DVBPR (model/PixelNet/dvbpr.py; csrc/dvbpr.hip) ----------------------------------------------------------------------- */
+/* The tables are ONE [1 + 2 n_users + n_items, Dh] buffer in the reference's registration order: theta_users row u at 1 + u,
+ * gamma_users row u at 1 + n_users + u, gamma_items row i at 1 + 2 n_users + i, row 0 a spare.  rows[6B] (pxr_table_rows_i64) =
+ * [gamma row of user[b] | theta row of user[b] | gamma rows of item_id.view(-1) | positions index.view(-1) into E, base 0]; E
+ * [M, Dh] = the encoder's output, one row per distinct image of the batch.
+ * Pair head (dvbpr.py:49-62): x_b = <gu_b, gi+ - gi-> + <tu_b, E[p_b] - E[n_b]>; lossrow[b] = -log sigmoid(x_b) (no 1e-8), loss =
+ * mean, coef[b] = d loss / d x_b.  Dh % 4 == 0, Dh <= 4096. */
+int pxr_dvbpr_pair_fwd_f32(const float* table, const int64_t* rows, const float* E, int Dh, int B, float* coef, float* lossrow,
+                           float* loss, void* stream);
+/* Its backward (autograd of dvbpr.py:49-62), c_b = coef[b] * grad_scale * (*grad_scale_dev if given): the three tables' gradient as
+ * sparse rows (slots as pxr_vbpr_pair_bwd_f32; *sp_n = 4B; contributions c_b (gi+ - gi-), c_b (E[p] - E[n]), +-c_b gu_b) and dE
+ * [M, Dh] dense: dE[m] = the sum over the positions k with index.view(-1)[k] == m, ascending, of +-c_b tu_b; +0.0 for a row no
+ * position names.  Position 0 is a real image.  Deterministic, no atomics.  cap >= 4B. */
+int pxr_dvbpr_pair_bwd_f32(const float* table, const int64_t* rows, const float* E, int64_t M, const float* coef, int Dh, int B,
+                           float grad_scale, const float* grad_scale_dev, float* dE, int64_t* sp_idx, float* sp_rows, int32_t* sp_n,
+                           int64_t cap, void* stream);
+
 /* ---- ACF (model/ViNet/acf.py; csrc/acf.hip) ------------------------------------------------------------------------------- */
 /* The tables are ONE [1 + n_items + n_users, E] buffer in the reference's parameter order: item_model row i at 1 + i (item 0 is
  * the reference's padding row: read, decayed, never given a gradient), user_embedding row u at 1 + n_items + u, row 0 a spare.

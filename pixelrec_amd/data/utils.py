@@ -22,7 +22,8 @@ SUPPORTED = {"SASRec": "SEQ", "MOSASRec": "SEQ", "FSASRec": "SEQ", "GRU4Rec": "S
              "MOGRU4Rec": "SEQ", "MONextItNet": "SEQ", "BERT4Rec": "SEQ", "LightGCN": "PAIR", "MF": "PAIR", "VBPR": "PAIR",
              "SRGNN": "AUGSEQ", "LightSANs": "TWOTOWER", "ACF": "SEQ", "VISRANK": "EVALONLY", "CuratorNet": "SEQ", "DIN": "SEQ",
              "DSSM": "SEQ", "FM": "SEQ", "WideDeep": "SEQ", "MODSSM": "SEQ", "MOFM": "SEQ",
-             "MODIN": "SEQ", "MOBERT4Rec": "SEQ", "MOSRGNN": "AUGSEQ", "MOMF": "PAIR"}      # REC/data/utils.py:24-33
+             "MODIN": "SEQ", "MOBERT4Rec": "SEQ", "MOSRGNN": "AUGSEQ", "MOMF": "PAIR",
+             "DVBPR": "PAIR"}      # REC/data/utils.py:24-33
 
 
 def load_data(config):
@@ -98,6 +99,7 @@ LOADERS = {
     "MOBERT4Rec": _seq_eval(MoBert4RecTrainBatcher),                   # :48 MOBERT4RecTrainDataset: BERT4Rec's masked windows
     "MOSRGNN": (MoGraphTrainBatcher, GraphEvalBatcher, _TrainLoader),  # :47 MOGraphTrainDataset: SRGNN's AUGSEQ prefixes
     "MOMF": (MoPairTrainBatcher, PairEvalBatcher, _TrainLoader),       # MOPairTrainDataset / PairEvalDataset: MF's pairs, users scored
+    "DVBPR": (MoPairTrainBatcher, PairEvalBatcher, _TrainLoader),      # :40 MOPairTrainDataset: the item ids are image_ids[index]
 }                                                                      # MO*: as positions into the batch's distinct images
 assert LOADERS.keys() == SUPPORTED.keys()
 

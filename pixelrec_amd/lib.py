@@ -167,6 +167,12 @@ _SIGNATURES = {
     "pxr_vbpr_pair_bwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "pxr_vbpr_bias_grad_f32": (_I, [_P, _P, _I, _I, _P, _P]),
     "pxr_vbpr_pack_f32": (_I, [_P, _P, _P, _P, _P, _I64, _I, _I, _P, _P]),
+    "pxr_conv2d_im2col_f32": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _I, _I, _I, _I, _I, _I, _I, _P, _I64, _P]),
+    "pxr_conv2d_col2im_f32": (_I, [_P, _I64, _I64, _I, _I, _I, _I, _I, _I, _I, _P, _I64, _I64, _I64, _I64, _P]),
+    "pxr_maxpool2x2_fwd_f32": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _I, _I, _I, _P, _I64, _I64, _I64, _I64, _P]),
+    "pxr_maxpool2x2_relu_bwd_f32": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I, _I, _I, _P, _P]),
+    "pxr_dvbpr_pair_fwd_f32": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "pxr_dvbpr_pair_bwd_f32": (_I, [_P, _P, _P, _I64, _P, _I, _I, _F, _P, _P, _P, _P, _P, _I64, _P]),
     "pxr_curator_pool_f32": (_I, [_P, _P, _I64, _I, _I, _I, _P, _P, _P]),
     "pxr_curator_pool_bwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "pxr_mul_f32": (_I, [_P, _P, _P, _I64, _P]),

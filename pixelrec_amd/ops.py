@@ -3115,3 +3115,229 @@ def wd_topk(T, hb, window, wide, wide_bias, w2, b2, wp, bp, K: int, hist_ptr=Non
                                 _l.ptr(b2), h2, _l.ptr(wp), _l.ptr(bp), _l.ptr(hist_ptr), _l.ptr(hist_items), K, _l.ptr(idx),
                                 _l.ptr(val), _l.ptr(ws), ws_bytes, _l.stream_ptr()), "pxr_wd_topk_f32")
     return idx, val
+
+
+# ------------------------------------------------------------------------------------------------ CNN-F: conv2d by im2col (csrc/conv2d.hip)
+# An activation is a torch VIEW of logical shape [n, C, H, W] whose strides say where it lives: the image batch is NCHW-contiguous,
+# a conv GEMM's [n Ho Wo, Cout] output is NHWC storage seen through .permute(0, 3, 1, 2).  The kernels take the four strides.
+def conv2d_out_hw(H: int, W: int, kh: int, kw: int, sh: int, sw: int):
+    """(Ho, Wo) of a padding-0, dilation-1 convolution (nn.Conv2d's floor rule); ValueError outside its domain."""
+    if kh <= 0 or kw <= 0 or sh <= 0 or sw <= 0 or kh > H or kw > W:
+        raise ValueError(f"conv2d: kernel {kh}x{kw} / stride {sh}x{sw} does not fit an input of {H}x{W}")
+    return (H - kh) // sh + 1, (W - kw) // sw + 1
+
+
+def conv2d_ldk(C: int, kh: int, kw: int) -> int:
+    """Row length of the im2col matrix: K = C kh kw rounded up to a multiple of 4 floats (the GEMMs' leading dimensions)."""
+    return (C * kh * kw + 3) // 4 * 4
+
+
+def conv2d_chunk_images(n: int, rows_per_image: int, ldk: int, workspace_bytes: int) -> int:
+    """Images per chunk under a byte budget for the column workspace: as many whole images as fit, at least one."""
+    return max(1, min(int(n), int(workspace_bytes) // (4 * rows_per_image * ldk)))
+
+
+_conv_ws: dict = {}
+
+
+def _conv_workspace(numel: int, device):
+    """Grow-only column workspace per (device, stream)."""
+    key = (device, _l.raw_stream())
+    b = _conv_ws.get(key)
+    if b is None or b.numel() < numel:
+        b = _conv_ws[key] = torch.empty(numel, dtype=torch.float32, device=device)
+    return b
+
+
+def _act(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _l.PxrError(f"{name}: expected a CUDA/HIP tensor (pixelrec_amd has no CPU fallback)")
+    if t.dtype != torch.float32 or t.dim() != 4:
+        raise _l.PxrError(f"{name}: expected a float32 [n, C, H, W] view, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def conv2d_im2col(x, kh: int, kw: int, sh: int, sw: int, col=None, ldk=None):
+    """x [n, C, H, W] (any strides) -> col [n Ho Wo, ldk], columns in (c, kh, kw) order, pad columns +0.0 (pxr_conv2d_im2col_f32;
+    dvbpr.py:113-114).  Bad geometry raises PxrError from the entry, without a launch."""
+    _act(x, "conv2d im2col: x")
+    n, C, H, W = x.shape
+    ldk = conv2d_ldk(C, kh, kw) if ldk is None else int(ldk)
+    if col is None:
+        Ho, Wo = conv2d_out_hw(H, W, kh, kw, sh, sw)
+        col = torch.empty(n * Ho * Wo, ldk, dtype=torch.float32, device=x.device)
+    _req(col, torch.float32, "col")
+    sane = kh > 0 and kw > 0 and sh > 0 and sw > 0 and kh <= H and kw <= W and ldk > 0
+    if sane and col.numel() != n * ((H - kh) // sh + 1) * ((W - kw) // sw + 1) * ldk:
+        raise _l.PxrError(f"conv2d im2col: col holds {col.numel()} floats, the geometry needs [n Ho Wo, ldk] with ldk={ldk}")
+    _l.check(_l.load().pxr_conv2d_im2col_f32(_l.ptr(x), *x.stride(), n, C, H, W, kh, kw, sh, sw, _l.ptr(col), ldk, _l.stream_ptr()),
+             "pxr_conv2d_im2col_f32")
+    return col
+
+
+def conv2d_col2im(dcol, dx, kh: int, kw: int, sh: int, sw: int, ldk=None):
+    """dcol [n Ho Wo, ldk] -> dx [n, C, H, W] (a view; written whole through its strides): the data gradient in gather form, kh outer,
+    kw inner, +0.0 where no window covers an element (pxr_conv2d_col2im_f32)."""
+    _act(dx, "conv2d col2im: dx")
+    _req(dcol, torch.float32, "dcol")
+    n, C, H, W = dx.shape
+    ldk = conv2d_ldk(C, kh, kw) if ldk is None else int(ldk)
+    sane = kh > 0 and kw > 0 and sh > 0 and sw > 0 and kh <= H and kw <= W and ldk > 0
+    if sane and dcol.numel() != n * ((H - kh) // sh + 1) * ((W - kw) // sw + 1) * ldk:
+        raise _l.PxrError(f"conv2d col2im: dcol holds {dcol.numel()} floats, the geometry needs [n Ho Wo, ldk] with ldk={ldk}")
+    _l.check(_l.load().pxr_conv2d_col2im_f32(_l.ptr(dcol), ldk, n, C, H, W, kh, kw, sh, sw, _l.ptr(dx), *dx.stride(), _l.stream_ptr()),
+             "pxr_conv2d_col2im_f32")
+    return dx
+
+
+def maxpool2x2_fwd(y, chw: bool = False):
+    """nn.MaxPool2d(2) over y [n, C, H, W] (a view) -> p [n, C, H // 2, W // 2]: NHWC storage seen as [n, C, Hp, Wp], or with chw=True
+    NCHW-contiguous -- the (c, h, w) order fcs.0 reads (pxr_maxpool2x2_fwd_f32; dvbpr.py:129-132)."""
+    _act(y, "maxpool: y")
+    n, C, H, W = y.shape
+    Hp, Wp = H // 2, W // 2
+    if chw:
+        p = torch.empty(n, C, max(Hp, 0), max(Wp, 0), dtype=torch.float32, device=y.device)
+    else:
+        p = torch.empty(n, max(Hp, 0), max(Wp, 0), C, dtype=torch.float32, device=y.device).permute(0, 3, 1, 2)
+    _l.check(_l.load().pxr_maxpool2x2_fwd_f32(_l.ptr(y), *y.stride(), n, C, H, W, _l.ptr(p), *p.stride(), _l.stream_ptr()),
+             "pxr_maxpool2x2_fwd_f32")
+    return p
+
+
+def maxpool2x2_relu_bwd(y, dp):
+    """The pool's backward fused with the mask of the ReLU in front of it: y [n, C, H, W] = the ReLU'd conv output that was pooled, dp
+    [n, C, H // 2, W // 2] (a view) -> dy with y's strides; first maximum wins, dropped rows / columns +0.0
+    (pxr_maxpool2x2_relu_bwd_f32)."""
+    _act(y, "maxpool backward: y"); _act(dp, "maxpool backward: dp")
+    n, C, H, W = y.shape
+    if tuple(dp.shape) != (n, C, H // 2, W // 2):
+        raise _l.PxrError(f"maxpool backward: dp must be {(n, C, H // 2, W // 2)}, got {tuple(dp.shape)}")
+    dy = torch.empty_strided(y.shape, y.stride(), dtype=torch.float32, device=y.device)
+    _l.check(_l.load().pxr_maxpool2x2_relu_bwd_f32(_l.ptr(y), *y.stride(), _l.ptr(dp), *dp.stride(), n, C, H, W, _l.ptr(dy),
+                                                   _l.stream_ptr()), "pxr_maxpool2x2_relu_bwd_f32")
+    return dy
+
+
+def _conv_operands(who, x, Wp, kh, kw):
+    _act(x, f"{who}: x"); _req(Wp, torch.float32, "Wp")
+    n, C, H, W = x.shape
+    if Wp.dim() != 2 or Wp.shape[1] != conv2d_ldk(C, kh, kw) or Wp.shape[0] % 4:
+        raise _l.PxrError(f"{who}: the weight operand must be [Cout, {conv2d_ldk(C, kh, kw)}] (K = C kh kw = {C * kh * kw} padded to a "
+                          f"multiple of 4, pad columns zero) with Cout % 4 == 0, got {tuple(Wp.shape)}")
+    return n, C, H, W, Wp.shape[0], Wp.shape[1]
+
+
+def conv2d_relu_fwd(x, Wp, b, kh: int, kw: int, sh: int, sw: int, workspace_bytes: int = 1 << 30, save_der: bool = False):
+    """relu(conv2d(x, W, b)) as chunks of whole images through im2col + the library GEMM with the bias + ReLU epilogue
+    (dvbpr.py:127).  x [n, C, H, W] (a view); Wp [Cout, ldk] = weight.view(Cout, K) with K padded to a multiple of 4 by zero
+    columns; the chunk size is the number of whole images whose columns fit workspace_bytes (at least one).  -> (y, der): y
+    [n, Cout, Ho, Wo] as a view of NHWC storage, der = relu'(pre-activation) in the same layout when save_der (the activation
+    epilogue's own second output), else None."""
+    n, C, H, W, Cout, ldk = _conv_operands("conv2d forward", x, Wp, kh, kw)
+    Ho, Wo = conv2d_out_hw(H, W, kh, kw, sh, sw)
+    R = Ho * Wo
+    per = conv2d_chunk_images(n, R, ldk, workspace_bytes)
+    ws = _conv_workspace(per * R * ldk, x.device)
+    y = der = None
+    if not save_der or per < n:
+        y = torch.empty(n, Ho, Wo, Cout, dtype=torch.float32, device=x.device)
+        der = torch.empty_like(y) if save_der else None
+    for i0 in range(0, n, per):
+        m = min(per, n - i0)
+        col = conv2d_im2col(x[i0:i0 + m], kh, kw, sh, sw, ws[:m * R * ldk].view(m * R, ldk), ldk)
+        if save_der:
+            yc, dc = linear_fwd(col, Wp, b, act="relu")
+            if per >= n:
+                y, der = yc.view(n, Ho, Wo, Cout), dc.view(n, Ho, Wo, Cout)
+            else:
+                y[i0:i0 + m].view(m * R, Cout).copy_(yc)
+                der[i0:i0 + m].view(m * R, Cout).copy_(dc)
+        else:
+            gemm(True, True, m * R, Cout, ldk, col, ldk, Wp, ldk, y[i0:i0 + m], Cout, EPI_BIAS_RELU, bias=b, use_ws=False)
+    return y.permute(0, 3, 1, 2), (der.permute(0, 3, 1, 2) if der is not None else None)
+
+
+def conv2d_bwd(dz, x, Wp, kh: int, kw: int, sh: int, sw: int, dWp, db, workspace_bytes: int = 1 << 30, need_dx: bool = True):
+    """Backward of conv2d_relu_fwd from dz [n, Cout, Ho, Wo] (a view of NHWC storage) = the gradient at the pre-activation.  Per chunk
+    of whole images: im2col recomputed from the saved input x; dW = dz^T col and db = the column sums of dz (one grouped
+    weight-gradient launch), added over the chunks IN CHUNK ORDER (pxr_add_f32); dcol = dz W into the same workspace; col2im.
+    dWp [Cout, ldk] and db [Cout] are overwritten.  -> dx [n, C, H, W] as a view of NHWC storage, or None (need_dx=False: the
+    first layer, whose input is the image)."""
+    n, C, H, W, Cout, ldk = _conv_operands("conv2d backward", x, Wp, kh, kw)
+    Ho, Wo = conv2d_out_hw(H, W, kh, kw, sh, sw)
+    R = Ho * Wo
+    _act(dz, "conv2d backward: dz")
+    dzm = dz.permute(0, 2, 3, 1)
+    if tuple(dz.shape) != (n, Cout, Ho, Wo) or not dzm.is_contiguous():
+        raise _l.PxrError(f"conv2d backward: dz must be {(n, Cout, Ho, Wo)} over NHWC storage, got {tuple(dz.shape)} strides {dz.stride()}")
+    dzm = dzm.reshape(n * R, Cout)
+    _req(dWp, torch.float32, "dWp"); _req(db, torch.float32, "db")
+    if tuple(dWp.shape) != (Cout, ldk) or db.numel() != Cout:
+        raise _l.PxrError(f"conv2d backward: dWp must be [{Cout}, {ldk}] and db [{Cout}]")
+    per = conv2d_chunk_images(n, R, ldk, workspace_bytes)
+    ws = _conv_workspace(per * R * ldk, x.device)
+    dx = torch.empty(n, H, W, C, dtype=torch.float32, device=x.device).permute(0, 3, 1, 2) if need_dx else None
+    tW = tb = None
+    for i0 in range(0, n, per):
+        m = min(per, n - i0)
+        col = conv2d_im2col(x[i0:i0 + m], kh, kw, sh, sw, ws[:m * R * ldk].view(m * R, ldk), ldk)
+        dy = dzm[i0 * R:(i0 + m) * R]
+        if i0 == 0:
+            grouped_linear_bwd_weight([(dy, col, dWp, db)])
+        else:
+            if tW is None:
+                tW, tb = torch.empty_like(dWp), torch.empty_like(db)
+            grouped_linear_bwd_weight([(dy, col, tW, tb)])
+            dWp.copy_(add(dWp, tW))
+            db.copy_(add(db, tb))
+        if need_dx:
+            linear_bwd_input(dy, Wp, out=col)                       # dcol = dz W, over the columns it was computed from
+            conv2d_col2im(col, dx[i0:i0 + m], kh, kw, sh, sw, ldk)
+    return dx
+
+
+# ------------------------------------------------------------------------------------------------ DVBPR (csrc/dvbpr.hip)
+def dvbpr_rows(user, item_id, index, n_users: int, n_items: int, n_rows: int, out=None):
+    """user int64 [B], item_id int64 [B, 2] | None, index int64 [B, 2] | None -> rows int64 [6B] = [gamma row of user | theta row of
+    user | gamma rows of item_id.view(-1) | positions index.view(-1) into E [n_rows, Dh], base 0] of the [1 + 2U + I, Dh] table
+    (theta_users at 1, gamma_users at 1 + U, gamma_items at 1 + 2U); the 2B user rows alone in evaluation.  Bad ids flag the status
+    word and are clamped."""
+    B = user.numel()
+    _pair_items("dvbpr rows", item_id, B)
+    _pair_items("dvbpr rows", index, B)
+    return _table_rows("dvbpr rows", [("user", user, n_users, 1 + n_users, 0), ("user", user, n_users, 1, 0),
+                                      ("item_id", item_id, n_items, 1 + 2 * n_users, 0), ("index", index, n_rows, 0, 0)], out,
+                       (6 * B if item_id is not None else 2 * B,))
+
+
+def dvbpr_pair_fwd(table, rows, E, B: int, out=None):
+    """DVBPR's pair loss head (dvbpr.py:49-62; pxr_dvbpr_pair_fwd_f32) on the table rows and positions of rows [6B] and the encoder's
+    output E [M, Dh] -> (loss [1], coef [B]).  out: a float32 [2B + 1] buffer to reuse."""
+    _req(table, torch.float32, "table"); _req(rows, torch.int64, "rows"); _req(E, torch.float32, "E")
+    Dh = table.shape[1]
+    if rows.numel() != 6 * B or E.dim() != 2 or E.shape[1] != Dh:
+        raise _l.PxrError(f"dvbpr pair head: need rows [6B] and E [M, Dh] for B={B}, Dh={Dh}")
+    f = out if out is not None else torch.empty(2 * B + 1, dtype=torch.float32, device=table.device)
+    coef, lossrow, loss = f[:B], f[B:2 * B], f[2 * B:]
+    _l.check(_l.load().pxr_dvbpr_pair_fwd_f32(_l.ptr(table), _l.ptr(rows), _l.ptr(E), Dh, B, _l.ptr(coef), _l.ptr(lossrow), _l.ptr(loss),
+                                              _l.stream_ptr()), "pxr_dvbpr_pair_fwd_f32")
+    return loss, coef
+
+
+def dvbpr_pair_bwd(table, rows, E, coef, B: int, sp: SparseRows, grad_scale=1.0, grad_scale_dev=None, dE=None):
+    """Its backward (pxr_dvbpr_pair_bwd_f32): the three tables' gradient as sparse rows into sp (cap >= 4B) and d loss / d E [M, Dh]
+    dense, every row written (position 0 included), in a fixed summation order.  -> dE."""
+    _req(table, torch.float32, "table"); _req(rows, torch.int64, "rows"); _req(E, torch.float32, "E"); _req(coef, torch.float32, "coef")
+    Dh = table.shape[1]
+    if rows.numel() != 6 * B or E.dim() != 2 or E.shape[1] != Dh or coef.numel() != B or sp.rows.shape[1] != Dh or sp.cap < 4 * B:
+        raise _l.PxrError(f"dvbpr pair head backward: need rows [6B], E [M, Dh], coef [B], sparse rows Dh wide with >= 4B slots "
+                          f"for B={B}, Dh={Dh}")
+    dE = dE if dE is not None else torch.empty_like(E)
+    _req(dE, torch.float32, "dE")
+    if dE.shape != E.shape:
+        raise _l.PxrError(f"dvbpr pair head backward: dE must be {tuple(E.shape)}, got {tuple(dE.shape)}")
+    _l.check(_l.load().pxr_dvbpr_pair_bwd_f32(_l.ptr(table), _l.ptr(rows), _l.ptr(E), E.shape[0], _l.ptr(coef), Dh, B, float(grad_scale),
+                                              _l.ptr(grad_scale_dev), _l.ptr(dE), _l.ptr(sp.idx), _l.ptr(sp.rows), _l.ptr(sp.n),
+                                              sp.cap, _l.stream_ptr()), "pxr_dvbpr_pair_bwd_f32")
+    return dE
