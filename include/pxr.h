@@ -63,7 +63,8 @@ int pxr_embed_gather_f32(const float* table, int64_t N, int D, const int64_t* id
 
 /* Sparse embedding backward (replaces autograd's dense embedding_dense_backward of sasrec.py:31/68):
  * (idx[n], rows[n,D]) -> ascending uniq_idx[<=n], uniq_rows[<=n,D] = scale * sum of the rows of each id,
- * *n_uniq_dev = count.  Id 0 (padding_idx) and out-of-range ids are dropped.  Deterministic (stable sort). */
+ * *n_uniq_dev = count.  Id 0 (padding_idx) and out-of-range ids are dropped.  Deterministic (stable sort).
+ * csrc/embed_grad.hip (the segment sums and every table-gradient entry) on the occurrence sort of csrc/occ_sort.cuh. */
 int64_t pxr_embed_grad_ws_bytes(int64_t n_occ);
 int pxr_embed_grad_rows_f32(const int64_t* idx, int64_t n, const float* rows, int D, int64_t n_table, float scale,
                             int64_t* uniq_idx, float* uniq_rows, int32_t* n_uniq_dev, void* ws, int64_t ws_bytes,
@@ -72,7 +73,8 @@ int pxr_embed_grad_rows_f32(const int64_t* idx, int64_t n, const float* rows, in
  * dense all-reduce, run.py:40): idx_all[W,cap] / rows_all[W,cap,D], every list ascending and unique over its whole
  * cap (unused tail slots hold ids >= n_table).  No re-sort: the lowest rank holding an id owns it and adds the other
  * ranks' rows in rank order (same fixed order on every replica).  Output is not compacted: out_idx[e] = id or 0
- * (empty slot, skipped by pxr_adamw_rows_f32 / pxr_adamw_table_f32), out_rows[e,:] = scale * sum, *n_out = W*cap. */
+ * (empty slot, skipped by pxr_adamw_rows_f32 / pxr_adamw_table_f32), out_rows[e,:] = scale * sum, *n_out = W*cap.
+ * csrc/merge_rows.hip. */
 int64_t pxr_merge_rows_ws_bytes(int W, int64_t cap);
 int pxr_merge_sorted_rows_f32(const int64_t* idx_all, const float* rows_all, int W, int64_t cap, int D,
                               int64_t n_table, float scale, int64_t* out_idx, float* out_rows, int32_t* n_out_dev,
@@ -108,7 +110,7 @@ int pxr_shard_bucket_ids_i64(const int64_t* ids, const int32_t* n_dev, int W, in
                              int64_t* req, int32_t* pos, int32_t* counts, void* stream);
 int pxr_scatter_rows_f32(const float* src, const int32_t* pos, int64_t n_src, int D, float* dst, int64_t dst_rows,
                          int row_offset, void* stream);
-/* Row-sharded table (north_star "embedding table optionally row-sharded", BASELINE configs[3]): owner of id =
+/* Row-sharded table (csrc/shard.hip; north_star "embedding table optionally row-sharded", BASELINE configs[3]): owner of id =
  * id % W, its row in the owner's shard = id / W + 1 (local row 0 = all-zero dummy).  local_rows[i] = that row if this
  * rank owns ids[i] (0 < id < n_table), else 0.  pxr_ids_to_compact: out[i] = 1 + position of ids[i] in the ascending
  * unique list (0 for padding): re-indexes a batch onto the [n_uniq+1, D] block of rows fetched from the owners. */

@@ -131,6 +131,16 @@ __device__ __forceinline__ float wave_max(float v) {
   v = fmaxf(v, pxr_dpp<0x143, 0xc>(v, v));
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+// inclusive scan over the 64 lanes of a wave (lane 63 ends up with the wave's total).  Must be called with all 64 lanes active.
+__device__ __forceinline__ int wave_scan_incl(int v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int t = __shfl_up(v, off, 64);
+    if (lane >= off) v += t;
+  }
+  return v;
+}
 
 namespace pxr {
 // fixed-order block sum of one value per thread (256 threads, red[256] in LDS); the total is returned to every thread

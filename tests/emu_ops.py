@@ -135,7 +135,7 @@ def install(monkeypatch):
     monkeypatch.setattr(vit_native.NativeTower, "_require_hip", staticmethod(lambda dev: None))
 
 
-# ---- row-sharded table helpers (csrc/embed_grad.hip: shard_* / scatter_rows kernels), restated in torch for the CPU test of
+# ---- row-sharded table helpers (csrc/shard.hip: shard_* / scatter_rows kernels), restated in torch for the CPU test of
 # the exchange choreography (tests/test_sharded_exchange_gloo.py).  Same contracts as the pixelrec_amd.ops wrappers.
 def shard_bucket_ids(ids, n_dev, world, n_table, pp_cap, pad_id):
     n = int(n_dev[0])

@@ -1,5 +1,5 @@
 """What the tests of the models trained from pixels share (tests/test_mo*_cpu.py, tests/test_gpu_mo*.py): the fixture naming, the
-tiny tower's config, the Trainer's optimizer for a bare model, the constants of csrc/embed_grad.hip, and the three test bodies
+tiny tower's config, the Trainer's optimizer for a bare model, the constants of csrc/occ_sort.cuh and csrc/embed_grad.hip, and the three test bodies
 that differ between the models in a few constants only -- the main.py run, the two-fresh-models loop and the optimizer state's
 round trip.  A plain helper module like tests/segsum_cases.py: no test, no fixture."""
 import os
@@ -56,12 +56,13 @@ def trainer_optimizer(m, optim_args):
 
 
 def sort_constants():
-    """(FP_MAX_N, SEG_SHORT, SEG_CHUNK) of csrc/embed_grad.hip."""
-    src = open(os.path.join(ROOT, "pixelrec_amd", "csrc", "embed_grad.hip")).read()
-    val = lambda k: int(re.search(r"constexpr int %s = (\d+);" % k, src).group(1))
-    mult = int(re.search(r"constexpr int FP_MAX_N = (\d+) \* RS_TILE;", src).group(1))
-    assert "enabled && n <= FP_MAX_N" in src                       # use_fused_sort's cut-over
-    return mult * val("RS_THREADS") * val("RS_ITEMS"), val("SEG_SHORT"), val("SEG_CHUNK")
+    """(FP_MAX_N of csrc/occ_sort.cuh, SEG_SHORT, SEG_CHUNK of csrc/embed_grad.hip)."""
+    read = lambda f: open(os.path.join(ROOT, "pixelrec_amd", "csrc", f)).read()
+    sort, seg = read("occ_sort.cuh"), read("embed_grad.hip")
+    val = lambda k, src: int(re.search(r"constexpr int %s = (\d+);" % k, src).group(1))
+    mult = int(re.search(r"constexpr int FP_MAX_N = (\d+) \* RS_TILE;", sort).group(1))
+    assert "enabled && n <= FP_MAX_N" in sort                      # use_fused_sort's cut-over
+    return mult * val("RS_THREADS", sort) * val("RS_ITEMS", sort), val("SEG_SHORT", seg), val("SEG_CHUNK", seg)
 
 
 def run_main_py(tmp_path, model_yaml, max_len=6, timeout=600):

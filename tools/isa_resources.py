@@ -55,8 +55,43 @@ def kernel_resources(so_path=None):
     return {d: res[n] for n, d in zip(names, dem)}
 
 
+def kernel_code(path):
+    """{demangled kernel name: (code bytes, sha256 of them)} of the gfx950 code objects in `path` (the library or one object file):
+    the bytes of .text that each kernel's function symbol spans.  Equal hashes = the same instructions, byte for byte."""
+    import hashlib
+
+    code = {}
+    for blob in code_objects(path):
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(blob)
+            f.flush()
+            txt = subprocess.run([READELF, "-S", "--symbols", "--wide", f.name], capture_output=True, text=True, check=True).stdout
+        sec = re.search(r"\]\s+\.text\s+PROGBITS\s+([0-9a-f]+)\s+([0-9a-f]+)\s+([0-9a-f]+)", txt)
+        if not sec:
+            continue
+        addr, off = int(sec.group(1), 16), int(sec.group(2), 16)
+        kernels = set(re.findall(r"\s(\S+)\.kd\s*$", txt, re.M))
+        for m in re.finditer(r"^\s*\d+:\s+([0-9a-f]+)\s+(\d+)\s+FUNC\s+\S+\s+\S+\s+\d+\s+(\S+)\s*$", txt, re.M):
+            if m.group(3) in kernels:
+                b = blob[off + int(m.group(1), 16) - addr:][:int(m.group(2))]
+                code[m.group(3)] = (len(b), hashlib.sha256(b).hexdigest()[:16])
+    names = list(code)
+    dem = subprocess.run([CXXFILT], input="\n".join(names), capture_output=True, text=True, check=True).stdout.splitlines()
+    return {d: code[n] for n, d in zip(names, dem)}
+
+
 if __name__ == "__main__":
-    pat = re.compile(sys.argv[1]) if len(sys.argv) > 1 else None
-    for name, r in sorted(kernel_resources().items(), key=lambda kv: (-kv[1]["scratch"], kv[0])):
+    # usage: isa_resources.py [--file PATH]... [regex]: with --file, the named libraries / object files, code hashes included
+    args, files = sys.argv[1:], []
+    while args[:1] == ["--file"]:
+        files.append(args[1])
+        args = args[2:]
+    pat = re.compile(args[0]) if args else None
+    rows = {}
+    for path in files or [None]:
+        res, code = kernel_resources(path), (kernel_code(path) if files else {})
+        rows.update({name: (r, code.get(name)) for name, r in res.items()})
+    for name, (r, c) in sorted(rows.items(), key=lambda kv: (-kv[1][0]["scratch"], kv[0])):
         if pat is None or pat.search(name):
-            print("%5d B scratch  %3d vgpr %3d agpr %3d sgpr %6d lds  %s" % (r["scratch"], r["vgpr"], r["agpr"], r["sgpr"], r["lds"], name[:150]))
+            tail = "  %6d B code %s" % c if c else ""
+            print("%5d B scratch  %3d vgpr %3d agpr %3d sgpr %6d lds%s  %s" % (r["scratch"], r["vgpr"], r["agpr"], r["sgpr"], r["lds"], tail, name[:150]))
