@@ -192,6 +192,18 @@ int pxr_ln_residual_fwd_f32(const float* x, const float* res, const float* gamma
                             int rows, int D, float* y, float* xhat, float* rstd, float p_drop, uint64_t seed,
                             uint32_t stream_id, const int64_t* step_dev, void* y_planes, int64_t y_plane_stride,
                             int64_t y_panel_rows, int planes_fmt, void* stream);
+/* The residual site reading its rows from a per-item cache: x_out[i,t,:] = cache[ids[i]*T + t, :] and y = LN(x_out), rows = n*T.
+ * The reference encodes every image of a step through the whole tower (model/PixelNet/mosasrec.py:69) and every item again per
+ * evaluation (trainer/trainer.py:339-355), although the first `tune_scale` parameters are frozen (model/load.py:97-99): with no
+ * dropout in CLIP and no augmentation in the store, the activation entering the first trainable block is a function of the item
+ * id alone.  cache [n_items, T*D] holds it per item; this entry is the first launch of that block -- its gather and its first
+ * LayerNorm in one pass.  x_out (required) is the block's residual input; y fp32 and / or planes (planes_fmt as above, unit
+ * scale), xhat [n*T,D] / rstd [n*T] optional: pxr_ln_residual_fwd_f32's outputs without dropout and `res`, and the same bits as
+ * pxr_embed_gather_f32 on the [n_items, T*D] view followed by it.  Offsets are 64-bit (the cache may exceed 2^31 elements; n*T
+ * may not); an id outside [0, n_items) sets PXR_STATUS_BAD_INDEX and is clamped. */
+int pxr_ln_gather_fwd_f32(const float* cache, int64_t n_items, const int64_t* ids, int n, int T, const float* gamma,
+                          const float* beta, float eps, int D, float* x_out, float* y, float* xhat, float* rstd,
+                          void* y_planes, int64_t y_plane_stride, int64_t y_panel_rows, int planes_fmt, void* stream);
 /* autograd of either site.  gather_mode=1: dy is w.r.t. the dropped output, dz = grad of (table row + pos).
  * gather_mode=0: dz = grad w.r.t. res, dx (optional) = grad w.r.t. x.  dgamma/dbeta are overwritten; pass both NULL to
  * defer the final reduction (partials stay in ws, reduce them with pxr_reduce_partials_multi_f32).  g_planes (residual sites

@@ -2,6 +2,7 @@
 //
 //   mode GATHER   : z = table[idx[b,t]] + pos_emb[t];  y = dropout(LN(z))          (sasrec.py:68,77-82 / :99-104)
 //   mode RESIDUAL : z = dropout(x) + res;              y = LN(z)                   (layers.py:614-615, :670-671)
+//   ... from CACHED ROWS (the image tower's prefix cache):  x = cache[ids[i]*T + t] -> x_out, then the RESIDUAL form on x
 //
 // LN is nn.LayerNorm: biased variance over the last dim, y = (z-mean)/sqrt(var+eps)*gamma + beta.
 // One 64-lane wave owns one row and keeps it in registers (VEC float4 per lane, D <= VEC*256), two-pass
@@ -54,6 +55,8 @@ struct LnFwdArgs {
   P3Mat yp;                 // optional: y also as planes (the next GEMM's operand format, planes.cuh); p == null: none
   int yp_fmt;               // PXR_PLANES_BF16X3 | PXR_PLANES_H2 (two fp16 planes; a value beyond the fp16 range flags `status`)
   BprHead head;             // RESIDUAL only: the loss head's forward on the rows this launch writes (items == null: none)
+                            // (cached rows: no head, and head.lossrow carries x_out [rows, D] -- a field of its own would move the
+                            //  argument block, and with it the instructions, of every other instantiation)
   int nt;                   // streaming-store policy, set by launch_ln_fwd: bit 0 y, bit 1 the planes of y, bit 2 xhat, bit 3 table-row loads
 };
 
@@ -67,9 +70,21 @@ struct LnFwdArgs {
 // rows of a workgroup are adjacent in every panel, so the workgroup assembles the 256-byte run of each (plane, panel) in LDS
 // (the memory image, padded to 320 bytes per run against bank conflicts) and writes it with 16-byte stores: whole lines.  The
 // arithmetic and the bytes written are those of the unstaged kernel.
+// CACHED ROWS (RPW_ = LN_RPW_CACHED: the residual form, one row per wave, with an indirect source; pxr_ln_gather_fwd_f32).  With the
+// front of the image tower frozen, the activation that enters its first trainable block is a pure function of the item id (no dropout
+// in CLIP, no augmentation in the store); model/prefix_cache.py keeps it as cache [n_items, T*D].  Token row (i, t) of a batch is read
+// from cache[ids[i]*T + t] (a.table / a.idx / a.L = T; 64-bit offsets, the id through checked_id), written back as it was read -- x_out,
+// the residual input of the block's out-projection epilogue -- and normalised by the residual form's row code with dropout and
+// residual off AT RUN TIME: an instantiation of the same statements in the same surroundings, so that the compiler contracts them
+// alike (a copy of the row code in a kernel of its own squared the deviations with FMAs where this one multiplies and adds) and the
+// outputs are those of pxr_embed_gather_f32 followed by pxr_ln_residual_fwd_f32, bit for bit, with one pass over the rows less.
 constexpr int LN_STAGE_RUN = 320;
-template <int VEC, bool GATHER, int RPW = 1, bool STAGE = false>
+constexpr int LN_RPW_CACHED = 0;
+template <int VEC, bool GATHER, int RPW_ = 1, bool STAGE = false>
 __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs a) {
+  constexpr bool ROWS = RPW_ == LN_RPW_CACHED;
+  constexpr int RPW = ROWS ? 1 : RPW_;
+  static_assert(!ROWS || (!GATHER && !STAGE), "the cached-rows source is a form of the plain residual site");
   static_assert(!STAGE || RPW == 1, "staging assumes one row per wave, four adjacent rows per workgroup");
   __shared__ __attribute__((aligned(16))) unsigned char stage_buf[STAGE ? 3 * VEC * 8 * LN_STAGE_RUN : 16];
   if (a.step_dev) a.seed += (uint64_t)a.step_dev[0];
@@ -95,6 +110,10 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs a) {
       // (an id outside the table is an error in the reference -- nn.Embedding raises: flagged, then clamped)
       src = a.table + checked_id(a.idx[(int64_t)b * a.idx_bstride + t], a.n_table, a.status, lane == 0) * D;
       add = a.pos + (int64_t)t * D;
+    } else if constexpr (ROWS) {
+      const int i = row / a.L, t = row - i * a.L;
+      src = a.table + (checked_id(a.idx[i], a.n_table, a.status, lane == 0 && t == 0) * a.L + t) * D;
+      add = a.res ? a.res + (int64_t)row * D : nullptr;
     } else {
       const int rr = live[w] ? row : (STAGE ? a.rows - 1 : row0);
       src = a.x + (int64_t)rr * D;
@@ -105,7 +124,7 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs a) {
       const int c = (k * 64 + lane) * 4;
       if (c < D) {
         float4 t4;
-        if (GATHER && (a.nt & 8)) t4 = pxr_ld_stream(src + c);
+        if ((GATHER || ROWS) && (a.nt & 8)) t4 = pxr_ld_stream(src + c);
         else t4 = *reinterpret_cast<const float4*>(src + c);
         if constexpr (!GATHER) {
           // dropout on the sub-layer output BEFORE the residual add (layers.py:614, :670)
@@ -158,6 +177,7 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs a) {
       if (c < D) {
         const float4 g = *reinterpret_cast<const float4*>(a.gamma + c);
         const float4 be = *reinterpret_cast<const float4*>(a.beta + c);
+        if constexpr (ROWS) *reinterpret_cast<float4*>(a.head.lossrow + (int64_t)row * D + c) = v[w][k];
         float4 xh;
         xh.x = (v[w][k].x - mean) * rstd; xh.y = (v[w][k].y - mean) * rstd;
         xh.z = (v[w][k].z - mean) * rstd; xh.w = (v[w][k].w - mean) * rstd;
@@ -474,6 +494,28 @@ static int launch_ln_fwd(const LnFwdArgs& a_in, hipStream_t st) {
   return pxr_check_launch("pxr_ln_fwd");
 }
 
+// The cached-rows form: stores as in launch_ln_fwd.  A cache row is read once per step and never again within it, so its loads are
+// the streaming (non-temporal) form.  Measured on MI355X at the shipped shape (ViT-B/16: 352 ids x 197 tokens x 768 = 69 344 rows
+// out of a 1.2 GB cache; x_out, xhat, rstd and two fp16 planes written, 745 MB moved; alternating launches, medians of 10, device
+// events -- tools/prefix_cache_bench.py): plain loads 198.2 us, streaming loads 174.1 us (4.3 TB/s).  PXR_PREFIX_NT=0 / 1 selects
+// plain / streaming loads (read at every call, so that one process can measure both); the bits do not depend on it.
+static int launch_ln_cached_fwd(const LnFwdArgs& a_in, hipStream_t st) {
+  LnFwdArgs a = a_in;
+  const char* e = getenv("PXR_PREFIX_NT");
+  const bool stream_loads = e ? atoi(e) != 0 : true;
+  a.nt = (ln_fwd_nt(a) & 7) | (stream_loads ? 8 : 0);
+  const int blocks = (a.rows + 3) / 4;
+  switch (ln_vec_for(a.D)) {
+    case 1: hipLaunchKernelGGL((ln_fwd_kernel<1, false, LN_RPW_CACHED>), dim3(blocks), dim3(256), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((ln_fwd_kernel<2, false, LN_RPW_CACHED>), dim3(blocks), dim3(256), 0, st, a); break;
+    case 4: hipLaunchKernelGGL((ln_fwd_kernel<4, false, LN_RPW_CACHED>), dim3(blocks), dim3(256), 0, st, a); break;
+    case 8: hipLaunchKernelGGL((ln_fwd_kernel<8, false, LN_RPW_CACHED>), dim3(blocks), dim3(256), 0, st, a); break;
+    case 16: hipLaunchKernelGGL((ln_fwd_kernel<16, false, LN_RPW_CACHED>), dim3(blocks), dim3(256), 0, st, a); break;
+    default: pxr_set_error("pxr_ln_gather_fwd_f32: D=%d > 4096 unsupported", a.D); return PXR_ERR_BAD_ARG;
+  }
+  return pxr_check_launch("pxr_ln_gather_fwd_f32");
+}
+
 template <bool GATHER>
 static int launch_ln_bwd(const LnBwdArgs& a, int nblk, hipStream_t st) {
   if (a.gp_exp) {       // stale-scale fp16 planes: residual sites, D <= 1024
@@ -563,6 +605,26 @@ extern "C" int pxr_ln_residual_fwd_f32(const float* x, const float* res, const f
   a.yp = P3Mat{reinterpret_cast<__bf16*>(y_planes), y_plane_stride, y_panel_rows};
   a.yp_fmt = planes_fmt == 1 ? PXR_PLANES_H2 : PXR_PLANES_BF16X3;
   return launch_ln_fwd<false>(a, (hipStream_t)stream);
+}
+// x_out[i,t,:] = cache[ids[i]*T + t, :];  y = LN(x_out)   over rows = n*T: the first LayerNorm of the first trainable tower block
+// reading its input from the per-item prefix cache [n_items, T*D] (CACHED ROWS above; the reference re-encodes every image,
+// mosasrec.py:69).  pxr_ln_residual_fwd_f32's outputs without dropout and `res`, plus the gathered rows themselves.
+extern "C" int pxr_ln_gather_fwd_f32(const float* cache, int64_t n_items, const int64_t* ids, int n, int T, const float* gamma,
+                                     const float* beta, float eps, int D, float* x_out, float* y, float* xhat, float* rstd,
+                                     void* y_planes, int64_t y_plane_stride, int64_t y_panel_rows, int planes_fmt, void* stream) {
+  PXR_REQUIRE(planes_fmt == 0 || planes_fmt == 1, "pxr_ln_gather_fwd_f32: planes_fmt must be 0 (bf16x3) or 1 (h2)");
+  PXR_REQUIRE(n >= 0 && T > 0 && D > 0 && D % 4 == 0 && n_items > 0 && (int64_t)n * T < (1ll << 31), "pxr_ln_gather_fwd_f32: bad shape");
+  if (n == 0) return PXR_OK;
+  PXR_REQUIRE(cache && ids && gamma && beta && x_out && (y_planes || (planes_fmt == 0 && y)), "pxr_ln_gather_fwd_f32: null pointer");
+  PXR_REQUIRE(p3_mat_ok(y_planes, y_plane_stride, y_panel_rows, (int64_t)n * T, D), "pxr_ln_gather_fwd_f32: bad planes");
+  LnFwdArgs a{};
+  a.table = cache; a.n_table = n_items; a.idx = ids; a.L = T; a.head.lossrow = x_out;
+  a.gamma = gamma; a.beta = beta; a.y = y; a.xhat = xhat; a.rstd = rstd;
+  a.rows = n * T; a.D = D; a.eps = eps;
+  a.status = pxr_status_word();      // the ids' bad-index flag, the h2 planes' range flag
+  a.yp = P3Mat{reinterpret_cast<__bf16*>(y_planes), y_plane_stride, y_panel_rows};
+  a.yp_fmt = planes_fmt == 1 ? PXR_PLANES_H2 : PXR_PLANES_BF16X3;
+  return launch_ln_cached_fwd(a, (hipStream_t)stream);
 }
 // The block's LAST LayerNorm with the loss head's forward fused in (BprHead): y = LN(dropout(x) + res) over rows = B*L, and
 // for every row the two target-row scores + the per-position loss term; then the fixed-order loss reduction (bpr_loss.hip).

@@ -55,6 +55,7 @@ _SIGNATURES = {
     "pxr_input_ln_fwd_f32": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _I64, _I,
                                   _P]),
     "pxr_ln_residual_fwd_f32": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _F, _U64, _U32, _P, _P, _I64, _I64, _I, _P]),
+    "pxr_ln_gather_fwd_f32": (_I, [_P, _I64, _P, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _P, _I64, _I64, _I, _P]),
     "pxr_ln_bwd_ws_bytes": (_I64, [_I, _I]),
     "pxr_ln_bwd_partial_rows": (_I, [_I]),
     "pxr_colsum_partial_rows": (_I, [_I]),

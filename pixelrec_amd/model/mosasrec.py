@@ -52,11 +52,14 @@ class MOSASRec(EncoderRows, SeqRecCore):
 
     def forward(self, interaction):
         """interaction = (images fp32 [B, 2(L+1), 3, H, W] ordered pos_0, neg_0, pos_1, neg_1, ... (trainset.py:145-165),
-        masked_index int64 [B, L]) -> 0-dim loss (mosasrec.py:66-93)."""
+        masked_index int64 [B, L]) -> 0-dim loss (mosasrec.py:66-93).  With a prefix cache on the encoder
+        (visual.build_prefix_cache) `images` may be the item ids int64 [B, 2(L+1)] in the same order instead
+        (data.images.interleave_pos_neg): the encoder then starts at its first trainable block."""
         items, masked_index = interaction
         B = masked_index.shape[0]
         self._ensure_packed()
-        item_emb = self.visual_encoder(items.flatten(0, 1)).view(B, -1, 2, self.embedding_size)   # mosasrec.py:69
+        # mosasrec.py:69 (ids: one per image, flattened the same way)
+        item_emb = self.visual_encoder(items.flatten(0, 1)).view(B, -1, 2, self.embedding_size)
         idx = self._row_ids(B, item_emb.device)
         masked_index = masked_index.contiguous()
         table = item_emb.detach().reshape(-1, self.embedding_size).contiguous()

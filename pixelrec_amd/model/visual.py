@@ -181,8 +181,9 @@ class _ItemEncoderBase(nn.Module):
 
         self._native = NativeTower(self)
         self._anchor = None
+        self.prefix_cache = None     # model/prefix_cache.py: the frozen prefix per item (build_prefix_cache); None: images only
         # weights rewritten behind the tower's back (load_state_dict; the trainable blocks never use cached planes)
-        self.register_load_state_dict_post_hook(lambda mod, _keys: mod._native.drop_weight_planes())
+        self.register_load_state_dict_post_hook(lambda mod, _keys: mod._weights_reloaded())
         if dnn_layers:
             self.rec_fc = MLPHead([input_dim] + [int(h) for h in dnn_layers] + [output_dim], act_name)
         else:
@@ -191,6 +192,23 @@ class _ItemEncoderBase(nn.Module):
             if isinstance(mod, nn.Linear):
                 nn.init.xavier_normal_(mod.weight.data)
                 nn.init.constant_(mod.bias.data, 0)
+
+    def build_prefix_cache(self, store, budget_bytes=None, chunk=100) -> bool:
+        """Encode the frozen front of the tower once per item of `store` (data.images.ImageStore) into HBM; afterwards the encoder
+        also takes int64 item ids and starts at its first trainable block.  False (one log line, nothing allocated) when the table
+        does not fit `budget_bytes` (default: half of the free device memory) or nothing in front of block 1 is frozen."""
+        from . import prefix_cache
+
+        self.prefix_cache = None
+        self.prefix_cache = prefix_cache.build(self, store, budget_bytes, chunk)
+        return self.prefix_cache is not None
+
+    def drop_prefix_cache(self):
+        self.prefix_cache = None
+
+    def _weights_reloaded(self):
+        self._native.drop_weight_planes()
+        self.drop_prefix_cache()
 
     def head_layers(self):
         """[(weight name, bias name, activation module | None)] of the head's Linear layers in order (names relative to this module)."""
@@ -210,7 +228,7 @@ class MeanItemEncoder(_ItemEncoderBase):
     native_method = "mean"
 
     def forward(self, x):                       # layers.py:125-128
-        if x.is_cuda:
+        if x.is_cuda or x.dtype == torch.int64:       # (int64: item ids into the prefix cache -- HIP only, run() raises on a CPU tensor)
             from . import vit_native
 
             return vit_native.run(self, x)
@@ -222,7 +240,7 @@ class ClsItemEncoder(_ItemEncoderBase):
     native_method = "cls"
 
     def forward(self, x):                       # layers.py:113-117
-        if x.is_cuda:
+        if x.is_cuda or x.dtype == torch.int64:       # (int64: item ids into the prefix cache -- HIP only, run() raises on a CPU tensor)
             from . import vit_native
 
             return vit_native.run(self, x)
@@ -236,7 +254,7 @@ class PoolItemEncoder(_ItemEncoderBase):
     native_method = "pool"
 
     def forward(self, x):
-        if x.is_cuda:
+        if x.is_cuda or x.dtype == torch.int64:       # (int64: item ids into the prefix cache -- HIP only, run() raises on a CPU tensor)
             from . import vit_native
 
             return vit_native.run(self, x)

@@ -92,6 +92,7 @@ class NativeTower:
             off += pad4(n)
         self.flat, self.gflat, self.views, self.segments = flat, gflat, views, segs
         self._wplanes = {}
+        self.enc.drop_prefix_cache()        # (computed from the buffer this one replaces)
 
     @staticmethod
     def _require_hip(dev):
@@ -194,18 +195,21 @@ class NativeTower:
         else:
             self._wplanes = {}
 
-    def _block_fwd_planes(self, i, x, keep=False, out_planes=False):
+    def _block_fwd_planes(self, i, x, keep=False, out_planes=False, out=None, src=None):
         """One block on the planes GEMMs.  keep=True (a trainable block of a training step) also returns what its backward
-        needs -- activations as planes where the weight-gradient / input-gradient GEMMs read them."""
+        needs -- activations as planes where the weight-gradient / input-gradient GEMMs read them.  out / src: see _block_fwd."""
         vm = "item_encoder.vision_model."
         P = lambda s_, **kw: self.view(f"{vm}encoder.layers.{i}.{s_}", **kw)
         H, heads, d, T, _ = self._shape()
-        n = x.shape[0]
-        M = n * T
         h2 = self._h2_block(i, train=keep)
         pf = "h2" if h2 else True          # format of the activation planes this block's producers write
         Wqkv, Wo, W1, W2 = W = self._block_weight_planes(i, h2)
-        _, xh1, rs1, h1p = ops.ln_residual_fwd(x, None, P("layer_norm1.weight"), P("layer_norm1.bias"), 1e-5, save=keep, planes=pf, want_y=False)
+        if src is not None:
+            x, _, xh1, rs1, h1p = ops.ln_gather_fwd(*src, T, P("layer_norm1.weight"), P("layer_norm1.bias"), 1e-5, save=keep, planes=pf, want_y=False)
+        else:
+            _, xh1, rs1, h1p = ops.ln_residual_fwd(x, None, P("layer_norm1.weight"), P("layer_norm1.bias"), 1e-5, save=keep, planes=pf, want_y=False)
+        n = x.shape[0]
+        M = n * T
         qkv = torch.empty(n, T, 3 * H, dtype=torch.float32, device=x.device)
         ops.gemm_planes(h1p, Wqkv, qkv.view(M, 3 * H), ops.EPI_BIAS, bias=P("self_attn.k_proj.bias", span=3))
         S = ctx = lse = None
@@ -224,7 +228,7 @@ class NativeTower:
         fp = ops.Planes.alloc(M, W1.rows, x.device, fmt=int(h2))
         gq = torch.empty(M, W1.rows, dtype=torch.float32, device=x.device) if keep else None
         ops.gemm_planes(h2p, W1, None, ops.EPI_BIAS_QGELU_GRAD if keep else ops.EPI_BIAS_QGELU, bias=P("mlp.fc1.bias"), aux=gq, Cp=fp)
-        x3 = torch.empty_like(x)
+        x3 = out if out is not None else torch.empty_like(x)
         # out_planes (the LAST block when the head's Linear runs on h2 operands): its output also leaves as h2 planes, unit scale
         x3p = ops.Planes.alloc(M, H, x.device, fmt=1) if (out_planes and h2) else None
         ops.gemm_planes(fp, W2, x3.view(M, H), ops.EPI_BIAS_ADD, bias=P("mlp.fc2.bias"), aux=x2.view(M, H), Cp=x3p)
@@ -314,59 +318,127 @@ class NativeTower:
         ops.gemm_batched(False, False, T, d, T, dP, 0, Tp, qkv, 2 * H, ld, dqkv, 0, ld, bh, heads, sP, sQ, sQ)  # dK = dS^T Q
         return dqkv
 
-    def _block_fwd(self, i, x, keep, out_planes=False):
+    def _block_fwd(self, i, x, keep, out_planes=False, out=None, src=None):
+        """Block i on x [n, T, H] -> (its output, what its backward needs | None).  out: a contiguous [n, T, H] buffer the block's
+        last GEMM writes its output into (the prefix cache's fill).  src = (cache [N, T*H], ids [n]) with x None: the block's input is
+        gathered from the prefix cache by the launch of its first LayerNorm (ops.ln_gather_fwd)."""
         self._last_out_planes = None
         if self._planes_on() and (not keep or os.environ.get("PXR_TOWER_TRAIN_PLANES", "1") != "0"):
-            return self._block_fwd_planes(i, x, keep, out_planes)
+            return self._block_fwd_planes(i, x, keep, out_planes, out, src)
         vm = "item_encoder.vision_model."
         P = lambda s, **kw: self.view(f"{vm}encoder.layers.{i}.{s}", **kw)
         H, heads, d, T, _ = self._shape()
+        if src is not None:
+            x, h1, xh1, rs1 = ops.ln_gather_fwd(*src, T, P("layer_norm1.weight"), P("layer_norm1.bias"), 1e-5, save=keep)
+        else:
+            h1, xh1, rs1 = ops.ln_residual_fwd(x, None, P("layer_norm1.weight"), P("layer_norm1.bias"), 1e-5, save=keep)
         n = x.shape[0]
-        h1, xh1, rs1 = ops.ln_residual_fwd(x, None, P("layer_norm1.weight"), P("layer_norm1.bias"), 1e-5, save=keep)
         qkv = ops.linear_fwd(h1, P("self_attn.k_proj.weight", span=3), P("self_attn.k_proj.bias", span=3))
         ctx, S = self._attn_fwd(qkv, n, T, heads, d, keep)
         x2 = ops.linear_epi(ctx, P("self_attn.out_proj.weight"), P("self_attn.out_proj.bias"), ops.EPI_BIAS_ADD, aux=x)
         h2, xh2, rs2 = ops.ln_residual_fwd(x2, None, P("layer_norm2.weight"), P("layer_norm2.bias"), 1e-5, save=keep)
         f, gq = ops.linear_epi(h2, P("mlp.fc1.weight"), P("mlp.fc1.bias"), ops.EPI_BIAS_QGELU_GRAD)
-        x3 = ops.linear_epi(f, P("mlp.fc2.weight"), P("mlp.fc2.bias"), ops.EPI_BIAS_ADD, aux=x2)
+        into = {"out": out} if out is not None else {}
+        x3 = ops.linear_epi(f, P("mlp.fc2.weight"), P("mlp.fc2.bias"), ops.EPI_BIAS_ADD, aux=x2, **into)
         saved = dict(xh1=xh1, rs1=rs1, h1=h1, qkv=qkv, P=S, ctx=ctx, xh2=xh2, rs2=rs2, h2=h2, gq=gq, f=f) if keep else None
         return x3, saved
 
-    def forward(self, images, need_grad: bool):
-        """images fp32 [n, 3, Hi, Wi] -> (item vectors [n, D], saved state | None)."""
-        self.ensure_packed()
-        e = self.enc
+    def _embed(self, images, keep0):
+        """images fp32 [n, 3, Hi, Wi] -> (tokens after pre_layrnorm [n, T, H], patches, xhat, rstd): what stands in front of block 0."""
         vm = "item_encoder.vision_model."
         H, heads, d, T, p = self._shape()
         n, c, Hi, Wi = images.shape
         if (Hi // p) * (Wi // p) != T - 1:
             raise ValueError(f"image size {Hi}x{Wi} does not give the encoder's {T - 1} patches of {p}x{p}")
-        first = self.first_trainable_block() if need_grad else 10 ** 9
         # patch projection: conv(k = s = p, no bias) == im2col (a layout change) + GEMM on the fp32 MFMA
         patches = images.view(n, c, Hi // p, p, Wi // p, p).permute(0, 2, 4, 1, 3, 5).reshape(-1, c * p * p).contiguous()
         wp = self.view(vm + "embeddings.patch_embedding.weight").view(H, -1)
         pe = ops.linear_fwd(patches, wp, None).view(n, T - 1, H)
         x0 = ops.vit_embed(pe, self.view(vm + "embeddings.class_embedding"), self.view(vm + "embeddings.position_embedding.weight"))
-        keep0 = first < 0
         x, xh0, rs0 = ops.ln_residual_fwd(x0, None, self.view(vm + "pre_layrnorm.weight"), self.view(vm + "pre_layrnorm.bias"),
                                           1e-5, save=keep0)
+        return x, patches, xh0, rs0
+
+    def _head_h2(self):
+        # opt-in (PXR_TOWER_H2_HEAD=1): the head's Linear over every token (method 'mean') on fp16 two-plane operands too -- the last
+        # block writes its output as planes, the weight is split with a device-chosen scale.  Measured on MI355X (ViT-B/16, 69 344
+        # tokens): 65.5 -> 66.2 ms per step -- the statistics pass over the head's gradient costs more than three products save on a
+        # 768 x 512 weight; off by default.
+        e = self.enc
+        head = e.head_layers()
+        return (e.native_method == "mean" and isinstance(head[-1][2], torch.nn.ReLU) and len(head) == 1
+                and os.environ.get("PXR_TOWER_H2_HEAD", "0") == "1" and self.view(head[0][0]).shape[0] % 32 == 0)
+
+    # ---- the frozen prefix.  With the embeddings and blocks 0 .. k-1 frozen (k = first_trainable_block() >= 1; k = 10 of 12 at the
+    # shipped tune_scale) the activation that enters block k is a pure function of the image: CLIP has no dropout and the store no
+    # augmentation.  The forward is therefore cut there -- forward_prefix is forward-only whatever the step does, forward_from is the
+    # rest -- and model/prefix_cache.py keeps forward_prefix's output per item, so a step or an evaluation over item ids starts at
+    # block k (forward_ids).
+    def forward_prefix(self, images, out=None):
+        """images fp32 [n, 3, Hi, Wi] -> x_k [n, T, H], the input of block k = first_trainable_block() (k >= 1).  out: a contiguous
+        [n, T, H] buffer that block k-1 writes x_k into."""
+        self.ensure_packed()
+        k = self.first_trainable_block()
+        if k < 1:
+            raise PxrError("forward_prefix: the embeddings or block 0 train -- the tower has no frozen prefix")
+        x = self._embed(images, False)[0]
+        for i in range(k):
+            x, _ = self._block_fwd(i, x, keep=False, out=out if i == k - 1 else None)
+        return x
+
+    def forward_from(self, x_k, need_grad: bool):
+        """x_k [n, T, H] (forward_prefix's output) -> (item vectors [n, D], saved state | None): blocks k .. n_layers-1 and the head."""
+        self.ensure_packed()
+        return self._from_block(self.first_trainable_block(), x_k, need_grad)
+
+    def forward_ids(self, ids, need_grad: bool):
+        """ids int64 [n] into the encoder's prefix cache -> (item vectors [n, D], saved state | None).  The gather rides in the first
+        LayerNorm of block k (pxr_ln_gather_fwd_f32); PXR_PREFIX_FUSED_LN=0, or no block after the prefix (only the head trains):
+        pxr_embed_gather_f32 on the [N, T*H] view, then forward_from -- the same bits."""
+        self.ensure_packed()
+        cache = self.enc.prefix_cache
+        if cache is None:
+            raise PxrError("the encoder has no prefix cache: item ids cannot be encoded (build_prefix_cache first, or pass images)")
+        k = cache.check(self)                # a stale cache raises here, in front of every launch
+        H, heads, d, T, _ = self._shape()
+        n_layers = len(self.enc.item_encoder.vision_model.encoder.layers)
+        if k == n_layers or os.environ.get("PXR_PREFIX_FUSED_LN", "1") == "0":
+            return self._from_block(k, ops.embed_gather(cache.table, ids).view(-1, T, H), need_grad)
+        return self._from_block(k, None, need_grad, src=(cache.table, ids))
+
+    def forward(self, images, need_grad: bool):
+        """images fp32 [n, 3, Hi, Wi] -> (item vectors [n, D], saved state | None)."""
+        self.ensure_packed()
+        k = self.first_trainable_block()
+        n_layers = len(self.enc.item_encoder.vision_model.encoder.layers)
+        if k >= 1 and not (k == n_layers and self._head_h2()):    # (the opt-in h2 head takes the last block's output as planes)
+            return self.forward_from(self.forward_prefix(images), need_grad)
+        x, patches, xh0, rs0 = self._embed(images, need_grad and k < 0)
+        return self._from_block(0, x, need_grad, emb=(patches, xh0, rs0))
+
+    def _from_block(self, start, x, need_grad: bool, emb=(None, None, None), src=None):
+        """Blocks start .. n_layers-1 and the head on x [n, T, H] (src: _block_fwd's, for block `start`); emb: _embed's saved state
+        when the embeddings train (start == 0)."""
+        e = self.enc
+        vm = "item_encoder.vision_model."
+        H, heads, d, T, p = self._shape()
+        first = self.first_trainable_block() if need_grad else 10 ** 9
+        keep0 = need_grad and first < 0
+        patches, xh0, rs0 = emb
         n_layers = len(e.item_encoder.vision_model.encoder.layers)
-        blocks = []
+        blocks = [None] * start
         head = e.head_layers()
         for _, _, a_ in head:
             if a_ is not None and not isinstance(a_, torch.nn.ReLU):
                 raise NotImplementedError("native image encoder: rec_fc activation must be relu or none (overall/ViT.yaml: relu)")
         act_relu = isinstance(head[-1][2], torch.nn.ReLU)
-        # opt-in (PXR_TOWER_H2_HEAD=1): the head's Linear over every token (method 'mean') on fp16 two-plane operands too -- the last
-        # block writes its output as planes, the weight is split with a device-chosen scale.  Measured on MI355X (ViT-B/16, 69 344
-        # tokens): 65.5 -> 66.2 ms per step -- the statistics pass over the head's gradient costs more than three products save on a
-        # 768 x 512 weight; off by default.
-        head_h2 = (e.native_method == "mean" and act_relu and len(head) == 1 and os.environ.get("PXR_TOWER_H2_HEAD", "0") == "1"
-                   and self.view(head[0][0]).shape[0] % 32 == 0)
-        for i in range(n_layers):
-            x, s = self._block_fwd(i, x, keep=need_grad and i >= first, out_planes=head_h2 and i == n_layers - 1)
+        head_h2 = self._head_h2()
+        for i in range(start, n_layers):
+            x, s = self._block_fwd(i, x, keep=need_grad and i >= first, out_planes=head_h2 and i == n_layers - 1,
+                                   src=src if i == start else None)
             blocks.append(s)
-        xp_last = getattr(self, "_last_out_planes", None) if n_layers else None
+        n = x.shape[0]
+        xp_last = getattr(self, "_last_out_planes", None) if n_layers > start else None
         # head: rec_fc (Linear + activation) on every token then the token mean, or on the class token only
         W, b = self.view(head[-1][0]), self.view(head[-1][1])
         head_in = x if e.native_method == "mean" else x[:, 0, :].contiguous()
@@ -515,8 +587,9 @@ class NativeTower:
 
 class _TowerFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, images, anchor, tower):
-        out, saved = tower.forward(images, need_grad=True)
+    def forward(ctx, x, anchor, tower):
+        fwd = tower.forward_ids if x.dtype == torch.int64 else tower.forward
+        out, saved = fwd(x, need_grad=True)
         ctx.tower, ctx.saved = tower, saved
         return out
 
@@ -527,14 +600,21 @@ class _TowerFn(torch.autograd.Function):
         return None, None, None
 
 
-def run(enc, images):
-    """MeanItemEncoder / ClsItemEncoder forward on a HIP tensor."""
+def run(enc, x):
+    """MeanItemEncoder / ClsItemEncoder / PoolItemEncoder forward on a HIP tensor: x fp32 images [n, 3, Hi, Wi], or int64 item ids
+    of any shape into the encoder's prefix cache (-> [x.numel(), D])."""
     tower = enc._native
+    ids = x.dtype == torch.int64
+    if ids:
+        if not x.is_cuda:
+            raise PxrError("item ids into the prefix cache must be a HIP tensor (the cache lives on the device; no CPU fallback)")
+        x = x.reshape(-1)
     tower.ensure_packed()
+    fwd = tower.forward_ids if ids else tower.forward      # (forward_ids refuses a missing or stale cache before it launches anything)
     trainable = any(p.requires_grad for p in enc.parameters())
     if torch.is_grad_enabled() and trainable:
-        if enc._anchor is None or enc._anchor.device != images.device:
-            enc._anchor = torch.zeros((), dtype=torch.float32, device=images.device, requires_grad=True)
-        return _TowerFn.apply(images.contiguous(), enc._anchor, tower)
-    out, _ = tower.forward(images.contiguous(), need_grad=False)
+        if enc._anchor is None or enc._anchor.device != x.device:
+            enc._anchor = torch.zeros((), dtype=torch.float32, device=x.device, requires_grad=True)
+        return _TowerFn.apply(x.contiguous(), enc._anchor, tower)
+    out, _ = fwd(x.contiguous(), need_grad=False)
     return out

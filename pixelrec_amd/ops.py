@@ -355,14 +355,18 @@ def linear_fwd(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor | None, gelu: b
 
 
 def linear_epi(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor, epi: int, aux: torch.Tensor | None = None,
-               tag: str = "gemm_kernel<KC,KC,*> (ViT linear)"):
+               tag: str = "gemm_kernel<KC,KC,*> (ViT linear)", out: torch.Tensor | None = None):
     """y = epilogue(x W^T + b) for the ViT-block epilogues (gemm_f32.hip): EPI_BIAS_ADD (aux = residual stream, read),
-    EPI_BIAS_QGELU_GRAD (aux = quick_gelu' saved for the backward, written; returned second), EPI_BIAS_RELU."""
+    EPI_BIAS_QGELU_GRAD (aux = quick_gelu' saved for the backward, written; returned second), EPI_BIAS_RELU.
+    out: a contiguous fp32 buffer of y's shape to write into (default: a new tensor)."""
     L = _l.load()
     _req(x, torch.float32, "x"); _req(W, torch.float32, "W")
     N, K = W.shape
     M = x.numel() // K
-    y = torch.empty(*x.shape[:-1], N, dtype=torch.float32, device=x.device)
+    if out is not None:
+        _req(out, torch.float32, "out")
+        assert out.shape == (*x.shape[:-1], N)
+    y = out if out is not None else torch.empty(*x.shape[:-1], N, dtype=torch.float32, device=x.device)
     out_aux = None
     if epi == EPI_BIAS_QGELU_GRAD:
         aux = out_aux = torch.empty_like(y)
@@ -1052,6 +1056,29 @@ def ln_residual_fwd(x, res, gamma, beta, eps, p_drop=0.0, seed=0, stream_id=0, s
                                         _l.ptr(rstd), p_drop, seed, stream_id, _l.ptr(step_dev), *_pl(yp), int(h2), _l.stream_ptr()),
              "pxr_ln_residual_fwd_f32")
     return (y, xhat, rstd, yp) if planes else (y, xhat, rstd)
+
+
+def ln_gather_fwd(cache, ids, T, gamma, beta, eps, save=True, planes: bool = False, want_y: bool = True):
+    """x[i, t, :] = cache[ids[i], t, :] and y = LN(x) in one launch (pxr_ln_gather_fwd_f32): cache fp32 [N, T*D], ids int64 [n].
+    Returns (x [n, T, D], y, xhat, rstd) (+ y as Planes with planes=True / "h2"; want_y=False then skips the fp32 copy of y) --
+    embed_gather(cache, ids) followed by ln_residual_fwd, bit for bit.  An id outside [0, N) is flagged and clamped."""
+    Lb = _l.load()
+    _req(cache, torch.float32, "cache"); _req(ids, torch.int64, "ids")
+    D = gamma.numel()
+    N, n = cache.shape[0], ids.numel()
+    if cache.dim() != 2 or cache.shape[1] != T * D or ids.dim() != 1:
+        raise _l.PxrError(f"ln_gather_fwd: cache must be [N, T*D = {T * D}] and ids [n], got {tuple(cache.shape)} / {tuple(ids.shape)}")
+    assert want_y or planes
+    device_status(cache.device)
+    x = torch.empty(n, T, D, dtype=torch.float32, device=cache.device)
+    y = torch.empty_like(x) if want_y else None
+    xhat = torch.empty_like(x) if save else None
+    rstd = torch.empty(n * T, dtype=torch.float32, device=cache.device) if save else None
+    h2 = planes == "h2"
+    yp = Planes.alloc(n * T, D, cache.device, fmt=int(h2)) if planes else None
+    _l.check(Lb.pxr_ln_gather_fwd_f32(_l.ptr(cache), N, _l.ptr(ids), n, T, _l.ptr(gamma), _l.ptr(beta), eps, D, _l.ptr(x), _l.ptr(y),
+                                      _l.ptr(xhat), _l.ptr(rstd), *_pl(yp), int(h2), _l.stream_ptr()), "pxr_ln_gather_fwd_f32")
+    return (x, y, xhat, rstd, yp) if planes else (x, y, xhat, rstd)
 
 
 def ln_residual_bpr_fwd(x, res, gamma, beta, eps, table, items, masked_index, p_drop=0.0, seed=0, stream_id=0, save=True,

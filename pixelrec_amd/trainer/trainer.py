@@ -227,6 +227,7 @@ class Trainer:
             if prev is not None:
                 yield prev, None
 
+        ids_step = self._prefix_cache(train_data) is not None      # the encoder takes item ids: the frozen prefix comes from its cache
         for data, next_items in with_next(_Prefetcher(train_data, self.device)):
             self._steps_done = getattr(self, "_steps_done", 0) + 1
             self._h2_stale_resume()
@@ -255,7 +256,8 @@ class Trainer:
             elif self.use_modality:   # assemble the image batch on the device from the HBM-resident store
                 from ..data.images import interleave_pos_neg
 
-                data = (self._image_store(train_data).batch(interleave_pos_neg(data[0])), data[1])
+                ids = interleave_pos_neg(data[0])
+                data = (ids if ids_step else self._image_store(train_data).batch(ids), data[1])
             elif next_items is not None:
                 self.model.module.set_next_batch(next_items)   # its table rows are caught up beside this step's GEMMs
             losses = self.model(data)
@@ -405,6 +407,7 @@ class Trainer:
     def fit(self, train_data, valid_data=None, verbose=True, saved=True, show_progress=False, callback_fn=None):
         if saved and self.start_epoch >= self.epochs:
             self._save_checkpoint(-1, verbose=verbose)
+        self._prefix_cache(train_data)           # `prefix_cache: True`: filled once, in front of the first epoch
         for epoch_idx in range(self.start_epoch, self.epochs):
             if self.config["need_training"] is None or self.config["need_training"]:
                 train_data.sampler.set_epoch(epoch_idx)
@@ -451,15 +454,40 @@ class Trainer:
             self._images = ImageStore.from_config(self.config, dl, self.device)
         return self._images
 
+    def _prefix_cache(self, loader=None):
+        """`prefix_cache: True` (a missing key means off): the visual encoder's cache of its frozen prefix per item
+        (model/prefix_cache.py) when it is valid for this Trainer's image store, else None -- the run then reads images exactly as
+        without the key.  Built at the first call, within `prefix_cache_gb` GiB when given (default: half of the free device
+        memory); a refusal is logged once.  Only models whose training step takes one id per image use it there (MOSASRec); the
+        `modal_inputs` models train on images, and every ViT model's evaluation encodes its catalogue from the cache."""
+        cfg = self.config
+        if not (getattr(self, "use_modality", False) and "prefix_cache" in cfg and cfg["prefix_cache"]):
+            return None
+        enc = getattr(self.model.module, "visual_encoder", None)
+        if not hasattr(enc, "build_prefix_cache"):       # (DVBPR's CNN has no frozen prefix)
+            return None
+        store = self._image_store(loader)
+        if not getattr(self, "_prefix_cache_asked", False):
+            self._prefix_cache_asked = True
+            gb = cfg["prefix_cache_gb"] if "prefix_cache_gb" in cfg else None
+            if enc.build_prefix_cache(store, None if gb is None else int(float(gb) * 2 ** 30)):
+                self.logger.info("prefix cache: %d items x %d B in HBM, the tower starts at block %d", store.n,
+                                 enc.prefix_cache.table.shape[1] * 4, enc.prefix_cache.k)
+            else:
+                self.logger.info("prefix cache: refused -- training and evaluation read images")
+        cache = enc.prefix_cache
+        return cache if cache is not None and cache.stale(enc._native, store) is None else None
+
     @torch.no_grad()
     def compute_item_feature(self, config, data, loader=None):
         """trainer.py:339-358: IDNet = the table itself; PixelNet = encode every item image in batches of 100."""
         if self.use_modality:
             store = self._image_store(loader)
             feats = []
+            cached = self._prefix_cache(loader) is not None       # compute_item hands its argument to the encoder: ids serve
             for s in range(0, store.n, 100):
                 ids = torch.arange(s, min(store.n, s + 100), device=self.device)
-                feats.append(self.model.module.compute_item(store.batch(ids)))   # id 0 -> zero image (batchset.py:58-60)
+                feats.append(self.model.module.compute_item(ids if cached else store.batch(ids)))   # id 0 -> zero image (batchset.py:58-60)
             extra = getattr(self.model.module, "extra_item_images", None)
             if extra is not None:
                 # a model whose catalogue holds images no store has (MOBERT4Rec: the ones image of the mask token, batchset.py:53)
